@@ -15,6 +15,11 @@ global batch of 512*N prefixes against its own candidates (open_knowledge_graph_
 two small RCCL all-reduces per step).  Per-GPU work is constant in N ("weak" scaling); `value` counts each
 global batch once.  The line also carries an `olp` object: the north-star's second shape (S-OLP, |E| = 2.5 M, d = 256,
 B = 4096, Zipf(1.1) prefix entities) at the SAME global size for every N (strong scaling), a handful of steps.
+
+A plain run sets up, warms up, times EXACTLY --steps steps in one window and prints the line; `ms_per_step` / `value` are
+that window.  --full adds everything else the line carries (repeated timed windows whose median becomes `ms_per_step`, the
+`roofline` kernel-timing pass, `eval`, `dropin`, `olp`, `configs`, `cpu_baseline`); without it those fields are null.
+--dump-outputs DIR writes what the timed step computed in its last step (after the first timed window) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -31,6 +36,7 @@ import torch  # noqa: E402
 
 FP32_MFMA_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32, dense
 N_BATCHES = 8                   # distinct pre-generated batches cycled through
+DUMP_BYTES = 64 << 20           # --dump-outputs writes at most this much
 
 
 def to_dev_batch(hb, w, dev):
@@ -38,6 +44,49 @@ def to_dev_batch(hb, w, dev):
     t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
     return PrefixBatch(po_rel=t(hb["po_rel"]), po_obj=t(hb["po_obj"]), sp_subj=t(hb["sp_subj"]), sp_rel=t(hb["sp_rel"]),
                        pos_row=t(hb["pos_row"]), pos_col=t(hb["pos_col"]), cand_first=2, n_cand=w.N)
+
+
+def dump_rows(n_rows, d, n_rows_total, budget=DUMP_BYTES):
+    """Row ids of a table that --dump-outputs writes: None (every row) when all tables fit the budget, else a fixed, seeded,
+    sorted sample of the same fraction of every table's rows.  A row costs two float32 rows (table + Adagrad sum) and its id."""
+    frac = (budget - 4096) / ((8.0 * d + 8.0) * n_rows_total)
+    if frac >= 1.0:
+        return None
+    return np.sort(np.random.default_rng(20240601).choice(n_rows, max(1, int(frac * n_rows)), replace=False))
+
+
+def dump_outputs(out_dir, step, sharded, dist, rank):
+    """What a caller of the timed step holds after its last step: the step's summed loss (float64) and the updated tables with
+    their Adagrad accumulators (float32).  The row-sharded entity table of a multi-rank run is reassembled on rank 0 (every
+    rank takes part in the collectives; only rank 0 writes)."""
+    dev = step.R.device
+    loss = step.reduce_loss() if sharded else step.loss_out
+    n_ent, (n_rel, d) = (step.n_ent if sharded else step.E.shape[0]), step.R.shape
+    ent_rows, rel_rows = dump_rows(n_ent, d, n_ent + n_rel), dump_rows(n_rel, d, n_ent + n_rel)
+
+    def rows(t, ids):
+        return t if ids is None else t[torch.from_numpy(ids).to(dev)]
+
+    def entity_rows(t):
+        if not sharded:
+            return rows(t, ent_rows)
+        ids = np.arange(n_ent) if ent_rows is None else ent_rows
+        out = torch.zeros((ids.size, d), dtype=t.dtype, device=dev)
+        mine = np.nonzero((ids >= step.ent_lo) & (ids < step.ent_hi))[0]
+        out[torch.from_numpy(mine).to(dev)] = t[torch.from_numpy(ids[mine] - step.ent_lo).to(dev)]
+        dist.all_reduce(out)                # the other ranks add zeros: every row arrives exactly as its owner holds it
+        return out
+
+    arrays = {"loss_sum": loss, "entity_embeddings": entity_rows(step.E), "entity_adagrad_sum": entity_rows(step.sumE),
+              "relation_embeddings": rows(step.R, rel_rows), "relation_adagrad_sum": rows(step.sumR, rel_rows)}
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy())
+    for name, ids in (("entity_rows", ent_rows), ("relation_rows", rel_rows)):
+        if ids is not None:                 # row ids of a sampled table, as float64 (exact below 2**53)
+            np.save(os.path.join(out_dir, name + ".npy"), ids.astype(np.float64))
 
 
 def host_cores():
@@ -209,6 +258,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="S-FB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the repeated windows, kernel timings, evaluation, drop-in, S-OLP, other configurations, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed step's outputs after its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     from open_knowledge_graph_embeddings_amd import synthetic
@@ -308,68 +360,73 @@ def main():
             el = float(tmax[0].item())        # every rank processed the same global batches: count them once
         return el
 
-    # A short window (the driver's --steps 20 is 2.8 ms of device time) is at the mercy of one clock ramp or one host
-    # hiccup, so the measurement is repeated: up to 9 windows of `steps` steps each (fewer when one window is long: about
-    # 20 s in total; the count follows from the rank-maximum time, so every rank runs the same number), and the line reports
-    # the MEDIAN window as ms_per_step / value, with the fastest and slowest beside it.
     windows = [timed_window()]
-    n_windows = max(1, min(9, int(20.0 / max(windows[0], 1e-6))))
-    if n_windows > 1 and n_windows % 2 == 0:
-        n_windows -= 1
-    while len(windows) < n_windows:
-        windows.append(timed_window())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step, sharded, dist, rank)
+    if args.full:
+        # A short window (--steps 20 is 2.8 ms of device time at S-FB) is at the mercy of one clock ramp or one host hiccup,
+        # so --full repeats the measurement: up to 9 windows of `steps` steps each (fewer when one window is long: about
+        # 20 s in total; the count follows from the rank-maximum time, so every rank runs the same number), and the line
+        # reports the MEDIAN window as ms_per_step / value, with the fastest and slowest beside it.
+        n_windows = max(1, min(9, int(20.0 / max(windows[0], 1e-6))))
+        if n_windows > 1 and n_windows % 2 == 0:
+            n_windows -= 1
+        while len(windows) < n_windows:
+            windows.append(timed_window())
     elapsed = float(np.median(windows))
     triples = sum(n_pos[i % N_BATCHES] for i in range(args.steps))
     loss_last = float((step.reduce_loss() if sharded else step.loss_out).item())
 
     # ---- roofline of the dominant kernel: HIP events on the launch stream, separate pass ------------------
     roof = None
-    # (every rank runs these steps -- the sharded step contains collectives -- but only rank 0 times its kernels)
-    eng = step.engine
-    # (outside the timed windows: 200 launches for a stable per-kernel average, whatever --steps says -- with the driver's
-    #  --steps 20 the whole run is a few tens of milliseconds and the first launches still see the clocks ramping)
-    ksteps = 200
-    for i in range(50):
-        run(i)
-    barrier()
-    if rank == 0:
-        eng.timing(True)
-    for i in range(ksteps):
-        run(i)
-    barrier()
-    if rank == 0:
-        per_kernel = eng.timing_collect()
-        eng.timing(False)
-        tot_ms, cnt = per_kernel["fused_tile_train"]
-        avg_s = tot_ms / cnt * 1e-3
-        n_local = step.n_cand_local if sharded else w.N
-        flops = 4.0 * w_run.B * n_local * w.d         # X = Q.C^T (2BNd) + dC = G^T.Q (2BNd) per launch, this rank
-        achieved = flops / avg_s / 1e12
-        # HBM bytes per launch of that kernel: from the committed PMC passes of this same command (tools/collect_profiles.sh:
-        # separate FETCH_SIZE / WRITE_SIZE runs, FETCH doubled as the gfx950 guide says); counters cannot be read inside
-        # a timed run, so the value is tagged with the file and the commit it was collected at
-        traffic, traffic_src = None, None
-        kname = "fused_tile64_kernel" if w.d <= 256 else "fused_tile32_kernel"
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath) and not sharded and args.workload == "S-FB":
-            tj = json.load(open(tpath))
-            hit = [v for k, v in tj.items() if k.startswith(kname)]
-            if hit:
-                traffic = hit[0]["hbm_bytes_per_launch"]
-                traffic_src = {"file": "profiles/pmc_traffic.json", "collected_at_commit": tj.get("_commit"),
-                               "command": tj.get("_command"), "how": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes"}
-        step_s = elapsed / args.steps
-        roof = {"bound": "mfma", "kernel": kname + "<train>", "achieved": achieved,
-                "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK_TFLOPS,
-                "traffic": traffic, "traffic_source": traffic_src, "avg_launch_us": avg_s * 1e6,
-                "kernels_us": {k: v[0] / v[1] * 1e3 for k, v in per_kernel.items()},
-                "step_flops_6BNd": 6.0 * w_run.B * n_local * w.d, "step_bytes_20Nd": 20.0 * n_local * w.d,
-                # the whole step against the same peak: 6 B N d flops (this rank's candidates) / measured step time
-                "step_frac": 6.0 * w_run.B * n_local * w.d / step_s / 1e12 / FP32_MFMA_PEAK_TFLOPS}
+    if args.full:
+        # (every rank runs these steps -- the sharded step contains collectives -- but only rank 0 times its kernels)
+        eng = step.engine
+        # (outside the timed windows: 200 launches for a stable per-kernel average, whatever --steps says -- with
+        #  --steps 20 the whole run is a few tens of milliseconds and the first launches still see the clocks ramping)
+        ksteps = 200
+        for i in range(50):
+            run(i)
+        barrier()
+        if rank == 0:
+            eng.timing(True)
+        for i in range(ksteps):
+            run(i)
+        barrier()
+        if rank == 0:
+            per_kernel = eng.timing_collect()
+            eng.timing(False)
+            tot_ms, cnt = per_kernel["fused_tile_train"]
+            avg_s = tot_ms / cnt * 1e-3
+            n_local = step.n_cand_local if sharded else w.N
+            flops = 4.0 * w_run.B * n_local * w.d         # X = Q.C^T (2BNd) + dC = G^T.Q (2BNd) per launch, this rank
+            achieved = flops / avg_s / 1e12
+            # HBM bytes per launch of that kernel: from the committed PMC passes of this same command (tools/collect_profiles.sh:
+            # separate FETCH_SIZE / WRITE_SIZE runs, FETCH doubled: on gfx950 it reports half the bytes of a wide streaming
+            # read); counters cannot be read inside
+            # a timed run, so the value is tagged with the file and the commit it was collected at
+            traffic, traffic_src = None, None
+            kname = "fused_tile64_kernel" if w.d <= 256 else "fused_tile32_kernel"
+            tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tpath) and not sharded and args.workload == "S-FB":
+                tj = json.load(open(tpath))
+                hit = [v for k, v in tj.items() if k.startswith(kname)]
+                if hit:
+                    traffic = hit[0]["hbm_bytes_per_launch"]
+                    traffic_src = {"file": "profiles/pmc_traffic.json", "collected_at_commit": tj.get("_commit"),
+                                   "command": tj.get("_command"), "how": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes"}
+            step_s = elapsed / args.steps
+            roof = {"bound": "mfma", "kernel": kname + "<train>", "achieved": achieved,
+                    "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK_TFLOPS,
+                    "traffic": traffic, "traffic_source": traffic_src, "avg_launch_us": avg_s * 1e6,
+                    "kernels_us": {k: v[0] / v[1] * 1e3 for k, v in per_kernel.items()},
+                    "step_flops_6BNd": 6.0 * w_run.B * n_local * w.d, "step_bytes_20Nd": 20.0 * n_local * w.d,
+                    # the whole step against the same peak: 6 B N d flops (this rank's candidates) / measured step time
+                    "step_frac": 6.0 * w_run.B * n_local * w.d / step_s / 1e12 / FP32_MFMA_PEAK_TFLOPS}
 
     # ---- evaluation leg (single GPU): score every candidate + filtered ranks (dataset.py:423-446) --------------
     ev = None
-    if rank == 0 and not sharded:
+    if args.full and rank == 0 and not sharded:
         hb = synthetic.make_eval_batch(w, seed=777)
         eb = to_dev_batch(hb, w, dev)
         t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
@@ -412,13 +469,13 @@ def main():
     #      zero_grad, AddLossModule forward, (loss.sum() / normalizer).backward(), optimizer.step()) on this package's Models /
     #      AddLossModule / OkgeAdagrad -- what a user of INTEGRATION.md section 1 gets without touching the training loop
     dropin = None
-    if rank == 0 and not sharded and args.workload == "S-FB" and os.environ.get("OKGE_BENCH_DROPIN", "1") == "1":
+    if args.full and rank == 0 and not sharded and args.workload == "S-FB" and os.environ.get("OKGE_BENCH_DROPIN", "1") == "1":
         dropin = run_dropin(w, host_batches, dev)
 
     # ---- the north-star's second shape: S-OLP (|E| = 2.5 M, |R| = 100 k, d = 256, B = 4096, Zipf(1.1) prefix entities),
     #      the SAME global problem at every N (strong scaling), entity table row-sharded over the ranks; a handful of steps
     olp = None
-    if args.workload == "S-FB" and os.environ.get("OKGE_BENCH_OLP", "1") == "1":
+    if args.full and args.workload == "S-FB" and os.environ.get("OKGE_BENCH_OLP", "1") == "1":
         del step, batches, Et, Rt
         torch.cuda.empty_cache()
         olp = run_olp(world, rank, dev, dist, barrier)
@@ -427,7 +484,7 @@ def main():
     #      configs[2] S-DM, configs[4] S-OLP-tok and configs[1] with the KL loss, through tools/bench_configs.py's code path,
     #      50 warm-up + 200 timed steps each, per-kernel HIP-event averages beside the step time
     configs = None
-    if rank == 0 and world == 1 and not sharded and args.workload == "S-FB" and os.environ.get("OKGE_BENCH_CONFIGS", "1") == "1":
+    if args.full and rank == 0 and world == 1 and not sharded and args.workload == "S-FB" and os.environ.get("OKGE_BENCH_CONFIGS", "1") == "1":
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_configs
         configs = {name: bench_configs.measure_config(name, dev, peak_tflops=FP32_MFMA_PEAK_TFLOPS) for name in ("S-DM", "S-OLP-tok", "S-FB-kl")}
@@ -437,7 +494,7 @@ def main():
             dist.destroy_process_group()
         return
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and not sharded:
+    if args.full and not args.no_cpu_baseline and world == 1 and not sharded:
         cpu = cpu_baseline(w, host_batches)
     line = {
         "metric": "training triples/sec (1-vs-all ComplEx d=200)" if w.name.startswith("S-FB") and w.d == 200

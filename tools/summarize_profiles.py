@@ -34,7 +34,7 @@ for k in sorted(set(fetch) | set(write)):
     fk, wk = fetch.get(k, {}).get("FETCH_SIZE", 0.0), write.get(k, {}).get("WRITE_SIZE", 0.0)
     traffic[k] = {"FETCH_SIZE_KB": fk, "WRITE_SIZE_KB": wk, "hbm_bytes_per_launch": 2.0 * fk * 1024 + wk * 1024}
 traffic["_command"] = "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- " + os.environ.get(
-    "OKGE_PROFILE_COMMAND", "python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline (OKGE_BENCH_OLP=0)")
+    "OKGE_PROFILE_COMMAND", "python3 bench.py --full --steps 50 --warmup 10 --no-cpu-baseline (OKGE_BENCH_OLP=0)")
 traffic["_commit"] = os.environ.get("OKGE_COMMIT")          # stamped by tools/publish_profiles.py in the build container
 json.dump(traffic, open(os.path.join(root, "pmc_traffic.json"), "w"), indent=1)
 with open(os.path.join(root, "pmc_summary.txt"), "w") as out:
