@@ -305,6 +305,46 @@ int okge_pool_backward(const okge_token_embedder *e, const int32_t *ids, int32_t
                        const float *raw, const float *d_out, int64_t ld, float *saved, float *dW,
                        float *d_bn_weight, float *d_bn_bias, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- LSTM token encoder -------------------------------------------------------------------------------
+ * Replaces LSTMRelationEmbedder._encode / _encode_tokens (model.py:966-986) up to (not including) its final dropout:
+ *   row id -> token_ids[id][0..max_len) (right-padded with 0; TokenBasedRelationEmbedder, model.py:579-597)
+ *          -> embedding rows of W (row 0 read as stored) -> one-layer torch.nn.LSTM (batch_first, gates i, f, g, o:
+ *             gates = x W_ih^T + b_ih + h W_hh^T + b_hh; h0 = c0 = 0), stepped through every position up to
+ *             last = count(tokens > 0) - 1, where -1 wraps to max_len - 1 (output[range(n), last_state], model.py:977-980)
+ *          -> h at last -> BatchNorm1d(eps, momentum) if bn_weight != NULL (per call as okge_pool_encode; model.py:981-982).
+ * A PASS takes up to 8 calls of one slot (a training step: candidates + po objects + sp subjects on the entity slot, po + sp
+ * relations on the relation slot); their rows are laid out one call after the other in raw / out / d_out ([rows][ld]).
+ * Running statistics and batch-norm gradients follow the order of the array.  d <= 512, max_len <= 64.
+ * okge_lstm_encode_calls  : raw = LSTM output rows, out = normalised rows (out unused without batch-norm);
+ *                           pos_tok [rows * max_len] (caller's buffer) = the token id of every position the LSTM steps
+ *                           through (0 past them).  training != 0 keeps what the backward needs in the workspace.
+ * okge_lstm_backward_calls: after a training encode with the same arguments and workspace: d_out -> batch-norm backward ->
+ *                           backward through time.  d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_bn_weight, d_bn_bias are WRITTEN;
+ *                           dW (vocab x d) += the token rows' gradient, summed per token in the order of pos_order = the
+ *                           positions sorted by pos_tok (stable; index plumbing by the caller); token 0 receives nothing.
+ * No float atomics: bit-reproducible.  Workspace: okge_lstm_workspace_bytes(total rows, max_len, d, training). */
+typedef struct okge_lstm_slot {
+    const float *W;              /* token embedding table (vocab x d) */
+    const int32_t *token_ids;    /* (n_ids x max_len) */
+    int32_t vocab, d, n_ids, max_len;
+    const float *w_ih, *w_hh;    /* weight_ih_l0, weight_hh_l0 (4d x d) */
+    const float *b_ih, *b_hh;    /* bias_ih_l0, bias_hh_l0 (4d) */
+    const float *bn_weight, *bn_bias;      /* NULL: no batch-norm */
+    float *bn_running_mean, *bn_running_var;
+    float bn_eps, bn_momentum;
+} okge_lstm_slot;
+typedef struct okge_lstm_call {
+    const int32_t *ids;          /* NULL: rows first_id .. first_id + n - 1 */
+    int32_t first_id, n;
+} okge_lstm_call;
+size_t okge_lstm_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training);
+int okge_lstm_encode_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, int32_t n_calls, int32_t training, float *raw,
+                           float *out, int64_t ld, int32_t *pos_tok, void *workspace, size_t workspace_bytes, void *stream);
+int okge_lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, int32_t n_calls, const float *raw,
+                             const float *d_out, int64_t ld, const int32_t *pos_tok, const int32_t *pos_order, float *dW,
+                             float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh, float *d_bn_weight, float *d_bn_bias,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- gradients of the plugin methods' scores (a caller's own loss) ----------------------------------------
  * Backward of sp_prefix_score / po_prefix_score / _score(prefix=True) (model.py:52-77, :198-229, :268-274) for a caller that
  * holds the dense (b, n) gradient g of the scores (the reference's autograd walks its four / one matrix products backwards):

@@ -995,6 +995,29 @@ int okge_scatter_rows(const float *rows, int64_t ld, const int32_t *ids, const i
     return OKGE_OK;
 }
 
+// ---- LSTM token encoder (okge_lstm.hip) ----------------------------------------------------------------------------
+size_t okge_lstm_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training)
+{
+    return lstm_workspace_bytes(rows, max_len, d, training);
+}
+
+int okge_lstm_encode_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, int32_t n_calls, int32_t training, float *raw,
+                           float *out, int64_t ld, int32_t *pos_tok, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ScopedTimer tm("lstm_encode", reinterpret_cast<hipStream_t>(stream));
+    return lstm_encode_calls(s, calls, n_calls, training, raw, out, ld, pos_tok, workspace, workspace_bytes, id_err_ptr(), stream);
+}
+
+int okge_lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, int32_t n_calls, const float *raw,
+                             const float *d_out, int64_t ld, const int32_t *pos_tok, const int32_t *pos_order, float *dW,
+                             float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh, float *d_bn_weight, float *d_bn_bias,
+                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    ScopedTimer tm("lstm_backward", reinterpret_cast<hipStream_t>(stream));
+    return lstm_backward_calls(s, calls, n_calls, raw, d_out, ld, pos_tok, pos_order, dW, d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_bn_weight,
+                               d_bn_bias, workspace, workspace_bytes, id_err_ptr(), stream);
+}
+
 int okge_score_triples(int32_t scorer, const float *subj, int64_t ld_subj, const float *rel, int64_t ld_rel,
                        const float *obj, int64_t ld_obj, int32_t n, int32_t d, float *out, void *stream)
 {

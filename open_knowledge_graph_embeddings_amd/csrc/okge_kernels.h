@@ -5,6 +5,7 @@
 #include <atomic>
 #include <stdint.h>
 #include "okge_device.h"
+#include "../../include/okge.h"
 
 namespace okge {
 
@@ -185,6 +186,14 @@ size_t pool_scatter_state_bytes(const PoolCall *calls, int n_calls);
 size_t pool_scatter_workspace_bytes(const PoolCall *calls, int n_calls);
 hipError_t launch_pool_backward_calls(const PoolCall *calls, int n_calls, int *id_err, hipStream_t st, void *state = nullptr,
                                       size_t state_bytes = 0, void *scratch = nullptr, size_t scratch_bytes = 0);
+// LSTM token encoder (okge_lstm.hip): the bodies of the C ABI's okge_lstm_* (okge.h), err = the device's id-error word
+size_t lstm_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training);
+int lstm_encode_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, int32_t n_calls, int32_t training, float *raw, float *out,
+                      int64_t ld, int32_t *pos_tok, void *workspace, size_t workspace_bytes, int *err, void *stream);
+int lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, int32_t n_calls, const float *raw, const float *d_out,
+                        int64_t ld, const int32_t *pos_tok, const int32_t *pos_order, float *dW, float *d_w_ih, float *d_w_hh,
+                        float *d_b_ih, float *d_b_hh, float *d_bn_weight, float *d_bn_bias, void *workspace, size_t workspace_bytes,
+                        int *err, void *stream);
 // dense Adagrad over up to four tensors in one launch; a tensor may come with a touched-row byte map (rows whose byte differs
 // from `stamp` hold an all-zero gradient by contract: it is neither read nor cleared)
 constexpr int ADAGRAD_MAX_SEGS = 4;
