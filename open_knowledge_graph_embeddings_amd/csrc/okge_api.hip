@@ -55,8 +55,6 @@ hipEvent_t get_event()
     return e;
 }
 
-constexpr int OKGE_MAX_DEVICES_SIDE = 64;
-
 struct ScopedTimer {
     hipStream_t st;
     bool        on;
@@ -78,36 +76,6 @@ struct ScopedTimer {
         g_launches.push_back(t);
     }
 };
-
-// ---- a side stream per (host thread, device): the partial-slab reduction of a training call BESIDE the dQ kernel -----------
-// An experiment, OFF unless OKGE_REDUCE_OVERLAP=1.  dc_reduce* is HBM-bound (17 us / 87 MB at configs[2], 9.5 us at configs[4]) and
-// the dQ kernel that follows it is MFMA-bound and needs nothing the reduction writes (it reads G^T and the masked candidate rows;
-// the reduction turns the tile kernel's partial slabs into dE rows): fork after the tile launch, join before whatever touches dE
-// or the slabs next (the prefix backward, the next range's tile launch); event record / wait pairs, captured as plain dependencies
-// when the caller's stream is capturing.  Correct (the whole GPU suite passes with it on) and SLOWER: next to the dQ kernel's
-// resident workgroups the reduction stretches 17 -> 66 us and the dQ kernel 54 -> 59 us: configs[2] 0.257 -> 0.276 ms, configs[4]
-// 0.728 -> 0.743, the 8-rank FB shape 0.154 -> 0.164 (profiles/round4_ablation.md section 7) -- like the two side-stream sweeps before.
-struct SideStream {
-    hipStream_t s = nullptr;
-    hipEvent_t  fork = nullptr, join = nullptr;
-    bool        ok = false;
-};
-static SideStream *side_stream()
-{
-    static const bool enabled = std::getenv("OKGE_REDUCE_OVERLAP") && std::atoi(std::getenv("OKGE_REDUCE_OVERLAP")) == 1;
-    if (!enabled) return nullptr;
-    thread_local SideStream side[OKGE_MAX_DEVICES_SIDE];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= OKGE_MAX_DEVICES_SIDE) return nullptr;
-    SideStream &x = side[dev];
-    if (!x.s) {
-        x.ok = hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking) == hipSuccess &&
-               hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&x.join, hipEventDisableTiming) == hipSuccess;
-        if (!x.s) x.s = reinterpret_cast<hipStream_t>(-1);       // (creation failed: never tried again, the reduction stays in line)
-    }
-    return x.ok ? &x : nullptr;
-}
 
 // ---- device word counting out-of-range ids (checked_row in the kernels); read and cleared by okge_id_errors ------------
 // One word PER DEVICE (keyed by hipGetDevice() at the call): a process that drives several devices must never hand a kernel
@@ -173,16 +141,14 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 struct Geometry {
     int    B, N, d, Bpad, D16, KB, LDK, ldq, ldg, tiles, b_split, b_per_block, nsplit;
-    int    tile_w, ktiles;      // fused train kernel: tile width (32 or 64 candidates) and tile count
     int    sk_wgs, sk_chunks;   // > 0: the train tile kernel is launched stream-K shaped over sk_wgs workgroups (okge_train64k.hip)
     // > 0: the LAST `tail_tiles` candidate tiles of the call (what is left over after whole rounds of one workgroup per CU)
     // are launched apart with the batch rows split over tail_split workgroups each, so the closing round is short
     int    tail_tiles, tail_split, tail_b_per_block;
-    bool   dq8;
     // training sweeps the candidates in RANGES of range_n (a multiple of 64) so that the one (B, N)-shaped
     // intermediate, G^T, and everything sized like it (masked rows Cm, KL statistics) is O(B x range_n):
     // 41 GB -> 1 GB at |E| = 2.5 M, B = 4096.  A range is one tile-kernel launch + one dq launch (slabs accumulate).
-    int    range_n, n_ranges, range_tiles, range_ktiles;
+    int    range_n, n_ranges, range_tiles;
     size_t off_Q, off_tptr, off_stats, off_lse, off_ysum, off_run, off_loss, off_GT, off_Cm, off_slab, off_dcs;
     size_t score_bytes, lse_bytes, total;
 };
@@ -258,25 +224,22 @@ bool make_geometry(int B, int N, int d, Geometry &g)
         }
         g.n_ranges = (g.tiles + g.range_tiles - 1) / g.range_tiles;
         g.range_n = g.range_tiles * NT;
-        g.range_ktiles = 2 * g.range_tiles;
     }
     g.ldg = g.range_tiles * NT;
-    // fused train kernel: one 8-wave workgroup per CU on 64-candidate tiles (slot sizes up to 256), or the 32-candidate
-    // cut for larger slots (an even tile count so that every 64-candidate chunk dq_kernel reads has been written)
-    // (slot sizes above 256: fused_tile64k_kernel, candidate tile in registers; OKGE_TILE_W=32 selects the round-1/2 cut)
-    g.tile_w = env_int("OKGE_TILE_W", 64) == 32 ? 32 : 64;
-    g.ktiles = g.tiles * (NT / g.tile_w);
-    const int slots = (g.tile_w == 64 || g.KB > 16) ? cu_count() : 2 * cu_count();   // one workgroup per CU, except the 32-wide cut at d <= 256
+    // fused train kernel: one 8-wave workgroup per CU on 64-candidate tiles (slot sizes above 256: fused_tile64k_kernel,
+    // candidate tile in registers)
+    const int slots = cu_count();
     // fill the CUs: if there are few candidate tiles, split the batch rows across blockIdx.y.  Cost of a split into c:
     // (rounds of workgroups over the slots) x (row blocks per workgroup + 1) -- the "+ 1" is a workgroup's fixed cost, the
     // candidate gather and the gradient write-back, about one 64-row block (profiles/round2_ablation.md §1) -- plus the c
-    // partial-gradient slabs dc_reduce adds up (an eighth of a block each).  Measured at cfg3 (313 tiles of 32, d = 512):
+    // partial-gradient slabs dc_reduce adds up (an eighth of a block each).  Measured at cfg3 on the retired 32-candidate cut
+    // (313 tiles of 32, d = 512):
     // c = 1 / 2 / 3 / 4 / 8 -> 0.299 / 0.288 / 0.294 / 0.303 / 0.364 ms per step; the model orders them 18 / 15 / 16 / 15 / 20.
     int bs = 1;
     {
         long best = -1;
         for (int c = 1; c <= bblks; ++c) {
-            const long rounds = ((long)g.ktiles * c + slots - 1) / slots, per = (bblks + c - 1) / c;
+            const long rounds = ((long)g.tiles * c + slots - 1) / slots, per = (bblks + c - 1) / c;
             const long cost = 8 * rounds * (per + 1) + c;
             if (best < 0 || cost < best) { best = cost; bs = c; }
         }
@@ -289,7 +252,7 @@ bool make_geometry(int B, int N, int d, Geometry &g)
     // slot sizes above 256 (fused_tile64k_kernel), one launch: (tile, 32-row chunk) units in equal runs over one workgroup
     // per CU instead of a (tiles, batch splits) grid -- see the kernel's header for the measurements behind it
     g.sk_wgs = g.sk_chunks = 0;
-    if (g.KB == 32 && g.tile_w == 64 && g.n_ranges == 1 && env_int("OKGE_STREAMK", 1) != 0 && env_int("OKGE_B_SPLIT", 0) == 0) {
+    if (g.KB == 32 && g.n_ranges == 1 && env_int("OKGE_STREAMK", 1) != 0 && env_int("OKGE_B_SPLIT", 0) == 0) {
         g.sk_chunks = (B + 31) / 32;
         const int64_t units = (int64_t)g.tiles * g.sk_chunks;
         g.sk_wgs = (int)std::min<int64_t>(std::min(cu_count(), 511), units);
@@ -302,14 +265,12 @@ bool make_geometry(int B, int N, int d, Geometry &g)
     // candidate gradients go through the batch-split slabs + dc_reduce.  Worth it when the rows per workgroup drop by >= 2 blocks.
     g.tail_tiles = g.tail_split = 0;
     g.tail_b_per_block = g.Bpad;
-    if (g.KB <= 16 && g.tile_w == 64 && g.b_split == 1) {
+    if (g.KB <= 16 && g.b_split == 1) {
         const TailSplit ts = tail_split(g.tiles - (g.n_ranges - 1) * g.range_tiles, g.Bpad, slots);
         if (ts.split > 1) { g.tail_tiles = ts.tiles; g.tail_split = ts.split; g.tail_b_per_block = ts.b_per_block; }
     }
-    // dQ kernel: (batch block, candidate range) workgroups: 8-wave workgroups, one per CU (d <= 256), else 4-wave, two per CU
-    // (slot sizes above 256: dq8k_kernel, 32-candidate chunks double-buffered; OKGE_DQ8K=0 selects dq_kernel<32>)
-    g.dq8 = (g.KB <= 16 && env_int("OKGE_DQ8", 1) != 0) || (g.KB == 32 && env_int("OKGE_DQ8K", 1) != 0);
-    int ns = std::max(1, (g.dq8 ? cu_count() : 2 * cu_count()) / bblks);
+    // dQ kernel: (batch block, candidate range) workgroups, 8 waves, one per CU
+    int ns = std::max(1, cu_count() / bblks);
     if (ns >= 8) ns = ns / 8 * 8;   // workgroups of one candidate range then share an XCD (blockIdx % 8)
     ns = env_int("OKGE_DQ_SPLIT", ns);
     ns = std::max(1, std::min(ns, g.range_tiles));
@@ -319,8 +280,10 @@ bool make_geometry(int B, int N, int d, Geometry &g)
     g.off_Q = off;     off += align_up((size_t)g.Bpad * g.ldq * sizeof(float), 256);
     g.score_bytes = off;
     // [row log-sum-exp part] per-range (max, sum-exp) tile statistics + the running per-row state
+    // (the tile offsets here and the loss partials below keep room for 32-candidate tiles, so that okge_train_workspace_bytes
+    //  answers as it did before that cut was retired)
     g.off_tptr = off;  off += align_up((size_t)(2 * g.tiles + 1) * sizeof(int32_t), 256);
-    g.off_stats = off; off += align_up((size_t)2 * g.range_ktiles * g.Bpad * 2 * sizeof(float), 256);
+    g.off_stats = off; off += align_up((size_t)4 * g.range_tiles * g.Bpad * 2 * sizeof(float), 256);   // <= 4 per tile
     g.off_lse = off;   off += align_up((size_t)g.Bpad * sizeof(float), 256);
     g.off_ysum = off;  off += align_up((size_t)g.Bpad * sizeof(float), 256);
     g.off_run = off;   off += align_up((size_t)g.Bpad * 2 * sizeof(float), 256);
@@ -390,7 +353,7 @@ FusedArgs tile_window(const FusedArgs &base, const Geometry &g, int t0)
 
 // the score sweep (MODE_SCORE / _STATS / _COUNT) of `tiles` 64-candidate tiles over all B rows: the 64 x 64 kernel up to slot size
 // 256 (rows are independent: the tail tiles simply run as (tile, row split) workgroups); above, the register-tile kernel in a
-// stream-K launch (no partial outputs to add up), or the 32 x 32 cut it replaced
+// stream-K launch (no partial outputs to add up)
 hipError_t launch_score_sweep(const Geometry &g, const FusedArgs &a0, int tiles, hipStream_t st, int mode = MODE_SCORE)
 {
     if (g.KB <= 16) {
@@ -403,7 +366,6 @@ hipError_t launch_score_sweep(const Geometry &g, const FusedArgs &a0, int tiles,
         at.b_per_block = ts.b_per_block;
         return launch_fused(mode, at, ts.tiles, ts.split, st);
     }
-    if (g.tile_w == 32) return launch_fused32(mode, a0, 2 * tiles, 1, st);
     FusedArgs a = a0;
     a.sk_tiles = tiles;
     const int64_t units = (int64_t)tiles * ((a.B + 31) / 32);
@@ -420,8 +382,8 @@ FusedArgs range_args(const FusedArgs &base, const Geometry &g, int r, int &tiles
     a.cand_first += n_lo;
     if (a.cand_ids) a.cand_ids += n_lo;
     a.cand_col0 += n_lo;
-    if (a.tile_ptr) a.tile_ptr += n_lo / g.tile_w;
-    if (a.loss_partial) a.loss_partial += (size_t)(n_lo / g.tile_w) * g.b_split;
+    if (a.tile_ptr) a.tile_ptr += n_lo / NT;
+    if (a.loss_partial) a.loss_partial += (size_t)(n_lo / NT) * g.b_split;
     tiles_r = (a.N + NT - 1) / NT;
     return a;
 }
@@ -446,7 +408,7 @@ int lse_pass(const Geometry &g, const FusedArgs &base, char *ws, float *row_lse,
             if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<stats>");
         }
         ScopedTimer tm("kl_row_lse", st);
-        // the 64x64 cut emits one (max, sum-exp) per 64-candidate tile, the 32x32 cut one per 16-candidate block
+        // the 64x64 cut emits one (max, sum-exp) per 64-candidate tile, the register-tile kernel one per 16-candidate block
         e = launch_kl_row_lse(s.stats, g.KB <= 16 ? tiles_r : 4 * tiles_r, g.B, g.Bpad,
                               reinterpret_cast<float *>(ws + g.off_run), r == 0, r == g.n_ranges - 1, row_lse, st,
                               r == 0 ? count_pos_row : nullptr, count_nnz, r == 0 ? count_ysum : nullptr);   // + the rows' label mass
@@ -570,7 +532,7 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
         if (opt) clr.prefix_flags = opt->prefix_flags;
         e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + g.off_Q), g.ldq,
                                   q_ext ? 0 : g.Bpad, nullptr, pos->col, pos->nnz,
-                                  reinterpret_cast<int32_t *>(ws + g.off_tptr), g.ktiles, g.tile_w, cand_col0, st,
+                                  reinterpret_cast<int32_t *>(ws + g.off_tptr), g.tiles, NT, cand_col0, st,
                                   (clear_grads || kl_own_lse || opt) ? &clr : nullptr);
         if (e != hipSuccess) return fail_hip(e, "encode_queries");
     }
@@ -634,11 +596,10 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
     q.slab = reinterpret_cast<float *>(ws + g.off_slab);
     q.d = g.d; q.KB = g.KB; q.LDK = g.LDK; q.Bpad = g.Bpad; q.ldq = g.ldq; q.ldg = g.ldg;
     q.nsplit = g.nsplit;
-    q.waves8 = g.dq8 ? 1 : 0;
     const int mode = loss_kind == OKGE_LOSS_KL ? MODE_TRAIN_KL : MODE_TRAIN_BCE;
     // (tail split: the tail launch's partials of row split y > 0 follow the per-tile ones -- index y * tail + x from the tail's
     //  first tile is contiguous with them)
-    const int n_loss_partials = g.sk_wgs > 0 ? g.sk_wgs : g.ktiles * g.b_split + g.tail_tiles * std::max(0, g.tail_split - 1);
+    const int n_loss_partials = g.sk_wgs > 0 ? g.sk_wgs : g.tiles * g.b_split + g.tail_tiles * std::max(0, g.tail_split - 1);
     for (int r = 0; r < g.n_ranges; ++r) {
         int tiles_r;
         const FusedArgs ar = range_args(a, g, r, tiles_r);
@@ -664,37 +625,28 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
                     e = launch_fused64(mode, at, tail_r, g.tail_split, st);
                 }
             } else {
-                e = g.tile_w == 64 ? launch_fused64(mode, ar, tiles_r, g.b_split, st) : launch_fused32(mode, ar, 2 * tiles_r, g.b_split, st);
+                e = launch_fused64(mode, ar, tiles_r, g.b_split, st);
             }
             if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<train>");
         }
         if (loss_only) continue;
-        // the partial slabs' reduction: on the side stream beside the dQ launch where there is one (see SideStream)
-        const bool reduce = tail_r > 0 || g.sk_wgs > 0 || g.b_split > 1;
-        SideStream *side = reduce ? side_stream() : nullptr;
-        hipStream_t rs = st;
-        if (side) {
-            if (hipEventRecord(side->fork, st) == hipSuccess && hipStreamWaitEvent(side->s, side->fork, 0) == hipSuccess) rs = side->s;
-            else side = nullptr;
-        }
         if (tail_r > 0) {
-            ScopedTimer tm("dc_reduce", rs);
+            ScopedTimer tm("dc_reduce", st);
             e = launch_dc_reduce(a.dC_slab, g.tail_split, tail_r * NT, g.D16, at.N, g.d, at.cand_ids, at.cand_first, a.cand_exclusive,
-                                 a.grads_zero, dE, a.n_table_rows, a.id_err, rs);
+                                 a.grads_zero, dE, a.n_table_rows, a.id_err, st);
             if (e != hipSuccess) return fail_hip(e, "dc_reduce");
         }
         if (g.sk_wgs > 0) {
-            ScopedTimer tm("dc_reduce", rs);
+            ScopedTimer tm("dc_reduce", st);
             e = launch_dc_reduce_streamk(a.dC_slab, tiles_r, g.sk_chunks, g.sk_wgs, g.D16, ar.N, g.d, cand->ids, cand->first_id,
-                                         a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err, rs);
+                                         a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err, st);
             if (e != hipSuccess) return fail_hip(e, "dc_reduce_streamk");
         } else if (g.b_split > 1) {                 // (few candidate tiles: always a single range)
-            ScopedTimer tm("dc_reduce", rs);
+            ScopedTimer tm("dc_reduce", st);
             e = launch_dc_reduce(a.dC_slab, g.b_split, g.tiles * NT, g.D16, g.N, g.d, cand->ids, cand->first_id, a.cand_exclusive,
-                                 a.grads_zero, dE, a.n_table_rows, a.id_err, rs);
+                                 a.grads_zero, dE, a.n_table_rows, a.id_err, st);
             if (e != hipSuccess) return fail_hip(e, "dc_reduce");
         }
-        if (side && hipEventRecord(side->join, side->s) != hipSuccess) return fail(OKGE_ERR_HIP, "side stream: event record");
         {
             ScopedTimer tm("dq", st);
             q.N = ar.N;
@@ -702,8 +654,6 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
             e = launch_dq(q, (g.Bpad / BC) * g.nsplit, st);
             if (e != hipSuccess) return fail_hip(e, "dq_kernel");
         }
-        // join: the next range's tile launch rewrites the slabs, the prefix backward adds into dE rows the reduction stores
-        if (side && hipStreamWaitEvent(st, side->join, 0) != hipSuccess) return fail(OKGE_ERR_HIP, "side stream: event wait");
     }
     if (loss_only) {
         ScopedTimer tm("loss_reduce", st);
@@ -1536,8 +1486,7 @@ static int eval_issue(int phases, const EvalCall &c, hipStream_t st)
     }
     if (phases & 2) {
         ScopedTimer tm("fused_tile_count", st);
-        // (slot sizes above 256: the register-tile kernel's counting mode in a stream-K launch; not on the OKGE_TILE_W=32 cut)
-        if (c.g.KB > 16 && c.g.tile_w == 32) return fail(OKGE_ERR_UNSUPPORTED, "the 32-wide cut (OKGE_TILE_W=32) has no counting sweep above slot size 256");
+        // (slot sizes above 256: the register-tile kernel's counting mode in a stream-K launch)
         e = launch_score_sweep(c.g, c.sweep, c.g.tiles, st, MODE_COUNT);
         if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<count>");
     }

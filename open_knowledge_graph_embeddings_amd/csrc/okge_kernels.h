@@ -46,9 +46,9 @@ struct FusedArgs {
     const int32_t *tile_ptr;   // [tiles + 1] offsets into pos_* per candidate tile
     const float   *row_lse, *row_ysum;   // KL
     float         *G;          // [Bpad][ldg]  dLoss/dX / normalizer, row-major, ldg = 64 * tiles
-    float         *Cm;         // [64 * tiles][16*KB]  masked (dropped-out) candidate rows, for dq_kernel
+    float         *Cm;         // [64 * tiles][16*KB]  masked (dropped-out) candidate rows, for the dQ kernel
     float         *dE;
-    float         *dC_slab;    // [gridDim.y][32 * ktiles][16*KB] partial candidate gradients when the batch is split over blockIdx.y
+    float         *dC_slab;    // [gridDim.y][64 * tiles][16*KB] partial candidate gradients when the batch is split over blockIdx.y
     double        *loss_partial;
     float         *X;          // score mode
     float         *stats;      // stats mode: float2 [tiles][Bpad]
@@ -77,7 +77,6 @@ struct DqArgs {
     float         *slab;       // [nsplit][Bpad][ldq]
     int32_t        d, KB, LDK, N, Bpad, ldq, ldg, nsplit;
     int32_t        accumulate; // add to the slabs instead of overwriting them (candidate ranges after the first)
-    int32_t        waves8;     // dq8_kernel: one 8-wave workgroup per CU, contraction split over two wave groups (d <= 256)
 };
 
 struct PrefixDev {
@@ -91,10 +90,8 @@ struct PrefixDev {
 };
 
 size_t     fused_shmem_bytes(int LDK);
-size_t     dq_shmem_bytes(int LDK);
 hipError_t launch_fused(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st);
 hipError_t launch_dq(const DqArgs &a, int grid_x, hipStream_t st);
-hipError_t launch_fused32(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st);
 hipError_t launch_fused64(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st);
 hipError_t launch_fused64k(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st);   // slot sizes above 256
 

@@ -160,7 +160,7 @@ __device__ __forceinline__ void loss_reduce_block(const double *__restrict__ par
     }
 }
 
-// dQ[b][k] = sum over candidate ranges of the dq_kernel slabs (sharded path: reduced before the all-reduce)
+// dQ[b][k] = sum over candidate ranges of the dQ kernel's slabs (sharded path: reduced before the all-reduce)
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float *__restrict__ slab, int nsplit, int64_t n4,
                                                           float *__restrict__ out, const double *__restrict__ loss_partials,
                                                           int n_partials, double *__restrict__ loss_out)

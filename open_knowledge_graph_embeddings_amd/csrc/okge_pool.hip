@@ -111,7 +111,6 @@ struct ScatterBatch {
     ScatterGroup g[POOL_MAX_CALLS];
     int32_t n_calls, n_groups;
     int32_t hist_rows;                 // rows per workgroup of pass 1 (SC_HIST_PAIRS / L)
-    int32_t ablate;                    // diagnostics (OKGE_SC_ABLATE): leave parts out to time the rest; results are then WRONG
     int32_t hist_cum[POOL_MAX_CALLS + 1];
 };
 
@@ -132,7 +131,6 @@ __device__ __forceinline__ void scatter_count_block(const ScatterBatch &sb, int 
     const ScatterCall &q = sb.c[c];
     const ScatterGroup &g = sb.g[q.group];
     const int L = g.L, r0 = lb * sb.hist_rows, nr = min(q.n, r0 + sb.hist_rows) - r0;
-    if (sb.ablate & 128) return;
     constexpr int PER = SC_HIST_PAIRS / 256;
     if (threadIdx.x == 0) n_found = 0;
     __syncthreads();
@@ -180,7 +178,6 @@ __device__ __forceinline__ void scatter_alloc_block(const ScatterBatch &sb, int 
     }
     const ScatterGroup &g = sb.g[gi];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (sb.ablate & 256) return;
     int c[PER];
     int mine[4] = {0, 0, 0, 0};                          // tokens with several pairs, their pairs, long segments, tokens with one pair
 #pragma unroll
@@ -702,7 +699,6 @@ __global__ __launch_bounds__(256) void pool_dx_kernel(const PoolBatch pb, const 
         // the cold pairs go to their token's segment: (token, pair) -> start[token] -> [returning atomic on the token's
         // counter, which pass 1 left at the pair count and which returns to zero here ->] one 4-byte store.  Tokens with a
         // single pair (four in five) need no atomic: the pair goes into the token's list entry.
-        if (sb.ablate & 1) return;
         int chunk = (int)blockIdx.x, gi = 0;
         while (gi + 1 < sb.n_groups && chunk >= sb.g[gi].hist_blocks) chunk -= sb.g[gi++].hist_blocks;
         const ScatterGroup &g = sb.g[gi];
@@ -753,10 +749,10 @@ __global__ __launch_bounds__(256) void pool_dx_kernel(const PoolBatch pb, const 
     auto load_column = [&](int k) {
         if (saved) { m = saved[k]; rs = saved[d + k]; db = saved[2 * d + k]; dw = saved[3 * d + k]; wk = q.bn_weight[k]; }
 #pragma unroll
-        for (int r = 0; r < SC_ROWS; ++r) gr[r] = (r < nr && !(sb.ablate & 8)) ? DY[(size_t)(r0 + r) * ld + k] : 0.f;
+        for (int r = 0; r < SC_ROWS; ++r) gr[r] = r < nr ? DY[(size_t)(r0 + r) * ld + k] : 0.f;
         if (saved) {
 #pragma unroll
-            for (int r = 0; r < SC_ROWS; ++r) x[r] = (r < nr && !(sb.ablate & 8)) ? X[(size_t)(r0 + r) * ld + k] : 0.f;
+            for (int r = 0; r < SC_ROWS; ++r) x[r] = r < nr ? X[(size_t)(r0 + r) * ld + k] : 0.f;
         }
     };
     for (int i = threadIdx.x; i < SC_HOT * SC_ROWS; i += blockDim.x) (&mult[0][0])[i] = 0.f;
@@ -789,8 +785,8 @@ __global__ __launch_bounds__(256) void pool_dx_kernel(const PoolBatch pb, const 
         }
 #pragma unroll
         for (int r = 0; r < SC_ROWS; ++r)
-            if (r < nr && !(sb.ablate & 4)) DX[(size_t)r * d + k] = gr[r];
-        for (int tk = 1; tk < ((sb.ablate & 2) ? 0 : SC_HOT); ++tk) {
+            if (r < nr) DX[(size_t)r * d + k] = gr[r];
+        for (int tk = 1; tk < SC_HOT; ++tk) {
             if (!(seen >> tk & 1u)) continue;            // (uniform)
             float acc = 0.f;
 #pragma unroll
@@ -894,7 +890,6 @@ __global__ __launch_bounds__(256, 4) void pool_sum_kernel(const ScatterBatch sb,
     static_assert(SC_WIN_WORDS >= SC_SORT_MAX && 4 * SC_LIST >= SC_SORT_MAX, "the rank sort of long segments reuses bm / lists");
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if ((int)blockIdx.x < n_hot) {
-        if (sb.ablate & 16) return;
         // the slabs of the workgroups of pool_dx_kernel that met the token, in block order: wave w takes a quarter of the
         // blocks, lists the ones whose mask has the token's bit (8 mask words = 256 blocks at a time) and adds their rows
         const ScatterGroup &g = sb.g[blockIdx.x / (SC_HOT - 1)];
@@ -929,7 +924,6 @@ __global__ __launch_bounds__(256, 4) void pool_sum_kernel(const ScatterBatch sb,
     }
     if ((int)blockIdx.x < n_hot + n_long) {
         const int lw = (int)blockIdx.x - n_hot;
-        if (sb.ablate & 32) return;
         for (int gi = 0; gi < sb.n_groups; ++gi) {
             const ScatterGroup &g = sb.g[gi];
             const int n_l = min(g.ctr[5], g.cap), d = g.d, L = g.L, P = g.P;
@@ -992,7 +986,6 @@ __global__ __launch_bounds__(256, 4) void pool_sum_kernel(const ScatterBatch sb,
     }
     // short segments: wave-private work, no workgroup barrier below this line.  Per token a chain of dependent loads (segment
     // -> pairs -> rows): the next token's segment is requested before the current one is worked on.
-    if (sb.ablate & 64) return;
     const int n_waves = 4 * ((int)gridDim.x - n_hot - n_long), wave = 4 * ((int)blockIdx.x - n_hot - n_long) + w;
     // tokens with one pair (four in five): dW[token] += DX[row], four tokens per wave side by side
     for (int gi = 0; gi < sb.n_groups; ++gi) {
@@ -1251,8 +1244,6 @@ hipError_t launch_pool_backward_calls(const PoolCall *calls, int n_calls, int *i
     std::memset(&sb, 0, sizeof(sb));
     sb.n_calls = n_calls;
     sb.n_groups = lo.n_groups;
-    static const int ablate = getenv("OKGE_SC_ABLATE") ? atoi(getenv("OKGE_SC_ABLATE")) : 0;
-    sb.ablate = ablate;
     char *sp = static_cast<char *>(scratch);
     auto take = [&](size_t bytes) { char *p = sp; sp += al256(bytes); return p; };
     for (int g = 0; g < lo.n_groups; ++g) {

@@ -7,12 +7,15 @@
 //     MODE_STATS writes per-row (max, sum-exp) partials for the KL loss' log_softmax (openkge/trainer.py:99-100).
 //     MODE_COUNT (fused evaluation) compares X in registers with each row's true answer scores and adds the tile's
 //     {#greater, #equal} to per-group counters: the rank rule of dataset.py:436-446 without the (B, N) score block.
-//     The training step (score -> loss -> dCand) is fused_tile32_kernel in okge_train32.hip.
+//     The training step (score -> loss -> dCand) is fused_tile64_kernel (okge_train64.hip) up to slot size 256 and
+//     fused_tile64k_kernel (okge_train64k.hip) above.
 //
-//   dq_kernel<KB>
-//     dQ = G . C : one workgroup per (64-row batch block, candidate range); partial slabs are summed by
+//   dq8_kernel<KB> (slot sizes up to 208), dq8k_kernel<KB> (209 .. 512)
+//     dQ = G . C : one 8-wave workgroup per (64-row batch block, candidate range); partial slabs are summed by
 //     prefix_backward_kernel (okge_misc.hip).  G arrives as 64x64 transposed blocks G^T[n][b] (16 KB each,
-//     written by fused_tile32_kernel straight from its registers) and is copied to LDS as is.
+//     written by the training tile kernel straight from its registers) and is copied to LDS as is.
+//     (The 4-wave, single-buffered dQ kernel these replaced was retired; its measurements are in
+//     profiles/round{2,3,4}_ablation.md.)
 //
 // KB = padded slot size / 16 is a compile-time constant so every operand read is unconditional.
 //
@@ -27,7 +30,6 @@
 //     ds_read_b128 lane group hit 16 distinct 16-byte LDS slots (conflict-free).  Leftover 16-column blocks
 //     (KB mod 4) use ds_read_b32 with natural columns.
 #include <algorithm>
-#include <cstdlib>
 
 #include "okge_device.h"
 #include "okge_kernels.h"
@@ -37,7 +39,7 @@ namespace okge {
 // ---- candidate tile: gather rows of E, apply dropout, park in LDS as Cs[NT][LDK] (zero padded) -----
 // Thread (tid>>3, tid&7) handles rows tid>>3 and 32 + tid>>3, octets (8 columns) tid&7, 8 + tid&7, ...
 // keepb (LDS, [NT][32] bytes) caches the keep flags for the dC epilogue; Cm (global [NT][16*KB]) receives the
-// masked tile for dq_kernel.  Either may be nullptr.
+// masked tile for the dQ kernel.  Either may be nullptr.
 template <int KB>
 __device__ __forceinline__ void load_cand_tile(float *Cs, const float *__restrict__ E, int d, const int32_t *__restrict__ cand_ids,
                                                int cand_first, int N, int n0, const DropDev &drop, bool vec_ok, int tid,
@@ -404,125 +406,20 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
     }
 }
 
-// ---- dQ = G . C over a candidate range -------------------------------------------------------------
-// G^T block (64 candidates x 64 batch rows, 16 KB contiguous) and masked
-// candidate tile (64 x 16*KB) of one chunk -> registers
-// slot sizes above 256: the 132 KB candidate tile leaves room for one workgroup per CU; it runs 8 waves, waves w and
-// w + 4 taking the two halves of the output columns (no exchange needed: disjoint outputs, shared G^T operand)
-template <int KB> struct DqCfg {
-    static constexpr int KS = KB <= 16 ? 1 : 2;
-    static constexpr int THREADS = 256 * KS;
-    static constexpr int QG = 8 * KS;                 // staging: column groups per row
-    static constexpr int NO = 2 * KB, NOIT = (NO + QG - 1) / QG;
-    static constexpr int GV = 4 / KS;                 // float4 of the G^T block per thread
-};
-
-template <int KB>
-__device__ __forceinline__ void dq_prefetch(v4f (&gv)[DqCfg<KB>::GV], v4f (&cv)[4 * DqCfg<KB>::NOIT],
-                                            const float *__restrict__ g_blk, const DqArgs &a, int ch, int tid)
-{
-    using Cfg = DqCfg<KB>;
-    constexpr int NO = Cfg::NO, NOIT = Cfg::NOIT, QG = Cfg::QG;
-#pragma unroll
-    for (int it = 0; it < Cfg::GV; ++it) gv[it] = *reinterpret_cast<const v4f *>(g_blk + (size_t)(tid + it * Cfg::THREADS) * 4);
-    const float *cm = a.Cm + (size_t)ch * NT * (16 * KB);
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const int r = tid / QG + 32 * pass;
-#pragma unroll
-        for (int it = 0; it < NOIT; ++it) {
-            const int o = min(tid % QG + QG * it, NO - 1);   // clamped: surplus lanes reload the last octet
-            cv[(2 * pass) * NOIT + it] = *reinterpret_cast<const v4f *>(cm + (size_t)r * (16 * KB) + 8 * o);
-            cv[(2 * pass + 1) * NOIT + it] = *reinterpret_cast<const v4f *>(cm + (size_t)r * (16 * KB) + 8 * o + 4);
-        }
-    }
-}
-
 constexpr int LDGT = 68;   // G^T tile leading dimension (16-byte aligned rows; the A operand is one ds_read_b32 per 13 MFMAs,
                            // so its 2-way conflict between slots 16 rows apart is irrelevant)
 
-template <int KB>
-__global__ __launch_bounds__(DqCfg<KB>::THREADS) void dq_kernel(const DqArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    using Cfg = DqCfg<KB>;
-    constexpr int LDK = lds_ld(16 * KB);
-    constexpr int KS = Cfg::KS, NTHR = Cfg::THREADS, QG = Cfg::QG;
-    constexpr int KBW = KB / KS;                      // 16-column output blocks of one wave
-    constexpr int KQ = KBW / 4, KR = KBW % 4;
-    static_assert(KS == 1 || KB % 8 == 0, "the column split needs whole quads of 16-column blocks per wave");
-    constexpr int NO = Cfg::NO, NOIT = Cfg::NOIT;
-    float *Cs = reinterpret_cast<float *>(smem);      // [NT][LDK]   masked candidate rows
-    float *Gt = Cs + NT * LDK;                        // [NT (n)][LDGT] : G^T tile, 64 batch rows wide
-
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, s = lane >> 4;
-    const int ks = KS == 1 ? 0 : w >> 2, wq = w & 3;  // column half, 16-row block of the 64 batch rows
-    const int split = blockIdx.x % a.nsplit, bblk = blockIdx.x / a.nsplit;
-    const int b0 = bblk * BC;
-    const int nJ = a.Bpad / BC;
-    const int nchunks = (a.N + NT - 1) / NT;
-    const int ch_lo = (int)((int64_t)split * nchunks / a.nsplit);
-    const int ch_hi = (int)((int64_t)(split + 1) * nchunks / a.nsplit);
-
-    v4f acc[KBW];                                     // dQ[b = b0 + 16wq + 4s + i][k = 16*KBW*ks + grad_col(kbi, c)]
-#pragma unroll
-    for (int kb = 0; kb < KBW; ++kb) acc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
-
-    // register-staged prefetch: the next chunk's G block and masked candidate tile are in flight during the MFMAs
-    v4f gv[Cfg::GV], cv[4 * NOIT];   // cv[(2*pass + half) * NOIT + it]
-    auto g_block = [&](int ch) { return a.G + ((size_t)ch * nJ + bblk) * 4096; };
-    if (ch_lo < ch_hi) dq_prefetch<KB>(gv, cv, g_block(ch_lo), a, ch_lo, tid);
-    for (int ch = ch_lo; ch < ch_hi; ++ch) {
-        // G^T block -> LDS (float4 number f: candidate f >> 4, batch rows 4 * (f & 15) ..)
-#pragma unroll
-        for (int it = 0; it < Cfg::GV; ++it) {
-            const int f = tid + it * NTHR;
-            *reinterpret_cast<v4f *>(Gt + (f >> 4) * LDGT + 4 * (f & 15)) = gv[it];
-        }
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const int r = tid / QG + 32 * pass;
-#pragma unroll
-            for (int it = 0; it < NOIT; ++it) {
-                const int o = tid % QG + QG * it;
-                if (o < NO) {
-                    *reinterpret_cast<v4f *>(Cs + r * LDK + 8 * o) = cv[(2 * pass) * NOIT + it];
-                    *reinterpret_cast<v4f *>(Cs + r * LDK + 8 * o + 4) = cv[(2 * pass + 1) * NOIT + it];
-                }
-            }
-        }
-        __syncthreads();
-        if (ch + 1 < ch_hi) dq_prefetch<KB>(gv, cv, g_block(ch + 1), a, ch + 1, tid);
-        // A[i = b][slot s, step t] = G^T[n = 16s + t][b = 16wq + c] ; B[slot][k] = C[n = 16s + t][k of this wave's half]
-        grad_product<KBW, false, LDK>(acc, Gt + 16 * s * LDGT + 16 * wq + c, LDGT, Cs + 16 * s * LDK + 16 * KBW * ks, c);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float *dst = a.slab + ((size_t)split * a.Bpad + b0 + 16 * wq + 4 * s + i) * a.ldq + 16 * KBW * ks;
-#pragma unroll
-        for (int kq = 0; kq < KQ; ++kq) {
-            v4f v = (v4f){acc[4 * kq][i], acc[4 * kq + 1][i], acc[4 * kq + 2][i], acc[4 * kq + 3][i]};
-            if (a.accumulate) v += *reinterpret_cast<const v4f *>(dst + 64 * kq + 4 * c);
-            *reinterpret_cast<v4f *>(dst + 64 * kq + 4 * c) = v;
-        }
-#pragma unroll
-        for (int r = 0; r < KR; ++r)
-            dst[64 * KQ + 16 * r + c] = a.accumulate ? dst[64 * KQ + 16 * r + c] + acc[4 * KQ + r][i] : acc[4 * KQ + r][i];
-    }
-}
-
 // ---- dQ = G . C, eight waves: the contraction of a 64-candidate chunk split over two wave groups ---------------------
-// Slot sizes up to 256.  Same workgroup-level job as dq_kernel (64 batch rows x a candidate range -> one slab), but one
-// 8-wave workgroup per CU takes a range TWICE as long: half the slabs (13.6 instead of 27 MB written here and read back
-// by the prefix backward at S-FB), half the first-chunk burst at kernel start, prologue / epilogue amortised over twice
-// the chunks -- at two waves per SIMD like the two co-resident 4-wave workgroups before.  Wave (wq = w & 3, kh = w >> 2):
+// Slot sizes up to 208 (two tile pairs fit the LDS).  One 8-wave workgroup per CU takes 64 batch rows x a candidate range
+// -> one slab: a range twice as long as two co-resident 4-wave workgroups would take, so half the slabs (13.6 instead of
+// 27 MB written here and read back by the prefix backward at S-FB), half the first-chunk burst at kernel start, prologue /
+// epilogue amortised over twice the chunks -- at the same two waves per SIMD.  Wave (wq = w & 3, kh = w >> 2):
 // batch rows 16wq.., contraction steps 8kh .. 8kh+7 of every slot (candidates 16s + 8kh + t: slots stay 16 rows apart, the
 // B operand reads keep their conflict-free bank pattern); the two halves are added through LDS before the slab store.
-// DB (slot sizes up to 208: two tile pairs fit the LDS): chunk ch+1 is parked in the second pair while chunk ch is being
-// multiplied -- ONE barrier per chunk and no staging phase in which all eight waves write LDS and request the next chunk
-// while the MFMA pipes idle.  The two waves of a SIMD take turns: group kh = 0 parks before its MFMAs, group kh = 1 after.
-template <int KB, bool DB>
+// Double-buffered: chunk ch+1 is parked in the second pair while chunk ch is being multiplied -- ONE barrier per chunk and
+// no staging phase in which all eight waves write LDS and request the next chunk while the MFMA pipes idle.  The two waves
+// of a SIMD take turns: group kh = 0 parks before its MFMAs, group kh = 1 after.
+template <int KB>
 __global__ __launch_bounds__(512, 2) void dq8_kernel(const DqArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -592,36 +489,26 @@ __global__ __launch_bounds__(512, 2) void dq8_kernel(const DqArgs a)
         if (kh == 0) grad_product<KB, false, LDK, 0, 8>(acc, gt + 16 * s * LDGT + 16 * wq + c, LDGT, cs + 16 * s * LDK, c);
         else         grad_product<KB, false, LDK, 8, 16>(acc, gt + 16 * s * LDGT + 16 * wq + c, LDGT, cs + 16 * s * LDK, c);
     };
-    if (ch_lo < ch_hi) prefetch(ch_lo);
-    if (DB) {
-        if (ch_lo < ch_hi) {
-            park(0);
-            if (ch_lo + 1 < ch_hi) prefetch(ch_lo + 1);
+    if (ch_lo < ch_hi) {
+        prefetch(ch_lo);
+        park(0);
+        if (ch_lo + 1 < ch_hi) prefetch(ch_lo + 1);
+    }
+    for (int ch = ch_lo; ch < ch_hi; ++ch) {
+        const int buf = (ch - ch_lo) & 1;
+        __syncthreads();                           // chunk ch is parked; the other pair's readers (chunk ch - 1) are done
+        const bool more = ch + 1 < ch_hi;
+        if (kh == 0 && more) {                     // this wave group parks its share of chunk ch + 1 first ...
+            park(buf ^ 1);
+            if (ch + 2 < ch_hi) prefetch(ch + 2);
         }
-        for (int ch = ch_lo; ch < ch_hi; ++ch) {
-            const int buf = (ch - ch_lo) & 1;
-            __syncthreads();                       // chunk ch is parked; the other pair's readers (chunk ch - 1) are done
-            const bool more = ch + 1 < ch_hi;
-            if (kh == 0 && more) {                 // this wave group parks its share of chunk ch + 1 first ...
-                park(buf ^ 1);
-                if (ch + 2 < ch_hi) prefetch(ch + 2);
-            }
-            product(buf);
-            if (kh == 1 && more) {                 // ... the other one after its MFMAs: a SIMD's two waves take turns
-                park(buf ^ 1);
-                if (ch + 2 < ch_hi) prefetch(ch + 2);
-            }
-        }
-        __syncthreads();                           // the pairs are free: pair 0's candidate tile takes the kh = 1 partial sums
-    } else {
-        for (int ch = ch_lo; ch < ch_hi; ++ch) {
-            park(0);
-            __syncthreads();
-            if (ch + 1 < ch_hi) prefetch(ch + 1);
-            product(0);
-            __syncthreads();
+        product(buf);
+        if (kh == 1 && more) {                     // ... the other one after its MFMAs: a SIMD's two waves take turns
+            park(buf ^ 1);
+            if (ch + 2 < ch_hi) prefetch(ch + 2);
         }
     }
+    __syncthreads();                               // the pairs are free: pair 0's candidate tile takes the kh = 1 partial sums
     // the two contraction halves: kh = 1 parks its partial rows in LDS, kh = 0 adds them and stores the slab rows
     if (kh == 1) {
 #pragma unroll
@@ -656,18 +543,17 @@ __global__ __launch_bounds__(512, 2) void dq8_kernel(const DqArgs a)
     }
 }
 
-// ---- dQ = G . C for slot sizes above 256 (KB = 32): 32-candidate chunks, double-buffered ------------------------------------
-// dq_kernel<32> keeps a 64-candidate tile (132 KB) + its G^T block in LDS, single-buffered: per chunk every wave parks 16
-// float4, the workgroup passes two barriers and waits for the next chunk's loads while the MFMA pipes idle -- 0.52 of the
-// fp32-MFMA peak at the DistMult d = 512 shape, and (one workgroup per CU but a grid sized for two) 64 candidate splits =
-// 64 MB of dQ slabs that the prefix backward reads back.  Here a chunk is 32 candidates: two (candidate tile, G^T tile) pairs
-// fit the LDS (2 x 66 KB + 2 x 8.5 KB), chunk ch + 1 is parked in the second pair while chunk ch is being multiplied -- ONE
-// barrier per chunk, no staging phase --, the two waves of a SIMD take turns (group ks = 0 parks before its MFMAs, group
-// ks = 1 after), and the candidate range of a workgroup is twice as long (32 splits: half the slabs).  Wave (wq = w & 3,
+// ---- dQ = G . C for slot sizes above 208 (KB = 16, 32): 32-candidate chunks, double-buffered ---------------------------------
+// Why 32-candidate chunks: a 64-candidate tile at KB = 32 (132 KB) + its G^T block fill the LDS single-buffered -- per chunk
+// every wave parks 16 float4, the workgroup passes two barriers and waits for the next chunk's loads while the MFMA pipes
+// idle: 0.52 of the fp32-MFMA peak at the DistMult d = 512 shape, and (one workgroup per CU but a grid sized for two) 64
+// candidate splits = 64 MB of dQ slabs that the prefix backward reads back.  Here a chunk is 32 candidates: two (candidate
+// tile, G^T tile) pairs fit the LDS (2 x 66 KB + 2 x 8.5 KB), chunk ch + 1 is parked in the second pair while chunk ch is
+// being multiplied -- ONE barrier per chunk, no staging phase --, the two waves of a SIMD take turns (group ks = 0 parks
+// before its MFMAs, group ks = 1 after), and the candidate range of a workgroup is twice as long (32 splits: half the slabs).  Wave (wq = w & 3,
 // ks = w >> 2): batch rows 16 wq .., output columns 256 ks ..; contraction rows of slot s: candidates 8 s + t, t < 8.
-// KB = 16 (slot sizes 209 .. 256, where two 64-candidate pairs do not fit the LDS and dq8_kernel runs its single-pair loop):
-// the same loop on 128-column halves.
-template <int KB, bool DEEP>
+// KB = 16 (slot sizes 209 .. 256, where two 64-candidate pairs do not fit the LDS): the same loop on 128-column halves.
+template <int KB>
 __global__ __launch_bounds__(512, 2) void dq8k_kernel(const DqArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -693,7 +579,10 @@ __global__ __launch_bounds__(512, 2) void dq8k_kernel(const DqArgs a)
 
     const int r16 = tid >> 4, q16 = tid & 15;         // staging: row r16 of the chunk, float4 columns q16 + 16 it
     // register sets of chunks in flight: one (the chunk after the one being multiplied), or DEEP: two -- chunk ch + 3 is
-    // requested while chunk ch is multiplied and parked two chunks later, i.e. two chunk times (~4 us) to cover the load latency
+    // requested while chunk ch is multiplied and parked two chunks later, i.e. two chunk times (~4 us) to cover the load latency.
+    // DEEP at KB = 16 only (cfg4 shard: 1059 -> 1046 us per range; at KB = 32 the 36 extra registers cost more than the latency
+    // they cover: 53.6 -> 54.2 us at cfg3)
+    constexpr bool DEEP = KB == 16;
     constexpr int NSET = DEEP ? 2 : 1;
     v4f gv[NSET], cv[NSET][NV];
     auto prefetch = [&](int ch, auto set) {
@@ -774,18 +663,13 @@ static hipError_t launch_fused_m(int mode, const FusedArgs &a, dim3 grid, size_t
         case MODE_SCORE: return launch_fused_t<KB, MODE_SCORE>(a, grid, shmem, st);
         case MODE_STATS: return launch_fused_t<KB, MODE_STATS>(a, grid, shmem, st);
         case MODE_COUNT: return launch_fused_t<KB, MODE_COUNT>(a, grid, shmem, st);
-        default:         return hipErrorInvalidValue;      // training: fused_tile32_kernel
+        default:         return hipErrorInvalidValue;      // training: fused_tile64_kernel
     }
 }
 
 size_t fused_shmem_bytes(int LDK)
 {
     return (size_t)(NT + BC) * LDK * sizeof(float) + (size_t)BC * LDG * sizeof(float);
-}
-
-size_t dq_shmem_bytes(int LDK)
-{
-    return (size_t)NT * LDK * sizeof(float) + (size_t)NT * 68 * sizeof(float);
 }
 
 hipError_t launch_fused(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st)
@@ -802,24 +686,10 @@ hipError_t launch_fused(int mode, const FusedArgs &a, int grid_x, int grid_y, hi
 }
 
 template <int KB>
-static hipError_t launch_dq_t(const DqArgs &a, int grid_x, size_t shmem, hipStream_t st)
+static hipError_t launch_dq8_t(const DqArgs &a, int grid_x, hipStream_t st)
 {
-    auto k = dq_kernel<KB>;
-    static LdsOptIn lds_opt_in;
-    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), shmem); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid_x), dim3(DqCfg<KB>::THREADS), shmem, st, a);
-    return hipGetLastError();
-}
-
-template <int KB>
-static hipError_t launch_dq8_t(const DqArgs &a, int grid_x, size_t shmem, hipStream_t st)
-{
-    // two LDS tile pairs (slot sizes up to 208); OKGE_DQ8_DB=0: the single-pair loop
-    static const bool db_on = [] { const char *e = getenv("OKGE_DQ8_DB"); return !e || atoi(e) != 0; }();
-    constexpr bool CAN_DB = KB <= 13;
-    const bool db = CAN_DB && db_on;
-    auto k = db ? dq8_kernel<KB, CAN_DB> : dq8_kernel<KB, false>;
-    if (db) shmem *= 2;
+    auto k = dq8_kernel<KB>;
+    const size_t shmem = (size_t)2 * (NT * lds_ld(16 * KB) + NT * LDGT) * sizeof(float);     // two LDS tile pairs
     static LdsOptIn lds_opt_in;
     if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), shmem); e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid_x), dim3(512), shmem, st, a);
@@ -829,40 +699,22 @@ static hipError_t launch_dq8_t(const DqArgs &a, int grid_x, size_t shmem, hipStr
 template <int KB>
 static hipError_t launch_dq8k_t(const DqArgs &a, int grid_x, hipStream_t st)
 {
+    auto k = dq8k_kernel<KB>;
     const size_t sh = (size_t)2 * (32 * lds_ld(16 * KB) + 32 * LDGT) * sizeof(float);
-    // two chunks of loads in flight per thread at KB = 16 (cfg4 shard: 1059 -> 1046 us per range; at KB = 32 the 36 extra
-    // registers cost more than the latency they cover: 53.6 -> 54.2 us at cfg3); OKGE_DQ_DEEP=0 / 1 overrides
-    static const bool deep = [] { const char *e = getenv("OKGE_DQ_DEEP"); return e ? atoi(e) != 0 : KB == 16; }();
-    auto k = deep ? dq8k_kernel<KB, true> : dq8k_kernel<KB, false>;
-    static LdsOptIn lds_opt_in[2];
-    if (hipError_t e = ensure_dynamic_lds(lds_opt_in[deep], reinterpret_cast<const void *>(k), sh); e != hipSuccess) return e;
+    static LdsOptIn lds_opt_in;
+    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), sh); e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid_x), dim3(512), sh, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_dq(const DqArgs &a, int grid_x, hipStream_t st)
 {
-    const size_t shmem = dq_shmem_bytes(a.LDK);
-    if (a.waves8) {
-        switch (a.KB) {
-            case 4:  return launch_dq8_t<4>(a, grid_x, shmem, st);
-            case 8:  return launch_dq8_t<8>(a, grid_x, shmem, st);
-            case 13: return launch_dq8_t<13>(a, grid_x, shmem, st);
-            case 16: {
-                // 32-candidate chunks in two LDS pairs (dq8k_kernel<16>); OKGE_DQ8K16=0: the single-pair loop of dq8_kernel
-                static const bool k16 = [] { const char *e = getenv("OKGE_DQ8K16"); return !e || atoi(e) != 0; }();
-                return k16 ? launch_dq8k_t<16>(a, grid_x, st) : launch_dq8_t<16>(a, grid_x, shmem, st);
-            }
-            default: break;
-        }
-    }
-    if (a.waves8 && a.KB == 32) return launch_dq8k_t<32>(a, grid_x, st);
     switch (a.KB) {
-        case 4:  return launch_dq_t<4>(a, grid_x, shmem, st);
-        case 8:  return launch_dq_t<8>(a, grid_x, shmem, st);
-        case 13: return launch_dq_t<13>(a, grid_x, shmem, st);
-        case 16: return launch_dq_t<16>(a, grid_x, shmem, st);
-        case 32: return launch_dq_t<32>(a, grid_x, shmem, st);
+        case 4:  return launch_dq8_t<4>(a, grid_x, st);
+        case 8:  return launch_dq8_t<8>(a, grid_x, st);
+        case 13: return launch_dq8_t<13>(a, grid_x, st);
+        case 16: return launch_dq8k_t<16>(a, grid_x, st);
+        case 32: return launch_dq8k_t<32>(a, grid_x, st);
         default: return hipErrorInvalidValue;
     }
 }

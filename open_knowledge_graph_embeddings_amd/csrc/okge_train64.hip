@@ -4,7 +4,7 @@
 // (openkge/model.py:198-229,268-274,455-510; openkge/trainer.py:75-106,234).
 //
 // One workgroup owns 64 candidate entities: it gathers and drops them out ONCE into LDS (and hands the masked rows
-// to dq_kernel through `Cm`), then sweeps the batch's folded query rows in
+// to the dQ kernel through `Cm`), then sweeps the batch's folded query rows in
 // 64-row chunks.  Wave roles: blk = w & 3 (16-candidate block of the tile), h = w >> 2 (32-row half of the chunk: row
 // groups 2h, 2h + 1).
 //   score product : the wave's two 16x16 blocks X[rows of group][candidates of blk], ONE candidate operand
@@ -20,9 +20,8 @@
 // spread over twice the MFMAs per wave.
 // The two row halves' dC partial sums are added through LDS in the write-back, which also applies the cached dropout
 // flags.  G is stored UNMASKED: padding rows (b >= B) have zero query rows and candidates n >= N zero candidate rows, so
-// whatever dLoss/dX says there meets a zero in both gradient products and the dQ rows of padding are never read.  G leaves for dq_kernel from registers as 64x64 transposed blocks Gt[(T * nJ + J)][n_local][b_local].
+// whatever dLoss/dX says there meets a zero in both gradient products and the dQ rows of padding are never read.  G leaves for the dQ kernel from registers as 64x64 transposed blocks Gt[(T * nJ + J)][n_local][b_local].
 #include <cstdio>
-#include <cstdlib>
 
 #include "okge_device.h"
 #include "okge_kernels.h"
@@ -63,7 +62,7 @@ template <int KB> struct Tile64Cfg {
 #define TL_STAMP_AT(idx) do { } while (0)
 #endif
 
-// REGC (slot sizes up to 208): every lane keeps its slice of the wave's candidate block -- the B operand of the whole
+// REGC (slot sizes up to 208, KB <= 13): every lane keeps its slice of the wave's candidate block -- the B operand of the whole
 // score sweep, KB float4 -- in registers, read from the gathered tile once.  The tile's LDS then serves as a SECOND query
 // chunk buffer: chunk i+1 is parked while chunk i is being worked on, so a chunk has ONE barrier and no staging phase
 // (with one buffer every wave parks, requests and waits between two barriers while the MFMA pipes idle: ~1.3 K of a
@@ -74,9 +73,10 @@ template <int KB> struct Tile64Cfg {
 // order 16 r + 4 j + s (two ds_read_b32 per block instead of one ds_read_b128, the candidate operand read that way once in
 // the prologue), which puts columns 200..207 into MFMAs 2 and 3 -- and those are not issued: 50 instead of 52 score MFMAs
 // per block.  (The gradient product still writes all 208 columns: its OUTPUT is padded, not its contraction.)
-template <int KB, int MODE, bool REGC, bool SHORTK = false>
+template <int KB, int MODE, bool SHORTK = false>
 __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const FusedArgs a)
 {
+    constexpr bool REGC = KB <= 13;   // candidate operand in registers + two query chunk buffers: 4 KB more registers per lane
     static_assert(!SHORTK || (REGC && KB >= 3), "the short last round comes with the register-resident candidate operand");
 #ifdef OKGE_STAMPS
     unsigned long long wg_t0;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     const int pos_lo = a.tile_ptr[blockIdx.x], pos_hi = a.tile_ptr[blockIdx.x + 1];
     const int pos_cached = min(pos_hi - pos_lo, POS_CACHE);
 
-    // ---- candidate tile: gather, dropout, LDS; masked copy for dq_kernel ------------------------------------------------
+    // ---- candidate tile: gather, dropout, LDS; masked copy for the dQ kernel --------------------------------------------
     {
         const int n = n0 + r8;
         const bool valid = n < a.N;
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
                 *reinterpret_cast<v4f *>(Cs + r8 * LDK + k) = v0[it];
                 *reinterpret_cast<v4f *>(Cs + r8 * LDK + k + 4) = v1[it];
                 keepb[r8 * KEEP_LD + o] = (uint8_t)bits[it];
-                if (REGC && blockIdx.y == 0 && !a.loss_only) {        // the masked rows for dq_kernel, straight from the registers
+                if (REGC && blockIdx.y == 0 && !a.loss_only) {        // the masked rows for the dQ kernel, straight from the registers
                     float *cm = a.Cm + (size_t)(n0 + r8) * (16 * KB);  // (the tile's LDS is reused before a later chunk could)
                     *reinterpret_cast<v4f *>(cm + k) = v0[it];
                     *reinterpret_cast<v4f *>(cm + k + 4) = v1[it];
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     for (int kb = 0; kb < KB; ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
     float lsum = 0.f;
     const bool col_edge = n0 + NT64 > a.N;           // the last tile: candidates past N are masked out of the loss
-    // masked candidate rows for dq_kernel: written from LDS one octet column group per chunk (chunks 1 .. NOIT), so that
+    // masked candidate rows for the dQ kernel: written from LDS one octet column group per chunk (chunks 1 .. NOIT), so that
     // neither the prologue's HBM burst -- every workgroup gathering at once -- nor a later chunk carries all 12 MB;
     // whatever is left when the sweep ends (fewer chunks than column groups) goes out in the write-back
     auto write_cm = [&](int it) {
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             if (b0 + 2 * BC64 < b_end) fetch_chunk(b0 + 2 * BC64);
         }
         if (!a.loss_only) {
-            // ---- G blocks -> HBM for dq_kernel: Gt[T][J][n_local][b_local], 4 consecutive batch rows per lane ------
+            // ---- G blocks -> HBM for the dQ kernel: Gt[T][J][n_local][b_local], 4 consecutive batch rows per lane --
             {
                 const size_t blk_idx = (size_t)blockIdx.x * (a.Bpad >> 6) + (b0 >> 6);
                 float *gdst = a.G + blk_idx * 4096 + (16 * blk + c) * 64 + 32 * h + 4 * s;
@@ -577,13 +577,9 @@ static size_t shmem64()
 template <int KB, int MODE>
 static hipError_t launch64_t(const FusedArgs &a, dim3 grid, hipStream_t st)
 {
-    // candidate operand in registers + two query chunk buffers: 4 KB more registers per lane, so slot sizes up to 208
-    static const bool regc_on = [] { const char *e = getenv("OKGE_TILE64_REGC"); return !e || atoi(e) != 0; }();
-    static const bool shortk_on = [] { const char *e = getenv("OKGE_TILE64_SHORTK"); return !e || atoi(e) != 0; }();
-    auto k = KB <= 13 && regc_on ? fused_tile64_kernel<KB, MODE, (KB <= 13)> : fused_tile64_kernel<KB, MODE, false>;
+    auto k = fused_tile64_kernel<KB, MODE>;
     // slot sizes 16 (KB - 1) + 1 .. + 8: the last contraction round needs two of its four MFMAs
-    if (KB == 13 && regc_on && shortk_on && a.d > 16 * (KB - 1) && a.d <= 16 * (KB - 1) + 8)
-        k = fused_tile64_kernel<KB, MODE, (KB == 13), (KB == 13)>;
+    if (KB == 13 && a.d > 16 * (KB - 1) && a.d <= 16 * (KB - 1) + 8) k = fused_tile64_kernel<KB, MODE, (KB == 13)>;
     const size_t shmem = shmem64<KB>();
     static LdsOptIn lds_opt_in;
     if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), shmem); e != hipSuccess) return e;
@@ -606,8 +602,7 @@ hipError_t launch_fused64(int mode, const FusedArgs &a, int grid_x, int grid_y, 
         case 4:  return launch64_m<4>(mode, a, grid, st);
         case 8:  return launch64_m<8>(mode, a, grid, st);
         case 13: return launch64_m<13>(mode, a, grid, st);
-        case 16: { static const bool k64 = [] { const char *e = getenv("OKGE_TILE64K_D256"); return e && atoi(e) != 0; }();
-                   return k64 ? launch_fused64k(mode, a, grid_x, grid_y, st) : launch64_m<16>(mode, a, grid, st); }
+        case 16: return launch64_m<16>(mode, a, grid, st);
         case 32: return launch_fused64k(mode, a, grid_x, grid_y, st);      // okge_train64k.hip
         default: return hipErrorInvalidValue;
     }

@@ -4,7 +4,7 @@
 // and the mm / sigmoid half of autograd's backward (openkge/model.py:198-229,268-274,455-510; openkge/trainer.py:75-106,234).
 //
 // Why another cut.  At d = 512 a 64-candidate tile is 128 KB and so is its gradient: the round-1/2 kernel for these sizes
-// (fused_tile32_kernel<32>) therefore worked on 32 x 32 steps with BOTH tiles in LDS (2 x 66 KB, single-buffered), 8 waves
+// (since retired, profiles/round3_ablation.md) therefore worked on 32 x 32 steps with BOTH tiles in LDS (2 x 66 KB, single-buffered), 8 waves
 // splitting the contraction: 128 MFMAs per wave between barriers, three barriers and an un-overlapped staging phase per step,
 // half-filled third round of workgroups at the DistMult d = 512 / N = 10 000 shape -- 0.435 of the fp32-MFMA peak
 // (profiles/round3_cfg_S-DM_*).  Here the on-chip budget is spent differently:
@@ -21,7 +21,7 @@
 //     partners compute it: a + b == b + a bit for bit, so they hold the same G), then dC += G^T . Q over the 32 rows for
 //     its 256 columns = 128 MFMAs with G as the A operand straight from the epilogue's registers.
 //     256 MFMAs per wave and chunk between two barriers (the 32 x 32 cut: 128 between three).
-// G leaves for dq_kernel from the ks = 0 waves as 64 x 64 transposed blocks, the masked candidate rows `Cm` from the
+// G leaves for the dQ kernel from the ks = 0 waves as 64 x 64 transposed blocks, the masked candidate rows `Cm` from the
 // prologue's registers.
 //
 // WORK DISTRIBUTION.  The shapes these slot sizes come with have FEW candidate tiles (DistMult d = 512 on N = 10 000
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
 #pragma nounroll
     for (int seg = 0;; ++seg) {
     int tile, b_begin, b_end;
-    bool first_rows;                     // the segment holding a tile's first rows hands the masked candidate rows to dq_kernel
+    bool first_rows;                     // the segment holding a tile's first rows hands the masked candidate rows to the dQ kernel
     float *slab_rows = nullptr;          // partial candidate gradients go here (row n_local); nullptr: straight into dE
     if (sk) {
         if (u >= u_end) break;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
             const int k = KH * ks + 16 * r + 4 * s;
 #pragma unroll
             for (int e = 0; e < 4; ++e) breg[r][e] = (valid && k + e < d && (nib[r] >> e & 1u)) ? breg[r][e] * sc : 0.f;
-            if (cm) *reinterpret_cast<v4f *>(cm + 16 * r) = breg[r];            // masked rows for dq_kernel (padding rows: 0)
+            if (cm) *reinterpret_cast<v4f *>(cm + 16 * r) = breg[r];            // masked rows for the dQ kernel (padding rows: 0)
         }
     }
     for (int i = tid; i < pos_cached; i += TK_THREADS)
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
             if (b0 + 2 * BCK < b_end) fetch_chunk(b0 + 2 * BCK);
         }
         if (!a.loss_only) {
-            // ---- G blocks -> HBM for dq_kernel: Gt[T][J][n_local][b_local], 4 consecutive batch rows per lane ------
+            // ---- G blocks -> HBM for the dQ kernel: Gt[T][J][n_local][b_local], 4 consecutive batch rows per lane --
             if (ks == 0) {
                 const size_t blk_idx = (size_t)tile * (a.Bpad >> 6) + (b0 >> 6);
                 float *gdst = a.G + blk_idx * 4096 + (16 * blk + c) * 64 + 32 * ((b0 >> 5) & 1) + 4 * s;
@@ -583,8 +583,6 @@ static hipError_t launch64k_t(const FusedArgs &a, dim3 grid, hipStream_t st)
 hipError_t launch_fused64k(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st)
 {
     const dim3 grid(grid_x, grid_y);
-    if (a.KB == 16 && (mode == MODE_TRAIN_BCE || mode == MODE_TRAIN_KL))      // experiment (OKGE_TILE64K_D256=1): d <= 256 on this layout
-        return mode == MODE_TRAIN_KL ? launch64k_t<16, MODE_TRAIN_KL>(a, grid, st) : launch64k_t<16, MODE_TRAIN_BCE>(a, grid, st);
     if ((mode != MODE_TRAIN_BCE && mode != MODE_TRAIN_KL && mode != MODE_SCORE && mode != MODE_STATS && mode != MODE_COUNT) || a.KB != 32)
         return hipErrorInvalidValue;
     if (mode == MODE_SCORE) return launch64k_t<32, MODE_SCORE>(a, grid, st);

@@ -357,11 +357,11 @@ WIDE = [
 ]
 
 
-@pytest.mark.parametrize("tile_w", ["64", "32"])
-@pytest.mark.parametrize("case", WIDE, ids=[f"{c[0]}-d{c[1]}-b{c[3]}+{c[4]}-{c[6]}-p{c[7]}-s{c[8]}" for c in WIDE])
-def test_wide_slots(hp, monkeypatch, case, tile_w):
-    """slot sizes 257..512 on the register-tile kernel (tile_w 64) and on the round-1/2 32 x 32 cut it replaced (OKGE_TILE_W=32):
-    scores, loss, gradients against the oracle with Philox dropout on every stream"""
+# (the ids end in the candidate tile width, 64, as they did while the retired 32-wide cut ran the same cases)
+@pytest.mark.parametrize("case", WIDE, ids=[f"{c[0]}-d{c[1]}-b{c[3]}+{c[4]}-{c[6]}-p{c[7]}-s{c[8]}-64" for c in WIDE])
+def test_wide_slots(hp, monkeypatch, case):
+    """slot sizes 257..512 on the register-tile kernel: scores, loss, gradients against the oracle with Philox dropout on every
+    stream"""
     from open_knowledge_graph_embeddings_amd import hotpath as H
     scorer, d, n_ent, n_po, n_sp, n_cand, loss_kind, p, split = case
     E, R, z, cand, y = random_problem(900 + WIDE.index(case), n_ent, 13, d, n_po, n_sp, n_cand)
@@ -376,7 +376,6 @@ def test_wide_slots(hp, monkeypatch, case, tile_w):
         batch.drop_po_ent, batch.drop_sp_ent = H.DropoutSpec(p, sd, H.STREAM_PO_ENT, step), H.DropoutSpec(p, sd, H.STREAM_SP_ENT, step)
         batch.drop_po_rel, batch.drop_sp_rel = H.DropoutSpec(0.25, sd, H.STREAM_PO_REL, step), H.DropoutSpec(0.25, sd, H.STREAM_SP_REL, step)
     ref = oracle_step(scorer, E, R, z, cand, y, loss_kind, 0.0, **kw)
-    monkeypatch.setenv("OKGE_TILE_W", tile_w)
     if split != "0":
         monkeypatch.setenv("OKGE_B_SPLIT", split)
     Et, Rt = dev(E), dev(R)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""ms per okge_score_prefixes call at the DistMult d = 512 evaluation shape (B = 512, N = 14 541): the register-tile score sweep
-(default) against the 32 x 32 cut (OKGE_TILE_W=32)."""
+"""ms per okge_score_prefixes call at the DistMult d = 512 evaluation shape (B = 512, N = 14 541): the register-tile score
+sweep."""
 import os, sys, time, torch, numpy as np
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 from open_knowledge_graph_embeddings_amd import hotpath as H
@@ -14,4 +14,4 @@ out = torch.empty((B, (n_ent - 2 + 3) // 4 * 4), device="cuda")[:, :n_ent - 2]
 for _ in range(5): hp.score(E, R, "distmult", batch, out=out)
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(50): hp.score(E, R, "distmult", batch, out=out)
-torch.cuda.synchronize(); print("OKGE_TILE_W", os.environ.get("OKGE_TILE_W"), "score ms", (time.perf_counter() - t0) / 50 * 1e3)
+torch.cuda.synchronize(); print("score ms", (time.perf_counter() - t0) / 50 * 1e3)
