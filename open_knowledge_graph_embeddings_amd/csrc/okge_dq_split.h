@@ -1,0 +1,148 @@
+// Building blocks of dq8s_kernel (okge_dq_split.hip): fp32 dQ = G . C on the bf16 matrix cores from three bf16 planes per
+// operand.  In a header so that tools/ubench/mfma_bf16_split.hip times exactly the loop the kernel runs.
+//
+// Arithmetic.  x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (round to nearest even; both
+// subtractions are exact in fp32, so the three planes carry all 24 bits of every normal x whose lo is not subnormal).  Six of
+// the nine plane products are kept: hi.hi in the MAIN accumulator; lo.hi, hi.lo, mid.mid, mid.hi, hi.mid -- each at most 2^-8
+// of the first -- in a CORRECTION accumulator of their own, smallest first; the two are added once, when the slab is stored.
+// mid.lo, lo.mid, lo.lo (<= 2^-24 relative) are dropped.  Every bf16 x bf16 product is exact in fp32.  How the matrix core adds
+// (profiles/dq_split_ablation.md, step 0): C and the 32 products of a step are aligned to the largest exponent among them,
+// each cut off two bits below that number's fp32 ulp, summed, and the sum is rounded to nearest even; subnormals are kept.  A
+// term far below C therefore loses up to a quarter ulp of C on its own -- which is why the small products have an accumulator
+// of their own scale: only one such add per 32 candidates touches the large sum, and the result is at least as accurate as
+// one fp32 fma chain (tests/test_dq_split.py).
+//
+// LDS image of a 32-candidate sub-chunk (one K = 32 step of v_mfma_f32_16x16x32_bf16), per operand and plane:
+// [kg = 0..3][slot] cells of 16 bytes = 8 bf16 = the candidates 8 kg .. 8 kg + 7 of one output column (C) or batch row (G):
+// exactly what lane (slot & 15, kg) of the MFMA holds, read with one ds_read_b128.  A cell row is a multiple of 256 B, so the
+// ds_read_b128 lane groups (which mix two kg) cover 16 distinct 16-byte bank slots: conflict-free.  The transpose (global
+// memory has the candidate index slowest) happens in the staging pattern: a staging thread loads one float4 -- four
+// neighbouring columns -- from each of the 8 candidates of a kg, which leaves it with four cells.  The cell of column
+// 4 q + j goes to slot j * NQ + q (NQ = columns / 4), so that neighbouring lanes write neighbouring cells (ds_write_b128,
+// conflict-free); the MFMA's column index is the slot, and slot_to_col() undoes the permutation when the slab is stored.
+#pragma once
+#include "okge_device.h"
+
+namespace okge {
+
+typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
+
+struct Planes { v8bf hi, mid, lo; };
+
+// 8 floats -> three cells
+__device__ __forceinline__ Planes split3(const float (&x)[8])
+{
+    Planes p;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const __bf16 h = (__bf16)x[k];
+        const float r1 = x[k] - (float)h;
+        const __bf16 m = (__bf16)r1;
+        const float r2 = r1 - (float)m;
+        p.hi[k] = h; p.mid[k] = m; p.lo[k] = (__bf16)r2;
+    }
+    return p;
+}
+
+__device__ __forceinline__ v4f mfma_bf16(v8bf a, v8bf b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+template <int KB>
+struct DqSplit {
+    static_assert(KB % 4 <= 1, "column blocks are dealt to four wave columns, at most one of them one block longer");
+    static constexpr int NC = 32;                     // candidates per sub-chunk
+    static constexpr int NS = 16 * KB;                // column slots
+    static constexpr int NQ = 4 * KB;                 // float4 quads of a candidate row
+    static constexpr int C_CELLS = 4 * NS, G_CELLS = 4 * 64;
+    static constexpr int BUF_CELLS = 3 * (C_CELLS + G_CELLS);     // one sub-chunk: C planes, then G planes
+    static constexpr int C_TASKS = 4 * NQ;            // staging threads 0 .. C_TASKS - 1: (kg, quad) of the candidate rows
+    static constexpr int G_TID0 = 384;                // staging threads 384 .. 447 (wave 6): (kg, quad) of the G^T block
+    static constexpr int NBW = KB / 4 + (KB % 4 ? 1 : 0);         // most column blocks a wave takes
+    static constexpr size_t LDS_BYTES = (size_t)2 * BUF_CELLS * 16;
+    static constexpr int LDO = NS + 4;                // leading dimension of the fp32 output image the store goes through
+    static_assert(C_TASKS <= G_TID0, "staging roles overlap");
+    static_assert((size_t)64 * LDO * 4 <= LDS_BYTES, "the output image reuses the operand buffers");
+
+    __device__ static int slot_to_col(int slot) { return 4 * (slot % NQ) + slot / NQ; }
+
+    // the 8 float4 a staging thread holds of one sub-chunk
+    struct Stage { v4f v[8]; };
+
+    // sub-chunk sc (32 candidates) of batch block bblk: global -> registers
+    __device__ static void prefetch(Stage &st, const float *G, const float *Cm, int sc, int bblk, int nJ, int tid)
+    {
+        if (tid < C_TASKS) {
+            const int kg = tid / NQ, q = tid % NQ;
+            const float *src = Cm + ((size_t)sc * NC + 8 * kg) * NS + 4 * q;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) st.v[k] = *reinterpret_cast<const v4f *>(src + (size_t)k * NS);
+        } else if (tid >= G_TID0 && tid < G_TID0 + 64) {
+            const int kg = (tid - G_TID0) >> 4, q = tid & 15;
+            const float *src = G + ((size_t)(sc >> 1) * nJ + bblk) * 4096 + ((sc & 1) * NC + 8 * kg) * 64 + 4 * q;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) st.v[k] = *reinterpret_cast<const v4f *>(src + k * 64);
+        }
+    }
+
+    // registers -> the three planes of LDS buffer `buf`
+    __device__ static void park(const Stage &st, v8bf *buf, int tid)
+    {
+        v8bf *dst;
+        int stride, plane;
+        if (tid < C_TASKS) {
+            dst = buf + (tid / NQ) * NS + tid % NQ; stride = NQ; plane = C_CELLS;
+        } else if (tid >= G_TID0 && tid < G_TID0 + 64) {
+            dst = buf + 3 * C_CELLS + ((tid - G_TID0) >> 4) * 64 + (tid & 15); stride = 16; plane = G_CELLS;
+        } else {
+            return;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float x[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = st.v[k][j];
+            const Planes p = split3(x);
+            dst[j * stride] = p.hi;
+            dst[j * stride + plane] = p.mid;
+            dst[j * stride + 2 * plane] = p.lo;
+        }
+    }
+
+    // Wave w = (row half h = w >> 2, wave column j = w & 3): batch-row slots 32 h .. 32 h + 31 x column blocks blk0 .. blk0 +
+    // nblk - 1.  KB = 13: the long wave column (4 blocks) is j = h, so the two waves of a SIMD (w and w + 4) hold 4 + 3 or
+    // 3 + 3 blocks.
+    __device__ static int wave_nblk(int h, int j) { return KB / 4 + ((KB % 4) && j == h ? 1 : 0); }
+    __device__ static int wave_blk0(int h, int j) { return (KB / 4) * j + ((KB % 4) && j > h ? 1 : 0); }
+
+    // one sub-chunk: acc[r][nb] (r = 16-row block of the half) += G planes x C planes, six products
+    __device__ static void product(v4f (&acc)[2][NBW], v4f (&corr)[2][NBW], const v8bf *buf, int h, int blk0, int nblk, int lane)
+    {
+        const int c = lane & 15, kg = lane >> 4;
+        const v8bf *gi = buf + 3 * C_CELLS + kg * 64 + 32 * h + c;
+        const v8bf *ci = buf + kg * NS + 16 * blk0 + c;
+        Planes a[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            a[r].hi = gi[16 * r]; a[r].mid = gi[16 * r + G_CELLS]; a[r].lo = gi[16 * r + 2 * G_CELLS];
+        }
+#pragma unroll
+        for (int nb = 0; nb < NBW; ++nb) {
+            if (nb < nblk) {
+                Planes b;
+                b.hi = ci[16 * nb]; b.mid = ci[16 * nb + C_CELLS]; b.lo = ci[16 * nb + 2 * C_CELLS];
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    v4f s = corr[r][nb];
+                    s = mfma_bf16(a[r].lo, b.hi, s);
+                    s = mfma_bf16(a[r].hi, b.lo, s);
+                    s = mfma_bf16(a[r].mid, b.mid, s);
+                    s = mfma_bf16(a[r].mid, b.hi, s);
+                    s = mfma_bf16(a[r].hi, b.mid, s);
+                    corr[r][nb] = s;
+                    acc[r][nb] = mfma_bf16(a[r].hi, b.hi, acc[r][nb]);
+                }
+            }
+        }
+    }
+};
+
+}  // namespace okge

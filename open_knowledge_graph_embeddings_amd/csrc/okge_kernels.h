@@ -92,6 +92,7 @@ struct PrefixDev {
 size_t     fused_shmem_bytes(int LDK);
 hipError_t launch_fused(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st);
 hipError_t launch_dq(const DqArgs &a, int grid_x, hipStream_t st);
+hipError_t launch_dq8s(const DqArgs &a, int grid_x, hipStream_t st);   // slot sizes up to 208 (KB = 4, 8, 13): bf16 three-plane product
 hipError_t launch_fused64(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st);
 hipError_t launch_fused64k(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st);   // slot sizes above 256
 

@@ -10,12 +10,12 @@
 //     The training step (score -> loss -> dCand) is fused_tile64_kernel (okge_train64.hip) up to slot size 256 and
 //     fused_tile64k_kernel (okge_train64k.hip) above.
 //
-//   dq8_kernel<KB> (slot sizes up to 208), dq8k_kernel<KB> (209 .. 512)
+//   dq8k_kernel<KB> (slot sizes 209 .. 512; up to 208: dq8s_kernel, okge_dq_split.hip)
 //     dQ = G . C : one 8-wave workgroup per (64-row batch block, candidate range); partial slabs are summed by
 //     prefix_backward_kernel (okge_misc.hip).  G arrives as 64x64 transposed blocks G^T[n][b] (16 KB each,
 //     written by the training tile kernel straight from its registers) and is copied to LDS as is.
-//     (The 4-wave, single-buffered dQ kernel these replaced was retired; its measurements are in
-//     profiles/round{2,3,4}_ablation.md.)
+//     (The 4-wave, single-buffered dQ kernel and the fp32-MFMA dq8_kernel for slot sizes up to 208 were retired; their
+//     measurements are in profiles/round{2,3,4}_ablation.md and profiles/dq_split_ablation.md.)
 //
 // KB = padded slot size / 16 is a compile-time constant so every operand read is unconditional.
 //
@@ -409,140 +409,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
 constexpr int LDGT = 68;   // G^T tile leading dimension (16-byte aligned rows; the A operand is one ds_read_b32 per 13 MFMAs,
                            // so its 2-way conflict between slots 16 rows apart is irrelevant)
 
-// ---- dQ = G . C, eight waves: the contraction of a 64-candidate chunk split over two wave groups ---------------------
-// Slot sizes up to 208 (two tile pairs fit the LDS).  One 8-wave workgroup per CU takes 64 batch rows x a candidate range
-// -> one slab: a range twice as long as two co-resident 4-wave workgroups would take, so half the slabs (13.6 instead of
-// 27 MB written here and read back by the prefix backward at S-FB), half the first-chunk burst at kernel start, prologue /
-// epilogue amortised over twice the chunks -- at the same two waves per SIMD.  Wave (wq = w & 3, kh = w >> 2):
-// batch rows 16wq.., contraction steps 8kh .. 8kh+7 of every slot (candidates 16s + 8kh + t: slots stay 16 rows apart, the
-// B operand reads keep their conflict-free bank pattern); the two halves are added through LDS before the slab store.
-// Double-buffered: chunk ch+1 is parked in the second pair while chunk ch is being multiplied -- ONE barrier per chunk and
-// no staging phase in which all eight waves write LDS and request the next chunk while the MFMA pipes idle.  The two waves
-// of a SIMD take turns: group kh = 0 parks before its MFMAs, group kh = 1 after.
-template <int KB>
-__global__ __launch_bounds__(512, 2) void dq8_kernel(const DqArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int LDK = lds_ld(16 * KB);
-    constexpr int NTHR = 512, QG = 16;                // staging: 16 column groups per row, 32 rows per pass
-    constexpr int KQ = KB / 4, KR = KB % 4;
-    constexpr int NO = 2 * KB, NOIT = (NO + QG - 1) / QG;
-    constexpr int PAIR = NT * LDK + NT * LDGT;        // floats of one (candidate tile, G^T tile) pair
-    float *Cs = reinterpret_cast<float *>(smem);      // [NT][LDK]   masked candidate rows (end: the kh = 1 partial sums)
-    float *Gt = Cs + NT * LDK;                        // [NT (n)][LDGT] : G^T tile, 64 batch rows wide
-
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, s = lane >> 4;
-    const int wq = w & 3, kh = w >> 2;
-    const int split = blockIdx.x % a.nsplit, bblk = blockIdx.x / a.nsplit;
-    const int b0 = bblk * BC;
-    const int nJ = a.Bpad / BC;
-    const int nchunks = (a.N + NT - 1) / NT;
-    const int ch_lo = (int)((int64_t)split * nchunks / a.nsplit);
-    const int ch_hi = (int)((int64_t)(split + 1) * nchunks / a.nsplit);
-
-    v4f acc[KB];                                      // dQ[b = b0 + 16wq + 4s + i][k = grad_col(kbi, c)], this wave's candidates
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) acc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
-
-    // register-staged prefetch of the next chunk: 2 float4 of the G^T block, 2 x NOIT x 2 float4 of the candidate tile
-    v4f gv[2], cv[4 * NOIT];
-    auto prefetch = [&](int ch) {
-        const float *g_blk = a.G + ((size_t)ch * nJ + bblk) * 4096;
-        const float *cm = a.Cm + (size_t)ch * NT * (16 * KB);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) gv[it] = *reinterpret_cast<const v4f *>(g_blk + (size_t)(tid + it * NTHR) * 4);
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const int r = tid / QG + 32 * pass;
-#pragma unroll
-            for (int it = 0; it < NOIT; ++it) {
-                const int o = min(tid % QG + QG * it, NO - 1);   // clamped: surplus lanes reload the last octet
-                cv[(2 * pass) * NOIT + it] = *reinterpret_cast<const v4f *>(cm + (size_t)r * (16 * KB) + 8 * o);
-                cv[(2 * pass + 1) * NOIT + it] = *reinterpret_cast<const v4f *>(cm + (size_t)r * (16 * KB) + 8 * o + 4);
-            }
-        }
-    };
-    // registers -> the LDS pair `buf` (0 / 1)
-    auto park = [&](int buf) {
-        float *cs = Cs + buf * PAIR, *gt = Gt + buf * PAIR;
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int f = tid + it * NTHR;
-            *reinterpret_cast<v4f *>(gt + (f >> 4) * LDGT + 4 * (f & 15)) = gv[it];
-        }
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const int r = tid / QG + 32 * pass;
-#pragma unroll
-            for (int it = 0; it < NOIT; ++it) {
-                const int o = tid % QG + QG * it;
-                if (o < NO) {
-                    *reinterpret_cast<v4f *>(cs + r * LDK + 8 * o) = cv[(2 * pass) * NOIT + it];
-                    *reinterpret_cast<v4f *>(cs + r * LDK + 8 * o + 4) = cv[(2 * pass + 1) * NOIT + it];
-                }
-            }
-        }
-    };
-    // A[i = b][slot s, step t] = G^T[n = 16s + t][b = 16wq + c] ; B[slot][k] = C[n = 16s + t][k]
-    auto product = [&](int buf) {
-        const float *cs = Cs + buf * PAIR, *gt = Gt + buf * PAIR;
-        if (kh == 0) grad_product<KB, false, LDK, 0, 8>(acc, gt + 16 * s * LDGT + 16 * wq + c, LDGT, cs + 16 * s * LDK, c);
-        else         grad_product<KB, false, LDK, 8, 16>(acc, gt + 16 * s * LDGT + 16 * wq + c, LDGT, cs + 16 * s * LDK, c);
-    };
-    if (ch_lo < ch_hi) {
-        prefetch(ch_lo);
-        park(0);
-        if (ch_lo + 1 < ch_hi) prefetch(ch_lo + 1);
-    }
-    for (int ch = ch_lo; ch < ch_hi; ++ch) {
-        const int buf = (ch - ch_lo) & 1;
-        __syncthreads();                           // chunk ch is parked; the other pair's readers (chunk ch - 1) are done
-        const bool more = ch + 1 < ch_hi;
-        if (kh == 0 && more) {                     // this wave group parks its share of chunk ch + 1 first ...
-            park(buf ^ 1);
-            if (ch + 2 < ch_hi) prefetch(ch + 2);
-        }
-        product(buf);
-        if (kh == 1 && more) {                     // ... the other one after its MFMAs: a SIMD's two waves take turns
-            park(buf ^ 1);
-            if (ch + 2 < ch_hi) prefetch(ch + 2);
-        }
-    }
-    __syncthreads();                               // the pairs are free: pair 0's candidate tile takes the kh = 1 partial sums
-    // the two contraction halves: kh = 1 parks its partial rows in LDS, kh = 0 adds them and stores the slab rows
-    if (kh == 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float *dst = Cs + (16 * wq + 4 * s + i) * LDK;
-#pragma unroll
-            for (int kq = 0; kq < KQ; ++kq)
-                *reinterpret_cast<v4f *>(dst + 64 * kq + 4 * c) = (v4f){acc[4 * kq][i], acc[4 * kq + 1][i], acc[4 * kq + 2][i], acc[4 * kq + 3][i]};
-#pragma unroll
-            for (int r = 0; r < KR; ++r) dst[64 * KQ + 16 * r + c] = acc[4 * KQ + r][i];
-        }
-    }
-    __syncthreads();
-    if (kh == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float *src = Cs + (16 * wq + 4 * s + i) * LDK;
-            float *dst = a.slab + ((size_t)split * a.Bpad + b0 + 16 * wq + 4 * s + i) * a.ldq;
-#pragma unroll
-            for (int kq = 0; kq < KQ; ++kq) {
-                v4f v = (v4f){acc[4 * kq][i], acc[4 * kq + 1][i], acc[4 * kq + 2][i], acc[4 * kq + 3][i]} +
-                        *reinterpret_cast<const v4f *>(src + 64 * kq + 4 * c);
-                if (a.accumulate) v += *reinterpret_cast<const v4f *>(dst + 64 * kq + 4 * c);
-                *reinterpret_cast<v4f *>(dst + 64 * kq + 4 * c) = v;
-            }
-#pragma unroll
-            for (int r = 0; r < KR; ++r) {
-                const float v = acc[4 * KQ + r][i] + src[64 * KQ + 16 * r + c];
-                dst[64 * KQ + 16 * r + c] = a.accumulate ? dst[64 * KQ + 16 * r + c] + v : v;
-            }
-        }
-    }
-}
-
 // ---- dQ = G . C for slot sizes above 208 (KB = 16, 32): 32-candidate chunks, double-buffered ---------------------------------
 // Why 32-candidate chunks: a 64-candidate tile at KB = 32 (132 KB) + its G^T block fill the LDS single-buffered -- per chunk
 // every wave parks 16 float4, the workgroup passes two barriers and waits for the next chunk's loads while the MFMA pipes
@@ -686,17 +552,6 @@ hipError_t launch_fused(int mode, const FusedArgs &a, int grid_x, int grid_y, hi
 }
 
 template <int KB>
-static hipError_t launch_dq8_t(const DqArgs &a, int grid_x, hipStream_t st)
-{
-    auto k = dq8_kernel<KB>;
-    const size_t shmem = (size_t)2 * (NT * lds_ld(16 * KB) + NT * LDGT) * sizeof(float);     // two LDS tile pairs
-    static LdsOptIn lds_opt_in;
-    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), shmem); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid_x), dim3(512), shmem, st, a);
-    return hipGetLastError();
-}
-
-template <int KB>
 static hipError_t launch_dq8k_t(const DqArgs &a, int grid_x, hipStream_t st)
 {
     auto k = dq8k_kernel<KB>;
@@ -710,9 +565,7 @@ static hipError_t launch_dq8k_t(const DqArgs &a, int grid_x, hipStream_t st)
 hipError_t launch_dq(const DqArgs &a, int grid_x, hipStream_t st)
 {
     switch (a.KB) {
-        case 4:  return launch_dq8_t<4>(a, grid_x, st);
-        case 8:  return launch_dq8_t<8>(a, grid_x, st);
-        case 13: return launch_dq8_t<13>(a, grid_x, st);
+        case 4: case 8: case 13: return launch_dq8s(a, grid_x, st);   // okge_dq_split.hip
         case 16: return launch_dq8k_t<16>(a, grid_x, st);
         case 32: return launch_dq8k_t<32>(a, grid_x, st);
         default: return hipErrorInvalidValue;

@@ -1,0 +1,172 @@
+// Microbenchmark for the three-plane bf16 dQ kernel (csrc/okge_dq_split.{h,hip}); results: profiles/dq_split_ablation.md.
+//  (a) How does v_mfma_f32_16x16x32_bf16 round?  Every A row is ak[0..31] and every B column is bk[0..31], so each output
+//      element is C + sum_k ak[k] bk[k] whatever the lane <-> k map; operands are chosen so that round-to-nearest, truncation,
+//      product-by-product accumulation and a wider internal sum give different fp32 bits.  Printed as hex.
+//  (b) Cycles per 32-candidate sub-chunk of the kernel's own loop at KB = 13, one 512-thread workgroup per CU:
+//      bare MFMAs on register operands / operands read from LDS (DqSplit::product) / product + plane split + park + barrier
+//      (the kernel's loop without its global loads).  The matrix-core floor is 78 MFMAs per SIMD x 16 cycles = 1248.
+// Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -o mfma_bf16_split.bin mfma_bf16_split.hip
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+#include "../../open_knowledge_graph_embeddings_amd/csrc/okge_dq_split.h"
+using namespace okge;
+
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
+
+// ---- (a) ------------------------------------------------------------------------------------------------------------
+struct Probe { const char *what; float c; float ak[32], bk[32]; };
+
+__global__ __launch_bounds__(64) void probe_kernel(const float *ak, const float *bk, const float *c0, float *out, int n)
+{
+    const int lane = threadIdx.x, kg = lane >> 4;
+    for (int p = 0; p < n; ++p) {
+        v8bf a, b;
+        for (int j = 0; j < 8; ++j) { a[j] = (__bf16)ak[32 * p + 8 * kg + j]; b[j] = (__bf16)bk[32 * p + 8 * kg + j]; }
+        v4f c = (v4f){c0[p], c0[p], c0[p], c0[p]};
+        c = mfma_bf16(a, b, c);
+        if (lane == 0) out[p] = c[0];
+        if (lane == 37) out[n + p] = c[3];            // another element of the tile: must be the same number
+    }
+}
+
+static unsigned bits(float f) { unsigned u; memcpy(&u, &f, 4); return u; }
+
+// ---- (b) ------------------------------------------------------------------------------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(512, 2) void loop_kernel(const float *src, float *out, unsigned long long *cyc, int iters)
+{
+    using S = DqSplit<13>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    v8bf *lds = reinterpret_cast<v8bf *>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int h = w >> 2, blk0 = S::wave_blk0(h, w & 3), nblk = S::wave_nblk(h, w & 3);
+    v4f acc[2][S::NBW], corr[2][S::NBW];
+    for (int r = 0; r < 2; ++r)
+        for (int nb = 0; nb < S::NBW; ++nb) acc[r][nb] = corr[r][nb] = (v4f){0.f, 0.f, 0.f, 0.f};
+    typename S::Stage st;
+    for (int k = 0; k < 8; ++k) st.v[k] = *reinterpret_cast<const v4f *>(src + (size_t)(tid * 8 + k) * 4);
+    S::park(st, lds, tid);
+    S::park(st, lds + S::BUF_CELLS, tid);
+    __syncthreads();
+    Planes ra, rb;
+    ra.hi = lds[lane]; ra.mid = lds[lane + 64]; ra.lo = lds[lane + 128];
+    rb.hi = lds[lane + 192]; rb.mid = lds[lane + 256]; rb.lo = lds[lane + 320];
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int it = 0; it < iters; ++it) {
+        const int buf = it & 1;
+        if (MODE == 0) {
+#pragma unroll
+            for (int nb = 0; nb < S::NBW; ++nb)
+                if (nb < nblk)
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        v4f s = corr[r][nb];
+                        s = mfma_bf16(ra.lo, rb.hi, s); s = mfma_bf16(ra.hi, rb.lo, s); s = mfma_bf16(ra.mid, rb.mid, s);
+                        s = mfma_bf16(ra.mid, rb.hi, s); s = mfma_bf16(ra.hi, rb.mid, s);
+                        corr[r][nb] = s;
+                        acc[r][nb] = mfma_bf16(ra.hi, rb.hi, acc[r][nb]);
+                    }
+        } else if (MODE == 1) {
+            S::product(acc, corr, lds + buf * S::BUF_CELLS, h, blk0, nblk, lane);
+        } else {
+            __syncthreads();
+            // the staged values change every iteration (as they do in the kernel), so the split cannot be hoisted out of the loop
+            for (int k = 0; k < 8; ++k) st.v[k] += (v4f){1e-3f, 1e-3f, 1e-3f, 1e-3f};
+            if (w < 4) S::park(st, lds + (buf ^ 1) * S::BUF_CELLS, tid);
+            S::product(acc, corr, lds + buf * S::BUF_CELLS, h, blk0, nblk, lane);
+            if (w >= 4) S::park(st, lds + (buf ^ 1) * S::BUF_CELLS, tid);
+        }
+    }
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    float s = 0.f;
+    for (int r = 0; r < 2; ++r)
+        for (int nb = 0; nb < S::NBW; ++nb) for (int i = 0; i < 4; ++i) s += acc[r][nb][i] + corr[r][nb][i];
+    out[blockIdx.x * 512 + tid] = s;
+    if (lane == 0) cyc[blockIdx.x * 8 + w] = t1 - t0;
+}
+
+template <int MODE>
+static int run_loop(const char *name, const float *src, float *out, unsigned long long *cyc, int blocks, int iters)
+{
+    auto k = loop_kernel<MODE>;
+    const size_t shmem = DqSplit<13>::LDS_BYTES;
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(512), shmem, 0, src, out, cyc, iters);   // warm-up
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(e0));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(512), shmem, 0, src, out, cyc, iters);
+    CK(hipEventRecord(e1));
+    CK(hipDeviceSynchronize());
+    float ms = 0.f;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    std::vector<unsigned long long> hc(blocks * 8);
+    CK(hipMemcpy(hc.data(), cyc, hc.size() * 8, hipMemcpyDeviceToHost));
+    unsigned long long mx = 0; double mean = 0;
+    for (auto c : hc) { mx = c > mx ? c : mx; mean += (double)c / hc.size(); }
+    // s_memtime ticks at a fixed 100 MHz-class clock on this part, so the event time is the trustworthy figure; both are printed
+    const double flop = 12.0 * 64 * 208 * 32 * (double)iters * blocks;
+    printf("%-44s %8.3f ms  %7.1f ns/sub-chunk  %6.1f TFLOP/s executed (bf16)   s_memtime ticks/iter: mean %.1f max %.1f\n", name, ms,
+           ms * 1e6 / iters, flop / (ms * 1e-3) * 1e-12, mean / iters, (double)mx / iters);
+    return 0;
+}
+
+int main()
+{
+    // (a)
+    std::vector<Probe> P;
+    auto add = [&](const char *what, float c) { Probe p{}; p.what = what; p.c = c; P.push_back(p); return &P.back(); };
+    const float u = ldexpf(1.f, -24);                 // half an ulp of 1.0
+    Probe *p;
+    p = add("C=1 + one product 1.0*2^-24 (tie)          RN-even 3f800000  trunc 3f800000", 1.f); p->ak[0] = 1.f; p->bk[0] = u;
+    p = add("C=1 + one product 1.5*2^-24                RN 3f800001  trunc 3f800000", 1.f); p->ak[0] = 1.5f; p->bk[0] = u;
+    p = add("C=1 + one product 3*2^-24 (tie)            RN-even 3f800002  trunc 3f800001", 1.f); p->ak[0] = 3.f; p->bk[0] = u;
+    p = add("C=1 + two products 0.75*2^-24              summed-then-RN 3f800001  one-by-one-RN 3f800000  trunc 3f800000", 1.f);
+    p->ak[0] = p->ak[9] = 0.75f; p->bk[0] = p->bk[9] = u;
+    p = add("C=1 + 32 products of 2^-25                 wide sum 3f800008  one-by-one (any rounding) 3f800000", 1.f);
+    for (int k = 0; k < 32; ++k) { p->ak[k] = 1.f; p->bk[k] = ldexpf(1.f, -25); }
+    p = add("C=1 - one product 2^-26                    RN 3f800000  trunc-to-zero/floor 3f7fffff", 1.f); p->ak[0] = -1.f; p->bk[0] = ldexpf(1.f, -26);
+    p = add("C=-1 + one product 2^-26                   RN bf800000  to-zero bf7fffff  floor bf800000", -1.f); p->ak[0] = 1.f; p->bk[0] = ldexpf(1.f, -26);
+    p = add("C=0, products 1.0 and 1.5*2^-24            RN 3f800001  trunc 3f800000", 0.f); p->ak[0] = 1.f; p->bk[0] = 1.f; p->ak[20] = 1.5f; p->bk[20] = u;
+    p = add("C=0, products 2^10, -2^10, 2^-20           exact 35800000  (0 = the small product fell off the internal sum)", 0.f);
+    p->ak[0] = 1024.f; p->bk[0] = 1.f; p->ak[1] = -1024.f; p->bk[1] = 1.f; p->ak[2] = 1.f; p->bk[2] = ldexpf(1.f, -20);
+    p = add("C=0, products 2^10, -2^10, 2^-40           exact 2b800000", 0.f);
+    p->ak[0] = 1024.f; p->bk[0] = 1.f; p->ak[1] = -1024.f; p->bk[1] = 1.f; p->ak[2] = 1.f; p->bk[2] = ldexpf(1.f, -40);
+    p = add("C=2^10, products -2^10, 2^-20              exact 35800000", 1024.f); p->ak[0] = -1024.f; p->bk[0] = 1.f; p->ak[2] = 1.f; p->bk[2] = ldexpf(1.f, -20);
+    p = add("C=0, one product 1e-19 * 1 (normal bf16)   kept: 2008xxxx-ish, flushed: 00000000", 0.f); p->ak[0] = 1e-19f; p->bk[0] = 1.f;
+    p = add("C=0, one product 1e-19 * 1e-19             (1e-38, a normal fp32 just above the subnormals)", 0.f); p->ak[0] = 1e-19f; p->bk[0] = 1e-19f;
+    p = add("C=0, one product 2^-70 * 2^-70 = 2^-140    subnormal result kept 00000200, flushed 00000000", 0.f); p->ak[0] = ldexpf(1.f, -70); p->bk[0] = ldexpf(1.f, -70);
+    p = add("C=0, one product 2^-130 * 2^10             subnormal bf16 input kept 03800000 (2^-120), flushed 00000000", 0.f); p->ak[0] = ldexpf(1.f, -130); p->bk[0] = 1024.f;
+    p = add("C=2^-130 (subnormal) + 0                   kept 00080000, flushed 00000000", ldexpf(1.f, -130));
+    const int n = (int)P.size();
+    std::vector<float> hak(32 * n), hbk(32 * n), hc(n), hout(2 * n);
+    for (int i = 0; i < n; ++i) { memcpy(&hak[32 * i], P[i].ak, 128); memcpy(&hbk[32 * i], P[i].bk, 128); hc[i] = P[i].c; }
+    float *dak, *dbk, *dc, *dout;
+    CK(hipMalloc(&dak, 128 * n)); CK(hipMalloc(&dbk, 128 * n)); CK(hipMalloc(&dc, 4 * n)); CK(hipMalloc(&dout, 8 * n));
+    CK(hipMemcpy(dak, hak.data(), 128 * n, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dbk, hbk.data(), 128 * n, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dc, hc.data(), 4 * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(probe_kernel, dim3(1), dim3(64), 0, 0, dak, dbk, dc, dout, n);
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(hout.data(), dout, 8 * n, hipMemcpyDeviceToHost));
+    printf("== (a) v_mfma_f32_16x16x32_bf16 rounding probes: got (lane 0 elt 0 / lane 37 elt 3)\n");
+    for (int i = 0; i < n; ++i) printf("  %08x / %08x  % .9e   %s\n", bits(hout[i]), bits(hout[n + i]), hout[i], P[i].what);
+
+    // (b)
+    const int blocks = 256, iters = 4000;
+    std::vector<float> hs(512 * 32);
+    unsigned x = 12345u;
+    for (auto &v : hs) { x = x * 1664525u + 1013904223u; v = ((int)(x >> 8) - (1 << 23)) * (1.f / (1 << 23)); }
+    float *src, *out; unsigned long long *cyc;
+    CK(hipMalloc(&src, hs.size() * 4)); CK(hipMalloc(&out, 4 * 512 * blocks)); CK(hipMalloc(&cyc, 8 * 8 * blocks));
+    CK(hipMemcpy(src, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+    printf("== (b) KB = 13 loop, %d workgroups x 512 threads, %d sub-chunks each; floor 1248 cycles per sub-chunk and SIMD\n", blocks, iters);
+    if (run_loop<0>("bare MFMAs, register operands", src, out, cyc, blocks, iters)) return 1;
+    if (run_loop<1>("operands from LDS (product)", src, out, cyc, blocks, iters)) return 1;
+    if (run_loop<2>("product + split + park + barrier", src, out, cyc, blocks, iters)) return 1;
+    return 0;
+}
