@@ -345,6 +345,43 @@ int okge_lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *call
                              float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh, float *d_bn_weight, float *d_bn_bias,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Tucker3 / RESCAL scorer with a projected relation --------------------------------------------------------
+ * Replaces, for LookupTucker3RelationModel, encode_rel's Linear (model.py:402-408, :482-490: M_b = reshape(W rho_b, (d, d)),
+ * W = relation_projection.0.weight (d^2, r_e) row-major) together with the two bmm of RescalRelationScorer._score
+ * (model.py:160-166) and autograd's walk back through them.  M (B, d^2) is never written to memory.
+ * Rows are the MASKED prefix rows okge_encode_rows made: ent_rows[B][ld_ent] (po objects first, then sp subjects),
+ * rel_rows[B][ld_rel] (rows of the (|R|, r_e) relation table).  1 <= d <= 256, 1 <= r_e <= 256 (else OKGE_ERR_UNSUPPORTED).
+ *   okge_tucker3_fold    Q[b] = M_b e_b (po rows) / e_b^T M_b (sp rows), written as a query block: okge_query_rows(B) rows of
+ *                        ldq = okge_query_ld(d) floats, padding zero -- what okge_train_tiles / okge_score_queries /
+ *                        okge_row_logsumexp / okge_evaluate_fused_shard take as `Q`.
+ *   okge_tucker3_backward  from dQ[.][ldq] (okge_train_tiles' output): d_ent_rows[B][d] = M_b^T dq_b resp. M_b dq_b,
+ *                        d_rel_rows[B][r_e] = W^T vec(dM_b), dW[d^2][r_e] (+)= sum_b vec(dM_b) rho_b^T with dM_b = dq_b e_b^T (po) /
+ *                        e_b dq_b^T (sp).  dW is STORED with OKGE_TRAIN_GRADS_ZERO in flags, accumulated otherwise; any of the
+ *                        three outputs may be NULL.  The row gradients then go through okge_scatter_rows.
+ *   okge_tucker3_score_triples  out[b] = s_b^T M_b o_b of encoded rows: triple_score / forward(subj, rel, obj) (model.py:144-145, :167-171).
+ * Exact-fp32 MFMA, sums nested as the reference nests them, no float atomics: bit-reproducible.
+ * Workspace: okge_tucker3_workspace_bytes(rows, d, r_e) (0 outside the supported range), 16-byte aligned. */
+size_t okge_tucker3_workspace_bytes(int32_t B, int32_t d, int32_t r_e);
+int okge_tucker3_fold(const float *W, int32_t d, int32_t r_e, const float *ent_rows, int64_t ld_ent, const float *rel_rows,
+                      int64_t ld_rel, int32_t n_po, int32_t n_sp, float *Q, int64_t ldq, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int okge_tucker3_backward(const float *W, int32_t d, int32_t r_e, const float *ent_rows, int64_t ld_ent, const float *rel_rows,
+                          int64_t ld_rel, const float *dQ, int64_t ldq, int32_t n_po, int32_t n_sp, int32_t flags, float *d_ent_rows,
+                          float *d_rel_rows, float *dW, void *workspace, size_t workspace_bytes, void *stream);
+int okge_tucker3_score_triples(const float *W, int32_t d, int32_t r_e, const float *subj, int64_t ld_subj, const float *rel,
+                               int64_t ld_rel, const float *obj, int64_t ld_obj, int32_t n, float *out, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+/* The plugin methods on MATERIALISED relation matrices (RescalRelationScorer._score / triple_score on the (n, d^2) rows encode_rel
+ * returns, model.py:147-173; off the training path -- the rows themselves are rel_rows . W^T, which okge_score_queries forms with W
+ * as the candidate table): M[n][ld_m], M_b[i][j] at i d + j; 1 <= d <= 256.
+ *   okge_tucker3_apply  transpose = 0: out[b] = x_b^T M_b (subj.bmm(rel), the sp prefix);  1: out[b] = M_b x_b (rel.bmm(obj), the po prefix)
+ *   okge_tucker3_outer  out[b][i d + j] = u_b[i] v_b[j]: the gradient of M_b under either product (autograd through bmm) */
+int okge_tucker3_apply(const float *M, int64_t ld_m, const float *x, int64_t ld_x, int32_t n, int32_t d, int32_t transpose, float *out,
+                       int64_t ld_out, void *stream);
+int okge_tucker3_outer(const float *u, int64_t ld_u, const float *v, int64_t ld_v, int32_t n, int32_t d, float *out, int64_t ld_out,
+                       void *stream);
+
 /* ---- gradients of the plugin methods' scores (a caller's own loss) ----------------------------------------
  * Backward of sp_prefix_score / po_prefix_score / _score(prefix=True) (model.py:52-77, :198-229, :268-274) for a caller that
  * holds the dense (b, n) gradient g of the scores (the reference's autograd walks its four / one matrix products backwards):

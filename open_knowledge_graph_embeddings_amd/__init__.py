@@ -7,7 +7,7 @@ HIP kernels for gfx950 behind the C ABI declared in ``include/okge.h``.
 from . import _native  # noqa: F401
 from ._native import OkgeError, build_native  # noqa: F401
 
-from . import model, token_pooled, lstm  # noqa: F401,E402  (token_pooled / lstm register their classes in model.Models)
+from . import model, token_pooled, lstm, tucker3  # noqa: F401,E402  (token_pooled / lstm / tucker3 register their classes in model.Models)
 from . import optim  # noqa: F401,E402  (registers OkgeAdagrad in torch.optim for the reference's OptimRegime)
 
 __all__ = ["OkgeError", "build_native"]

@@ -945,6 +945,104 @@ int okge_scatter_rows(const float *rows, int64_t ld, const int32_t *ids, const i
     return OKGE_OK;
 }
 
+// ---- Tucker3 / RESCAL scorer (okge_tucker3.hip) -------------------------------------------------------------------
+// workspace: [rows x d scratch of score_triples][slabs of the split products]
+static size_t tucker3_scratch_bytes(int32_t B, int32_t d) { return align_up((size_t)B * d * sizeof(float), 256); }
+
+static int check_tucker3(const float *W, int32_t d, int32_t r, int32_t B, const void *workspace, size_t workspace_bytes)
+{
+    if (!W || d <= 0 || r <= 0 || B <= 0) return fail(OKGE_ERR_INVALID, "bad tucker3 arguments (W, d, r_e, rows)");
+    if (d > 256 || r > 256) return fail(OKGE_ERR_UNSUPPORTED, "tucker3: slot sizes / relation sizes above 256 are not supported");
+    if (!workspace || workspace_bytes < okge_tucker3_workspace_bytes(B, d, r) || reinterpret_cast<uintptr_t>(workspace) % 16)
+        return fail(OKGE_ERR_WORKSPACE, "workspace too small or unaligned (okge_tucker3_workspace_bytes)");
+    return OKGE_OK;
+}
+
+size_t okge_tucker3_workspace_bytes(int32_t B, int32_t d, int32_t r_e)
+{
+    if (B <= 0 || d <= 0 || r_e <= 0 || d > 256 || r_e > 256) return 0;
+    return tucker3_scratch_bytes(B, d) + tucker3_workspace_bytes(B, d, r_e, cu_count());
+}
+
+int okge_tucker3_fold(const float *W, int32_t d, int32_t r_e, const float *ent_rows, int64_t ld_ent, const float *rel_rows,
+                      int64_t ld_rel, int32_t n_po, int32_t n_sp, float *Q, int64_t ldq, void *workspace, size_t workspace_bytes,
+                      void *stream)
+{
+    if (n_po < 0 || n_sp < 0) return fail(OKGE_ERR_INVALID, "bad tucker3 arguments (row counts)");
+    const int B = n_po + n_sp;
+    if (int rc = check_tucker3(W, d, r_e, B, workspace, workspace_bytes)) return rc;
+    if (!ent_rows || !rel_rows || !Q || ld_ent < d || ld_rel < r_e || ldq != okge_query_ld(d))
+        return fail(OKGE_ERR_INVALID, "bad tucker3_fold arguments (rows, query block: ldq = okge_query_ld(d))");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float *slab = reinterpret_cast<float *>(static_cast<char *>(workspace) + tucker3_scratch_bytes(B, d));
+    ScopedTimer tm("tucker3_fold", st);
+    hipError_t e = launch_tucker3_fold(W, ent_rows, ld_ent, rel_rows, ld_rel, n_po, B, d, r_e, 0, Q, okge_query_rows(B), ldq, (int)ldq, slab,
+                                       cu_count(), st);
+    if (e != hipSuccess) return fail_hip(e, "tucker3_fold");
+    return OKGE_OK;
+}
+
+int okge_tucker3_backward(const float *W, int32_t d, int32_t r_e, const float *ent_rows, int64_t ld_ent, const float *rel_rows,
+                          int64_t ld_rel, const float *dQ, int64_t ldq, int32_t n_po, int32_t n_sp, int32_t flags, float *d_ent_rows,
+                          float *d_rel_rows, float *dW, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (n_po < 0 || n_sp < 0) return fail(OKGE_ERR_INVALID, "bad tucker3 arguments (row counts)");
+    const int B = n_po + n_sp;
+    if (int rc = check_tucker3(W, d, r_e, B, workspace, workspace_bytes)) return rc;
+    if (!ent_rows || !rel_rows || !dQ || ld_ent < d || ld_rel < r_e || ldq < d)
+        return fail(OKGE_ERR_INVALID, "bad tucker3_backward arguments (rows, dQ)");
+    if (flags & ~OKGE_TRAIN_GRADS_ZERO) return fail(OKGE_ERR_INVALID, "tucker3_backward takes OKGE_TRAIN_GRADS_ZERO only");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float *slab = reinterpret_cast<float *>(static_cast<char *>(workspace) + tucker3_scratch_bytes(B, d));
+    ScopedTimer tm("tucker3_backward", st);
+    hipError_t e = launch_tucker3_backward(W, ent_rows, ld_ent, rel_rows, ld_rel, dQ, ldq, n_po, B, d, r_e,
+                                           (flags & OKGE_TRAIN_GRADS_ZERO) ? 1 : 0, d_ent_rows, d_rel_rows, dW, slab, cu_count(), st);
+    if (e != hipSuccess) return fail_hip(e, "tucker3_backward");
+    return OKGE_OK;
+}
+
+int okge_tucker3_score_triples(const float *W, int32_t d, int32_t r_e, const float *subj, int64_t ld_subj, const float *rel,
+                               int64_t ld_rel, const float *obj, int64_t ld_obj, int32_t n, float *out, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_tucker3(W, d, r_e, n, workspace, workspace_bytes)) return rc;
+    if (!subj || !rel || !obj || !out || ld_subj < d || ld_rel < r_e || ld_obj < d)
+        return fail(OKGE_ERR_INVALID, "bad tucker3_score_triples arguments");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float *q = static_cast<float *>(workspace);
+    float *slab = reinterpret_cast<float *>(static_cast<char *>(workspace) + tucker3_scratch_bytes(n, d));
+    ScopedTimer tm("tucker3_triples", st);
+    hipError_t e = launch_tucker3_triples(W, subj, ld_subj, rel, ld_rel, obj, ld_obj, n, d, r_e, q, slab, out, cu_count(), st);
+    if (e != hipSuccess) return fail_hip(e, "tucker3_score_triples");
+    return OKGE_OK;
+}
+
+int okge_tucker3_apply(const float *M, int64_t ld_m, const float *x, int64_t ld_x, int32_t n, int32_t d, int32_t transpose, float *out,
+                       int64_t ld_out, void *stream)
+{
+    if (!M || !x || !out || n < 0 || d <= 0 || ld_m < (int64_t)d * d || ld_x < d || ld_out < d)
+        return fail(OKGE_ERR_INVALID, "bad tucker3_apply arguments");
+    if (d > 256) return fail(OKGE_ERR_UNSUPPORTED, "tucker3: slot sizes above 256 are not supported");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ScopedTimer tm("tucker3_apply", st);
+    hipError_t e = launch_tucker3_apply(M, ld_m, x, ld_x, n, d, transpose != 0, out, ld_out, st);
+    if (e != hipSuccess) return fail_hip(e, "tucker3_apply");
+    return OKGE_OK;
+}
+
+int okge_tucker3_outer(const float *u, int64_t ld_u, const float *v, int64_t ld_v, int32_t n, int32_t d, float *out, int64_t ld_out,
+                       void *stream)
+{
+    if (!u || !v || !out || n < 0 || d <= 0 || ld_u < d || ld_v < d || ld_out < (int64_t)d * d)
+        return fail(OKGE_ERR_INVALID, "bad tucker3_outer arguments");
+    if (d > 256) return fail(OKGE_ERR_UNSUPPORTED, "tucker3: slot sizes above 256 are not supported");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ScopedTimer tm("tucker3_outer", st);
+    hipError_t e = launch_tucker3_outer(u, ld_u, v, ld_v, n, d, out, ld_out, st);
+    if (e != hipSuccess) return fail_hip(e, "tucker3_outer");
+    return OKGE_OK;
+}
+
 // ---- LSTM token encoder (okge_lstm.hip) ----------------------------------------------------------------------------
 size_t okge_lstm_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training)
 {

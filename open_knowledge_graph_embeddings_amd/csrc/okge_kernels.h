@@ -192,6 +192,20 @@ int lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, in
                         int64_t ld, const int32_t *pos_tok, const int32_t *pos_order, float *dW, float *d_w_ih, float *d_w_hh,
                         float *d_b_ih, float *d_b_hh, float *d_bn_weight, float *d_bn_bias, void *workspace, size_t workspace_bytes,
                         int *err, void *stream);
+// Tucker3 / RESCAL fold and backward (okge_tucker3.hip); cus = compute units of the device (split of the long contractions)
+int tucker3_splits(int B, int Nn, int outer, int cus);
+size_t tucker3_workspace_bytes(int B, int d, int r, int cus);
+hipError_t launch_tucker3_fold(const float *W, const float *x, int64_t ld_x, const float *rho, int64_t ld_r, int n_po, int B, int d, int r,
+                               int transpose, float *out, int rows_out, int64_t ld_out, int cols_out, float *slab, int cus, hipStream_t st);
+hipError_t launch_tucker3_backward(const float *W, const float *ent, int64_t ld_e, const float *rho, int64_t ld_r, const float *dq,
+                                   int64_t ld_q, int n_po, int B, int d, int r, int fresh, float *d_ent, float *d_rel, float *dW,
+                                   float *slab, int cus, hipStream_t st);
+hipError_t launch_tucker3_triples(const float *W, const float *subj, int64_t ld_s, const float *rho, int64_t ld_r, const float *obj,
+                                  int64_t ld_o, int n, int d, int r, float *q, float *slab, float *out, int cus, hipStream_t st);
+hipError_t launch_tucker3_apply(const float *M, int64_t ld_m, const float *x, int64_t ld_x, int n, int d, int transpose, float *out,
+                                int64_t ld_out, hipStream_t st);
+hipError_t launch_tucker3_outer(const float *u, int64_t ld_u, const float *v, int64_t ld_v, int n, int d, float *out, int64_t ld_out,
+                                hipStream_t st);
 // dense Adagrad over up to four tensors in one launch; a tensor may come with a touched-row byte map (rows whose byte differs
 // from `stamp` hold an all-zero gradient by contract: it is neither read nor cleared)
 constexpr int ADAGRAD_MAX_SEGS = 4;

@@ -127,7 +127,8 @@ class AddLossModule(nn.Module):
         m = self.model
         eng = m.engine()
         dev = m.entity_embedding.weight.device
-        token_model = hasattr(m, "entity_token_ids")
+        # (models that bring their own fused step -- autograd_step / loss_only: the token encoders, Tucker3 -- share one route)
+        token_model = hasattr(m, "entity_token_ids") or getattr(m, "fused_step_model", False)
         n_ent, first = m.train_data.entities_size, m.train_data.min_entities_size
         po, sp = inputs
         if FAST_CALL and not token_model and m.training and torch.is_grad_enabled() and isinstance(labels, tuple) \
