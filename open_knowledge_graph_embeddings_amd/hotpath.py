@@ -76,6 +76,12 @@ def validate_ids(batch, n_ent, n_rel):
 STREAM_CAND, STREAM_PO_ENT, STREAM_PO_REL, STREAM_SP_ENT, STREAM_SP_REL = 0, 1, 2, 3, 4
 
 
+def dropout_specs(p_ent, p_rel, seed, step, step_dev=None):
+    """the five masks of one step in stream order: the entity streams drop with p_ent, the relation streams with p_rel"""
+    return tuple(DropoutSpec(p_rel if stream in (STREAM_PO_REL, STREAM_SP_REL) else p_ent, seed, stream, step, step_dev=step_dev)
+                 for stream in (STREAM_CAND, STREAM_PO_ENT, STREAM_PO_REL, STREAM_SP_ENT, STREAM_SP_REL))
+
+
 @dataclass
 class PrefixBatch:
     """One batch in device memory: po rows (rel, obj) first, then sp rows (subj, rel); positives as
@@ -215,6 +221,13 @@ class HotPath:
             keep.append(ct)
         return pb, c, keep
 
+    def _positives(self, b: PrefixBatch):
+        """-> (okge_positives, the int32 tensors it points into)"""
+        keep = [_i32(b.pos_row, self.device), _i32(b.pos_col, self.device)]
+        pos = N.Positives()
+        pos.row, pos.col, pos.nnz = _ptr(keep[0]), _ptr(keep[1]), b.nnz
+        return pos, keep
+
     # -- entry points -------------------------------------------------------------------------------
     def score(self, E, R, scorer, batch: PrefixBatch, out=None):
         """(B, N) scores of every prefix against every candidate (eval / *_prefix_score)."""
@@ -242,9 +255,7 @@ class HotPath:
         t = self._tables(E, R, scorer)
         B, n = batch.B, c.n
         ws = self.workspace(B, n, t.d)
-        pos = N.Positives()
-        prow, pcol = _i32(batch.pos_row, self.device), _i32(batch.pos_col, self.device)
-        pos.row, pos.col, pos.nnz = _ptr(prow), _ptr(pcol), batch.nnz
+        pos, keep_pos = self._positives(batch)
         if normalizer is None:
             normalizer = float(B) * float(n)
         if loss_out is None:
@@ -259,7 +270,7 @@ class HotPath:
             loss_out.data_ptr(), _ptr(dE), _ptr(dR),
             None if scores is None else scores.data_ptr(), 0 if scores is None else scores.stride(0),
             ws.data_ptr(), self._ws_bytes, self._stream()), "okge_train_forward_backward")
-        del keep, prow, pcol
+        del keep, keep_pos
         return loss_out
 
     # -- entity-sharded phases (include/okge.h: okge_encode_queries / okge_train_tiles / okge_prefix_backward) ----
@@ -306,16 +317,16 @@ class HotPath:
         return out
 
     def train_tiles(self, E_local, R, scorer, Q, batch: PrefixBatch, shard: Shard, dE, dQ, n_cand_global, loss="bce",
-                    label_smoothing=0.0, normalizer=None, loss_out=None, grads_zero=False, row_lse=None):
+                    label_smoothing=0.0, normalizer=None, loss_out=None, grads_zero=False, row_lse=None, *, loss_only=False,
+                    B=None):
         """Local candidates only: batch.cand_first / n_cand are LOCAL row indices, batch.pos_col GLOBAL columns.
-        KL loss: `row_lse` = log-sum-exp of every row's scores over ALL shards' candidates."""
+        KL loss: `row_lse` = log-sum-exp of every row's scores over ALL shards' candidates.  loss_only: no gradients.
+        B: query rows in Q, for a batch that names candidates and positives only (default: the batch's rows)."""
         pb, c, keep = self._batch(batch)
         t = self._tables(E_local, R, scorer)
-        B, n = batch.B, c.n
+        B, n = batch.B if B is None else int(B), c.n
         ws = self.workspace(B, n, t.d)
-        pos = N.Positives()
-        prow, pcol = _i32(batch.pos_row, self.device), _i32(batch.pos_col, self.device)
-        pos.row, pos.col, pos.nnz = _ptr(prow), _ptr(pcol), batch.nnz
+        pos, keep_pos = self._positives(batch)
         if normalizer is None:
             normalizer = float(B) * float(n_cand_global)
         if loss_out is None:
@@ -324,9 +335,10 @@ class HotPath:
         N.check(self.lib.okge_train_tiles(
             ctypes.byref(t), ctypes.byref(sh), Q.data_ptr(), Q.stride(0), B, ctypes.byref(c), ctypes.byref(pos),
             N.LOSSES[loss] if isinstance(loss, str) else int(loss), float(label_smoothing), float(normalizer),
-            int(n_cand_global), N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0, _ptr(row_lse), loss_out.data_ptr(),
+            int(n_cand_global), (N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0) | (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) |
+            (N.OKGE_TRAIN_UNIQUE_CANDIDATES if batch.cand_unique else 0), _ptr(row_lse), loss_out.data_ptr(),
             dE.data_ptr(), dQ.data_ptr(), ws.data_ptr(), self._ws_bytes, self._stream()), "okge_train_tiles")
-        del keep, prow, pcol
+        del keep, keep_pos
         return loss_out
 
     def score_queries(self, E_local, R, scorer, Q, B, batch: PrefixBatch, shard: Shard, out=None):

@@ -2,12 +2,11 @@
 over the HIP kernels of csrc/okge_lstm.hip (forward and backward through time on the exact-fp32 MFMA), and the training
 step that drives the fused prefix-scoring path on rows encoded from tokens.
 
-The step is TokenPooledTrainStep's (token_pooled.py) with the LSTM in place of the pooling: the encoded (and batch-normed)
-rows of one batch -- candidates, po objects, sp subjects on the entity slot; po / sp relations on the relation slot -- form
-two small "virtual" tables, the fused step (score -> loss -> backward, dropout included) runs on them, and its dense row
-gradients go back through batch-norm and the LSTM into the token tables, the LSTM weights and the batch-norm parameters.
-The three entity calls share one LSTM pass and the two relation calls another; batch-norm statistics stay per call, in the
-reference's order (trainer.py:75-91).  The dense Adagrad then moves every parameter, as the reference's optimizer does.
+The step is virtual_tables.VirtualTableStep (layout and skeleton, shared with token_pooled.py) with the LSTM as the encoder:
+the fused step's dense row gradients go back through batch-norm and the LSTM into the token tables, the LSTM weights and the
+batch-norm parameters.  The three entity calls share one LSTM pass and the two relation calls another; batch-norm statistics
+stay per call, in the reference's order (trainer.py:75-91).  The dense Adagrad then moves every parameter, as the reference's
+optimizer does.
 """
 from __future__ import annotations
 
@@ -18,7 +17,8 @@ import torch
 from . import _native as N
 from . import hotpath as H
 from .model import ComplexRelationScorer, DistmultRelationScorer, Models
-from .token_pooled import BN_EPS, BN_MOMENTUM, UnigramPoolingRelationEmbedder, _i32, token_id_matrix
+from . import virtual_tables as VT
+from .token_pooled import BN_EPS, BN_MOMENTUM, UnigramPoolingRelationEmbedder, token_id_matrix
 
 MAX_SLOT = 512                                     # the fused tile kernels' largest slot size
 PRECOMPUTE_CHUNK = 16384                           # rows per encode call of precompute_embeddings_from_tokens
@@ -37,13 +37,8 @@ class LSTMSlot:
         dev = W.device
         self.dW = torch.zeros_like(W)
         self.sumW = torch.zeros_like(W)
-        n = sum(p.numel() for p in self.lstm)
-        self.d_flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.sum_flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.dlstm, o = [], 0
-        for p in self.lstm:
-            self.dlstm.append(self.d_flat[o:o + p.numel()].view_as(p))
-            o += p.numel()
+        self.fresh_lstm_grads()
+        self.sum_flat = torch.zeros_like(self.d_flat)
         self.bn = None
         if bn is not None:
             d = self.d
@@ -51,6 +46,11 @@ class LSTMSlot:
             self.running_mean, self.running_var = running
             self.d_bn = torch.zeros(2 * d, dtype=torch.float32, device=dev)
             self.sum_bn = torch.zeros(2 * d, dtype=torch.float32, device=dev)
+
+    def fresh_lstm_grads(self):
+        """d_flat: one zeroed gradient buffer; dlstm: the four LSTM tensors' gradients as views of it"""
+        self.d_flat = torch.zeros(sum(p.numel() for p in self.lstm), dtype=torch.float32, device=self.W.device)
+        self.dlstm = [g.view_as(p) for g, p in zip(self.d_flat.split([p.numel() for p in self.lstm]), self.lstm)]
 
     def c(self):
         s = N.LstmSlot()
@@ -122,23 +122,16 @@ class LstmPass:
                                                   self._stream()), "okge_lstm_backward_calls")
 
 
-class LSTMTrainStep:
+class LSTMTrainStep(VT.VirtualTableStep):
     """forward + loss + backward + Adagrad for LSTM{Complex,Distmult}RelationModel (Trainer.compute_one_batch,
     trainer.py:181-257, over model.py:966-998).  The optimizer is dense: every token row, LSTM tensor and batch-norm parameter
     moves every step (utils/optim.py:139-160)."""
 
     def __init__(self, entity: LSTMSlot, relation: LSTMSlot, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8,
                  label_smoothing=0.0, dropout=0.0, relation_dropout=None, seed=0, engine=None):
-        self.entity, self.relation, self.scorer, self.loss = entity, relation, scorer, loss
-        self.lr, self.weight_decay, self.eps, self.label_smoothing = lr, weight_decay, eps, label_smoothing
-        self.dropout = dropout
-        self.relation_dropout = dropout if relation_dropout is None else relation_dropout
-        self.seed, self.steps = seed, 0
-        self.device = entity.W.device
-        self.engine = engine or H.HotPath(self.device)
+        super().__init__(entity, relation, scorer, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
+                         label_smoothing=label_smoothing, dropout=dropout, relation_dropout=relation_dropout, seed=seed, engine=engine)
         self.passes = (LstmPass(self.device), LstmPass(self.device))
-        self.loss_out = torch.zeros(1, dtype=torch.float64, device=self.device)
-        self._rows = (0, 0)
         self.decay_window = 1
 
     def state_tensors(self):
@@ -152,65 +145,29 @@ class LSTMTrainStep:
     def flush(self):
         """(no deferred updates here: every parameter is current after every step)"""
 
-    def _buffers(self, n_ent_rows, n_rel_rows):
-        d = self.entity.d
-        if n_ent_rows > self._rows[0] or n_rel_rows > self._rows[1]:
-            dev = self.device
-            self._rows = (n_ent_rows, n_rel_rows)
-            self.EV, self.EX, self.dEV = (torch.zeros((n_ent_rows, d), device=dev) for _ in range(3))
-            self.RV, self.RX, self.dRV = (torch.zeros((n_rel_rows, d), device=dev) for _ in range(3))
-        return self.EV, self.EX, self.dEV, self.RV, self.RX, self.dRV
-
-    def step(self, batch: H.PrefixBatch, normalizer=None):
-        """`batch` carries ENTITY / RELATION ids exactly as for the lookup models."""
-        loss = self.forward_backward(batch, normalizer)
-        self.optimizer_step()
-        return loss
-
-    def forward_backward(self, batch: H.PrefixBatch, normalizer=None, scores=None):
-        """Leaves the dense gradients in the slots' dW, d_flat (dlstm) and d_bn ([d weight | d bias])."""
-        self.steps += 1
+    def _encode(self, batch: H.PrefixBatch, bufs):
+        """one LSTM pass per slot over its calls, in the reference's encode order; -> the two slots' non-empty calls"""
         dev = self.device
-        n_po, n_sp, N_c = batch.n_po, batch.n_sp, batch.n_candidates
-        B = n_po + n_sp
-        EV, EX, dEV, RV, RX, dRV = self._buffers(N_c + B, B)
-        ent, rel = self.entity, self.relation
-        # the reference's encode order: candidates, (po rel, po obj), (sp subj, sp rel) -- trainer.py:75-91; one pass per slot
-        ecalls = [c for c in ((_i32(batch.cand_ids, dev), batch.cand_first, N_c), (_i32(batch.po_obj, dev), 0, n_po),
-                              (_i32(batch.sp_subj, dev), 0, n_sp)) if c[2] > 0]
-        rcalls = [c for c in ((_i32(batch.po_rel, dev), 0, n_po), (_i32(batch.sp_rel, dev), 0, n_sp)) if c[2] > 0]
-        pe, pr = self.passes
-        pe.encode(ent, ecalls, True, EX[:N_c + B], EV[:N_c + B])
-        pr.encode(rel, rcalls, True, RX[:B], RV[:B])
-        EVt, RVt = (EV if ent.bn is not None else EX), (RV if rel.bn is not None else RX)
-        key = (N_c, n_po, n_sp)
-        if getattr(self, "_ar_key", None) != key:
-            # virtual-table rows: entity rows [cand | po obj | sp subj], relation rows [po rel | sp rel]
-            rng = torch.arange(0, N_c + B, dtype=torch.int32, device=dev)
-            self._ar_key, self._ar = key, (rng[:n_po], rng[N_c:N_c + n_po], rng[N_c + n_po:N_c + B], rng[n_po:B])
-        ar_po_rel, ar_po_obj, ar_sp_subj, ar_sp_rel = self._ar
-        s, t = self.seed, self.steps
-        DE = lambda stream: H.DropoutSpec(self.dropout, s, stream, t)              # noqa: E731
-        DR = lambda stream: H.DropoutSpec(self.relation_dropout, s, stream, t)     # noqa: E731
-        vb = H.PrefixBatch(po_rel=ar_po_rel if n_po else None, po_obj=ar_po_obj if n_po else None,
-                           sp_subj=ar_sp_subj if n_sp else None, sp_rel=ar_sp_rel if n_sp else None,
-                           pos_row=batch.pos_row, pos_col=batch.pos_col, cand_first=0, n_cand=N_c,
-                           drop_cand=DE(H.STREAM_CAND), drop_po_ent=DE(H.STREAM_PO_ENT), drop_sp_ent=DE(H.STREAM_SP_ENT),
-                           drop_po_rel=DR(H.STREAM_PO_REL), drop_sp_rel=DR(H.STREAM_SP_REL))
-        self.engine.forward_backward(EVt[:N_c + B], RVt[:B], self.scorer, vb, dEV[:N_c + B], dRV[:B], loss=self.loss,
-                                     label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out,
-                                     scores=scores, grads_zero=True, distinct_prefix_rows=True)
-        pe.backward(ent, ecalls, EX[:N_c + B], dEV[:N_c + B], ent.dW, ent.dlstm, ent.d_bn if ent.bn is not None else None)
-        pr.backward(rel, rcalls, RX[:B], dRV[:B], rel.dW, rel.dlstm, rel.d_bn if rel.bn is not None else None)
-        return self.loss_out
+        EV, EX, dEV, RV, RX, dRV = bufs
+        calls = ([], [])
+        for relation, ids, first, rows in VT.encode_calls(batch):
+            if rows.stop > rows.start:
+                calls[relation].append((H._i32(ids, dev), first, rows.stop - rows.start))
+        self.passes[0].encode(self.entity, calls[0], True, EX, EV)
+        self.passes[1].encode(self.relation, calls[1], True, RX, RV)
+        return calls
+
+    def _backward(self, batch, bufs, calls):
+        """dEV / dRV -> batch-norm and the LSTM backward through time -> the slots' dW, d_flat (dlstm), d_bn ([d weight | d bias])"""
+        EV, EX, dEV, RV, RX, dRV = bufs
+        for ps, sl, cs, X, dV in zip(self.passes, (self.entity, self.relation), calls, (EX, RX), (dEV, dRV)):
+            ps.backward(sl, cs, X, dV, sl.dW, sl.dlstm, sl.d_bn if sl.bn is not None else None)
 
     def optimizer_step(self):
         tensors = self.entity.optimizer_tensors() + self.relation.optimizer_tensors()
         for i in range(0, len(tensors), 4):                       # (okge_adagrad_multi: up to four tensors per launch)
             self.engine.adagrad_multi(tensors[i:i + 4], self.lr, self.weight_decay, self.eps)
-        for sl, bn in getattr(self, "module_batchnorms", ()):          # keep an attached nn.Module's parameters current
-            bn.weight.data.copy_(sl.bn[:sl.d])
-            bn.bias.data.copy_(sl.bn[sl.d:])
+        self._sync_module_batchnorms()
 
 
 class LSTMEncodeFn(torch.autograd.Function):
@@ -365,28 +322,34 @@ class LSTMRelationEmbedder(UnigramPoolingRelationEmbedder):
                 self.relations_embedding_from_tokens = table(self.train_data.relations_size, True)
 
     # -- AddLossModule / autograd bridge (the reference Trainer's path: trainer.py:142, 206-234) ---------------------
+    def _lstm_slots(self, flat):
+        """the two slots over the module's parameters; flat: the four LSTM tensors of each slot become views of one flat
+        buffer (one optimizer segment)"""
+        slots = []
+        for relation in (False, True):
+            emb, tok, lstm, bn = self._parts(relation)
+            ps, buf = self._lstm_tensors(lstm), None
+            if flat:
+                buf = torch.cat([q.data.reshape(-1) for q in ps])
+                for q, view in zip(ps, buf.split([q.numel() for q in ps])):
+                    q.data = view.view_as(q)
+            slots.append(LSTMSlot(emb.weight.data, tok, [q.data for q in ps], None if bn is None else (bn.weight.data, bn.bias.data),
+                                  None if bn is None else (bn.running_mean, bn.running_var), flat=buf))
+        return slots
+
     def autograd_step(self, loss, label_smoothing):
         """the cached LSTMTrainStep behind AddLossModule: shares the module's parameters; its optimizer is NOT used (the
         caller's torch optimizer steps the module parameters)"""
         st = getattr(self, "_ag_step", None)
         if st is None or st.loss != loss or st.label_smoothing != label_smoothing or st.entity.W.data_ptr() != self.entity_embedding.weight.data_ptr():
-            slots = []
-            for relation in (False, True):
-                emb, tok, lstm, bn = self._parts(relation)
-                slots.append(LSTMSlot(emb.weight.data, tok, [q.data for q in self._lstm_tensors(lstm)],
-                                      None if bn is None else (bn.weight.data, bn.bias.data),
-                                      None if bn is None else (bn.running_mean, bn.running_var)))
+            slots = self._lstm_slots(flat=False)
             st = self._ag_step = LSTMTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, label_smoothing=label_smoothing,
                                                dropout=self.entity_dropout, relation_dropout=self.relation_dropout, seed=self.dropout_seed)
         for sl, relation in ((st.entity, False), (st.relation, True)):
             emb, tok, lstm, bn = self._parts(relation)
             sl.lstm = [q.data for q in self._lstm_tensors(lstm)]             # (a torch optimizer may have replaced nothing, but
             sl.dW = torch.zeros_like(sl.W)                                     #  the gradient buffers went to autograd: fresh ones)
-            sl.d_flat = torch.zeros_like(sl.d_flat)
-            sl.dlstm, o = [], 0
-            for q in sl.lstm:
-                sl.dlstm.append(sl.d_flat[o:o + q.numel()].view_as(q))
-                o += q.numel()
+            sl.fresh_lstm_grads()
             if bn is not None:                                                 # the module's parameters may have been stepped outside
                 sl.bn[:sl.d].copy_(bn.weight.data)
                 sl.bn[sl.d:].copy_(bn.bias.data)
@@ -409,17 +372,7 @@ class LSTMRelationEmbedder(UnigramPoolingRelationEmbedder):
     def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0):
         """The training driver for this model: shares the module's parameters (updated in place).  The four LSTM tensors of
         each slot become views of one flat buffer (one optimizer segment)."""
-        slots = []
-        for relation in (False, True):
-            emb, tok, lstm, bn = self._parts(relation)
-            ps = self._lstm_tensors(lstm)
-            flat = torch.cat([q.data.reshape(-1) for q in ps])
-            o = 0
-            for q in ps:
-                q.data = flat[o:o + q.numel()].view_as(q)
-                o += q.numel()
-            slots.append(LSTMSlot(emb.weight.data, tok, [q.data for q in ps], None if bn is None else (bn.weight.data, bn.bias.data),
-                                  None if bn is None else (bn.running_mean, bn.running_var), flat=flat))
+        slots = self._lstm_slots(flat=True)
         st = LSTMTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
                            label_smoothing=label_smoothing, dropout=self.entity_dropout, relation_dropout=self.relation_dropout,
                            seed=self.dropout_seed)

@@ -2,12 +2,11 @@
 (openkge/model.py:561-796) over the HIP kernels of csrc/okge_pool.hip, and the training step that drives the fused
 prefix-scoring path on rows computed from tokens.
 
-Design: the pooled (and batch-normed) rows of one batch -- candidates, po objects, sp subjects; po / sp relations -- are
-written into two small "virtual" tables; the unchanged fused step (score -> loss -> backward, dropout included) runs on
-those tables; its dense row gradients then go back through batch-norm and the pooling into the token tables' dense
-gradients, and Adagrad sweeps the token tables and the batch-norm parameters.  Every `_encode` call of the reference
-(candidates, po rows, sp rows -- trainer.py:75-91) normalises with ITS OWN batch statistics and updates the running
-statistics; that order is kept.
+Design: the pooled (and batch-normed) rows of one batch are written into the two virtual tables of virtual_tables.py (layout
+and step skeleton); the fused step's dense row gradients then go back through batch-norm and the pooling into the token
+tables' dense gradients, and Adagrad sweeps the token tables and the batch-norm parameters.  Every `_encode` call of the
+reference (candidates, po rows, sp rows -- trainer.py:75-91) normalises with ITS OWN batch statistics and updates the
+running statistics; that order is kept.
 """
 from __future__ import annotations
 
@@ -18,6 +17,7 @@ import torch
 
 from . import _native as N
 from . import hotpath as H
+from . import virtual_tables as VT
 from .model import ComplexRelationScorer, DistmultRelationScorer, Models, RelationEmbedder
 
 POOLS = {"sum": 0, "mean": 1, "max": 2}
@@ -201,17 +201,14 @@ class PoolEngine:
         del keep
 
 
-def _i32(t, dev):
-    return None if t is None else t.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-
-
-class TokenPooledTrainStep:
+class TokenPooledTrainStep(VT.VirtualTableStep):
     """forward + loss + backward + Adagrad for UnigramPooling{Complex,Distmult}RelationModel
     (Trainer.compute_one_batch, trainer.py:181-257, over model.py:762-796)."""
 
     def __init__(self, entity: TokenSlot, relation: TokenSlot, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8,
                  label_smoothing=0.0, dropout=0.0, seed=0, engine=None, overlap_sweep=None, decay_window=None):
-        self.entity, self.relation, self.scorer, self.loss = entity, relation, scorer, loss
+        super().__init__(entity, relation, scorer, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
+                         label_smoothing=label_smoothing, dropout=dropout, seed=seed, engine=engine)
         # decay_window (OKGE_LAZY_DECAY; 1 = every row every step): the reference's Adagrad moves EVERY token row in
         # every step by its weight-decay term (utils/optim.py:139-160) -- 1 GB of read-modify-write at configs[4], 175 us of a
         # 0.78 ms step, for rows nothing reads.  With a window W > 1 a row no batch names takes its pending decay-only steps
@@ -244,16 +241,11 @@ class TokenPooledTrainStep:
             overlap_sweep = os.environ.get("OKGE_OVERLAP_SWEEP", "0") == "1"
         self.overlap_sweep = bool(overlap_sweep)
         self._side, self._side_done = None, None
-        self.lr, self.weight_decay, self.eps, self.label_smoothing = lr, weight_decay, eps, label_smoothing
-        self.dropout, self.seed, self.steps = dropout, seed, 0
-        self.device = entity.W.device
-        self.engine = engine or H.HotPath(self.device)
         self.pool = PoolEngine(self.device)
         # (rounds 1-2 ran the five encode / backward calls of a step one by one, the relation slot's on a side stream:
         #  35 small launches; they now go to the library as ONE batch each way: three launches forward, three backward)
-        self.loss_out = torch.zeros(1, dtype=torch.float64, device=self.device)
-        self.step_dev = None              # device step counter, attached by GraphedTrainStep
-        self._rows = 0
+        self.saved = torch.zeros((5, 4 * entity.d), device=self.device)      # batch-norm statistics of the five encode calls
+        self._early_swept = False
 
     def state_tensors(self):
         self.flush()
@@ -315,10 +307,10 @@ class TokenPooledTrainStep:
         """token-table rows this batch's backward can touch (with repeats; row 0 = padding included, its gradient is 0):
         the token ids of the candidate + prefix entities, and of the prefix relations -- known from the ids alone"""
         dev = self.device
-        cand = _i32(batch.cand_ids, dev) if batch.cand_ids is not None else \
+        cand = H._i32(batch.cand_ids, dev) if batch.cand_ids is not None else \
             torch.arange(batch.cand_first, batch.cand_first + batch.n_candidates, dtype=torch.int32, device=dev)
-        ent = torch.cat([x for x in (cand, _i32(batch.po_obj, dev), _i32(batch.sp_subj, dev)) if x is not None]).long()
-        rel = torch.cat([x for x in (_i32(batch.po_rel, dev), _i32(batch.sp_rel, dev)) if x is not None]).long()
+        ent = torch.cat([x for x in (cand, H._i32(batch.po_obj, dev), H._i32(batch.sp_subj, dev)) if x is not None]).long()
+        rel = torch.cat([x for x in (H._i32(batch.po_rel, dev), H._i32(batch.sp_rel, dev)) if x is not None]).long()
         ie, ir = self.sparse_grad_indices()
         return [(ie, self.entity.token_ids.index_select(0, ent)), (ir, self.relation.token_ids.index_select(0, rel))]
 
@@ -330,46 +322,19 @@ class TokenPooledTrainStep:
                 sl.d_bn = next(gi)
                 sl.running_mean, sl.running_var = next(si), next(si)
 
-    def _buffers(self, n_ent_rows, n_rel_rows):
-        d = self.entity.d
-        if n_ent_rows > self._rows or n_rel_rows > getattr(self, "_rrows", 0):
-            dev = self.device
-            self._rows, self._rrows = n_ent_rows, n_rel_rows
-            self.EV, self.EX, self.dEV = (torch.zeros((n_ent_rows, d), device=dev) for _ in range(3))
-            self.RV, self.RX, self.dRV = (torch.zeros((n_rel_rows, d), device=dev) for _ in range(3))
-            self.saved = torch.zeros((5, 4 * d), device=dev)
-        return self.EV, self.EX, self.dEV, self.RV, self.RX, self.dRV
-
-    def step(self, batch: H.PrefixBatch, normalizer=None):
-        """`batch` carries ENTITY / RELATION ids exactly as for the lookup models."""
-        self._in_step = True
-        try:
-            loss = self.forward_backward(batch, normalizer)
-        finally:
-            self._in_step = False
-        self.optimizer_step()
-        return loss
-
-    def forward_backward(self, batch: H.PrefixBatch, normalizer=None, scores=None):
-        """Leaves the dense gradients in entity/relation .dW and .d_bn ([d weight | d bias])."""
-        self.steps += 1
+    def _encode(self, batch: H.PrefixBatch, bufs):
+        """catch-up of owed decay steps, the pooling (+ batch-norm) forward of the five calls, the early side-stream sweep"""
         dev = self.device
-        n_po, n_sp, N_c = batch.n_po, batch.n_sp, batch.n_candidates
-        B = n_po + n_sp
-        EV, EX, dEV, RV, RX, dRV = self._buffers(N_c + B, B)
+        EV, EX, dEV, RV, RX, dRV = bufs
         ent, rel, pe = self.entity, self.relation, self.pool
-        sv = self.saved
-        bn_e, bn_r = ent.bn is not None, rel.bn is not None
         # the reference's encode order: candidates, (po rel, po obj), (sp subj, sp rel)   -- trainer.py:75-91
-        calls = [(ent, _i32(batch.cand_ids, dev), batch.cand_first, N_c, EX[:N_c], EV[:N_c], dEV[:N_c], sv[0] if bn_e else None),
-                 (rel, _i32(batch.po_rel, dev), 0, n_po, RX[:n_po], RV[:n_po], dRV[:n_po], sv[1] if bn_r else None),
-                 (ent, _i32(batch.po_obj, dev), 0, n_po, EX[N_c:N_c + n_po], EV[N_c:N_c + n_po], dEV[N_c:N_c + n_po], sv[2] if bn_e else None),
-                 (ent, _i32(batch.sp_subj, dev), 0, n_sp, EX[N_c + n_po:N_c + B], EV[N_c + n_po:N_c + B], dEV[N_c + n_po:N_c + B], sv[3] if bn_e else None),
-                 (rel, _i32(batch.sp_rel, dev), 0, n_sp, RX[n_po:B], RV[n_po:B], dRV[n_po:B], sv[4] if bn_r else None)]
+        # calls: (slot, ids, first id, n, raw rows, batch-normed rows, row gradients, saved statistics)
+        calls = []
+        for (relation, ids, first, rows), sv in zip(VT.encode_calls(batch), self.saved.unbind(0)):
+            sl, X, V, dV = (rel, RX, RV, dRV) if relation else (ent, EX, EV, dEV)
+            calls.append((sl, H._i32(ids, dev), first, rows.stop - rows.start, X[rows], V[rows], dV[rows], sv if sl.bn is not None else None))
         # forward of all five calls: raw pooled rows -> EX / RX, batch-normed rows -> EV / RV (per-call statistics, running
         # statistics updated in this order)
-        # (only inside step(): a caller that runs forward_backward alone -- the autograd bridge, ReplicaStep, whose other replicas'
-        #  rows receive gradients in the exchange -- gets no early update)
         enc_calls = [(c_[0], c_[1], c_[2], c_[3], c_[4], c_[5] if c_[0].bn is not None else c_[4], c_[7]) for c_ in calls]
         if self.decay_window > 1:
             # the token rows this batch names take the decay-only steps they owe before the forward reads them (always
@@ -377,7 +342,9 @@ class TokenPooledTrainStep:
             self._settle_hparams()
             lr, wd, eps = self._hparams()
             pe.catch_up_calls(enc_calls, self.engine.lazy_tensors(self._lazy_tables()), self._counters, lr, wd, eps)
-        overlap = (self.overlap_sweep and self.decay_window == 1 and getattr(self, "_in_step", False) and ent.touched is not None
+        # (only inside step(): a caller that runs forward_backward alone -- the autograd bridge, ReplicaStep, whose other replicas'
+        #  rows receive gradients in the exchange -- gets no early update)
+        overlap = (self.overlap_sweep and self.decay_window == 1 and self._in_step and ent.touched is not None
                    and rel.touched is not None and not torch.cuda.is_current_stream_capturing())
         if self._side_done is not None:            # the previous step's side sweep wrote rows this forward may read
             torch.cuda.current_stream(dev).wait_event(self._side_done)
@@ -394,29 +361,11 @@ class TokenPooledTrainStep:
                                           self.lr, self.weight_decay, self.eps)
                 self._side_done = self._side.record_event()
             self._early_swept = True
-        EVt, RVt = (EV if bn_e else EX), (RV if bn_r else RX)
-        # the fused step on the virtual tables: candidates are rows 0..N-1, prefix entities follow
-        # row indices of the virtual tables: they depend on the batch's shape only -- built once per shape (four arange
-        # launches per step otherwise: 18 us of a 0.9 ms step at configs[4])
-        key = (N_c, n_po, n_sp)
-        if getattr(self, "_ar_key", None) != key:
-            rng = torch.arange(0, N_c + B, dtype=torch.int32, device=dev)
-            self._ar_key, self._ar = key, (rng[:n_po], rng[N_c:N_c + n_po], rng[N_c + n_po:N_c + B], rng[n_po:B])
-        ar_po_rel, ar_po_obj, ar_sp_subj, ar_sp_rel = self._ar
-        p, s, t = self.dropout, self.seed, self.steps
-        DS = lambda stream: H.DropoutSpec(p, s, stream, t, step_dev=self.step_dev)      # noqa: E731
-        vb = H.PrefixBatch(po_rel=ar_po_rel if n_po else None, po_obj=ar_po_obj if n_po else None,
-                           sp_subj=ar_sp_subj if n_sp else None, sp_rel=ar_sp_rel if n_sp else None,
-                           pos_row=batch.pos_row, pos_col=batch.pos_col, cand_first=0, n_cand=N_c,
-                           drop_cand=DS(H.STREAM_CAND), drop_po_ent=DS(H.STREAM_PO_ENT), drop_sp_ent=DS(H.STREAM_SP_ENT),
-                           drop_po_rel=DS(H.STREAM_PO_REL), drop_sp_rel=DS(H.STREAM_SP_REL))
-        self.engine.forward_backward(EVt[:N_c + B], RVt[:B], self.scorer, vb, dEV[:N_c + B], dRV[:B], loss=self.loss,
-                                     label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out,
-                                     scores=scores, grads_zero=True, distinct_prefix_rows=True)
-        # (every row of dEV / dRV is STORED by that call -- the candidate rows by the tile kernel (grads_zero), the prefix rows,
-        #  one per batch row in these virtual tables, by the prefix backward (distinct_prefix_rows): nothing to clear per step)
-        pe.backward_calls([(c_[0], c_[1], c_[2], c_[3], c_[4], c_[6], c_[7]) for c_ in calls])
-        return self.loss_out
+        return calls
+
+    def _backward(self, batch, bufs, calls):
+        """dEV / dRV -> batch-norm and pooling backward of the five calls -> the slots' dW, d_bn ([d weight | d bias])"""
+        self.pool.backward_calls([(c_[0], c_[1], c_[2], c_[3], c_[4], c_[6], c_[7]) for c_ in calls])
 
     def mark_sparse_rows(self, index, rows):
         """sharded.ReplicaStep wrote other replicas' gradient rows into a sparse gradient (grad_tensors()[index]): stamp them"""
@@ -438,7 +387,7 @@ class TokenPooledTrainStep:
             return
         # one launch: token tables (gradient rows the backward did not stamp are neither read nor cleared) + batch-norm parameters
         # (after an early sweep of the unstamped rows -- forward_backward, overlap_sweep -- only the stamped rows are left)
-        rows = 2 if getattr(self, "_early_swept", False) else 0
+        rows = 2 if self._early_swept else 0
         tensors = [(sl.W, sl.dW, sl.sumW, sl.touched, sl.stamp, rows) for sl in (e, r)]
         tensors += [(sl.bn, sl.d_bn, sl.sum_bn) for sl in (e, r) if sl.bn is not None]
         self._early_swept = False
@@ -448,14 +397,7 @@ class TokenPooledTrainStep:
     def _after_update(self):
         for sl in (self.entity, self.relation):
             sl.next_stamp()
-        for sl, bn in getattr(self, "module_batchnorms", ()):          # keep an attached nn.Module's parameters current
-            bn.weight.data.copy_(sl.bn_weight)
-            bn.bias.data.copy_(sl.bn_bias)
-            # ... and its running statistics, once ReplicaStep.rebind has moved ours into the exchange buffer (the module's
-            # eval-mode encode, state_dict and checkpoints read the module's buffers)
-            if sl.running_mean.data_ptr() != bn.running_mean.data_ptr():
-                bn.running_mean.copy_(sl.running_mean)
-                bn.running_var.copy_(sl.running_var)
+        self._sync_module_batchnorms()
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -584,14 +526,12 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
 
     def precompute_embeddings_from_tokens(self):
         if self.entity_embedding_from_tokens is None:
-            was_training = self.training
             super().train(False)                       # the reference calls self.eval() here and stays in eval mode
             dev = self.entity_embedding.weight.device
             ar = lambda n: torch.arange(n, dtype=torch.int32, device=dev)      # noqa: E731
             with torch.no_grad():                      # model.py:682: the precomputed tables carry no graph
                 self.entity_embedding_from_tokens = self._encode(ar(self.train_data.entities_size), False, H.STREAM_CAND).squeeze(1)
                 self.relations_embedding_from_tokens = self._encode(ar(self.train_data.relations_size), True, H.STREAM_SP_REL).squeeze(1)
-            del was_training
 
     def get_all_subj(self):
         self.precompute_embeddings_from_tokens()
@@ -681,24 +621,14 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
             parts_e.append(self.encode_subj(batch.sp_subj).squeeze(1))
             parts_r.append(self.encode_rel(batch.sp_rel).squeeze(1))
         EV, RV = torch.cat(parts_e).contiguous(), torch.cat(parts_r).contiguous()
-        ar = lambda a, b: torch.arange(a, b, dtype=torch.int32, device=dev)        # noqa: E731
-        vb = H.PrefixBatch(po_rel=ar(0, n_po) if n_po else None, po_obj=ar(n_c, n_c + n_po) if n_po else None,
-                           sp_subj=ar(n_c + n_po, n_c + n_po + n_sp) if n_sp else None, sp_rel=ar(n_po, n_po + n_sp) if n_sp else None,
-                           pos_row=batch.pos_row, pos_col=batch.pos_col, cand_first=0, n_cand=n_c)
+        vb = VT.VirtualTables(dev).batch(n_c, n_po, n_sp, batch.pos_row, batch.pos_col)
         return eng.forward_backward(EV, RV, self.scorer_name, vb, None, None, loss=loss, label_smoothing=label_smoothing,
                                     normalizer=1.0, scores=scores, loss_only=True)
 
     def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0):
         """The training driver for this model: shares the module's parameters (updated in place)."""
         self.flush_steps()                 # an earlier driver (another epoch's learning rate, ...) may still owe decay-only steps
-        slots = []
-        for emb, tok, bn in ((self.entity_embedding, self.entity_token_ids, self.entity_batchnorm),
-                             (self.relation_embedding, self.relation_token_ids, self.relation_batchnorm)):
-            s = TokenSlot(emb.weight.data, tok, self.pool, bn is not None, None if bn is None else bn.weight.data,
-                          None if bn is None else bn.bias.data)
-            if bn is not None:
-                s.running_mean, s.running_var = bn.running_mean, bn.running_var
-            slots.append(s)
+        slots = self._module_slots()
         st = TokenPooledTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
                                   label_smoothing=label_smoothing, dropout=self.entity_dropout, seed=self.dropout_seed)
         if self.entity_batchnorm is not None:

@@ -19,6 +19,7 @@ import os
 from . import _native as N
 from . import hotpath as H
 from .metrics import MetricResult
+from .virtual_tables import VirtualTables
 
 CALLER_THREAD_BACKWARD = os.environ.get("OKGE_BACKWARD_ON_CALLER_THREAD", "1") == "1"
 FAST_CALL = os.environ.get("OKGE_DROPIN_FAST", "1") == "1"      # persistent argument structs for the common training call
@@ -48,8 +49,8 @@ def _flat(t):
 
 
 class _VirtualTablesLossFn(torch.autograd.Function):
-    """Loss of already ENCODED rows (embedder variants that fall through to torch): the rows of one batch form two small
-    virtual tables -- EV = [candidates | po objects | sp subjects], RV = [po relations | sp relations] -- the fused HIP
+    """Loss of already ENCODED rows (embedder variants that fall through to torch): the rows of one batch form the two small
+    virtual tables EV / RV and `vb` names positions in them (virtual_tables.py defines the layout) -- the fused HIP
     step runs on them without dropout (it was applied by the encode) and returns the dense row gradients, which autograd
     carries back through the projection / batch-norm / normalisation into the parameters."""
 
@@ -288,7 +289,7 @@ class AddLossModule(nn.Module):
         two directions then run as two fused calls whose losses add (reduction='sum' is a plain sum over rows)."""
         dev = m.entity_embedding.weight.device
         n_po, n_sp, n_c = batch.n_po, batch.n_sp, batch.n_candidates
-        ar = lambda a, b: torch.arange(a, b, dtype=torch.int32, device=dev)        # noqa: E731
+        vt = VirtualTables(dev)                                                     # (one arange for the call's position batches)
         calls = []                                                                  # (EV, RV, virtual batch, output rows)
         with torch.set_grad_enabled(want_grad):
             if per_direction:
@@ -308,14 +309,14 @@ class AddLossModule(nn.Module):
                     rel = m.encode_rel(batch.po_rel).reshape(n_po, -1)
                     obj = m.encode_obj(batch.po_obj).reshape(n_po, -1)
                     prow, pcol = direction_positives(in_po, 0)
-                    vb = H.PrefixBatch(po_rel=ar(0, n_po), po_obj=ar(n_c, n_c + n_po), pos_row=prow, pos_col=pcol, cand_first=0, n_cand=n_c)
+                    vb = vt.batch(n_c, n_po, 0, prow, pcol)
                     calls.append((torch.cat([cand, obj]), rel, vb, slice(0, n_po)))
                 if n_sp:
                     subj = m.encode_subj(batch.sp_subj).reshape(n_sp, -1)
                     rel = m.encode_rel(batch.sp_rel).reshape(n_sp, -1)
                     cand = m.get_all_obj().reshape(n_c, -1)
                     prow, pcol = direction_positives(~in_po, n_po)
-                    vb = H.PrefixBatch(sp_subj=ar(n_c, n_c + n_sp), sp_rel=ar(0, n_sp), pos_row=prow, pos_col=pcol, cand_first=0, n_cand=n_c)
+                    vb = vt.batch(n_c, 0, n_sp, prow, pcol)
                     calls.append((torch.cat([cand, subj]), rel, vb, slice(n_po, n_po + n_sp)))
             else:
                 if all_entities:
@@ -323,7 +324,8 @@ class AddLossModule(nn.Module):
                 elif batch.cand_ids is not None:
                     cand = m.precompute_batch_shared_inputs(batch.cand_ids)
                 else:
-                    cand = m.precompute_batch_shared_inputs(ar(batch.cand_first, batch.cand_first + n_c))
+                    cand = m.precompute_batch_shared_inputs(torch.arange(batch.cand_first, batch.cand_first + n_c, dtype=torch.int32,
+                                                                         device=dev))
                 parts_e, parts_r = [cand.reshape(n_c, -1)], []
                 if n_po:
                     parts_r.append(m.encode_rel(batch.po_rel).reshape(n_po, -1))
@@ -331,10 +333,7 @@ class AddLossModule(nn.Module):
                 if n_sp:
                     parts_e.append(m.encode_subj(batch.sp_subj).reshape(n_sp, -1))
                     parts_r.append(m.encode_rel(batch.sp_rel).reshape(n_sp, -1))
-                vb = H.PrefixBatch(po_rel=ar(0, n_po) if n_po else None, po_obj=ar(n_c, n_c + n_po) if n_po else None,
-                                   sp_subj=ar(n_c + n_po, n_c + n_po + n_sp) if n_sp else None,
-                                   sp_rel=ar(n_po, n_po + n_sp) if n_sp else None,
-                                   pos_row=batch.pos_row, pos_col=batch.pos_col, cand_first=0, n_cand=n_c)
+                vb = vt.batch(n_c, n_po, n_sp, batch.pos_row, batch.pos_col)
                 calls.append((torch.cat(parts_e), torch.cat(parts_r), vb, slice(0, n_po + n_sp)))
         hook_loss = m.after_batch_loss_hook(epoch)
         eng = m.engine()

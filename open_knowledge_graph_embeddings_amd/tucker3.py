@@ -4,15 +4,13 @@
     M_b = reshape(W rho_b, (d, d))        W = relation_projection.0.weight (d^2, r_e), rho = rows of the (|R|, r_e) relation table
     sp:  q_b = e_b^T M_b      po:  q_b = M_b e_b      scores[b, :] = q_b . Cand^T
 
-Everything from q on is the tile kernels' work on a caller-supplied query block (okge_train_tiles / okge_score_queries /
+Everything from q on is the tile kernels' work on a caller-supplied query block (HotPath.train_tiles / okge_score_queries /
 okge_row_logsumexp / okge_evaluate_fused_shard; the tables descriptor they get names the ENTITY table twice -- the relation slot
 of the descriptor is never dereferenced by these calls -- and the DistMult scorer id, which they do not look at).  In front of
 them: okge_encode_rows (masked prefix rows) -> okge_tucker3_fold; behind them: okge_tucker3_backward -> okge_scatter_rows.
 M (B, d^2) is never materialised on the training path.
 """
 from __future__ import annotations
-
-import ctypes
 
 import torch
 
@@ -22,9 +20,6 @@ from .model import LookupBaseRelationEmbedder, Models, PAD, RelationEmbedder, Re
 
 MAX_SLOT = 256                                     # d and r_e the fold / backward kernels take
 TILE_SCORER = "distmult"                           # (not looked at by the query-block calls; DistMult has no even-d rule)
-
-
-_i32 = H._i32
 
 
 class Tucker3Kernels:
@@ -145,10 +140,7 @@ class Tucker3TrainStep:
         given = (batch.drop_cand, batch.drop_po_ent, batch.drop_po_rel, batch.drop_sp_ent, batch.drop_sp_rel)
         if any(g.p > 0 for g in given) or not training:
             return given if training else (H.NO_DROP,) * 5
-        s, t = self.seed, self.steps
-        DE = lambda stream: H.DropoutSpec(self.dropout, s, stream, t)              # noqa: E731
-        DR = lambda stream: H.DropoutSpec(self.relation_dropout, s, stream, t)     # noqa: E731
-        return DE(H.STREAM_CAND), DE(H.STREAM_PO_ENT), DR(H.STREAM_PO_REL), DE(H.STREAM_SP_ENT), DR(H.STREAM_SP_REL)
+        return H.dropout_specs(self.dropout, self.relation_dropout, self.seed, self.steps)
 
     def encode_and_fold(self, batch, drops):
         """masked prefix rows of the batch (okge_encode_rows, per direction: each has its own mask stream) -> query block"""
@@ -157,11 +149,11 @@ class Tucker3TrainStep:
         self._buffers(n_po + n_sp)
         _, d_po_e, d_po_r, d_sp_e, d_sp_r = drops
         if n_po:
-            eng.encode_rows(self.E, _i32(batch.po_obj, dev), drop=d_po_e, out=self.ent_rows[:n_po])
-            eng.encode_rows(self.R, _i32(batch.po_rel, dev), drop=d_po_r, out=self.rel_rows[:n_po])
+            eng.encode_rows(self.E, H._i32(batch.po_obj, dev), drop=d_po_e, out=self.ent_rows[:n_po])
+            eng.encode_rows(self.R, H._i32(batch.po_rel, dev), drop=d_po_r, out=self.rel_rows[:n_po])
         if n_sp:
-            eng.encode_rows(self.E, _i32(batch.sp_subj, dev), drop=d_sp_e, out=self.ent_rows[n_po:])
-            eng.encode_rows(self.R, _i32(batch.sp_rel, dev), drop=d_sp_r, out=self.rel_rows[n_po:])
+            eng.encode_rows(self.E, H._i32(batch.sp_subj, dev), drop=d_sp_e, out=self.ent_rows[n_po:])
+            eng.encode_rows(self.R, H._i32(batch.sp_rel, dev), drop=d_sp_r, out=self.rel_rows[n_po:])
         return self.kernels.fold(self.W, self.ent_rows, self.rel_rows, n_po, n_sp, self.Q)
 
     def _cand_batch(self, batch, drop_cand):
@@ -169,30 +161,14 @@ class Tucker3TrainStep:
                              n_cand=batch.n_cand, cand_unique=batch.cand_unique, drop_cand=drop_cand)
 
     def _tiles(self, cb, B, normalizer, loss_only, grads_zero=True):
-        """okge_train_tiles on the folded queries: loss, candidate gradients into dE, dQ"""
-        eng, dev = self.engine, self.device
-        E = self.E
-        n = cb.n_candidates
+        """the tile kernels on the folded queries (HotPath.train_tiles): loss, candidate gradients into dE, dQ"""
+        eng, E = self.engine, self.E
         row_lse = None
         if self.loss == "kl":
             row_lse = eng.row_logsumexp(E, E, TILE_SCORER, self.Q, B, cb, self.shard)
-        pb, c, keep = eng._batch(cb)
-        t = eng._tables(E, E, TILE_SCORER)
-        ws = eng.workspace(B, n, self.d)
-        pos = N.Positives()
-        prow, pcol = _i32(cb.pos_row, dev), _i32(cb.pos_col, dev)
-        pos.row, pos.col, pos.nnz = H._ptr(prow), H._ptr(pcol), cb.nnz
-        sh = self.shard.c()
-        flags = (N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0) | (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) | \
-                (N.OKGE_TRAIN_UNIQUE_CANDIDATES if cb.cand_unique else 0)
-        N.check(self.engine.lib.okge_train_tiles(
-            ctypes.byref(t), ctypes.byref(sh), self.Q.data_ptr(), self.Q.stride(0), B, ctypes.byref(c), ctypes.byref(pos),
-            N.LOSSES[self.loss], float(self.label_smoothing if self.loss == "bce" else 0.0),
-            float(normalizer if normalizer is not None else float(B) * float(n)), int(n), flags, H._ptr(row_lse),
-            self.loss_out.data_ptr(), self.dE.data_ptr(), self.dQ.data_ptr(), ws.data_ptr(), eng._ws_bytes, eng._stream()),
-            "okge_train_tiles")
-        del keep, prow, pcol
-        return self.loss_out
+        return eng.train_tiles(E, E, TILE_SCORER, self.Q, cb, self.shard, self.dE, self.dQ, cb.n_candidates, loss=self.loss,
+                               label_smoothing=self.label_smoothing if self.loss == "bce" else 0.0, normalizer=normalizer,
+                               loss_out=self.loss_out, grads_zero=grads_zero, row_lse=row_lse, loss_only=loss_only, B=B)
 
     # -- the step --------------------------------------------------------------------------------------------------------
     def step(self, batch: H.PrefixBatch, normalizer=None):
@@ -217,11 +193,11 @@ class Tucker3TrainStep:
         self.kernels.backward(self.W, self.ent_rows, self.rel_rows, self.dQ, n_po, n_sp, self.d_ent, self.d_rel, self.dW, fresh=not accumulate)
         _, d_po_e, d_po_r, d_sp_e, d_sp_r = drops
         if n_po:
-            eng.scatter_rows(self.d_ent[:n_po], _i32(batch.po_obj, dev), 0, self.dE, d_po_e)
-            eng.scatter_rows(self.d_rel[:n_po], _i32(batch.po_rel, dev), 0, self.dR, d_po_r)
+            eng.scatter_rows(self.d_ent[:n_po], H._i32(batch.po_obj, dev), 0, self.dE, d_po_e)
+            eng.scatter_rows(self.d_rel[:n_po], H._i32(batch.po_rel, dev), 0, self.dR, d_po_r)
         if n_sp:
-            eng.scatter_rows(self.d_ent[n_po:], _i32(batch.sp_subj, dev), 0, self.dE, d_sp_e)
-            eng.scatter_rows(self.d_rel[n_po:], _i32(batch.sp_rel, dev), 0, self.dR, d_sp_r)
+            eng.scatter_rows(self.d_ent[n_po:], H._i32(batch.sp_subj, dev), 0, self.dE, d_sp_e)
+            eng.scatter_rows(self.d_rel[n_po:], H._i32(batch.sp_rel, dev), 0, self.dR, d_sp_r)
         return self.loss_out
 
     def loss_only(self, batch: H.PrefixBatch, scores=None, normalizer=1.0):

@@ -1,0 +1,124 @@
+"""The "virtual tables" of a batch whose rows are ENCODED (pooled, LSTM-encoded, projected ...) instead of looked up, and
+the training-step skeleton on top of them.  This module is the one place that knows the layout:
+
+    EV = [candidates | po objects | sp subjects]   (N + n_po + n_sp rows)        RV = [po relations | sp relations]
+
+The unchanged fused step (score -> loss -> backward, dropout included) runs on EV / RV as if they were embedding tables, with
+a PrefixBatch of row POSITIONS in place of ids: candidates are the range 0..N-1, every prefix names its own row.  Every row of
+the two tables is then one candidate or one batch row, so the call STORES every gradient row (grads_zero: candidate rows by
+the tile kernel; distinct_prefix_rows: prefix rows by the prefix backward) and nothing is cleared per step.  Either direction
+may be empty.  Nothing here launches a kernel of its own; it works on any torch device.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import hotpath as H
+
+
+def row_ranges(n_cand, n_po, n_sp):
+    """Rows of the five encode calls, in the reference's call order (trainer.py:75-91): candidates, po relations, po objects,
+    sp subjects, sp relations -- the 1st, 3rd and 4th are rows of EV, the 2nd and 5th rows of RV."""
+    B = n_po + n_sp
+    return slice(0, n_cand), slice(0, n_po), slice(n_cand, n_cand + n_po), slice(n_cand + n_po, n_cand + B), slice(n_po, B)
+
+
+def encode_calls(batch: H.PrefixBatch):
+    """The five encode calls of a batch in that order: (relation slot?, ids or None, first id, rows of EV / RV)."""
+    cand, po_rel, po_obj, sp_subj, sp_rel = row_ranges(batch.n_candidates, batch.n_po, batch.n_sp)
+    return ((False, batch.cand_ids, batch.cand_first, cand), (True, batch.po_rel, 0, po_rel), (False, batch.po_obj, 0, po_obj),
+            (False, batch.sp_subj, 0, sp_subj), (True, batch.sp_rel, 0, sp_rel))
+
+
+class VirtualTables:
+    """Position batches and the growing row buffers of one user (a step, a module) on one device."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._arange = torch.empty(0, dtype=torch.int32, device=self.device)
+        self._key, self._positions, self._bufs = None, None, None
+
+    def batch(self, n_cand, n_po, n_sp, pos_row, pos_col, drops=None):
+        """The PrefixBatch of positions over EV / RV; positives pass through.  drops: hotpath.dropout_specs(...), or None when
+        the encode already applied the dropout.  The positions depend on the shape only: views of one arange, kept for the next
+        call of the same shape (four arange launches per step otherwise: 18 us of a 0.9 ms token-pooled step at configs[4])."""
+        key = (n_cand, n_po, n_sp)
+        if self._key != key:
+            if self._arange.numel() < n_cand + n_po + n_sp:
+                self._arange = torch.arange(0, n_cand + n_po + n_sp, dtype=torch.int32, device=self.device)
+            rng = self._arange
+            self._key, self._positions = key, tuple(rng[rows] if rows.stop > rows.start else None for rows in row_ranges(*key)[1:])
+        po_rel, po_obj, sp_subj, sp_rel = self._positions
+        cand, po_ent, po_r, sp_ent, sp_r = drops or (H.NO_DROP,) * 5
+        return H.PrefixBatch(po_rel=po_rel, po_obj=po_obj, sp_subj=sp_subj, sp_rel=sp_rel, pos_row=pos_row, pos_col=pos_col,
+                             cand_first=0, n_cand=n_cand, drop_cand=cand, drop_po_ent=po_ent, drop_po_rel=po_r,
+                             drop_sp_ent=sp_ent, drop_sp_rel=sp_r)
+
+    def buffers(self, n_cand, n_po, n_sp, d):
+        """EV, EX, dEV, RV, RX, dRV trimmed to the batch's rows: encoded rows (after batch-norm), raw rows (before it), row
+        gradients.  Reallocated (zeroed) only when a batch needs more rows than any before it."""
+        rows = (n_cand + n_po + n_sp,) * 3 + (n_po + n_sp,) * 3
+        if self._bufs is None or any(n > b.shape[0] for n, b in zip(rows, self._bufs)):
+            self._bufs = tuple(torch.zeros((n, d), device=self.device) for n in rows)
+        return tuple(b[:n] for b, n in zip(self._bufs, rows))
+
+
+class VirtualTableStep:
+    """Skeleton of a training step that encodes a batch's rows into virtual tables: count the step, get the buffers, `_encode`,
+    the fused call on the virtual tables, `_backward`.  A subclass brings optimizer_step() and the two hooks:
+        _encode(batch, bufs) -> saved  fill EX / RX (and EV / RV behind a batch-norm) with the batch's rows
+        _backward(batch, bufs, saved)  carry dEV / dRV back through the encoder into the slots' gradients
+    entity / relation are its slots (.W, .d, .bn or None).  dropout is the entity streams', relation_dropout (default: the
+    same) the relation streams' drop probability."""
+
+    def __init__(self, entity, relation, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0,
+                 dropout=0.0, relation_dropout=None, seed=0, engine=None):
+        self.entity, self.relation, self.scorer, self.loss = entity, relation, scorer, loss
+        self.lr, self.weight_decay, self.eps, self.label_smoothing = lr, weight_decay, eps, label_smoothing
+        self.dropout = dropout
+        self.relation_dropout = dropout if relation_dropout is None else relation_dropout
+        self.seed, self.steps = seed, 0
+        self.device = entity.W.device
+        self.engine = engine or H.HotPath(self.device)
+        self.tables = VirtualTables(self.device)
+        self.loss_out = torch.zeros(1, dtype=torch.float64, device=self.device)
+        self.step_dev = None              # device step counter, attached by GraphedTrainStep
+        self.module_batchnorms = ()       # ((slot, nn.BatchNorm1d), ...) of an attached module, set by its train_step()
+        self._in_step = False
+
+    def step(self, batch: H.PrefixBatch, normalizer=None):
+        """`batch` carries ENTITY / RELATION ids exactly as for the lookup models."""
+        self._in_step = True
+        try:
+            loss = self.forward_backward(batch, normalizer)
+        finally:
+            self._in_step = False
+        self.optimizer_step()
+        return loss
+
+    def forward_backward(self, batch: H.PrefixBatch, normalizer=None, scores=None):
+        """Leaves the dense gradients in the slots (what `_backward` writes); returns the summed loss, a device double[1]."""
+        self.steps += 1
+        shape = (batch.n_candidates, batch.n_po, batch.n_sp)
+        bufs = self.tables.buffers(*shape, self.entity.d)
+        saved = self._encode(batch, bufs)
+        EV, EX, dEV, RV, RX, dRV = bufs
+        vb = self.tables.batch(*shape, batch.pos_row, batch.pos_col,
+                               H.dropout_specs(self.dropout, self.relation_dropout, self.seed, self.steps, self.step_dev))
+        self.engine.forward_backward(EV if self.entity.bn is not None else EX, RV if self.relation.bn is not None else RX,
+                                     self.scorer, vb, dEV, dRV, loss=self.loss, label_smoothing=self.label_smoothing,
+                                     normalizer=normalizer, loss_out=self.loss_out, scores=scores, grads_zero=True,
+                                     distinct_prefix_rows=True)
+        self._backward(batch, bufs, saved)
+        return self.loss_out
+
+    def _sync_module_batchnorms(self):
+        """after an optimizer step: keep an attached nn.Module's batch-norm parameters current"""
+        for sl, bn in self.module_batchnorms:
+            bn.weight.data.copy_(sl.bn[:sl.d])
+            bn.bias.data.copy_(sl.bn[sl.d:])
+            # ... and its running statistics, once ReplicaStep.rebind has moved ours into the exchange buffer (the module's
+            # eval-mode encode, state_dict and checkpoints read the module's buffers)
+            if sl.running_mean.data_ptr() != bn.running_mean.data_ptr():
+                bn.running_mean.copy_(sl.running_mean)
+                bn.running_var.copy_(sl.running_var)
