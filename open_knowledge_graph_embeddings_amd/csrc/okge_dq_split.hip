@@ -87,12 +87,7 @@ __global__ __launch_bounds__(512, 2) void dq8s_kernel(const DqArgs a)
 template <int KB>
 static hipError_t launch_dq8s_t(const DqArgs &a, int grid_x, hipStream_t st)
 {
-    auto k = dq8s_kernel<KB>;
-    const size_t shmem = DqSplit<KB>::LDS_BYTES;
-    static LdsOptIn lds_opt_in;
-    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), shmem); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid_x), dim3(512), shmem, st, a);
-    return hipGetLastError();
+    return launch_with_lds<dq8s_kernel<KB>>(dim3(grid_x), dim3(512), DqSplit<KB>::LDS_BYTES, st, a);
 }
 
 hipError_t launch_dq8s(const DqArgs &a, int grid_x, hipStream_t st)

@@ -6,6 +6,7 @@
 #pragma once
 #include "okge_device.h"
 #include "okge_kernels.h"
+#include "okge_tile.h"
 
 namespace okge {
 
@@ -197,7 +198,7 @@ __device__ __forceinline__ void eval_points_block(const EvalPointsArgs &a, int b
         col = (int)checked_row(col, a.n_cand_global, p.id_err);
         const int loc = col - a.col_lo;
         if (loc < 0 || loc >= a.n_cand) return nullptr;
-        const int64_t cid = checked_row(a.cand_ids ? (int64_t)a.cand_ids[loc] : (int64_t)a.cand_first + loc, a.table_rows, p.id_err);
+        const int64_t cid = cand_table_row(a.cand_ids, a.cand_first, loc, a.table_rows, p.id_err);
         return a.E + cid * d;
     };
     for (int64_t g = g0; g < g_hi; g += nthr) {

@@ -9,8 +9,8 @@
 
 namespace okge {
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE setting: every launcher keeps one of these as a
-// function-local static and opts the kernel in once per device (and again if a larger size is asked for), keyed by
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE setting: launch_with_lds keeps one of these per kernel
+// and opts the kernel in once per device (and again if a larger size is asked for), keyed by
 // hipGetDevice() -- one process per GPU is the normal deployment, but a process driving two devices must work too.
 struct LdsOptIn {
     std::atomic<size_t> bytes[64];
@@ -27,6 +27,18 @@ inline hipError_t ensure_dynamic_lds(LdsOptIn &state, const void *kernel, size_t
     if (e == hipSuccess) state.bytes[dev].store(shmem, std::memory_order_release);
     return e;
 }
+#ifdef __HIPCC__
+// Launch of a kernel that may need more dynamic LDS than the default limit.  One instantiation, hence one opt-in state, per
+// kernel.
+template <auto Kernel, class Args>
+inline hipError_t launch_with_lds(dim3 grid, dim3 block, size_t shmem, hipStream_t st, const Args &args)
+{
+    static LdsOptIn lds_opt_in;
+    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(Kernel), shmem); e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, grid, block, shmem, st, args);
+    return hipGetLastError();
+}
+#endif
 
 constexpr int NT = 64;             // candidate rows per tile
 constexpr int BC = 64;             // batch rows per chunk

@@ -11,6 +11,7 @@
 
 #include "okge_device.h"
 #include "okge_kernels.h"
+#include "okge_tile.h"
 #include "okge_eval_device.h"
 
 namespace okge {
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void dc_reduce_kernel(const float *__restrict_
         const float4 v = *reinterpret_cast<const float4 *>(slab + ((size_t)sidx * rows_pad + n) * D16 + k);
         acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
-    const int64_t cid = checked_row(cand_ids ? (int64_t)cand_ids[n] : (int64_t)cand_first + n, table_rows, id_err);
+    const int64_t cid = cand_table_row(cand_ids, cand_first, n, table_rows, id_err);
     float *dst = dE + cid * d + k;
     const float v[4] = {acc.x, acc.y, acc.z, acc.w};
 #pragma unroll
@@ -252,7 +253,7 @@ __global__ __launch_bounds__(256) void dc_reduce_streamk_kernel(const float *__r
             const float4 v = *reinterpret_cast<const float4 *>(slab + ((size_t)slots[j] * 64 + r) * D16 + k);
             acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
         }
-        const int64_t cid = checked_row(cand_ids ? (int64_t)cand_ids[n] : (int64_t)cand_first + n, table_rows, k ? nullptr : id_err);
+        const int64_t cid = cand_table_row(cand_ids, cand_first, n, table_rows, k ? nullptr : id_err);
         float *dst = dE + cid * d + k;
         const float v[4] = {acc.x, acc.y, acc.z, acc.w};
 #pragma unroll

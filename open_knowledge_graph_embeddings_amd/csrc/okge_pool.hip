@@ -1233,11 +1233,7 @@ hipError_t launch_pool_backward_calls(const PoolCall *calls, int n_calls, int *i
             hipLaunchKernelGGL(bn_finish_kernel<2>, dim3(p2.cum[nb]), dim3(256), 0, st, p2, no_plan, p2.cum[nb]);
         }
         const PoolBatch p3 = make_batch(calls, n_calls, id_err, [](const PoolCall &q) { return (q.n + POOL_BWD_ROWS - 1) / POOL_BWD_ROWS; });
-        static LdsOptIn lds_a;
-        const size_t shmem = sizeof(float) * HOT_TOKENS * dmax;
-        if (hipError_t e = ensure_dynamic_lds(lds_a, reinterpret_cast<const void *>(&pool_backward_kernel), shmem)) return e;
-        hipLaunchKernelGGL(pool_backward_kernel, dim3(p3.cum[n_calls] + (nb ? 1 : 0)), dim3(256), shmem, st, p3);
-        return hipGetLastError();
+        return launch_with_lds<pool_backward_kernel>(dim3(p3.cum[n_calls] + (nb ? 1 : 0)), dim3(256), sizeof(float) * HOT_TOKENS * dmax, st, p3);
     }
     // ---- scatter plan
     ScatterBatch sb;

@@ -33,6 +33,7 @@
 
 #include "okge_device.h"
 #include "okge_kernels.h"
+#include "okge_tile.h"
 
 namespace okge {
 
@@ -50,7 +51,7 @@ __device__ __forceinline__ void load_cand_tile(float *Cs, const float *__restric
     const int r = tid >> 3, n = n0 + r;
     const bool valid = n < N;
     int64_t cid = 0;
-    if (valid) cid = checked_row(cand_ids ? (int64_t)cand_ids[n] : (int64_t)cand_first + n, table_rows, (tid & 7) ? nullptr : id_err);
+    if (valid) cid = cand_table_row(cand_ids, cand_first, n, table_rows, (tid & 7) ? nullptr : id_err);
     const float *row = E + cid * d;
     float4 v0[NOIT], v1[NOIT];
     if (vec_ok) {
@@ -94,30 +95,30 @@ __device__ __forceinline__ void load_cand_tile(float *Cs, const float *__restric
     }
 }
 
-// acc[kbi] += A^T-style gradient product over 64 contraction rows held in LDS.
-//   arow : &A[0][out_row(lane)] element for contraction row 0, slot offset included by caller = base + (16*s)*lda
-//   brow : &B[16*s][0] + lane column offset handled here
-// Contraction row of (slot s, step t) is 16*s + t.  A is read 4 steps at a time when A_VEC (A stored with
-// the contraction index contiguous), else one ds_read_b32 per step.
-template <int KB, bool A_VEC, int LDK = lds_ld(16 * KB), int T0 = 0, int T1 = 16>   // LDK: leading dimension of the B tile (wider
-__device__ __forceinline__ void grad_product(v4f (&acc)[KB], const float *a_base, int lda, const float *b_base,   // than 16*KB when a
-                                             int c)                            // wave takes a column range of it); steps T0 .. T1-1
+// acc[kbi] += A^T-style gradient product over 4 * STEPS contraction rows held in LDS.
+//   a_base : &A[STEPS*s][out_row(lane)], the slot's first contraction row (slot offset included by the caller)
+//   b_base : &B[STEPS*s][0]; the lane's column offset is handled here
+// Contraction row of (slot s, step t) is STEPS*s + t, t < STEPS.
+// A[row][out] is read with one ds_read_b32 per step.  LDK: leading dimension of the B tile (wider than 16*KB when a wave
+// takes a column range of it).
+template <int KB, int LDK, int STEPS>
+__device__ __forceinline__ void grad_product(v4f (&acc)[KB], const float *a_base, int lda, const float *b_base, int c)
 {
     constexpr int KQ = KB / 4, KR = KB % 4;
-    // b_base points at B[16*s][0].  Operands of step t+1 are requested before the KB MFMAs of step t issue.
+    // Operands of step t+1 are requested before the KB MFMAs of step t issue.
     v4f pb[KQ > 0 ? KQ : 1], nb[KQ > 0 ? KQ : 1];
     float pr[KR > 0 ? KR : 1], nr[KR > 0 ? KR : 1];
     float pa, na = 0.f;
-    auto a_at = [&](int t) { return A_VEC ? a_base[t] : a_base[t * lda]; };   // A[out][16s + t]  |  A[16s + t][out]
+    auto a_at = [&](int t) { return a_base[t * lda]; };   // A[slot's row t][out]
 #pragma unroll
-    for (int kq = 0; kq < KQ; ++kq) pb[kq] = *reinterpret_cast<const v4f *>(b_base + T0 * LDK + 64 * kq + 4 * c);
+    for (int kq = 0; kq < KQ; ++kq) pb[kq] = *reinterpret_cast<const v4f *>(b_base + 64 * kq + 4 * c);
 #pragma unroll
-    for (int r = 0; r < KR; ++r) pr[r] = b_base[T0 * LDK + 64 * KQ + 16 * r + c];
-    pa = a_at(T0);
+    for (int r = 0; r < KR; ++r) pr[r] = b_base[64 * KQ + 16 * r + c];
+    pa = a_at(0);
     __builtin_amdgcn_sched_group_barrier(0x100, KQ + KR + 1, 2);
 #pragma unroll
-    for (int t = T0; t < T1; ++t) {
-        if (t + 1 < T1) {
+    for (int t = 0; t < STEPS; ++t) {
+        if (t + 1 < STEPS) {
             const float *brow = b_base + (t + 1) * LDK;
 #pragma unroll
             for (int kq = 0; kq < KQ; ++kq) nb[kq] = *reinterpret_cast<const v4f *>(brow + 64 * kq + 4 * c);
@@ -134,7 +135,7 @@ __device__ __forceinline__ void grad_product(v4f (&acc)[KB], const float *a_base
         }
 #pragma unroll
         for (int r = 0; r < KR; ++r) acc[4 * KQ + r] = mfma16(pa, pr[r], acc[4 * KQ + r]);
-        if (t + 1 < T1) {
+        if (t + 1 < STEPS) {
 #pragma unroll
             for (int kq = 0; kq < KQ; ++kq) pb[kq] = nb[kq];
 #pragma unroll
@@ -144,14 +145,6 @@ __device__ __forceinline__ void grad_product(v4f (&acc)[KB], const float *a_base
         }
         __builtin_amdgcn_sched_group_barrier(0x008, KB, 2);                // then this step's MFMAs
     }
-}
-
-// Column held by lane column-index c of accumulator block kbi (see "Operand feeding" above).
-template <int KB>
-__device__ __forceinline__ int grad_col(int kbi, int c)
-{
-    constexpr int KQ = KB / 4;
-    return kbi < 4 * KQ ? 64 * (kbi >> 2) + 4 * c + (kbi & 3) : 64 * KQ + 16 * (kbi - 4 * KQ) + c;
 }
 
 // Score / stats / count sweep of one 64-candidate tile over the batch in chunks of 64 rows: ONE 8-wave workgroup per CU
@@ -439,7 +432,7 @@ __global__ __launch_bounds__(512, 2) void dq8k_kernel(const DqArgs a)
     const int ch_lo = (int)((int64_t)split * nchunks / a.nsplit);
     const int ch_hi = (int)((int64_t)(split + 1) * nchunks / a.nsplit);
 
-    v4f acc[KBW];                                     // dQ[b = b0 + 16wq + 4s + i][k = 16 KBW ks + grad_col(kbi, c)]
+    v4f acc[KBW];                                     // dQ[b = b0 + 16wq + 4s + i][k = 16 KBW ks + 64 (kbi >> 2) + 4 c + (kbi & 3)]
 #pragma unroll
     for (int kb = 0; kb < KBW; ++kb) acc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
 
@@ -477,7 +470,7 @@ __global__ __launch_bounds__(512, 2) void dq8k_kernel(const DqArgs a)
             if (ch + 1 + NSET < ch_hi) prefetch(ch + 1 + NSET, nxt);
         }
         // A[i = b][slot s, step t] = G^T[n = 8s + t][b = 16wq + c] ; B[slot][k] = C[n = 8s + t][16 KBW ks + k]
-        grad_product<KBW, false, LDK, 0, 8>(acc, Gt + buf * PAIR + 8 * s * LDGT + 16 * wq + c, LDGT,
+        grad_product<KBW, LDK, 8>(acc, Gt + buf * PAIR + 8 * s * LDGT + 16 * wq + c, LDGT,
                                             Cs + buf * PAIR + 8 * s * LDK + 16 * KBW * ks, c);
         if (ks == 1 && more) {                 // ... the other one after its MFMAs: a SIMD's two waves take turns
             park(buf ^ 1, nxt);
@@ -515,11 +508,7 @@ __global__ __launch_bounds__(512, 2) void dq8k_kernel(const DqArgs a)
 template <int KB, int MODE>
 static hipError_t launch_fused_t(const FusedArgs &a, dim3 grid, size_t shmem, hipStream_t st)
 {
-    auto k = fused_tile_kernel<KB, MODE>;
-    static LdsOptIn lds_opt_in;
-    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), shmem); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, grid, dim3(FUSED_THREADS), shmem, st, a);
-    return hipGetLastError();
+    return launch_with_lds<fused_tile_kernel<KB, MODE>>(grid, dim3(FUSED_THREADS), shmem, st, a);
 }
 
 template <int KB>
@@ -554,12 +543,8 @@ hipError_t launch_fused(int mode, const FusedArgs &a, int grid_x, int grid_y, hi
 template <int KB>
 static hipError_t launch_dq8k_t(const DqArgs &a, int grid_x, hipStream_t st)
 {
-    auto k = dq8k_kernel<KB>;
     const size_t sh = (size_t)2 * (32 * lds_ld(16 * KB) + 32 * LDGT) * sizeof(float);
-    static LdsOptIn lds_opt_in;
-    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), sh); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid_x), dim3(512), sh, st, a);
-    return hipGetLastError();
+    return launch_with_lds<dq8k_kernel<KB>>(dim3(grid_x), dim3(512), sh, st, a);
 }
 
 hipError_t launch_dq(const DqArgs &a, int grid_x, hipStream_t st)

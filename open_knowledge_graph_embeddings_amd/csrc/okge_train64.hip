@@ -25,16 +25,11 @@
 
 #include "okge_device.h"
 #include "okge_kernels.h"
+#include "okge_tile.h"
 
 namespace okge {
 
-constexpr int NT64 = 64, BC64 = 64, T64_THREADS = 512;
-
-template <int KB> struct Tile64Cfg {
-    static constexpr int LDK = lds_ld(16 * KB);
-    static constexpr int NO = 2 * KB;                         // 8-column octets per row
-    static constexpr int KEEP_LD = NO < 32 ? 32 : NO;         // keep-flag bytes per row (LDS and global)
-};
+constexpr int NT64 = TILE_N, BC64 = 64, T64_THREADS = TILE_THREADS;
 
 #ifdef OKGE_STAMPS
 // diagnostic build (tools/build_stamps.sh): workgroup placement + per-chunk phase timeline of wave 0
@@ -84,7 +79,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     int tl_n = 0;
 #endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using Cfg = Tile64Cfg<KB>;
+    using Cfg = TileCfg<KB>;
     constexpr int LDK = Cfg::LDK, NO = Cfg::NO, KEEP_LD = Cfg::KEEP_LD;
     constexpr int KQ = KB / 4, KR = KB % 4;
     constexpr int QG = 8;                                       // staging: column groups per row (512 threads / 64 rows)
@@ -118,6 +113,13 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             qreg[it] = (b < b_end) ? *reinterpret_cast<const v4f *>(src + 4 * q) : (v4f){0.f, 0.f, 0.f, 0.f};
         }
     };
+    auto park_chunk = [&](float *dst) {
+#pragma unroll
+        for (int it = 0; it < NQIT; ++it) {
+            const int q = q8 + QG * it;
+            if (q < NQ) *reinterpret_cast<v4f *>(dst + r8 * LDK + 4 * q) = qreg[it];
+        }
+    };
     const uint32_t dstep = a.drop_c.enabled ? drop_step(a.drop_c) : 0u;   // before the loads whose latency hides the masks
     fetch_chunk(b_begin);
 
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         const int n = n0 + r8;
         const bool valid = n < a.N;
         int64_t cid = 0;
-        if (valid) cid = checked_row(a.cand_ids ? (int64_t)a.cand_ids[n] : (int64_t)a.cand_first + n, a.n_table_rows, q8 ? nullptr : a.id_err);
+        if (valid) cid = cand_table_row(a.cand_ids, a.cand_first, n, a.n_table_rows, q8 ? nullptr : a.id_err);
         const float *row = a.E + cid * d;
         v4f v0[NOIT], v1[NOIT];
         if (vec_ok) {
@@ -169,8 +171,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         }
         __builtin_amdgcn_sched_barrier(0);
         // (after the mask arithmetic: vmcnt retires in order, so waiting for these loads waits for the rows as well)
-        for (int i = tid; i < pos_cached; i += T64_THREADS)
-            posc[i] = ((uint32_t)a.pos_row[pos_lo + i] << 6) | (uint32_t)(a.pos_col[pos_lo + i] - a.cand_col0 - n0);
+        cache_tile_positives(a, posc, pos_lo, pos_cached, n0, tid);
         if (tid < 3 * BC64 * 2) ybits3[tid] = 0u;
 #pragma unroll
         for (int it = 0; it < NOIT; ++it) {
@@ -226,11 +227,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             breg[KB - 1][1] = Cs[(16 * blk + c) * LDK + 16 * (KB - 1) + 4 + s];
         }
         cm_done = NOIT;                 // (written in the prologue)
-#pragma unroll
-        for (int it = 0; it < NQIT; ++it) {
-            const int q = q8 + QG * it;
-            if (q < NQ) *reinterpret_cast<v4f *>(Qs + r8 * LDK + 4 * q) = qreg[it];
-        }
+        park_chunk(Qs);
         if (b_begin + BC64 < b_end) fetch_chunk(b_begin + BC64);
     }
 
@@ -238,19 +235,8 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     // Three buffers in rotation: chunk i's bits are SET while chunk i-1's score product runs (they need no barrier of their
     // own: two lie between the set and the epilogue that reads them) and the buffer chunk i-1 used is cleared then too --
     // in the staging phase, between the two barriers of a chunk, nothing overlaps these dependent LDS round trips.
-    auto set_label_bits = [&](int bb, uint32_t *yb) {
-        for (int i = tid; i < pos_cached; i += T64_THREADS) {
-            const uint32_t v = posc[i];
-            const int row = (int)(v >> 6) - bb;
-            if (row >= 0 && row < BC64) atomicOr(&yb[BC64 * ((v >> 5) & 1u) + row], 1u << (v & 31u));
-        }
-        for (int q = pos_lo + POS_CACHE + tid; q < pos_hi; q += T64_THREADS) {      // overflow: rare
-            const int row = a.pos_row[q] - bb;
-            const int col = a.pos_col[q] - a.cand_col0 - n0;
-            if (row >= 0 && row < BC64) atomicOr(&yb[BC64 * (col >> 5) + row], 1u << (col & 31));
-        }
-    };
-    set_label_bits(b_begin, ybits3);        // chunk 0 (the three buffers were cleared before the prologue's barrier)
+    auto set_chunk_labels = [&](int bb, uint32_t *yb) { set_label_bits<BC64>(a, posc, pos_lo, pos_hi, pos_cached, n0, bb, yb, tid); };
+    set_chunk_labels(b_begin, ybits3);        // chunk 0 (the three buffers were cleared before the prologue's barrier)
     int par = 0;
     for (int b0 = b_begin; b0 < b_end; b0 += BC64, par = par == 2 ? 0 : par + 1) {
         uint32_t *ybits = ybits3 + par * (2 * BC64);
@@ -260,11 +246,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         TL_STAMP_AT(48 + ((b0 - b_begin) >> 6));   // chunk entered (the previous chunk's closing barrier passed)
         if (!REGC) {
             // ---- phase A: park the prefetched chunk, prefetch the next chunk -------------------------------------
-#pragma unroll
-            for (int it = 0; it < NQIT; ++it) {
-                const int q = q8 + QG * it;
-                if (q < NQ) *reinterpret_cast<v4f *>(Qs + r8 * LDK + 4 * q) = qreg[it];
-            }
+            park_chunk(Qs);
             TL_STAMP_AT(56 + ((b0 - b_begin) >> 6));   // query chunk parked
             if (b0 + BC64 < b_end) fetch_chunk(b0 + BC64);
             TL_STAMP_AT(72 + ((b0 - b_begin) >> 6));   // next chunk requested
@@ -275,7 +257,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         {   // under the score product: the next chunk's label bits, the buffer after that cleared, one group of masked rows out
             const int pn = par == 2 ? 0 : par + 1, pc = pn == 2 ? 0 : pn + 1;
             if (tid < 2 * BC64) ybits3[pc * (2 * BC64) + tid] = 0u;
-            if (b0 + BC64 < b_end) set_label_bits(b0 + BC64, ybits3 + pn * (2 * BC64));
+            if (b0 + BC64 < b_end) set_chunk_labels(b0 + BC64, ybits3 + pn * (2 * BC64));
             if (!REGC && b0 > b_begin && cm_done < NOIT) write_cm(cm_done++);
         }
 
@@ -341,7 +323,6 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         // ---- loss epilogue: G = dLoss/dX / normalizer, kept in registers --------------------------------------
         v4f g4[2];
         {
-            constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
             // label words of the wave's 2 x 4 rows, candidate half blk >> 1; the block's bit is 16 * (blk & 1) + c
             const uint32_t *yrow = ybits + BC64 * (blk >> 1) + 32 * h + 4 * s;
             const uint4 yw0 = *reinterpret_cast<const uint4 *>(yrow), yw1 = *reinterpret_cast<const uint4 *>(yrow + 16);
@@ -366,49 +347,28 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
                 for (int i = 0; i < 4; ++i) {
                     const float xv = x[i];
                     const bool pos = (yw[rg][i] >> ybit) & 1u;
-                    float gg, l;
-                    if (MODE == MODE_TRAIN_BCE) {
-                        // BCEWithLogits: max(x,0) - x*y + log1p(exp(-|x|)); d/dx = sigmoid(x) - y
-                        // v_exp_f32 / v_rcp_f32 / v_log_f32 (1 ulp each); 1 + e is in (1, 2]
+                    const int brow = b0 + 32 * h + 16 * rg + 4 * s + i;
+                    if (MODE == MODE_TRAIN_BCE && LOGPROD) {
                         const float y = pos ? a.y_pos : a.y_neg;
-                        const float e = __builtin_amdgcn_exp2f(-fabsf(xv) * LOG2E);
-                        float ope = 1.f + e;
-                        const float rcp = __builtin_amdgcn_rcpf(ope);
-                        const float sig = xv >= 0.f ? rcp : e * rcp;
-                        if (LOGPROD) {
-                            l = fmaxf(xv, 0.f) - xv * y;
-                            if (edge && !(nvalid && b0 + 32 * h + 16 * rg + 4 * s + i < b_end)) { l = 0.f; ope = 1.f; }
-                            lin += l;
-                            prod *= ope;
-                            g4[rg][i] = fmaf(sig, a.inv_norm, pos ? gy_pos : gy_neg);
-                            continue;
-                        }
-                        l = fmaxf(xv, 0.f) - xv * y + __builtin_amdgcn_logf(ope) * LN2;
-                        gg = sig - y;
-                    } else {
-                        // KLDiv(sum)(log_softmax(x), y), y in {0,1} unnormalised (trainer.py:99-101):
-                        // loss = -sum_pos log_softmax; d/dx = softmax * sum_n y - y
-                        const int b = min(b0 + 32 * h + 16 * rg + 4 * s + i, a.B - 1);
-                        const float lsm = xv - a.row_lse[b];
-                        l = pos ? -lsm : 0.f;
-                        gg = __builtin_amdgcn_exp2f(lsm * LOG2E) * a.row_ysum[b] - (pos ? 1.f : 0.f);
+                        BceTerms t = bce_terms(xv);
+                        float l = fmaxf(xv, 0.f) - xv * y;
+                        if (edge && !(nvalid && brow < b_end)) { l = 0.f; t.ope = 1.f; }
+                        lin += l;
+                        prod *= t.ope;
+                        g4[rg][i] = fmaf(t.sig, a.inv_norm, pos ? gy_pos : gy_neg);
+                        continue;
                     }
-                    // (a shard's last tile also sees the positives of the next shard's first columns: masked like padding)
-                    if (edge) l = (nvalid && b0 + 32 * h + 16 * rg + 4 * s + i < b_end) ? l : 0.f;
-                    lsum += l;
-                    g4[rg][i] = gg * a.inv_norm;
+                    const LossTerm t = loss_element<MODE>(a, xv, pos, brow, edge, nvalid, b_end);
+                    lsum += t.l;
+                    g4[rg][i] = t.g;
                 }
             }
-            if (MODE == MODE_TRAIN_BCE && LOGPROD) lsum += lin + __builtin_amdgcn_logf(prod) * LN2;
+            if (MODE == MODE_TRAIN_BCE && LOGPROD) lsum += lin + __builtin_amdgcn_logf(prod) * TILE_LN2;
         }
         if (REGC && b0 + BC64 < b_end) {
             // park the next chunk in the other buffer (its last readers finished before this chunk's barrier) and request the
             // chunk after it: by now the waves of a SIMD are a phase apart, so this runs beside the other wave's MFMAs
-#pragma unroll
-            for (int it = 0; it < NQIT; ++it) {
-                const int q = q8 + QG * it;
-                if (q < NQ) *reinterpret_cast<v4f *>(Qn + r8 * LDK + 4 * q) = qreg[it];
-            }
+            park_chunk(Qn);
             if (b0 + 2 * BC64 < b_end) fetch_chunk(b0 + 2 * BC64);
         }
         if (!a.loss_only) {
@@ -492,66 +452,12 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         }
     }
     TL_STAMP_AT(43);       // partial sums combined
-    {
-        const double ls = wave_sum((double)lsum);
-        if (lane == 0) red[w] = ls;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double tot = 0.0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) tot += red[i];
-        a.loss_partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
-    }
+    store_loss_partial(lsum, red, a.loss_partial + (size_t)blockIdx.y * gridDim.x + blockIdx.x, tid);
     TL_STAMP_AT(44);       // loss partial out
-    const int n = n0 + r8;
-    if (!a.loss_only && n < a.N) {
-        const int64_t cid = checked_row(a.cand_ids ? (int64_t)a.cand_ids[n] : (int64_t)a.cand_first + n, a.n_table_rows, nullptr);
-        float *drow = a.dE + cid * d;
-        const bool exclusive = gridDim.y == 1 && a.cand_exclusive;    // one workgroup per entity row: plain stores
-        // batch split over blockIdx.y: every workgroup stores ITS partial rows into a slab (plain 16-byte stores);
-        // dc_reduce_kernel sums the slabs into dE
-        float *srow = gridDim.y > 1 ? a.dC_slab + ((size_t)blockIdx.y * gridDim.x * NT64 + n) * (16 * KB) : nullptr;
-#pragma unroll
-        for (int it = 0; it < NOIT; ++it) {
-            const int o = q8 + QG * it, k = 8 * o;
-            if (o >= NO || k >= d) continue;
-            v4f v[2];
-            v[0] = *reinterpret_cast<const v4f *>(Cs + r8 * LDK + k);
-            v[1] = *reinterpret_cast<const v4f *>(Cs + r8 * LDK + k + 4);
-            if (a.drop_c.enabled) {
-                const uint32_t bits = keepb[r8 * KEEP_LD + o];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[0][e] *= (bits >> e & 1u) ? a.drop_c.scale : 0.f;
-                    v[1][e] *= (bits >> (4 + e) & 1u) ? a.drop_c.scale : 0.f;
-                }
-            }
-            if (srow) {                                   // 16*KB columns per slab row: k + 8 <= 16*KB always
-                *reinterpret_cast<v4f *>(srow + k) = v[0];
-                *reinterpret_cast<v4f *>(srow + k + 4) = v[1];
-                continue;
-            }
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int kk = k + 4 * hh;
-                if (kk >= d) continue;
-                if (exclusive && vec_ok) {
-                    v4f o4 = v[hh];
-                    if (!a.grads_zero) o4 += *reinterpret_cast<const v4f *>(drow + kk);
-                    *reinterpret_cast<v4f *>(drow + kk) = o4;
-                } else if (exclusive) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (kk + e < d) drow[kk + e] = a.grads_zero ? v[hh][e] : drow[kk + e] + v[hh][e];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (kk + e < d) atomicAdd(drow + kk + e, v[hh][e]);
-                }
-            }
-        }
-    }
+    // batch split over blockIdx.y: every workgroup stores ITS partial rows into a slab (plain 16-byte stores);
+    // dc_reduce_kernel sums the slabs into dE
+    store_tile_gradient<KB>(a, Cs, keepb, gridDim.y > 1 ? a.dC_slab + ((size_t)blockIdx.y * gridDim.x * NT64 + n0) * (16 * KB) : nullptr,
+                            n0, tid);
 #ifdef OKGE_STAMPS
     if (a.stamps_dbg && tid == 0) {
         unsigned long long wg_t1;
@@ -569,7 +475,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
 template <int KB>
 static size_t shmem64()
 {
-    using Cfg = Tile64Cfg<KB>;
+    using Cfg = TileCfg<KB>;
     return (size_t)(NT64 + BC64) * Cfg::LDK * sizeof(float) + 3 * BC64 * 2 * sizeof(uint32_t) + 8 * sizeof(double) +
            NT64 * Cfg::KEEP_LD + POS_CACHE * sizeof(uint32_t);
 }
@@ -577,14 +483,10 @@ static size_t shmem64()
 template <int KB, int MODE>
 static hipError_t launch64_t(const FusedArgs &a, dim3 grid, hipStream_t st)
 {
-    auto k = fused_tile64_kernel<KB, MODE>;
     // slot sizes 16 (KB - 1) + 1 .. + 8: the last contraction round needs two of its four MFMAs
-    if (KB == 13 && a.d > 16 * (KB - 1) && a.d <= 16 * (KB - 1) + 8) k = fused_tile64_kernel<KB, MODE, (KB == 13)>;
-    const size_t shmem = shmem64<KB>();
-    static LdsOptIn lds_opt_in;
-    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), shmem); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, grid, dim3(T64_THREADS), shmem, st, a);
-    return hipGetLastError();
+    if (KB == 13 && a.d > 16 * (KB - 1) && a.d <= 16 * (KB - 1) + 8)
+        return launch_with_lds<fused_tile64_kernel<KB, MODE, (KB == 13)>>(grid, dim3(T64_THREADS), shmem64<KB>(), st, a);
+    return launch_with_lds<fused_tile64_kernel<KB, MODE>>(grid, dim3(T64_THREADS), shmem64<KB>(), st, a);
 }
 
 template <int KB>

@@ -40,15 +40,13 @@
 
 #include "okge_device.h"
 #include "okge_kernels.h"
+#include "okge_tile.h"
 
 namespace okge {
 
-constexpr int NTK = 64, BCK = 32, TK_THREADS = 512;
+constexpr int NTK = TILE_N, BCK = 32, TK_THREADS = TILE_THREADS;
 
-template <int KB> struct Tile64kCfg {
-    static constexpr int LDK = lds_ld(16 * KB);
-    static constexpr int NO = 2 * KB;                         // 8-column octets per row
-    static constexpr int KEEP_LD = NO < 32 ? 32 : NO;         // keep-flag bytes per row
+template <int KB> struct Tile64kCfg : TileCfg<KB> {
     static constexpr int KBW = KB / 2;                        // 16-column rounds of one wave's column half
     static constexpr int KQW = KBW / 4;                       // 64-column quads of one wave's gradient columns
 };
@@ -171,8 +169,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
         const int nl = 16 * blk + c, n = n0 + nl;
         const bool valid = n < a.N;
         int64_t cid = 0;
-        if (valid) cid = checked_row(a.cand_ids ? (int64_t)a.cand_ids[n] : (int64_t)a.cand_first + n, a.n_table_rows,
-                                     (s == 0 && ks == 0) ? a.id_err : nullptr);
+        if (valid) cid = cand_table_row(a.cand_ids, a.cand_first, n, a.n_table_rows, (s == 0 && ks == 0) ? a.id_err : nullptr);
         const float *row = a.E + cid * d;
         if (vec_ok) {
             // branch-free: all 16 loads back to back (out-of-range pieces read the row's first floats and are zeroed below)
@@ -225,8 +222,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
             if (cm) *reinterpret_cast<v4f *>(cm + 16 * r) = breg[r];            // masked rows for the dQ kernel (padding rows: 0)
         }
     }
-    for (int i = tid; i < pos_cached; i += TK_THREADS)
-        posc[i] = ((uint32_t)a.pos_row[pos_lo + i] << 6) | (uint32_t)(a.pos_col[pos_lo + i] - a.cand_col0 - n0);
+    cache_tile_positives(a, posc, pos_lo, pos_cached, n0, tid);
     if (tid < 3 * 2 * BCK) ybits3[tid] = 0u;
     park_chunk(Qb);
     if (b_begin + BCK < b_end) fetch_chunk(b_begin + BCK);
@@ -237,19 +233,8 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
     for (int kb = 0; kb < KBW; ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
     const bool col_edge = n0 + NTK > a.N;
 
-    auto set_label_bits = [&](int bb, uint32_t *yb) {
-        for (int i = tid; i < pos_cached; i += TK_THREADS) {
-            const uint32_t v = posc[i];
-            const int row = (int)(v >> 6) - bb;
-            if (row >= 0 && row < BCK) atomicOr(&yb[BCK * ((v >> 5) & 1u) + row], 1u << (v & 31u));
-        }
-        for (int q = pos_lo + POS_CACHE + tid; q < pos_hi; q += TK_THREADS) {      // overflow: rare
-            const int row = a.pos_row[q] - bb;
-            const int col = a.pos_col[q] - a.cand_col0 - n0;
-            if (row >= 0 && row < BCK) atomicOr(&yb[BCK * (col >> 5) + row], 1u << (col & 31));
-        }
-    };
-    if (TRAIN) set_label_bits(b_begin, ybits3);     // (chunk 0: set after the clear above, read after the chunk's mid barrier)
+    auto set_chunk_labels = [&](int bb, uint32_t *yb) { set_label_bits<BCK>(a, posc, pos_lo, pos_hi, pos_cached, n0, bb, yb, tid); };
+    if (TRAIN) set_chunk_labels(b_begin, ybits3);     // (chunk 0: set after the clear above, read after the chunk's mid barrier)
 
     int par = 0, buf = 0;
     for (int b0 = b_begin; b0 < b_end; b0 += BCK, par = par == 2 ? 0 : par + 1, buf ^= 1) {
@@ -270,7 +255,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
         if (TRAIN) {   // under the score product: the next chunk's label bits, the buffer after that cleared
             const int pn = par == 2 ? 0 : par + 1, pc = pn == 2 ? 0 : pn + 1;
             if (tid < 2 * BCK) ybits3[pc * (2 * BCK) + tid] = 0u;
-            if (b0 + BCK < b_end) set_label_bits(b0 + BCK, ybits3 + pn * (2 * BCK));
+            if (b0 + BCK < b_end) set_chunk_labels(b0 + BCK, ybits3 + pn * (2 * BCK));
         }
 
         // ---- partial score blocks over this wave's column half: rows 16 rg + 4 s + i, candidates 16 blk + c ---------------
@@ -409,40 +394,23 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
         // ---- loss epilogue: G = dLoss/dX / normalizer, kept in registers -------------------------------------------------
         v4f g4[2];
         {
-            constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
             const uint32_t *yrow = ybits + BCK * (blk >> 1) + 4 * s;
             const uint4 yw0 = *reinterpret_cast<const uint4 *>(yrow), yw1 = *reinterpret_cast<const uint4 *>(yrow + 16);
             const uint32_t yw[2][4] = {{yw0.x, yw0.y, yw0.z, yw0.w}, {yw1.x, yw1.y, yw1.z, yw1.w}};
             const int ybit = 16 * (blk & 1) + c;
             const bool edge = col_edge || b0 + BCK > b_end;       // uniform: only the last tile / a partial last chunk
             const bool nvalid = n0 + 16 * blk + c < a.N;
+            constexpr int LOSS = MODE == MODE_TRAIN_BCE ? MODE_TRAIN_BCE : MODE_TRAIN_KL;   // (the sweep modes left the chunk above)
 #pragma unroll
             for (int rg = 0; rg < 2; ++rg) {
                 const v4f x = rg == 0 ? x0 : x1;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float xv = x[i];
                     const bool pos = (yw[rg][i] >> ybit) & 1u;
-                    float gg, l;
-                    if (MODE == MODE_TRAIN_BCE) {
-                        // BCEWithLogits: max(x,0) - x*y + log1p(exp(-|x|)); d/dx = sigmoid(x) - y
-                        const float y = pos ? a.y_pos : a.y_neg;
-                        const float e = __builtin_amdgcn_exp2f(-fabsf(xv) * LOG2E);
-                        const float ope = 1.f + e;
-                        const float rcp = __builtin_amdgcn_rcpf(ope);
-                        const float sig = xv >= 0.f ? rcp : e * rcp;
-                        l = fmaxf(xv, 0.f) - xv * y + __builtin_amdgcn_logf(ope) * LN2;
-                        gg = sig - y;
-                    } else {
-                        // KLDiv(sum)(log_softmax(x), y), y in {0,1} unnormalised (trainer.py:99-101)
-                        const int b = min(b0 + 16 * rg + 4 * s + i, a.B - 1);
-                        const float lsm = xv - a.row_lse[b];
-                        l = pos ? -lsm : 0.f;
-                        gg = __builtin_amdgcn_exp2f(lsm * LOG2E) * a.row_ysum[b] - (pos ? 1.f : 0.f);
-                    }
-                    if (edge) l = (nvalid && b0 + 16 * rg + 4 * s + i < b_end) ? l : 0.f;
-                    lsum += l;                                   // (counted by the ks == 0 partner only, below)
-                    g4[rg][i] = gg * a.inv_norm;
+                    const int brow = b0 + 16 * rg + 4 * s + i;
+                    const LossTerm t = loss_element<LOSS>(a, x[i], pos, brow, edge, nvalid, b_end);
+                    lsum += t.l;                                 // (counted by the ks == 0 partner only, below)
+                    g4[rg][i] = t.g;
                 }
             }
         }
@@ -493,69 +461,13 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
         }
     }
     __syncthreads();
-    const int r8 = tid >> 3, q8 = tid & 7;                       // write-back role: row r8 of the tile, octets q8 + 8 it
-    const int n = n0 + r8;
-    if (!a.loss_only && n < a.N) {
-        const int64_t cid = checked_row(a.cand_ids ? (int64_t)a.cand_ids[n] : (int64_t)a.cand_first + n, a.n_table_rows, nullptr);
-        float *drow = a.dE + cid * d;
-        const bool exclusive = !slab_rows && a.cand_exclusive;    // one workgroup per entity row: plain stores
-        float *srow = slab_rows ? slab_rows + (size_t)r8 * D16 : nullptr;
-#pragma unroll
-        for (int it = 0; it < NO / 8; ++it) {
-            const int o = q8 + 8 * it, k = 8 * o;
-            if (k >= d) continue;
-            v4f v[2];
-            v[0] = *reinterpret_cast<const v4f *>(Qb + r8 * LDK + k);
-            v[1] = *reinterpret_cast<const v4f *>(Qb + r8 * LDK + k + 4);
-            if (a.drop_c.enabled) {
-                const uint32_t bits = keepb[r8 * KEEP_LD + o];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[0][e] *= (bits >> e & 1u) ? a.drop_c.scale : 0.f;
-                    v[1][e] *= (bits >> (4 + e) & 1u) ? a.drop_c.scale : 0.f;
-                }
-            }
-            if (srow) {                                   // 16*KB columns per slab row: k + 8 <= 16*KB always
-                *reinterpret_cast<v4f *>(srow + k) = v[0];
-                *reinterpret_cast<v4f *>(srow + k + 4) = v[1];
-                continue;
-            }
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int kk = k + 4 * hh;
-                if (kk >= d) continue;
-                if (exclusive && vec_ok) {
-                    v4f o4 = v[hh];
-                    if (!a.grads_zero) o4 += *reinterpret_cast<const v4f *>(drow + kk);
-                    *reinterpret_cast<v4f *>(drow + kk) = o4;
-                } else if (exclusive) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (kk + e < d) drow[kk + e] = a.grads_zero ? v[hh][e] : drow[kk + e] + v[hh][e];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (kk + e < d) atomicAdd(drow + kk + e, v[hh][e]);
-                }
-            }
-        }
-    }
+    store_tile_gradient<KB>(a, Qb, keepb, slab_rows, n0, tid);
     }   // segments
 
     if (!TRAIN) return;
     // ---- this workgroup's loss partial (all its segments; the ks == 0 partner of every pair counted) -------------------------
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    {
-        const double ls = wave_sum((double)((w >> 2) == 0 ? lsum : 0.f));
-        if (lane == 0) red[w] = ls;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double tot = 0.0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) tot += red[i];
-        a.loss_partial[sk ? (size_t)blockIdx.x : (size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
-    }
+    store_loss_partial(threadIdx.x < 4 * 64 ? lsum : 0.f, red,      // waves 0 .. 3: ks == 0
+                       a.loss_partial + (sk ? (size_t)blockIdx.x : (size_t)blockIdx.y * gridDim.x + blockIdx.x), threadIdx.x);
 }
 
 // ---- launcher ---------------------------------------------------------------------------------------------------
@@ -570,12 +482,7 @@ static size_t shmem64k()
 template <int KB, int MODE>
 static hipError_t launch64k_t(const FusedArgs &a, dim3 grid, hipStream_t st)
 {
-    auto k = fused_tile64k_kernel<KB, MODE>;
-    const size_t shmem = shmem64k<KB>();
-    static LdsOptIn lds_opt_in;
-    if (hipError_t e = ensure_dynamic_lds(lds_opt_in, reinterpret_cast<const void *>(k), shmem); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, grid, dim3(TK_THREADS), shmem, st, a);
-    return hipGetLastError();
+    return launch_with_lds<fused_tile64k_kernel<KB, MODE>>(grid, dim3(TK_THREADS), shmem64k<KB>(), st, a);
 }
 
 // grid_x = number of 64-candidate tiles (or workgroups of a stream-K launch), slot sizes above 256 (KB = 32); MODE_SCORE: the
