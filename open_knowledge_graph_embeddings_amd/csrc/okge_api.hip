@@ -933,7 +933,8 @@ int okge_prefix_score_backward(int32_t scorer, int32_t sp, const float *g, int64
 int okge_scatter_rows(const float *rows, int64_t ld, const int32_t *ids, const int32_t *order, int32_t first_id, int32_t n, int32_t d,
                       const okge_dropout *drop, float *table_grad, int32_t table_rows, void *stream)
 {
-    if (!rows || !table_grad || n < 0 || d <= 0 || ld < d || table_rows <= 0) return fail(OKGE_ERR_INVALID, "bad scatter_rows arguments");
+    if ((!rows && n > 0) || !table_grad || n < 0 || d <= 0 || ld < d || table_rows <= 0)      // (no rows: an empty tensor has no address)
+        return fail(OKGE_ERR_INVALID, "bad scatter_rows arguments");
     if (!ids && (first_id < 0 || (int64_t)first_id + n > table_rows)) return fail(OKGE_ERR_INVALID, "row range outside the table");
     if (ids && n > 1 && !order) return fail(OKGE_ERR_INVALID, "scatter_rows with ids needs the positions sorted by id");
     okge_dropout none;

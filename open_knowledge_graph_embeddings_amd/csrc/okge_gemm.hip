@@ -111,7 +111,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
     }
 }
 
-// q = fold(ent, rel): the operand with score = q . cand^T (model.py:205-216 regrouped, :268-274), same roundings as the forward
+// q = fold(ent, rel): the operand with score = q . cand^T (model.py:205-216 regrouped, :268-274), fold_complex's roundings: every
+// product and the sum rounded on their own.  Written out under `fp contract(off)`: __fmul_rn / __fadd_rn are plain `*` / `+` to
+// hipcc, which fused fold_complex here into v_mul + v_fmac (tests/test_score_backward_shapes.py::test_unit_gradient_copies_rows).
 __global__ __launch_bounds__(128) void fold_rows_kernel(int scorer, int sp, const float *__restrict__ ent, int64_t ld_e,
                                                         const float *__restrict__ rel, int64_t ld_r, int d, float *__restrict__ q)
 {
@@ -123,7 +125,13 @@ __global__ __launch_bounds__(128) void fold_rows_kernel(int scorer, int sp, cons
         return;
     }
     const int h = d >> 1;
-    for (int k = threadIdx.x; k < h; k += blockDim.x) fold_complex(sp != 0, e[k], e[h + k], r[k], r[h + k], o[k], o[h + k]);
+    for (int k = threadIdx.x; k < h; k += blockDim.x) {
+#pragma clang fp contract(off)
+        const float e1 = e[k], e2 = e[h + k], r1 = r[k], r2 = r[h + k];
+        const float a = e1 * r1, bb = e2 * r2, c = e2 * r1, dd = e1 * r2;
+        o[k] = sp ? a - bb : a + bb;
+        o[h + k] = sp ? c + dd : c - dd;
+    }
 }
 
 // (d_ent, d_rel) from dq: the transpose of the fold

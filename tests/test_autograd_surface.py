@@ -2,7 +2,9 @@
 `po_prefix_score` / `forward` / `_score`): HIP forward + the GEMM / chain-rule backward of autograd_score.py, against the
 reference's op sequence differentiated by ATen -- oracle/torch_twin.TwinModel (openkge/model.py:198-240, :268-278,
 :455-480; pinned by tests/test_oracle_golden.py) in FLOAT64 on the CPU.  Tolerances: scores 2e-5 absolute (fp32 sums of
-d <= 200 terms of size 0.1), gradients 1e-4 of the largest gradient entry."""
+d <= 200 terms of size 0.1), gradients 1e-4 of the largest gradient entry.  Sizes: small batches (b <= 16, N <= 298) for the
+surface, and one own-loss batch at full size (b = 512 in both directions, all 14 539 candidates of a 14 541-entity table,
+d = 200), where the backward's transposed-A product runs 32 chunks of its contraction and the other one 32 splits."""
 import numpy as np
 import pytest
 import torch
@@ -69,6 +71,30 @@ def test_prefix_scores_carry_a_graph(okge_lib, kind, d, mode):
         y = m.sp_prefix_score(subj.cuda(), rel_s.cuda())
     assert not y.requires_grad
     np.testing.assert_allclose(y.cpu().numpy(), x_sp.detach().cpu().numpy(), rtol=0, atol=2e-6)
+
+
+@pytest.mark.parametrize("kind", ["complex", "distmult"])
+def test_prefix_scores_carry_a_graph_at_full_size(okge_lib, kind):
+    """the own loss of test_prefix_scores_carry_a_graph in eval mode at b = 512 per direction, every candidate of a
+    14 541-entity table, d = 200: scores and both tables' gradients against the float64 twin, the same tolerances"""
+    n_ent, n_rel, d, b = 14541, 240, 200, 512
+    m, twin, rng = _pair(kind, n_ent, n_rel, d, seed=77)
+    m.eval()
+    subj, rel_s, rel_o, obj = _ids(rng, 2, n_ent, b), _ids(rng, 2, n_rel, b), _ids(rng, 2, n_rel, b), _ids(rng, 2, n_ent, b)
+    W1 = torch.from_numpy(rng.standard_normal((b, n_ent - 2)))
+    W2 = torch.from_numpy(rng.standard_normal((b, n_ent - 2)))
+    own = lambda x1, x2, w1, w2: (torch.tanh(x1) * w1).sum() + (x2 * x2 * w2).sum()       # noqa: E731
+    x_sp = m.sp_prefix_score(subj.cuda(), rel_s.cuda())
+    x_po = m.po_prefix_score(rel_o.cuda(), obj.cuda())
+    assert x_sp.requires_grad and x_po.requires_grad and x_sp.shape == (b, n_ent - 2) and x_po.shape == (b, n_ent - 2)
+    own(x_sp, x_po, W1.float().cuda(), W2.float().cuda()).backward()
+    cand = twin.enc_ent(torch.arange(2, n_ent))
+    r_sp = twin.score(twin.enc_ent(subj), twin.enc_rel(rel_s), cand, sp=True)
+    r_po = twin.score(twin.enc_ent(obj), twin.enc_rel(rel_o), cand, sp=False)
+    own(r_sp, r_po, W1, W2).backward()
+    np.testing.assert_allclose(x_sp.detach().cpu().numpy(), r_sp.detach().numpy(), rtol=0, atol=2e-5)
+    np.testing.assert_allclose(x_po.detach().cpu().numpy(), r_po.detach().numpy(), rtol=0, atol=2e-5)
+    _compare_grads(m, twin)
 
 
 @pytest.mark.parametrize("kind", ["complex", "distmult"])
