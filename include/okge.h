@@ -345,6 +345,49 @@ int okge_lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *call
                              float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh, float *d_bn_weight, float *d_bn_bias,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Bigram token encoder ------------------------------------------------------------------------------
+ * Replaces BigramPoolingRelationEmbedder._encode (model.py:874-897, gates=False) up to (not including) its final dropout,
+ * TOGETHER with the id -> token mapping the reference's encode_* leave out (tokens = token_ids[ids]):
+ *   row id -> token_ids[id][0..max_len) -> embedding rows x_t of W (row 0 read as stored)
+ *          -> Conv1d(d, d, kernel_size 2, no bias): Y[t] = K0 x_t + K1 x_{t+1}, K_j = conv_weight[:, :, j], t = 0 .. max_len - 2
+ *          -> normalize 2: BatchNorm1d(d, momentum=None) over ALL n (max_len - 1) positions of the call, padded ones included
+ *             (training: the call's statistics, running statistics as a cumulative average with factor 1 / num_batches_tracked,
+ *             one count per call in call order; evaluation: the running statistics)
+ *          -> + x_{t+1} -> x mask[t] = (token[t+1] > 0) -> sum (pool 0) or max (pool 1) over t
+ *          -> normalize 1: / (sum mask + 1e-12).
+ * A PASS is up to 8 calls of ONE slot, their rows one after the other in out / d_out ([rows][ld]).  d <= 512,
+ * 2 <= max_len <= 64.  A token id outside the vocabulary reads row 0 and is counted (okge_id_errors).
+ * okge_bigram_encode_calls  : out = pooled rows; pos_tok [rows * max_len] (caller's buffer) = the guarded token id of every
+ *                             (row, t).  training != 0 keeps what the backward needs in the workspace.
+ * okge_bigram_backward_calls: after a training encode with the same arguments and workspace.  d_conv (d, d, 2), d_bn_weight,
+ *                             d_bn_bias are WRITTEN; dW (vocab x d) += the token rows' gradient, summed per token in the order
+ *                             of pos_order = the positions sorted by pos_tok (stable; index plumbing by the caller); token 0
+ *                             receives nothing.
+ * No float atomics: bit-reproducible.  Workspace: okge_bigram_workspace_bytes(total rows, max_len, d, training). */
+typedef struct okge_bigram_slot {
+    const float *W;              /* token embedding table (vocab x d) */
+    const int32_t *token_ids;    /* (n_ids x max_len) */
+    int32_t vocab, d, n_ids, max_len;
+    const float *conv_weight;    /* (d, d, 2) */
+    int32_t pool;                /* 0 sum, 1 max */
+    int32_t normalize;           /* 0 none, 1 mean, 2 batchnorm */
+    const float *bn_weight, *bn_bias;          /* normalize 2 only */
+    float *bn_running_mean, *bn_running_var;
+    int64_t *bn_num_batches_tracked;           /* device word */
+    float bn_eps;
+    int32_t _pad;
+} okge_bigram_slot;
+typedef struct okge_bigram_call {
+    const int32_t *ids;          /* NULL: rows first_id .. first_id + n - 1 */
+    int32_t first_id, n;
+} okge_bigram_call;
+size_t okge_bigram_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training);
+int okge_bigram_encode_calls(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t n_calls, int32_t training, float *out,
+                             int64_t ld, int32_t *pos_tok, void *workspace, size_t workspace_bytes, void *stream);
+int okge_bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t n_calls, const float *d_out,
+                               int64_t ld, const int32_t *pos_tok, const int32_t *pos_order, float *dW, float *d_conv,
+                               float *d_bn_weight, float *d_bn_bias, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Tucker3 / RESCAL scorer with a projected relation --------------------------------------------------------
  * Replaces, for LookupTucker3RelationModel, encode_rel's Linear (model.py:402-408, :482-490: M_b = reshape(W rho_b, (d, d)),
  * W = relation_projection.0.weight (d^2, r_e) row-major) together with the two bmm of RescalRelationScorer._score

@@ -1044,6 +1044,28 @@ int okge_tucker3_outer(const float *u, int64_t ld_u, const float *v, int64_t ld_
     return OKGE_OK;
 }
 
+// ---- Bigram token encoder (okge_bigram.hip) --------------------------------------------------------------------------
+size_t okge_bigram_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training)
+{
+    return bigram_workspace_bytes(rows, max_len, d, training);
+}
+
+int okge_bigram_encode_calls(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t n_calls, int32_t training, float *out,
+                             int64_t ld, int32_t *pos_tok, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ScopedTimer tm("bigram_encode", reinterpret_cast<hipStream_t>(stream));
+    return bigram_encode_calls(s, calls, n_calls, training, out, ld, pos_tok, workspace, workspace_bytes, id_err_ptr(), stream);
+}
+
+int okge_bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t n_calls, const float *d_out,
+                               int64_t ld, const int32_t *pos_tok, const int32_t *pos_order, float *dW, float *d_conv,
+                               float *d_bn_weight, float *d_bn_bias, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ScopedTimer tm("bigram_backward", reinterpret_cast<hipStream_t>(stream));
+    return bigram_backward_calls(s, calls, n_calls, d_out, ld, pos_tok, pos_order, dW, d_conv, d_bn_weight, d_bn_bias, workspace,
+                                 workspace_bytes, id_err_ptr(), stream);
+}
+
 // ---- LSTM token encoder (okge_lstm.hip) ----------------------------------------------------------------------------
 size_t okge_lstm_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training)
 {

@@ -204,6 +204,13 @@ int lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, in
                         int64_t ld, const int32_t *pos_tok, const int32_t *pos_order, float *dW, float *d_w_ih, float *d_w_hh,
                         float *d_b_ih, float *d_b_hh, float *d_bn_weight, float *d_bn_bias, void *workspace, size_t workspace_bytes,
                         int *err, void *stream);
+// Bigram token encoder (okge_bigram.hip): the bodies of the C ABI's okge_bigram_* (okge.h), err = the device's id-error word
+size_t bigram_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training);
+int bigram_encode_calls(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t n_calls, int32_t training, float *out, int64_t ld,
+                        int32_t *pos_tok, void *workspace, size_t workspace_bytes, int *err, void *stream);
+int bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t n_calls, const float *d_out, int64_t ld,
+                          const int32_t *pos_tok, const int32_t *pos_order, float *dW, float *d_conv, float *d_bn_weight,
+                          float *d_bn_bias, void *workspace, size_t workspace_bytes, int *err, void *stream);
 // Tucker3 / RESCAL fold and backward (okge_tucker3.hip); cus = compute units of the device (split of the long contractions)
 int tucker3_splits(int B, int Nn, int outer, int cus);
 size_t tucker3_workspace_bytes(int B, int d, int r, int cus);
