@@ -37,7 +37,13 @@ enum okge_status {
     OKGE_ERR_HIP = -4           /* a HIP runtime call or kernel launch failed                      */
 };
 
-enum okge_scorer { OKGE_COMPLEX = 0, OKGE_DISTMULT = 1 };   /* model.py:176-240 / :243-278 */
+enum okge_scorer { OKGE_COMPLEX = 0, OKGE_DISTMULT = 1,     /* model.py:176-240 / :243-278 */
+                   /* the data-bias baselines (model.py:281-350): the query row is ONE encoded row, copied -- the relation
+                    * (sp: rel . obj^T, po: rel . subj^T) or the prefix entity (sp: subj . obj^T, po: obj . subj^T); the other
+                    * slot's row is not read and receives no gradient.  Prefix scoring, training and evaluation only:
+                    * okge_score_triples, okge_train_step, okge_fold_queries and okge_evaluate_fused_shard answer
+                    * OKGE_ERR_UNSUPPORTED.  No even-d rule. */
+                   OKGE_BIAS_RELATION = 2, OKGE_BIAS_ENTITY = 3 };
 enum okge_loss   { OKGE_LOSS_BCE = 0, OKGE_LOSS_KL = 1 };   /* trainer.py:93-106           */
 
 /* Dropout applied to gathered embedding rows (model.py:461-462, F.dropout in training mode).

@@ -14,19 +14,31 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_i
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libokge_hip.so")
-SOURCES = ["okge_api.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_misc.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
+SOURCES = ["okge_api.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_misc.hip", "okge_bias.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
 # every header a source may include: all of csrc/*.h (listed by the directory, so a new header cannot be forgotten) + the ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "okge.h")]
 
 OKGE_COMPLEX, OKGE_DISTMULT = 0, 1
+OKGE_BIAS_RELATION, OKGE_BIAS_ENTITY = 2, 3      # the data-bias baselines (model.py:281-350): prefix scoring only
 OKGE_LOSS_BCE, OKGE_LOSS_KL = 0, 1
 OKGE_TRAIN_GRADS_ZERO = 1
 OKGE_TRAIN_LOSS_ONLY = 2
 OKGE_TRAIN_UNIQUE_CANDIDATES = 4
 OKGE_TRAIN_DISTINCT_PREFIX_ROWS = 8
 OKGE_TRAIN_CLEAR_GRADS = 16
-SCORERS = {"complex": OKGE_COMPLEX, "distmult": OKGE_DISTMULT}
+SCORERS = {"complex": OKGE_COMPLEX, "distmult": OKGE_DISTMULT, "bias_relation": OKGE_BIAS_RELATION,
+           "bias_entity": OKGE_BIAS_ENTITY}
 LOSSES = {"bce": OKGE_LOSS_BCE, "kl": OKGE_LOSS_KL}
+BIAS_SCORERS = ("bias_relation", "bias_entity")
+
+
+def refuse_bias_scorer(scorer, who):
+    """The data-bias scorers leave one slot without a gradient (model.py:281-350).  A step driver whose optimizer moves every
+    parameter would step that slot on a zero gradient -- weight decay and the accumulator make that a real move -- so drivers
+    that are not built for it refuse at construction; so do the sharded paths."""
+    if scorer in BIAS_SCORERS or scorer in (OKGE_BIAS_RELATION, OKGE_BIAS_ENTITY):
+        raise NotImplementedError(f"{who} does not take the {scorer!r} scorer: the data-bias models train through "
+                                  f"LSTMTrainStep / AddLossModule, which leave the unused slot untouched")
 
 # every symbol include/okge.h declares
 EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_train_forward_backward",

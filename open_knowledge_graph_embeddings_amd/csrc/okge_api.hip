@@ -300,12 +300,25 @@ bool make_geometry(int B, int N, int d, Geometry &g)
     return true;
 }
 
+bool known_scorer(int32_t scorer)
+{
+    return scorer == OKGE_COMPLEX || scorer == OKGE_DISTMULT || scorer == OKGE_BIAS_RELATION || scorer == OKGE_BIAS_ENTITY;
+}
+const char *scorer_name(int32_t scorer) { return scorer == OKGE_BIAS_RELATION ? "OKGE_BIAS_RELATION" : "OKGE_BIAS_ENTITY"; }
+// the data-bias scorers (model.py:281-350) score prefixes only and leave one slot without a gradient: the entry points that
+// score triples, step every table or fold from exchanged entity rows refuse them before anything is written
+int refuse_bias(int32_t scorer, const char *entry, const char *why)
+{
+    if (scorer != OKGE_BIAS_RELATION && scorer != OKGE_BIAS_ENTITY) return OKGE_OK;
+    return fail(OKGE_ERR_UNSUPPORTED, std::string(entry) + " does not take the " + scorer_name(scorer) + " scorer: " + why);
+}
+
 int check_common(const okge_tables *t, const okge_prefix_batch *b, const okge_candidates *c)
 {
     if (!t || !b || !c) return fail(OKGE_ERR_INVALID, "null descriptor");
     if (!t->E || !t->R) return fail(OKGE_ERR_INVALID, "null embedding table");
     if (t->d <= 0 || t->n_ent <= 0 || t->n_rel <= 0) return fail(OKGE_ERR_INVALID, "bad table shape");
-    if (t->scorer != OKGE_COMPLEX && t->scorer != OKGE_DISTMULT) return fail(OKGE_ERR_INVALID, "unknown scorer");
+    if (!known_scorer(t->scorer)) return fail(OKGE_ERR_INVALID, "unknown scorer");
     if (t->scorer == OKGE_COMPLEX && (t->d & 1)) return fail(OKGE_ERR_INVALID, "ComplEx needs an even slot size");
     if (t->d > 512) return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels");
     if (b->n_po < 0 || b->n_sp < 0 || b->n_po + b->n_sp <= 0) return fail(OKGE_ERR_INVALID, "empty batch");
@@ -708,6 +721,7 @@ int okge_train_step(const okge_tables *t, const okge_prefix_batch *batch, const 
                     double *loss_out, float *dE, float *dR, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (int rc = check_common(t, batch, cand)) return rc;
+    if (int rc = refuse_bias(t->scorer, "okge_train_step", "its update steps both tables, the unused slot has no gradient")) return rc;
     if (!dR || !opt || !opt->sum_E || !opt->sum_R || !opt->prefix_flags) return fail(OKGE_ERR_INVALID, "null output / optimizer state");
     if (flags & (OKGE_TRAIN_LOSS_ONLY | OKGE_TRAIN_DISTINCT_PREFIX_ROWS))
         return fail(OKGE_ERR_INVALID, "okge_train_step updates the tables: not with LOSS_ONLY / DISTINCT_PREFIX_ROWS");
@@ -763,6 +777,7 @@ int okge_fold_queries(const okge_tables *t, const okge_prefix_batch *batch, cons
     std::memset(&none, 0, sizeof(none));
     none.n = 1; none.first_id = 0;
     if (int rc = check_common(t, batch, &none)) return rc;
+    if (int rc = refuse_bias(t->scorer, "okge_fold_queries", "the sharded paths are not built for it")) return rc;
     if (!ent_rows || !Q || ldq != okge_query_ld(t->d)) return fail(OKGE_ERR_INVALID, "bad query block");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     PrefixDev p = to_dev(*batch, t);
@@ -878,8 +893,8 @@ int okge_prefix_backward_segmented(const okge_tables *t, const okge_shard *sh, c
     if (!grad_rows || (!has_r && !has_e) || (has_r && (!rel_order || !rel_seg_ptr || n_rel_seg <= 0 || n_rel_seg > B)) ||
         (has_e && (!ent_order || !ent_seg_ptr || n_ent_seg <= 0 || n_ent_seg > B)))
         return fail(OKGE_ERR_INVALID, "bad row segments (order[B], seg_ptr[n_seg + 1], 1 <= n_seg <= B; grad_rows[2][rows][ldq])");
-    const bool vec = t->scorer == OKGE_DISTMULT ? (t->d % 4 == 0) : (t->d % 8 == 0);
-    if (!vec) return fail(OKGE_ERR_UNSUPPORTED, "segmented gradients need d % 8 == 0 (ComplEx) / d % 4 == 0 (DistMult)");
+    const bool vec = t->scorer == OKGE_COMPLEX ? (t->d % 8 == 0) : (t->d % 4 == 0);
+    if (!vec) return fail(OKGE_ERR_UNSUPPORTED, "segmented gradients need d % 8 == 0 (ComplEx) / d % 4 == 0 (DistMult, data-bias)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const PrefixDev p = to_dev(*batch, t, sh);
     ScopedTimer tm("prefix_backward", st);
@@ -917,7 +932,7 @@ int okge_prefix_score_backward(int32_t scorer, int32_t sp, const float *g, int64
 {
     if (!g || !ent || !rel || !cand || b <= 0 || n <= 0 || d <= 0 || ld_g < n || ld_ent < d || ld_rel < d || ld_cand < d)
         return fail(OKGE_ERR_INVALID, "bad prefix_score_backward arguments");
-    if (scorer != OKGE_COMPLEX && scorer != OKGE_DISTMULT) return fail(OKGE_ERR_INVALID, "unknown scorer");
+    if (!known_scorer(scorer)) return fail(OKGE_ERR_INVALID, "unknown scorer");
     if (scorer == OKGE_COMPLEX && (d & 1)) return fail(OKGE_ERR_INVALID, "ComplEx needs an even slot size");
     if (!d_ent && !d_rel && !d_cand) return OKGE_OK;
     if (!workspace || workspace_bytes < score_backward_workspace_bytes(b, n, d) || reinterpret_cast<uintptr_t>(workspace) % 16)
@@ -1094,7 +1109,8 @@ int okge_score_triples(int32_t scorer, const float *subj, int64_t ld_subj, const
 {
     if (!subj || !rel || !obj || !out || n < 0 || d <= 0 || ld_subj < d || ld_rel < d || ld_obj < d)
         return fail(OKGE_ERR_INVALID, "bad score_triples arguments");
-    if (scorer != OKGE_COMPLEX && scorer != OKGE_DISTMULT) return fail(OKGE_ERR_INVALID, "unknown scorer");
+    if (!known_scorer(scorer)) return fail(OKGE_ERR_INVALID, "unknown scorer");
+    if (int rc = refuse_bias(scorer, "okge_score_triples", "it scores prefixes only (model.py:311-312, :347-348)")) return rc;
     if (scorer == OKGE_COMPLEX && (d & 1)) return fail(OKGE_ERR_INVALID, "ComplEx needs an even slot size");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ScopedTimer tm("score_triples", st);
@@ -1649,6 +1665,7 @@ int okge_evaluate_fused_shard(int32_t phase, const okge_tables *t, const okge_sh
     if (phase != 1 && phase != 2 && phase != 4) return fail(OKGE_ERR_INVALID, "phase must be 1 (points), 2 (sweep) or 4 (counts)");
     if (!t || !t->E || !t->R || t->d <= 0 || t->n_ent <= 0 || !cand || cand->n <= 0 || B <= 0 || !Q || !true_scores || !counts)
         return fail(OKGE_ERR_INVALID, "bad sharded evaluate arguments");
+    if (int rc = refuse_bias(t->scorer, "okge_evaluate_fused_shard", "the sharded paths are not built for it")) return rc;
     if (int rc = check_shard(t, sh)) return rc;
     if (ldq != okge_query_ld(t->d)) return fail(OKGE_ERR_INVALID, "query block leading dimension must be okge_query_ld(d)");
     if (sh->cand_col0 < 0 || (int64_t)sh->cand_col0 + cand->n > n_cand_global)

@@ -126,8 +126,10 @@ __device__ __forceinline__ void eval_points_block(const EvalPointsArgs &a, int b
     }
     // ---- stage B
     const int h = d >> 1;
-    const bool cplx = a.scorer != SC_DISTMULT;
-    const int n_fold = cplx ? h : d;                        // folded columns: one per thread, two above 256 (DistMult d <= 512)
+    const bool cplx = a.scorer == SC_COMPLEX;
+    // data-bias scorers (model.py:281-350): the query is a copy of ONE row; the other slot's row is not read
+    const bool use_e = a.scorer != SC_BIAS_RELATION, use_r = a.scorer != SC_BIAS_ENTITY;
+    const int n_fold = cplx ? h : d;                        // folded columns: one per thread, two above 256 (d <= 512)
     float ea[2] = {0.f, 0.f}, eb[2] = {0.f, 0.f}, ra[2] = {0.f, 0.f}, rb[2] = {0.f, 0.f};
     if (rs.owned) {
         const float *e = a.E + rs.ent * d, *r = a.R + rs.rel * d;
@@ -135,7 +137,8 @@ __device__ __forceinline__ void eval_points_block(const EvalPointsArgs &a, int b
         for (int it = 0; it < 2; ++it) {
             const int k = tid + it * nthr;
             if (k < n_fold) {
-                ea[it] = e[k]; ra[it] = r[k];
+                if (use_e) ea[it] = e[k];
+                if (use_r) ra[it] = r[k];
                 if (cplx) { eb[it] = e[h + k]; rb[it] = r[h + k]; }
             }
         }
@@ -172,7 +175,7 @@ __device__ __forceinline__ void eval_points_block(const EvalPointsArgs &a, int b
             const int k = tid + it * nthr;
             if (k < n_fold) {
                 if (cplx) fold_complex(rs.sp, ea[it], eb[it], ra[it], rb[it], qs[k], qs[h + k]);
-                else qs[k] = __fmul_rn(ea[it], ra[it]);
+                else qs[k] = !use_r ? ea[it] : !use_e ? ra[it] : __fmul_rn(ea[it], ra[it]);
             }
         }
     }

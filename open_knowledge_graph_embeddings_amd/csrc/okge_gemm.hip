@@ -120,6 +120,11 @@ __global__ __launch_bounds__(128) void fold_rows_kernel(int scorer, int sp, cons
     const int b = blockIdx.x;
     const float *e = ent + (size_t)b * ld_e, *r = rel + (size_t)b * ld_r;
     float *o = q + (size_t)b * d;
+    if (sc_is_bias(scorer)) {                            // data-bias scorers (model.py:281-350): a copy of the one row
+        const float *u = scorer == SC_BIAS_ENTITY ? e : r;
+        for (int k = threadIdx.x; k < d; k += blockDim.x) o[k] = u[k];
+        return;
+    }
     if (scorer == SC_DISTMULT) {
         for (int k = threadIdx.x; k < d; k += blockDim.x) o[k] = __fmul_rn(e[k], r[k]);
         return;
@@ -142,6 +147,14 @@ __global__ __launch_bounds__(128) void fold_backward_kernel(int scorer, int sp, 
     const int b = blockIdx.x;
     const float *e = ent + (size_t)b * ld_e, *r = rel + (size_t)b * ld_r, *g = dq + (size_t)b * d;
     float *de = d_ent ? d_ent + (size_t)b * d : nullptr, *dr = d_rel ? d_rel + (size_t)b * d : nullptr;
+    if (sc_is_bias(scorer)) {                            // dq to the used operand, zeros to the other one if it is asked for
+        const bool use_e = scorer == SC_BIAS_ENTITY;
+        for (int k = threadIdx.x; k < d; k += blockDim.x) {
+            if (de) de[k] = use_e ? g[k] : 0.f;
+            if (dr) dr[k] = use_e ? 0.f : g[k];
+        }
+        return;
+    }
     if (scorer == SC_DISTMULT) {
         for (int k = threadIdx.x; k < d; k += blockDim.x) {
             if (de) de[k] = g[k] * r[k];

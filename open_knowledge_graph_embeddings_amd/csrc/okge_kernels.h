@@ -48,7 +48,9 @@ constexpr int POS_CACHE = 512;     // positives of one candidate tile cached in 
 
 enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4 };
 enum { LOSS_BCE = 0, LOSS_KL = 1 };
-enum { SC_COMPLEX = 0, SC_DISTMULT = 1 };
+enum { SC_COMPLEX = 0, SC_DISTMULT = 1, SC_BIAS_RELATION = 2, SC_BIAS_ENTITY = 3 };   // = enum okge_scorer
+// the data-bias scorers (model.py:281-350): the folded query row is a copy of ONE masked row
+__host__ __device__ constexpr bool sc_is_bias(int scorer) { return scorer == SC_BIAS_RELATION || scorer == SC_BIAS_ENTITY; }
 
 struct FusedArgs {
     const float   *E;          // entity table (n_ent, d)
@@ -136,6 +138,13 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
                                   hipStream_t st, const int32_t *rel_order = nullptr, const int32_t *rel_seg_ptr = nullptr,
                                   int n_rel_seg = 0, const int32_t *ent_order = nullptr, const int32_t *ent_seg_ptr = nullptr,
                                   int n_ent_seg = 0, float *grad_rows = nullptr, int distinct = 0, const AdagradFuse *fuse = nullptr);
+// the data-bias scorers' chain-rule launch (okge_bias.hip; called by launch_prefix_backward): d % 4 == 0 -> the float4 kernel
+// (which also reduces the loss partials and may store rows to dr_rows / de_rows), otherwise the scalar kernel; neither table is
+// read: the gradient of a copy needs no operand
+hipError_t launch_bias_prefix_rows(int d, int scorer, const PrefixDev &p, const float *slab,
+                                   int nsplit, int Bpad, int ldq, const float *ent_rows, float *dE, float *dR,
+                                   const double *loss_partials, int n_partials, double *loss_out, float *dr_rows, float *de_rows,
+                                   int distinct, hipStream_t st);
 hipError_t launch_adagrad_finish(const AdagradFuse &af, const PrefixDev &p, hipStream_t st);
 hipError_t launch_loss_reduce(const double *partials, int n, double *loss_out, hipStream_t st);
 hipError_t launch_kl_count_pos(const int32_t *pos_row, int nnz, int Bpad, float *row_ysum, hipStream_t st);

@@ -13,6 +13,7 @@
 #include "okge_kernels.h"
 #include "okge_tile.h"
 #include "okge_eval_device.h"
+#include "okge_prefix_device.h"
 
 namespace okge {
 
@@ -35,7 +36,16 @@ __device__ __forceinline__ void encode_query_row(const float *__restrict__ E, co
     const DropDev &de = rs.sp ? p.drop_sp_ent : p.drop_po_ent;
     const DropDev &dr = rs.sp ? p.drop_sp_rel : p.drop_po_rel;
     const float *e = E + rs.ent * d, *r = R + rs.rel * d;
-    if (scorer == SC_DISTMULT) {
+    if (sc_is_bias(scorer)) {
+        // data-bias scorers (model.py:281-350): the query is a copy of the one masked row, with that slot's own dropout
+        // stream; the other slot's row is not read (the entity row only where the caller wants the masked entity rows)
+        const bool use_e = scorer == SC_BIAS_ENTITY;
+        for (int k = threadIdx.x; k < d; k += blockDim.x) {
+            const float ev = (use_e || er) ? e[k] * drop_mult1(de, rs.pos, k, d) : 0.f;
+            if (q) q[k] = use_e ? ev : r[k] * drop_mult1(dr, rs.pos, k, d);
+            if (er) er[k] = ev;
+        }
+    } else if (scorer == SC_DISTMULT) {
         for (int k = threadIdx.x; k < d; k += blockDim.x) {
             const float ev = e[k] * drop_mult1(de, rs.pos, k, d);
             if (q) q[k] = __fmul_rn(ev, __fmul_rn(r[k], drop_mult1(dr, rs.pos, k, d)));
@@ -143,22 +153,6 @@ __global__ __launch_bounds__(128) void fold_queries_kernel(const float *__restri
         }
     }
     for (int k = d + threadIdx.x; k < ldq; k += blockDim.x) q[k] = 0.f;
-}
-
-__device__ __forceinline__ void loss_reduce_block(const double *__restrict__ partials, int n, double *__restrict__ out)
-{
-    __shared__ double red[4];
-    const int nw = blockDim.x >> 6;
-    double v = 0.0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) v += partials[i];
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < nw; ++i) t += red[i];
-        out[0] = t;
-    }
 }
 
 // dQ[b][k] = sum over candidate ranges of the dQ kernel's slabs (sharded path: reduced before the all-reduce)
@@ -333,17 +327,6 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const double *__restri
     loss_reduce_block(partials, n, out);
 }
 
-__device__ __forceinline__ float4 f4mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 f4fma(float4 a, float4 b, float4 c)
-{
-    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
-}
-__device__ __forceinline__ float4 f4neg(float4 a) { return make_float4(-a.x, -a.y, -a.z, -a.w); }
-__device__ __forceinline__ void atomic_add4(float *p, float4 v)
-{
-    atomicAdd(p, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
-}
-
 // One batch row per 128-thread workgroup: lane = (column group g = tid >> 2, split quarter sq = tid & 3).  The four
 // lanes of a column group sum disjoint quarters of the nsplit dQ slabs (all their loads are issued at once) and
 // combine with two shuffles; sq == 0 then applies the chain rule and scatters.  Needs d % 8 == 0 (ComplEx) or
@@ -459,29 +442,7 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
         if (de_rows || distinct) *reinterpret_cast<float4 *>(pe) = v;
         else atomic_add4(pe, v);
     };
-    auto dq_sum = [&](int k, bool active) {
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (active) {
-            int sidx = s_lo;
-            if (NB > 1)
-                for (; sidx + NB <= s_hi; sidx += NB) {
-                    float4 v[NB];
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) v[u] = *reinterpret_cast<const float4 *>(sl + (sidx + u) * split_stride + k);
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
-                }
-            for (; sidx < s_hi; ++sidx) {
-                const float4 v = *reinterpret_cast<const float4 *>(sl + sidx * split_stride + k);
-                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
-        }
-        // the four lanes of a column group are a DPP quad: xor 1, xor 2 as quad permutes (a ds_bpermute shuffle each
-        // would cost ~60 cycles on this latency-bound path)
-        acc.x += dpp_mov<0xB1>(acc.x); acc.y += dpp_mov<0xB1>(acc.y); acc.z += dpp_mov<0xB1>(acc.z); acc.w += dpp_mov<0xB1>(acc.w);
-        acc.x += dpp_mov<0x4E>(acc.x); acc.y += dpp_mov<0x4E>(acc.y); acc.z += dpp_mov<0x4E>(acc.z); acc.w += dpp_mov<0x4E>(acc.w);
-        return acc;
-    };
+    auto dq_sum = [&](int k, bool active) { return dq_quad_sum<NB>(sl, split_stride, s_lo, s_hi, k, active); };
     // The keep nibbles of a column group: lane sq computes ONE of the (up to four) Philox calls the group needs and the
     // chain-rule lane collects them by shuffles; the table rows are requested before the slab sums so that their round
     // trip overlaps the slabs' (ids -> {rows, slabs, masks} -> atomics instead of ids -> slabs -> masks -> rows -> atomics).
@@ -1332,7 +1293,7 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
 {
     const int B = p.n_po + p.n_sp;
     if (B <= 0) return hipSuccess;
-    const bool vec = scorer == SC_DISTMULT ? (d % 4 == 0) : (d % 8 == 0);
+    const bool vec = scorer == SC_COMPLEX ? (d % 8 == 0) : (d % 4 == 0);       // (ComplEx: float4 over each half)
     if (fuse && !vec) return hipErrorInvalidValue;
     if (vec) {
         // grad_rows: [2][Bpad][ldq] scratch -- relation rows, then entity rows
@@ -1345,9 +1306,13 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
             af = *fuse;
             sweep_wgs = (int)std::min<int64_t>(16384, (af.n_ent * (d / 4) + 127) / 128);     // one float4 per thread up to 2 M of them
         }
-        const int cols = scorer == SC_DISTMULT ? d : d / 2;
+        const int cols = scorer == SC_COMPLEX ? d / 2 : d;
         const int chunks = fuse ? 1 : std::min(8, (cols + 127) / 128);       // (the fused sweep's workgroups count on a 1-D grid)
-        if (nsplit >= 8)
+        if (sc_is_bias(scorer)) {
+            if (fuse) return hipErrorInvalidValue;       // (okge_train_step refuses the data-bias scorers)
+            if (hipError_t e = launch_bias_prefix_rows(d, scorer, p, slab, nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials,
+                                                       n_partials, loss_out, dr_rows, de_rows, distinct, st); e != hipSuccess) return e;
+        } else if (nsplit >= 8)
             hipLaunchKernelGGL(prefix_backward_vec_kernel<8>, dim3(B + 1 + sweep_wgs, chunks), dim3(128), 0, st, E, R, d, scorer, p, slab,
                                nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials, n_partials, loss_out, dr_rows, de_rows, distinct, af, B);
         else
@@ -1359,8 +1324,12 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
                                rel, ent, dR, dE);
         }
     } else {
-        hipLaunchKernelGGL(prefix_backward_kernel, dim3(B), dim3(128), 0, st, E, R, d, scorer, p, slab, nsplit, Bpad, ldq,
-                           ent_rows, dE, dR, distinct);
+        if (sc_is_bias(scorer)) {
+            if (hipError_t e = launch_bias_prefix_rows(d, scorer, p, slab, nsplit, Bpad, ldq, ent_rows, dE, dR, nullptr, 0, nullptr,
+                                                       nullptr, nullptr, distinct, st); e != hipSuccess) return e;
+        } else
+            hipLaunchKernelGGL(prefix_backward_kernel, dim3(B), dim3(128), 0, st, E, R, d, scorer, p, slab, nsplit, Bpad, ldq,
+                               ent_rows, dE, dR, distinct);
         if (loss_partials)
             hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, loss_partials, n_partials, loss_out);
     }

@@ -125,7 +125,16 @@ class LstmPass:
 class LSTMTrainStep(VT.VirtualTableStep):
     """forward + loss + backward + Adagrad for LSTM{Complex,Distmult}RelationModel (Trainer.compute_one_batch,
     trainer.py:181-257, over model.py:966-998).  The optimizer is dense: every token row, LSTM tensor and batch-norm parameter
-    moves every step (utils/optim.py:139-160)."""
+    moves every step (utils/optim.py:139-160).
+
+    With the "bias_entity" scorer (DataBiasOnlyEntityModel, model.py:317-350, :1036-1039) the relation slot never reaches the
+    score: the reference's backward leaves every relation parameter without a gradient and torch's Adagrad skips them.  Here
+    the relation slot is then encoded forward only, and only behind a batch-norm (its running statistics still move: the
+    encode runs in training mode, model.py:58-59, :72-73); no backward through it, and optimizer_step() touches neither its
+    parameters nor its gradients nor its accumulators.  "bias_relation" is the ordinary step: the prefix entities' gradient
+    rows arrive as zeros."""
+
+    bias_scorers = True
 
     def __init__(self, entity: LSTMSlot, relation: LSTMSlot, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8,
                  label_smoothing=0.0, dropout=0.0, relation_dropout=None, seed=0, engine=None):
@@ -133,6 +142,7 @@ class LSTMTrainStep(VT.VirtualTableStep):
                          label_smoothing=label_smoothing, dropout=dropout, relation_dropout=relation_dropout, seed=seed, engine=engine)
         self.passes = (LstmPass(self.device), LstmPass(self.device))
         self.decay_window = 1
+        self.relation_unused = scorer == "bias_entity"
 
     def state_tensors(self):
         out = []
@@ -154,17 +164,20 @@ class LSTMTrainStep(VT.VirtualTableStep):
             if rows.stop > rows.start:
                 calls[relation].append((H._i32(ids, dev), first, rows.stop - rows.start))
         self.passes[0].encode(self.entity, calls[0], True, EX, EV)
-        self.passes[1].encode(self.relation, calls[1], True, RX, RV)
+        if not self.relation_unused or self.relation.bn is not None:      # (unused: only for the running statistics)
+            self.passes[1].encode(self.relation, calls[1], True, RX, RV)
         return calls
 
     def _backward(self, batch, bufs, calls):
         """dEV / dRV -> batch-norm and the LSTM backward through time -> the slots' dW, d_flat (dlstm), d_bn ([d weight | d bias])"""
         EV, EX, dEV, RV, RX, dRV = bufs
         for ps, sl, cs, X, dV in zip(self.passes, (self.entity, self.relation), calls, (EX, RX), (dEV, dRV)):
+            if sl is self.relation and self.relation_unused:
+                continue
             ps.backward(sl, cs, X, dV, sl.dW, sl.dlstm, sl.d_bn if sl.bn is not None else None)
 
     def optimizer_step(self):
-        tensors = self.entity.optimizer_tensors() + self.relation.optimizer_tensors()
+        tensors = self.entity.optimizer_tensors() + ([] if self.relation_unused else self.relation.optimizer_tensors())
         for i in range(0, len(tensors), 4):                       # (okge_adagrad_multi: up to four tensors per launch)
             self.engine.adagrad_multi(tensors[i:i + 4], self.lr, self.weight_decay, self.eps)
         self._sync_module_batchnorms()

@@ -29,6 +29,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from . import _native as N
 from . import hotpath as H
 from .train_step import FusedTrainStep
 
@@ -114,6 +115,7 @@ class ShardedTrainStep:
     def __init__(self, E_local, R, scorer, n_ent, min_entities_size=2, lr=0.3, weight_decay=1e-10, eps=1e-8,
                  loss="bce", label_smoothing=0.0, input_dropout=0.0, relation_input_dropout=0.0, seed=0, engine=None,
                  group=None):
+        N.refuse_bias_scorer(scorer, type(self).__name__)
         self.group = group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
@@ -248,6 +250,7 @@ class ShardedEvaluator:
     the score-block path (any slot size)."""
 
     def __init__(self, E_local, R, scorer, n_ent, min_entities_size=2, engine=None, group=None):
+        N.refuse_bias_scorer(scorer, type(self).__name__)
         self.group = group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
@@ -380,6 +383,7 @@ class ReplicaStep:
     [(index into grad_tensors(), int tensor of touched rows, duplicates allowed)]."""
 
     def __init__(self, inner, group=None, sparse=True):
+        N.refuse_bias_scorer(getattr(inner, "scorer", None), type(self).__name__)
         self.inner, self.group = inner, group
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
         self.grads, self.stats = list(inner.grad_tensors()), list(inner.stat_tensors())

@@ -21,6 +21,7 @@ class FusedTrainStep:
                  grad_clip: float = 0.0, accumulate: int = 1):
         """Defaults follow config/fb15k237/fb15k237-complex-kge.yaml and the optimizer OptimRegime actually
         builds (utils/optim.py:29,139-160): Adagrad(lr, weight_decay=1e-10, eps=1e-8 leaked from Adam)."""
+        N.refuse_bias_scorer(scorer, type(self).__name__)
         self.E, self.R = E, R
         self.scorer, self.loss = scorer, loss
         self.lr, self.weight_decay, self.eps = lr, weight_decay, eps

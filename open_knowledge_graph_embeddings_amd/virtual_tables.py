@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _native as N
 from . import hotpath as H
 
 
@@ -71,8 +72,12 @@ class VirtualTableStep:
     entity / relation are its slots (.W, .d, .bn or None).  dropout is the entity streams', relation_dropout (default: the
     same) the relation streams' drop probability."""
 
+    bias_scorers = False              # a subclass that leaves a data-bias scorer's unused slot untouched says True
+
     def __init__(self, entity, relation, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0,
                  dropout=0.0, relation_dropout=None, seed=0, engine=None):
+        if not self.bias_scorers:
+            N.refuse_bias_scorer(scorer, type(self).__name__)
         self.entity, self.relation, self.scorer, self.loss = entity, relation, scorer, loss
         self.lr, self.weight_decay, self.eps, self.label_smoothing = lr, weight_decay, eps, label_smoothing
         self.dropout = dropout

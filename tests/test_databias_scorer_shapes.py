@@ -1,0 +1,300 @@
+"""The two data-bias scorer kinds (OKGE_BIAS_RELATION / OKGE_BIAS_ENTITY, openkge/model.py:281-350) in the kernels alone: plain
+tables through HotPath, no LSTM.
+
+The yardstick is exact.  A bias scorer equals the existing DistMult path with the unused operand all ones -- 1 * x is exact at
+every rounding the fold and the chain rule perform -- so every bias call is compared with a DistMult TWIN call that differs in:
+    bias_relation   the rows the prefixes' entity ids name are 1.0f, the prefix-entity dropout streams are off
+    bias_entity     the relation table is all 1.0f, the relation dropout streams are off
+Against the twin the loss, the score block, the candidate rows' gradient and the used slot's gradient are BIT-EQUAL, and the
+unused slot's gradient is exactly zero: in store mode the gradient buffers start as NaN (zeros prove the store), in atomic
+mode they start as zeros, as the ABI requires.  The prefix entity rows are never candidates (bias_relation's twin changes them).
+In atomic mode every duplicated id occurs exactly twice: two addends commute, the result does not depend on the order."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+SCORERS = ("bias_relation", "bias_entity")
+UNSUPPORTED = -2
+
+
+def _dev(a, dt=None):
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    return (t if dt is None else t.to(dt)).cuda()
+
+
+def _twice(rng, pool, n):
+    """n ids from `pool`, every one used at most twice"""
+    ids = rng.permutation(pool)[:(n + 1) // 2]
+    return rng.permutation(np.concatenate([ids, ids])[:n]).astype(np.int32)
+
+
+class Case:
+    """tables, ids and positives of one call; store = the virtual-table layout [candidates | po objects | sp subjects] with a
+    relation row per batch row, otherwise an id-table layout whose prefix entities lie behind the candidates"""
+
+    def __init__(self, seed, d, n_po, n_sp, N, store, cand_list=False):
+        rng = np.random.default_rng(seed)
+        B = n_po + n_sp
+        self.d, self.n_po, self.n_sp, self.N, self.B, self.store = d, n_po, n_sp, N, B, store
+        if store:
+            self.first, n_ent, n_rel = 0, N + B, B
+            ent = N + np.arange(B, dtype=np.int32)
+            rel = np.arange(B, dtype=np.int32)
+        else:
+            self.first, n_ent, n_rel = 2, 2 + N + B, B + 2
+            ent = _twice(rng, np.arange(2 + N, n_ent), B)
+            rel = _twice(rng, np.arange(2, n_rel), B)
+        self.ent, self.rel = ent, rel
+        self.cand = rng.permutation(np.arange(self.first, self.first + N)).astype(np.int32) if cand_list else None
+        self.E = (rng.standard_normal((n_ent, d)) * 0.3).astype(np.float32)
+        self.R = (rng.standard_normal((n_rel, d)) * 0.3).astype(np.float32)
+        y = np.zeros((B, N), np.float32)
+        for b in range(B):
+            y[b, rng.choice(N, size=int(rng.integers(1, 4)), replace=False)] = 1
+        self.y = y
+
+    def batch(self, H, drops):
+        b = H.PrefixBatch()
+        if self.n_po:
+            b.po_rel, b.po_obj = _dev(self.rel[:self.n_po]), _dev(self.ent[:self.n_po])
+        if self.n_sp:
+            b.sp_subj, b.sp_rel = _dev(self.ent[self.n_po:]), _dev(self.rel[self.n_po:])
+        if self.cand is None:
+            b.cand_first, b.n_cand = self.first, self.N
+        else:
+            b.cand_ids, b.cand_unique = _dev(self.cand), False
+        b.pos_row, b.pos_col = H.positives_from_dense(_dev(self.y))
+        b.drop_cand, b.drop_po_ent, b.drop_po_rel, b.drop_sp_ent, b.drop_sp_rel = drops
+        return b
+
+    def cand_rows(self):
+        return np.arange(self.first, self.first + self.N) if self.cand is None else self.cand
+
+
+def _drops(H, scorer, p, twin):
+    """p on the candidates and on every prefix stream of the bias call; the twin switches the unused slot's streams off"""
+    cand, po_e, po_r, sp_e, sp_r = H.dropout_specs(p, p, 77, 5)
+    if twin and scorer == "bias_relation":
+        po_e = sp_e = H.NO_DROP
+    if twin and scorer == "bias_entity":
+        po_r = sp_r = H.NO_DROP
+    return cand, po_e, po_r, sp_e, sp_r
+
+
+def _tables(c, scorer, twin):
+    E, R = c.E.copy(), c.R.copy()
+    if twin and scorer == "bias_relation":
+        E[c.ent] = 1.0
+    if twin and scorer == "bias_entity":
+        R[:] = 1.0
+    return _dev(E), _dev(R)
+
+
+def _call(H, hp, c, scorer, twin, loss, p):
+    E, R = _tables(c, scorer, twin)
+    fill = float("nan") if c.store else 0.0
+    dE, dR = torch.full_like(E, fill), torch.full_like(R, fill)
+    scores = torch.full((c.B, (c.N + 3) // 4 * 4), -7.0, device="cuda")[:, :c.N]
+    out = hp.forward_backward(E, R, "distmult" if twin else scorer, c.batch(H, _drops(H, scorer, p, twin)), dE, dR, loss=loss,
+                              label_smoothing=0.1 if loss == "bce" else 0.0, scores=scores, grads_zero=c.store,
+                              distinct_prefix_rows=c.store)
+    torch.cuda.synchronize()
+    return out.clone(), scores.clone(), dE, dR
+
+
+def _compare(c, scorer, mine, twin):
+    loss, scores, dE, dR = mine
+    t_loss, t_scores, t_dE, t_dR = twin
+    assert torch.equal(loss, t_loss) and torch.isfinite(loss).all()
+    assert torch.equal(scores, t_scores)
+    cand = torch.from_numpy(np.asarray(c.cand_rows(), np.int64)).cuda()
+    assert torch.equal(dE[cand], t_dE[cand]) and dE[cand].abs().sum() > 0
+    ent = torch.from_numpy(np.unique(c.ent).astype(np.int64)).cuda()
+    rel = torch.from_numpy(np.unique(c.rel).astype(np.int64)).cuda()
+    if scorer == "bias_relation":
+        assert torch.equal(dR, t_dR) and dR[rel].abs().sum() > 0
+        assert not dE[ent].ne(0).any()                        # (NaN != 0: a row nobody stored fails here)
+    else:
+        assert torch.equal(dE[ent], t_dE[ent]) and dE[ent].abs().sum() > 0
+        assert not (dR[rel].ne(0).any() if c.store else dR.ne(0).any())
+    from open_knowledge_graph_embeddings_amd import _native as NV
+    assert NV.id_errors() == 0
+
+
+def _run(monkeypatch, scorer, d, n_po, n_sp, N, store, loss="bce", p=0.0, cand_list=False, dq_split=None, seed=0):
+    from open_knowledge_graph_embeddings_amd import hotpath as H
+    if dq_split is not None:
+        monkeypatch.setenv("OKGE_DQ_SPLIT", str(dq_split))
+    hp = H.HotPath("cuda:0")
+    c = Case(2000 + seed, d, n_po, n_sp, N, store, cand_list)
+    _compare(c, scorer, _call(H, hp, c, scorer, False, loss, p), _call(H, hp, c, scorer, True, loss, p))
+
+
+# d: 3, 6 scalar chain-rule kernel; 12 float4 kernel, partial column chunk; 128 one 128-column chunk; 132 two; 260 the above-256
+# tile kernel; 512 the limit -- all in store mode with both directions present
+@pytest.mark.parametrize("scorer", SCORERS)
+@pytest.mark.parametrize("d", [3, 6, 12, 128, 132, 260, 512])
+def test_store_mode_every_slot_size(okge_lib, monkeypatch, scorer, d):
+    _run(monkeypatch, scorer, d, 7, 9, 130, True, p=0.4 if d in (6, 132, 512) else 0.0, seed=d)
+
+
+# every other axis at least once: (n_po, n_sp) incl. one direction empty and 16 / 17 rows against the 16-row query padding,
+# N under one candidate tile and two tiles plus a remainder, id-list candidates, KL, dropout, one / several dQ slabs, atomic mode
+AXES = [
+    # d, n_po, n_sp, N, store, loss, p, cand_list, dq_split
+    (12, 0, 5, 17, True, "bce", 0.0, False, None),
+    (12, 5, 0, 17, True, "kl", 0.4, False, 1),
+    (132, 9, 8, 130, True, "kl", 0.0, False, 3),
+    (6, 7, 9, 17, True, "bce", 0.0, False, 1),
+    (128, 7, 9, 130, True, "bce", 0.4, False, 2),
+    (260, 9, 8, 130, True, "bce", 0.4, False, 1),
+    (3, 7, 9, 130, False, "bce", 0.4, False, None),
+    (12, 9, 8, 17, False, "bce", 0.0, True, 1),
+    (132, 7, 9, 130, False, "kl", 0.4, True, 3),
+    (128, 0, 5, 130, False, "bce", 0.0, False, None),
+    (260, 5, 0, 17, False, "bce", 0.4, True, None),
+    (512, 7, 9, 130, False, "kl", 0.0, False, 2),
+    # beyond the issue's list: 33 candidate tiles -> 33 dQ slabs, the only way into the float4 kernel's instantiation with eight
+    # slab loads in flight (it is chosen from 8 slabs on, and its unrolled loop runs from 8 slabs per lane quarter on)
+    (132, 7, 9, 2100, True, "bce", 0.4, False, None),
+    (12, 9, 8, 2100, False, "bce", 0.0, False, None),
+]
+
+
+@pytest.mark.parametrize("scorer", SCORERS)
+@pytest.mark.parametrize("i", range(len(AXES)))
+def test_axes(okge_lib, monkeypatch, scorer, i):
+    d, n_po, n_sp, N, store, loss, p, cand_list, dq_split = AXES[i]
+    _run(monkeypatch, scorer, d, n_po, n_sp, N, store, loss, p, cand_list, dq_split, seed=100 + i)
+
+
+@pytest.mark.parametrize("scorer", SCORERS)
+@pytest.mark.parametrize("d,which", [(12, "both"), (132, "rel"), (260, "ent")])
+def test_segmented_backward_entry(okge_lib, scorer, d, which):
+    """okge_encode_queries + okge_prefix_backward_segmented: query block, masked entity rows and both gradients against the
+    twin; the row buffers start as NaN, so the unused slot's zeros prove that its rows were stored"""
+    from open_knowledge_graph_embeddings_amd import hotpath as H
+    from open_knowledge_graph_embeddings_amd.sharded import make_row_segments
+    hp = H.HotPath("cuda:0")
+    c = Case(2300 + d, d, 7, 9, 17, False)
+    sh = H.Shard(0, c.E.shape[0])
+    rows, ld = hp.query_shape(c.B, d)
+    g = torch.Generator().manual_seed(d)
+    dQ = torch.randn((rows, ld), generator=g).cuda()
+    seg = make_row_segments(c.rel[:c.n_po], c.ent[:c.n_po], c.ent[c.n_po:], c.rel[c.n_po:], "cuda", min_rows=1, min_rows_per_relation=0.0)
+    if which == "rel":
+        seg.ent = None
+    if which == "ent":
+        seg.rel = None
+    got = []
+    for twin in (False, True):
+        E, R = _tables(c, scorer, twin)
+        b = c.batch(H, _drops(H, scorer, 0.4, twin))
+        enc = hp.encode_queries(E, R, "distmult" if twin else scorer, b, sh)
+        dE, dR = torch.zeros_like(E), torch.zeros_like(R)
+        hp._grad_rows = torch.full((2, rows, ld), float("nan"), device="cuda")
+        hp.prefix_backward(E, R, "distmult" if twin else scorer, b, sh, dQ, None, dE, dR, rel_segments=seg)
+        torch.cuda.synchronize()
+        got.append((enc.clone(), dE, dR))
+    (enc, dE, dR), (t_enc, t_dE, t_dR) = got
+    assert torch.equal(enc[0], t_enc[0])                               # the query block, padding columns and rows included
+    assert not enc[0][:, d:].any() and not enc[0][c.B:].any()
+    if scorer == "bias_entity":
+        assert torch.equal(enc[1], t_enc[1])                           # the masked entity rows keep their meaning
+        assert torch.equal(dE, t_dE) and dE.abs().sum() > 0 and not dR.ne(0).any()
+    else:
+        assert torch.equal(dR, t_dR) and dR.abs().sum() > 0 and not dE.ne(0).any()
+
+
+@pytest.mark.parametrize("scorer", SCORERS)
+@pytest.mark.parametrize("d", [3, 12, 132])
+@pytest.mark.parametrize("b,n", [(9, 40), (65, 333)])
+def test_prefix_score_backward(okge_lib, scorer, d, b, n):
+    """okge_prefix_score_backward (the autograd surface): all three outputs bit-equal to the ones-twin's, the unused operand's
+    requested gradient all zero (the outputs start as NaN)"""
+    from open_knowledge_graph_embeddings_amd import _native as NV
+    from open_knowledge_graph_embeddings_amd import hotpath as H
+    hp = H.HotPath("cuda:0")
+    g = torch.Generator().manual_seed(1000 * d + b)
+    G, ent, rel = torch.randn((b, n), generator=g).cuda(), torch.randn((b, d), generator=g).cuda(), torch.randn((b, d), generator=g).cuda()
+    cand = torch.randn((n, d), generator=g).cuda()
+    ones = torch.ones_like(ent)
+    def run(kind, sp, e, r, need=(True, True, True)):
+        """the library call on outputs that start as NaN"""
+        ws = torch.empty(int(hp.lib.okge_prefix_score_backward_workspace_bytes(b, n, d)), dtype=torch.uint8, device="cuda")
+        out = [torch.full(shape, float("nan"), device="cuda") if w else None for shape, w in zip(((b, d), (b, d), (n, d)), need)]
+        NV.check(hp.lib.okge_prefix_score_backward(NV.SCORERS[kind], int(sp), G.data_ptr(), G.stride(0), b, n, e.data_ptr(), e.stride(0),
+                                                   r.data_ptr(), r.stride(0), cand.data_ptr(), cand.stride(0), d,
+                                                   *(None if x is None else x.data_ptr() for x in out), ws.data_ptr(), ws.numel(),
+                                                   hp._stream()), "okge_prefix_score_backward")
+        torch.cuda.synchronize()
+        return out
+    used, unused = (1, 0) if scorer == "bias_relation" else (0, 1)
+    for sp in (False, True):
+        mine = run(scorer, sp, ent, rel)
+        twin = run("distmult", sp, ones if scorer == "bias_relation" else ent, ones if scorer == "bias_entity" else rel)
+        assert torch.equal(mine[used], twin[used]) and torch.equal(mine[2], twin[2])
+        assert mine[used].abs().sum() > 0 and mine[2].abs().sum() > 0
+        assert not mine[unused].ne(0).any()                    # (NaN != 0: zeros prove the store)
+        only = run(scorer, sp, ent, rel, need=(used == 0, used == 1, False))
+        assert torch.equal(only[used], twin[used])
+        alone = run(scorer, sp, ent, rel, need=(unused == 0, unused == 1, False))
+        assert not alone[unused].ne(0).any()
+
+
+def test_refusing_entry_points(okge_lib):
+    """okge_score_triples, okge_train_step, okge_fold_queries, okge_evaluate_fused_shard: OKGE_ERR_UNSUPPORTED, a message that
+    names the scorer, the outputs' sentinels intact"""
+    from open_knowledge_graph_embeddings_amd import _native as NV
+    from open_knowledge_graph_embeddings_amd import hotpath as H
+    hp = H.HotPath("cuda:0")
+    L = hp.lib
+    c = Case(2400, 12, 3, 4, 17, False)
+    E, R = _dev(c.E), _dev(c.R)
+    st = hp._stream()
+    for scorer in SCORERS:
+        kind = NV.SCORERS[scorer]
+        name = {"bias_relation": b"OKGE_BIAS_RELATION", "bias_entity": b"OKGE_BIAS_ENTITY"}[scorer]
+        rows = torch.ones((5, 12), device="cuda")
+        out = torch.full((5, 1), -7.0, device="cuda")
+        rc = L.okge_score_triples(kind, rows.data_ptr(), 12, rows.data_ptr(), 12, rows.data_ptr(), 12, 5, 12, out.data_ptr(), st)
+        assert rc == UNSUPPORTED and name in L.okge_last_error()
+        b = c.batch(H, (H.NO_DROP,) * 5)
+        pb, cd, keep = hp._batch(b)
+        t = hp._tables(E, R, scorer)
+        # okge_fold_queries
+        nrows, ld = hp.query_shape(c.B, 12)
+        er, Q = torch.ones((nrows, ld), device="cuda"), torch.full((nrows, ld), -7.0, device="cuda")
+        rc = L.okge_fold_queries(ctypes.byref(t), ctypes.byref(pb), er.data_ptr(), ld, Q.data_ptr(), st)
+        assert rc == UNSUPPORTED and name in L.okge_last_error()
+        # okge_train_step
+        pos, keep_pos = hp._positives(b)
+        ws = hp.workspace(c.B, c.N, 12)
+        dE, dR = torch.full_like(E, -7.0), torch.full_like(R, -7.0)
+        sumE, sumR = torch.full_like(E, -7.0), torch.full_like(R, -7.0)
+        flags = torch.full((E.shape[0],), -7, dtype=torch.int32, device="cuda")
+        loss = torch.full((1,), -7.0, dtype=torch.float64, device="cuda")
+        opt = NV.AdagradOpt()
+        opt.sum_E, opt.sum_R, opt.prefix_flags, opt.lr, opt.weight_decay, opt.eps = sumE.data_ptr(), sumR.data_ptr(), flags.data_ptr(), 0.1, 0.0, 1e-8
+        E0, R0 = E.clone(), R.clone()
+        rc = L.okge_train_step(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(cd), ctypes.byref(pos), 0, 0.0, 1.0, 0, ctypes.byref(opt),
+                               loss.data_ptr(), dE.data_ptr(), dR.data_ptr(), ws.data_ptr(), hp._ws_bytes, st)
+        assert rc == UNSUPPORTED and name in L.okge_last_error()
+        # okge_evaluate_fused_shard
+        true_scores, counts = torch.full((c.B,), -7.0, device="cuda"), torch.full((c.B, 2), -7, dtype=torch.int64, device="cuda")
+        ar = torch.arange(c.B + 1, dtype=torch.int64, device="cuda")
+        ids = torch.zeros(c.B, dtype=torch.int32, device="cuda")
+        zero = torch.zeros(c.B + 1, dtype=torch.int64, device="cuda")
+        with pytest.raises(NV.OkgeError, match=name.decode()):
+            hp.evaluate_fused_shard(1, E, R, scorer, Q, c.B, b, H.Shard(0, E.shape[0]), c.N, zero, torch.zeros(0, dtype=torch.int32, device="cuda"),
+                                    ar, ar, ids, true_scores, counts)
+        torch.cuda.synchronize()
+        for x in (out, Q, dE, dR, sumE, sumR, loss, true_scores):
+            assert bool((x == -7.0).all())
+        assert bool((flags == -7).all()) and bool((counts == -7).all())
+        assert torch.equal(E, E0) and torch.equal(R, R0)
+        del keep, keep_pos
