@@ -112,8 +112,12 @@ class LstmSlot(Structure):
                 ("bn_eps", c_float), ("bn_momentum", c_float)]
 
 
-class LstmCall(Structure):
+class TokenCall(Structure):
+    """okge_lstm_call and okge_bigram_call: one layout (rows ids[0..n), or first_id .. first_id + n - 1 when ids is NULL)"""
     _fields_ = [("ids", c_void_p), ("first_id", c_int32), ("n", c_int32)]
+
+
+LstmCall = BigramCall = TokenCall
 
 
 class BigramSlot(Structure):
@@ -121,10 +125,6 @@ class BigramSlot(Structure):
                 ("max_len", c_int32), ("conv_weight", c_void_p), ("pool", c_int32), ("normalize", c_int32),
                 ("bn_weight", c_void_p), ("bn_bias", c_void_p), ("bn_running_mean", c_void_p), ("bn_running_var", c_void_p),
                 ("bn_num_batches_tracked", c_void_p), ("bn_eps", c_float), ("_pad", c_int32)]
-
-
-class BigramCall(Structure):
-    _fields_ = [("ids", c_void_p), ("first_id", c_int32), ("n", c_int32)]
 
 
 class AdagradOpt(Structure):

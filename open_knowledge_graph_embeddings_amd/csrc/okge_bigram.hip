@@ -4,7 +4,7 @@
 // None) over ALL n (L-1) positions of the call, padded ones included] -> + x_{t+1} -> x mask[t] = token[t+1] > 0 -> sum or max over
 // t -> ['mean': / (sum mask + 1e-12)].  Forward and backward, fp32 throughout, products on the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32).
 //
-// One PASS encodes the rows of up to BIGRAM_MAX_CALLS calls of one slot.  Position p = r (L-1) + t of row r; P = rows (L-1):
+// One PASS encodes the rows of up to ENC_MAX_CALLS calls of one slot.  Position p = r (L-1) + t of row r; P = rows (L-1):
 //   1 bigram_prep_kernel      token id of every (r, t) behind the id guard (-> pos_tok) and its live flag (token > 0)
 //   2 bigram_wt_kernel        [K0 | K1]^T (2d x d), and for the backward [K0 | K1] (d x 2d)
 //   3 bigram_gemm_kernel<FWD> Y = [x_t | x_{t+1}] . [K0 | K1]^T over the P positions: one launch, the token-row gather is the
@@ -28,28 +28,21 @@
 #include <string>
 
 #include "../../include/okge.h"
-#include "okge_kernels.h"
+#include "okge_token_encoder.h"
 
 namespace okge {
 
 namespace {
 
-constexpr int BIGRAM_MAX_CALLS = 8;
 constexpr int BIGRAM_MAX_LEN = 64;
-constexpr int TM = 64, TN = 128, TK = 16;
-constexpr int LDA = TK + 4;              // A tile [64 m][16 k]
-constexpr int LDB = TN + 16;             // [16 k][128 n] tiles: rows 16 banks apart
-constexpr int LDAT = TM + 16;            // A tile of the transposed product [16 k][64 m]
-constexpr int BN_COLS = 16, BN_LANES = 16;
+constexpr int GRID_CAP = 65536;          // workgroups of a grid-stride launch
 
 enum { B_FWD = 0, B_DX = 1, B_DW = 2 };
 enum { POOL_SUM = 0, POOL_MAX = 1 };
 enum { NORM_NONE = 0, NORM_MEAN = 1, NORM_BATCHNORM = 2 };
 
-struct CallsDev {
-    const int32_t *ids[BIGRAM_MAX_CALLS];
-    int32_t        first_id[BIGRAM_MAX_CALLS], row0[BIGRAM_MAX_CALLS + 1], chunk0[BIGRAM_MAX_CALLS + 1];
-    int32_t        n_calls, chunk;       // chunk: positions per batch-norm partial sum
+struct CallsDev : EncCalls {
+    int32_t chunk0[ENC_MAX_CALLS + 1], chunk;      // chunk: positions per batch-norm partial sum; chunk0: first chunk of a call
 };
 
 // workspace of a pass (carved in this order; sizes from rows R, max_len L, slot size d)
@@ -61,52 +54,31 @@ struct BigramWs {
     size_t   bytes;
 };
 
-inline int dw_splits(int64_t P, int d)
-{
-    const int64_t tiles = (int64_t)((d + TM - 1) / TM) * ((2 * d + TN - 1) / TN);
-    int64_t s = std::max<int64_t>(1, std::min<int64_t>(16, 1024 / std::max<int64_t>(tiles, 1)));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(s, P / 256));
-}
-
 BigramWs carve(char *p, int R, int L, int d, bool training)
 {
     BigramWs w;
     std::memset(&w, 0, sizeof(w));
     const int64_t P = (int64_t)R * (L - 1), PT = (int64_t)R * L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char * {
-        char *q = p ? p + off : nullptr;
-        off += (bytes + 255) / 256 * 256;
-        return q;
-    };
+    Carver cv{p};
     w.chunk = (int)std::max<int64_t>(2048, ((P + 4095) / 4096 + 15) / 16 * 16);
     w.max_chunks = (int)((P + w.chunk - 1) / w.chunk);
-    w.live = (uint8_t *)take((size_t)PT);
-    w.wt = (float *)take(sizeof(float) * (size_t)2 * d * d);
-    w.Y = (float *)take(sizeof(float) * (size_t)P * d);
-    w.bn = (float *)take(sizeof(float) * (size_t)BIGRAM_MAX_CALLS * 4 * d);
-    w.part = (double *)take(sizeof(double) * (size_t)(w.max_chunks + BIGRAM_MAX_CALLS) * 2 * d);
+    w.live = cv.take<uint8_t>((size_t)PT);
+    w.wt = cv.take<float>((size_t)2 * d * d);
+    w.Y = cv.take<float>((size_t)P * d);
+    w.bn = cv.take<float>((size_t)ENC_MAX_CALLS * 4 * d);
+    w.part = cv.take<double>((size_t)(w.max_chunks + ENC_MAX_CALLS) * 2 * d);
     if (training) {
-        w.splits = dw_splits(P, d);
-        w.amax = (uint8_t *)take((size_t)R * d);
-        w.wt2 = (float *)take(sizeof(float) * (size_t)2 * d * d);
-        w.dE = (float *)take(sizeof(float) * (size_t)P * d);
-        w.dYX = (float *)take(sizeof(float) * (size_t)PT * d);
-        w.dXc = (float *)take(sizeof(float) * (size_t)P * 2 * d);
-        w.slab = (float *)take(sizeof(float) * (size_t)w.splits * d * 2 * d);
+        w.splits = dw_splits(P, tiles_of(d, 2 * d));
+        w.amax = cv.take<uint8_t>((size_t)R * d);
+        w.wt2 = cv.take<float>((size_t)2 * d * d);
+        w.dE = cv.take<float>((size_t)P * d);
+        w.dYX = cv.take<float>((size_t)PT * d);
+        w.dXc = cv.take<float>((size_t)P * 2 * d);
+        w.slab = cv.take<float>((size_t)w.splits * d * 2 * d);
     }
-    w.bytes = off;
+    w.bytes = cv.bytes;
     return w;
 }
-
-__device__ __forceinline__ int call_of(const CallsDev &c, int r)
-{
-    int k = 0;
-    while (k + 1 < c.n_calls && r >= c.row0[k + 1]) ++k;
-    return k;
-}
-
-inline unsigned grid1(int64_t n, int per = 256) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(65536, (n + per - 1) / per)); }
 
 // ---- 1: tokens of the pass ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bigram_prep_kernel(const CallsDev c, const int32_t *__restrict__ tok, int n_ids, int vocab, int L,
@@ -147,8 +119,7 @@ struct GemmArgs {
     int32_t        d, L, P, k_per_split;
 };
 
-// C[m][n] = sum_k A(m, k) B(k, n) on a 64 x 128 tile: 4 waves, wave (wm, wn) = 32 rows x 64 columns = 2 x 4 MFMA blocks,
-// K in chunks of 16 through LDS (the next chunk's global loads in registers while the current one is multiplied).
+// One 64 x 128 tile of a product of the pass (enc_gemm_tile: 4 waves, K in chunks of 16 through LDS):
 //   FWD  M = P, K = 2d, N = d    A(m, k) = [x_t | x_{t+1}] of position m (gathered token rows), B = wt
 //   DX   M = P, K = d,  N = 2d   A = dY, B = wt2
 //   DW   M = d, K = P (this split's slab), N = 2d   A(m, k) = dY[k][m], B(k, n) = [x_t | x_{t+1}] of position k
@@ -156,11 +127,9 @@ template <int MODE>
 __global__ __launch_bounds__(256) void bigram_gemm_kernel(const GemmArgs a)
 {
     constexpr bool TA = MODE == B_DW;
-    __shared__ float As[TA ? TK * LDAT : TM * LDA];
-    __shared__ float Bs[TK * LDB];
     const int d = a.d, L = a.L, Lm = a.L - 1;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1;
-    const int m0 = blockIdx.x * TM, n0 = blockIdx.y * TN;
+    const int tid = threadIdx.x;
+    const int m0 = blockIdx.x * TM;
     int M, K, N, k_lo = 0;
     if (MODE == B_FWD) { M = a.P; K = 2 * d; N = d; }
     else if (MODE == B_DX) { M = a.P; K = d; N = 2 * d; }
@@ -184,95 +153,25 @@ __global__ __launch_bounds__(256) void bigram_gemm_kernel(const GemmArgs a)
         }
     }
     v4f acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
-    float ra[4], rb[8];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
+    enc_gemm_tile<TA>(
+        k_lo, K, N,
+        [&](int j, int kk) -> float {
             if (TA) {                                    // A[k][m] = dY[position k][channel m]
-                const int kk = k0 + (tid >> 6) + 4 * j, m = m0 + (tid & 63);
-                ra[j] = (kk < K && m < M) ? a.dY[(size_t)kk * d + m] : 0.f;
-            } else {
-                const int kk = k0 + (tid & 15);
-                float v = 0.f;
-                if (kk < K && xr[j]) {
-                    if (MODE == B_FWD) v = kk < d ? xr[j][kk] : hr[j][kk - d];
-                    else v = xr[j][kk];
-                }
-                ra[j] = v;
+                const int m = m0 + (tid & 63);
+                return m < M ? a.dY[(size_t)kk * d + m] : 0.f;
             }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int kk = k0 + (tid >> 7) + 2 * j, n = n0 + (tid & 127);
-            float v = 0.f;
-            if (kk < K && n < N) {
-                if (MODE == B_FWD) v = a.wt[(size_t)kk * N + n];
-                else if (MODE == B_DX) v = a.wt2[(size_t)kk * N + n];
-                else {                                   // [x_t | x_{t+1}] of position kk
-                    const size_t i = (size_t)(kk / Lm) * L + kk % Lm;
-                    v = n < d ? a.W[(size_t)a.pos_tok[i] * d + n] : a.W[(size_t)a.pos_tok[i + 1] * d + (n - d)];
-                }
-            }
-            rb[j] = v;
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (TA) As[((tid >> 6) + 4 * j) * LDAT + (tid & 63)] = ra[j];
-            else As[((tid >> 4) + 16 * j) * LDA + (tid & 15)] = ra[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) Bs[((tid >> 7) + 2 * j) * LDB + (tid & 127)] = rb[j];
-    };
-    if (k_lo < K) load(k_lo);
-    for (int k0 = k_lo; k0 < K; k0 += TK) {
-        __syncthreads();                                 // the previous chunk has been multiplied
-        stage();
-        __syncthreads();
-        if (k0 + TK < K) load(k0 + TK);
-        // blocked summation: the chunk's 16 products as a fresh MFMA chain, then one add into the running sum
-        v4f part[2][4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) part[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k4 = 0; k4 < TK; k4 += 4) {
-            float av[2], bv[4];
-            const int kk = k4 + (lane >> 4);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int m = 32 * wm + 16 * i + (lane & 15);
-                av[i] = TA ? As[kk * LDAT + m] : As[m * LDA + kk];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bv[j] = Bs[kk * LDB + 64 * wn + 16 * j + (lane & 15)];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) part[i][j] = mfma16(av[i], bv[j], part[i][j]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] += part[i][j];
-    }
-    // result register r of lane l in block (i, j): row 32 wm + 16 i + 4 (l >> 4) + r, column 64 wn + 16 j + (l & 15)
-    float *out = MODE == B_FWD ? a.Y : MODE == B_DX ? a.dXc : a.slab + (size_t)blockIdx.z * M * N;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + 32 * wm + 16 * i + 4 * (lane >> 4) + r, n = n0 + 64 * wn + 16 * j + (lane & 15);
-                if (m < M && n < N) out[(size_t)m * N + n] = acc[i][j][r];
-            }
+            if (!xr[j]) return 0.f;
+            if (MODE == B_FWD) return kk < d ? xr[j][kk] : hr[j][kk - d];
+            return xr[j][kk];
+        },
+        [&](int kk, int n) -> float {
+            if (MODE == B_FWD) return a.wt[(size_t)kk * N + n];
+            if (MODE == B_DX) return a.wt2[(size_t)kk * N + n];
+            const size_t i = (size_t)(kk / Lm) * L + kk % Lm;               // [x_t | x_{t+1}] of position kk
+            return n < d ? a.W[(size_t)a.pos_tok[i] * d + n] : a.W[(size_t)a.pos_tok[i + 1] * d + (n - d)];
+        },
+        acc);
+    enc_store_tile(acc, MODE == B_FWD ? a.Y : MODE == B_DX ? a.dXc : a.slab + (size_t)blockIdx.z * M * N, M, N);
 }
 
 // dK (d, d, 2) from the split-K slabs [d][2d], added in split order
@@ -290,16 +189,6 @@ __global__ __launch_bounds__(256) void bigram_dw_finish_kernel(const float *__re
 // ---- batch-norm over ALL positions of each call (BatchNorm1d(d, momentum=None, eps 1e-5) inside entity_encoder_in) ----------
 // Workgroup = (16 columns, one chunk of positions, one call), 16 position lanes per column; sums in double, the 16 lanes and
 // then the chunks added in a fixed order.
-__device__ __forceinline__ double bn_colsum(double v, double *red)
-{
-    const int col = threadIdx.x % BN_COLS, ln = threadIdx.x / BN_COLS;
-    __syncthreads();
-    red[ln * BN_COLS + col] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int j = 0; j < BN_LANES; ++j) s += red[j * BN_COLS + col];
-    return s;
-}
 
 struct BnDev {
     const float *w, *b;
@@ -479,20 +368,6 @@ __global__ __launch_bounds__(256) void bigram_bn_dy_kernel(const CallsDev c, con
     }
 }
 
-__global__ __launch_bounds__(256) void bigram_bn_grad_kernel(int n_calls, int d, const float *__restrict__ saved, float *__restrict__ d_w,
-                                                             float *__restrict__ d_b)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= d) return;
-    float gw = 0.f, gb = 0.f;
-    for (int c = 0; c < n_calls; ++c) {
-        gw += saved[(size_t)c * 4 * d + 2 * d + k];
-        gb += saved[(size_t)c * 4 * d + 3 * d + k];
-    }
-    d_w[k] = gw;
-    d_b[k] = gb;
-}
-
 // dx[r, t] = dE[r, t-1] (residual) + (dY K1)[r, t-1] + (dY K0)[r, t]; dXc = [dY K0 | dY K1] per position
 __global__ __launch_bounds__(256) void bigram_dx_kernel(const float *__restrict__ dE, const float *__restrict__ dXc, int64_t PT, int d, int L,
                                                         float *__restrict__ dX)
@@ -513,7 +388,7 @@ __global__ __launch_bounds__(256) void bigram_dx_kernel(const float *__restrict_
 
 int check_slot(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t n_calls, CallsDev &c, int &R)
 {
-    if (!s || !calls || n_calls <= 0 || n_calls > BIGRAM_MAX_CALLS) return report_error(OKGE_ERR_INVALID, "1 to 8 bigram calls per pass");
+    if (!s || !calls || n_calls <= 0 || n_calls > ENC_MAX_CALLS) return report_error(OKGE_ERR_INVALID, "1 to 8 bigram calls per pass");
     if (!s->W || !s->token_ids || !s->conv_weight || s->d <= 0 || s->vocab <= 0 || s->n_ids <= 0)
         return report_error(OKGE_ERR_INVALID, "bad bigram slot");
     if (s->max_len < 2 || s->max_len > BIGRAM_MAX_LEN) return report_error(OKGE_ERR_UNSUPPORTED, "bigram max_len must lie in 2..64");
@@ -522,22 +397,8 @@ int check_slot(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t
     if (s->normalize < NORM_NONE || s->normalize > NORM_BATCHNORM) return report_error(OKGE_ERR_INVALID, "bigram normalize: 0, 1 (mean) or 2 (batchnorm)");
     if (s->normalize == NORM_BATCHNORM && (!s->bn_weight || !s->bn_bias || !s->bn_running_mean || !s->bn_running_var || !s->bn_num_batches_tracked))
         return report_error(OKGE_ERR_INVALID, "bigram batch-norm needs weight, bias, running statistics and the counter");
-    std::memset(&c, 0, sizeof(c));
-    c.n_calls = n_calls;
-    int64_t rows = 0;
-    for (int i = 0; i < n_calls; ++i) {
-        if (calls[i].n < 0) return report_error(OKGE_ERR_INVALID, "negative row count");
-        if (!calls[i].ids && (calls[i].first_id < 0 || (int64_t)calls[i].first_id + calls[i].n > s->n_ids))
-            return report_error(OKGE_ERR_INVALID, "row range outside the token-id matrix");
-        c.ids[i] = calls[i].ids;
-        c.first_id[i] = calls[i].first_id;
-        c.row0[i] = (int32_t)rows;
-        rows += calls[i].n;
-    }
-    c.row0[n_calls] = (int32_t)rows;
-    if (rows <= 0 || rows * s->max_len > INT32_MAX / 4) return report_error(OKGE_ERR_INVALID, "bigram pass of 1 .. 2^29 / max_len rows");
-    R = (int)rows;
-    return OKGE_OK;
+    c = CallsDev{};
+    return check_calls(calls, n_calls, s->n_ids, s->max_len, "bigram", c, R);
 }
 
 void set_chunks(CallsDev &c, int Lm, int chunk)
@@ -584,8 +445,8 @@ int bigram_encode_calls(const okge_bigram_slot *s, const okge_bigram_call *calls
     set_chunks(c, Lm, w.chunk);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t P = (int64_t)R * Lm, PT = (int64_t)R * L;
-    hipLaunchKernelGGL(bigram_prep_kernel, dim3(grid1(PT)), dim3(256), 0, st, c, s->token_ids, s->n_ids, s->vocab, L, PT, pos_tok, w.live, err);
-    hipLaunchKernelGGL(bigram_wt_kernel, dim3(grid1((int64_t)2 * d * d)), dim3(256), 0, st, s->conv_weight, d, w.wt, training ? w.wt2 : nullptr);
+    hipLaunchKernelGGL(bigram_prep_kernel, dim3(grid1(PT, 256, GRID_CAP)), dim3(256), 0, st, c, s->token_ids, s->n_ids, s->vocab, L, PT, pos_tok, w.live, err);
+    hipLaunchKernelGGL(bigram_wt_kernel, dim3(grid1((int64_t)2 * d * d, 256, GRID_CAP)), dim3(256), 0, st, s->conv_weight, d, w.wt, training ? w.wt2 : nullptr);
     GemmArgs a;
     std::memset(&a, 0, sizeof(a));
     a.W = s->W; a.wt = w.wt; a.pos_tok = pos_tok; a.Y = w.Y; a.d = d; a.L = L; a.P = (int32_t)P;
@@ -606,7 +467,7 @@ int bigram_encode_calls(const okge_bigram_slot *s, const okge_bigram_call *calls
     std::memset(&pa, 0, sizeof(pa));
     pa.W = s->W; pa.Y = w.Y; pa.saved = w.bn; pa.pos_tok = pos_tok; pa.live = w.live; pa.amax = w.amax; pa.out = out; pa.ld = ld;
     pa.d = d; pa.L = L; pa.R = R; pa.pool = s->pool; pa.normalize = s->normalize; pa.training = training != 0;
-    hipLaunchKernelGGL(bigram_pool_kernel, dim3(grid1((int64_t)R * d)), dim3(256), 0, st, c, b, pa);
+    hipLaunchKernelGGL(bigram_pool_kernel, dim3(grid1((int64_t)R * d, 256, GRID_CAP)), dim3(256), 0, st, c, b, pa);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return report_error(OKGE_ERR_HIP, std::string("bigram_encode: ") + hipGetErrorString(e));
     return OKGE_OK;
@@ -628,7 +489,7 @@ int bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call *cal
     set_chunks(c, Lm, w.chunk);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t P = (int64_t)R * Lm, PT = (int64_t)R * L;
-    hipLaunchKernelGGL(bigram_denc_kernel, dim3(grid1((int64_t)R * d)), dim3(256), 0, st, d_out, ld, (const uint8_t *)w.live,
+    hipLaunchKernelGGL(bigram_denc_kernel, dim3(grid1((int64_t)R * d, 256, GRID_CAP)), dim3(256), 0, st, d_out, ld, (const uint8_t *)w.live,
                        (const uint8_t *)w.amax, R, d, L, s->pool, s->normalize, w.dE);
     const float *dY = w.dE;
     if (bn) {
@@ -638,9 +499,9 @@ int bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call *cal
                            (const float *)w.Y, (const float *)w.dE, (const float *)w.bn, w.part);
         hipLaunchKernelGGL(bigram_bn_finish_kernel<1>, dim3((d + 255) / 256, n_calls), dim3(256), 0, st, c, Lm, d, s->bn_eps,
                            (const double *)w.part, w.bn);
-        hipLaunchKernelGGL(bigram_bn_dy_kernel, dim3(grid1(P * d)), dim3(256), 0, st, c, bn_of(s), Lm, d, P, (const float *)w.Y,
+        hipLaunchKernelGGL(bigram_bn_dy_kernel, dim3(grid1(P * d, 256, GRID_CAP)), dim3(256), 0, st, c, bn_of(s), Lm, d, P, (const float *)w.Y,
                            (const float *)w.dE, (const float *)w.bn, w.dYX);
-        hipLaunchKernelGGL(bigram_bn_grad_kernel, dim3((d + 255) / 256), dim3(256), 0, st, n_calls, d, (const float *)w.bn, d_bn_weight,
+        hipLaunchKernelGGL(enc_bn_grad_kernel, dim3((d + 255) / 256), dim3(256), 0, st, n_calls, d, (const float *)w.bn, d_bn_weight,
                            d_bn_bias);
         dY = w.dYX;
     }
@@ -650,15 +511,11 @@ int bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call *cal
     a.d = d; a.L = L; a.P = (int32_t)P;
     a.k_per_split = (int)(((P + w.splits - 1) / w.splits + TK - 1) / TK * TK);
     hipLaunchKernelGGL(bigram_gemm_kernel<B_DW>, dim3((d + TM - 1) / TM, (2 * d + TN - 1) / TN, w.splits), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(bigram_dw_finish_kernel, dim3(grid1((int64_t)2 * d * d)), dim3(256), 0, st, (const float *)w.slab, w.splits, d, d_conv);
+    hipLaunchKernelGGL(bigram_dw_finish_kernel, dim3(grid1((int64_t)2 * d * d, 256, GRID_CAP)), dim3(256), 0, st, (const float *)w.slab, w.splits, d, d_conv);
     hipLaunchKernelGGL(bigram_gemm_kernel<B_DX>, dim3((unsigned)((P + TM - 1) / TM), (2 * d + TN - 1) / TN), dim3(256), 0, st, a);
     // (dX takes the place of dY: the two products have read it)
-    hipLaunchKernelGGL(bigram_dx_kernel, dim3(grid1(PT * d)), dim3(256), 0, st, (const float *)w.dE, (const float *)w.dXc, PT, d, L, w.dYX);
-    DropDev none;
-    std::memset(&none, 0, sizeof(none));
-    none.scale = 1.f;
-    hipError_t e = launch_scatter_rows(w.dYX, d, pos_tok, pos_order, 0, (int)PT, d, none, dW, s->vocab, err, st);
-    if (e == hipSuccess) e = hipGetLastError();
+    hipLaunchKernelGGL(bigram_dx_kernel, dim3(grid1(PT * d, 256, GRID_CAP)), dim3(256), 0, st, (const float *)w.dE, (const float *)w.dXc, PT, d, L, w.dYX);
+    const hipError_t e = scatter_token_grads(w.dYX, d, pos_tok, pos_order, (int)PT, dW, s->vocab, err, st);
     if (e != hipSuccess) return report_error(OKGE_ERR_HIP, std::string("bigram_backward: ") + hipGetErrorString(e));
     return OKGE_OK;
 }

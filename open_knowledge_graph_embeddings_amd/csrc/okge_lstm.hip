@@ -3,7 +3,7 @@
 // h0 = c0 = 0) -> h at last = count(tokens > 0) - 1 (-1 wraps to max_len - 1) -> [BatchNorm1d per call] -> rows.
 // Forward and backward through time, fp32 throughout, products on the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32).
 //
-// One PASS encodes the rows of up to LSTM_MAX_CALLS calls of one slot (the LSTM is row-independent; batch-norm stays per call):
+// One PASS encodes the rows of up to ENC_MAX_CALLS calls of one slot (the LSTM is row-independent; batch-norm stays per call):
 //   1 lstm_rank_kernel    len = last + 1 of every row (ids behind the id guard), its rank among the rows of its 256-row block
 //                         with the same len, and the block's count per len
 //   2 lstm_scan_kernel    counting sort by len, DESCENDING (block order inside a len: stable): n_t = rows still live at step t,
@@ -32,27 +32,19 @@
 #include <string>
 
 #include "../../include/okge.h"
-#include "okge_kernels.h"
+#include "okge_token_encoder.h"
 
 namespace okge {
 
 namespace {
 
-constexpr int LSTM_MAX_CALLS = 8;
 constexpr int LSTM_MAX_LEN = 64;
 constexpr int RB = 256;                  // rows per block of the counting sort
-constexpr int TM = 64, TN = 128, TK = 16;
-constexpr int LDA = TK + 4;              // A tile [64 m][16 k]
-constexpr int LDB = TN + 16;             // [16 k][128 n] tiles: rows 16 banks apart, 4 rows x 16 columns hit 64 banks
-constexpr int LDAT = TM + 16;            // A tile of the transposed product [16 k][64 m]
+constexpr int GRID_CAP = 4096;           // workgroups of a grid-stride launch
 
 enum { G_FWD = 0, G_BWD = 1, G_DX = 2, G_DW = 3 };
 
-struct CallsDev {
-    const int32_t *ids[LSTM_MAX_CALLS];
-    int32_t        first_id[LSTM_MAX_CALLS], row0[LSTM_MAX_CALLS + 1];
-    int32_t        n_calls;
-};
+using CallsDev = EncCalls;
 
 // workspace of a pass (carved in this order; sizes from rows R, max_len L, slot size d)
 struct LstmWs {
@@ -62,55 +54,36 @@ struct LstmWs {
     size_t   bytes;
 };
 
-inline int dw_splits(int64_t pm, int d)
-{
-    const int64_t tiles = (int64_t)((4 * d + TM - 1) / TM) * ((2 * d + 1 + TN - 1) / TN);
-    int64_t s = std::max<int64_t>(1, std::min<int64_t>(16, 1024 / std::max<int64_t>(tiles, 1)));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(s, pm / 256));
-}
-
 __host__ __device__ inline int d32_of(int d) { return (d + 31) / 32 * 32; }
 
 LstmWs carve(char *p, int R, int L, int d, bool training)
 {
     LstmWs w;
     std::memset(&w, 0, sizeof(w));
-    const int64_t pm = (int64_t)R * L, nblk = (R + RB - 1) / RB;
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char * {
-        char *q = p ? p + off : nullptr;
-        off += (bytes + 255) / 256 * 256;
-        return q;
-    };
-    w.lens = (int32_t *)take(sizeof(int32_t) * R);
-    w.rank = (int32_t *)take(sizeof(int32_t) * R);
-    w.cnt = (int32_t *)take(sizeof(int32_t) * nblk * L);
-    w.base = (int32_t *)take(sizeof(int32_t) * nblk * L);
-    w.meta = (int32_t *)take(sizeof(int32_t) * (2 * L + 2));
-    w.order = (int32_t *)take(sizeof(int32_t) * R);
-    w.slen = (int32_t *)take(sizeof(int32_t) * R);
-    w.pprev = (int32_t *)take(sizeof(int32_t) * pm);
-    w.wt = (float *)take(sizeof(float) * (size_t)2 * d * 4 * d32_of(d));
-    w.C = (float *)take(sizeof(float) * (size_t)pm * d);
-    w.H = (float *)take(sizeof(float) * (size_t)pm * d);
-    w.bn = (float *)take(sizeof(float) * (size_t)LSTM_MAX_CALLS * 4 * d);
+    const size_t pm = (size_t)R * L, nblk = (R + RB - 1) / RB;
+    Carver cv{p};
+    w.lens = cv.take<int32_t>(R);
+    w.rank = cv.take<int32_t>(R);
+    w.cnt = cv.take<int32_t>(nblk * L);
+    w.base = cv.take<int32_t>(nblk * L);
+    w.meta = cv.take<int32_t>(2 * L + 2);
+    w.order = cv.take<int32_t>(R);
+    w.slen = cv.take<int32_t>(R);
+    w.pprev = cv.take<int32_t>(pm);
+    w.wt = cv.take<float>((size_t)2 * d * 4 * d32_of(d));
+    w.C = cv.take<float>(pm * d);
+    w.H = cv.take<float>(pm * d);
+    w.bn = cv.take<float>((size_t)ENC_MAX_CALLS * 4 * d);
     if (training) {
-        w.splits = dw_splits(pm, d);
-        w.gates = (float *)take(sizeof(float) * (size_t)pm * 4 * d);
-        w.dc = (float *)take(sizeof(float) * (size_t)R * d);
-        w.dY = (float *)take(sizeof(float) * (size_t)R * d);
-        w.slab = (float *)take(sizeof(float) * (size_t)w.splits * 4 * d * (2 * d + 1));
-        w.dX = (float *)take(sizeof(float) * (size_t)pm * d);
+        w.splits = dw_splits((int64_t)pm, tiles_of(4 * d, 2 * d + 1));
+        w.gates = cv.take<float>(pm * 4 * d);
+        w.dc = cv.take<float>((size_t)R * d);
+        w.dY = cv.take<float>((size_t)R * d);
+        w.slab = cv.take<float>((size_t)w.splits * 4 * d * (2 * d + 1));
+        w.dX = cv.take<float>(pm * d);
     }
-    w.bytes = off;
+    w.bytes = cv.bytes;
     return w;
-}
-
-__device__ __forceinline__ int call_of(const CallsDev &c, int r)
-{
-    int k = 0;
-    while (k + 1 < c.n_calls && r >= c.row0[k + 1]) ++k;
-    return k;
 }
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
@@ -237,14 +210,13 @@ struct GemmArgs {
     int32_t        d, L, t, training, k_per_split;
 };
 
-// C[m][n] = sum_k A(m, k) B(k, n) on a 64 x 128 tile: 4 waves, wave (wm, wn) = 32 rows x 64 columns = 2 x 4 MFMA blocks,
-// K in chunks of 16 through LDS (the next chunk's global loads in registers while the current one is multiplied).
+// One 64 x 128 tile of a product of the pass (enc_gemm_tile: 4 waves, K in chunks of 16 through LDS):
+//   FWD  gates_t = [x_t | h_{t-1}] . wt for the n_t live rows      BWD  dh_t = dG_{t+1} . W_hh
+//   DX   dx = dG . W_ih over the P positions                       DW   dG^T . [x | h_{t-1} | 1] over this split's positions
 template <int MODE>
 __global__ __launch_bounds__(256) void lstm_gemm_kernel(const GemmArgs a)
 {
     constexpr bool TA = MODE == G_DW;
-    __shared__ float As[TA ? TK * LDAT : TM * LDA];
-    __shared__ float Bs[TK * LDB];
     const int d = a.d, L = a.L, t = a.t;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1;
     const int m0 = blockIdx.x * TM, n0 = blockIdx.y * TN;
@@ -278,87 +250,25 @@ __global__ __launch_bounds__(256) void lstm_gemm_kernel(const GemmArgs a)
         }
     }
     v4f acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
-    float ra[4], rb[8];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
+    enc_gemm_tile<TA>(
+        k_lo, K, N,
+        [&](int j, int kk) -> float {
             if (TA) {                                    // A[k][m] = dG[position k][gate row m]
-                const int kk = k0 + (tid >> 6) + 4 * j, m = m0 + (tid & 63);
-                ra[j] = (kk < K && m < M) ? a.gates[(size_t)kk * 4 * d + m] : 0.f;
-            } else {
-                const int kk = k0 + (tid & 15);
-                float v = 0.f;
-                if (kk < K) {
-                    if (MODE == G_FWD) v = kk < d ? (xr[j] ? xr[j][kk] : 0.f) : (hr[j] ? hr[j][kk - d] : 0.f);
-                    else v = xr[j] ? xr[j][kk] : 0.f;
-                }
-                ra[j] = v;
+                const int m = m0 + (tid & 63);
+                return m < M ? a.gates[(size_t)kk * 4 * d + m] : 0.f;
             }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int kk = k0 + (tid >> 7) + 2 * j, n = n0 + (tid & 127);
-            float v = 0.f;
-            if (kk < K && n < N) {
-                if (MODE == G_FWD) v = a.wt[(size_t)kk * N + n];
-                else if (MODE == G_BWD) v = a.w_hh[(size_t)kk * d + n];
-                else if (MODE == G_DX) v = a.w_ih[(size_t)kk * d + n];
-                else {                                   // [x | h_{t-1} | 1] of position kk
-                    if (n < d) v = a.W[(size_t)a.pos_tok[kk] * d + n];
-                    else if (n < 2 * d) { const int pp = a.pprev[kk]; v = pp >= 0 ? a.H[(size_t)pp * d + (n - d)] : 0.f; }
-                    else v = 1.f;
-                }
-            }
-            rb[j] = v;
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (TA) As[((tid >> 6) + 4 * j) * LDAT + (tid & 63)] = ra[j];
-            else As[((tid >> 4) + 16 * j) * LDA + (tid & 15)] = ra[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) Bs[((tid >> 7) + 2 * j) * LDB + (tid & 127)] = rb[j];
-    };
-    if (k_lo < K) load(k_lo);
-    for (int k0 = k_lo; k0 < K; k0 += TK) {
-        __syncthreads();                                 // the previous chunk has been multiplied
-        stage();
-        __syncthreads();
-        if (k0 + TK < K) load(k0 + TK);
-        // blocked summation: the chunk's 16 products as a fresh MFMA chain, then one add into the running sum (one k-ordered
-        // chain over all of K -- up to P = 10^5 terms in the weight gradients -- lost a factor 3-4 in accuracy to a blocked sgemm)
-        v4f part[2][4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) part[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k4 = 0; k4 < TK; k4 += 4) {
-            float av[2], bv[4];
-            const int kk = k4 + (lane >> 4);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int m = 32 * wm + 16 * i + (lane & 15);
-                av[i] = TA ? As[kk * LDAT + m] : As[m * LDA + kk];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bv[j] = Bs[kk * LDB + 64 * wn + 16 * j + (lane & 15)];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) part[i][j] = mfma16(av[i], bv[j], part[i][j]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] += part[i][j];
-    }
+            if (MODE == G_FWD) return kk < d ? (xr[j] ? xr[j][kk] : 0.f) : (hr[j] ? hr[j][kk - d] : 0.f);
+            return xr[j] ? xr[j][kk] : 0.f;
+        },
+        [&](int kk, int n) -> float {
+            if (MODE == G_FWD) return a.wt[(size_t)kk * N + n];
+            if (MODE == G_BWD) return a.w_hh[(size_t)kk * d + n];
+            if (MODE == G_DX) return a.w_ih[(size_t)kk * d + n];
+            if (n < d) return a.W[(size_t)a.pos_tok[kk] * d + n];            // [x | h_{t-1} | 1] of position kk
+            if (n < 2 * d) { const int pp = a.pprev[kk]; return pp >= 0 ? a.H[(size_t)pp * d + (n - d)] : 0.f; }
+            return 1.f;
+        },
+        acc);
     // result register r of lane l in block (i, j): row 32 wm + 16 i + 4 (l >> 4) + r, column 64 wn + 16 j + (l & 15)
     if (MODE == G_FWD) {
         const int unit = blockIdx.y * 32 + 16 * wn + (lane & 15);
@@ -412,16 +322,7 @@ __global__ __launch_bounds__(256) void lstm_gemm_kernel(const GemmArgs a)
                 }
         }
     } else {
-        float *out = MODE == G_DX ? a.dX : a.slab + (size_t)blockIdx.z * M * N;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int m = m0 + 32 * wm + 16 * i + 4 * (lane >> 4) + r, n = n0 + 64 * wn + 16 * j + (lane & 15);
-                    if (m < M && n < N) out[(size_t)m * N + n] = acc[i][j][r];
-                }
+        enc_store_tile(acc, MODE == G_DX ? a.dX : a.slab + (size_t)blockIdx.z * M * N, M, N);
     }
 }
 
@@ -442,19 +343,8 @@ __global__ __launch_bounds__(256) void lstm_dw_finish_kernel(const float *__rest
 }
 
 // ---- batch-norm over the output rows of each call (BatchNorm1d(momentum 0.1, eps 1e-5), model.py:611-612, :985-986) ----------
-// Workgroup = (16 columns, one call), 16 row lanes per column; column sums in double, the 16 lanes added in a fixed order.
-constexpr int BN_COLS = 16, BN_LANES = 16;
-
-__device__ __forceinline__ double bn_colsum(double v, double *red)
-{
-    const int col = threadIdx.x % BN_COLS, ln = threadIdx.x / BN_COLS;
-    __syncthreads();
-    red[ln * BN_COLS + col] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int j = 0; j < BN_LANES; ++j) s += red[j * BN_COLS + col];
-    return s;
-}
+// Workgroup = (16 columns, one call), 16 row lanes per column; column sums in double, the 16 lanes added in a fixed order
+// (bn_colsum).
 
 struct BnDev {
     const float *w, *b;
@@ -550,45 +440,14 @@ __global__ __launch_bounds__(256) void lstm_bn_bwd_kernel(const CallsDev c, cons
     }
 }
 
-__global__ __launch_bounds__(256) void lstm_bn_grad_kernel(int n_calls, int d, const float *__restrict__ saved, float *__restrict__ d_w,
-                                                           float *__restrict__ d_b)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= d) return;
-    float gw = 0.f, gb = 0.f;
-    for (int c = 0; c < n_calls; ++c) {
-        gw += saved[(size_t)c * 4 * d + 2 * d + k];
-        gb += saved[(size_t)c * 4 * d + 3 * d + k];
-    }
-    d_w[k] = gw;
-    d_b[k] = gb;
-}
-
-inline unsigned grid1(int64_t n, int per = 256) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (n + per - 1) / per)); }
-
 int check_slot(const okge_lstm_slot *s, const okge_lstm_call *calls, int32_t n_calls, CallsDev &c, int &R)
 {
-    if (!s || !calls || n_calls <= 0 || n_calls > LSTM_MAX_CALLS) return report_error(OKGE_ERR_INVALID, "1 to 8 LSTM calls per pass");
+    if (!s || !calls || n_calls <= 0 || n_calls > ENC_MAX_CALLS) return report_error(OKGE_ERR_INVALID, "1 to 8 LSTM calls per pass");
     if (!s->W || !s->token_ids || !s->w_ih || !s->w_hh || !s->b_ih || !s->b_hh || s->d <= 0 || s->vocab <= 0 || s->n_ids <= 0)
         return report_error(OKGE_ERR_INVALID, "bad LSTM slot");
     if (s->max_len <= 0 || s->max_len > LSTM_MAX_LEN) return report_error(OKGE_ERR_UNSUPPORTED, "LSTM max_len must lie in 1..64");
     if (s->d > 512) return report_error(OKGE_ERR_UNSUPPORTED, "LSTM slot sizes above 512");
-    std::memset(&c, 0, sizeof(c));
-    c.n_calls = n_calls;
-    int64_t rows = 0;
-    for (int i = 0; i < n_calls; ++i) {
-        if (calls[i].n < 0) return report_error(OKGE_ERR_INVALID, "negative row count");
-        if (!calls[i].ids && (calls[i].first_id < 0 || (int64_t)calls[i].first_id + calls[i].n > s->n_ids))
-            return report_error(OKGE_ERR_INVALID, "row range outside the token-id matrix");
-        c.ids[i] = calls[i].ids;
-        c.first_id[i] = calls[i].first_id;
-        c.row0[i] = (int32_t)rows;
-        rows += calls[i].n;
-    }
-    c.row0[n_calls] = (int32_t)rows;
-    if (rows <= 0 || rows * s->max_len > INT32_MAX / 4) return report_error(OKGE_ERR_INVALID, "LSTM pass of 1 .. 2^29 / max_len rows");
-    R = (int)rows;
-    return OKGE_OK;
+    return check_calls(calls, n_calls, s->n_ids, s->max_len, "LSTM", c, R);
 }
 
 BnDev bn_of(const okge_lstm_slot *s)
@@ -632,7 +491,7 @@ int lstm_encode_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, int3
     hipLaunchKernelGGL(lstm_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, nblk, L, w.base, w.meta);
     hipLaunchKernelGGL(lstm_pack_kernel, dim3(nblk), dim3(RB), 0, st, c, s->token_ids, s->n_ids, s->vocab, L, R, w.lens, w.rank, w.base,
                        w.meta, w.order, w.slen, pos_tok, w.pprev, err);
-    hipLaunchKernelGGL(lstm_wt_kernel, dim3(grid1((int64_t)2 * d * 4 * d32_of(d))), dim3(256), 0, st, s->w_ih, s->w_hh, d, w.wt);
+    hipLaunchKernelGGL(lstm_wt_kernel, dim3(grid1((int64_t)2 * d * 4 * d32_of(d), 256, GRID_CAP)), dim3(256), 0, st, s->w_ih, s->w_hh, d, w.wt);
     GemmArgs a;
     std::memset(&a, 0, sizeof(a));
     a.W = s->W; a.wt = w.wt; a.w_ih = s->w_ih; a.w_hh = s->w_hh; a.b_ih = s->b_ih; a.b_hh = s->b_hh;
@@ -674,7 +533,7 @@ int lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, in
     if (bn) {
         hipLaunchKernelGGL(lstm_bn_bwd_kernel, dim3((d + BN_COLS - 1) / BN_COLS, n_calls), dim3(256), 0, st, c, bn_of(s), raw, d_out, ld, d,
                            w.bn, w.dY);
-        hipLaunchKernelGGL(lstm_bn_grad_kernel, dim3((d + 255) / 256), dim3(256), 0, st, n_calls, d, (const float *)w.bn, d_bn_weight, d_bn_bias);
+        hipLaunchKernelGGL(enc_bn_grad_kernel, dim3((d + 255) / 256), dim3(256), 0, st, n_calls, d, (const float *)w.bn, d_bn_weight, d_bn_bias);
         dY = w.dY;
         ld_dy = d;
     }
@@ -693,14 +552,10 @@ int lstm_backward_calls(const okge_lstm_slot *s, const okge_lstm_call *calls, in
     a.t = 0;
     a.k_per_split = (int)(((pm + w.splits - 1) / w.splits + TK - 1) / TK * TK);
     hipLaunchKernelGGL(lstm_gemm_kernel<G_DW>, dim3((4 * d + TM - 1) / TM, (2 * d + 1 + TN - 1) / TN, w.splits), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(lstm_dw_finish_kernel, dim3(grid1((int64_t)4 * d * (2 * d + 1))), dim3(256), 0, st, (const float *)w.slab, w.splits, d,
+    hipLaunchKernelGGL(lstm_dw_finish_kernel, dim3(grid1((int64_t)4 * d * (2 * d + 1), 256, GRID_CAP)), dim3(256), 0, st, (const float *)w.slab, w.splits, d,
                        d_w_ih, d_w_hh, d_b_ih, d_b_hh);
     hipLaunchKernelGGL(lstm_gemm_kernel<G_DX>, dim3((unsigned)((pm + TM - 1) / TM), (d + TN - 1) / TN), dim3(256), 0, st, a);
-    DropDev none;
-    std::memset(&none, 0, sizeof(none));
-    none.scale = 1.f;
-    e = launch_scatter_rows(w.dX, d, pos_tok, pos_order, 0, (int)pm, d, none, dW, s->vocab, err, st);
-    if (e == hipSuccess) e = hipGetLastError();
+    e = scatter_token_grads(w.dX, d, pos_tok, pos_order, (int)pm, dW, s->vocab, err, st);
     if (e != hipSuccess) return report_error(OKGE_ERR_HIP, std::string("lstm_backward: ") + hipGetErrorString(e));
     return OKGE_OK;
 }
