@@ -291,7 +291,9 @@ bool make_geometry(int B, int N, int d, Geometry &g)
     // [training part]
     g.off_loss = off;  off += align_up((size_t)std::max(2 * g.tiles * g.b_split + g.tail_tiles * g.tail_split, g.sk_wgs) * sizeof(double), 256);
     g.off_GT = off;    off += align_up((size_t)g.Bpad * g.ldg * sizeof(float), 256);
-    g.off_Cm = off;    off += align_up((size_t)g.range_tiles * NT * g.D16 * sizeof(float), 256);
+    // masked candidate rows of a range: three bf16 planes (6 bytes per element) up to slot size 208, fp32 rows above
+    g.off_Cm = off;    off += align_up(g.KB <= 13 ? (size_t)g.range_tiles * plane_cells_per_tile(g.D16) * sizeof(v8bf)
+                                                  : (size_t)g.range_tiles * NT * g.D16 * sizeof(float), 256);
     g.off_slab = off;  off += align_up((size_t)g.nsplit * g.Bpad * g.ldq * sizeof(float), 256);
     g.off_dcs = off;   off += g.sk_wgs > 0 ? align_up((size_t)2 * g.sk_wgs * NT * g.D16 * sizeof(float), 256)
                                      : g.b_split > 1 ? align_up((size_t)g.b_split * g.tiles * NT * g.D16 * sizeof(float), 256)
@@ -358,6 +360,7 @@ FusedArgs tile_window(const FusedArgs &base, const Geometry &g, int t0)
     if (a.loss_partial) a.loss_partial += t0;
     if (a.G) a.G += (size_t)t0 * (g.Bpad / BC) * (BC * NT);
     if (a.Cm) a.Cm += (size_t)t0 * NT * g.D16;
+    if (a.Cplanes) a.Cplanes += (size_t)t0 * plane_cells_per_tile(g.D16);
     if (a.X) a.X += (size_t)t0 * NT;
     if (a.stats) a.stats += (size_t)t0 * g.Bpad * 2;
     if (a.rk_slab) a.rk_slab += (size_t)t0 * a.rk_ngroups;
@@ -561,7 +564,8 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
     a.cand_exclusive = (!cand->ids || (flags & OKGE_TRAIN_UNIQUE_CANDIDATES)) ? 1 : 0;
     a.loss_only = loss_only ? 1 : 0;
     a.G = reinterpret_cast<float *>(ws + g.off_GT);
-    a.Cm = reinterpret_cast<float *>(ws + g.off_Cm);
+    if (g.KB <= 13) a.Cplanes = reinterpret_cast<v8bf *>(ws + g.off_Cm);
+    else a.Cm = reinterpret_cast<float *>(ws + g.off_Cm);
     a.dE = dE;
     a.dC_slab = (g.b_split > 1 || g.sk_wgs > 0 || g.tail_split > 1) ? reinterpret_cast<float *>(ws + g.off_dcs) : nullptr;
     a.loss_partial = reinterpret_cast<double *>(ws + g.off_loss);
@@ -605,7 +609,7 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
 #endif
     DqArgs q;
     std::memset(&q, 0, sizeof(q));
-    q.G = a.G; q.Cm = a.Cm;
+    q.G = a.G; q.Cm = a.Cm; q.Cplanes = a.Cplanes;
     q.slab = reinterpret_cast<float *>(ws + g.off_slab);
     q.d = g.d; q.KB = g.KB; q.LDK = g.LDK; q.Bpad = g.Bpad; q.ldq = g.ldq; q.ldg = g.ldg;
     q.nsplit = g.nsplit;

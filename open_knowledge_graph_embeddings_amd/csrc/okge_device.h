@@ -7,6 +7,7 @@
 namespace okge {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef __bf16 v8bf __attribute__((ext_vector_type(8)));   // one 16-byte cell of a bf16 plane (okge_dq_split.h)
 
 constexpr int WAVE = 64;
 

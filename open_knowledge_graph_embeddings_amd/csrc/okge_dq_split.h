@@ -15,17 +15,25 @@
 // LDS image of a 32-candidate sub-chunk (one K = 32 step of v_mfma_f32_16x16x32_bf16), per operand and plane:
 // [kg = 0..3][slot] cells of 16 bytes = 8 bf16 = the candidates 8 kg .. 8 kg + 7 of one output column (C) or batch row (G):
 // exactly what lane (slot & 15, kg) of the MFMA holds, read with one ds_read_b128.  A cell row is a multiple of 256 B, so the
-// ds_read_b128 lane groups (which mix two kg) cover 16 distinct 16-byte bank slots: conflict-free.  The transpose (global
-// memory has the candidate index slowest) happens in the staging pattern: a staging thread loads one float4 -- four
-// neighbouring columns -- from each of the 8 candidates of a kg, which leaves it with four cells.  The cell of column
-// 4 q + j goes to slot j * NQ + q (NQ = columns / 4), so that neighbouring lanes write neighbouring cells (ds_write_b128,
-// conflict-free); the MFMA's column index is the slot, and slot_to_col() undoes the permutation when the slab is stored.
+// ds_read_b128 lane groups (which mix two kg) cover 16 distinct 16-byte bank slots: conflict-free.
+//
+// C operand.  The planes of a masked candidate row are a function of that row alone, so they are made ONCE, by the tile kernel
+// (fused_tile64_kernel, okge_train64.hip: write_planes below, from the tile it parked in LDS), and leave it in this very image:
+// per sub-chunk [plane hi|mid|lo][kg][slot], 3 * C_CELLS contiguous cells, a tile's two sub-chunks back to back.  Staging
+// here is a flat copy, cell i of the block to cell i of the buffer: no conversion, no transpose.  The cell of column 4 q + j
+// sits in slot j * NQ + q (NQ = columns / 4): the writer holds one float4 -- four neighbouring columns -- of each of a kg's 8
+// candidates, which leaves it with four cells, and with that slot order neighbouring lanes store neighbouring cells.  The
+// MFMA's column index is the slot, and slot_to_col() undoes the permutation when the slab is stored.
+//
+// G operand.  G^T arrives in fp32 (the tile kernel's loss epilogue has no room for the split: DESIGN.md 8 (6)) and is split
+// here: thread (kg, batch row) of waves 2, 3, 6, 7 -- one kg per wave; the SIMDs whose two waves hold 3 + 3 column blocks at
+// KB = 13 -- loads that row's 8 candidates (8 dwords, coalesced over the lanes) and parks three cells.  Batch row 4 q + j sits
+// in slot 16 j + q.
 #pragma once
 #include "okge_device.h"
+#include "okge_kernels.h"
 
 namespace okge {
-
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 
 struct Planes { v8bf hi, mid, lo; };
 
@@ -54,56 +62,72 @@ struct DqSplit {
     static constexpr int NQ = 4 * KB;                 // float4 quads of a candidate row
     static constexpr int C_CELLS = 4 * NS, G_CELLS = 4 * 64;
     static constexpr int BUF_CELLS = 3 * (C_CELLS + G_CELLS);     // one sub-chunk: C planes, then G planes
-    static constexpr int C_TASKS = 4 * NQ;            // staging threads 0 .. C_TASKS - 1: (kg, quad) of the candidate rows
-    static constexpr int G_TID0 = 384;                // staging threads 384 .. 447 (wave 6): (kg, quad) of the G^T block
+    static constexpr int C_BLOCK = 3 * C_CELLS;       // the C planes of one sub-chunk, as the tile kernel writes them
+    static constexpr int THREADS = 512;
+    static constexpr int C_COPY = (C_BLOCK + THREADS - 1) / THREADS;      // most cells of the block a thread copies
     static constexpr int NBW = KB / 4 + (KB % 4 ? 1 : 0);         // most column blocks a wave takes
     static constexpr size_t LDS_BYTES = (size_t)2 * BUF_CELLS * 16;
     static constexpr int LDO = NS + 4;                // leading dimension of the fp32 output image the store goes through
-    static_assert(C_TASKS <= G_TID0, "staging roles overlap");
+    static_assert(2 * C_BLOCK == plane_cells_per_tile(NS), "a tile is two sub-chunk blocks");
     static_assert((size_t)64 * LDO * 4 <= LDS_BYTES, "the output image reuses the operand buffers");
 
     __device__ static int slot_to_col(int slot) { return 4 * (slot % NQ) + slot / NQ; }
 
-    // the 8 float4 a staging thread holds of one sub-chunk
-    struct Stage { v4f v[8]; };
-
-    // sub-chunk sc (32 candidates) of batch block bblk: global -> registers
-    __device__ static void prefetch(Stage &st, const float *G, const float *Cm, int sc, int bblk, int nJ, int tid)
+    // Tile kernel side: the 64 masked candidate rows parked in LDS as tile[64][ldk] fp32 (rows past N and columns past d are
+    // zeros there, and come out as zero planes) -> the tile's two sub-chunk blocks at dst.  Thread (8-candidate group g8 =
+    // 4 sub-chunk + kg, column quad q): 8 ds_read_b128, four split3, 12 16-byte stores, neighbouring lanes neighbouring cells.
+    __device__ static void write_planes(const float *tile, int ldk, v8bf *dst, int tid)
     {
-        if (tid < C_TASKS) {
-            const int kg = tid / NQ, q = tid % NQ;
-            const float *src = Cm + ((size_t)sc * NC + 8 * kg) * NS + 4 * q;
+        if (tid >= 8 * NQ) return;
+        const int g8 = tid / NQ, q = tid % NQ;
+        v4f v[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) st.v[k] = *reinterpret_cast<const v4f *>(src + (size_t)k * NS);
-        } else if (tid >= G_TID0 && tid < G_TID0 + 64) {
-            const int kg = (tid - G_TID0) >> 4, q = tid & 15;
-            const float *src = G + ((size_t)(sc >> 1) * nJ + bblk) * 4096 + ((sc & 1) * NC + 8 * kg) * 64 + 4 * q;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) st.v[k] = *reinterpret_cast<const v4f *>(src + k * 64);
-        }
-    }
-
-    // registers -> the three planes of LDS buffer `buf`
-    __device__ static void park(const Stage &st, v8bf *buf, int tid)
-    {
-        v8bf *dst;
-        int stride, plane;
-        if (tid < C_TASKS) {
-            dst = buf + (tid / NQ) * NS + tid % NQ; stride = NQ; plane = C_CELLS;
-        } else if (tid >= G_TID0 && tid < G_TID0 + 64) {
-            dst = buf + 3 * C_CELLS + ((tid - G_TID0) >> 4) * 64 + (tid & 15); stride = 16; plane = G_CELLS;
-        } else {
-            return;
-        }
+        for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const v4f *>(tile + (8 * g8 + k) * ldk + 4 * q);
+        dst += (g8 >> 2) * C_BLOCK + (g8 & 3) * NS + q;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float x[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) x[k] = st.v[k][j];
+            for (int k = 0; k < 8; ++k) x[k] = v[k][j];
             const Planes p = split3(x);
-            dst[j * stride] = p.hi;
-            dst[j * stride + plane] = p.mid;
-            dst[j * stride + 2 * plane] = p.lo;
+            dst[j * NQ] = p.hi;
+            dst[j * NQ + C_CELLS] = p.mid;
+            dst[j * NQ + 2 * C_CELLS] = p.lo;
+        }
+    }
+
+    // what a staging thread holds of one sub-chunk: its cells of the C block and, on the G waves, one batch row's 8 candidates
+    struct Stage { v8bf c[C_COPY]; float g[8]; };
+    __device__ static bool g_wave(int tid) { return tid & 128; }                        // waves 2, 3, 6, 7
+    __device__ static int g_kg(int tid) { return ((tid >> 8) << 1) | ((tid >> 6) & 1); }
+
+    // sub-chunk sc (32 candidates) of batch block bblk: global -> registers
+    __device__ static void prefetch(Stage &st, const float *G, const v8bf *Cplanes, int sc, int bblk, int nJ, int tid)
+    {
+        const v8bf *src = Cplanes + (size_t)sc * C_BLOCK + tid;
+#pragma unroll
+        for (int i = 0; i < C_COPY; ++i)
+            if ((i + 1) * THREADS <= C_BLOCK || i * THREADS + tid < C_BLOCK) st.c[i] = src[i * THREADS];
+        if (g_wave(tid)) {
+            const int lane = tid & 63, b = 4 * (lane & 15) + (lane >> 4);               // slot `lane` holds batch row b
+            const float *gs = G + ((size_t)(sc >> 1) * nJ + bblk) * 4096 + ((sc & 1) * NC + 8 * g_kg(tid)) * 64 + b;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) st.g[k] = gs[k * 64];
+        }
+    }
+
+    // registers -> LDS buffer `buf`: the C cells as they are, G^T split into its three planes
+    __device__ static void park(const Stage &st, v8bf *buf, int tid)
+    {
+#pragma unroll
+        for (int i = 0; i < C_COPY; ++i)
+            if ((i + 1) * THREADS <= C_BLOCK || i * THREADS + tid < C_BLOCK) buf[i * THREADS + tid] = st.c[i];
+        if (g_wave(tid)) {
+            v8bf *dst = buf + C_BLOCK + g_kg(tid) * 64 + (tid & 63);
+            const Planes p = split3(st.g);
+            dst[0] = p.hi;
+            dst[G_CELLS] = p.mid;
+            dst[2 * G_CELLS] = p.lo;
         }
     }
 

@@ -4,8 +4,8 @@
 // threads, workgroup = 64 batch rows x a contiguous run of 64-candidate chunks -> one [64][16 KB] slab block, written or (with
 // `accumulate`) added to; no atomics, fixed summation order, so two runs give identical bits.
 //
-// Loop: 32-candidate sub-chunks (two per chunk), two LDS buffers, ONE barrier per sub-chunk: sub-chunk i + 1 is split into
-// planes and parked in the second buffer while sub-chunk i is being multiplied.  Two register sets per staging thread keep the
+// Loop: 32-candidate sub-chunks (two per chunk), two LDS buffers, ONE barrier per sub-chunk: sub-chunk i + 1 -- the candidate
+// planes as the tile kernel wrote them, G^T split here -- is parked in the second buffer while sub-chunk i is being multiplied.  Two register sets per staging thread keep the
 // loads of sub-chunks i + 2 and i + 3 in flight (a sub-chunk is multiplied in well under a load latency).  Of a SIMD's two
 // waves the one with w < 4 parks before its MFMAs and the other one after: they take turns at the matrix core.
 #include "okge_dq_split.h"
@@ -40,19 +40,19 @@ __global__ __launch_bounds__(512, 2) void dq8s_kernel(const DqArgs a)
         const bool more = sc + 1 < sc_hi;
         if (w < 4 && more) {
             S::park(nxt, lds + (buf ^ 1) * S::BUF_CELLS, tid);
-            if (sc + 3 < sc_hi) S::prefetch(nxt, a.G, a.Cm, sc + 3, bblk, nJ, tid);
+            if (sc + 3 < sc_hi) S::prefetch(nxt, a.G, a.Cplanes, sc + 3, bblk, nJ, tid);
         }
         S::product(acc, corr, lds + buf * S::BUF_CELLS, h, blk0, nblk, lane);
         if (w >= 4 && more) {
             S::park(nxt, lds + (buf ^ 1) * S::BUF_CELLS, tid);
-            if (sc + 3 < sc_hi) S::prefetch(nxt, a.G, a.Cm, sc + 3, bblk, nJ, tid);
+            if (sc + 3 < sc_hi) S::prefetch(nxt, a.G, a.Cplanes, sc + 3, bblk, nJ, tid);
         }
     };
     if (sc_lo < sc_hi) {                              // (sc_hi - sc_lo is even)
-        S::prefetch(st[0], a.G, a.Cm, sc_lo, bblk, nJ, tid);
-        S::prefetch(st[1], a.G, a.Cm, sc_lo + 1, bblk, nJ, tid);
+        S::prefetch(st[0], a.G, a.Cplanes, sc_lo, bblk, nJ, tid);
+        S::prefetch(st[1], a.G, a.Cplanes, sc_lo + 1, bblk, nJ, tid);
         S::park(st[0], lds, tid);
-        if (sc_lo + 2 < sc_hi) S::prefetch(st[0], a.G, a.Cm, sc_lo + 2, bblk, nJ, tid);
+        if (sc_lo + 2 < sc_hi) S::prefetch(st[0], a.G, a.Cplanes, sc_lo + 2, bblk, nJ, tid);
     }
     for (int sc = sc_lo; sc < sc_hi; sc += 2) {
         step(sc, 0, st[1]);

@@ -44,6 +44,8 @@ constexpr int NT = 64;             // candidate rows per tile
 constexpr int BC = 64;             // batch rows per chunk
 constexpr int LDG = 68;            // leading dimension of the 64x64 G / X tile in LDS (4*odd)
 constexpr int FUSED_THREADS = 512; // 8 waves, two per SIMD (fused_tile_kernel: score / stats / count sweep)
+// 16-byte cells of the three bf16 planes of one 64-candidate tile of D16 columns (layout: okge_dq_split.h)
+constexpr int plane_cells_per_tile(int D16) { return 3 * NT * D16 / 8; }
 constexpr int POS_CACHE = 512;     // positives of one candidate tile cached in LDS (more spill to global reads)
 
 enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4 };
@@ -60,7 +62,7 @@ struct FusedArgs {
     const int32_t *tile_ptr;   // [tiles + 1] offsets into pos_* per candidate tile
     const float   *row_lse, *row_ysum;   // KL
     float         *G;          // [Bpad][ldg]  dLoss/dX / normalizer, row-major, ldg = 64 * tiles
-    float         *Cm;         // [64 * tiles][16*KB]  masked (dropped-out) candidate rows, for the dQ kernel
+    float         *Cm;         // [64 * tiles][16*KB]  masked (dropped-out) candidate rows, for the dQ kernel (slot sizes above 208)
     float         *dE;
     float         *dC_slab;    // [gridDim.y][64 * tiles][16*KB] partial candidate gradients when the batch is split over blockIdx.y
     double        *loss_partial;
@@ -83,11 +85,13 @@ struct FusedArgs {
     int           *id_err;         // device word counting out-of-range ids
     int32_t        loss_only;  // forward + loss only: no G store, no dC product, no write-back
     int32_t        sk_tiles;   // fused_tile64k_kernel: > 0 = stream-K launch over this many candidate tiles (grid = workgroups)
+    v8bf          *Cplanes;    // [tiles][plane_cells_per_tile]  slot sizes up to 208: the masked candidate rows as three bf16 planes, in place of Cm
 };
 
 struct DqArgs {
     const float   *G;
-    const float   *Cm;         // masked candidate rows written by the tile kernel
+    const float   *Cm;         // masked candidate rows written by the tile kernel: fp32 rows (dq8k_kernel) ...
+    const v8bf    *Cplanes;    // ... or their three bf16 planes (dq8s_kernel); the other one is nullptr
     float         *slab;       // [nsplit][Bpad][ldq]
     int32_t        d, KB, LDK, N, Bpad, ldq, ldg, nsplit;
     int32_t        accumulate; // add to the slabs instead of overwriting them (candidate ranges after the first)

@@ -4,7 +4,7 @@
 // (openkge/model.py:198-229,268-274,455-510; openkge/trainer.py:75-106,234).
 //
 // One workgroup owns 64 candidate entities: it gathers and drops them out ONCE into LDS (and hands the masked rows
-// to the dQ kernel through `Cm`), then sweeps the batch's folded query rows in
+// to the dQ kernel: as three bf16 planes through `Cplanes` up to slot size 208, as fp32 rows through `Cm` above), then sweeps the batch's folded query rows in
 // 64-row chunks.  Wave roles: blk = w & 3 (16-candidate block of the tile), h = w >> 2 (32-row half of the chunk: row
 // groups 2h, 2h + 1).
 //   score product : the wave's two 16x16 blocks X[rows of group][candidates of blk], ONE candidate operand
@@ -24,6 +24,7 @@
 #include <cstdio>
 
 #include "okge_device.h"
+#include "okge_dq_split.h"
 #include "okge_kernels.h"
 #include "okge_tile.h"
 
@@ -186,24 +187,26 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
                 *reinterpret_cast<v4f *>(Cs + r8 * LDK + k) = v0[it];
                 *reinterpret_cast<v4f *>(Cs + r8 * LDK + k + 4) = v1[it];
                 keepb[r8 * KEEP_LD + o] = (uint8_t)bits[it];
-                if (REGC && blockIdx.y == 0 && !a.loss_only) {        // the masked rows for the dQ kernel, straight from the registers
-                    float *cm = a.Cm + (size_t)(n0 + r8) * (16 * KB);  // (the tile's LDS is reused before a later chunk could)
-                    *reinterpret_cast<v4f *>(cm + k) = v0[it];
-                    *reinterpret_cast<v4f *>(cm + k + 4) = v1[it];
-                }
             }
         }
     }
     TL_STAMP_AT(41);       // tile parked in LDS
     __syncthreads();
     TL_STAMP_AT(42);
+    // REGC: the masked rows leave for the dQ kernel as the three bf16 planes it multiplies from, split ONCE here instead of by
+    // each of its row-block workgroups, from the parked tile (its LDS is reused only behind the first chunk's barrier; only the
+    // prefetched query chunk is live in registers at this point, so the split does not meet the sweep's allocation)
+    if constexpr (REGC) {
+        if (blockIdx.y == 0 && !a.loss_only)
+            DqSplit<KB>::write_planes(Cs, LDK, a.Cplanes + (size_t)blockIdx.x * plane_cells_per_tile(16 * KB), tid);
+    }
 
     v4f dc[KB];                                      // dC[n = 16blk + 4s + i][k = grad col(kbi, c)], rows of half h
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
     float lsum = 0.f;
     const bool col_edge = n0 + NT64 > a.N;           // the last tile: candidates past N are masked out of the loss
-    // masked candidate rows for the dQ kernel: written from LDS one octet column group per chunk (chunks 1 .. NOIT), so that
+    // !REGC: masked candidate rows (fp32) for the dQ kernel: written from LDS one octet column group per chunk (chunks 1 .. NOIT), so that
     // neither the prologue's HBM burst -- every workgroup gathering at once -- nor a later chunk carries all 12 MB;
     // whatever is left when the sweep ends (fewer chunks than column groups) goes out in the write-back
     auto write_cm = [&](int it) {
@@ -226,7 +229,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             breg[KB - 1][0] = Cs[(16 * blk + c) * LDK + 16 * (KB - 1) + s];
             breg[KB - 1][1] = Cs[(16 * blk + c) * LDK + 16 * (KB - 1) + 4 + s];
         }
-        cm_done = NOIT;                 // (written in the prologue)
+        cm_done = NOIT;                 // (left as planes, above)
         park_chunk(Qs);
         if (b_begin + BC64 < b_end) fetch_chunk(b_begin + BC64);
     }

@@ -3,8 +3,11 @@
 //      element is C + sum_k ak[k] bk[k] whatever the lane <-> k map; operands are chosen so that round-to-nearest, truncation,
 //      product-by-product accumulation and a wider internal sum give different fp32 bits.  Printed as hex.
 //  (b) Cycles per 32-candidate sub-chunk of the kernel's own loop at KB = 13, one 512-thread workgroup per CU:
-//      bare MFMAs on register operands / operands read from LDS (DqSplit::product) / product + plane split + park + barrier
-//      (the kernel's loop without its global loads).  The matrix-core floor is 78 MFMAs per SIMD x 16 cycles = 1248.
+//      bare MFMAs on register operands / operands read from LDS (DqSplit::product) / product + park + barrier (the kernel's
+//      loop without its global loads) in its two forms: BEFORE the tile kernel wrote the candidate planes -- every fp32
+//      candidate row and G^T split here, the retired staging kept below as OldStage / park_split_all -- and as it is NOW --
+//      candidate cells copied, G^T split on four waves (DqSplit::park).  The matrix-core floor is 78 MFMAs per SIMD x 16
+//      cycles = 1248.
 // Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -o mfma_bf16_split.bin mfma_bf16_split.hip
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -35,6 +38,46 @@ __global__ __launch_bounds__(64) void probe_kernel(const float *ak, const float 
 static unsigned bits(float f) { unsigned u; memcpy(&u, &f, 4); return u; }
 
 // ---- (b) ------------------------------------------------------------------------------------------------------------
+// the staging dq8s_kernel had while the masked candidate rows reached it in fp32: threads 0 .. 4 NQ - 1 hold 8 candidates x one
+// float4 of the rows, wave 6 the same of the G^T block; everything is split when it is parked
+struct OldStage { v4f v[8]; };
+template <int KB>
+__device__ void park_split_all(const OldStage &st, v8bf *buf, int tid)
+{
+    using S = DqSplit<KB>;
+    constexpr int C_TASKS = 4 * S::NQ, G_TID0 = 384;
+    v8bf *dst;
+    int stride, plane;
+    if (tid < C_TASKS) {
+        dst = buf + (tid / S::NQ) * S::NS + tid % S::NQ; stride = S::NQ; plane = S::C_CELLS;
+    } else if (tid >= G_TID0 && tid < G_TID0 + 64) {
+        dst = buf + 3 * S::C_CELLS + ((tid - G_TID0) >> 4) * 64 + (tid & 15); stride = 16; plane = S::G_CELLS;
+    } else {
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float x[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = st.v[k][j];
+        const Planes p = split3(x);
+        dst[j * stride] = p.hi;
+        dst[j * stride + plane] = p.mid;
+        dst[j * stride + 2 * plane] = p.lo;
+    }
+}
+
+// variant not kept: candidate cells copied as now, G^T still split by wave 6 alone (one float4 x 8 candidates per thread)
+template <int KB>
+__device__ void park_copy_g_wave6(const typename DqSplit<KB>::Stage &st, const OldStage &g, v8bf *buf, int tid)
+{
+    using S = DqSplit<KB>;
+#pragma unroll
+    for (int i = 0; i < S::C_COPY; ++i)
+        if (i * S::THREADS + tid < S::C_BLOCK) buf[i * S::THREADS + tid] = st.c[i];
+    if (tid >= 384 && tid < 448) park_split_all<KB>(g, buf, tid);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void loop_kernel(const float *src, float *out, unsigned long long *cyc, int iters)
 {
@@ -46,8 +89,15 @@ __global__ __launch_bounds__(512, 2) void loop_kernel(const float *src, float *o
     v4f acc[2][S::NBW], corr[2][S::NBW];
     for (int r = 0; r < 2; ++r)
         for (int nb = 0; nb < S::NBW; ++nb) acc[r][nb] = corr[r][nb] = (v4f){0.f, 0.f, 0.f, 0.f};
-    typename S::Stage st;
-    for (int k = 0; k < 8; ++k) st.v[k] = *reinterpret_cast<const v4f *>(src + (size_t)(tid * 8 + k) * 4);
+    OldStage old;
+    for (int k = 0; k < 8; ++k) old.v[k] = *reinterpret_cast<const v4f *>(src + (size_t)(tid * 8 + k) * 4);
+    typename S::Stage st;                             // any finite bf16 cells / floats will do
+    for (int i = 0; i < S::C_COPY; ++i) {
+        float x[8];
+        for (int k = 0; k < 8; ++k) x[k] = old.v[k][i & 3] + (float)i;
+        st.c[i] = split3(x).hi;
+    }
+    for (int k = 0; k < 8; ++k) st.g[k] = old.v[k][0];
     S::park(st, lds, tid);
     S::park(st, lds + S::BUF_CELLS, tid);
     __syncthreads();
@@ -71,10 +121,22 @@ __global__ __launch_bounds__(512, 2) void loop_kernel(const float *src, float *o
                     }
         } else if (MODE == 1) {
             S::product(acc, corr, lds + buf * S::BUF_CELLS, h, blk0, nblk, lane);
-        } else {
+        } else if (MODE == 2) {
             __syncthreads();
             // the staged values change every iteration (as they do in the kernel), so the split cannot be hoisted out of the loop
-            for (int k = 0; k < 8; ++k) st.v[k] += (v4f){1e-3f, 1e-3f, 1e-3f, 1e-3f};
+            for (int k = 0; k < 8; ++k) old.v[k] += (v4f){1e-3f, 1e-3f, 1e-3f, 1e-3f};
+            if (w < 4) park_split_all<13>(old, lds + (buf ^ 1) * S::BUF_CELLS, tid);
+            S::product(acc, corr, lds + buf * S::BUF_CELLS, h, blk0, nblk, lane);
+            if (w >= 4) park_split_all<13>(old, lds + (buf ^ 1) * S::BUF_CELLS, tid);
+        } else if (MODE == 4) {
+            __syncthreads();
+            for (int k = 0; k < 8; ++k) old.v[k] += (v4f){1e-3f, 1e-3f, 1e-3f, 1e-3f};
+            if (w < 4) park_copy_g_wave6<13>(st, old, lds + (buf ^ 1) * S::BUF_CELLS, tid);
+            S::product(acc, corr, lds + buf * S::BUF_CELLS, h, blk0, nblk, lane);
+            if (w >= 4) park_copy_g_wave6<13>(st, old, lds + (buf ^ 1) * S::BUF_CELLS, tid);
+        } else {
+            __syncthreads();
+            for (int k = 0; k < 8; ++k) st.g[k] += 1e-3f;
             if (w < 4) S::park(st, lds + (buf ^ 1) * S::BUF_CELLS, tid);
             S::product(acc, corr, lds + buf * S::BUF_CELLS, h, blk0, nblk, lane);
             if (w >= 4) S::park(st, lds + (buf ^ 1) * S::BUF_CELLS, tid);
@@ -167,6 +229,8 @@ int main()
     printf("== (b) KB = 13 loop, %d workgroups x 512 threads, %d sub-chunks each; floor 1248 cycles per sub-chunk and SIMD\n", blocks, iters);
     if (run_loop<0>("bare MFMAs, register operands", src, out, cyc, blocks, iters)) return 1;
     if (run_loop<1>("operands from LDS (product)", src, out, cyc, blocks, iters)) return 1;
-    if (run_loop<2>("product + split + park + barrier", src, out, cyc, blocks, iters)) return 1;
+    if (run_loop<2>("before: product + split of C and G^T + park", src, out, cyc, blocks, iters)) return 1;
+    if (run_loop<3>("now: product + C cells copied, G^T split by 4 waves", src, out, cyc, blocks, iters)) return 1;
+    if (run_loop<4>("not kept: C cells copied, G^T split by wave 6", src, out, cyc, blocks, iters)) return 1;
     return 0;
 }
