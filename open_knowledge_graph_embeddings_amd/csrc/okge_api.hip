@@ -149,7 +149,7 @@ struct Geometry {
     // intermediate, G^T, and everything sized like it (masked rows Cm, KL statistics) is O(B x range_n):
     // 41 GB -> 1 GB at |E| = 2.5 M, B = 4096.  A range is one tile-kernel launch + one dq launch (slabs accumulate).
     int    range_n, n_ranges, range_tiles;
-    size_t off_Q, off_tptr, off_stats, off_lse, off_ysum, off_run, off_loss, off_GT, off_Cm, off_slab, off_dcs;
+    size_t off_Q, off_tptr, off_stats, off_lse, off_ysum, off_run, off_loss, off_GT, off_Cm, off_slab, off_dcs, off_Qp;
     size_t score_bytes, lse_bytes, total;
 };
 
@@ -298,6 +298,8 @@ bool make_geometry(int B, int N, int d, Geometry &g)
     g.off_dcs = off;   off += g.sk_wgs > 0 ? align_up((size_t)2 * g.sk_wgs * NT * g.D16 * sizeof(float), 256)
                                      : g.b_split > 1 ? align_up((size_t)g.b_split * g.tiles * NT * g.D16 * sizeof(float), 256)
                                      : g.tail_split > 1 ? align_up((size_t)g.tail_split * g.tail_tiles * NT * g.D16 * sizeof(float), 256) : 0;
+    // the folded queries once more as three bf16 planes, for the tile kernel's gradient product (okge_tile_grad_split.h)
+    g.off_Qp = off;    off += tile_grad_split(g.KB) ? align_up((size_t)g.Bpad * g.D16 * 6, 256) : 0;
     g.total = off;
     return true;
 }
@@ -546,11 +548,18 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
             clr.p[2] = dE + hi * d64;           clr.n[2] = ((int64_t)t->n_ent - hi) * d64;
         }
         if (opt) clr.prefix_flags = opt->prefix_flags;
+        // the tile kernel's gradient product reads Q as three bf16 planes: written by the launch that folds the rows, or from
+        // the caller's block by a launch of its own
+        v8bf *q_planes = tile_grad_split(g.KB) && !loss_only ? reinterpret_cast<v8bf *>(ws + g.off_Qp) : nullptr;
         e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + g.off_Q), g.ldq,
                                   q_ext ? 0 : g.Bpad, nullptr, pos->col, pos->nnz,
                                   reinterpret_cast<int32_t *>(ws + g.off_tptr), g.tiles, NT, cand_col0, st,
-                                  (clear_grads || kl_own_lse || opt) ? &clr : nullptr);
+                                  (clear_grads || kl_own_lse || opt) ? &clr : nullptr, q_planes, g.KB);
         if (e != hipSuccess) return fail_hip(e, "encode_queries");
+        if (q_ext && q_planes) {
+            e = launch_query_planes(q_ext, g.ldq, B, g.Bpad, g.d, g.KB, q_planes, st);
+            if (e != hipSuccess) return fail_hip(e, "query_planes");
+        }
     }
     FusedArgs a;
     fill_fused_common(a, g, t, cand, ws);
@@ -566,6 +575,7 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
     a.G = reinterpret_cast<float *>(ws + g.off_GT);
     if (g.KB <= 13) a.Cplanes = reinterpret_cast<v8bf *>(ws + g.off_Cm);
     else a.Cm = reinterpret_cast<float *>(ws + g.off_Cm);
+    if (tile_grad_split(g.KB)) a.Qplanes = reinterpret_cast<const v8bf *>(ws + g.off_Qp);
     a.dE = dE;
     a.dC_slab = (g.b_split > 1 || g.sk_wgs > 0 || g.tail_split > 1) ? reinterpret_cast<float *>(ws + g.off_dcs) : nullptr;
     a.loss_partial = reinterpret_cast<double *>(ws + g.off_loss);

@@ -37,17 +37,25 @@ namespace okge {
 
 struct Planes { v8bf hi, mid, lo; };
 
+// one float -> its three bf16
+struct Split1 { __bf16 hi, mid, lo; };
+__device__ __forceinline__ Split1 split1(float x)
+{
+    const __bf16 h = (__bf16)x;
+    const float r1 = x - (float)h;
+    const __bf16 m = (__bf16)r1;
+    const float r2 = r1 - (float)m;
+    return {h, m, (__bf16)r2};
+}
+
 // 8 floats -> three cells
 __device__ __forceinline__ Planes split3(const float (&x)[8])
 {
     Planes p;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const __bf16 h = (__bf16)x[k];
-        const float r1 = x[k] - (float)h;
-        const __bf16 m = (__bf16)r1;
-        const float r2 = r1 - (float)m;
-        p.hi[k] = h; p.mid[k] = m; p.lo[k] = (__bf16)r2;
+        const Split1 v = split1(x[k]);
+        p.hi[k] = v.hi; p.mid[k] = v.mid; p.lo[k] = v.lo;
     }
     return p;
 }

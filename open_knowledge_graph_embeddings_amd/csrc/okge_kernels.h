@@ -46,6 +46,9 @@ constexpr int LDG = 68;            // leading dimension of the 64x64 G / X tile 
 constexpr int FUSED_THREADS = 512; // 8 waves, two per SIMD (fused_tile_kernel: score / stats / count sweep)
 // 16-byte cells of the three bf16 planes of one 64-candidate tile of D16 columns (layout: okge_dq_split.h)
 constexpr int plane_cells_per_tile(int D16) { return 3 * NT * D16 / 8; }
+// the instances of fused_tile64_kernel whose gradient product dC = G^T . Q runs on the bf16 matrix cores, from three bf16 planes
+// of Q made once per step (okge_tile_grad_split.h)
+constexpr bool tile_grad_split(int KB) { return KB == 13; }
 constexpr int POS_CACHE = 512;     // positives of one candidate tile cached in LDS (more spill to global reads)
 
 enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4 };
@@ -86,6 +89,7 @@ struct FusedArgs {
     int32_t        loss_only;  // forward + loss only: no G store, no dC product, no write-back
     int32_t        sk_tiles;   // fused_tile64k_kernel: > 0 = stream-K launch over this many candidate tiles (grid = workgroups)
     v8bf          *Cplanes;    // [tiles][plane_cells_per_tile]  slot sizes up to 208: the masked candidate rows as three bf16 planes, in place of Cm
+    const v8bf    *Qplanes;    // [Bpad / 64][chunk image]  tile_grad_split(KB): Q as three bf16 planes (okge_tile_grad_split.h)
 };
 
 struct DqArgs {
@@ -120,7 +124,10 @@ constexpr int CLEAR_REGIONS = 4;
 struct ClearSpec { float *p[CLEAR_REGIONS]; int64_t n[CLEAR_REGIONS]; int32_t *prefix_flags; };   // prefix_flags: [n_ent] words, set to 1 for every prefix entity row (okge_train_step)
 hipError_t launch_encode_queries(const float *E, const float *R, int d, int scorer, const PrefixDev &p, float *Q,
                                  int ldq, int Bpad, float *ent_rows, const int32_t *pos_col, int nnz, int32_t *tile_ptr,
-                                 int tiles, int tile_w, int cand_col0, hipStream_t st, const ClearSpec *clear = nullptr);
+                                 int tiles, int tile_w, int cand_col0, hipStream_t st, const ClearSpec *clear = nullptr,
+                                 v8bf *q_planes = nullptr, int KB = 0);       // q_planes: Q also as three bf16 planes (okge_tile_grad_split.h)
+// the same planes from a query block computed elsewhere: rows B .. Bpad - 1 are not read and come out as zero planes
+hipError_t launch_query_planes(const float *Q, int ldq, int B, int Bpad, int d, int KB, v8bf *q_planes, hipStream_t st);
 hipError_t launch_fold_queries(const float *R, int d, int scorer, const PrefixDev &p, const float *ent_rows, float *Q, int ldq,
                                int Bpad, hipStream_t st);
 hipError_t launch_slab_reduce(const float *slab, int nsplit, int64_t n, float *out, const double *loss_partials,

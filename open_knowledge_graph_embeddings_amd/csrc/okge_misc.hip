@@ -14,6 +14,7 @@
 #include "okge_tile.h"
 #include "okge_eval_device.h"
 #include "okge_prefix_device.h"
+#include "okge_tile_grad_split.h"
 
 namespace okge {
 
@@ -92,7 +93,8 @@ __global__ __launch_bounds__(128) void encode_queries_kernel(const float *__rest
                                                              float *__restrict__ ent_rows,
                                                              const int32_t *__restrict__ pos_col, int nnz,
                                                              int32_t *__restrict__ tile_ptr, int tiles, int tile_w,
-                                                             int cand_col0, int tp_wgs, const ClearSpec clr)
+                                                             int cand_col0, int tp_wgs, const ClearSpec clr,
+                                                             __bf16 *__restrict__ q_planes, int KB)
 {
     if ((int)blockIdx.x >= Bpad + tp_wgs) {
         // more extra workgroups (OKGE_TRAIN_CLEAR_GRADS): the gradient regions the step accumulates into without storing
@@ -125,6 +127,20 @@ __global__ __launch_bounds__(128) void encode_queries_kernel(const float *__rest
     }
     encode_query_row(E, R, d, scorer, p, b, Q ? Q + (size_t)b * ldq : nullptr,      // Q == nullptr: only the masked
                      ent_rows ? ent_rows + (size_t)b * ldq : nullptr, ldq);         // entity rows are wanted
+    if (Q && q_planes) {
+        // the row again as three bf16 planes for the tile kernel's gradient product, from the fp32 row this workgroup just stored.
+        // Other threads of the workgroup stored the elements a thread reads back here: the barrier (with its workgroup-scope fence)
+        // is what makes that read legal -- it must stay between the stores above and write_query_row_planes
+        __syncthreads();
+        write_query_row_planes(Q + (size_t)b * ldq, d, KB, b, q_planes);
+    }
+}
+
+// the query planes of a block that was folded elsewhere (okge_train_tiles)
+__global__ __launch_bounds__(128) void query_planes_kernel(const float *__restrict__ Q, int ldq, int B, int d, int KB, __bf16 *__restrict__ q_planes)
+{
+    const int b = blockIdx.x;
+    write_query_row_planes(b < B ? Q + (size_t)b * ldq : nullptr, d, KB, b, q_planes);
 }
 
 // Q[b] = fold(masked entity row b, dropout(R[rel_b])) from ALREADY MASKED entity rows (sharded path: the rows arrive
@@ -1226,7 +1242,7 @@ hipError_t launch_score_triples(const float *S, int64_t lds_, const float *Rr, i
 
 hipError_t launch_encode_queries(const float *E, const float *R, int d, int scorer, const PrefixDev &p, float *Q,
                                  int ldq, int Bpad, float *ent_rows, const int32_t *pos_col, int nnz, int32_t *tile_ptr,
-                                 int tiles, int tile_w, int cand_col0, hipStream_t st, const ClearSpec *clear)
+                                 int tiles, int tile_w, int cand_col0, hipStream_t st, const ClearSpec *clear, v8bf *q_planes, int KB)
 {
     const int extra = tile_ptr ? (tiles + 1 + 127) / 128 : 0;
     ClearSpec clr = {};
@@ -1240,7 +1256,13 @@ hipError_t launch_encode_queries(const float *E, const float *R, int d, int scor
     }
     if (Bpad + extra + clear_wgs <= 0) return hipSuccess;
     hipLaunchKernelGGL(encode_queries_kernel, dim3((unsigned)(Bpad + extra + clear_wgs)), dim3(128), 0, st, E, R, d, scorer, p, Q,
-                       ldq, Bpad, ent_rows, pos_col, nnz, tile_ptr, tiles, tile_w, cand_col0, extra, clr);
+                       ldq, Bpad, ent_rows, pos_col, nnz, tile_ptr, tiles, tile_w, cand_col0, extra, clr, reinterpret_cast<__bf16 *>(q_planes), KB);
+    return hipGetLastError();
+}
+
+hipError_t launch_query_planes(const float *Q, int ldq, int B, int Bpad, int d, int KB, v8bf *q_planes, hipStream_t st)
+{
+    hipLaunchKernelGGL(query_planes_kernel, dim3(Bpad), dim3(128), 0, st, Q, ldq, B, d, KB, reinterpret_cast<__bf16 *>(q_planes));
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 //   dC product    : dC[candidates of blk][all columns] += G^T . Q over the wave's 32 batch rows; the G blocks are the A
 //                   operands straight from the epilogue's registers (the MFMA result layout of X is the A layout of
 //                   the next product); both row groups accumulate into the SAME 13 x 4 accumulator registers.
+//                   KB = 13 (GSPLIT below): the same product on the bf16 matrix cores, from three bf16 planes per operand.
 // Why this cut (measured on the 32 x 32 predecessor, two 4-wave workgroups per CU, profiles/round2_*): fp32 MFMA shares
 // the SIMD's issue with VALU, so the loop costs MFMA + VALU cycles; per MFMA this cut stages half as many query rows,
 // passes half as many barriers and issues 40 % of the LDS operand reads, and the per-chunk address / label / loop VALU is
@@ -27,6 +28,7 @@
 #include "okge_dq_split.h"
 #include "okge_kernels.h"
 #include "okge_tile.h"
+#include "okge_tile_grad_split.h"
 
 namespace okge {
 
@@ -74,6 +76,14 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
 {
     constexpr bool REGC = KB <= 13;   // candidate operand in registers + two query chunk buffers: 4 KB more registers per lane
     static_assert(!SHORTK || (REGC && KB >= 3), "the short last round comes with the register-resident candidate operand");
+    // GSPLIT (okge_tile_grad_split.h): the gradient product on the bf16 matrix cores.  LDS then holds ONE fp32 query chunk (the
+    // tile's region, once every wave has taken its candidate operand from it) and ONE chunk of query planes, and a chunk has
+    // two barriers with each park running under the other phase:
+    //   barrier; score product of chunk i, planes of chunk i landing beside it (global -> LDS, no registers); epilogue;
+    //   barrier; gradient product of chunk i, fp32 chunk i+1 parked beside it.
+    constexpr bool GSPLIT = tile_grad_split(KB);
+    static_assert(!GSPLIT || REGC, "the plane buffer takes the place of the second fp32 chunk buffer");
+    using TGS = TileGradSplit<KB>;
 #ifdef OKGE_STAMPS
     unsigned long long wg_t0;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wg_t0)::"memory");
@@ -90,7 +100,10 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     const int d = a.d;
     float *Cs = reinterpret_cast<float *>(smem);              // [64][LDK]
     float *Qs = Cs + NT64 * LDK;                              // [64][LDK]
-    uint32_t *ybits3 = reinterpret_cast<uint32_t *>(Qs + BC64 * LDK);    // [3][2 halves][64 rows] label bits, three chunks in rotation
+    v8bf *Pl = reinterpret_cast<v8bf *>(Qs);                  // GSPLIT: [TGS::CHUNK_CELLS] query planes; its head is Qs in the write-back
+    static_assert(!GSPLIT || (size_t)TGS::CHUNK_CELLS * sizeof(v8bf) >= (size_t)BC64 * LDK * sizeof(float), "Qs fits the plane buffer");
+    uint32_t *ybits3 = GSPLIT ? reinterpret_cast<uint32_t *>(Pl + TGS::CHUNK_CELLS)
+                              : reinterpret_cast<uint32_t *>(Qs + BC64 * LDK);    // [3][2 halves][64 rows] label bits, three chunks in rotation
     double *red = reinterpret_cast<double *>(ybits3 + 3 * BC64 * 2);     // [8]
     uint8_t *keepb = reinterpret_cast<uint8_t *>(red + 8);               // [64][KEEP_LD] keep flags of the tile
     uint32_t *posc = reinterpret_cast<uint32_t *>(keepb + NT64 * KEEP_LD);   // [POS_CACHE] (row << 6 | col)
@@ -230,7 +243,12 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             breg[KB - 1][1] = Cs[(16 * blk + c) * LDK + 16 * (KB - 1) + 4 + s];
         }
         cm_done = NOIT;                 // (left as planes, above)
-        park_chunk(Qs);
+        if (GSPLIT) {                   // the first chunk goes where the tile is: once every wave has read its operand (and the planes)
+            __syncthreads();
+            park_chunk(Cs);
+        } else {
+            park_chunk(Qs);
+        }
         if (b_begin + BC64 < b_end) fetch_chunk(b_begin + BC64);
     }
 
@@ -244,7 +262,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     for (int b0 = b_begin; b0 < b_end; b0 += BC64, par = par == 2 ? 0 : par + 1) {
         uint32_t *ybits = ybits3 + par * (2 * BC64);
         // query chunk buffer of this chunk / of the next (REGC: the two LDS tiles alternate)
-        float *Qc = REGC && (((b0 - b_begin) >> 6) & 1) ? Cs : Qs;
+        float *Qc = GSPLIT || (REGC && (((b0 - b_begin) >> 6) & 1)) ? Cs : Qs;
         float *Qn = REGC ? (Qc == Qs ? Cs : Qs) : Qs;
         TL_STAMP_AT(48 + ((b0 - b_begin) >> 6));   // chunk entered (the previous chunk's closing barrier passed)
         if (!REGC) {
@@ -257,6 +275,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         TL_STAMP();   // [0] staged, before the barrier
         __syncthreads();   // REGC: this chunk's rows are parked (during the previous chunk) and the other buffer is free
         TL_STAMP();   // [1] start of score product
+        if (GSPLIT && !a.loss_only) TGS::copy_chunk(a.Qplanes + (size_t)(b0 >> 6) * TGS::CHUNK_CELLS, Pl, w, lane);
         {   // under the score product: the next chunk's label bits, the buffer after that cleared, one group of masked rows out
             const int pn = par == 2 ? 0 : par + 1, pc = pn == 2 ? 0 : pn + 1;
             if (tid < 2 * BC64) ybits3[pc * (2 * BC64) + tid] = 0u;
@@ -318,10 +337,12 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         const float *qb = Qc + (32 * h + 4 * s) * LDK;
         v4f pb[KQ > 0 ? KQ : 1];
         float pr[KR > 0 ? KR : 1];
+        if (!GSPLIT) {
 #pragma unroll
-        for (int kq = 0; kq < KQ; ++kq) pb[kq] = *reinterpret_cast<const v4f *>(qb + 64 * kq + 4 * c);
+            for (int kq = 0; kq < KQ; ++kq) pb[kq] = *reinterpret_cast<const v4f *>(qb + 64 * kq + 4 * c);
 #pragma unroll
-        for (int r = 0; r < KR; ++r) pr[r] = qb[64 * KQ + 16 * r + c];
+            for (int r = 0; r < KR; ++r) pr[r] = qb[64 * KQ + 16 * r + c];
+        }
 
         // ---- loss epilogue: G = dLoss/dX / normalizer, kept in registers --------------------------------------
         v4f g4[2];
@@ -368,7 +389,15 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             }
             if (MODE == MODE_TRAIN_BCE && LOGPROD) lsum += lin + __builtin_amdgcn_logf(prod) * TILE_LN2;
         }
-        if (REGC && b0 + BC64 < b_end) {
+        if (GSPLIT) {
+            // this wave's pieces of the planes have landed; behind the barrier everybody's have, and the fp32 chunk has no reader left
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (b0 + BC64 < b_end) {
+                park_chunk(Cs);
+                if (b0 + 2 * BC64 < b_end) fetch_chunk(b0 + 2 * BC64);
+            }
+        } else if (REGC && b0 + BC64 < b_end) {
             // park the next chunk in the other buffer (its last readers finished before this chunk's barrier) and request the
             // chunk after it: by now the waves of a SIMD are a phase apart, so this runs beside the other wave's MFMAs
             park_chunk(Qn);
@@ -383,7 +412,12 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
                 *reinterpret_cast<v4f *>(gdst + 16) = g4[1];
             }
             // ---- dC += G^T . Q over this wave's 32 batch rows: A operands straight from g4 ------------------------
+            // GSPLIT: one K = 32 step of the bf16 MFMA per plane product and column block, the lane's 8 G values split here
             // sub-step u = 4 rg + t, slot s  <->  batch row 32h + 16rg + 4s + t ; A = G[row][n = 16blk + c] = g4[rg][t]
+            if constexpr (GSPLIT) {
+                v4f none[1];
+                TGS::template product<true>(dc, none, TGS::a_planes(g4), Pl, h, lane);
+            } else
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const float av = g4[u >> 2][u & 3];
@@ -479,7 +513,8 @@ template <int KB>
 static size_t shmem64()
 {
     using Cfg = TileCfg<KB>;
-    return (size_t)(NT64 + BC64) * Cfg::LDK * sizeof(float) + 3 * BC64 * 2 * sizeof(uint32_t) + 8 * sizeof(double) +
+    const size_t chunk = tile_grad_split(KB) ? (size_t)TileGradSplit<KB>::CHUNK_CELLS * sizeof(v8bf) : (size_t)BC64 * Cfg::LDK * sizeof(float);
+    return (size_t)NT64 * Cfg::LDK * sizeof(float) + chunk + 3 * BC64 * 2 * sizeof(uint32_t) + 8 * sizeof(double) +
            NT64 * Cfg::KEEP_LD + POS_CACHE * sizeof(uint32_t);
 }
 

@@ -8,6 +8,12 @@
 //      candidate row and G^T split here, the retired staging kept below as OldStage / park_split_all -- and as it is NOW --
 //      candidate cells copied, G^T split on four waves (DqSplit::park).  The matrix-core floor is 78 MFMAs per SIMD x 16
 //      cycles = 1248.
+//  (c) The train tile's gradient phase dC += G^T . Q per 64-row chunk at KB = 13 (csrc/okge_tile_grad_split.h), 256 workgroups of 8 waves, one
+//      barrier per chunk: the fp32 loop fused_tile64_kernel runs today (104 v_mfma_f32_16x16x4_f32 per wave, operands read from
+//      the fp32 chunk in LDS) against the three-plane form (one split3 of the lane's 8 G values, 78 v_mfma_f32_16x16x32_bf16, B
+//      cells read from the plane image) with the corrections folded per chunk or in an accumulator of their own, each without
+//      and with the next chunk's planes copied global -> LDS beside it.  Floors per SIMD (two waves): 2 x 3328 cycles fp32,
+//      2 x 1248 bf16; the LDS reads of the bf16 form are 8 waves x 39 KiB per chunk.
 // Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -o mfma_bf16_split.bin mfma_bf16_split.hip
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -15,6 +21,7 @@
 #include <cstring>
 #include <vector>
 #include "../../open_knowledge_graph_embeddings_amd/csrc/okge_dq_split.h"
+#include "../../open_knowledge_graph_embeddings_amd/csrc/okge_tile_grad_split.h"
 using namespace okge;
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
@@ -177,6 +184,119 @@ static int run_loop(const char *name, const float *src, float *out, unsigned lon
     return 0;
 }
 
+// ---- (c) ------------------------------------------------------------------------------------------------------------
+// MODE 0: the fp32 loop (a frozen copy, see below); 1 / 2: three planes, corrections folded / in their own accumulator; 3 / 4: the same with the next
+// chunk's planes copied beside the product.  Every mode declares the same LDS (two plane chunks), so one workgroup per CU.
+template <int MODE>
+__global__ __launch_bounds__(512, 2) void grad_phase_kernel(const float *src, const v8bf *planes, float *out, unsigned long long *cyc, int iters)
+{
+    constexpr int KB = 13, KQ = KB / 4, KR = KB % 4, LDK = lds_ld(16 * KB);
+    constexpr bool FOLD = MODE == 1 || MODE == 3, COPY = MODE >= 3;
+    using T = TileGradSplit<KB>;
+    static_assert(64 * LDK * 4 <= T::CHUNK_CELLS * 16, "the fp32 chunk fits the first plane buffer");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    v8bf *lds = reinterpret_cast<v8bf *>(smem);           // two plane chunks; the fp32 loop reads the first as [64][LDK] floats
+    const float *Qs = reinterpret_cast<const float *>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, s = lane >> 4, h = w >> 2;
+    // any finite numbers will do: floats of magnitude < 1 for the fp32 loop, bf16 cells for the plane loops
+    if (MODE == 0) {
+        for (int i = tid; i < 64 * LDK; i += 512) reinterpret_cast<float *>(smem)[i] = src[i & 16383];
+    } else {
+        for (int i = tid; i < 2 * T::CHUNK_CELLS; i += 512) {
+            float x[8];
+            for (int k = 0; k < 8; ++k) x[k] = src[(8 * i + k) & 16383];
+            lds[i] = split3(x).hi;
+        }
+    }
+    v4f g4[2];
+    for (int rg = 0; rg < 2; ++rg) g4[rg] = *reinterpret_cast<const v4f *>(src + 8 * tid + 4 * rg) * 1e-3f;
+    v4f dc[KB], corr[FOLD || MODE == 0 ? 1 : KB];
+    for (int kb = 0; kb < KB; ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
+    for (auto &v : corr) v = (v4f){0.f, 0.f, 0.f, 0.f};
+    __syncthreads();
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int it = 0; it < iters; ++it) {
+        __syncthreads();
+        // G changes every chunk, as in the kernel: the split cannot be hoisted out of the loop
+        for (int rg = 0; rg < 2; ++rg) g4[rg] += (v4f){1e-6f, 2e-6f, 3e-6f, 4e-6f};
+        if constexpr (MODE == 0) {
+            const float *qb = Qs + (32 * h + 4 * s) * LDK;
+            v4f pb[KQ];
+            float pr[KR];
+#pragma unroll
+            for (int kq = 0; kq < KQ; ++kq) pb[kq] = *reinterpret_cast<const v4f *>(qb + 64 * kq + 4 * c);
+#pragma unroll
+            for (int r = 0; r < KR; ++r) pr[r] = qb[64 * KQ + 16 * r + c];
+#pragma unroll
+            // a FROZEN COPY of the fp32 loop fused_tile64_kernel ran at KB = 13 before this form (okge_train64.hip, "dC += G^T . Q",
+            // as it still stands there for the other instances): the baseline of the comparison, not shared code -- an edit of
+            // the kernel's fp32 loop does not reach it
+            for (int u = 0; u < 8; ++u) {
+                const float av = g4[u >> 2][u & 3];
+                v4f nb[KQ];
+                float nr[KR];
+                if (u + 1 < 8) {
+                    const float *brow = qb + (16 * ((u + 1) >> 2) + ((u + 1) & 3)) * LDK;
+#pragma unroll
+                    for (int kq = 0; kq < KQ; ++kq) nb[kq] = *reinterpret_cast<const v4f *>(brow + 64 * kq + 4 * c);
+#pragma unroll
+                    for (int r = 0; r < KR; ++r) nr[r] = brow[64 * KQ + 16 * r + c];
+                }
+#pragma unroll
+                for (int kq = 0; kq < KQ; ++kq)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dc[4 * kq + e] = mfma16(av, pb[kq][e], dc[4 * kq + e]);
+#pragma unroll
+                for (int r = 0; r < KR; ++r) dc[4 * KQ + r] = mfma16(av, pr[r], dc[4 * KQ + r]);
+                if (u + 1 < 8) {
+#pragma unroll
+                    for (int kq = 0; kq < KQ; ++kq) pb[kq] = nb[kq];
+#pragma unroll
+                    for (int r = 0; r < KR; ++r) pr[r] = nr[r];
+                    __builtin_amdgcn_sched_group_barrier(0x100, KQ + KR, 1);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, KB, 1);
+            }
+        } else {
+            const int buf = COPY ? it & 1 : 0;
+            if (COPY) T::copy_chunk(planes + (size_t)(it & 7) * T::CHUNK_CELLS, lds + (buf ^ 1) * T::CHUNK_CELLS, w, lane);
+            const Planes a = T::a_planes(g4);
+            T::template product<FOLD>(dc, corr, a, lds + buf * T::CHUNK_CELLS, h, lane);
+        }
+    }
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    float sum = 0.f;
+    for (int kb = 0; kb < KB; ++kb) for (int i = 0; i < 4; ++i) sum += dc[kb][i];
+    for (auto &v : corr) for (int i = 0; i < 4; ++i) sum += v[i];
+    out[blockIdx.x * 512 + tid] = sum;
+    if (lane == 0) cyc[blockIdx.x * 8 + w] = t1 - t0;
+}
+
+template <int MODE>
+static int run_phase(const char *name, const float *src, const v8bf *planes, float *out, unsigned long long *cyc, int blocks, int iters)
+{
+    auto k = grad_phase_kernel<MODE>;
+    const size_t shmem = (size_t)2 * TileGradSplit<13>::CHUNK_CELLS * 16;
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(512), shmem, 0, src, planes, out, cyc, iters);   // warm-up
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(e0));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(512), shmem, 0, src, planes, out, cyc, iters);
+    CK(hipEventRecord(e1));
+    CK(hipDeviceSynchronize());
+    float ms = 0.f;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    std::vector<unsigned long long> hc(blocks * 8);
+    CK(hipMemcpy(hc.data(), cyc, hc.size() * 8, hipMemcpyDeviceToHost));
+    unsigned long long mx = 0; double mean = 0;
+    for (auto v : hc) { mx = v > mx ? v : mx; mean += (double)v / hc.size(); }
+    printf("%-58s %8.3f ms  %7.1f ns/chunk   s_memtime ticks/chunk: mean %.1f max %.1f\n", name, ms, ms * 1e6 / iters, mean / iters,
+           (double)mx / iters);
+    return 0;
+}
+
 int main()
 {
     // (a)
@@ -232,5 +352,20 @@ int main()
     if (run_loop<2>("before: product + split of C and G^T + park", src, out, cyc, blocks, iters)) return 1;
     if (run_loop<3>("now: product + C cells copied, G^T split by 4 waves", src, out, cyc, blocks, iters)) return 1;
     if (run_loop<4>("not kept: C cells copied, G^T split by wave 6", src, out, cyc, blocks, iters)) return 1;
+
+    // (c)
+    using T = TileGradSplit<13>;
+    std::vector<v8bf> hp((size_t)8 * T::CHUNK_CELLS);
+    for (size_t i = 0; i < hp.size(); ++i)
+        for (int k = 0; k < 8; ++k) hp[i][k] = (__bf16)hs[(8 * i + k) & 16383];
+    v8bf *planes;
+    CK(hipMalloc(&planes, hp.size() * sizeof(v8bf)));
+    CK(hipMemcpy(planes, hp.data(), hp.size() * sizeof(v8bf), hipMemcpyHostToDevice));
+    printf("== (c) KB = 13 gradient phase of the train tile, %d workgroups x 512 threads, %d chunks each, one barrier per chunk\n", blocks, iters);
+    if (run_phase<0>("today: fp32, 104 MFMAs per wave", src, planes, out, cyc, blocks, iters)) return 1;
+    if (run_phase<1>("three planes, corrections folded per chunk", src, planes, out, cyc, blocks, iters)) return 1;
+    if (run_phase<2>("three planes, corrections in their own accumulator", src, planes, out, cyc, blocks, iters)) return 1;
+    if (run_phase<3>("folded + next chunk's planes copied beside it", src, planes, out, cyc, blocks, iters)) return 1;
+    if (run_phase<4>("own accumulator + next chunk's planes copied beside it", src, planes, out, cyc, blocks, iters)) return 1;
     return 0;
 }
