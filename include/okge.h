@@ -731,6 +731,49 @@ int okge_rank_counts(const float *scores, int64_t ld_scores, int32_t B, int32_t 
                      const int64_t *filt_ptr, const int32_t *filt_col, const int64_t *row_ptr,
                      const float *true_scores, int64_t *counts, void *stream);
 
+/* ---- top-k link prediction ---------------------------------------------------------------------------------
+ * Which entities does the model predict for (s, p, ?) / (?, p, o): per row the k best candidates of
+ * sp_prefix_score / po_prefix_score (model.py:52-74) under the filter the evaluation applies (dataset.py:423-453), without
+ * the (B, N) score block.  The score sweep runs per candidate range in a top-k mode and leaves, per 64-candidate tile and row,
+ * the tile's best k records (score, column); a merge kernel folds them into the running (B, k) list, which is the output.
+ *
+ * ONE total order, used by the sweep, the merge, across shards and by the tests:
+ *   - candidate a precedes b if score(a) > score(b);
+ *   - equal scores, by float comparison (so -0.0 == +0.0): the smaller candidate COLUMN first (column = position in the
+ *     call's full candidate list; sharded: shard->cand_col0 + local position);
+ *   - a NaN score orders as -inf: after every number, before the padding (the record keeps the NaN);
+ *   - filtered columns are excluded outright (not set to -1e8);
+ *   - a row with fewer than k eligible candidates is padded at the tail with score = -inf, col = -1, id = -1.
+ * The order is total and the merge associative, so the result is bit-identical however the candidates are cut into tiles,
+ * ranges or shards; scores carry the bits okge_score_prefixes / okge_score_queries write.
+ *
+ *   k            1 .. 64 (the reference's widest metric is Hits@50); k < 1: OKGE_ERR_INVALID, k > 64: OKGE_ERR_UNSUPPORTED
+ *   filter       optional CSR (NULL, NULL, 0): filt_col[filt_ptr[b] .. filt_ptr[b + 1]) = the columns row b excludes.  Each
+ *                row's columns must be ASCENDING (okge_collate_batch emits them so).  Sharded: columns are global and the
+ *                arrays identical on every rank.
+ *   range_n      candidates per sweep range, rounded down to a multiple of 64 (at least 64); 0 = the library's default: the
+ *                range's records -- tiles_per_range x okge_query_rows(B) x k x 8 bytes, plus above slot size 256 the range's
+ *                score block, okge_query_rows(B) x range_n x 4 bytes -- stay under 256 MiB.
+ *   workspace    okge_topk_workspace_bytes: the query block + one range's records (+ score block); the running list is the output.
+ * Eval mode only: any dropout p > 0 or cand->table answers OKGE_ERR_UNSUPPORTED, as okge_evaluate_fused does; so do slot sizes
+ * above 512 and the data-bias scorers.  Bad ids raise the device id guard (okge_id_errors).
+ *
+ * okge_topk_prefixes  single device: folds the queries as okge_score_prefixes does, then sweeps.  out_scores / out_cols /
+ *                     out_ids are [B][k]; out_ids = cand->ids[col], or cand->first_id + col for a range.
+ * okge_topk_queries   takes the folded query block like okge_score_queries / okge_row_logsumexp and sweeps the LOCAL
+ *                     candidates; columns are global.  Each rank all-gathers its (B, k) lists and calls
+ * okge_topk_merge     merges [n_lists][B][k] lists into one [B][k] list (any order of the lists gives the same result). */
+size_t okge_topk_workspace_bytes(int32_t B, int32_t N, int32_t d, int32_t k, int32_t range_n);
+int okge_topk_prefixes(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, int32_t k,
+                       const int64_t *filt_ptr, const int32_t *filt_col, int64_t n_filter, int32_t range_n, float *out_scores,
+                       int32_t *out_cols, int32_t *out_ids, void *workspace, size_t workspace_bytes, void *stream);
+int okge_topk_queries(const okge_tables *t, const okge_shard *shard, const float *Q, int64_t ldq, int32_t B,
+                      const okge_candidates *local_cand, int32_t k, const int64_t *filt_ptr, const int32_t *filt_col,
+                      int64_t n_filter, int32_t range_n, float *out_scores, int32_t *out_cols, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int okge_topk_merge(const float *scores, const int32_t *cols, int32_t n_lists, int32_t B, int32_t k, float *out_scores,
+                    int32_t *out_cols, void *stream);
+
 /* ---- id safety ----------------------------------------------------------------------------------------
  * Ids live in device memory; the kernels check every row index they form from one against its table, substitute row 0
  * (the padding row) for an index outside it and count the event in a device word.  okge_id_errors copies the count to

@@ -14,7 +14,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_i
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libokge_hip.so")
-SOURCES = ["okge_api.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_misc.hip", "okge_bias.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
+SOURCES = ["okge_api.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_misc.hip", "okge_topk.hip", "okge_bias.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
 # every header a source may include: all of csrc/*.h (listed by the directory, so a new header cannot be forgotten) + the ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "okge.h")]
 
@@ -50,6 +50,7 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_tucker3_workspace_bytes", "okge_tucker3_fold", "okge_tucker3_backward", "okge_tucker3_score_triples", "okge_tucker3_apply", "okge_tucker3_outer",
            "okge_collate_batch", "okge_collate_batches", "okge_dataset_open", "okge_dataset_sizes",
            "okge_dataset_copy", "okge_dataset_close", "okge_encode_rows", "okge_scale_inplace", "okge_rescale_gradients", "okge_adagrad_step", "okge_adagrad_step2", "okge_id_errors", "okge_clip_grad_norm", "okge_merge_logsumexp", "okge_filtered_ranks", "okge_timing_enable",
+           "okge_topk_workspace_bytes", "okge_topk_prefixes", "okge_topk_queries", "okge_topk_merge",
            "okge_timing_reset", "okge_timing_collect"]
 
 
@@ -378,6 +379,16 @@ def lib():
     L.okge_clip_grad_norm.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_size_t, c_void_p]
     L.okge_merge_logsumexp.restype = c_int32
     L.okge_merge_logsumexp.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p]
+    L.okge_topk_workspace_bytes.restype = c_size_t
+    L.okge_topk_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32]
+    L.okge_topk_prefixes.restype = c_int32
+    L.okge_topk_prefixes.argtypes = [POINTER(Tables), POINTER(PrefixBatch), POINTER(Candidates), c_int32, c_void_p, c_void_p,
+                                     c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.okge_topk_queries.restype = c_int32
+    L.okge_topk_queries.argtypes = [POINTER(Tables), POINTER(Shard), c_void_p, c_int64, c_int32, POINTER(Candidates), c_int32,
+                                    c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.okge_topk_merge.restype = c_int32
+    L.okge_topk_merge.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
     L.okge_filtered_ranks.restype = c_int32
     L.okge_filtered_ranks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]

@@ -366,6 +366,7 @@ FusedArgs tile_window(const FusedArgs &base, const Geometry &g, int t0)
     if (a.X) a.X += (size_t)t0 * NT;
     if (a.stats) a.stats += (size_t)t0 * g.Bpad * 2;
     if (a.rk_slab) a.rk_slab += (size_t)t0 * a.rk_ngroups;
+    if (a.tk_part) a.tk_part += (size_t)t0 * g.Bpad * a.tk_k;
     return a;
 }
 
@@ -432,6 +433,100 @@ int lse_pass(const Geometry &g, const FusedArgs &base, char *ws, float *row_lse,
                               r == 0 ? count_pos_row : nullptr, count_nnz, r == 0 ? count_ysum : nullptr);   // + the rows' label mass
         if (e != hipSuccess) return fail_hip(e, "kl_row_lse");
     }
+    return OKGE_OK;
+}
+
+// ---- top-k link prediction -------------------------------------------------------------------------------------------------
+// The sweep runs per candidate range; a range leaves [tiles of the range][Bpad][k] records and one merge launch folds them into
+// the running (B, k) list, which IS the caller's output.  Default range: the records (plus, above slot size 256, the range's
+// score block) stay under TOPK_PARTIAL_CAP; whole rounds of one tile per CU when a range is that long, as in training.
+constexpr size_t TOPK_PARTIAL_CAP = (size_t)256 << 20;
+struct TopkGeometry { size_t off_part, off_X, total; };
+
+bool make_topk_geometry(int B, int N, int d, int k, int range_n, Geometry &g, TopkGeometry &tg)
+{
+    if (k < 1 || k > 64 || range_n < 0 || d > 512 || !make_geometry(B, N, d, g)) return false;
+    const bool wide = g.KB > 16;
+    const size_t per_tile = (size_t)g.Bpad * ((size_t)k * sizeof(TopkRec) + (wide ? NT * sizeof(float) : 0));
+    int64_t rt;
+    if (range_n > 0) {
+        rt = std::max(1, range_n / NT);
+    } else {
+        rt = std::max<int64_t>(1, (int64_t)(TOPK_PARTIAL_CAP / per_tile));
+        const int cus = cu_count();
+        if (!wide && rt >= cus) rt = rt / cus * cus;
+    }
+    g.range_tiles = (int)std::min<int64_t>(rt, g.tiles);
+    g.n_ranges = (g.tiles + g.range_tiles - 1) / g.range_tiles;
+    g.range_n = g.range_tiles * NT;
+    g.b_split = 1;
+    g.b_per_block = g.Bpad;
+    size_t off = g.score_bytes;                                  // the query block (okge_topk_prefixes)
+    tg.off_part = off; off += align_up((size_t)g.range_tiles * g.Bpad * k * sizeof(TopkRec), 256);
+    tg.off_X = off;    off += wide ? align_up((size_t)g.Bpad * g.range_n * sizeof(float), 256) : 0;
+    tg.total = off;
+    return true;
+}
+
+int topk_pass(const Geometry &g, const TopkGeometry &tg, const FusedArgs &base, char *ws, int k, const int64_t *filt_ptr,
+              const int32_t *filt_col, float *out_scores, int32_t *out_cols, int32_t *out_ids, hipStream_t st)
+{
+    FusedArgs b = base;
+    TopkRec *part = reinterpret_cast<TopkRec *>(ws + tg.off_part);
+    b.b_per_block = g.Bpad;
+    b.tk_k = k;
+    b.tk_filt_ptr = filt_ptr;
+    b.tk_filt_col = filt_col;
+    for (int r = 0; r < g.n_ranges; ++r) {
+        int tiles_r;
+        FusedArgs s = range_args(b, g, r, tiles_r);
+        hipError_t e;
+        if (g.KB <= 16) {
+            s.tk_part = part;
+            // (the name tells whether the closing round of this range was launched apart: launch_score_sweep asks the same question)
+            ScopedTimer tm(tail_split(tiles_r, g.Bpad, cu_count()).split > 1 ? "fused_tile_topk_tail" : "fused_tile_topk", st);
+            e = launch_score_sweep(g, s, tiles_r, st, MODE_TOPK);
+            if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<topk>");
+        } else {
+            s.X = reinterpret_cast<float *>(ws + tg.off_X);
+            s.ldx = g.range_n;
+            {
+                ScopedTimer tm("fused_tile_score", st);
+                e = launch_score_sweep(g, s, tiles_r, st, MODE_SCORE);
+                if (e != hipSuccess) return fail_hip(e, "fused_tile64k_kernel<score>");
+            }
+            ScopedTimer tm("topk_cut", st);
+            e = launch_topk_cut(s.X, s.ldx, g.B, g.Bpad, s.N, s.cand_col0, filt_ptr, filt_col, k, part, st);
+            if (e != hipSuccess) return fail_hip(e, "topk_cut");
+        }
+        ScopedTimer tm("topk_merge", st);
+        TopkMergeArgs m;
+        std::memset(&m, 0, sizeof(m));
+        m.sc = &part->score; m.cl = &part->col; m.elem_stride = 2;
+        m.L = tiles_r; m.rows_ld = g.Bpad; m.kq = k; m.B = g.B; m.k = k;
+        m.first = r == 0;
+        m.out_sc = out_scores; m.out_cl = out_cols;
+        if (r == g.n_ranges - 1 && out_ids) { m.out_id = out_ids; m.cand_ids = base.cand_ids; m.cand_first = base.cand_first; }
+        e = launch_topk_merge(m, st);
+        if (e != hipSuccess) return fail_hip(e, "topk_merge");
+    }
+    return OKGE_OK;
+}
+
+bool any_dropout(const okge_prefix_batch *b, const okge_candidates *c)
+{
+    return c->drop.p > 0.f || (b && (b->drop_po_ent.p > 0.f || b->drop_po_rel.p > 0.f || b->drop_sp_ent.p > 0.f || b->drop_sp_rel.p > 0.f));
+}
+
+int check_topk(int32_t k, const okge_prefix_batch *b, const okge_candidates *c, const int64_t *filt_ptr, const int32_t *filt_col,
+               int64_t n_filter, int32_t range_n, const float *out_scores, const int32_t *out_cols)
+{
+    if (k < 1) return fail(OKGE_ERR_INVALID, "k must be at least 1");
+    if (k > 64) return fail(OKGE_ERR_UNSUPPORTED, "top-k keeps at most 64 candidates per row");
+    if (c->table) return fail(OKGE_ERR_UNSUPPORTED, "top-k takes its candidates from the entity table");
+    if (any_dropout(b, c)) return fail(OKGE_ERR_UNSUPPORTED, "top-k is an eval-mode call: no dropout");
+    if (range_n < 0 || n_filter < 0 || (n_filter > 0 && (!filt_ptr || !filt_col))) return fail(OKGE_ERR_INVALID, "bad filter / range");
+    if (!out_scores || !out_cols) return fail(OKGE_ERR_INVALID, "null output");
     return OKGE_OK;
 }
 
@@ -870,6 +965,78 @@ int okge_row_logsumexp(const okge_tables *t, const okge_shard *sh, const float *
     a.Q = Q;
     a.cand_col0 = sh->cand_col0;
     return lse_pass(g, a, ws, row_lse, st);
+}
+
+size_t okge_topk_workspace_bytes(int32_t B, int32_t N, int32_t d, int32_t k, int32_t range_n)
+{
+    Geometry g;
+    TopkGeometry tg;
+    return make_topk_geometry(B, N, d, k, range_n, g, tg) ? tg.total : 0;
+}
+
+int okge_topk_prefixes(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, int32_t k,
+                       const int64_t *filt_ptr, const int32_t *filt_col, int64_t n_filter, int32_t range_n, float *out_scores,
+                       int32_t *out_cols, int32_t *out_ids, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_common(t, batch, cand)) return rc;
+    if (int rc = refuse_bias(t->scorer, "okge_topk_prefixes", "predictions are built for the ComplEx and DistMult scorers")) return rc;
+    if (int rc = check_topk(k, batch, cand, filt_ptr, filt_col, n_filter, range_n, out_scores, out_cols)) return rc;
+    if (!out_ids) return fail(OKGE_ERR_INVALID, "null output");
+    Geometry g;
+    TopkGeometry tg;
+    if (!make_topk_geometry(batch->n_po + batch->n_sp, cand->n, t->d, k, range_n, g, tg)) return fail(OKGE_ERR_INVALID, "bad shape");
+    if (!workspace || workspace_bytes < tg.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    const PrefixDev p = to_dev(*batch, t);
+    {
+        ScopedTimer tm("encode_queries", st);
+        hipError_t e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + g.off_Q),
+                                             g.ldq, g.Bpad, nullptr, nullptr, 0, nullptr, g.tiles, NT, 0, st);
+        if (e != hipSuccess) return fail_hip(e, "encode_queries");
+    }
+    FusedArgs a;
+    fill_fused_common(a, g, t, cand, ws);
+    return topk_pass(g, tg, a, ws, k, n_filter > 0 ? filt_ptr : nullptr, filt_col, out_scores, out_cols, out_ids, st);
+}
+
+int okge_topk_queries(const okge_tables *t, const okge_shard *sh, const float *Q, int64_t ldq, int32_t B,
+                      const okge_candidates *cand, int32_t k, const int64_t *filt_ptr, const int32_t *filt_col, int64_t n_filter,
+                      int32_t range_n, float *out_scores, int32_t *out_cols, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (cand && cand->table) return fail(OKGE_ERR_UNSUPPORTED, "top-k takes its candidates from the entity table");
+    if (int rc = check_query_call(t, sh, Q, ldq, B, cand)) return rc;
+    if (int rc = check_topk(k, nullptr, cand, filt_ptr, filt_col, n_filter, range_n, out_scores, out_cols)) return rc;
+    Geometry g;
+    TopkGeometry tg;
+    if (!make_topk_geometry(B, cand->n, t->d, k, range_n, g, tg)) return fail(OKGE_ERR_INVALID, "bad shape");
+    if (!workspace || workspace_bytes < tg.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    FusedArgs a;
+    fill_fused_common(a, g, t, cand, ws);
+    a.Q = Q;
+    a.cand_col0 = sh->cand_col0;
+    return topk_pass(g, tg, a, ws, k, n_filter > 0 ? filt_ptr : nullptr, filt_col, out_scores, out_cols, nullptr, st);
+}
+
+int okge_topk_merge(const float *scores, const int32_t *cols, int32_t n_lists, int32_t B, int32_t k, float *out_scores,
+                    int32_t *out_cols, void *stream)
+{
+    if (!scores || !cols || !out_scores || !out_cols || n_lists <= 0 || B <= 0) return fail(OKGE_ERR_INVALID, "bad lists");
+    if (k < 1) return fail(OKGE_ERR_INVALID, "k must be at least 1");
+    if (k > 64) return fail(OKGE_ERR_UNSUPPORTED, "top-k keeps at most 64 candidates per row");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    TopkMergeArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.sc = scores; m.cl = cols; m.elem_stride = 1;
+    m.L = n_lists; m.rows_ld = B; m.kq = k; m.B = B; m.k = k;
+    m.first = 1;
+    m.out_sc = out_scores; m.out_cl = out_cols;
+    ScopedTimer tm("topk_merge", st);
+    hipError_t e = launch_topk_merge(m, st);
+    if (e != hipSuccess) return fail_hip(e, "topk_merge");
+    return OKGE_OK;
 }
 
 int okge_prefix_backward(const okge_tables *t, const okge_shard *sh, const okge_prefix_batch *batch, const float *dQ,

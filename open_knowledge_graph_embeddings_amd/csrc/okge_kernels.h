@@ -5,6 +5,7 @@
 #include <atomic>
 #include <stdint.h>
 #include "okge_device.h"
+#include "okge_topk.h"
 #include "../../include/okge.h"
 
 namespace okge {
@@ -51,7 +52,7 @@ constexpr int plane_cells_per_tile(int D16) { return 3 * NT * D16 / 8; }
 constexpr bool tile_grad_split(int KB) { return KB == 13; }
 constexpr int POS_CACHE = 512;     // positives of one candidate tile cached in LDS (more spill to global reads)
 
-enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4 };
+enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4, MODE_TOPK = 5 };
 enum { LOSS_BCE = 0, LOSS_KL = 1 };
 enum { SC_COMPLEX = 0, SC_DISTMULT = 1, SC_BIAS_RELATION = 2, SC_BIAS_ENTITY = 3 };   // = enum okge_scorer
 // the data-bias scorers (model.py:281-350): the folded query row is a copy of ONE masked row
@@ -90,6 +91,11 @@ struct FusedArgs {
     int32_t        sk_tiles;   // fused_tile64k_kernel: > 0 = stream-K launch over this many candidate tiles (grid = workgroups)
     v8bf          *Cplanes;    // [tiles][plane_cells_per_tile]  slot sizes up to 208: the masked candidate rows as three bf16 planes, in place of Cm
     const v8bf    *Qplanes;    // [Bpad / 64][chunk image]  tile_grad_split(KB): Q as three bf16 planes (okge_tile_grad_split.h)
+    // top-k mode (okge_topk.h): per (tile, row) the tile's best tk_k eligible candidates as (score, global column) records
+    TopkRec       *tk_part;    // [tiles][Bpad][tk_k]
+    const int64_t *tk_filt_ptr;   // [B + 1] CSR of each row's filtered GLOBAL columns (ascending), or nullptr
+    const int32_t *tk_filt_col;
+    int32_t        tk_k;
 };
 
 struct DqArgs {
@@ -303,5 +309,22 @@ hipError_t launch_ranks(const float *scores, int64_t ld, int B, int N, const int
                         const int32_t *filt_col, const int64_t *row_ptr, const int64_t *grp_ptr, const int32_t *ids,
                         int64_t *ranks, int col0, const float *true_in, float *true_out, int64_t *counts_out,
                         hipStream_t st);
+// top-k link prediction (okge_topk.hip).  Cut: the per-tile records of fused_tile_kernel<KB, MODE_TOPK> from a materialised
+// score block X[B][ldx] of N local candidates (slot sizes above 256).  Merge: per row, L lists of kq records + the running
+// (B, k) list -> the running list, in the total order of okge_topk.h.
+hipError_t launch_topk_cut(const float *X, int64_t ldx, int B, int Bpad, int N, int cand_col0, const int64_t *filt_ptr,
+                           const int32_t *filt_col, int kq, TopkRec *part, hipStream_t st);
+struct TopkMergeArgs {
+    const float   *sc;          // record (list l, row b, slot s) is element ((l * rows_ld + b) * kq + s) * elem_stride of sc / cl
+    const int32_t *cl;
+    int32_t        elem_stride, L, rows_ld, kq, B, k;
+    int32_t        first;       // 1: the running list starts empty; 0: it is read from out_*
+    float         *out_sc;      // [B][k]
+    int32_t       *out_cl;
+    int32_t       *out_id;      // optional: entity id of every column (cand_ids[col] or cand_first + col; -1 for padding)
+    const int32_t *cand_ids;
+    int32_t        cand_first;
+};
+hipError_t launch_topk_merge(const TopkMergeArgs &a, hipStream_t st);
 
 }  // namespace okge

@@ -1,12 +1,14 @@
 // Prefix-scoring kernels for gfx950 (MI355X), 64x64 cut.
 //
-//   fused_tile_kernel<KB, MODE>   MODE_SCORE | MODE_STATS | MODE_COUNT
+//   fused_tile_kernel<KB, MODE>   MODE_SCORE | MODE_STATS | MODE_COUNT | MODE_TOPK
 //     One workgroup owns a tile of NT=64 candidate entities (gathered + dropped-out once into LDS) and sweeps the
 //     batch's folded query rows in chunks of BC=64:  X = Q_chunk . C_tile^T  (v_mfma_f32_16x16x4_f32, exact fp32).
 //     MODE_SCORE writes X (evaluation / *_prefix_score: openkge/model.py:52-74,198-229,268-274);
 //     MODE_STATS writes per-row (max, sum-exp) partials for the KL loss' log_softmax (openkge/trainer.py:99-100).
 //     MODE_COUNT (fused evaluation) compares X in registers with each row's true answer scores and adds the tile's
 //     {#greater, #equal} to per-group counters: the rank rule of dataset.py:436-446 without the (B, N) score block.
+//     MODE_TOPK (link prediction) stages X as MODE_SCORE does -- the same bits -- and leaves per (tile, row) the tile's best k
+//     unfiltered candidates as (score, column) records (okge_topk.h); topk_merge_kernel (okge_topk.hip) folds them per row.
 //     The training step (score -> loss -> dCand) is fused_tile64_kernel (okge_train64.hip) up to slot size 256 and
 //     fused_tile64k_kernel (okge_train64k.hip) above.
 //
@@ -223,6 +225,11 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
                 for (int k = tid; k < (int)(rk_c1 - rk_c0); k += FUSED_THREADS) reinterpret_cast<uint32_t *>(Xs)[k] = 0u;
         }
         __syncthreads();
+        uint64_t tk_mask = 0;                                 // MODE_TOPK: the filtered ones of this tile's 64 columns, for row tid / 8
+        if (MODE == MODE_TOPK) {
+            const int b = b0 + (tid >> 3);
+            if (a.tk_filt_ptr && b < b_end) tk_mask = topk_filter_mask(a.tk_filt_ptr, a.tk_filt_col, b, a.cand_col0 + n0);
+        }
 
         // ---- phase B: X = Q_chunk . C^T ; wave w owns rows 16wq..16wq+15 x candidate blocks 2nh, 2nh+1 ----------
         v4f x[NBW];
@@ -360,6 +367,20 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
                 if (nh == 1) count_pass(true);
                 __syncthreads();
             }
+        } else if (MODE == MODE_TOPK) {
+            // the tile's best tk_k eligible candidates of every row of the chunk, selected from the staged block
+#pragma unroll
+            for (int nb = 0; nb < NBW; ++nb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) Xs[(16 * wq + 4 * s + i) * LDG + 16 * (nb0 + nb) + c] = x[nb][i];
+            __syncthreads();
+            const int b = b0 + (tid >> 3), j8 = 8 * (tid & 7);
+            uint32_t elig8 = 0;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) elig8 |= (n0 + j8 + m < a.N && !((tk_mask >> (j8 + m)) & 1ull)) ? 1u << m : 0u;
+            topk_select_rows<LDG>(Xs, tid, elig8, a.tk_k, a.cand_col0 + n0,
+                                  b < b_end ? a.tk_part + ((size_t)blockIdx.x * a.Bpad + b) * a.tk_k : nullptr);
+            __syncthreads();
         } else {
             // MODE_STATS: per row of the chunk, max and sum-exp over this tile's candidates: each wave reduces its 32
             // candidates, the second wave of a row parks its pair in LDS and the first merges (running max / sum-exp)
@@ -518,6 +539,7 @@ static hipError_t launch_fused_m(int mode, const FusedArgs &a, dim3 grid, size_t
         case MODE_SCORE: return launch_fused_t<KB, MODE_SCORE>(a, grid, shmem, st);
         case MODE_STATS: return launch_fused_t<KB, MODE_STATS>(a, grid, shmem, st);
         case MODE_COUNT: return launch_fused_t<KB, MODE_COUNT>(a, grid, shmem, st);
+        case MODE_TOPK:  return launch_fused_t<KB, MODE_TOPK>(a, grid, shmem, st);
         default:         return hipErrorInvalidValue;      // training: fused_tile64_kernel
     }
 }

@@ -367,6 +367,73 @@ class HotPath:
         del keep
         return out
 
+    # -- top-k link prediction (include/okge.h: okge_topk_prefixes / okge_topk_queries / okge_topk_merge) ----------------
+    def _topk_workspace(self, B, n, d, k, range_n):
+        need = int(self.lib.okge_topk_workspace_bytes(B, n, d, int(k), int(range_n)))
+        if need == 0:
+            raise N.OkgeError(f"invalid top-k problem B={B} N={n} d={d} k={k} range_n={range_n} (1 <= k <= 64, d <= 512)")
+        if need > self._ws_bytes:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._ws_bytes = need
+        return self._ws
+
+    def _filter(self, filt_ptr, filt_col):
+        """-> (filt_ptr int64, filt_col int32, n_filter) on the device, or (None, None, 0)"""
+        if filt_ptr is None or filt_col is None or int(filt_col.numel()) == 0:
+            return None, None, 0
+        fp = filt_ptr.reshape(-1)
+        if fp.dtype != torch.int64 or fp.device != self.device or not fp.is_contiguous():
+            fp = fp.to(device=self.device, dtype=torch.int64).contiguous()
+        fc = _i32(filt_col, self.device)
+        return fp, fc, int(fc.numel())
+
+    def topk_prefixes(self, E, R, scorer, batch: PrefixBatch, k, filt_ptr=None, filt_col=None, range_n=0):
+        """-> (scores (B, k) fp32, cols (B, k) int32, ids (B, k) int32): every row's k best unfiltered candidates in the total
+        order of include/okge.h, without the (B, N) score block.  filt_ptr / filt_col: CSR of each row's excluded columns."""
+        self._check(batch, E, R)
+        pb, c, keep = self._batch(batch)
+        t = self._tables(E, R, scorer)
+        B, k = batch.B, int(k)
+        ws = self._topk_workspace(B, c.n, t.d, k, range_n) if 1 <= k <= 64 and t.d <= 512 else self.workspace(B, c.n, min(t.d, 512), "score")
+        fp, fc, nf = self._filter(filt_ptr, filt_col)
+        shape = (B, max(k, 1))
+        scores = torch.empty(shape, dtype=torch.float32, device=self.device)
+        cols = torch.empty(shape, dtype=torch.int32, device=self.device)
+        ids = torch.empty(shape, dtype=torch.int32, device=self.device)
+        N.check(self.lib.okge_topk_prefixes(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), k, _ptr(fp), _ptr(fc), nf,
+                                            int(range_n), scores.data_ptr(), cols.data_ptr(), ids.data_ptr(), ws.data_ptr(),
+                                            self._ws_bytes, self._stream()), "okge_topk_prefixes")
+        del keep
+        return scores, cols, ids
+
+    def topk_queries(self, E_local, R, scorer, Q, B, batch: PrefixBatch, shard: Shard, k, filt_ptr=None, filt_col=None, range_n=0):
+        """-> (scores (B, k), cols (B, k)) of precomputed query rows against the LOCAL candidates; columns and filter columns
+        are global (shard.cand_col0 + local position)."""
+        pb, c, keep = self._batch(batch)
+        t = self._tables(E_local, R, scorer)
+        k = int(k)
+        ws = self._topk_workspace(B, c.n, t.d, k, range_n)
+        fp, fc, nf = self._filter(filt_ptr, filt_col)
+        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        cols = torch.empty((B, k), dtype=torch.int32, device=self.device)
+        sh = shard.c()
+        N.check(self.lib.okge_topk_queries(ctypes.byref(t), ctypes.byref(sh), Q.data_ptr(), Q.stride(0), B, ctypes.byref(c), k,
+                                           _ptr(fp), _ptr(fc), nf, int(range_n), scores.data_ptr(), cols.data_ptr(),
+                                           ws.data_ptr(), self._ws_bytes, self._stream()), "okge_topk_queries")
+        del keep
+        return scores, cols
+
+    def topk_merge(self, scores, cols):
+        """(n_lists, B, k) lists -> the (B, k) list of their union in the same order"""
+        n_lists, B, k = scores.shape
+        scores, cols = scores.contiguous(), cols.contiguous()
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_c = torch.empty((B, k), dtype=torch.int32, device=self.device)
+        N.check(self.lib.okge_topk_merge(scores.data_ptr(), cols.data_ptr(), n_lists, B, k, out_s.data_ptr(), out_c.data_ptr(),
+                                         self._stream()), "okge_topk_merge")
+        return out_s, out_c
+
     def prefix_backward(self, E_local, R, scorer, batch: PrefixBatch, shard: Shard, dQ, ent_rows, dE, dR, rel_segments=None):
         """rel_segments: sharded.RowSegments (make_row_segments) -- relation and / or entity gradients by sorted segments
         instead of float atomics"""

@@ -68,6 +68,28 @@ class RelationScorer(RelationModel):
         """scores (b, N) of (?, rel, obj) against all subjects, or against pre-encoded rows `many_subj`."""
         return self._prefix_score(H.PrefixBatch(po_rel=rel, po_obj=obj), many_subj)
 
+    def sp_prefix_topk(self, subj, rel, k, many_obj=None, filter=None):
+        """the k best objects of (subj, rel, ?) per row -> (scores (b, k), entity ids (b, k), candidate columns (b, k)) in the
+        order of include/okge.h ("top-k link prediction"), without the (b, N) block of sp_prefix_score + torch.topk.
+        many_obj: None = all entities from min_entities_size, or an int tensor of candidate entity ids; filter =
+        (filt_ptr, filt_col): CSR of each row's excluded columns (the evaluation's filter, dataset.py:423-453).  Eval mode."""
+        return self._prefix_topk_checked(H.PrefixBatch(sp_subj=subj, sp_rel=rel), k, many_obj, filter)
+
+    def po_prefix_topk(self, rel, obj, k, many_subj=None, filter=None):
+        """the k best subjects of (?, rel, obj) per row; see sp_prefix_topk"""
+        return self._prefix_topk_checked(H.PrefixBatch(po_rel=rel, po_obj=obj), k, many_subj, filter)
+
+    def _prefix_topk_checked(self, batch, k, many, filter):
+        if self.scorer_name not in ("complex", "distmult") or not hasattr(self, "_prefix_topk"):
+            raise NotImplementedError(f"top-k predictions are built for the ComplEx and DistMult scorers, not {self.scorer_name!r}")
+        if self.training and self._any_dropout():
+            raise NotImplementedError("top-k predictions are an eval-mode call: call model.eval() first (dropout is on)")
+        if many is not None:
+            batch.cand_ids = many.reshape(-1)
+        fp, fc = filter if filter is not None else (None, None)
+        with torch.no_grad():
+            return self._prefix_topk(batch, int(k), fp, fc)
+
     def precompute_batch_shared_inputs(self, entity_ids):
         return self.encode_obj(entity_ids)
 
@@ -326,6 +348,20 @@ class LookupBaseRelationEmbedder(RelationEmbedder):
         batch.drop_po_rel = self.dropout_spec(H.STREAM_PO_REL, True)
         batch.drop_sp_rel = self.dropout_spec(H.STREAM_SP_REL, True)
         return eng.score(self.E, self.R, self.scorer_name, batch)
+
+
+    # -- fused top-k prediction (ids in, the k best candidates out) ----------------------------------------------
+    def _any_dropout(self):
+        return max(self.dropout, self.input_dropout, self.relation_dropout, self.relation_input_dropout) > 0
+
+    def _prefix_topk(self, batch: H.PrefixBatch, k, filt_ptr, filt_col):
+        if self.encode_in_torch:
+            raise NotImplementedError("top-k predictions cover the plain lookup embedder (no batch_norm / projection / normalize)")
+        if batch.cand_ids is None:         # all entities with id >= min_entities_size (model.py:512-523)
+            batch.cand_first = self.train_data.min_entities_size
+            batch.n_cand = self.E.shape[0] - batch.cand_first
+        scores, cols, ids = self.engine().topk_prefixes(self.E, self.R, self.scorer_name, batch, k, filt_ptr, filt_col)
+        return scores, ids, cols
 
 
 class LookupSimpleRelationEmbedder(LookupBaseRelationEmbedder):

@@ -16,7 +16,8 @@ loss is separable, so one step needs exactly two small exchanges:
 
 The KL loss (log_softmax over ALL candidates, trainer.py:99-101) adds one: all-gather of the [B] per-shard row
 log-sum-exp.  Evaluation (`ShardedEvaluator`) exchanges the true-answer scores (all-reduce max) and the integer
-{#greater, #equal} counts (all-reduce sum); exact ranks need counts, not a per-shard top-k.
+{#greater, #equal} counts (all-reduce sum); exact ranks need counts, not a per-shard top-k.  Predictions
+(`ShardedTopKPredictor`) are the per-shard top-k: all-gather of the [B, k] scores and columns, merged on every rank.
 
 Entity rows, their dense gradients and Adagrad accumulators never leave their rank; the (small) relation table is
 replicated and its gradient is formed identically everywhere from the exchanged entity rows.
@@ -235,19 +236,9 @@ class ShardedTrainStep:
         return total
 
 
-class ShardedEvaluator:
-    """Filtered ranks with the candidates sharded like the entity table (compute_metrics' rank rule,
-    dataset.py:423-446; exchange plan of SURVEY.md section 8e).
-
-    `ranks()` runs the FUSED counting sweep on this rank's candidates (okge_evaluate_fused_shard; slot sizes up to 512):
-        exchange 1   the prefixes' entity rows -> folded queries (all-gather of the owned rows with an ExchangePlan, else
-                     all-reduce), as in training
-        points       every answer group's true score over the ids this rank holds       -> all-reduce(MAX)  [n_groups] floats
-        sweep        the local candidate tiles against the global true scores, counting > / == in registers
-        counts       + the filter correction for the filter columns this rank holds     -> all-reduce(SUM)  [n_groups, 2] int64
-        rank = #greater + #equal // 2: exact, identical on every rank, bit-equal to the single-device evaluation.
-    No (B, N / world) score block exists (5.1 GB per rank and batch at |E| = 2.5 M, B = 4096); `ranks_materialised()` keeps
-    the score-block path (any slot size)."""
+class ShardedCandidates:
+    """What the candidate-sharded evaluation-side drivers share: this rank's slice of the 1-vs-all candidate list and the folded
+    query block of ALL prefixes (exchange 1 of the training step, eval mode)."""
 
     def __init__(self, E_local, R, scorer, n_ent, min_entities_size=2, engine=None, group=None):
         N.refuse_bias_scorer(scorer, type(self).__name__)
@@ -260,6 +251,7 @@ class ShardedEvaluator:
         self.E, self.R, self.scorer = E_local, R, scorer
         self.engine = engine or H.HotPath(E_local.device)
         c_lo = max(self.ent_lo, min_entities_size)
+        self.min_ent = min_entities_size
         self.cand_first_local = c_lo - self.ent_lo
         self.n_cand_local = max(0, self.ent_hi - c_lo)
         self.n_cand_global = n_ent - min_entities_size
@@ -284,6 +276,21 @@ class ShardedEvaluator:
     def _local(self, batch):
         return H.PrefixBatch(po_rel=batch.po_rel, po_obj=batch.po_obj, sp_subj=batch.sp_subj, sp_rel=batch.sp_rel,
                              cand_first=self.cand_first_local, n_cand=self.n_cand_local)
+
+
+class ShardedEvaluator(ShardedCandidates):
+    """Filtered ranks with the candidates sharded like the entity table (compute_metrics' rank rule,
+    dataset.py:423-446; exchange plan of SURVEY.md section 8e).
+
+    `ranks()` runs the FUSED counting sweep on this rank's candidates (okge_evaluate_fused_shard; slot sizes up to 512):
+        exchange 1   the prefixes' entity rows -> folded queries (all-gather of the owned rows with an ExchangePlan, else
+                     all-reduce), as in training
+        points       every answer group's true score over the ids this rank holds       -> all-reduce(MAX)  [n_groups] floats
+        sweep        the local candidate tiles against the global true scores, counting > / == in registers
+        counts       + the filter correction for the filter columns this rank holds     -> all-reduce(SUM)  [n_groups, 2] int64
+        rank = #greater + #equal // 2: exact, identical on every rank, bit-equal to the single-device evaluation.
+    No (B, N / world) score block exists (5.1 GB per rank and batch at |E| = 2.5 M, B = 4096); `ranks_materialised()` keeps
+    the score-block path (any slot size)."""
 
     def local_scores(self, batch: H.PrefixBatch, plan: ExchangePlan = None):
         return self.engine.score_queries(self.E, self.R, self.scorer, self.queries(batch, plan), batch.B, self._local(batch),
@@ -321,6 +328,39 @@ class ShardedEvaluator:
         counts = eng.rank_counts(x, self.col0, filt_ptr, filt_col, row_ptr, true)
         dist.all_reduce(counts, group=self.group)
         return counts[:, 0] + counts[:, 1] // 2
+
+
+class ShardedTopKPredictor(ShardedCandidates):
+    """Top-k link prediction with the candidates sharded like the entity table (predict.TopKPredictor is the single-device one).
+    Each rank sweeps ITS candidates (okge_topk_queries: columns are global, so is the filter), then
+        all-gather   [B, k] scores and [B, k] columns of every rank (a rank without candidates sends a padding list)
+        merge        okge_topk_merge over the `world` lists
+    The order is total and the merge associative (include/okge.h), so the result is identical on every rank and bit-equal to the
+    single-device list.  run() -> (scores (B, k) fp32, ids (B, k) int32 entity ids, cols (B, k) int32 columns)."""
+
+    def __init__(self, E_local, R, scorer, n_ent, k, min_entities_size=2, engine=None, group=None, range_n=None):
+        super().__init__(E_local, R, scorer, n_ent, min_entities_size, engine, group)
+        self.k, self.range_n = int(k), 0 if range_n is None else int(range_n)
+
+    def run(self, batch, filt_ptr=None, filt_col=None, plan: ExchangePlan = None):
+        from .predict import batch_and_filter
+        batch, filt_ptr, filt_col = batch_and_filter(batch, filt_ptr, filt_col)
+        eng, B, k, dev = self.engine, batch.B, self.k, self.E.device
+        Q = self.queries(batch, plan)
+        if self.n_cand_local > 0:
+            s, c = eng.topk_queries(self.E, self.R, self.scorer, Q, B, self._local(batch), self.shard, k, filt_ptr, filt_col,
+                                    self.range_n)
+        else:
+            s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+            c = torch.full((B, k), -1, dtype=torch.int32, device=dev)
+        if self.world > 1:
+            every_s = torch.empty((self.world * B, k), dtype=torch.float32, device=dev)
+            every_c = torch.empty((self.world * B, k), dtype=torch.int32, device=dev)
+            dist.all_gather_into_tensor(every_s, s.contiguous(), group=self.group)
+            dist.all_gather_into_tensor(every_c, c.contiguous(), group=self.group)
+            s, c = eng.topk_merge(every_s.view(self.world, B, k), every_c.view(self.world, B, k))
+        ids = torch.where(c >= 0, c + self.min_ent, c)
+        return s, ids, c
 
 
 class ReplicaTrainStep(FusedTrainStep):

@@ -564,6 +564,19 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
             return self._score(self.encode_subj(batch.sp_subj), self.encode_rel(batch.sp_rel), many, prefix=True, sp=True, po=False)
         return self._score(many, self.encode_rel(batch.po_rel), self.encode_obj(batch.po_obj), prefix=True, sp=False, po=True)
 
+    # -- top-k prediction over the tables precomputed from tokens (RelationScorer.sp_prefix_topk / po_prefix_topk) -------
+    def _any_dropout(self):
+        return max(self.entity_dropout or 0.0, self.relation_dropout or 0.0) > 0
+
+    def _prefix_topk(self, batch: H.PrefixBatch, k, filt_ptr, filt_col):
+        self.precompute_embeddings_from_tokens()
+        E, R = self.entity_embedding_from_tokens, self.relations_embedding_from_tokens
+        if batch.cand_ids is None:
+            batch.cand_first = self.train_data.min_entities_size
+            batch.n_cand = E.shape[0] - batch.cand_first
+        scores, cols, ids = self.engine().topk_prefixes(E.contiguous(), R.contiguous(), self.scorer_name, batch, k, filt_ptr, filt_col)
+        return scores, ids, cols
+
     # -- AddLossModule / autograd bridge (the reference Trainer's path: trainer.py:142, 206-234) ---------------------
     def _module_slots(self):
         slots = []

@@ -1,0 +1,263 @@
+"""GPU: okge_topk_prefixes (fused_tile_kernel<KB, MODE_TOPK> / the score-and-cut route above slot size 256 + topk_merge_kernel)
+against the EXISTING materialising kernel: HotPath.score's (B, N) block, copied to the host, through tests/topk_reference.py.
+Scores must be bit-equal, columns and ids identical -- the bit-equality the fused evaluation already claims between the sweep
+modes.  One independent check per (scorer, d) against float64."""
+import numpy as np
+import pytest
+import torch
+
+import topk_reference as tr
+from oracle import kge_oracle as ko
+
+pytestmark = pytest.mark.gpu
+
+N_ENT, N_REL = 1502, 11                      # candidates 1-vs-all from id 2: N up to 1500
+SCORERS = ["complex", "distmult"]
+DS = [16, 200, 256, 264, 512]                # KB 4 / 13 / 16 and both wide-slot geometries (264, 512 -> the score-and-cut route)
+BS = [(1, "po"), (1, "sp"), (63, "mixed"), (65, "po"), (130, "mixed"), (130, "sp")]
+NS = [1, 63, 64, 65, 197, 1500]
+KS = [1, 3, 10, 50, 64]
+KMAX = 64
+
+
+@pytest.fixture(scope="module")
+def hp():
+    from open_knowledge_graph_embeddings_amd.hotpath import HotPath
+    return HotPath(torch.device("cuda:0"))
+
+
+def make_tables(d, kind="normal", seed=0):
+    rng = np.random.default_rng(seed + d)
+    if kind == "ties":                       # exact ties are common
+        vals = np.asarray([-0.5, 0.0, 0.5], np.float32)
+        return rng.choice(vals, size=(N_ENT, d)), rng.choice(vals, size=(N_REL, d))
+    if kind == "zero":
+        return np.zeros((N_ENT, d), np.float32), np.zeros((N_REL, d), np.float32)
+    return (rng.standard_normal((N_ENT, d)) * 0.3).astype(np.float32), (rng.standard_normal((N_REL, d)) * 0.3).astype(np.float32)
+
+
+def make_batch(B, kind, seed, dev, cand_ids=None, n_cand=0):
+    from open_knowledge_graph_embeddings_amd.hotpath import PrefixBatch
+    rng = np.random.default_rng(seed)
+    n_po = B if kind == "po" else 0 if kind == "sp" else B // 2
+    n_sp = B - n_po
+    ids = {"po_rel": rng.integers(2, N_REL, n_po), "po_obj": rng.integers(2, N_ENT, n_po),
+           "sp_subj": rng.integers(2, N_ENT, n_sp), "sp_rel": rng.integers(2, N_REL, n_sp)}
+    t = {k: (torch.from_numpy(v.astype(np.int32)).to(dev) if len(v) else None) for k, v in ids.items()}
+    pb = PrefixBatch(po_rel=t["po_rel"], po_obj=t["po_obj"], sp_subj=t["sp_subj"], sp_rel=t["sp_rel"], cand_first=2, n_cand=n_cand)
+    if cand_ids is not None:
+        pb.cand_ids = torch.from_numpy(cand_ids).to(dev)
+    return pb, ids
+
+
+def make_filter(B, N, seed):
+    """sorted CSR with some empty rows; row 0 names columns 63, 64 and N - 1; row 1 leaves only 2 eligible candidates"""
+    rng = np.random.default_rng(seed)
+    rows = []
+    for b in range(B):
+        n = 0 if b % 4 == 3 else int(rng.integers(0, min(N, 40) + 1))
+        rows.append(set(rng.choice(N, size=n, replace=False).tolist()))
+    rows[0] |= {c for c in (63, 64, N - 1) if 0 <= c < N}
+    if B > 1 and N > 2:
+        rows[1] = set(range(N)) - {int(rng.integers(0, N // 2)), int(rng.integers(N // 2, N))}
+    rows = [sorted(r) for r in rows]
+    ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    return ptr, np.asarray([c for r in rows for c in r], np.int32)
+
+
+def run_topk(hp, Et, Rt, scorer, pb, k, filt=None, range_n=0):
+    fp, fc = (None, None) if filt is None else (torch.from_numpy(filt[0]).cuda(), torch.from_numpy(filt[1]).cuda())
+    s, c, ids = hp.topk_prefixes(Et, Rt, scorer, pb, k, fp, fc, range_n=range_n)
+    torch.cuda.synchronize()
+    return s.cpu().numpy(), c.cpu().numpy(), ids.cpu().numpy()
+
+
+def check_case(hp, Et, Rt, scorer, pb, N, filt, ks, ranges, what, cand_ids=None):
+    """reference: the materialised block through the NumPy rule, once at k = 64 (a top-k list is a prefix of the top-64 list)"""
+    X = hp.score(Et, Rt, scorer, pb).cpu().numpy()
+    assert X.shape[1] == N
+    fp, fc = (None, None) if filt is None else filt
+    want = tr.topk_rows(X, KMAX, fp, fc, ids=cand_ids, first_id=2)
+    for k in ks:
+        for rn in ranges:
+            got = run_topk(hp, Et, Rt, scorer, pb, k, filt, rn)
+            tr.assert_same(got, tuple(w[:, :k] for w in want), f"{what} k={k} range_n={rn}")
+    return X, want
+
+
+@pytest.mark.parametrize("d", DS)
+@pytest.mark.parametrize("scorer", SCORERS)
+def test_topk_equals_materialised_scores(hp, scorer, d):
+    dev = torch.device("cuda:0")
+    E, R = make_tables(d)
+    Et, Rt = torch.from_numpy(E).to(dev), torch.from_numpy(R).to(dev)
+    n_padded = 0
+    for bi, (B, bkind) in enumerate(BS):
+        for ni, N in enumerate(NS):
+            pb, _ = make_batch(B, bkind, 100 * bi + ni, dev, n_cand=N)
+            ranges = [0, 128] if N in (197, 1500) else [0]
+            for filt in (None, make_filter(B, N, 7 * bi + ni)):
+                _, want = check_case(hp, Et, Rt, scorer, pb, N, filt, KS, ranges,
+                                     f"{scorer} d={d} B={B}/{bkind} N={N} filter={'yes' if filt else 'no'}")
+                n_padded += int((want[1] == -1).any())
+    assert n_padded > 0                      # k > N and the two-eligible row really padded
+
+
+@pytest.mark.parametrize("d", DS)
+@pytest.mark.parametrize("scorer", SCORERS)
+def test_topk_candidate_list_with_duplicates(hp, scorer, d):
+    """an id list in which ids repeat: equal scores, which tie-break by column; ids come from the list"""
+    dev = torch.device("cuda:0")
+    E, R = make_tables(d, seed=1)
+    Et, Rt = torch.from_numpy(E).to(dev), torch.from_numpy(R).to(dev)
+    rng = np.random.default_rng(d)
+    for N in (65, 197):
+        cand = rng.integers(2, 40, N).astype(np.int32)           # 38 distinct ids in N places
+        pb, _ = make_batch(65, "mixed", N, dev, cand_ids=cand)
+        for filt in (None, make_filter(65, N, N)):
+            X, want = check_case(hp, Et, Rt, scorer, pb, N, filt, [3, 50], [0, 128] if N == 197 else [0],
+                                 f"{scorer} d={d} id list N={N}", cand_ids=cand)
+        assert (X[:, 0:1] == X[:, np.flatnonzero(cand == cand[0])]).all()       # duplicates do tie exactly
+
+
+@pytest.mark.parametrize("d", DS)
+@pytest.mark.parametrize("scorer", SCORERS)
+def test_topk_ties_zero_table_and_nan(hp, scorer, d):
+    dev = torch.device("cuda:0")
+    B, N = 65, 197
+    # tables from {-0.5, 0, 0.5}: exact ties are common
+    E, R = make_tables(d, "ties")
+    Et, Rt = torch.from_numpy(E).to(dev), torch.from_numpy(R).to(dev)
+    pb, _ = make_batch(B, "mixed", 5, dev, n_cand=N)
+    X, _ = check_case(hp, Et, Rt, scorer, pb, N, make_filter(B, N, 3), [10, 64], [0, 128], f"{scorer} d={d} tie table")
+    assert np.mean([len(np.unique(row)) for row in X]) < 0.9 * N                 # exact ties occur in the typical row
+    # all-zero table: every score is 0, the columns must be 0 .. k - 1
+    Ez, Rz = make_tables(d, "zero")
+    s, c, ids = run_topk(hp, torch.from_numpy(Ez).to(dev), torch.from_numpy(Rz).to(dev), scorer, pb, 50)
+    assert (c == np.arange(50)[None, :]).all() and (ids == c + 2).all() and (s == 0).all()
+    # one entity row NaN: its column comes after every finite score and before the padding
+    E, R = make_tables(d, seed=2)
+    nan_col = 70
+    E[nan_col + 2] = np.nan
+    Et, Rt = torch.from_numpy(E).to(dev), torch.from_numpy(R).to(dev)
+    pb, ids_np = make_batch(B, "mixed", 6, dev, n_cand=N)
+    clean = [r for r, e in enumerate(np.concatenate([ids_np["po_obj"], ids_np["sp_subj"]])) if e != nan_col + 2]
+    for filt in (None, make_filter(B, N, 9)):
+        X, _ = check_case(hp, Et, Rt, scorer, pb, N, filt, [64], [0, 128], f"{scorer} d={d} NaN row")
+    assert all(np.isnan(X[r, nan_col]) and np.isfinite(np.delete(X[r], nan_col)).all() for r in clean)
+    # 61 eligible columns, 0 .. 59 and the NaN one: it is entry 60, behind the 60 numbers and in front of the padding
+    out = np.asarray([c_ for c_ in range(60, N) if c_ != nan_col], np.int32)
+    s, c, _ = run_topk(hp, Et, Rt, scorer, pb, 64, (np.arange(B + 1, dtype=np.int64) * len(out), np.tile(out, B)))
+    for r in clean:
+        assert c[r, 60] == nan_col and np.isnan(s[r, 60]) and (c[r, 61:] == -1).all() and (s[r, 61:] == -np.inf).all()
+        assert np.isfinite(s[r, :60]).all() and sorted(c[r, :60].tolist()) == list(range(60))
+
+
+def test_topk_tail_split_launch(hp):
+    """more 64-candidate tiles than compute units and three 64-row blocks: the closing round of the sweep is launched apart with
+    the rows split (launch_score_sweep), so the records' per-tile pointer must move with the window.  The N = 1500 cases above
+    have 24 tiles and never take that launch; the library's timing name says whether this one did."""
+    dev = torch.device("cuda:0")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n_ent = (cus + 1) * 64 + 2
+    rng = np.random.default_rng(4)
+    E = (rng.standard_normal((n_ent, 16)) * 0.3).astype(np.float32)
+    R = (rng.standard_normal((N_REL, 16)) * 0.3).astype(np.float32)
+    Et, Rt = torch.from_numpy(E).to(dev), torch.from_numpy(R).to(dev)
+    from open_knowledge_graph_embeddings_amd.hotpath import PrefixBatch
+    B = 130
+    pb = PrefixBatch(sp_subj=torch.from_numpy(rng.integers(2, n_ent, B).astype(np.int32)).to(dev),
+                     sp_rel=torch.from_numpy(rng.integers(2, N_REL, B).astype(np.int32)).to(dev), cand_first=2, n_cand=n_ent - 2)
+    filt = make_filter(B, n_ent - 2, 1)
+    X = hp.score(Et, Rt, "distmult", pb).cpu().numpy()
+    want = tr.topk_rows(X, 10, filt[0], filt[1], first_id=2)
+    hp.timing(True)
+    try:
+        got = run_topk(hp, Et, Rt, "distmult", pb, 10, filt)
+        names = hp.timing_collect()
+    finally:
+        hp.timing(False)
+    assert "fused_tile_topk_tail" in names, names
+    tr.assert_same(got, want, "tail split")
+
+
+@pytest.mark.parametrize("d", DS)
+@pytest.mark.parametrize("scorer", SCORERS)
+def test_topk_against_float64(hp, scorer, d):
+    """independent of the materialising kernel: every returned column's float64 score is at least the float64 k-th best minus
+    2e-4 (twice the project's 1e-4 score bound), and the returned scores are within 1e-4 of float64"""
+    dev = torch.device("cuda:0")
+    B, N, k = 65, 197, 10
+    E, R = make_tables(d, seed=3)
+    pb, ids = make_batch(B, "mixed", 8, dev, n_cand=N)
+    kind = ko.KIND_NAMES[scorer]
+    E64, R64 = E.astype(np.float64), R.astype(np.float64)
+    X64 = np.concatenate([ko.score_prefix(kind, ko.DIR_PO, E64[ids["po_obj"]], R64[ids["po_rel"]], E64[2:2 + N]),
+                          ko.score_prefix(kind, ko.DIR_SP, E64[ids["sp_subj"]], R64[ids["sp_rel"]], E64[2:2 + N])])
+    filt = make_filter(B, N, 2)
+    s, c, _ = run_topk(hp, torch.from_numpy(E).to(dev), torch.from_numpy(R).to(dev), scorer, pb, k, filt)
+    for b in range(B):
+        elig = np.setdiff1d(np.arange(N), filt[1][filt[0][b]:filt[0][b + 1]])
+        live = c[b] >= 0
+        assert live.sum() == min(k, len(elig)) and np.isin(c[b][live], elig).all() and len(set(c[b][live])) == live.sum()
+        kth = np.sort(X64[b, elig])[::-1][live.sum() - 1]
+        if b == 0:
+            print(f"{scorer} d={d} row 0: min margin to the f64 k-th best {(X64[b, c[b][live]] - kth).min():.3e}, "
+                  f"max |score - f64| {np.abs(s[b][live] - X64[b, c[b][live]]).max():.3e}")
+        assert (X64[b, c[b][live]] >= kth - 2e-4).all()
+        assert np.abs(s[b][live] - X64[b, c[b][live]]).max() < 1e-4
+
+
+def test_predictor_takes_a_collated_evaluation_batch(hp):
+    """predict.TopKPredictor on a dataset.CollatedBatch (as the producer builds it with is_training_data=False) uses its filter CSR"""
+    from open_knowledge_graph_embeddings_amd.dataset import CollatedBatch
+    from open_knowledge_graph_embeddings_amd.predict import TopKPredictor
+    dev = torch.device("cuda:0")
+    B, N, k = 65, 197, 10
+    E, R = make_tables(24)
+    Et, Rt = torch.from_numpy(E).to(dev), torch.from_numpy(R).to(dev)
+    pb, _ = make_batch(B, "mixed", 3, dev, n_cand=N)
+    filt = make_filter(B, N, 4)
+    cb = CollatedBatch(batch=pb, normalizer_loss=float(B * N), normalizer_metric=1.0, n_cand=N,
+                       filt_ptr=torch.from_numpy(filt[0]).to(dev), filt_col=torch.from_numpy(filt[1]).to(dev))
+    pred = TopKPredictor(Et, Rt, "complex", k, engine=hp, range_n=64)
+    s, ids, c = (x.cpu().numpy() for x in pred.run(cb))
+    want = tr.topk_rows(hp.score(Et, Rt, "complex", pb).cpu().numpy(), k, filt[0], filt[1], first_id=2)
+    tr.assert_same((s, c, ids), want, "collated batch")
+    s2, _, c2 = (x.cpu().numpy() for x in pred.run(pb))          # a bare PrefixBatch: no filter
+    tr.assert_same((s2, c2), tr.topk_rows(hp.score(Et, Rt, "complex", pb).cpu().numpy(), k)[:2], "no filter")
+    assert (c != c2).any()
+
+
+def test_topk_invalid_arguments(hp):
+    """documented statuses, returned before any launch: k = 0 (-1), k = 65 (-2), dropout (-2), a candidate table (-2), d = 520 (-2)"""
+    from open_knowledge_graph_embeddings_amd import OkgeError
+    from open_knowledge_graph_embeddings_amd.hotpath import DropoutSpec
+    dev = torch.device("cuda:0")
+    E, R = make_tables(16)
+    Et, Rt = torch.from_numpy(E).to(dev), torch.from_numpy(R).to(dev)
+
+    def status(pb, k, Et=Et, Rt=Rt):
+        with pytest.raises(OkgeError) as ei:
+            hp.topk_prefixes(Et, Rt, "complex", pb, k)
+        return str(ei.value)
+    pb, _ = make_batch(5, "mixed", 0, dev, n_cand=100)
+    assert "code -1" in status(pb, 0)
+    assert "code -2" in status(pb, 65)
+    pb.drop_cand = DropoutSpec(p=0.5)
+    assert "code -2" in status(pb, 10)
+    pb, _ = make_batch(5, "mixed", 0, dev, n_cand=100)
+    pb.drop_sp_rel = DropoutSpec(p=0.25)
+    assert "code -2" in status(pb, 10)
+    pb, _ = make_batch(5, "mixed", 0, dev, n_cand=100)
+    pb.cand_table, pb.cand_first = Et[:200].contiguous(), 0
+    assert "code -2" in status(pb, 10)
+    pb, _ = make_batch(5, "mixed", 0, dev, n_cand=100)
+    E520 = torch.zeros((N_ENT, 520), device=dev)
+    assert "code -2" in status(pb, 10, E520, torch.zeros((N_REL, 520), device=dev))
+    with pytest.raises(OkgeError) as ei:                         # the merge refuses the same k
+        hp.topk_merge(torch.zeros((2, 3, 65), device=dev), torch.zeros((2, 3, 65), dtype=torch.int32, device=dev))
+    assert "code -2" in str(ei.value)
+    torch.cuda.synchronize()
+    s, c, ids = run_topk(hp, Et, Rt, "complex", make_batch(5, "mixed", 0, dev, n_cand=100)[0], 10)     # and the engine still works
+    assert (c >= 0).all() and (ids == c + 2).all()
