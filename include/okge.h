@@ -157,6 +157,20 @@ int okge_score_prefixes(const okge_tables *t, const okge_prefix_batch *batch, co
  *               reference (trainer.py:229-234) without two fill launches per step.  Contiguous candidate range
  *               (cand->ids == NULL), unsharded table. */
 #define OKGE_TRAIN_CLEAR_GRADS 16
+/*               OKGE_TRAIN_ROW_GRADS -- gradients in OCCURRENCE ROWS instead of tables: what nn.Embedding(sparse=True)
+ *               (model_config.sparse, model.py:390-391) hands autograd -- one value row per looked-up id, uncoalesced.
+ *                 dE : (cand->n + n_po + n_sp, d).  Row j < N = cand->n: gradient of candidate column j, already multiplied by
+ *                      that column's dropout mask; row N + i: gradient of the prefix entity row of batch row i (po rows first).
+ *                 dR : (n_po + n_sp, d).  Row i: gradient of the relation row of batch row i.
+ *               Every row is STORED exactly once: nothing is read or accumulated, no float atomics, no zero fill -- the buffers
+ *               may hold anything on entry.  cand->ids (repeats allowed) / the contiguous range and the prefix ids still name the
+ *               rows of the real tables that are gathered.  Dropout masks are the ones the dense step draws for the same batch,
+ *               seed and step (the Philox counter is keyed by position, not by id).  Not with OKGE_TRAIN_LOSS_ONLY or
+ *               cand->table; GRADS_ZERO / UNIQUE_CANDIDATES / DISTINCT_PREFIX_ROWS / CLEAR_GRADS are ignored (implied).  The
+ *               data-bias scorers answer OKGE_ERR_UNSUPPORTED.  Workspace: okge_train_row_grads_workspace_bytes -- the step's
+ *               own scratch plus the gathered rows, (N + 2 B) x d floats.  Feed the rows to okge_adagrad_rows with the
+ *               occurrence ids [cand ids | po_obj | sp_subj] and [po_rel | sp_rel]. */
+#define OKGE_TRAIN_ROW_GRADS 32
 int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *batch,
                                 const okge_candidates *cand, const okge_positives *pos,
                                 int32_t loss_kind, float label_smoothing, double normalizer, int32_t flags,
@@ -231,6 +245,8 @@ int okge_prefix_backward_segmented(const okge_tables *t, const okge_shard *shard
  * environment OKGE_GT_MBYTES), so this grows with B x min(N, range), not with B x N: the reference's autograd graph
  * keeps several (B, N) fp32 tensors alive instead (trainer.py:75-106). */
 size_t okge_train_workspace_bytes(int32_t B, int32_t N, int32_t d);
+/* The same for okge_train_forward_backward(OKGE_TRAIN_ROW_GRADS): the above plus the gathered occurrence rows. */
+size_t okge_train_row_grads_workspace_bytes(int32_t B, int32_t N, int32_t d);
 /* Scratch of the scoring-only calls (okge_score_prefixes, okge_evaluate_batch): the folded query block. */
 size_t okge_score_workspace_bytes(int32_t B, int32_t d);
 /* Scratch of okge_row_logsumexp: query block + one range of (max, sum-exp) tile statistics. */
@@ -526,6 +542,37 @@ int okge_adagrad_lazy(const okge_lazy_tensor *tensors, int32_t n_tensors, int32_
 /* calls: the batch's okge_pool_encode_calls list; tables: the lazy tensors (matched to a call by p == e->W) */
 int okge_pool_catch_up_calls(const okge_pool_call *calls, int32_t n_calls, const okge_lazy_tensor *tables, int32_t n_tables,
                              const int32_t *counters, float lr, float weight_decay, float eps, void *stream);
+
+/* ---- row-sparse Adagrad: coalesce occurrence rows and update only the table rows they name --------------------------------
+ * Replaces torch.optim.Adagrad's sparse branch (torch/optim/adagrad.py, _single_tensor_adagrad: grad.coalesce(), then
+ * state_sum.add_(grad^2), param.add_(grad / (sqrt(state_sum_rows) + eps), alpha=-clr)) for the gradients
+ * nn.Embedding(sparse=True) leaves on entity_embedding.weight / relation_embedding.weight (model.py:390-391), for up to two
+ * tensors in one call.  Per tensor: table p and accumulator state_sum (table_rows x row_len, contiguous), n occurrence ids
+ * (int32, device) and their gradient rows g[n][ld_g].
+ *   coalescing : for every distinct id its occurrence rows are added in ASCENDING occurrence position, sequentially in fp32 --
+ *                ((g_a + g_b) + g_c) ... -- which fixes the result bit for bit (torch's coalesce() sums in an order of its own).
+ *   update     : on the coalesced row exactly okge_adagrad_step at weight_decay = 0 -- sum = fma(g, g, sum),
+ *                p = p - lr * (g / (sqrt(sum) + eps)), correctly rounded sqrt and division -- with no weight-decay term at all
+ *                (torch refuses weight_decay != 0 with sparse gradients; so do the callers of this function).  A dense step at
+ *                weight_decay = 0 leaves a row with an all-zero gradient bit-unchanged, so the two steps agree on every row.
+ *   untouched  : rows whose id does not occur are neither read nor written.
+ *   bad ids    : an id outside [0, table_rows) is skipped and counted (okge_id_errors); nothing is written for it.
+ *   cost       : O(n log n) on 8-byte keys (ordered chunks of 1024, then merge passes) + the n gradient rows and the distinct
+ *                table rows; nothing proportional to the table.  One lane group walks one run of equal ids, so a single id
+ *                repeated thousands of times is summed by one group (the order of the additions is part of the contract).
+ *   graphs     : no host synchronisation, no count read back; the launches are fixed by (n of each tensor).
+ * n up to 2^20 per tensor (beyond: OKGE_ERR_UNSUPPORTED); n = 0 is a no-op.  16-byte accesses when row_len and ld_g are
+ * multiples of 4 and the three bases are 16-byte aligned, single floats otherwise.  The two tensors must not overlap. */
+typedef struct okge_rows_tensor {
+    float         *p, *state_sum;
+    const int32_t *ids;
+    const float   *g;
+    int64_t        ld_g;
+    int32_t        n, table_rows, row_len, _pad;
+} okge_rows_tensor;
+size_t okge_adagrad_rows_workspace_bytes(int64_t n0, int64_t n1);      /* n of the first / second tensor (0: absent) */
+int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float lr, float eps, void *workspace,
+                      size_t workspace_bytes, void *stream);
 
 /* ---- the whole step in one call: okge_train_forward_backward + the dense Adagrad update of both tables ------------------
  * (Trainer.compute_one_batch's training branch end to end, trainer.py:217-257 with utils/optim.py:139-160.)  Same arithmetic,

@@ -14,7 +14,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_i
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libokge_hip.so")
-SOURCES = ["okge_api.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_misc.hip", "okge_topk.hip", "okge_bias.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
+SOURCES = ["okge_api.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_misc.hip", "okge_topk.hip", "okge_bias.hip", "okge_sparse.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
 # every header a source may include: all of csrc/*.h (listed by the directory, so a new header cannot be forgotten) + the ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "okge.h")]
 
@@ -26,6 +26,7 @@ OKGE_TRAIN_LOSS_ONLY = 2
 OKGE_TRAIN_UNIQUE_CANDIDATES = 4
 OKGE_TRAIN_DISTINCT_PREFIX_ROWS = 8
 OKGE_TRAIN_CLEAR_GRADS = 16
+OKGE_TRAIN_ROW_GRADS = 32
 SCORERS = {"complex": OKGE_COMPLEX, "distmult": OKGE_DISTMULT, "bias_relation": OKGE_BIAS_RELATION,
            "bias_entity": OKGE_BIAS_ENTITY}
 LOSSES = {"bce": OKGE_LOSS_BCE, "kl": OKGE_LOSS_KL}
@@ -51,6 +52,7 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_collate_batch", "okge_collate_batches", "okge_dataset_open", "okge_dataset_sizes",
            "okge_dataset_copy", "okge_dataset_close", "okge_encode_rows", "okge_scale_inplace", "okge_rescale_gradients", "okge_adagrad_step", "okge_adagrad_step2", "okge_id_errors", "okge_clip_grad_norm", "okge_merge_logsumexp", "okge_filtered_ranks", "okge_timing_enable",
            "okge_topk_workspace_bytes", "okge_topk_prefixes", "okge_topk_queries", "okge_topk_merge",
+           "okge_train_row_grads_workspace_bytes", "okge_adagrad_rows", "okge_adagrad_rows_workspace_bytes",
            "okge_timing_reset", "okge_timing_collect"]
 
 
@@ -138,6 +140,11 @@ class AdagradTensor(Structure):
                 ("row_len", c_int32), ("touched_stamp", c_int32), ("zero_grad", c_int32), ("rows", c_int32)]
 
 
+class RowsTensor(Structure):
+    _fields_ = [("p", c_void_p), ("state_sum", c_void_p), ("ids", c_void_p), ("g", c_void_p), ("ld_g", c_int64),
+                ("n", c_int32), ("table_rows", c_int32), ("row_len", c_int32), ("_pad", c_int32)]
+
+
 class LazyTensor(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("state_sum", c_void_p), ("rows", c_int64), ("row_steps", c_void_p),
                 ("row_touched", c_void_p), ("row_len", c_int32), ("touched_stamp", c_int32)]
@@ -218,6 +225,12 @@ def lib():
     L.okge_last_error.restype = c_char_p
     L.okge_train_workspace_bytes.restype = c_size_t
     L.okge_train_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.okge_train_row_grads_workspace_bytes.restype = c_size_t
+    L.okge_train_row_grads_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.okge_adagrad_rows_workspace_bytes.restype = c_size_t
+    L.okge_adagrad_rows_workspace_bytes.argtypes = [c_int64, c_int64]
+    L.okge_adagrad_rows.restype = c_int32
+    L.okge_adagrad_rows.argtypes = [POINTER(RowsTensor), c_int32, c_float, c_float, c_void_p, c_size_t, c_void_p]
     L.okge_score_workspace_bytes.restype = c_size_t
     L.okge_score_workspace_bytes.argtypes = [c_int32, c_int32]
     L.okge_lse_workspace_bytes.restype = c_size_t

@@ -812,6 +812,73 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
     return OKGE_OK;
 }
 
+// ---- OKGE_TRAIN_ROW_GRADS: gradients in occurrence rows ---------------------------------------------------------------------
+// The occurrence rows of the batch are gathered into two small tables behind the step's own scratch -- EV = [candidate rows |
+// prefix entity rows], RV = relation rows -- and the step runs on them with positions for ids: a contiguous candidate range
+// 0 .. N-1 and OKGE_TRAIN_DISTINCT_PREFIX_ROWS, the path the encoded-row ("virtual table") models take.  Every gradient row is
+// then STORED once, at its position; the tile kernels are the ones every other caller runs, untouched.  Dropout counters are
+// keyed by position (okge_dropout), so the masks are the dense step's.
+struct RowGradsLayout { size_t off_EV, off_RV, off_ids, total; };
+static RowGradsLayout row_grads_layout(const Geometry &g)
+{
+    RowGradsLayout l;
+    size_t off = align_up(g.total, 256);
+    l.off_EV = off;  off += align_up((size_t)(g.N + g.B) * g.d * sizeof(float), 256);
+    l.off_RV = off;  off += align_up((size_t)g.B * g.d * sizeof(float), 256);
+    l.off_ids = off; off += align_up((size_t)2 * g.B * sizeof(int32_t), 256);
+    l.total = off;
+    return l;
+}
+
+size_t okge_train_row_grads_workspace_bytes(int32_t B, int32_t N, int32_t d)
+{
+    Geometry g;
+    if (!make_geometry(B, N, d, g)) return 0;
+    return row_grads_layout(g).total;
+}
+
+static int train_row_grads(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, const okge_positives *pos,
+                           int32_t loss_kind, float label_smoothing, double normalizer, int32_t flags, double *loss_out, float *dE,
+                           float *dR, float *scores, int64_t ld_scores, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (flags & OKGE_TRAIN_LOSS_ONLY) return fail(OKGE_ERR_INVALID, "OKGE_TRAIN_ROW_GRADS asks for gradients: not with OKGE_TRAIN_LOSS_ONLY");
+    if (cand->table) return fail(OKGE_ERR_INVALID, "training needs candidates from the entity table");
+    if (!dE || !dR) return fail(OKGE_ERR_INVALID, "null output");
+    if (int rc = refuse_bias(t->scorer, "okge_train_forward_backward(OKGE_TRAIN_ROW_GRADS)", "the unused slot's rows have no gradient to store")) return rc;
+    const int B = batch->n_po + batch->n_sp, N = cand->n;
+    Geometry g;
+    make_geometry(B, N, t->d, g);
+    const RowGradsLayout l = row_grads_layout(g);
+    if (!workspace || workspace_bytes < l.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_train_row_grads_workspace_bytes)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    RowsGather a;
+    std::memset(&a, 0, sizeof(a));
+    a.E = t->E; a.R = t->R;
+    a.EV = reinterpret_cast<float *>(ws + l.off_EV); a.RV = reinterpret_cast<float *>(ws + l.off_RV);
+    a.pos_ids = reinterpret_cast<int32_t *>(ws + l.off_ids);
+    a.cand_ids = cand->ids; a.cand_first = cand->first_id; a.N = N;
+    a.po_obj = batch->po_obj; a.sp_subj = batch->sp_subj; a.po_rel = batch->po_rel; a.sp_rel = batch->sp_rel;
+    a.n_po = batch->n_po; a.n_sp = batch->n_sp; a.d = t->d;
+    a.n_ent = t->n_ent; a.n_rel = t->n_rel;
+    a.id_err = id_err_ptr();
+    a.vec = (t->d % 4 == 0 && (reinterpret_cast<uintptr_t>(t->E) | reinterpret_cast<uintptr_t>(t->R)) % 16 == 0) ? 1 : 0;
+    {
+        ScopedTimer tm("rows_gather", st);
+        if (hipError_t e = launch_rows_gather(a, st); e != hipSuccess) return fail_hip(e, "rows_gather");
+    }
+    okge_tables tv = *t;
+    tv.E = a.EV; tv.R = a.RV; tv.n_ent = N + B; tv.n_rel = B;
+    okge_prefix_batch vb = *batch;
+    vb.po_obj = a.pos_ids; vb.sp_subj = a.pos_ids + batch->n_po;
+    vb.po_rel = a.pos_ids + B; vb.sp_rel = a.pos_ids + B + batch->n_po;
+    okge_candidates vc = *cand;
+    vc.ids = nullptr; vc.first_id = 0;
+    return train_core(&tv, nullptr, &vb, nullptr, 0, B, &vc, pos, loss_kind, label_smoothing, normalizer, N,
+                      OKGE_TRAIN_GRADS_ZERO | OKGE_TRAIN_UNIQUE_CANDIDATES | OKGE_TRAIN_DISTINCT_PREFIX_ROWS, loss_out, dE, dR, nullptr,
+                      scores, ld_scores, nullptr, workspace, g.total, stream);
+}
+
 int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
                                 const okge_positives *pos, int32_t loss_kind, float label_smoothing,
                                 double normalizer, int32_t flags, double *loss_out, float *dE, float *dR,
@@ -820,6 +887,9 @@ int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *b
 {
     if (int rc = check_common(t, batch, cand)) return rc;
     if (!(flags & OKGE_TRAIN_LOSS_ONLY) && !dR) return fail(OKGE_ERR_INVALID, "null output");
+    if (flags & OKGE_TRAIN_ROW_GRADS)
+        return train_row_grads(t, batch, cand, pos, loss_kind, label_smoothing, normalizer, flags, loss_out, dE, dR, scores, ld_scores,
+                               workspace, workspace_bytes, stream);
     return train_core(t, nullptr, batch, nullptr, 0, batch->n_po + batch->n_sp, cand, pos, loss_kind, label_smoothing,
                       normalizer, cand->n, flags, loss_out, dE, dR, nullptr, scores, ld_scores, nullptr, workspace,
                       workspace_bytes, stream);
@@ -1528,6 +1598,65 @@ int okge_adagrad_multi(const okge_adagrad_tensor *tensors, int32_t n_tensors, fl
     ScopedTimer tm("adagrad", st);
     hipError_t e = launch_adagrad_multi(segs, n_tensors, lr, weight_decay, eps, st);
     if (e != hipSuccess) return fail_hip(e, "adagrad");
+    return OKGE_OK;
+}
+
+// ---- okge_adagrad_rows: torch's sparse Adagrad on occurrence rows ---------------------------------------------------------------
+constexpr int64_t ROWS_MAX_N = (int64_t)1 << 20;
+static size_t rows_keys_bytes(int64_t n) { return n > 0 ? align_up((size_t)n * sizeof(uint64_t), 256) : 0; }
+
+size_t okge_adagrad_rows_workspace_bytes(int64_t n0, int64_t n1)
+{
+    if (n0 < 0 || n1 < 0 || n0 > ROWS_MAX_N || n1 > ROWS_MAX_N) return 0;
+    return 2 * rows_keys_bytes(n0) + 2 * rows_keys_bytes(n1);
+}
+
+int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float lr, float eps, void *workspace, size_t workspace_bytes,
+                      void *stream)
+{
+    if (n_tensors < 0 || n_tensors > ROWS_MAX_SEGS || (n_tensors > 0 && !tensors)) return fail(OKGE_ERR_INVALID, "one or two tensors");
+    RowsSegs segs;
+    std::memset(&segs, 0, sizeof(segs));
+    size_t need = 0;
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_rows_tensor &x = tensors[k];
+        if (x.n < 0) return fail(OKGE_ERR_INVALID, "negative occurrence count");
+        if (x.n > ROWS_MAX_N) return fail(OKGE_ERR_UNSUPPORTED, "okge_adagrad_rows takes up to 2^20 occurrence rows per tensor");
+        if (x.n == 0) continue;
+        if (!x.p || !x.state_sum || !x.ids || !x.g) return fail(OKGE_ERR_INVALID, "null tensor");
+        if (x.table_rows <= 0 || x.row_len <= 0 || x.ld_g < x.row_len) return fail(OKGE_ERR_INVALID, "bad table shape / leading dimension");
+        need += 2 * rows_keys_bytes(x.n);
+    }
+    if (need == 0) return OKGE_OK;
+    if (!workspace || workspace_bytes < need) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_adagrad_rows_workspace_bytes)");
+    char *ws = static_cast<char *>(workspace);
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_rows_tensor &x = tensors[k];
+        if (x.n == 0) continue;
+        RowsSeg &sg = segs.s[segs.n_segs++];
+        sg.p = x.p; sg.s = x.state_sum; sg.g = x.g; sg.ids = x.ids; sg.ld_g = x.ld_g;
+        sg.n = x.n; sg.table_rows = x.table_rows; sg.row_len = x.row_len;
+        sg.keys[0] = reinterpret_cast<uint64_t *>(ws); ws += rows_keys_bytes(x.n);
+        sg.keys[1] = reinterpret_cast<uint64_t *>(ws); ws += rows_keys_bytes(x.n);
+        sg.vec = (x.row_len % 4 == 0 && x.ld_g % 4 == 0 &&
+                  (reinterpret_cast<uintptr_t>(x.p) | reinterpret_cast<uintptr_t>(x.state_sum) | reinterpret_cast<uintptr_t>(x.g)) % 16 == 0) ? 1 : 0;
+        // lanes per run: one per 16-byte column group up to 16 (rows of 64 floats and more: 4 runs in flight per wave, each
+        // lane several independent column groups)
+        const int groups = sg.vec ? x.row_len / 4 : x.row_len;
+        sg.lane_shift = 0;
+        while (sg.lane_shift < 4 && (1 << sg.lane_shift) < groups) ++sg.lane_shift;
+    }
+    segs.id_err = id_err_ptr();
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int sorted_in = 0;
+    {
+        ScopedTimer tm("rows_sort", st);
+        if (hipError_t e = launch_rows_sort(segs, &sorted_in, st); e != hipSuccess) return fail_hip(e, "rows_sort");
+    }
+    {
+        ScopedTimer tm("rows_update", st);
+        if (hipError_t e = launch_rows_update(segs, sorted_in, lr, eps, st); e != hipSuccess) return fail_hip(e, "rows_update");
+    }
     return OKGE_OK;
 }
 

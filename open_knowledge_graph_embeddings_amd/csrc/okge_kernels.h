@@ -261,6 +261,32 @@ constexpr int LAZY_STEP = 0, LAZY_FLUSH = 1;
 struct LazySeg { float *p, *g, *s; int32_t *steps; uint8_t *touched; int64_t rows; int32_t row_len, stamp; };
 hipError_t launch_adagrad_lazy(const LazySeg *segs, int n_segs, int32_t *counters, int window, int mode, float lr, float wd,
                                float eps, hipStream_t st);
+// row-sparse training (okge_sparse.hip).  Gather: the occurrence rows of one batch -- candidates, prefix entities, relations --
+// as the two small tables EV (N + B rows) / RV (B rows) of the relabelled problem, and the position ids that name them
+// (pos_ids[0..B) = N + i, pos_ids[B..2B) = i).
+struct RowsGather {
+    const float   *E, *R;
+    float         *EV, *RV;
+    const int32_t *cand_ids, *po_obj, *sp_subj, *po_rel, *sp_rel;
+    int32_t       *pos_ids;
+    int           *id_err;
+    int64_t        n_ent, n_rel;
+    int32_t        cand_first, N, n_po, n_sp, d, vec;
+};
+hipError_t launch_rows_gather(const RowsGather &a, hipStream_t st);
+// okge_adagrad_rows: one segment per tensor.  keys[0] / keys[1]: n 8-byte sort keys each (ping-pong of the merge passes)
+constexpr int ROWS_MAX_SEGS = 2;
+struct RowsSeg {
+    float         *p, *s;
+    const float   *g;
+    const int32_t *ids;
+    uint64_t      *keys[2];
+    int64_t        ld_g;
+    int32_t        n, table_rows, row_len, vec, lane_shift;      // 1 << lane_shift lanes share one run of equal ids
+};
+struct RowsSegs { RowsSeg s[ROWS_MAX_SEGS]; int n_segs; int *id_err; };
+hipError_t launch_rows_sort(const RowsSegs &segs, int *sorted_in, hipStream_t st);
+hipError_t launch_rows_update(const RowsSegs &segs, int sorted_in, float lr, float eps, hipStream_t st);
 hipError_t launch_dc_reduce(const float *slab, int nsplit, int rows_pad, int D16, int N, int d, const int32_t *cand_ids,
                             int cand_first, int exclusive, int grads_zero, float *dE, int64_t table_rows, int *id_err,
                             hipStream_t st);

@@ -1,0 +1,222 @@
+// Row-sparse training of the lookup models (model_config.sparse: nn.Embedding(sparse=True) + torch's sparse Adagrad,
+// model.py:390-391).  Kernels of
+//   okge_train_forward_backward(OKGE_TRAIN_ROW_GRADS)   rows_gather_kernel: the occurrence rows of one batch as two small tables
+//   okge_adagrad_rows                                   rows_sort_chunk_kernel / rows_merge_kernel: occurrences ordered by (id, position)
+//                                                       rows_update_kernel: per distinct id, its gradient rows added up in ascending
+//                                                       position, sequentially in fp32, then the Adagrad update of that one table row
+// Nothing here is proportional to the table: the sort is O(n log n) on 8-byte keys, the update touches the n gradient rows and
+// the distinct table rows they name.  No float atomics, no host synchronisation; the launch sequence depends on the n alone.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "okge_kernels.h"
+
+namespace okge {
+
+namespace {
+
+constexpr int SORT_CHUNK = 1024;          // keys one workgroup orders in LDS (bitonic network, one compare-exchange per thread and step)
+constexpr int MERGE_PER_THREAD = 4;       // outputs one thread of a merge pass produces
+constexpr uint64_t KEY_SKIP = ~0ull;      // an occurrence whose id lies outside the table: sorts behind every real key, never written
+
+__device__ __forceinline__ void copy_row(const float *__restrict__ src, float *__restrict__ dst, int d, int vec)
+{
+    if (vec) {
+        const float4 *s4 = reinterpret_cast<const float4 *>(src);
+        float4 *d4 = reinterpret_cast<float4 *>(dst);
+        for (int k = threadIdx.x; k < (d >> 2); k += blockDim.x) d4[k] = s4[k];
+    } else {
+        for (int k = threadIdx.x; k < d; k += blockDim.x) dst[k] = src[k];
+    }
+}
+
+// block r < N: candidate r; N <= r < N + B: prefix entity of batch row r - N; then: relation of batch row r - N - B
+// (po rows first, as everywhere).  The position ids the relabelled problem names its rows by are written alongside.
+__global__ __launch_bounds__(64) void rows_gather_kernel(const RowsGather a)
+{
+    const int r = blockIdx.x, B = a.n_po + a.n_sp;
+    int *err = threadIdx.x == 0 ? a.id_err : nullptr;
+    if (r < a.N) {
+        const int64_t row = checked_row(a.cand_ids ? (int64_t)a.cand_ids[r] : (int64_t)a.cand_first + r, a.n_ent, err);
+        copy_row(a.E + row * a.d, a.EV + (size_t)r * a.d, a.d, a.vec);
+    } else if (r < a.N + B) {
+        const int i = r - a.N;
+        const int64_t row = checked_row(i < a.n_po ? a.po_obj[i] : a.sp_subj[i - a.n_po], a.n_ent, err);
+        copy_row(a.E + row * a.d, a.EV + (size_t)r * a.d, a.d, a.vec);
+        if (threadIdx.x == 0) a.pos_ids[i] = r;
+    } else {
+        const int i = r - a.N - B;
+        const int64_t row = checked_row(i < a.n_po ? a.po_rel[i] : a.sp_rel[i - a.n_po], a.n_rel, err);
+        copy_row(a.R + row * a.d, a.RV + (size_t)i * a.d, a.d, a.vec);
+        if (threadIdx.x == 0) a.pos_ids[B + i] = i;
+    }
+}
+
+// keys (id << 32 | position) of one chunk of occurrences, ordered: positions are distinct, so the order is total and "stable"
+__global__ __launch_bounds__(SORT_CHUNK / 2) void rows_sort_chunk_kernel(const RowsSegs segs)
+{
+    const RowsSeg &sg = segs.s[blockIdx.y];
+    __shared__ uint64_t k[SORT_CHUNK];
+    const int base = blockIdx.x * SORT_CHUNK, tid = threadIdx.x;
+    if (base >= sg.n) return;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int t = tid + h * (SORT_CHUNK / 2), i = base + t;
+        uint64_t key = KEY_SKIP;
+        if (i < sg.n) {
+            const int32_t id = sg.ids[i];
+            if ((uint32_t)id < (uint32_t)sg.table_rows) key = ((uint64_t)(uint32_t)id << 32) | (uint32_t)i;
+            else if (segs.id_err) atomicAdd(segs.id_err, 1);
+        }
+        k[t] = key;
+    }
+    __syncthreads();
+    for (int size = 2; size <= SORT_CHUNK; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const int lo = 2 * tid - (tid & (stride - 1));
+            const bool up = (lo & size) == 0;
+            const uint64_t x = k[lo], y = k[lo + stride];
+            if ((x > y) == up) { k[lo] = y; k[lo + stride] = x; }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int t = tid + h * (SORT_CHUNK / 2);
+        if (base + t < sg.n) sg.keys[0][base + t] = k[t];
+    }
+}
+
+// one pass of the merge sort: ordered runs of `run` keys are merged in pairs, src -> dst; every thread finds its cut of the
+// pair by bisection along its diagonal (merge path) and emits MERGE_PER_THREAD keys.  A run without a partner is copied.
+__global__ __launch_bounds__(256) void rows_merge_kernel(const RowsSegs segs, int run, int from)
+{
+    const RowsSeg &sg = segs.s[blockIdx.y];
+    const uint64_t *__restrict__ src = sg.keys[from];
+    uint64_t *__restrict__ dst = sg.keys[from ^ 1];
+    const int n = sg.n;
+    const int out0 = (blockIdx.x * 256 + threadIdx.x) * MERGE_PER_THREAD;
+    if (out0 >= n) return;
+    const int base = out0 / (2 * run) * (2 * run);
+    const int a_end = min(base + run, n), b_end = min(base + 2 * run, n);
+    const uint64_t *A = src + base, *Bk = src + a_end;
+    const int len_a = a_end - base, len_b = b_end - a_end, diag = out0 - base;
+    int lo = max(0, diag - len_b), hi = min(diag, len_a);
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (A[mid] < Bk[diag - 1 - mid]) lo = mid + 1; else hi = mid;
+    }
+    int ia = lo, ib = diag - lo;
+    for (int k = 0; k < MERGE_PER_THREAD && out0 + k < b_end; ++k) {
+        const bool take_a = ib >= len_b || (ia < len_a && A[ia] < Bk[ib]);
+        dst[out0 + k] = take_a ? A[ia++] : Bk[ib++];
+    }
+}
+
+// the arithmetic of adagrad_kernel (okge_misc.hip) at weight_decay = 0, element for element: no decay term at all
+__device__ __forceinline__ void adagrad1_rows(float &p, float g, float &s, float lr, float eps)
+{
+    s = fmaf(g, g, s);
+    p = p - lr * (g / (sqrtf(s) + eps));
+}
+
+// V floats per access (4: 16-byte loads and stores; 1: row lengths / leading dimensions / bases that do not allow them).
+// `lanes` lanes share the head of one run of equal ids: each walks the run for its columns, adding the gradient rows in
+// ascending position, and updates its columns of the table row.  Runs are short in training batches (a candidate list names
+// an entity once, a batch repeats a prefix entity a few times), so a lane's chain is a handful of dependent loads; several
+// runs are in flight per wave (64 / lanes) and the waves of a CU hide the rest.
+template <int V>
+__device__ __forceinline__ void rows_update_run(const RowsSeg &sg, const uint64_t *__restrict__ keys, int i, uint32_t id, uint32_t pos,
+                                                int lane, int lanes, float lr, float eps)
+{
+    const int cols = sg.row_len / V;
+    const int64_t ldg = sg.ld_g / V;
+    const size_t prow = (size_t)id * cols;
+    for (int c = lane; c < cols; c += lanes) {
+        if constexpr (V == 4) {
+            float4 *p4 = reinterpret_cast<float4 *>(sg.p), *s4 = reinterpret_cast<float4 *>(sg.s);
+            const float4 *g4 = reinterpret_cast<const float4 *>(sg.g);
+            float4 pv = p4[prow + c], sv = s4[prow + c];
+            float4 acc = g4[(size_t)pos * ldg + c];
+            for (int j = i + 1; j < sg.n; ++j) {
+                const uint64_t kj = keys[j];
+                if ((uint32_t)(kj >> 32) != id) break;
+                const float4 b = g4[(size_t)(uint32_t)kj * ldg + c];
+                acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
+            }
+            adagrad1_rows(pv.x, acc.x, sv.x, lr, eps);
+            adagrad1_rows(pv.y, acc.y, sv.y, lr, eps);
+            adagrad1_rows(pv.z, acc.z, sv.z, lr, eps);
+            adagrad1_rows(pv.w, acc.w, sv.w, lr, eps);
+            p4[prow + c] = pv;
+            s4[prow + c] = sv;
+        } else {
+            float pv = sg.p[prow + c], sv = sg.s[prow + c];
+            float acc = sg.g[(size_t)pos * ldg + c];
+            for (int j = i + 1; j < sg.n; ++j) {
+                const uint64_t kj = keys[j];
+                if ((uint32_t)(kj >> 32) != id) break;
+                acc += sg.g[(size_t)(uint32_t)kj * ldg + c];
+            }
+            adagrad1_rows(pv, acc, sv, lr, eps);
+            sg.p[prow + c] = pv;
+            sg.s[prow + c] = sv;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void rows_update_kernel(const RowsSegs segs, int sorted_in, float lr, float eps)
+{
+    const RowsSeg &sg = segs.s[blockIdx.y];
+    const uint64_t *__restrict__ keys = sg.keys[sorted_in];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int i = t >> sg.lane_shift, lane = t & ((1 << sg.lane_shift) - 1);
+    if (i >= sg.n) return;
+    const uint64_t key = keys[i];
+    if (key == KEY_SKIP) return;                                                  // id outside the table: counted, never written
+    const uint32_t id = (uint32_t)(key >> 32);
+    if (i > 0 && (uint32_t)(keys[i - 1] >> 32) == id) return;                     // not the head of its run
+    if (sg.vec) rows_update_run<4>(sg, keys, i, id, (uint32_t)key, lane, 1 << sg.lane_shift, lr, eps);
+    else rows_update_run<1>(sg, keys, i, id, (uint32_t)key, lane, 1 << sg.lane_shift, lr, eps);
+}
+
+}  // namespace
+
+hipError_t launch_rows_gather(const RowsGather &a, hipStream_t st)
+{
+    const int rows = a.N + 2 * (a.n_po + a.n_sp);
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rows_gather_kernel, dim3(rows), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+// keys[0] / keys[1] of every segment: n keys each.  Returns in *sorted_in which of the two holds the ordered keys.
+hipError_t launch_rows_sort(const RowsSegs &segs, int *sorted_in, hipStream_t st)
+{
+    int n_max = 0;
+    for (int k = 0; k < segs.n_segs; ++k) n_max = std::max(n_max, segs.s[k].n);
+    *sorted_in = 0;
+    if (n_max <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rows_sort_chunk_kernel, dim3((n_max + SORT_CHUNK - 1) / SORT_CHUNK, segs.n_segs), dim3(SORT_CHUNK / 2), 0, st, segs);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    const int per_block = 256 * MERGE_PER_THREAD;
+    for (int64_t run = SORT_CHUNK; run < n_max; run <<= 1) {                       // (a shorter segment's late passes are copies)
+        hipLaunchKernelGGL(rows_merge_kernel, dim3((n_max + per_block - 1) / per_block, segs.n_segs), dim3(256), 0, st, segs, (int)run,
+                           *sorted_in);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        *sorted_in ^= 1;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_rows_update(const RowsSegs &segs, int sorted_in, float lr, float eps, hipStream_t st)
+{
+    int64_t threads = 0;
+    for (int k = 0; k < segs.n_segs; ++k) threads = std::max<int64_t>(threads, (int64_t)segs.s[k].n << segs.s[k].lane_shift);
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rows_update_kernel, dim3((unsigned)((threads + 255) / 256), segs.n_segs), dim3(256), 0, st, segs, sorted_in, lr, eps);
+    return hipGetLastError();
+}
+
+}  // namespace okge

@@ -151,6 +151,28 @@ def _i32(t, dev):
     return t
 
 
+def occurrence_ids(dev, cand_ids, cand_first, n, po_obj, sp_subj, po_rel, sp_rel, out=None):
+    """(ids_e, ids_r) int32 on the device: [candidate ids | po_obj | sp_subj] and [po_rel | sp_rel] -- the table row every
+    occurrence row of okge_train_forward_backward(OKGE_TRAIN_ROW_GRADS) belongs to.  Index plumbing on the device, no host
+    read; `out` = (ids_e, ids_r) buffers to fill in place (a captured graph refills them on replay)."""
+    n_po = 0 if po_obj is None else int(po_obj.numel())
+    n_sp = 0 if sp_subj is None else int(sp_subj.numel())
+    if out is None:
+        out = (torch.empty(n + n_po + n_sp, dtype=torch.int32, device=dev), torch.empty(n_po + n_sp, dtype=torch.int32, device=dev))
+    ids_e, ids_r = out
+    if cand_ids is None:
+        torch.arange(cand_first, cand_first + n, dtype=torch.int32, device=dev, out=ids_e[:n])
+    else:
+        ids_e[:n].copy_(_i32(cand_ids, dev))
+    if n_po:
+        ids_e[n:n + n_po].copy_(_i32(po_obj, dev))
+        ids_r[:n_po].copy_(_i32(po_rel, dev))
+    if n_sp:
+        ids_e[n + n_po:].copy_(_i32(sp_subj, dev))
+        ids_r[n_po:].copy_(_i32(sp_rel, dev))
+    return ids_e, ids_r
+
+
 class HotPath:
     """Owns the scratch workspace for one device and issues the C-ABI calls on torch's current stream."""
 
@@ -175,6 +197,8 @@ class HotPath:
             need = int(self.lib.okge_score_workspace_bytes(B, d))
         elif kind == "lse":
             need = int(self.lib.okge_lse_workspace_bytes(B, n_cand, d))
+        elif kind == "train_rows":
+            need = int(self.lib.okge_train_row_grads_workspace_bytes(B, n_cand, d))
         else:
             need = int(self.lib.okge_train_workspace_bytes(B, n_cand, d))
         if need == 0:
@@ -247,14 +271,19 @@ class HotPath:
 
     def forward_backward(self, E, R, scorer, batch: PrefixBatch, dE, dR, loss="bce", label_smoothing=0.0,
                          normalizer=None, loss_out=None, scores=None, grads_zero=False, loss_only=False,
-                         distinct_prefix_rows=False, clear_grads=False):
+                         distinct_prefix_rows=False, clear_grads=False, row_grads=False):
         """Fused forward + loss + backward; accumulates into dE / dR (clear_grads: into whatever-they-held buffers that the
-        call itself clears, okge.h OKGE_TRAIN_CLEAR_GRADS); returns the summed loss as a device double[1] tensor (no host sync)."""
+        call itself clears, okge.h OKGE_TRAIN_CLEAR_GRADS); returns the summed loss as a device double[1] tensor (no host sync).
+        row_grads: dE (N + B, d) / dR (B, d) are occurrence-row buffers, every row stored once (okge.h OKGE_TRAIN_ROW_GRADS)."""
         self._check(batch, E, R)
         pb, c, keep = self._batch(batch)
         t = self._tables(E, R, scorer)
         B, n = batch.B, c.n
-        ws = self.workspace(B, n, t.d)
+        if row_grads:
+            if loss_only or dE is None or dR is None or tuple(dE.shape) != (n + B, t.d) or tuple(dR.shape) != (B, t.d) \
+                    or not dE.is_contiguous() or not dR.is_contiguous():
+                raise N.OkgeError(f"row_grads: dE must be a contiguous ({n + B}, {t.d}) and dR a ({B}, {t.d}) fp32 buffer")
+        ws = self.workspace(B, n, t.d, "train_rows" if row_grads else "train")
         pos, keep_pos = self._positives(batch)
         if normalizer is None:
             normalizer = float(B) * float(n)
@@ -266,7 +295,7 @@ class HotPath:
             (N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0) | (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) |
             (N.OKGE_TRAIN_UNIQUE_CANDIDATES if batch.cand_unique else 0) |
             (N.OKGE_TRAIN_DISTINCT_PREFIX_ROWS if distinct_prefix_rows else 0) |
-            (N.OKGE_TRAIN_CLEAR_GRADS if clear_grads else 0),
+            (N.OKGE_TRAIN_CLEAR_GRADS if clear_grads else 0) | (N.OKGE_TRAIN_ROW_GRADS if row_grads else 0),
             loss_out.data_ptr(), _ptr(dE), _ptr(dR),
             None if scores is None else scores.data_ptr(), 0 if scores is None else scores.stride(0),
             ws.data_ptr(), self._ws_bytes, self._stream()), "okge_train_forward_backward")
@@ -549,6 +578,33 @@ class HotPath:
                 a.rows = int(t[5]) if len(t) > 5 else 0          # 0 all rows, 1 the unstamped rows only, 2 the stamped rows only
         N.check(self.lib.okge_adagrad_multi(arr, len(tensors), float(lr), float(weight_decay), float(eps), self._stream()),
                 "okge_adagrad_multi")
+
+    def adagrad_rows(self, p, state_sum, ids, g, lr, eps=1e-8, second=None):
+        """okge_adagrad_rows: the occurrence rows g (n, row_len) of the int32 device ids are coalesced per id in ascending
+        position and the named rows of p / state_sum take one Adagrad step (weight_decay = 0); every other row is left alone.
+        second: another (p, state_sum, ids, g) for the same launches."""
+        tensors = [(p, state_sum, ids, g)] + ([tuple(second)] if second is not None else [])
+        arr = (N.RowsTensor * len(tensors))()
+        for a, (p_, s_, i_, g_) in zip(arr, tensors):
+            n = int(i_.numel())
+            if i_.dtype != torch.int32 or not i_.is_contiguous() or i_.device != self.device:
+                raise N.OkgeError("adagrad_rows: ids must be a contiguous int32 tensor on the engine's device")
+            for x in (p_, s_, g_):
+                if x.dtype != torch.float32 or x.device != self.device:
+                    raise N.OkgeError("adagrad_rows: fp32 tensors on the engine's device")
+            if p_.dim() != 2 or not p_.is_contiguous() or not s_.is_contiguous() or s_.shape != p_.shape:
+                raise N.OkgeError("adagrad_rows: p and state_sum must be contiguous (rows, row_len) tensors of one shape")
+            if n and (g_.dim() != 2 or g_.shape[0] != n or g_.shape[1] != p_.shape[1] or g_.stride(1) != 1):
+                raise N.OkgeError("adagrad_rows: g must hold one row of row_len floats per id, last dim contiguous")
+            a.p, a.state_sum, a.ids, a.g = p_.data_ptr(), s_.data_ptr(), i_.data_ptr(), g_.data_ptr()
+            a.ld_g = int(g_.stride(0)) if n > 1 else int(p_.shape[1])
+            a.n, a.table_rows, a.row_len = n, int(p_.shape[0]), int(p_.shape[1])
+        ns = [int(a.n) for a in arr] + [0]
+        need = int(self.lib.okge_adagrad_rows_workspace_bytes(ns[0], ns[1]))
+        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < need:
+            self._rows_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        N.check(self.lib.okge_adagrad_rows(arr, len(tensors), float(lr), float(eps), self._rows_ws.data_ptr(), self._rows_ws.numel(),
+                                           self._stream()), "okge_adagrad_rows")
 
     @staticmethod
     def lazy_tensors(tensors):

@@ -1,5 +1,6 @@
 """`OkgeAdagrad`: torch.optim.Adagrad's dense update (the optimizer OptimRegime builds for every reference config,
-utils/optim.py:139-160) on the HIP sweep kernel -- one launch per PAIR of parameters instead of ATen's foreach chain.
+utils/optim.py:139-160) on the HIP sweep kernel -- one launch per PAIR of parameters instead of ATen's foreach chain -- and
+its sparse branch (row-sparse gradients at weight_decay = 0) on okge_adagrad_rows.
 
 The reference names its optimizer in YAML (`optimization_config.optimizer`) and looks the class up in
 `torch.optim.__dict__` (utils/optim.py:143-144), constructing it from the PREVIOUS optimizer's param_groups -- which is
@@ -55,19 +56,26 @@ class OkgeAdagrad(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         for group in self.param_groups:
-            todo = []
+            todo, rows = [], []
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 g = p.grad
-                if g.is_sparse or p.dtype != torch.float32 or g.dtype != torch.float32 or p.device.type != "cuda" or \
-                        not p.is_contiguous():
-                    raise RuntimeError("OkgeAdagrad updates dense contiguous fp32 parameters on the GPU (model_config.sparse: false)")
+                if g.is_sparse and group["weight_decay"] != 0:      # (torch.optim.Adagrad's own refusal and text)
+                    raise RuntimeError("weight_decay option is not compatible with sparse gradients")
+                if p.dtype != torch.float32 or g.dtype != torch.float32 or p.device.type != "cuda" or not p.is_contiguous():
+                    raise RuntimeError("OkgeAdagrad updates dense contiguous fp32 parameters on the GPU")
+                if g.is_sparse and (p.dim() != 2 or g.sparse_dim() != 1):
+                    raise RuntimeError("OkgeAdagrad takes row-sparse gradients (one sparse dimension) of 2-d parameters")
                 st = self.state[p]
                 if st["sum"].device != p.device:
                     st["sum"] = st["sum"].to(p.device)
                 st["step"] += 1
-                todo.append((p, g if g.is_contiguous() else g.contiguous(), st))
+                if g.is_sparse:                # (uncoalesced, as nn.Embedding(sparse=True) / AddLossModule(sparse_grads=True) leave it)
+                    rows.append((p, g, st))
+                else:
+                    todo.append((p, g if g.is_contiguous() else g.contiguous(), st))
+            self._step_rows(group, rows)
             if not todo:
                 continue
             if group["lr_decay"] != 0:
@@ -87,6 +95,32 @@ class OkgeAdagrad(torch.optim.Optimizer):
                     eng.adagrad(p0.data, g0, s0["sum"], clrs[i], group["weight_decay"], group["eps"], zero_grad=False)
                     i += 1
         return loss
+
+    def _step_rows(self, group, rows):
+        """torch.optim.Adagrad's sparse branch on okge_adagrad_rows: the value rows are coalesced per index in ascending
+        position and only the rows they name are updated; `sum` stays dense (the state layout does not change).  Two
+        parameters of one learning rate share the launches."""
+        i = 0
+        while i < len(rows):
+            p0, g0, s0 = rows[i]
+            clr = group["lr"] / (1 + (float(s0["step"]) - 1) * group["lr_decay"]) if group["lr_decay"] != 0 else group["lr"]
+            second = None
+            if i + 1 < len(rows):
+                p1, g1, s1 = rows[i + 1]
+                clr1 = group["lr"] / (1 + (float(s1["step"]) - 1) * group["lr_decay"]) if group["lr_decay"] != 0 else group["lr"]
+                if clr1 == clr:
+                    second = (p1.data, s1["sum"], _row_ids(g1), _row_values(g1))
+            self._engine(p0.device).adagrad_rows(p0.data, s0["sum"], _row_ids(g0), _row_values(g0), clr, group["eps"], second=second)
+            i += 2 if second is not None else 1
+
+
+def _row_ids(g):
+    return g._indices()[0].to(torch.int32).contiguous()
+
+
+def _row_values(g):
+    v = g._values()
+    return v if v.dim() == 2 and v.stride(1) == 1 else v.reshape(v.shape[0], -1).contiguous()
 
 
 import sys as _sys

@@ -18,10 +18,21 @@ class FusedTrainStep:
     def __init__(self, E: torch.Tensor, R: torch.Tensor, scorer: str, loss: str = "bce", lr: float = 0.3,
                  weight_decay: float = 1e-10, eps: float = 1e-8, label_smoothing: float = 0.0,
                  input_dropout: float = 0.0, relation_input_dropout: float = 0.0, seed: int = 0, engine=None,
-                 grad_clip: float = 0.0, accumulate: int = 1):
+                 grad_clip: float = 0.0, accumulate: int = 1, sparse: bool = False):
         """Defaults follow config/fb15k237/fb15k237-complex-kge.yaml and the optimizer OptimRegime actually
-        builds (utils/optim.py:29,139-160): Adagrad(lr, weight_decay=1e-10, eps=1e-8 leaked from Adam)."""
+        builds (utils/optim.py:29,139-160): Adagrad(lr, weight_decay=1e-10, eps=1e-8 leaked from Adam).
+
+        sparse (model_config.sparse, model.py:390-391): gradients stay in occurrence rows and only the table rows a batch
+        names are updated (okge_adagrad_rows) -- no dense dE / dR, nothing per step that grows with the tables.  Needs
+        weight_decay = 0, as torch's sparse Adagrad does; no clipping (torch cannot clip sparse gradients), no accumulation."""
         N.refuse_bias_scorer(scorer, type(self).__name__)
+        self.sparse = bool(sparse)
+        if self.sparse:
+            if weight_decay != 0:
+                raise ValueError("weight_decay option is not compatible with sparse gradients")
+            if float(grad_clip or 0.0) > 0 or int(accumulate) > 1:
+                raise NotImplementedError("FusedTrainStep(sparse=True): grad_clip and accumulate need dense gradients "
+                                          "(torch.nn.utils.clip_grad_norm_ refuses sparse gradients)")
         self.E, self.R = E, R
         self.scorer, self.loss = scorer, loss
         self.lr, self.weight_decay, self.eps = lr, weight_decay, eps
@@ -29,7 +40,9 @@ class FusedTrainStep:
         self.input_dropout, self.relation_input_dropout = input_dropout, relation_input_dropout
         self.seed = seed
         self.engine = engine or H.HotPath(E.device)
-        self.dE, self.dR = torch.zeros_like(E), torch.zeros_like(R)       # dense .grad (model_config.sparse False)
+        # dense .grad (model_config.sparse False); the sparse step keeps per-shape occurrence-row buffers instead (_row_buffers)
+        self.dE, self.dR = (None, None) if self.sparse else (torch.zeros_like(E), torch.zeros_like(R))
+        self._rows = {}
         self.sumE, self.sumR = torch.zeros_like(E), torch.zeros_like(R)   # Adagrad state 'sum' (init 0)
         self.steps = 0
         self.step_dev = None              # device step counter, attached by GraphedTrainStep
@@ -45,13 +58,30 @@ class FusedTrainStep:
         # bit-identical, S-FB 0.1302-0.1310 vs 0.1308-0.1313 ms/step -- under the 3 % bar, so the two-call sequence stays the default
         import os
         d = E.shape[1]
-        self.fuse_update = (os.environ.get("OKGE_FUSED_UPDATE", "0") == "1" and self.grad_clip == 0 and self.accumulate == 1
+        self.fuse_update = (not self.sparse and os.environ.get("OKGE_FUSED_UPDATE", "0") == "1" and self.grad_clip == 0 and self.accumulate == 1
                             and d % (4 if scorer == "distmult" else 8) == 0)
         self._fuse_now, self._fused_done, self._opt = False, False, None
 
     def state_tensors(self):
         """every tensor a step mutates (GraphedTrainStep snapshots them around its warm-up)"""
+        if self.sparse:                   # (the row buffers are written whole before they are read, every step)
+            return [self.E, self.R, self.sumE, self.sumR]
         return [self.E, self.R, self.dE, self.dR, self.sumE, self.sumR]
+
+    # -- sparse step: occurrence rows ------------------------------------------------------------------------------------
+    def _row_buffers(self, batch: H.PrefixBatch):
+        """per shape (N, n_po, n_sp): gradient rows gE (N + B, d) / gR (B, d) and the occurrence ids idE = [candidate ids |
+        po_obj | sp_subj], idR = [po_rel | sp_rel] -- persistent storage, so a captured graph refills and reuses it"""
+        n, n_po, n_sp = batch.n_candidates, batch.n_po, batch.n_sp
+        key = (n, n_po, n_sp)
+        rb = self._rows.get(key)
+        if rb is None:
+            dev, d, B = self.E.device, self.E.shape[1], n_po + n_sp
+            rb = self._rows[key] = dict(gE=torch.empty((n + B, d), dtype=torch.float32, device=dev),
+                                        gR=torch.empty((B, d), dtype=torch.float32, device=dev),
+                                        idE=torch.empty(n + B, dtype=torch.int32, device=dev),
+                                        idR=torch.empty(B, dtype=torch.int32, device=dev))
+        return rb
 
     def _set_dropout(self, batch: H.PrefixBatch, training=True):
         pe = self.input_dropout if training else 0.0
@@ -98,6 +128,15 @@ class FusedTrainStep:
         pos.row, pos.col, pos.nnz = batch.pos_row.data_ptr(), batch.pos_col.data_ptr(), batch.nnz
         eng = self.engine
         ws = eng.workspace(n_po + n_sp, n, t.d)
+        if self.sparse:
+            rb = self._cur_rows
+            ws = eng.workspace(n_po + n_sp, n, t.d, "train_rows")
+            N.check(eng.lib.okge_train_forward_backward(
+                ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), ctypes.byref(pos), N.LOSSES[self.loss], float(self.label_smoothing),
+                float(normalizer if normalizer is not None else (n_po + n_sp) * n), N.OKGE_TRAIN_ROW_GRADS, self.loss_out.data_ptr(),
+                rb["gE"].data_ptr(), rb["gR"].data_ptr(), None, 0, ws.data_ptr(), eng._ws_bytes, eng._stream()),
+                "okge_train_forward_backward")
+            return self.loss_out
         flags = (N.OKGE_TRAIN_GRADS_ZERO if self._grads_zero else 0) | (N.OKGE_TRAIN_UNIQUE_CANDIDATES if batch.cand_unique else 0)
         if self._fuse_now:
             # the whole step incl. the Adagrad update in ONE library call (okge_train_step): the entity sweep rides in the
@@ -132,6 +171,17 @@ class FusedTrainStep:
 
     def forward_backward(self, batch: H.PrefixBatch, normalizer=None):
         """trainer.py:206-234.  Returns the summed loss (device double[1], valid after stream sync)."""
+        if self.sparse:
+            rb = self._cur_rows = self._row_buffers(batch)
+            H.occurrence_ids(self.E.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
+                             batch.po_rel, batch.sp_rel, out=(rb["idE"], rb["idR"]))
+            self._last_full = False
+            if isinstance(self.engine, H.HotPath) and self._plain(batch):
+                return self._fast_forward_backward(batch, normalizer)
+            self._set_dropout(batch)
+            return self.engine.forward_backward(self.E, self.R, self.scorer, batch, rb["gE"], rb["gR"], loss=self.loss,
+                                                label_smoothing=self.label_smoothing, normalizer=normalizer,
+                                                loss_out=self.loss_out, row_grads=True)
         if self._dE_stale and not (self._grads_zero and self._covers_all_rows(batch)):
             self.dE.zero_()               # a sampled candidate list leaves rows untouched: they must read as zero
             self._dE_stale = False
@@ -146,7 +196,13 @@ class FusedTrainStep:
     def optimizer_step(self, lazy_zero=False):
         """trainer.py:240-244: optimizer.step() then zero_grad() -- one sweep per table.  lazy_zero (used by step()
         after a 1-vs-all batch): the entity gradient is not cleared here because the next 1-vs-all step overwrites
-        every row it uses; it is cleared on demand if a sampled candidate list comes next."""
+        every row it uses; it is cleared on demand if a sampled candidate list comes next.
+        Sparse step: torch's sparse Adagrad on the occurrence rows of the last forward_backward -- nothing to clear."""
+        if self.sparse:
+            rb = self._cur_rows
+            self.engine.adagrad_rows(self.E, self.sumE, rb["idE"], rb["gE"], self.lr, self.eps,
+                                     second=(self.R, self.sumR, rb["idR"], rb["gR"]))
+            return
         self.engine.adagrad2(self.E, self.dE, self.sumE, self.R, self.dR, self.sumR, self.lr, self.weight_decay,
                              self.eps, zero_grad=2 if lazy_zero else 1)
         self._dE_stale = bool(lazy_zero)

@@ -32,8 +32,12 @@ class _FusedLossFn(torch.autograd.Function):
     if they differ (one launch that reads a single float when they agree; before: two passes over 11.6 MB)."""
 
     @staticmethod
-    def forward(ctx, e_weight, r_weight, loss, g_e, g_r, engine, applied):
+    def forward(ctx, e_weight, r_weight, loss, g_e, g_r, engine, applied, row_ids):
+        """row_ids: None (g_e / g_r are dense table gradients) or the occurrence ids (ids_e, ids_r) of gradient ROWS
+        (AddLossModule(sparse_grads=True)): backward then hands autograd uncoalesced sparse tensors, as the backward of
+        nn.Embedding(sparse=True) does (model.py:390-391)"""
         ctx.g_e, ctx.g_r, ctx.engine, ctx.applied = g_e, g_r, engine, applied
+        ctx.row_ids, ctx.shapes = row_ids, (e_weight.shape, r_weight.shape)
         return loss.to(torch.float32).reshape(())               # (the cast already yields a fresh tensor)
 
     @staticmethod
@@ -41,7 +45,11 @@ class _FusedLossFn(torch.autograd.Function):
         alpha = grad_out.reshape(1).to(torch.float32).contiguous()
         g_e, g_r, ctx.g_e, ctx.g_r = ctx.g_e, ctx.g_r, None, None   # no reference left behind: AccumulateGrad then TAKES the
         ctx.engine.rescale_gradients_(g_e, g_r, alpha, ctx.applied) # buffers as .grad instead of copying them (an 11.6 MB
-        return g_e, g_r, None, None, None, None, None               # copy per step at FB15k-237)
+        if ctx.row_ids is not None:                                 # copy per step at FB15k-237)
+            (ids_e, ids_r), ctx.row_ids = ctx.row_ids, None         # (the rescale above acted on the value rows)
+            g_e = torch.sparse_coo_tensor(ids_e[None].long(), g_e, ctx.shapes[0])
+            g_r = torch.sparse_coo_tensor(ids_r[None].long(), g_r, ctx.shapes[1])
+        return g_e, g_r, None, None, None, None, None, None
 
 
 def _flat(t):
@@ -98,12 +106,21 @@ class AddLossModule(nn.Module):
     returns None in its place: the reference's Trainer reads the predictions only in evaluation (trainer.py:258-272), and
     the (B, N) block is the one thing the fused training kernels never need to write (29.8 MB per step at FB15k-237)."""
 
-    def __init__(self, model, loss, bce_label_smoothing=0.0, training_outputs=True):
+    def __init__(self, model, loss, bce_label_smoothing=0.0, training_outputs=True, sparse_grads=False):
         super().__init__()
         self.model = model
         self.loss = loss
         self.bce_label_smoothing = bce_label_smoothing
         self.training_outputs = training_outputs
+        # sparse_grads (not in the reference's signature; what model_config.sparse selects there, model.py:390-391): in training
+        # mode the two embedding weights receive UNCOALESCED sparse gradients -- one value row per candidate / prefix occurrence,
+        # stored by the fused step -- for an optimizer with a sparse branch (OkgeAdagrad, weight_decay = 0)
+        self.sparse_grads = bool(sparse_grads)
+        if self.sparse_grads and (hasattr(model, "entity_token_ids") or getattr(model, "fused_step_model", False)
+                                  or getattr(model, "encode_in_torch", False) or not hasattr(model, "entity_embedding")
+                                  or getattr(model, "scorer_name", None) not in ("complex", "distmult")):
+            raise NotImplementedError("sparse_grads=True is built for the ComplEx / DistMult lookup models without batch-norm, "
+                                      "projection or normalisation (the encoded-row and token models return dense gradients)")
         if isinstance(loss, (BCEWithLogitsLoss, KLDivLoss)) and loss.reduction != "sum":
             # trainer.py:106 sums whatever the loss returns and scripts/train.py builds both losses with reduction='sum';
             # the fused kernels produce exactly that sum -- any other reduction would be silently different
@@ -188,8 +205,13 @@ class AddLossModule(nn.Module):
             # a contiguous candidate range: the call stores the candidate rows and clears the rest itself (all of dR, the
             # reserved rows in front of the candidates) inside its first launch -- fresh buffers, no fill launches.
             # An id list: candidate rows accumulate, so the buffers start from zero.
-            clear = batch.cand_ids is None
-            g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
+            clear = batch.cand_ids is None and not self.sparse_grads
+            row_ids = None
+            if self.sparse_grads:
+                g_e, g_r = E.new_empty((n + B, E.shape[1])), R.new_empty((B, R.shape[1]))
+                row_ids = H.occurrence_ids(dev, batch.cand_ids, batch.cand_first, n, batch.po_obj, batch.sp_subj, batch.po_rel, batch.sp_rel)
+            else:
+                g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
             # the factor the Trainer will apply (trainer.py:221: loss / normalizer_loss, normalizer_loss = B x N,
             # dataset.py:935) goes into the fused step; _FusedLossFn.backward checks it against what autograd delivers
             # (torch divides a fp32 tensor by a Python number as a multiplication by fp32(1) / fp32(number), forward and
@@ -197,9 +219,10 @@ class AddLossModule(nn.Module):
             #  reciprocal is exactly that)
             applied = np.float32(1.0) / np.float32(float(B) * float(n))
             loss = eng.forward_backward(E, R, m.scorer_name, batch, g_e, g_r, loss=kind, label_smoothing=smoothing,
-                                        normalizer=1.0 / float(applied), scores=all_outputs, grads_zero=True, clear_grads=clear)
+                                        normalizer=1.0 / float(applied), scores=all_outputs, grads_zero=True, clear_grads=clear,
+                                        row_grads=self.sparse_grads)
             result = _FusedLossFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, g_e, g_r, eng,
-                                        float(applied))
+                                        float(applied), row_ids)
         else:
             loss = eng.forward_backward(m.E, m.R, m.scorer_name, batch, None, None, loss=kind, label_smoothing=smoothing,
                                         normalizer=1.0, scores=all_outputs, loss_only=True)
@@ -262,20 +285,29 @@ class AddLossModule(nn.Module):
         all_outputs = None
         if self.training_outputs:
             all_outputs = torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :n]
-        clear = cand is None
-        g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
+        clear = cand is None and not self.sparse_grads
+        row_ids = None
+        if self.sparse_grads:
+            g_e, g_r = E.new_empty((n + B, E.shape[1])), R.new_empty((B, R.shape[1]))
+            row_ids = H.occurrence_ids(dev, cand, first, n, po[1] if n_po else None, sp[0] if n_sp else None,
+                                      po[0] if n_po else None, sp[1] if n_sp else None)
+            flags = N.OKGE_TRAIN_ROW_GRADS
+        else:
+            g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
+            flags = N.OKGE_TRAIN_GRADS_ZERO | (N.OKGE_TRAIN_CLEAR_GRADS if clear else 0)
         applied = np.float32(1.0) / np.float32(float(B) * float(n))           # (see forward below)
         loss = torch.empty(1, dtype=torch.float64, device=dev)
-        ws = eng.workspace(B, n, t.d)
+        ws = eng.workspace(B, n, t.d, "train_rows" if self.sparse_grads else "train")
         smoothing = self.bce_label_smoothing if kind == "bce" else 0.0
         N.check(eng.lib.okge_train_forward_backward(
             ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), ctypes.byref(pos), N.LOSSES[kind], float(smoothing), 1.0 / float(applied),
-            N.OKGE_TRAIN_GRADS_ZERO | (N.OKGE_TRAIN_CLEAR_GRADS if clear else 0), loss.data_ptr(), g_e.data_ptr(), g_r.data_ptr(),
+            flags, loss.data_ptr(), g_e.data_ptr(), g_r.data_ptr(),
             None if all_outputs is None else all_outputs.data_ptr(), 0 if all_outputs is None else all_outputs.stride(0),
             ws.data_ptr(), eng._ws_bytes, eng._stream()), "okge_train_forward_backward")
         if CALLER_THREAD_BACKWARD and torch.autograd.is_multithreading_enabled():
             torch.autograd.set_multithreading_enabled(False)                   # (see forward below)
-        result = _FusedLossFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, g_e, g_r, eng, float(applied))
+        result = _FusedLossFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, g_e, g_r, eng, float(applied),
+                                    row_ids)
         return result, hook_loss, all_outputs
 
     def _variant_result(self, m, batch, kind, smoothing, want_grad, all_outputs, epoch, all_entities, per_direction):
