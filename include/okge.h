@@ -574,6 +574,48 @@ size_t okge_adagrad_rows_workspace_bytes(int64_t n0, int64_t n1);      /* n of t
 int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float lr, float eps, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* ---- row-sparse Adagrad WITH weight decay: the decay-only updates of the rows no batch names, deferred ------------------------
+ * The reference trains with weight_decay = 1e-10 on DENSE Adagrad (utils/optim.py:139-160): every row of a table moves in every
+ * step, by its own decay term when no gradient reached it.  That update depends on the row's (p, state_sum) alone, so it can be
+ * applied later, all pending steps at once in registers -- the scheme of okge_adagrad_lazy above, here for the tables the
+ * row-sparse step updates.  Per table row_steps[table_rows] (int32, start 0) = optimizer steps the row has seen;
+ * counters[0] = T, the steps taken, counters[1] = scratch (both start 0; one pair for all tensors).  One training step:
+ *   okge_rows_catch_up        BEFORE anything reads a row (the gather of OKGE_TRAIN_ROW_GRADS): every row an id of the lists names
+ *                   with row_steps < T takes its T - row_steps pending decay-only steps and stands at T.  One owner per row
+ *                   (integer atomicMax claim on row_steps), however many occurrences name it; ids outside the table are skipped.
+ *   okge_adagrad_rows_decay   (a) coalescing exactly as okge_adagrad_rows: per distinct id its occurrence rows are added in
+ *                   ASCENDING occurrence position, sequentially in fp32; (b) on the coalesced row g the dense kernel's expression
+ *                   WITH the decay term, okge_adagrad_step's arithmetic element for element -- g' = fma(wd, p, g),
+ *                   sum = fma(g', g', sum), p = p - lr * (g' / (sqrt(sum) + eps)), correctly rounded sqrt and division -- and
+ *                   row_steps[id] = T + 1.  A LAGGING row -- named by the lists with row_steps[id] < T, because the caller skipped
+ *                   the catch-up -- first replays its T - row_steps[id] pending decay-only steps, so the call is correct on its
+ *                   own (the caller's forward then read a stale row: that is the caller's business).  Ids outside the table are
+ *                   skipped and counted (okge_id_errors), nothing is written for them.  (c) the due slice: rows with
+ *                   r % window == T % window and row_steps[r] < T + 1 take their pending decay-only steps up to T + 1 (the rows
+ *                   (b) wrote are skipped); then T += 1 on the device.  n = 0 still runs (c).
+ *   okge_adagrad_lazy(OKGE_LAZY_FLUSH)   every row to T, before anything else reads the tables (evaluation, checkpoints, the
+ *                   host).  Pass state_sum as the lazy tensor's g: no row is stamped, so it is never read.
+ * After a flush, tables and accumulators are BIT-IDENTICAL to okge_adagrad_step on the densified gradient at the same
+ * weight_decay, whatever the window (same operations per element in the same order), provided the densified gradient itself is
+ * order-free.  Between steps a row no batch named may lag by up to window - 1 decay-only steps.  lr, weight_decay and eps must
+ * not change while steps are pending (flush first).  No host synchronisation, no count read back; T lives on the device so that
+ * a captured HIP graph replays correctly.
+ * Needs row_len % 4 == 0, ld_g % 4 == 0 and 16-byte aligned p / state_sum / g (else OKGE_ERR_UNSUPPORTED); n up to 2^20 per
+ * tensor; table_rows < 2^31.  p, state_sum, row_steps, table_rows and row_len are read whatever n is; ids / g may be NULL when
+ * n = 0, and okge_rows_catch_up does not read g.  Workspace of okge_adagrad_rows_decay: okge_adagrad_rows_workspace_bytes. */
+typedef struct okge_rows_decay_tensor {
+    float         *p, *state_sum;
+    const int32_t *ids;
+    const float   *g;
+    int64_t        ld_g;
+    int32_t       *row_steps;
+    int32_t        n, table_rows, row_len, _pad;
+} okge_rows_decay_tensor;
+int okge_rows_catch_up(const okge_rows_decay_tensor *tensors, int32_t n_tensors, const int32_t *counters, float lr, float weight_decay,
+                       float eps, void *stream);
+int okge_adagrad_rows_decay(const okge_rows_decay_tensor *tensors, int32_t n_tensors, int32_t *counters, int32_t window, float lr,
+                            float weight_decay, float eps, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the whole step in one call: okge_train_forward_backward + the dense Adagrad update of both tables ------------------
  * (Trainer.compute_one_batch's training branch end to end, trainer.py:217-257 with utils/optim.py:139-160.)  Same arithmetic,
  * element for element, as okge_train_forward_backward followed by okge_adagrad_step2(zero_grad = 2 or 1) -- tables and

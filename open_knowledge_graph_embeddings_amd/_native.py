@@ -53,6 +53,7 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_dataset_copy", "okge_dataset_close", "okge_encode_rows", "okge_scale_inplace", "okge_rescale_gradients", "okge_adagrad_step", "okge_adagrad_step2", "okge_id_errors", "okge_clip_grad_norm", "okge_merge_logsumexp", "okge_filtered_ranks", "okge_timing_enable",
            "okge_topk_workspace_bytes", "okge_topk_prefixes", "okge_topk_queries", "okge_topk_merge",
            "okge_train_row_grads_workspace_bytes", "okge_adagrad_rows", "okge_adagrad_rows_workspace_bytes",
+           "okge_rows_catch_up", "okge_adagrad_rows_decay",
            "okge_timing_reset", "okge_timing_collect"]
 
 
@@ -145,6 +146,11 @@ class RowsTensor(Structure):
                 ("n", c_int32), ("table_rows", c_int32), ("row_len", c_int32), ("_pad", c_int32)]
 
 
+class RowsDecayTensor(Structure):
+    _fields_ = [("p", c_void_p), ("state_sum", c_void_p), ("ids", c_void_p), ("g", c_void_p), ("ld_g", c_int64),
+                ("row_steps", c_void_p), ("n", c_int32), ("table_rows", c_int32), ("row_len", c_int32), ("_pad", c_int32)]
+
+
 class LazyTensor(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("state_sum", c_void_p), ("rows", c_int64), ("row_steps", c_void_p),
                 ("row_touched", c_void_p), ("row_len", c_int32), ("touched_stamp", c_int32)]
@@ -231,6 +237,11 @@ def lib():
     L.okge_adagrad_rows_workspace_bytes.argtypes = [c_int64, c_int64]
     L.okge_adagrad_rows.restype = c_int32
     L.okge_adagrad_rows.argtypes = [POINTER(RowsTensor), c_int32, c_float, c_float, c_void_p, c_size_t, c_void_p]
+    L.okge_rows_catch_up.restype = c_int32
+    L.okge_rows_catch_up.argtypes = [POINTER(RowsDecayTensor), c_int32, c_void_p, c_float, c_float, c_float, c_void_p]
+    L.okge_adagrad_rows_decay.restype = c_int32
+    L.okge_adagrad_rows_decay.argtypes = [POINTER(RowsDecayTensor), c_int32, c_void_p, c_int32, c_float, c_float, c_float, c_void_p,
+                                          c_size_t, c_void_p]
     L.okge_score_workspace_bytes.restype = c_size_t
     L.okge_score_workspace_bytes.argtypes = [c_int32, c_int32]
     L.okge_lse_workspace_bytes.restype = c_size_t

@@ -35,6 +35,8 @@ def _gather_rows(local, n_rows, group):
 
 def _full_tables(step):
     """(E, R, sumE, sumR) as full tables, whatever the step class."""
+    if hasattr(step, "flush"):                                    # deferred weight decay: rows may owe decay-only steps
+        step.flush()
     if hasattr(step, "ent_lo"):                                   # ShardedTrainStep: gather the row shards
         return (_gather_rows(step.E, step.n_ent, step.group), step.R, _gather_rows(step.sumE, step.n_ent, step.group),
                 step.sumR)
@@ -77,6 +79,8 @@ def load_reference_checkpoint(step, ckpt_or_path, reset_optimizer=False):
     lo, hi = (step.ent_lo, step.ent_hi) if hasattr(step, "ent_lo") else (0, E.shape[0])
     if E[lo:hi].shape != step.E.shape or R.shape != step.R.shape:
         raise ValueError(f"checkpoint tables {tuple(E.shape)}, {tuple(R.shape)} do not fit this model")
+    if hasattr(step, "flush"):                                    # deferred weight decay: no row may owe steps to the loaded tables
+        step.flush()
     step.E.copy_(E[lo:hi])
     step.R.copy_(R)
     if reset_optimizer:
@@ -92,6 +96,7 @@ def load_reference_checkpoint(step, ckpt_or_path, reset_optimizer=False):
         step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
         if float(group.get("lr_decay", 0)) != 0 or float(group.get("initial_accumulator_value", 0)) != 0:
             raise NotImplementedError("Adagrad lr_decay / initial_accumulator_value are not used by the reference configs")
-    step.dE.zero_()
-    step.dR.zero_()
+    if step.dE is not None:                                       # (the row-sparse step keeps no dense gradients)
+        step.dE.zero_()
+        step.dR.zero_()
     return ckpt

@@ -1611,6 +1611,24 @@ size_t okge_adagrad_rows_workspace_bytes(int64_t n0, int64_t n1)
     return 2 * rows_keys_bytes(n0) + 2 * rows_keys_bytes(n1);
 }
 
+// one segment per tensor with n > 0, its two key buffers cut from the workspace; steps: the table's row_steps (deferred decay) or null
+static void rows_segment(RowsSegs &segs, char *&ws, float *p, float *state_sum, const int32_t *ids, const float *g, int64_t ld_g, int32_t n,
+                         int32_t table_rows, int32_t row_len, int32_t *steps)
+{
+    RowsSeg &sg = segs.s[segs.n_segs++];
+    sg.p = p; sg.s = state_sum; sg.g = g; sg.ids = ids; sg.ld_g = ld_g;
+    sg.n = n; sg.table_rows = table_rows; sg.row_len = row_len; sg.steps = steps;
+    sg.keys[0] = reinterpret_cast<uint64_t *>(ws); ws += rows_keys_bytes(n);
+    sg.keys[1] = reinterpret_cast<uint64_t *>(ws); ws += rows_keys_bytes(n);
+    sg.vec = (row_len % 4 == 0 && ld_g % 4 == 0 &&
+              (reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(state_sum) | reinterpret_cast<uintptr_t>(g)) % 16 == 0) ? 1 : 0;
+    // lanes per run: one per 16-byte column group up to 16 (rows of 64 floats and more: 4 runs in flight per wave, each
+    // lane several independent column groups)
+    const int groups = sg.vec ? row_len / 4 : row_len;
+    sg.lane_shift = 0;
+    while (sg.lane_shift < 4 && (1 << sg.lane_shift) < groups) ++sg.lane_shift;
+}
+
 int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float lr, float eps, void *workspace, size_t workspace_bytes,
                       void *stream)
 {
@@ -1632,19 +1650,7 @@ int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float 
     char *ws = static_cast<char *>(workspace);
     for (int k = 0; k < n_tensors; ++k) {
         const okge_rows_tensor &x = tensors[k];
-        if (x.n == 0) continue;
-        RowsSeg &sg = segs.s[segs.n_segs++];
-        sg.p = x.p; sg.s = x.state_sum; sg.g = x.g; sg.ids = x.ids; sg.ld_g = x.ld_g;
-        sg.n = x.n; sg.table_rows = x.table_rows; sg.row_len = x.row_len;
-        sg.keys[0] = reinterpret_cast<uint64_t *>(ws); ws += rows_keys_bytes(x.n);
-        sg.keys[1] = reinterpret_cast<uint64_t *>(ws); ws += rows_keys_bytes(x.n);
-        sg.vec = (x.row_len % 4 == 0 && x.ld_g % 4 == 0 &&
-                  (reinterpret_cast<uintptr_t>(x.p) | reinterpret_cast<uintptr_t>(x.state_sum) | reinterpret_cast<uintptr_t>(x.g)) % 16 == 0) ? 1 : 0;
-        // lanes per run: one per 16-byte column group up to 16 (rows of 64 floats and more: 4 runs in flight per wave, each
-        // lane several independent column groups)
-        const int groups = sg.vec ? x.row_len / 4 : x.row_len;
-        sg.lane_shift = 0;
-        while (sg.lane_shift < 4 && (1 << sg.lane_shift) < groups) ++sg.lane_shift;
+        if (x.n > 0) rows_segment(segs, ws, x.p, x.state_sum, x.ids, x.g, x.ld_g, x.n, x.table_rows, x.row_len, nullptr);
     }
     segs.id_err = id_err_ptr();
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1657,6 +1663,82 @@ int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float 
         ScopedTimer tm("rows_update", st);
         if (hipError_t e = launch_rows_update(segs, sorted_in, lr, eps, st); e != hipSuccess) return fail_hip(e, "rows_update");
     }
+    return OKGE_OK;
+}
+
+// ---- deferred weight decay on the row-sparse step: okge_rows_catch_up, okge_adagrad_rows_decay ----------------------------------
+// the table side of a tensor, which both entry points need whatever n is (lazy_rows and the sweep are float4 only)
+static int rows_decay_table(const okge_rows_decay_tensor &x, const char *who)
+{
+    if (x.n < 0) return fail(OKGE_ERR_INVALID, "negative occurrence count");
+    if (x.n > ROWS_MAX_N) return fail(OKGE_ERR_UNSUPPORTED, std::string(who) + " takes up to 2^20 occurrence rows per tensor");
+    if (!x.p || !x.state_sum || !x.row_steps || x.table_rows <= 0 || x.row_len <= 0) return fail(OKGE_ERR_INVALID, "null tensor / bad table shape");
+    if (x.n > 0 && !x.ids) return fail(OKGE_ERR_INVALID, "null ids");
+    if (x.row_len % 4 || (reinterpret_cast<uintptr_t>(x.p) | reinterpret_cast<uintptr_t>(x.state_sum)) % 16)
+        return fail(OKGE_ERR_UNSUPPORTED, "deferred weight decay needs row_len % 4 == 0 and 16-byte aligned tables");
+    return OKGE_OK;
+}
+
+int okge_rows_catch_up(const okge_rows_decay_tensor *tensors, int32_t n_tensors, const int32_t *counters, float lr, float weight_decay,
+                       float eps, void *stream)
+{
+    if (n_tensors < 0 || n_tensors > ROWS_MAX_SEGS || (n_tensors > 0 && !tensors)) return fail(OKGE_ERR_INVALID, "one or two tensors");
+    if (!counters) return fail(OKGE_ERR_INVALID, "okge_rows_catch_up needs the counters");
+    RowsCatchSeg segs[ROWS_MAX_SEGS];
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_rows_decay_tensor &x = tensors[k];
+        if (int rc = rows_decay_table(x, "okge_rows_catch_up")) return rc;
+        segs[k] = RowsCatchSeg{x.p, x.state_sum, x.row_steps, x.ids, x.n, x.table_rows, x.row_len, 0};
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ScopedTimer tm("rows_catch_up", st);
+    if (hipError_t e = launch_rows_catch_up(segs, n_tensors, counters, lr, weight_decay, eps, st); e != hipSuccess)
+        return fail_hip(e, "rows_catch_up");
+    return OKGE_OK;
+}
+
+int okge_adagrad_rows_decay(const okge_rows_decay_tensor *tensors, int32_t n_tensors, int32_t *counters, int32_t window, float lr,
+                            float weight_decay, float eps, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (n_tensors <= 0 || n_tensors > ROWS_MAX_SEGS || !tensors) return fail(OKGE_ERR_INVALID, "one or two tensors");
+    if (!counters || window < 1) return fail(OKGE_ERR_INVALID, "okge_adagrad_rows_decay needs the counters and window >= 1");
+    size_t need = 0;
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_rows_decay_tensor &x = tensors[k];
+        if (int rc = rows_decay_table(x, "okge_adagrad_rows_decay")) return rc;
+        if (x.n == 0) continue;
+        if (!x.g || x.ld_g < x.row_len) return fail(OKGE_ERR_INVALID, "null gradient rows / bad leading dimension");
+        if (x.ld_g % 4 || reinterpret_cast<uintptr_t>(x.g) % 16)
+            return fail(OKGE_ERR_UNSUPPORTED, "deferred weight decay needs ld_g % 4 == 0 and 16-byte aligned gradient rows");
+        need += 2 * rows_keys_bytes(x.n);
+    }
+    if (need && (!workspace || workspace_bytes < need)) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_adagrad_rows_workspace_bytes)");
+    RowsSegs segs;
+    std::memset(&segs, 0, sizeof(segs));
+    LazySeg sweep[ROWS_MAX_SEGS];
+    char *ws = static_cast<char *>(workspace);
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_rows_decay_tensor &x = tensors[k];
+        if (x.n > 0) rows_segment(segs, ws, x.p, x.state_sum, x.ids, x.g, x.ld_g, x.n, x.table_rows, x.row_len, x.row_steps);
+        // no row of the sweep is stamped, so its gradient operand is never read: the accumulator stands in (as in the pool catch-up)
+        sweep[k] = LazySeg{x.p, x.state_sum, x.state_sum, x.row_steps, nullptr, x.table_rows, x.row_len, 0};
+    }
+    segs.id_err = id_err_ptr();
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (segs.n_segs) {
+        int sorted_in = 0;
+        {
+            ScopedTimer tm("rows_sort", st);
+            if (hipError_t e = launch_rows_sort(segs, &sorted_in, st); e != hipSuccess) return fail_hip(e, "rows_sort");
+        }
+        ScopedTimer tm("rows_update", st);
+        if (hipError_t e = launch_rows_update_decay(segs, sorted_in, counters, lr, weight_decay, eps, st); e != hipSuccess)
+            return fail_hip(e, "rows_update_decay");
+    }
+    // the due slice -- rows with r % window == T % window that the update above did not bring to T + 1 -- and T += 1 on the device
+    ScopedTimer tm("rows_decay_sweep", st);
+    if (hipError_t e = launch_adagrad_lazy(sweep, n_tensors, counters, window, LAZY_STEP, lr, weight_decay, eps, st); e != hipSuccess)
+        return fail_hip(e, "rows_decay_sweep");
     return OKGE_OK;
 }
 

@@ -283,10 +283,19 @@ struct RowsSeg {
     uint64_t      *keys[2];
     int64_t        ld_g;
     int32_t        n, table_rows, row_len, vec, lane_shift;      // 1 << lane_shift lanes share one run of equal ids
+    int32_t       *steps;                                        // okge_adagrad_rows_decay: [table_rows] optimizer steps each row has seen
 };
 struct RowsSegs { RowsSeg s[ROWS_MAX_SEGS]; int n_segs; int *id_err; };
 hipError_t launch_rows_sort(const RowsSegs &segs, int *sorted_in, hipStream_t st);
 hipError_t launch_rows_update(const RowsSegs &segs, int sorted_in, float lr, float eps, hipStream_t st);
+// deferred weight decay on the row-sparse step (okge_rows_catch_up / okge_adagrad_rows_decay): every segment 16-byte accessible
+// (vec) with a step counter per table row; counters[0] = T, the optimizer steps taken
+hipError_t launch_rows_update_decay(const RowsSegs &segs, int sorted_in, const int32_t *counters, float lr, float wd, float eps,
+                                    hipStream_t st);
+struct RowsCatchSeg { float *p, *s; int32_t *steps; const int32_t *ids; int32_t n, table_rows, row_len, _pad; };
+struct RowsCatchSegs { RowsCatchSeg s[ROWS_MAX_SEGS]; int n_segs; int64_t wave0[ROWS_MAX_SEGS + 1]; };
+hipError_t launch_rows_catch_up(const RowsCatchSeg *segs, int n_segs, const int32_t *counters, float lr, float wd, float eps,
+                                hipStream_t st);
 hipError_t launch_dc_reduce(const float *slab, int nsplit, int rows_pad, int D16, int N, int d, const int32_t *cand_ids,
                             int cand_first, int exclusive, int grads_zero, float *dE, int64_t table_rows, int *id_err,
                             hipStream_t st);

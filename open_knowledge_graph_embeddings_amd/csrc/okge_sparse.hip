@@ -4,11 +4,15 @@
 //   okge_adagrad_rows                                   rows_sort_chunk_kernel / rows_merge_kernel: occurrences ordered by (id, position)
 //                                                       rows_update_kernel: per distinct id, its gradient rows added up in ascending
 //                                                       position, sequentially in fp32, then the Adagrad update of that one table row
+//   okge_rows_catch_up                                  rows_catch_up_kernel: the rows a batch names take the decay-only steps they owe
+//   okge_adagrad_rows_decay                             rows_update_decay_kernel: the same walk with the weight-decay term, per-row step
+//                                                       counters kept (deferred weight decay; the rotating sweep is okge_misc.hip's)
 // Nothing here is proportional to the table: the sort is O(n log n) on 8-byte keys, the update touches the n gradient rows and
 // the distinct table rows they name.  No float atomics, no host synchronisation; the launch sequence depends on the n alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 
 #include "okge_kernels.h"
 
@@ -126,9 +130,11 @@ __device__ __forceinline__ void adagrad1_rows(float &p, float g, float &s, float
 // ascending position, and updates its columns of the table row.  Runs are short in training batches (a candidate list names
 // an entity once, a batch repeats a prefix entity a few times), so a lane's chain is a handful of dependent loads; several
 // runs are in flight per wave (64 / lanes) and the waves of a CU hide the rest.
-template <int V>
+// DECAY (V == 4 only; okge_adagrad_rows_decay): the row first takes the `lag` decay-only steps it still owes, then the update
+// carries the weight-decay term -- adagrad4, the dense kernel's expression.
+template <int V, bool DECAY = false>
 __device__ __forceinline__ void rows_update_run(const RowsSeg &sg, const uint64_t *__restrict__ keys, int i, uint32_t id, uint32_t pos,
-                                                int lane, int lanes, float lr, float eps)
+                                                int lane, int lanes, float lr, float eps, float wd = 0.f, int lag = 0)
 {
     const int cols = sg.row_len / V;
     const int64_t ldg = sg.ld_g / V;
@@ -145,10 +151,22 @@ __device__ __forceinline__ void rows_update_run(const RowsSeg &sg, const uint64_
                 const float4 b = g4[(size_t)(uint32_t)kj * ldg + c];
                 acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
             }
-            adagrad1_rows(pv.x, acc.x, sv.x, lr, eps);
-            adagrad1_rows(pv.y, acc.y, sv.y, lr, eps);
-            adagrad1_rows(pv.z, acc.z, sv.z, lr, eps);
-            adagrad1_rows(pv.w, acc.w, sv.w, lr, eps);
+            if constexpr (DECAY) {
+                // decay_replay4 votes across the wave.  Here the wave's lanes belong to different runs, lanes that are no head
+                // of a run have returned and only the lanes of lagging rows enter (lag differs from run to run): the votes see
+                // an arbitrary subset of the wave.  Both are used in the safe direction only -- "every active lane's operands
+                // are ordinary" picks the short sqrt / div sequences, which return the generic bits on such operands, and one
+                // lane that is not sends all to the generic code; "no active lane moved" skips steps that would return the bits
+                // they were given, and one lane that moved makes the others repeat a step that changes nothing.  Either way
+                // every lane ends with the bits of `lag` plain steps, whoever else took part in the vote.
+                if (lag > 0) decay_replay4(pv, sv, lag, lr, wd, eps);
+                adagrad4(pv, acc, sv, lr, wd, eps);
+            } else {
+                adagrad1_rows(pv.x, acc.x, sv.x, lr, eps);
+                adagrad1_rows(pv.y, acc.y, sv.y, lr, eps);
+                adagrad1_rows(pv.z, acc.z, sv.z, lr, eps);
+                adagrad1_rows(pv.w, acc.w, sv.w, lr, eps);
+            }
             p4[prow + c] = pv;
             s4[prow + c] = sv;
         } else {
@@ -179,6 +197,56 @@ __global__ __launch_bounds__(256) void rows_update_kernel(const RowsSegs segs, i
     if (i > 0 && (uint32_t)(keys[i - 1] >> 32) == id) return;                     // not the head of its run
     if (sg.vec) rows_update_run<4>(sg, keys, i, id, (uint32_t)key, lane, 1 << sg.lane_shift, lr, eps);
     else rows_update_run<1>(sg, keys, i, id, (uint32_t)key, lane, 1 << sg.lane_shift, lr, eps);
+}
+
+// okge_adagrad_rows_decay: the same heads and the same walk; sg.vec holds by the entry point's preconditions.  T = the steps
+// taken so far (counters[0], advanced by the sweep that follows this launch): a named row that still lags behind T -- the
+// caller skipped okge_rows_catch_up -- replays what it owes first; every updated row then stands at T + 1.  One group of
+// lanes owns a run, so nobody else reads or writes this row's counter; the group reads it before any of its lanes stores.
+__global__ __launch_bounds__(256) void rows_update_decay_kernel(const RowsSegs segs, int sorted_in, const int32_t *__restrict__ counters,
+                                                                float lr, float wd, float eps)
+{
+    const RowsSeg &sg = segs.s[blockIdx.y];
+    const uint64_t *__restrict__ keys = sg.keys[sorted_in];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int i = t >> sg.lane_shift, lane = t & ((1 << sg.lane_shift) - 1);
+    if (i >= sg.n) return;
+    const uint64_t key = keys[i];
+    if (key == KEY_SKIP) return;                                                  // id outside the table: counted, never written
+    const uint32_t id = (uint32_t)(key >> 32);
+    if (i > 0 && (uint32_t)(keys[i - 1] >> 32) == id) return;                     // not the head of its run
+    const int T = counters[0];
+    const int lag = max(0, T - sg.steps[id]);
+    rows_update_run<4, true>(sg, keys, i, id, (uint32_t)key, lane, 1 << sg.lane_shift, lr, eps, wd, lag);
+    if (lane == 0) sg.steps[id] = T + 1;
+}
+
+// Catch-up of the deferred decay-only steps before the forward gathers the rows (the scheme of pool_catch_up_kernel,
+// okge_pool.hip).  Lane = occurrence: an id whose row lags behind T claims it with an integer atomicMax on the row's step
+// counter -- the first claim wins, one owner per row however many occurrences name it -- then the wave replays its claimed rows,
+// lane = column quad (lazy_rows).  Nothing in this launch reads a row it does not own; the gather runs in a later launch.
+// ROWS_CATCH occurrences per wave and turn: many short waves, each with a handful of dependent row replays.
+constexpr int ROWS_CATCH = 16;
+
+__global__ __launch_bounds__(256, 5) void rows_catch_up_kernel(const RowsCatchSegs segs, const int32_t *__restrict__ counters, float lr, float wd,
+                                                            float eps)
+{
+    const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= segs.wave0[segs.n_segs]) return;                                   // (the whole wave)
+    int k = 0;
+    while (gw >= segs.wave0[k + 1]) ++k;
+    const RowsCatchSeg &sg = segs.s[k];
+    const int T = counters[0], lane = threadIdx.x & 63;
+    const int64_t i = (gw - segs.wave0[k]) * ROWS_CATCH + lane;
+    int32_t id = -1;
+    if (lane < ROWS_CATCH && i < sg.n) id = sg.ids[i];
+    int from = T;
+    bool claim = false;
+    if ((uint32_t)id < (uint32_t)sg.table_rows && sg.steps[id] < T) {           // (ids outside the table: skipped here, counted by the sort)
+        from = atomicMax(&sg.steps[id], T);
+        claim = from < T;
+    }
+    lazy_rows(__ballot(claim), id, T - from, false, sg.p, sg.s, sg.s, sg.row_len, lane, lr, wd, eps);
 }
 
 }  // namespace
@@ -216,6 +284,38 @@ hipError_t launch_rows_update(const RowsSegs &segs, int sorted_in, float lr, flo
     for (int k = 0; k < segs.n_segs; ++k) threads = std::max<int64_t>(threads, (int64_t)segs.s[k].n << segs.s[k].lane_shift);
     if (threads <= 0) return hipSuccess;
     hipLaunchKernelGGL(rows_update_kernel, dim3((unsigned)((threads + 255) / 256), segs.n_segs), dim3(256), 0, st, segs, sorted_in, lr, eps);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_update_decay(const RowsSegs &segs, int sorted_in, const int32_t *counters, float lr, float wd, float eps,
+                                    hipStream_t st)
+{
+    int64_t threads = 0;
+    for (int k = 0; k < segs.n_segs; ++k) {
+        if (!segs.s[k].vec || !segs.s[k].steps) return hipErrorInvalidValue;
+        threads = std::max<int64_t>(threads, (int64_t)segs.s[k].n << segs.s[k].lane_shift);
+    }
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rows_update_decay_kernel, dim3((unsigned)((threads + 255) / 256), segs.n_segs), dim3(256), 0, st, segs, sorted_in,
+                       counters, lr, wd, eps);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_catch_up(const RowsCatchSeg *segs, int n_segs, const int32_t *counters, float lr, float wd, float eps,
+                                hipStream_t st)
+{
+    if (n_segs < 0 || n_segs > ROWS_MAX_SEGS || !counters) return hipErrorInvalidValue;
+    RowsCatchSegs a;
+    std::memset(&a, 0, sizeof(a));
+    for (int k = 0; k < n_segs; ++k) {
+        if (segs[k].n <= 0) continue;
+        a.s[a.n_segs] = segs[k];
+        a.wave0[a.n_segs + 1] = a.wave0[a.n_segs] + (segs[k].n + ROWS_CATCH - 1) / ROWS_CATCH;
+        ++a.n_segs;
+    }
+    const int64_t waves = a.wave0[a.n_segs];
+    if (waves <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rows_catch_up_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a, counters, lr, wd, eps);
     return hipGetLastError();
 }
 

@@ -606,6 +606,48 @@ class HotPath:
         N.check(self.lib.okge_adagrad_rows(arr, len(tensors), float(lr), float(eps), self._rows_ws.data_ptr(), self._rows_ws.numel(),
                                            self._stream()), "okge_adagrad_rows")
 
+    def _rows_decay_tensors(self, tensors, who):
+        """(p, state_sum, ids, g or None, row_steps) tuples -> the okge_rows_decay_tensor array"""
+        arr = (N.RowsDecayTensor * len(tensors))()
+        for a, (p_, s_, i_, g_, st_) in zip(arr, tensors):
+            n = int(i_.numel())
+            for x in (i_, st_):
+                if x.dtype != torch.int32 or not x.is_contiguous() or x.device != self.device:
+                    raise N.OkgeError(f"{who}: ids and row_steps must be contiguous int32 tensors on the engine's device")
+            for x in (p_, s_) + (() if g_ is None else (g_,)):
+                if x.dtype != torch.float32 or x.device != self.device:
+                    raise N.OkgeError(f"{who}: fp32 tensors on the engine's device")
+            if p_.dim() != 2 or not p_.is_contiguous() or not s_.is_contiguous() or s_.shape != p_.shape or st_.numel() != p_.shape[0]:
+                raise N.OkgeError(f"{who}: p and state_sum must be contiguous (rows, row_len) tensors of one shape, row_steps (rows,)")
+            a.p, a.state_sum, a.ids, a.row_steps = p_.data_ptr(), s_.data_ptr(), i_.data_ptr(), st_.data_ptr()
+            a.n, a.table_rows, a.row_len, a.ld_g = n, int(p_.shape[0]), int(p_.shape[1]), int(p_.shape[1])
+            if g_ is not None:
+                if n and (g_.dim() != 2 or g_.shape[0] != n or g_.shape[1] != p_.shape[1] or g_.stride(1) != 1):
+                    raise N.OkgeError(f"{who}: g must hold one row of row_len floats per id, last dim contiguous")
+                a.g = g_.data_ptr()
+                if n > 1:
+                    a.ld_g = int(g_.stride(0))
+        return arr
+
+    def rows_catch_up(self, tensors, counters, lr, weight_decay=1e-10, eps=1e-8):
+        """okge_rows_catch_up: the rows the int32 device ids name take the decay-only steps they still owe, before anything
+        reads them.  tensors: one or two (p, state_sum, ids, row_steps); counters: int32[2] on the device."""
+        arr = self._rows_decay_tensors([(p, s, i, None, st) for p, s, i, st in tensors], "rows_catch_up")
+        N.check(self.lib.okge_rows_catch_up(arr, len(tensors), counters.data_ptr(), float(lr), float(weight_decay), float(eps),
+                                            self._stream()), "okge_rows_catch_up")
+
+    def adagrad_rows_decay(self, tensors, counters, window, lr, weight_decay=1e-10, eps=1e-8):
+        """okge_adagrad_rows_decay: okge_adagrad_rows with the dense step's weight-decay term on the named rows, then the due
+        slice of the deferred decay-only steps and T += 1.  tensors: one or two (p, state_sum, ids, g, row_steps)."""
+        arr = self._rows_decay_tensors(tensors, "adagrad_rows_decay")
+        ns = [int(a.n) for a in arr] + [0]
+        need = int(self.lib.okge_adagrad_rows_workspace_bytes(ns[0], ns[1]))
+        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < need:
+            self._rows_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        N.check(self.lib.okge_adagrad_rows_decay(arr, len(tensors), counters.data_ptr(), int(window), float(lr), float(weight_decay),
+                                                 float(eps), self._rows_ws.data_ptr(), self._rows_ws.numel(), self._stream()),
+                "okge_adagrad_rows_decay")
+
     @staticmethod
     def lazy_tensors(tensors):
         """(p, g, state_sum[, row_steps, touched_map, stamp]) tuples -> the okge_lazy_tensor array of okge_adagrad_lazy"""

@@ -18,18 +18,33 @@ class FusedTrainStep:
     def __init__(self, E: torch.Tensor, R: torch.Tensor, scorer: str, loss: str = "bce", lr: float = 0.3,
                  weight_decay: float = 1e-10, eps: float = 1e-8, label_smoothing: float = 0.0,
                  input_dropout: float = 0.0, relation_input_dropout: float = 0.0, seed: int = 0, engine=None,
-                 grad_clip: float = 0.0, accumulate: int = 1, sparse: bool = False):
+                 grad_clip: float = 0.0, accumulate: int = 1, sparse: bool = False, decay_window=None):
         """Defaults follow config/fb15k237/fb15k237-complex-kge.yaml and the optimizer OptimRegime actually
         builds (utils/optim.py:29,139-160): Adagrad(lr, weight_decay=1e-10, eps=1e-8 leaked from Adam).
 
         sparse (model_config.sparse, model.py:390-391): gradients stay in occurrence rows and only the table rows a batch
         names are updated (okge_adagrad_rows) -- no dense dE / dR, nothing per step that grows with the tables.  Needs
-        weight_decay = 0, as torch's sparse Adagrad does; no clipping (torch cannot clip sparse gradients), no accumulation."""
+        weight_decay = 0, as torch's sparse Adagrad does; no clipping (torch cannot clip sparse gradients), no accumulation.
+
+        decay_window (sparse only; None: off): the row-sparse step WITH the reference's weight decay.  Dense Adagrad moves
+        every row every step by its decay term; such a decay-only update depends on the row alone, so a row no batch names takes
+        it later, all pending steps at once in registers (okge_rows_catch_up / okge_adagrad_rows_decay, okge.h): when a batch
+        names it (catch-up before the forward), when its turn in the rotating 1 / decay_window sweep comes, or at flush().  After
+        flush() tables and accumulators are bit-identical to the dense step's wherever that step's atomics are order-free.
+        CONTRACT: between steps, rows no batch named may lag by up to decay_window - 1 decay-only steps -- call flush() before
+        reading .E / .sumE / .R / .sumR or handing them to an evaluator (state_tensors() and the checkpoint writer do), and
+        before discarding a step object whose tables live on.  Needs d % 4 == 0."""
         N.refuse_bias_scorer(scorer, type(self).__name__)
         self.sparse = bool(sparse)
+        self.decay_window = None if decay_window is None else int(decay_window)
+        if self.decay_window is not None and (not self.sparse or self.decay_window < 1):
+            raise ValueError("decay_window (deferred weight decay) belongs to the sparse step and is >= 1")
         if self.sparse:
-            if weight_decay != 0:
+            if weight_decay != 0 and self.decay_window is None:
                 raise ValueError("weight_decay option is not compatible with sparse gradients")
+            if self.decay_window is not None and E.shape[1] % 4:
+                raise NotImplementedError("FusedTrainStep(sparse=True, decay_window=...): the deferred decay works on 16-byte "
+                                          "column groups, the slot size must be a multiple of 4")
             if float(grad_clip or 0.0) > 0 or int(accumulate) > 1:
                 raise NotImplementedError("FusedTrainStep(sparse=True): grad_clip and accumulate need dense gradients "
                                           "(torch.nn.utils.clip_grad_norm_ refuses sparse gradients)")
@@ -44,6 +59,13 @@ class FusedTrainStep:
         self.dE, self.dR = (None, None) if self.sparse else (torch.zeros_like(E), torch.zeros_like(R))
         self._rows = {}
         self.sumE, self.sumR = torch.zeros_like(E), torch.zeros_like(R)   # Adagrad state 'sum' (init 0)
+        if self.decay_window is not None:
+            # deferred weight decay: optimizer steps every row has seen, [steps taken, scratch] on the device (a captured graph
+            # replays them), and the (lr, weight_decay, eps) of the steps rows still owe -- None: every row is current
+            self.rowsE = torch.zeros(E.shape[0], dtype=torch.int32, device=E.device)
+            self.rowsR = torch.zeros(R.shape[0], dtype=torch.int32, device=R.device)
+            self._counters = torch.zeros(2, dtype=torch.int32, device=E.device)
+        self._pending = None
         self.steps = 0
         self.step_dev = None              # device step counter, attached by GraphedTrainStep
         self._grads_zero = True           # fresh buffers; kept true by the zero_grad fused into Adagrad
@@ -64,9 +86,36 @@ class FusedTrainStep:
 
     def state_tensors(self):
         """every tensor a step mutates (GraphedTrainStep snapshots them around its warm-up)"""
+        if self.decay_window is not None:  # (a caller that restores a snapshot restores the step counters with it)
+            self.flush()
+            return [self.E, self.R, self.sumE, self.sumR, self.rowsE, self.rowsR, self._counters]
         if self.sparse:                   # (the row buffers are written whole before they are read, every step)
             return [self.E, self.R, self.sumE, self.sumR]
         return [self.E, self.R, self.dE, self.dR, self.sumE, self.sumR]
+
+    # -- sparse step with deferred weight decay (decay_window) ----------------------------------------------------------
+    def _hparams(self):
+        return (float(self.lr), float(self.weight_decay), float(self.eps))
+
+    def flush(self):
+        """every row of both tables takes the decay-only steps it still owes: afterwards the tables are the dense step's"""
+        if self._pending is None:
+            return
+        lr, wd, eps = self._pending
+        # (no row is stamped in a flush, so the gradient operand is never read: the accumulator stands in)
+        self.engine.adagrad_lazy([(self.E, self.sumE, self.sumE, self.rowsE), (self.R, self.sumR, self.sumR, self.rowsR)],
+                                 self._counters, self.decay_window, True, lr, wd, eps)
+        self._pending = None
+
+    def mark_pending(self):
+        """a captured graph holding this step was replayed: rows may owe steps again (GraphedTrainStep)"""
+        if self.decay_window is not None and self.decay_window > 1:
+            self._pending = self._hparams()
+
+    def _settle_hparams(self):
+        """pending steps were taken with the lr / weight decay / eps of their time: flush before these change"""
+        if self._pending is not None and self._pending != self._hparams():
+            self.flush()
 
     # -- sparse step: occurrence rows ------------------------------------------------------------------------------------
     def _row_buffers(self, batch: H.PrefixBatch):
@@ -176,6 +225,11 @@ class FusedTrainStep:
             H.occurrence_ids(self.E.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
                              batch.po_rel, batch.sp_rel, out=(rb["idE"], rb["idR"]))
             self._last_full = False
+            if self.decay_window is not None:      # the rows this batch names take what they owe BEFORE the gather reads them
+                self._settle_hparams()
+                lr, wd, eps = self._hparams()
+                self.engine.rows_catch_up([(self.E, self.sumE, rb["idE"], self.rowsE), (self.R, self.sumR, rb["idR"], self.rowsR)],
+                                          self._counters, lr, wd, eps)
             if isinstance(self.engine, H.HotPath) and self._plain(batch):
                 return self._fast_forward_backward(batch, normalizer)
             self._set_dropout(batch)
@@ -197,7 +251,18 @@ class FusedTrainStep:
         """trainer.py:240-244: optimizer.step() then zero_grad() -- one sweep per table.  lazy_zero (used by step()
         after a 1-vs-all batch): the entity gradient is not cleared here because the next 1-vs-all step overwrites
         every row it uses; it is cleared on demand if a sampled candidate list comes next.
-        Sparse step: torch's sparse Adagrad on the occurrence rows of the last forward_backward -- nothing to clear."""
+        Sparse step: torch's sparse Adagrad on the occurrence rows of the last forward_backward -- nothing to clear; with a
+        decay_window the same rows take the dense step's expression, then the due slice of the deferred decay-only steps."""
+        if self.decay_window is not None:
+            rb = self._cur_rows
+            self._settle_hparams()
+            lr, wd, eps = self._hparams()
+            self.engine.adagrad_rows_decay([(self.E, self.sumE, rb["idE"], rb["gE"], self.rowsE),
+                                            (self.R, self.sumR, rb["idR"], rb["gR"], self.rowsR)],
+                                           self._counters, self.decay_window, lr, wd, eps)
+            if self.decay_window > 1:
+                self._pending = (lr, wd, eps)
+            return
         if self.sparse:
             rb = self._cur_rows
             self.engine.adagrad_rows(self.E, self.sumE, rb["idE"], rb["gE"], self.lr, self.eps,
