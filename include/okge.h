@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define OKGE_ABI_VERSION 1
+#define OKGE_ABI_VERSION 2
 
 enum okge_status {
     OKGE_OK = 0,
@@ -41,7 +41,7 @@ enum okge_scorer { OKGE_COMPLEX = 0, OKGE_DISTMULT = 1,     /* model.py:176-240 
                    /* the data-bias baselines (model.py:281-350): the query row is ONE encoded row, copied -- the relation
                     * (sp: rel . obj^T, po: rel . subj^T) or the prefix entity (sp: subj . obj^T, po: obj . subj^T); the other
                     * slot's row is not read and receives no gradient.  Prefix scoring, training and evaluation only:
-                    * okge_score_triples, okge_train_step, okge_fold_queries and okge_evaluate_fused_shard answer
+                    * okge_score_triples, okge_fold_queries and okge_evaluate_fused_shard answer
                     * OKGE_ERR_UNSUPPORTED.  No even-d rule. */
                    OKGE_BIAS_RELATION = 2, OKGE_BIAS_ENTITY = 3 };
 enum okge_loss   { OKGE_LOSS_BCE = 0, OKGE_LOSS_KL = 1 };   /* trainer.py:93-106           */
@@ -298,8 +298,8 @@ typedef struct okge_pool_call {
     float *saved;
     const float *d_out;
     float *dW, *d_bn_weight, *d_bn_bias;
-    uint8_t *row_touched;        /* optional: [vocab] bytes; backward: row_touched[t] = touched_stamp for every row t of dW written;
-                                    forward (training != 0): for every token row the call reads (padding row 0 included) */
+    uint8_t *row_touched;        /* optional: [vocab] bytes; the backward sets row_touched[t] = touched_stamp for every row t of dW it
+                                    writes; the forward does not read or write it */
     int32_t touched_stamp;       /* 1..255 (okge_adagrad_multi reads the map with the same stamp) */
     int32_t _pad;
 } okge_pool_call;
@@ -505,10 +505,6 @@ typedef struct okge_adagrad_tensor {
     int64_t n;
     const uint8_t *row_touched;
     int32_t row_len, touched_stamp, zero_grad;
-    int32_t rows;                /* 0: all rows; 1: only the rows WITHOUT the stamp (weight-decay-only update, the gradient is not read);
-                                    2: only the rows WITH the stamp.  1 then 2 = 0, row for row: the rows no token of the batch names can
-                                    take their update while the step's matrix kernels run (okge_pool_encode_calls stamps the rows the
-                                    forward reads, so the sweep of the others may start right behind it on another stream) */
 } okge_adagrad_tensor;
 int okge_adagrad_multi(const okge_adagrad_tensor *tensors, int32_t n_tensors, float lr, float weight_decay, float eps,
                        void *stream);
@@ -615,25 +611,6 @@ int okge_rows_catch_up(const okge_rows_decay_tensor *tensors, int32_t n_tensors,
                        float eps, void *stream);
 int okge_adagrad_rows_decay(const okge_rows_decay_tensor *tensors, int32_t n_tensors, int32_t *counters, int32_t window, float lr,
                             float weight_decay, float eps, void *workspace, size_t workspace_bytes, void *stream);
-
-/* ---- the whole step in one call: okge_train_forward_backward + the dense Adagrad update of both tables ------------------
- * (Trainer.compute_one_batch's training branch end to end, trainer.py:217-257 with utils/optim.py:139-160.)  Same arithmetic,
- * element for element, as okge_train_forward_backward followed by okge_adagrad_step2(zero_grad = 2 or 1) -- tables and
- * accumulators end up bit-identical -- but the update rides in the step's own launches: the sweep over the entity rows that no
- * prefix of the batch names (their gradient is final once the tile kernel has run) runs in extra workgroups of the
- * prefix-backward launch, which is latency-bound and leaves the memory system idle; one small launch finishes the <= B prefix
- * entity rows and the relation table (gradient cleared).  prefix_flags: n_ent int32 words the caller zeroes ONCE and thereafter
- * only hands to this function (it leaves them zero).  zero_entity_grad: clear dE as okge_adagrad_step does; 0 when the next step
- * overwrites every candidate row anyway (1-vs-all with OKGE_TRAIN_GRADS_ZERO). */
-typedef struct okge_adagrad {
-    float *sum_E, *sum_R;
-    float lr, weight_decay, eps;
-    int32_t zero_entity_grad;
-    int32_t *prefix_flags;
-} okge_adagrad;
-int okge_train_step(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, const okge_positives *pos,
-                    int32_t loss_kind, float label_smoothing, double normalizer, int32_t flags, const okge_adagrad *opt,
-                    double *loss_out, float *dE, float *dR, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- batch producer (HOST pointers; no device work) ---------------------------------------------------
  * Replaces OneToNMentionRelationDataset_collate_func (dataset.py:724-940) and the packed answer-group decoding

@@ -45,7 +45,7 @@ def refuse_bias_scorer(scorer, who):
 EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_train_forward_backward",
            "okge_train_workspace_bytes", "okge_score_workspace_bytes", "okge_lse_workspace_bytes", "okge_query_ld", "okge_query_rows", "okge_encode_queries", "okge_train_tiles",
            "okge_prefix_backward", "okge_prefix_backward_segmented", "okge_fold_queries", "okge_score_queries", "okge_row_logsumexp", "okge_group_true_scores",
-           "okge_rank_counts", "okge_rank_metrics", "okge_evaluate_batch", "okge_evaluate_fused", "okge_evaluate_fused_shard", "okge_evaluate_fused_batches", "okge_eval_workspace_bytes", "okge_score_triples", "okge_pool_workspace_bytes", "okge_pool_encode", "okge_pool_backward", "okge_pool_encode_calls", "okge_pool_backward_calls", "okge_pool_scatter_state_bytes", "okge_pool_backward_workspace_bytes", "okge_adagrad_multi", "okge_adagrad_lazy", "okge_pool_catch_up_calls", "okge_train_step", "okge_prefix_score_backward", "okge_prefix_score_backward_workspace_bytes", "okge_scatter_rows",
+           "okge_rank_counts", "okge_rank_metrics", "okge_evaluate_batch", "okge_evaluate_fused", "okge_evaluate_fused_shard", "okge_evaluate_fused_batches", "okge_eval_workspace_bytes", "okge_score_triples", "okge_pool_workspace_bytes", "okge_pool_encode", "okge_pool_backward", "okge_pool_encode_calls", "okge_pool_backward_calls", "okge_pool_scatter_state_bytes", "okge_pool_backward_workspace_bytes", "okge_adagrad_multi", "okge_adagrad_lazy", "okge_pool_catch_up_calls", "okge_prefix_score_backward", "okge_prefix_score_backward_workspace_bytes", "okge_scatter_rows",
            "okge_lstm_workspace_bytes", "okge_lstm_encode_calls", "okge_lstm_backward_calls",
            "okge_bigram_workspace_bytes", "okge_bigram_encode_calls", "okge_bigram_backward_calls",
            "okge_tucker3_workspace_bytes", "okge_tucker3_fold", "okge_tucker3_backward", "okge_tucker3_score_triples", "okge_tucker3_apply", "okge_tucker3_outer",
@@ -131,14 +131,9 @@ class BigramSlot(Structure):
                 ("bn_num_batches_tracked", c_void_p), ("bn_eps", c_float), ("_pad", c_int32)]
 
 
-class AdagradOpt(Structure):
-    _fields_ = [("sum_E", c_void_p), ("sum_R", c_void_p), ("lr", c_float), ("weight_decay", c_float), ("eps", c_float),
-                ("zero_entity_grad", c_int32), ("prefix_flags", c_void_p)]
-
-
 class AdagradTensor(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("state_sum", c_void_p), ("n", c_int64), ("row_touched", c_void_p),
-                ("row_len", c_int32), ("touched_stamp", c_int32), ("zero_grad", c_int32), ("rows", c_int32)]
+                ("row_len", c_int32), ("touched_stamp", c_int32), ("zero_grad", c_int32)]
 
 
 class RowsTensor(Structure):
@@ -379,9 +374,6 @@ def lib():
     L.okge_tucker3_apply.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p]
     L.okge_tucker3_outer.restype = c_int32
     L.okge_tucker3_outer.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p]
-    L.okge_train_step.restype = c_int32
-    L.okge_train_step.argtypes = [POINTER(Tables), POINTER(PrefixBatch), POINTER(Candidates), POINTER(Positives), c_int32, c_float,
-                                  c_double, c_int32, POINTER(AdagradOpt), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     L.okge_adagrad_multi.restype = c_int32
     L.okge_adagrad_multi.argtypes = [POINTER(AdagradTensor), c_int32, c_float, c_float, c_float, c_void_p]
     L.okge_adagrad_lazy.restype = c_int32
@@ -421,7 +413,7 @@ def lib():
     L.okge_timing_reset.restype = c_int32
     L.okge_timing_collect.restype = c_int32
     L.okge_timing_collect.argtypes = [POINTER(c_char_p), POINTER(c_double), POINTER(c_int64), c_int32]
-    if L.okge_abi_version() != 1:
+    if L.okge_abi_version() != 2:
         raise OkgeError("libokge_hip.so ABI version mismatch")
     _LIB = L
     return L

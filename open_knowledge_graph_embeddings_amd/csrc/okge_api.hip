@@ -600,8 +600,7 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
                       int64_t ldq_ext, int32_t B, const okge_candidates *cand, const okge_positives *pos,
                       int32_t loss_kind, float label_smoothing, double normalizer, int32_t n_cand_global, int32_t flags,
                       double *loss_out, float *dE, float *dR, float *dq_out, float *scores, int64_t ld_scores,
-                      const float *row_lse_ext, void *workspace, size_t workspace_bytes, void *stream,
-                      const okge_adagrad *opt = nullptr)
+                      const float *row_lse_ext, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!pos || pos->nnz < 0 || (pos->nnz > 0 && (!pos->col || !pos->row)))
         return fail(OKGE_ERR_INVALID, "bad positives");
@@ -642,14 +641,13 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
             clr.p[1] = dE;                      clr.n[1] = (int64_t)cand->first_id * d64;
             clr.p[2] = dE + hi * d64;           clr.n[2] = ((int64_t)t->n_ent - hi) * d64;
         }
-        if (opt) clr.prefix_flags = opt->prefix_flags;
         // the tile kernel's gradient product reads Q as three bf16 planes: written by the launch that folds the rows, or from
         // the caller's block by a launch of its own
         v8bf *q_planes = tile_grad_split(g.KB) && !loss_only ? reinterpret_cast<v8bf *>(ws + g.off_Qp) : nullptr;
         e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + g.off_Q), g.ldq,
                                   q_ext ? 0 : g.Bpad, nullptr, pos->col, pos->nnz,
                                   reinterpret_cast<int32_t *>(ws + g.off_tptr), g.tiles, NT, cand_col0, st,
-                                  (clear_grads || kl_own_lse || opt) ? &clr : nullptr, q_planes, g.KB);
+                                  (clear_grads || kl_own_lse) ? &clr : nullptr, q_planes, g.KB);
         if (e != hipSuccess) return fail_hip(e, "encode_queries");
         if (q_ext && q_planes) {
             e = launch_query_planes(q_ext, g.ldq, B, g.Bpad, g.d, g.KB, q_planes, st);
@@ -793,21 +791,10 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
     {
         ScopedTimer tm("prefix_backward", st);      // + the deterministic loss reduction (one extra workgroup)
         const PrefixDev p = to_dev(*batch, t, sh);
-        AdagradFuse af = {};
-        if (opt) {
-            af.E = const_cast<float *>(t->E); af.sumE = opt->sum_E; af.dE = dE; af.R = const_cast<float *>(t->R); af.sumR = opt->sum_R; af.dR = dR;
-            af.flags = opt->prefix_flags; af.n_ent = t->n_ent; af.n_rel = t->n_rel; af.d = t->d; af.zero_dE = opt->zero_entity_grad; af.on = 1;
-            af.lr = opt->lr; af.wd = opt->weight_decay; af.eps = opt->eps;
-        }
         e = launch_prefix_backward(t->E, t->R, t->d, t->scorer, p, q.slab, g.nsplit, g.Bpad, g.ldq, nullptr, dE, dR,
                                    a.loss_partial, n_loss_partials, loss_out, st, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr,
-                                   (flags & OKGE_TRAIN_DISTINCT_PREFIX_ROWS) ? 1 : 0, opt ? &af : nullptr);
+                                   (flags & OKGE_TRAIN_DISTINCT_PREFIX_ROWS) ? 1 : 0);
         if (e != hipSuccess) return fail_hip(e, "prefix_backward");
-        if (opt) {
-            ScopedTimer tf("adagrad_finish", st);
-            e = launch_adagrad_finish(af, p, st);
-            if (e != hipSuccess) return fail_hip(e, "adagrad_finish");
-        }
     }
     return OKGE_OK;
 }
@@ -893,24 +880,6 @@ int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *b
     return train_core(t, nullptr, batch, nullptr, 0, batch->n_po + batch->n_sp, cand, pos, loss_kind, label_smoothing,
                       normalizer, cand->n, flags, loss_out, dE, dR, nullptr, scores, ld_scores, nullptr, workspace,
                       workspace_bytes, stream);
-}
-
-int okge_train_step(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, const okge_positives *pos,
-                    int32_t loss_kind, float label_smoothing, double normalizer, int32_t flags, const okge_adagrad *opt,
-                    double *loss_out, float *dE, float *dR, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (int rc = check_common(t, batch, cand)) return rc;
-    if (int rc = refuse_bias(t->scorer, "okge_train_step", "its update steps both tables, the unused slot has no gradient")) return rc;
-    if (!dR || !opt || !opt->sum_E || !opt->sum_R || !opt->prefix_flags) return fail(OKGE_ERR_INVALID, "null output / optimizer state");
-    if (flags & (OKGE_TRAIN_LOSS_ONLY | OKGE_TRAIN_DISTINCT_PREFIX_ROWS))
-        return fail(OKGE_ERR_INVALID, "okge_train_step updates the tables: not with LOSS_ONLY / DISTINCT_PREFIX_ROWS");
-    if (t->scorer == OKGE_DISTMULT ? t->d % 4 : t->d % 8)
-        return fail(OKGE_ERR_UNSUPPORTED, "okge_train_step needs a slot size that is a multiple of 4 (DistMult) / 8 (ComplEx)");
-    if ((reinterpret_cast<uintptr_t>(t->E) | reinterpret_cast<uintptr_t>(t->R) | reinterpret_cast<uintptr_t>(dE) | reinterpret_cast<uintptr_t>(dR) |
-         reinterpret_cast<uintptr_t>(opt->sum_E) | reinterpret_cast<uintptr_t>(opt->sum_R)) % 16)
-        return fail(OKGE_ERR_INVALID, "tables, gradients and accumulators must be 16-byte aligned");
-    return train_core(t, nullptr, batch, nullptr, 0, batch->n_po + batch->n_sp, cand, pos, loss_kind, label_smoothing, normalizer,
-                      cand->n, flags, loss_out, dE, dR, nullptr, nullptr, 0, nullptr, workspace, workspace_bytes, stream, opt);
 }
 
 // ---- entity-sharded phases ---------------------------------------------------------------------------------------
@@ -1406,10 +1375,6 @@ static int pool_call_dev(const okge_pool_call &c, bool backward, bool training, 
         if (bn && training && !c.saved)
             return fail(OKGE_ERR_INVALID, "training-mode batch-norm needs the saved-statistics buffer (4*d floats)");
         q.saved = bn && training ? c.saved : nullptr;
-        if (training && c.row_touched) {                    // forward in training mode: every token row the call READS is stamped
-            if (c.touched_stamp < 1 || c.touched_stamp > 255) return fail(OKGE_ERR_INVALID, "touched_stamp must lie in 1..255");
-            q.touched = c.row_touched; q.touched_stamp = c.touched_stamp;
-        }
     } else {
         if (!c.d_out || !c.dW) return fail(OKGE_ERR_INVALID, "bad backward arguments");
         if (bn && (!c.saved || !c.d_bn_weight || !c.d_bn_bias))
@@ -1591,8 +1556,7 @@ int okge_adagrad_multi(const okge_adagrad_tensor *tensors, int32_t n_tensors, fl
             if (t.touched_stamp < 1 || t.touched_stamp > 255) return fail(OKGE_ERR_INVALID, "touched_stamp must lie in 1..255");
             if (!t.zero_grad) return fail(OKGE_ERR_INVALID, "a touched-row map needs zero_grad (rows not stamped must hold zero gradients)");
         }
-        if (t.rows < 0 || t.rows > 2 || (t.rows && !t.row_touched)) return fail(OKGE_ERR_INVALID, "rows: 0 all, 1 unstamped only, 2 stamped only (1 / 2 need a map)");
-        segs[i] = AdagradSegM{t.p, t.g, t.state_sum, t.n, t.row_touched, t.row_len, t.touched_stamp, t.zero_grad, t.rows};
+        segs[i] = AdagradSegM{t.p, t.g, t.state_sum, t.n, t.row_touched, t.row_len, t.touched_stamp, t.zero_grad};
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ScopedTimer tm("adagrad", st);

@@ -121,10 +121,6 @@ __global__ __launch_bounds__(128) void encode_queries_kernel(const float *__rest
         return;
     }
     const int b = blockIdx.x;
-    if (clr.prefix_flags && threadIdx.x == 0 && b < p.n_po + p.n_sp) {              // okge_train_step: this row's entity gets prefix gradients
-        const RowSrc rs = row_source(p, b, false);
-        if (rs.owned) clr.prefix_flags[rs.ent] = 1;
-    }
     encode_query_row(E, R, d, scorer, p, b, Q ? Q + (size_t)b * ldq : nullptr,      // Q == nullptr: only the masked
                      ent_rows ? ent_rows + (size_t)b * ldq : nullptr, ldq);         // entity rows are wanted
     if (Q && q_planes) {
@@ -350,67 +346,6 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const double *__restri
 // NB: slab loads kept in flight per lane (8 for the single-device step's 32 split-K slabs; 1 for the sharded step, whose dQ
 // arrives already reduced: 89 instead of 149 registers = 5 instead of 3 waves per SIMD, which is what bounds a launch of
 // 4096 one-row workgroups -- 2.7 rounds of a ~7 us dependent-load chain at 3 waves)
-// ---- okge_train_step: Adagrad inside the step's last launches (AdagradFuse, okge_kernels.h) -------------------------------
-// (bits_differ, adagrad4: okge_device.h)
-
-// entity rows without a prefix flag: their gradient row is final (the tile kernel stored it, no prefix of the batch names them)
-__device__ __forceinline__ void fused_entity_sweep(const AdagradFuse &af, int wg, int n_wgs)
-{
-    const uint32_t row4 = (uint32_t)af.d >> 2;
-    const int64_t n4 = af.n_ent * row4, stride = (int64_t)n_wgs * blockDim.x;
-    float4 *p4 = reinterpret_cast<float4 *>(af.E), *g4 = reinterpret_cast<float4 *>(af.dE), *s4 = reinterpret_cast<float4 *>(af.sumE);
-    for (int64_t i = (int64_t)wg * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        // (the flag is requested WITH the row data, not before it: one round trip; a flagged row's loads are wasted, there are <= B)
-        const int32_t flagged = af.flags[(uint32_t)i / row4];
-        float4 pv = p4[i], sv = s4[i];
-        const float4 gv = g4[i], p_old = pv, s_old = sv;
-        if (flagged != 0) continue;
-        adagrad4(pv, gv, sv, af.lr, af.wd, af.eps);
-        if (bits_differ(pv, p_old)) p4[i] = pv;
-        if (bits_differ(sv, s_old)) s4[i] = sv;
-        if (af.zero_dE && ((__float_as_uint(gv.x) | __float_as_uint(gv.y) | __float_as_uint(gv.z) | __float_as_uint(gv.w)) != 0u))
-            g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-
-// the rest: workgroup b < B claims its batch row's prefix entity row (the flag goes back to 0: several batch rows may name one
-// entity, one of them updates it), the workgroups behind sweep the relation table (gradient cleared, as okge_adagrad_step2 does)
-__global__ __launch_bounds__(128) void adagrad_finish_kernel(const AdagradFuse af, const PrefixDev p, int B)
-{
-    __shared__ int64_t claimed;
-    const uint32_t row4 = (uint32_t)af.d >> 2;
-    if ((int)blockIdx.x < B) {
-        if (threadIdx.x == 0) {
-            const RowSrc rs = row_source(p, blockIdx.x, false);
-            claimed = (rs.owned && atomicExch(&af.flags[rs.ent], 0) != 0) ? rs.ent : -1;
-        }
-        __syncthreads();
-        const int64_t row = claimed;
-        if (row < 0) return;
-        float4 *p4 = reinterpret_cast<float4 *>(af.E) + row * row4, *g4 = reinterpret_cast<float4 *>(af.dE) + row * row4;
-        float4 *s4 = reinterpret_cast<float4 *>(af.sumE) + row * row4;
-        for (uint32_t i = threadIdx.x; i < row4; i += blockDim.x) {
-            float4 pv = p4[i], sv = s4[i];
-            const float4 gv = g4[i];
-            adagrad4(pv, gv, sv, af.lr, af.wd, af.eps);
-            p4[i] = pv;
-            s4[i] = sv;
-            if (af.zero_dE) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        return;
-    }
-    const int64_t n4 = (int64_t)af.n_rel * row4, stride = (int64_t)(gridDim.x - B) * blockDim.x;
-    float4 *p4 = reinterpret_cast<float4 *>(af.R), *g4 = reinterpret_cast<float4 *>(af.dR), *s4 = reinterpret_cast<float4 *>(af.sumR);
-    for (int64_t i = (int64_t)(blockIdx.x - B) * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 pv = p4[i], sv = s4[i];
-        const float4 gv = g4[i], p_old = pv, s_old = sv;
-        adagrad4(pv, gv, sv, af.lr, af.wd, af.eps);
-        if (bits_differ(pv, p_old)) p4[i] = pv;
-        if (bits_differ(sv, s_old)) s4[i] = sv;
-        if ((__float_as_uint(gv.x) | __float_as_uint(gv.y) | __float_as_uint(gv.z) | __float_as_uint(gv.w)) != 0u) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-
 template <int NB>
 __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *__restrict__ E, const float *__restrict__ R,
                                                                   int d, int scorer, const PrefixDev p,
@@ -420,20 +355,15 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
                                                                   const double *__restrict__ loss_partials,
                                                                   int n_partials, double *__restrict__ loss_out,
                                                                   float *__restrict__ dr_rows, float *__restrict__ de_rows,
-                                                                  int distinct, const AdagradFuse af, int B_rows)
+                                                                  int distinct)
 {
     // blockIdx.y: 128-column chunk of the row (rows longer than 128 floats per half: the chunks were a loop of dependent
     // round trips inside one workgroup -- 21 us at DistMult d = 512 -- and are workgroups of their own now)
-    if ((int)blockIdx.x >= B_rows && blockIdx.y != 0) return;
-    if ((int)blockIdx.x > B_rows) {                      // okge_train_step: workgroups behind the loss reduction sweep the entity table
-        fused_entity_sweep(af, (int)blockIdx.x - B_rows - 1, (int)gridDim.x - B_rows - 1);
-        return;
-    }
     // dr_rows / de_rows ([B][ldq] each, or nullptr): the relation- / entity-gradient row of every batch row is STORED there
     // instead of being added into dR / dE with float atomics -- row_segment_sum_kernel then adds up the rows of each
     // relation / entity (okge_prefix_backward_segmented)
-    if ((int)blockIdx.x == B_rows) {
-        if (loss_partials) loss_reduce_block(loss_partials, n_partials, loss_out);
+    if (blockIdx.x == gridDim.x - 1) {                   // the workgroup behind the batch rows: the deterministic loss reduction
+        if (blockIdx.y == 0 && loss_partials) loss_reduce_block(loss_partials, n_partials, loss_out);
         return;
     }
     const int b = blockIdx.x, grp = threadIdx.x >> 2, sq = threadIdx.x & 3;
@@ -735,7 +665,7 @@ __global__ __launch_bounds__(256) void adagrad2_kernel(const AdagradSeg a, const
 // cleared -- such rows still run through the arithmetic (the reference's wd * p reaches ALL rows) on p and sum alone.
 // The stamp is never erased: the caller moves to another stamp after every update (a stale byte that meets its stamp again
 // 255 updates later only costs the read of a gradient row that is zero).
-struct AdagradSegsDev { AdagradSegM s[ADAGRAD_MAX_SEGS]; int n, unroll; };
+struct AdagradSegsDev { AdagradSegM s[ADAGRAD_MAX_SEGS]; int n; };
 
 // (U iterations of the grid-stride loop side by side: the map byte decides whether the gradient is loaded at all, so one
 //  iteration is TWO dependent round trips -- run one at a time the sweep was latency-bound, slower than the map-less one)
@@ -759,21 +689,13 @@ __device__ __forceinline__ void adagrad_sweep_map(const AdagradSegM sg, float lr
             if (MAP) mb[u] = sg.touched[shift >= 0 ? (uint32_t)i >> shift : (uint32_t)i / row4];
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            live[u] = ok[u] && mb[u] == stamp;
-            if (MAP && sg.rows == 1) { ok[u] = ok[u] && !live[u]; live[u] = false; }     // unstamped rows only (never a gradient read)
-            if (MAP && sg.rows == 2) ok[u] = live[u];                                     // stamped rows only
-        }
+        for (int u = 0; u < U; ++u) live[u] = ok[u] && mb[u] == stamp;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + u * stride;
-            pv[u] = sv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            pv[u] = sv[u] = gv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (ok[u]) { pv[u] = p4[i]; sv[u] = s4[i]; }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            gv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (live[u]) gv[u] = g4[i0 + u * stride];
+            if (live[u]) gv[u] = g4[i];
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -802,55 +724,14 @@ __device__ __forceinline__ void adagrad_sweep_map(const AdagradSegM sg, float lr
     }
 }
 
-// rows == 1 on its own launch: the weight-decay-only update of the rows WITHOUT the stamp, built to run BESIDE the step's matrix
-// kernels on another stream -- one-wave workgroups and few registers, so that a wave fits the register file the fused tile
-// kernel leaves over (230 x 2 of 512 per SIMD at d = 256); two rows in flight per lane
-__global__ __launch_bounds__(64) void adagrad_unstamped_kernel(const AdagradSegsDev segs, float lr, float wd, float eps)
-{
-    const int64_t first = (int64_t)blockIdx.x * 64 + threadIdx.x, stride = (int64_t)gridDim.x * 64;
-    for (int k = 0; k < segs.n; ++k) {
-        const AdagradSegM sg = segs.s[k];
-        if (!sg.touched || sg.rows != 1) continue;
-        const int64_t n4 = sg.n >> 2;
-        float4 *p4 = reinterpret_cast<float4 *>(sg.p), *s4 = reinterpret_cast<float4 *>(sg.s);
-        const uint32_t row4 = (uint32_t)(sg.row_len >> 2);
-        const int shift = (row4 & (row4 - 1)) == 0 ? 31 - __clz(row4) : -1;
-        const uint8_t stamp = (uint8_t)sg.stamp;
-        for (int64_t i0 = first; i0 < n4; i0 += 2 * stride) {
-            const int64_t i1 = i0 + stride;
-            const bool ok1 = i1 < n4;
-            const uint8_t m0 = sg.touched[shift >= 0 ? (uint32_t)i0 >> shift : (uint32_t)i0 / row4];
-            const uint8_t m1 = ok1 ? sg.touched[shift >= 0 ? (uint32_t)i1 >> shift : (uint32_t)i1 / row4] : stamp;
-            float4 pa = p4[i0], sa = s4[i0], pb = pa, sb = sa;
-            if (ok1) { pb = p4[i1]; sb = s4[i1]; }
-            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (m0 != stamp) {
-                const float4 po = pa, so = sa;
-                adagrad4(pa, zero, sa, lr, wd, eps);
-                if (bits_differ(pa, po)) p4[i0] = pa;
-                if (bits_differ(sa, so)) s4[i0] = sa;
-            }
-            if (ok1 && m1 != stamp) {
-                const float4 po = pb, so = sb;
-                adagrad4(pb, zero, sb, lr, wd, eps);
-                if (bits_differ(pb, po)) p4[i1] = pb;
-                if (bits_differ(sb, so)) s4[i1] = sb;
-            }
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void adagrad_multi_kernel(const AdagradSegsDev segs, float lr, float wd, float eps)
 {
     const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
 #pragma unroll
     for (int k = 0; k < ADAGRAD_MAX_SEGS; ++k)
         if (k < segs.n) {
-            if (segs.s[k].touched) {
-                if (segs.unroll == 4) adagrad_sweep_map<4, true>(segs.s[k], lr, wd, eps, first, stride);
-                else if (segs.unroll == 2) adagrad_sweep_map<2, true>(segs.s[k], lr, wd, eps, first, stride);
-                else adagrad_sweep_map<1, true>(segs.s[k], lr, wd, eps, first, stride);
-            } else adagrad_sweep_map<1, false>(segs.s[k], lr, wd, eps, first, stride);
+            if (segs.s[k].touched) adagrad_sweep_map<4, true>(segs.s[k], lr, wd, eps, first, stride);
+            else adagrad_sweep_map<1, false>(segs.s[k], lr, wd, eps, first, stride);
         }
 }
 
@@ -1311,35 +1192,27 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
                                   float *dR, const double *loss_partials, int n_partials, double *loss_out,
                                   hipStream_t st, const int32_t *rel_order, const int32_t *rel_seg_ptr, int n_rel_seg,
                                   const int32_t *ent_order, const int32_t *ent_seg_ptr, int n_ent_seg, float *grad_rows,
-                                  int distinct, const AdagradFuse *fuse)
+                                  int distinct)
 {
     const int B = p.n_po + p.n_sp;
     if (B <= 0) return hipSuccess;
     const bool vec = scorer == SC_COMPLEX ? (d % 8 == 0) : (d % 4 == 0);       // (ComplEx: float4 over each half)
-    if (fuse && !vec) return hipErrorInvalidValue;
     if (vec) {
         // grad_rows: [2][Bpad][ldq] scratch -- relation rows, then entity rows
         const bool seg_r = grad_rows && rel_order && rel_seg_ptr && n_rel_seg > 0;
         const bool seg_e = grad_rows && ent_order && ent_seg_ptr && n_ent_seg > 0;
         float *dr_rows = seg_r ? grad_rows : nullptr, *de_rows = seg_e ? grad_rows + (size_t)Bpad * ldq : nullptr;
-        AdagradFuse af = {};
-        int sweep_wgs = 0;
-        if (fuse) {
-            af = *fuse;
-            sweep_wgs = (int)std::min<int64_t>(16384, (af.n_ent * (d / 4) + 127) / 128);     // one float4 per thread up to 2 M of them
-        }
         const int cols = scorer == SC_COMPLEX ? d / 2 : d;
-        const int chunks = fuse ? 1 : std::min(8, (cols + 127) / 128);       // (the fused sweep's workgroups count on a 1-D grid)
+        const int chunks = std::min(8, (cols + 127) / 128);
         if (sc_is_bias(scorer)) {
-            if (fuse) return hipErrorInvalidValue;       // (okge_train_step refuses the data-bias scorers)
             if (hipError_t e = launch_bias_prefix_rows(d, scorer, p, slab, nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials,
                                                        n_partials, loss_out, dr_rows, de_rows, distinct, st); e != hipSuccess) return e;
         } else if (nsplit >= 8)
-            hipLaunchKernelGGL(prefix_backward_vec_kernel<8>, dim3(B + 1 + sweep_wgs, chunks), dim3(128), 0, st, E, R, d, scorer, p, slab,
-                               nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials, n_partials, loss_out, dr_rows, de_rows, distinct, af, B);
+            hipLaunchKernelGGL(prefix_backward_vec_kernel<8>, dim3(B + 1, chunks), dim3(128), 0, st, E, R, d, scorer, p, slab,
+                               nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials, n_partials, loss_out, dr_rows, de_rows, distinct);
         else
-            hipLaunchKernelGGL(prefix_backward_vec_kernel<1>, dim3(B + 1 + sweep_wgs, chunks), dim3(128), 0, st, E, R, d, scorer, p, slab,
-                               nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials, n_partials, loss_out, dr_rows, de_rows, distinct, af, B);
+            hipLaunchKernelGGL(prefix_backward_vec_kernel<1>, dim3(B + 1, chunks), dim3(128), 0, st, E, R, d, scorer, p, slab,
+                               nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials, n_partials, loss_out, dr_rows, de_rows, distinct);
         if (seg_r || seg_e) {
             const RowSegments rel{rel_order, rel_seg_ptr, seg_r ? n_rel_seg : 0}, ent{ent_order, ent_seg_ptr, seg_e ? n_ent_seg : 0};
             hipLaunchKernelGGL(row_segment_sum_kernel, dim3(rel.n_seg + ent.n_seg), dim3(128), 0, st, dr_rows, de_rows, ldq, d, p,
@@ -1355,15 +1228,6 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
         if (loss_partials)
             hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, loss_partials, n_partials, loss_out);
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_adagrad_finish(const AdagradFuse &af, const PrefixDev &p, hipStream_t st)
-{
-    const int B = p.n_po + p.n_sp;
-    const int r_wgs = (int)std::min<int64_t>(256, ((int64_t)af.n_rel * (af.d / 4) + 127) / 128);
-    if (B + r_wgs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(adagrad_finish_kernel, dim3(B + r_wgs), dim3(128), 0, st, af, p, B);
     return hipGetLastError();
 }
 
@@ -1443,21 +1307,12 @@ hipError_t launch_adagrad_multi(const AdagradSegM *segs, int n_segs, float lr, f
     AdagradSegsDev a;
     std::memset(&a, 0, sizeof(a));
     a.n = n_segs;
-    static const int unroll = getenv("OKGE_ADAGRAD_U") ? atoi(getenv("OKGE_ADAGRAD_U")) : 4;
-    a.unroll = unroll;
     int64_t n4 = 0;
     for (int k = 0; k < n_segs; ++k) {
         a.s[k] = segs[k];
         n4 = std::max(n4, (segs[k].n + 3) / 4);
     }
     if (n4 <= 0) return hipSuccess;
-    bool all_unstamped = true;
-    for (int k = 0; k < n_segs; ++k) all_unstamped = all_unstamped && segs[k].rows == 1 && segs[k].touched;
-    if (all_unstamped) {                                 // the lean kernel that runs beside the matrix kernels
-        const int blocks = (int)std::min((int64_t)32768, (n4 + 127) / 128);
-        hipLaunchKernelGGL(adagrad_unstamped_kernel, dim3(blocks), dim3(64), 0, st, a, lr, wd, eps);
-        return hipGetLastError();
-    }
     const int blocks = (int)std::min((int64_t)16384, (n4 + 255) / 256);
     hipLaunchKernelGGL(adagrad_multi_kernel, dim3(blocks), dim3(256), 0, st, a, lr, wd, eps);
     return hipGetLastError();

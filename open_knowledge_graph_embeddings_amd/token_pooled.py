@@ -91,6 +91,9 @@ class PoolEngine:
         self.lib = N.lib()
         self._ws, self._ws_bytes = None, 0
         self._state, self._state_bytes = None, 0
+        # token-table scatter of the backward: "plan" = store-and-sum (bit-reproducible, okge.h) wherever it applies,
+        # "atomics" = float atomics everywhere (the path max pooling and d % 4 != 0 always take)
+        self.scatter = "plan"
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -128,7 +131,7 @@ class PoolEngine:
 
 
     # -- a batch of _encode calls in one go (okge_pool_encode_calls / okge_pool_backward_calls) ----------------------
-    def _calls(self, calls, backward, stamp_forward=False):
+    def _calls(self, calls, backward):
         """calls: [(slot, ids, first_id, n, raw, out_or_d_out, saved)] with n > 0 -> (ctypes array, keep-alive list)"""
         arr = (N.PoolCall * len(calls))()
         keep, need = [], 0
@@ -148,8 +151,6 @@ class PoolEngine:
                     x.row_touched, x.touched_stamp = touched.data_ptr(), int(slot.stamp)
             else:
                 x.out = other.data_ptr()
-                if stamp_forward and getattr(slot, "touched", None) is not None:      # the forward stamps every token row it reads
-                    x.row_touched, x.touched_stamp = slot.touched.data_ptr(), int(slot.stamp)
             need += int(self.lib.okge_pool_workspace_bytes(int(n), slot.d))
         if backward and self.scatter_plan(calls):
             need = int(self.lib.okge_pool_backward_workspace_bytes(arr, len(calls)))
@@ -164,16 +165,14 @@ class PoolEngine:
         return arr, keep
 
     def scatter_plan(self, calls):
-        """store-and-sum scatter (bit-reproducible, okge.h) where it applies; OKGE_POOL_SCATTER=atomics keeps the old path"""
-        if os.environ.get("OKGE_POOL_SCATTER", "plan") == "atomics":
-            return False
-        return all(c[0].pool != "max" and c[0].d % 4 == 0 for c in calls)
+        """store-and-sum scatter (bit-reproducible, okge.h) where it applies, unless self.scatter asks for the atomics"""
+        return self.scatter != "atomics" and all(c[0].pool != "max" and c[0].d % 4 == 0 for c in calls)
 
-    def encode_calls(self, calls, training, stamp=False):
+    def encode_calls(self, calls, training):
         calls = [c for c in calls if c[3] > 0]
         if not calls:
             return
-        arr, keep = self._calls(calls, False, stamp_forward=stamp and training)
+        arr, keep = self._calls(calls, False)
         N.check(self.lib.okge_pool_encode_calls(arr, len(calls), int(training), None if self._ws is None else self._ws.data_ptr(),
                                                 self._ws_bytes, self._stream()), "okge_pool_encode_calls")
         del keep
@@ -206,7 +205,7 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
     (Trainer.compute_one_batch, trainer.py:181-257, over model.py:762-796)."""
 
     def __init__(self, entity: TokenSlot, relation: TokenSlot, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8,
-                 label_smoothing=0.0, dropout=0.0, seed=0, engine=None, overlap_sweep=None, decay_window=None):
+                 label_smoothing=0.0, dropout=0.0, seed=0, engine=None, decay_window=None):
         super().__init__(entity, relation, scorer, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
                          label_smoothing=label_smoothing, dropout=dropout, seed=seed, engine=engine)
         # decay_window (OKGE_LAZY_DECAY; 1 = every row every step): the reference's Adagrad moves EVERY token row in
@@ -229,23 +228,10 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
         self.decay_window = max(1, int(decay_window)) if lazy_ok else 1
         self._counters = torch.zeros(2, dtype=torch.int32, device=entity.W.device)      # [optimizer steps taken, scratch]
         self._pending = None              # (lr, weight_decay, eps) of the deferred steps; None: every row is current
-        # overlap_sweep (OKGE_OVERLAP_SWEEP=1; an experiment, OFF by default): the Adagrad update of the token rows NO token of the
-        # batch names (85 % of them at configs[4]; the reference's weight decay reaches every row: 0.9 GB of read-modify-write per
-        # step) on a side stream BESIDE the step's matrix kernels -- the pooling forward stamps the rows it reads, so the others are
-        # known right behind it and nothing of the step reads or writes them.  Same arithmetic row for row (rows = 1 then rows = 2
-        # of okge_adagrad_multi; bit-equal tables: test_overlapped_sweep_is_bit_equal_to_the_plain_step).  Measured at configs[4]:
-        # the late sweep shrinks 178 -> ~25 us, but the fused tile kernel beside the side sweep stretches 292 -> 398 us and the
-        # encode launch 15 -> 43 us: 0.826 -> 0.852 ms cold, 0.725 -> 0.763 warm -- a loss (fp32 MFMA shares the SIMD's issue
-        # with the sweep's sqrt / div VALU work, profiles/round4_ablation.md section 5), like the S-FB attempt of round 2.
-        if overlap_sweep is None:
-            overlap_sweep = os.environ.get("OKGE_OVERLAP_SWEEP", "0") == "1"
-        self.overlap_sweep = bool(overlap_sweep)
-        self._side, self._side_done = None, None
         self.pool = PoolEngine(self.device)
         # (rounds 1-2 ran the five encode / backward calls of a step one by one, the relation slot's on a side stream:
         #  35 small launches; they now go to the library as ONE batch each way: three launches forward, three backward)
         self.saved = torch.zeros((5, 4 * entity.d), device=self.device)      # batch-norm statistics of the five encode calls
-        self._early_swept = False
 
     def state_tensors(self):
         self.flush()
@@ -323,7 +309,7 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
                 sl.running_mean, sl.running_var = next(si), next(si)
 
     def _encode(self, batch: H.PrefixBatch, bufs):
-        """catch-up of owed decay steps, the pooling (+ batch-norm) forward of the five calls, the early side-stream sweep"""
+        """catch-up of owed decay steps, then the pooling (+ batch-norm) forward of the five calls"""
         dev = self.device
         EV, EX, dEV, RV, RX, dRV = bufs
         ent, rel, pe = self.entity, self.relation, self.pool
@@ -342,25 +328,7 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
             self._settle_hparams()
             lr, wd, eps = self._hparams()
             pe.catch_up_calls(enc_calls, self.engine.lazy_tensors(self._lazy_tables()), self._counters, lr, wd, eps)
-        # (only inside step(): a caller that runs forward_backward alone -- the autograd bridge, ReplicaStep, whose other replicas'
-        #  rows receive gradients in the exchange -- gets no early update)
-        overlap = (self.overlap_sweep and self.decay_window == 1 and self._in_step and ent.touched is not None
-                   and rel.touched is not None and not torch.cuda.is_current_stream_capturing())
-        if self._side_done is not None:            # the previous step's side sweep wrote rows this forward may read
-            torch.cuda.current_stream(dev).wait_event(self._side_done)
-            self._side_done = None
-        pe.encode_calls(enc_calls, True, stamp=overlap)
-        self._early_swept = False
-        if overlap:
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=dev)
-            main = torch.cuda.current_stream(dev)
-            self._side.wait_event(main.record_event())       # the maps are complete: every row without the stamp is free
-            with torch.cuda.stream(self._side):
-                self.engine.adagrad_multi([(sl.W, sl.dW, sl.sumW, sl.touched, sl.stamp, 1) for sl in (ent, rel)],
-                                          self.lr, self.weight_decay, self.eps)
-                self._side_done = self._side.record_event()
-            self._early_swept = True
+        pe.encode_calls(enc_calls, True)
         return calls
 
     def _backward(self, batch, bufs, calls):
@@ -386,11 +354,8 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
             self._after_update()
             return
         # one launch: token tables (gradient rows the backward did not stamp are neither read nor cleared) + batch-norm parameters
-        # (after an early sweep of the unstamped rows -- forward_backward, overlap_sweep -- only the stamped rows are left)
-        rows = 2 if self._early_swept else 0
-        tensors = [(sl.W, sl.dW, sl.sumW, sl.touched, sl.stamp, rows) for sl in (e, r)]
+        tensors = [(sl.W, sl.dW, sl.sumW, sl.touched, sl.stamp) for sl in (e, r)]
         tensors += [(sl.bn, sl.d_bn, sl.sum_bn) for sl in (e, r) if sl.bn is not None]
-        self._early_swept = False
         eng.adagrad_multi(tensors, self.lr, self.weight_decay, self.eps)
         self._after_update()
 

@@ -89,15 +89,10 @@ class VirtualTableStep:
         self.loss_out = torch.zeros(1, dtype=torch.float64, device=self.device)
         self.step_dev = None              # device step counter, attached by GraphedTrainStep
         self.module_batchnorms = ()       # ((slot, nn.BatchNorm1d), ...) of an attached module, set by its train_step()
-        self._in_step = False
 
     def step(self, batch: H.PrefixBatch, normalizer=None):
         """`batch` carries ENTITY / RELATION ids exactly as for the lookup models."""
-        self._in_step = True
-        try:
-            loss = self.forward_backward(batch, normalizer)
-        finally:
-            self._in_step = False
+        loss = self.forward_backward(batch, normalizer)
         self.optimizer_step()
         return loss
 

@@ -33,9 +33,9 @@ def test_scorer_kinds_in_the_binding():
     assert N.SCORERS["complex"] == 0 and N.SCORERS["distmult"] == 1
 
 
-def test_header_carries_the_two_enum_values_at_abi_version_1():
+def test_header_carries_the_two_enum_values_at_abi_version_2():
     text = open(os.path.join(ROOT, "include", "okge.h")).read()
-    assert re.search(r"#define\s+OKGE_ABI_VERSION\s+1\b", text)
+    assert re.search(r"#define\s+OKGE_ABI_VERSION\s+2\b", text)
     enum = re.search(r"enum\s+okge_scorer\s*\{(.*?)\};", text, re.S).group(1)
     assert re.search(r"OKGE_BIAS_RELATION\s*=\s*2\b", enum) and re.search(r"OKGE_BIAS_ENTITY\s*=\s*3\b", enum)
     assert "model.py:281-350" in enum
@@ -111,7 +111,7 @@ def test_entity_model_keeps_relation_parameters_out_of_the_autograd_bridge():
 
 @pytest.mark.parametrize("scorer", BIAS)
 def test_c_abi_refusals_come_before_any_device_work(scorer):
-    """okge_score_triples, okge_train_step, okge_fold_queries, okge_evaluate_fused_shard: OKGE_ERR_UNSUPPORTED with a message
+    """okge_score_triples, okge_fold_queries, okge_evaluate_fused_shard: OKGE_ERR_UNSUPPORTED with a message
     naming the scorer, from the argument checks alone -- host buffers stand in for device memory, nothing reads or writes
     them (their sentinels stay), no device is needed.  An unknown scorer id is still OKGE_ERR_INVALID."""
     import ctypes
@@ -129,13 +129,10 @@ def test_c_abi_refusals_come_before_any_device_work(scorer):
     pb.n_po = 3
     c = N.Candidates()
     c.first_id, c.n = 0, 5
-    pos, opt, sh = N.Positives(), N.AdagradOpt(), N.Shard()
-    opt.sum_E = opt.sum_R = opt.prefix_flags = p
+    sh = N.Shard()
     sh.ent_lo, sh.ent_hi = 0, 10
     calls = {
         "okge_score_triples": lambda: L.okge_score_triples(kind, p, 12, p, 12, p, 12, 5, 12, p, None),
-        "okge_train_step": lambda: L.okge_train_step(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), ctypes.byref(pos), 0, 0.0, 1.0, 0,
-                                                     ctypes.byref(opt), p, p, p, p, buf.nbytes, None),
         "okge_fold_queries": lambda: L.okge_fold_queries(ctypes.byref(t), ctypes.byref(pb), p, 16, p, None),
         "okge_evaluate_fused_shard": lambda: L.okge_evaluate_fused_shard(1, ctypes.byref(t), ctypes.byref(sh), p, 16, 3, ctypes.byref(c), 5, q,
                                                                          None, 0, q, q, q, 3, p, p, p, buf.nbytes, None),

@@ -18,7 +18,7 @@ def test_header_symbols_exported():
     assert declared == set(_native.EXPORTS), declared ^ set(_native.EXPORTS)
     for sym in declared:
         assert getattr(L, sym) is not None
-    assert L.okge_abi_version() == 1
+    assert L.okge_abi_version() == 2
 
 
 def test_workspace_query_and_argument_errors():

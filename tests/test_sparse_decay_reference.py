@@ -82,7 +82,7 @@ def test_fused_train_step_decay_window_surface():
     from open_knowledge_graph_embeddings_amd.train_step import FusedTrainStep
     E, R = torch.zeros(6, 8), torch.zeros(3, 8)
     st = FusedTrainStep(E, R, "complex", sparse=True, weight_decay=1e-10, decay_window=4, engine=object())
-    assert st.decay_window == 4 and st.dE is None and not st.fuse_update and st._pending is None
+    assert st.decay_window == 4 and st.dE is None and st._pending is None
     assert st.rowsE.dtype == torch.int32 and st.rowsE.shape == (6,) and st.rowsR.shape == (3,) and st._counters.tolist() == [0, 0]
     with pytest.raises(NotImplementedError, match="multiple of 4"):
         FusedTrainStep(torch.zeros(6, 6), torch.zeros(3, 6), "complex", sparse=True, weight_decay=1e-10, decay_window=4, engine=object())

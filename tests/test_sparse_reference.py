@@ -102,16 +102,8 @@ def test_fused_train_step_sparse_refusals():
     with pytest.raises(NotImplementedError, match="accumulate"):
         FusedTrainStep(E, R, "complex", weight_decay=0.0, sparse=True, accumulate=2, engine=object())
     st = FusedTrainStep(E, R, "distmult", weight_decay=0.0, sparse=True, engine=object())
-    assert st.dE is None and st.dR is None and not st.fuse_update
+    assert st.dE is None and st.dR is None
     assert [t.data_ptr() for t in st.state_tensors()] == [t.data_ptr() for t in (st.E, st.R, st.sumE, st.sumR)]
-
-
-def test_fused_train_step_sparse_ignores_fused_update(monkeypatch):
-    from open_knowledge_graph_embeddings_amd.train_step import FusedTrainStep
-    monkeypatch.setenv("OKGE_FUSED_UPDATE", "1")
-    E, R = torch.zeros(6, 8), torch.zeros(3, 8)
-    assert FusedTrainStep(E, R, "complex", weight_decay=0.0, engine=object()).fuse_update
-    assert not FusedTrainStep(E, R, "complex", weight_decay=0.0, sparse=True, engine=object()).fuse_update
 
 
 def _meta(n_ent, n_rel):

@@ -234,7 +234,7 @@ def _plan_step(c, scorer="complex", **kw):
 
 
 @pytest.mark.parametrize("case", ["short", "long_one_window", "long_two_windows", "mean_bn", "d256_bn"])
-def test_scatter_plan_matches_oracle_and_is_bit_reproducible(okge_lib, monkeypatch, case):
+def test_scatter_plan_matches_oracle_and_is_bit_reproducible(okge_lib, case):
     """the same step three times from cleared gradients: token-table gradients EQUAL bit for bit (the atomics' sums moved in
     the last bits), within tolerance of the float64 oracle and of the atomics path; every segment class is met"""
     rng = np.random.default_rng({"short": 1, "long_one_window": 2, "long_two_windows": 3, "mean_bn": 4, "d256_bn": 5}[case])
@@ -268,8 +268,8 @@ def test_scatter_plan_matches_oracle_and_is_bit_reproducible(okge_lib, monkeypat
         stamped = sl.touched == sl.stamp
         assert bool((stamped | ~nz).all()), "a row with a gradient is not stamped"
     # the atomics path on the same inputs
-    monkeypatch.setenv("OKGE_POOL_SCATTER", "atomics")
     st2, e2, r2, b2 = _plan_step(c)
+    st2.pool.scatter = "atomics"
     st2.forward_backward(b2)
     torch.cuda.synchronize()
     for a, o in ((e2.dW, runs[0][0]), (r2.dW, runs[0][1])):
@@ -293,44 +293,6 @@ def test_touched_map_adagrad_is_bit_equal_to_the_dense_sweep(okge_lib):
     for x, y in ((a[1], b_[1]), (a[2], b_[2])):
         assert torch.equal(x.W, y.W) and torch.equal(x.sumW, y.sumW) and torch.equal(x.bn, y.bn)
         assert float(x.dW.abs().max()) == 0.0                    # cleared where stamped, zero elsewhere
-
-
-def test_overlapped_sweep_is_bit_equal_to_the_plain_step(okge_lib):
-    """overlap_sweep: the update of the token rows no token of the batch names runs on a side stream beside the step's matrix
-    kernels (rows = 1 of okge_adagrad_multi right behind the pooling forward, rows = 2 after the backward) -- same arithmetic
-    row for row: tables, accumulators, batch-norm parameters and losses bit-equal to the step without it, over several steps
-    with DIFFERENT batches (the next forward must wait for the side sweep of the step before)"""
-    from open_knowledge_graph_embeddings_amd.hotpath import PrefixBatch, positives_from_dense
-    from open_knowledge_graph_embeddings_amd.token_pooled import TokenPooledTrainStep, TokenSlot
-    rng = np.random.default_rng(21)
-    c = _plan_case(rng, d=64, L=6, n_ent=2000, vt_e=5000, N=900, n_po=96, n_sp=96, bn=True, mid_tokens=(45,))
-
-    def make(overlap):
-        bn = c["bn_e"]
-        e = TokenSlot(dev(c["We"]), dev(c["ent_tok"]), "sum", True, dev(bn["weight"]), dev(bn["bias"]))
-        r = TokenSlot(dev(c["Wr"]), dev(c["rel_tok"]), "sum", True, dev(c["bn_r"]["weight"]), dev(c["bn_r"]["bias"]))
-        return TokenPooledTrainStep(e, r, "complex", lr=0.1, dropout=0.1, seed=3, overlap_sweep=overlap, decay_window=1), e, r
-    a, b_ = make(True), make(False)
-    assert a[0].overlap_sweep and not b_[0].overlap_sweep
-    r2 = np.random.default_rng(5)
-    for step in range(6):
-        N, B = 900, 192
-        y = np.zeros((B, N), np.float32)
-        y[np.arange(B), r2.integers(0, N, B)] = 1
-        mk = lambda: PrefixBatch(cand_ids=dev(r2_c), po_rel=dev(pr), po_obj=dev(po), sp_subj=dev(ss), sp_rel=dev(sr))   # noqa: E731
-        r2_c = r2.integers(2, 2000, N).astype(np.int32)
-        pr, po = r2.integers(2, 40, B // 2).astype(np.int32), r2.integers(2, 2000, B // 2).astype(np.int32)
-        ss, sr = r2.integers(2, 2000, B // 2).astype(np.int32), r2.integers(2, 40, B // 2).astype(np.int32)
-        losses = []
-        for st, _, _ in (a, b_):
-            bt = mk()
-            bt.pos_row, bt.pos_col = positives_from_dense(dev(y))
-            losses.append(float(st.step(bt)[0]))
-        assert losses[0] == losses[1], (step, losses)
-    torch.cuda.synchronize()
-    for x, y_ in ((a[1], b_[1]), (a[2], b_[2])):
-        assert torch.equal(x.W, y_.W) and torch.equal(x.sumW, y_.sumW) and torch.equal(x.bn, y_.bn) and torch.equal(x.sum_bn, y_.sum_bn)
-        assert float(x.dW.abs().max()) == 0.0
 
 
 def _lazy_problem(seed=31):
@@ -582,16 +544,16 @@ def test_twelve_reference_optimizer_steps_with_rows_no_batch_names(okge_lib, win
 
 
 @pytest.mark.parametrize("pool", ["max", "sum_atomics"])
-def test_lazy_decay_on_the_atomics_backward(okge_lib, monkeypatch, pool):
-    """the deferred decay behind the float-atomic token-table scatter (max pooling always takes it; OKGE_POOL_SCATTER=atomics for
-    the others): the backward's sums differ in the last bits from run to run there, so the rows a batch names are compared to a
+def test_lazy_decay_on_the_atomics_backward(okge_lib, pool):
+    """the deferred decay behind the float-atomic token-table scatter (max pooling always takes it; the pool engine's scatter = "atomics"
+    for the others): the backward's sums differ in the last bits from run to run there, so the rows a batch names are compared to a
     tolerance -- but every row NO batch named must still equal the eager run bit for bit after flush(), and the map must be clean"""
-    if pool == "sum_atomics":
-        monkeypatch.setenv("OKGE_POOL_SCATTER", "atomics")
     rng = np.random.default_rng(41)
     c = _plan_case(rng, d=64, L=5, n_ent=900, vt_e=6000, N=300, n_po=48, n_sp=48, pool="max" if pool == "max" else "sum", bn=True)
     a, b_ = _plan_step(c, decay_window=4), _plan_step(c, decay_window=1)
-    assert a[0].decay_window == 4 and not (pool == "max" and a[0].pool.scatter_plan([(a[1],)]))
+    if pool == "sum_atomics":
+        a[0].pool.scatter = b_[0].pool.scatter = "atomics"
+    assert a[0].decay_window == 4 and not a[0].pool.scatter_plan([(a[1],)])
     for _ in range(7):
         a[0].step(a[3])
         b_[0].step(b_[3])

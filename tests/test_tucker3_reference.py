@@ -165,7 +165,7 @@ def test_names_in_registry_header_and_exports():
            "okge_tucker3_apply", "okge_tucker3_outer"}
     assert new <= declared and new <= set(_native.EXPORTS)
     assert "okge_tucker3.hip" in _native.SOURCES
-    assert re.search(r"#define OKGE_ABI_VERSION 1\b", header)
+    assert re.search(r"#define OKGE_ABI_VERSION 2\b", header)
 
 
 def test_argument_errors_before_any_device_work():

@@ -123,7 +123,7 @@ def test_token_pooled_step_hands_the_engine_the_virtual_tables(bn):
     log = []
 
     class Pool:
-        def encode_calls(self, calls, training, stamp=False):
+        def encode_calls(self, calls, training):
             log.append("encode")
             self.encoded = [(c[0], c[3], c[4].data_ptr(), c[5].data_ptr(), c[6] is not None) for c in calls if c[3] > 0]
 

@@ -46,7 +46,7 @@ def main():
     for warm in (False, True):
         timed("adagrad_step2 (dense)", lambda st: eng.adagrad2(e["W"], e["g"], e["s"], r["W"], r["g"], r["s"], 0.1), warm)
         timed("adagrad_multi, no map", lambda st: eng.adagrad_multi([(e["W"], e["g"], e["s"]), (r["W"], r["g"], r["s"])], 0.1), warm)
-        timed(f"adagrad_multi, map (U={os.environ.get('OKGE_ADAGRAD_U', '4')})",
+        timed("adagrad_multi, map (U=4)",
               lambda st: eng.adagrad_multi([(e["W"], e["g"], e["s"], e["map"], st), (r["W"], r["g"], r["s"], r["map"], st)], 0.1), warm)
 
 
