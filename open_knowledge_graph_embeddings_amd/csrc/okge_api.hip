@@ -14,6 +14,7 @@
 
 #include "../../include/okge.h"
 #include "okge_kernels.h"
+#include "okge_plan.h"
 
 using namespace okge;
 
@@ -137,29 +138,10 @@ PrefixDev to_dev(const okge_prefix_batch &b, const okge_tables *t, const okge_sh
     return p;
 }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static_assert(sizeof(v8bf) == PLANE_CELL_BYTES && sizeof(TopkRec) == TOPK_REC_BYTES, "okge_plan.h sizes its regions with these");
 
-struct Geometry {
-    int    B, N, d, Bpad, D16, KB, LDK, ldq, ldg, tiles, b_split, b_per_block, nsplit;
-    int    sk_wgs, sk_chunks;   // > 0: the train tile kernel is launched stream-K shaped over sk_wgs workgroups (okge_train64k.hip)
-    // > 0: the LAST `tail_tiles` candidate tiles of the call (what is left over after whole rounds of one workgroup per CU)
-    // are launched apart with the batch rows split over tail_split workgroups each, so the closing round is short
-    int    tail_tiles, tail_split, tail_b_per_block;
-    // training sweeps the candidates in RANGES of range_n (a multiple of 64) so that the one (B, N)-shaped
-    // intermediate, G^T, and everything sized like it (masked rows Cm, KL statistics) is O(B x range_n):
-    // 41 GB -> 1 GB at |E| = 2.5 M, B = 4096.  A range is one tile-kernel launch + one dq launch (slabs accumulate).
-    int    range_n, n_ranges, range_tiles;
-    size_t off_Q, off_tptr, off_stats, off_lse, off_ysum, off_run, off_loss, off_GT, off_Cm, off_slab, off_dcs, off_Qp;
-    size_t score_bytes, lse_bytes, total;
-};
-
-int env_int(const char *name, int dflt)
-{
-    const char *v = std::getenv(name);
-    return v && *v ? std::atoi(v) : dflt;
-}
-
-// compute units of the current device (stream-K launches: one workgroup per CU); 256 where no device answers
+// compute units of the current device (stream-K launches: one workgroup per CU); 256 where no device answers.  The planner
+// (okge_plan.h) takes it as an argument.
 int cu_count()
 {
     static std::mutex mu;
@@ -172,136 +154,6 @@ int cu_count()
         cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
     }
     return cus[dev];
-}
-
-// Tail split of a launch of `tiles` equal tiles, one workgroup per CU (slot sizes up to 256): the `tail` tiles left over after
-// whole rounds would cost a whole round's time; launched apart with the rows split `split` ways they cost 1 / split of it.
-// Worth it when the rows per workgroup drop by at least two 64-row blocks.  (cfg4 shard: 4883 tiles = 19 rounds + 19 tiles.)
-struct TailSplit { int tiles, split, b_per_block; };
-TailSplit tail_split(int tiles, int Bpad, int slots)
-{
-    TailSplit t = {0, 0, Bpad};
-    const int bblks = Bpad / BC, tail = tiles % slots;
-    if (tiles <= slots || tail == 0 || env_int("OKGE_TAIL_SPLIT", 1) == 0) return t;
-    const int c = std::min(slots / tail, bblks);
-    if (c < 2) return t;
-    const int per = (bblks + c - 1) / c;
-    if (bblks - per < 2) return t;
-    t.tiles = tail;
-    t.b_per_block = per * BC;
-    t.split = (Bpad + t.b_per_block - 1) / t.b_per_block;
-    return t;
-}
-
-bool make_geometry(int B, int N, int d, Geometry &g)
-{
-    if (B <= 0 || N <= 0 || d <= 0) return false;
-    g.B = B; g.N = N; g.d = d;
-    g.Bpad = (B + BC - 1) / BC * BC;
-    // slot size padded to a width the tile kernels are instantiated for (zero columns are free of error,
-    // not of time: d in (128, 208] runs as 208, etc.)
-    const int kb = (d + 15) / 16;
-    g.KB = kb <= 4 ? 4 : kb <= 8 ? 8 : kb <= 13 ? 13 : kb <= 16 ? 16 : 32;
-    g.D16 = 16 * g.KB;
-    g.LDK = lds_ld(g.D16);
-    g.ldq = g.D16;
-    g.tiles = (N + NT - 1) / NT;
-    const int bblks = g.Bpad / BC;
-    // candidate ranges: G^T of one range stays under OKGE_GT_MBYTES (default 1024 MiB)
-    {
-        const int64_t budget = (int64_t)std::max(1, env_int("OKGE_GT_MBYTES", 1024)) << 20;
-        int64_t rt = budget / ((int64_t)g.Bpad * NT * (int64_t)sizeof(float));     // 64-candidate tiles per range
-        rt = std::max<int64_t>(1, std::min<int64_t>(rt, g.tiles));
-        g.range_tiles = (int)rt;
-        g.n_ranges = (g.tiles + g.range_tiles - 1) / g.range_tiles;
-        const int cus = cu_count();
-        if (g.n_ranges > 1 && g.KB <= 16 && rt >= cus) {
-            // slot sizes up to 256 run one workgroup per CU and tile: ranges of whole rounds (a multiple of the CU count: 256
-            // tiles on an MI355X), so that only the LAST range ends in a partial round -- the one the tail split below shortens
-            g.range_tiles = (int)(rt / cus * cus);
-        } else {
-            g.range_tiles = (g.tiles + g.n_ranges - 1) / g.n_ranges;              // even out the ranges
-        }
-        g.n_ranges = (g.tiles + g.range_tiles - 1) / g.range_tiles;
-        g.range_n = g.range_tiles * NT;
-    }
-    g.ldg = g.range_tiles * NT;
-    // fused train kernel: one 8-wave workgroup per CU on 64-candidate tiles (slot sizes above 256: fused_tile64k_kernel,
-    // candidate tile in registers)
-    const int slots = cu_count();
-    // fill the CUs: if there are few candidate tiles, split the batch rows across blockIdx.y.  Cost of a split into c:
-    // (rounds of workgroups over the slots) x (row blocks per workgroup + 1) -- the "+ 1" is a workgroup's fixed cost, the
-    // candidate gather and the gradient write-back, about one 64-row block (profiles/round2_ablation.md §1) -- plus the c
-    // partial-gradient slabs dc_reduce adds up (an eighth of a block each).  Measured at cfg3 on the retired 32-candidate cut
-    // (313 tiles of 32, d = 512):
-    // c = 1 / 2 / 3 / 4 / 8 -> 0.299 / 0.288 / 0.294 / 0.303 / 0.364 ms per step; the model orders them 18 / 15 / 16 / 15 / 20.
-    int bs = 1;
-    {
-        long best = -1;
-        for (int c = 1; c <= bblks; ++c) {
-            const long rounds = ((long)g.tiles * c + slots - 1) / slots, per = (bblks + c - 1) / c;
-            const long cost = 8 * rounds * (per + 1) + c;
-            if (best < 0 || cost < best) { best = cost; bs = c; }
-        }
-    }
-    bs = std::max(1, env_int("OKGE_B_SPLIT", bs));
-    bs = std::min(bs, bblks);
-    g.b_per_block = (bblks + bs - 1) / bs * BC;
-    g.b_split = (g.Bpad + g.b_per_block - 1) / g.b_per_block;
-    if (g.n_ranges > 1) { g.b_split = 1; g.b_per_block = g.Bpad; }   // many tiles: no batch split
-    // slot sizes above 256 (fused_tile64k_kernel), one launch: (tile, 32-row chunk) units in equal runs over one workgroup
-    // per CU instead of a (tiles, batch splits) grid -- see the kernel's header for the measurements behind it
-    g.sk_wgs = g.sk_chunks = 0;
-    if (g.KB == 32 && g.n_ranges == 1 && env_int("OKGE_STREAMK", 1) != 0 && env_int("OKGE_B_SPLIT", 0) == 0) {
-        g.sk_chunks = (B + 31) / 32;
-        const int64_t units = (int64_t)g.tiles * g.sk_chunks;
-        g.sk_wgs = (int)std::min<int64_t>(std::min(cu_count(), 511), units);
-        g.b_split = 1;
-        g.b_per_block = g.Bpad;
-    }
-    // tail split (slot sizes up to 256, more tiles than CUs): equal tiles in rounds of one per CU leave a closing round with
-    // `tail` < 256 workgroups that still takes a whole round's time (cfg4 shard: 4883 tiles = 19 rounds + 19 tiles -> 20 rounds,
-    // 4.6 % of the kernel idle).  The tail tiles are launched apart with the rows split floor(256 / tail) ways; their partial
-    // candidate gradients go through the batch-split slabs + dc_reduce.  Worth it when the rows per workgroup drop by >= 2 blocks.
-    g.tail_tiles = g.tail_split = 0;
-    g.tail_b_per_block = g.Bpad;
-    if (g.KB <= 16 && g.b_split == 1) {
-        const TailSplit ts = tail_split(g.tiles - (g.n_ranges - 1) * g.range_tiles, g.Bpad, slots);
-        if (ts.split > 1) { g.tail_tiles = ts.tiles; g.tail_split = ts.split; g.tail_b_per_block = ts.b_per_block; }
-    }
-    // dQ kernel: (batch block, candidate range) workgroups, 8 waves, one per CU
-    int ns = std::max(1, cu_count() / bblks);
-    if (ns >= 8) ns = ns / 8 * 8;   // workgroups of one candidate range then share an XCD (blockIdx % 8)
-    ns = env_int("OKGE_DQ_SPLIT", ns);
-    ns = std::max(1, std::min(ns, g.range_tiles));
-    g.nsplit = ns;
-    size_t off = 0;
-    // [score-only part] the query block
-    g.off_Q = off;     off += align_up((size_t)g.Bpad * g.ldq * sizeof(float), 256);
-    g.score_bytes = off;
-    // [row log-sum-exp part] per-range (max, sum-exp) tile statistics + the running per-row state
-    // (the tile offsets here and the loss partials below keep room for 32-candidate tiles, so that okge_train_workspace_bytes
-    //  answers as it did before that cut was retired)
-    g.off_tptr = off;  off += align_up((size_t)(2 * g.tiles + 1) * sizeof(int32_t), 256);
-    g.off_stats = off; off += align_up((size_t)4 * g.range_tiles * g.Bpad * 2 * sizeof(float), 256);   // <= 4 per tile
-    g.off_lse = off;   off += align_up((size_t)g.Bpad * sizeof(float), 256);
-    g.off_ysum = off;  off += align_up((size_t)g.Bpad * sizeof(float), 256);
-    g.off_run = off;   off += align_up((size_t)g.Bpad * 2 * sizeof(float), 256);
-    g.lse_bytes = off;
-    // [training part]
-    g.off_loss = off;  off += align_up((size_t)std::max(2 * g.tiles * g.b_split + g.tail_tiles * g.tail_split, g.sk_wgs) * sizeof(double), 256);
-    g.off_GT = off;    off += align_up((size_t)g.Bpad * g.ldg * sizeof(float), 256);
-    // masked candidate rows of a range: three bf16 planes (6 bytes per element) up to slot size 208, fp32 rows above
-    g.off_Cm = off;    off += align_up(g.KB <= 13 ? (size_t)g.range_tiles * plane_cells_per_tile(g.D16) * sizeof(v8bf)
-                                                  : (size_t)g.range_tiles * NT * g.D16 * sizeof(float), 256);
-    g.off_slab = off;  off += align_up((size_t)g.nsplit * g.Bpad * g.ldq * sizeof(float), 256);
-    g.off_dcs = off;   off += g.sk_wgs > 0 ? align_up((size_t)2 * g.sk_wgs * NT * g.D16 * sizeof(float), 256)
-                                     : g.b_split > 1 ? align_up((size_t)g.b_split * g.tiles * NT * g.D16 * sizeof(float), 256)
-                                     : g.tail_split > 1 ? align_up((size_t)g.tail_split * g.tail_tiles * NT * g.D16 * sizeof(float), 256) : 0;
-    // the folded queries once more as three bf16 planes, for the tile kernel's gradient product (okge_tile_grad_split.h)
-    g.off_Qp = off;    off += tile_grad_split(g.KB) ? align_up((size_t)g.Bpad * g.D16 * 6, 256) : 0;
-    g.total = off;
-    return true;
 }
 
 bool known_scorer(int32_t scorer)
@@ -335,7 +187,8 @@ int check_common(const okge_tables *t, const okge_prefix_batch *b, const okge_ca
     return OKGE_OK;
 }
 
-void fill_fused_common(FusedArgs &a, const Geometry &g, const okge_tables *t, const okge_candidates *c, char *ws)
+// the arguments every tile launch shares; Q: the folded queries.  b_per_block: all rows (the sweeps; train_core sets its split)
+void fill_fused_common(FusedArgs &a, const Shape &s, const okge_tables *t, const okge_candidates *c, const float *Q)
 {
     std::memset(&a, 0, sizeof(a));
     a.E = c->table ? c->table : t->E;       // table the candidate rows are gathered from
@@ -343,15 +196,15 @@ void fill_fused_common(FusedArgs &a, const Geometry &g, const okge_tables *t, co
     a.id_err = id_err_ptr();
     a.cand_ids = c->ids;
     a.cand_first = c->first_id;
-    a.Q = ws ? reinterpret_cast<const float *>(ws + g.off_Q) : nullptr;
+    a.Q = Q;
     a.drop_c = to_dev(c->drop);
-    a.d = g.d; a.KB = g.KB; a.LDK = g.LDK; a.N = g.N; a.B = g.B; a.Bpad = g.Bpad; a.ldq = g.ldq; a.ldg = g.ldg;
-    a.b_per_block = g.b_per_block;
+    a.d = s.d; a.KB = s.KB; a.LDK = s.LDK; a.N = s.N; a.B = s.B; a.Bpad = s.Bpad; a.ldq = s.ldq;
+    a.b_per_block = s.Bpad;
 }
 
 
 // Arguments of the tiles from `t0` on of a launch: every per-tile pointer and the candidate window move with them
-FusedArgs tile_window(const FusedArgs &base, const Geometry &g, int t0)
+FusedArgs tile_window(const FusedArgs &base, const Shape &s, int t0)
 {
     FusedArgs a = base;
     a.N = base.N - t0 * NT;
@@ -360,139 +213,118 @@ FusedArgs tile_window(const FusedArgs &base, const Geometry &g, int t0)
     a.cand_col0 += t0 * NT;
     if (a.tile_ptr) a.tile_ptr += t0;
     if (a.loss_partial) a.loss_partial += t0;
-    if (a.G) a.G += (size_t)t0 * (g.Bpad / BC) * (BC * NT);
-    if (a.Cm) a.Cm += (size_t)t0 * NT * g.D16;
-    if (a.Cplanes) a.Cplanes += (size_t)t0 * plane_cells_per_tile(g.D16);
+    if (a.G) a.G += (size_t)t0 * (s.Bpad / BC) * (BC * NT);
+    if (a.Cm) a.Cm += (size_t)t0 * NT * s.D16;
+    if (a.Cplanes) a.Cplanes += (size_t)t0 * plane_cells_per_tile(s.D16);
     if (a.X) a.X += (size_t)t0 * NT;
-    if (a.stats) a.stats += (size_t)t0 * g.Bpad * 2;
+    if (a.stats) a.stats += (size_t)t0 * s.Bpad * 2;
     if (a.rk_slab) a.rk_slab += (size_t)t0 * a.rk_ngroups;
-    if (a.tk_part) a.tk_part += (size_t)t0 * g.Bpad * a.tk_k;
+    if (a.tk_part) a.tk_part += (size_t)t0 * s.Bpad * a.tk_k;
     return a;
 }
 
-// the score sweep (MODE_SCORE / _STATS / _COUNT) of `tiles` 64-candidate tiles over all B rows: the 64 x 64 kernel up to slot size
-// 256 (rows are independent: the tail tiles simply run as (tile, row split) workgroups); above, the register-tile kernel in a
-// stream-K launch (no partial outputs to add up)
-hipError_t launch_score_sweep(const Geometry &g, const FusedArgs &a0, int tiles, hipStream_t st, int mode = MODE_SCORE)
+// the score sweep (MODE_SCORE / _STATS / _COUNT / _TOPK) of p.tiles 64-candidate tiles over all B rows, as plan_sweep cut it:
+// the 64 x 64 kernel up to slot size 256 (rows are independent: the tail tiles simply run as (tile, row split) workgroups);
+// above, the register-tile kernel in a stream-K launch (no partial outputs to add up)
+hipError_t launch_sweep(const Shape &s, const SweepPlan &p, const FusedArgs &a0, hipStream_t st, int mode = MODE_SCORE)
 {
-    if (g.KB <= 16) {
-        const TailSplit ts = a0.b_per_block >= g.Bpad ? tail_split(tiles, g.Bpad, cu_count()) : TailSplit{0, 0, g.Bpad};
-        if (ts.split < 2) return launch_fused(mode, a0, tiles, 1, st);
-        FusedArgs am = a0;
-        am.N = (tiles - ts.tiles) * NT;
-        if (hipError_t e = launch_fused(mode, am, tiles - ts.tiles, 1, st); e != hipSuccess) return e;
-        FusedArgs at = tile_window(a0, g, tiles - ts.tiles);
-        at.b_per_block = ts.b_per_block;
-        return launch_fused(mode, at, ts.tiles, ts.split, st);
+    if (p.sk_wgs > 0) {
+        FusedArgs a = a0;
+        a.sk_tiles = p.tiles;
+        return launch_fused64k(mode, a, p.sk_wgs, 1, st);
     }
-    FusedArgs a = a0;
-    a.sk_tiles = tiles;
-    const int64_t units = (int64_t)tiles * ((a.B + 31) / 32);
-    return launch_fused64k(mode, a, (int)std::min<int64_t>(std::min(cu_count(), 511), units), 1, st);
+    if (p.tail_split < 2) return launch_fused(mode, a0, p.tiles, 1, st);
+    FusedArgs am = a0;
+    am.N = p.main_tiles * NT;
+    if (hipError_t e = launch_fused(mode, am, p.main_tiles, 1, st); e != hipSuccess) return e;
+    FusedArgs at = tile_window(a0, s, p.main_tiles);
+    at.b_per_block = p.tail_b_per_block;
+    return launch_fused(mode, at, p.tail_tiles, p.tail_split, st);
 }
 
-// Arguments of candidate range r (geometry: ranges of g.range_n candidates): local candidate 0 of the launch is
+// what a sweep needs beside its arguments: the shape and what the planner reads
+struct SweepCtx {
+    const Shape &s;
+    int          cus;
+    Knobs        knobs;
+    SweepPlan    plan(int tiles) const { return plan_sweep(s, tiles, cus, knobs); }
+};
+
+// Arguments of candidate range r (ranges of rg.range_n candidates): local candidate 0 of the launch is
 // candidate r * range_n of the call.  Positives / dropout keep their global columns through cand_col0.
-FusedArgs range_args(const FusedArgs &base, const Geometry &g, int r, int &tiles_r)
+// loss_stride: loss partials per tile of the launch that owns base.loss_partial (the train plan's b_split)
+FusedArgs range_args(const FusedArgs &base, const Shape &s, const Ranges &rg, int r, int &tiles_r, int loss_stride = 1)
 {
     FusedArgs a = base;
-    const int n_lo = r * g.range_n;
-    a.N = std::min(g.range_n, g.N - n_lo);
+    const int n_lo = r * rg.range_n;
+    a.N = std::min(rg.range_n, s.N - n_lo);
     a.cand_first += n_lo;
     if (a.cand_ids) a.cand_ids += n_lo;
     a.cand_col0 += n_lo;
     if (a.tile_ptr) a.tile_ptr += n_lo / NT;
-    if (a.loss_partial) a.loss_partial += (size_t)(n_lo / NT) * g.b_split;
+    if (a.loss_partial) a.loss_partial += (size_t)(n_lo / NT) * loss_stride;
     tiles_r = (a.N + NT - 1) / NT;
     return a;
 }
 
 // per-row log-sum-exp over all candidates of the call (KL loss): one score-statistics pass per candidate range, merged
 // into a running (max, sum-exp) per row; the (B, N) scores are never materialised
-int lse_pass(const Geometry &g, const FusedArgs &base, char *ws, float *row_lse, hipStream_t st,
+int lse_pass(const SweepCtx &cx, const Ranges &rg, const LseLayout &l, const FusedArgs &base, char *ws, float *row_lse, hipStream_t st,
              const int32_t *count_pos_row = nullptr, int count_nnz = 0, float *count_ysum = nullptr)
 {
+    const Shape &g = cx.s;
     FusedArgs b = base;
-    b.stats = reinterpret_cast<float *>(ws + g.off_stats);
+    b.stats = reinterpret_cast<float *>(ws + l.off_stats);
     b.b_per_block = g.Bpad;
     b.tile_ptr = nullptr;
     b.loss_partial = nullptr;
-    for (int r = 0; r < g.n_ranges; ++r) {
+    for (int r = 0; r < rg.n_ranges; ++r) {
         int tiles_r;
-        const FusedArgs s = range_args(b, g, r, tiles_r);
+        const FusedArgs s = range_args(b, g, rg, r, tiles_r);
         hipError_t e;
         {
             ScopedTimer tm("fused_tile_stats", st);
-            e = launch_score_sweep(g, s, tiles_r, st, MODE_STATS);      // (slot sizes above 256: four 16-candidate blocks per tile)
+            e = launch_sweep(g, cx.plan(tiles_r), s, st, MODE_STATS);      // (slot sizes above 256: four 16-candidate blocks per tile)
             if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<stats>");
         }
         ScopedTimer tm("kl_row_lse", st);
         // the 64x64 cut emits one (max, sum-exp) per 64-candidate tile, the register-tile kernel one per 16-candidate block
         e = launch_kl_row_lse(s.stats, g.KB <= 16 ? tiles_r : 4 * tiles_r, g.B, g.Bpad,
-                              reinterpret_cast<float *>(ws + g.off_run), r == 0, r == g.n_ranges - 1, row_lse, st,
+                              reinterpret_cast<float *>(ws + l.off_run), r == 0, r == rg.n_ranges - 1, row_lse, st,
                               r == 0 ? count_pos_row : nullptr, count_nnz, r == 0 ? count_ysum : nullptr);   // + the rows' label mass
         if (e != hipSuccess) return fail_hip(e, "kl_row_lse");
     }
     return OKGE_OK;
 }
 
-// ---- top-k link prediction -------------------------------------------------------------------------------------------------
-// The sweep runs per candidate range; a range leaves [tiles of the range][Bpad][k] records and one merge launch folds them into
-// the running (B, k) list, which IS the caller's output.  Default range: the records (plus, above slot size 256, the range's
-// score block) stay under TOPK_PARTIAL_CAP; whole rounds of one tile per CU when a range is that long, as in training.
-constexpr size_t TOPK_PARTIAL_CAP = (size_t)256 << 20;
-struct TopkGeometry { size_t off_part, off_X, total; };
-
-bool make_topk_geometry(int B, int N, int d, int k, int range_n, Geometry &g, TopkGeometry &tg)
-{
-    if (k < 1 || k > 64 || range_n < 0 || d > 512 || !make_geometry(B, N, d, g)) return false;
-    const bool wide = g.KB > 16;
-    const size_t per_tile = (size_t)g.Bpad * ((size_t)k * sizeof(TopkRec) + (wide ? NT * sizeof(float) : 0));
-    int64_t rt;
-    if (range_n > 0) {
-        rt = std::max(1, range_n / NT);
-    } else {
-        rt = std::max<int64_t>(1, (int64_t)(TOPK_PARTIAL_CAP / per_tile));
-        const int cus = cu_count();
-        if (!wide && rt >= cus) rt = rt / cus * cus;
-    }
-    g.range_tiles = (int)std::min<int64_t>(rt, g.tiles);
-    g.n_ranges = (g.tiles + g.range_tiles - 1) / g.range_tiles;
-    g.range_n = g.range_tiles * NT;
-    g.b_split = 1;
-    g.b_per_block = g.Bpad;
-    size_t off = g.score_bytes;                                  // the query block (okge_topk_prefixes)
-    tg.off_part = off; off += align_up((size_t)g.range_tiles * g.Bpad * k * sizeof(TopkRec), 256);
-    tg.off_X = off;    off += wide ? align_up((size_t)g.Bpad * g.range_n * sizeof(float), 256) : 0;
-    tg.total = off;
-    return true;
-}
-
-int topk_pass(const Geometry &g, const TopkGeometry &tg, const FusedArgs &base, char *ws, int k, const int64_t *filt_ptr,
+// ---- top-k link prediction (ranges and workspace: plan_topk) ---------------------------------------------------------------
+int topk_pass(const SweepCtx &cx, const TopkPlan &tp, const FusedArgs &base, char *ws, int k, const int64_t *filt_ptr,
               const int32_t *filt_col, float *out_scores, int32_t *out_cols, int32_t *out_ids, hipStream_t st)
 {
+    const Shape &g = cx.s;
     FusedArgs b = base;
-    TopkRec *part = reinterpret_cast<TopkRec *>(ws + tg.off_part);
+    TopkRec *part = reinterpret_cast<TopkRec *>(ws + tp.off_part);
     b.b_per_block = g.Bpad;
     b.tk_k = k;
     b.tk_filt_ptr = filt_ptr;
     b.tk_filt_col = filt_col;
-    for (int r = 0; r < g.n_ranges; ++r) {
+    for (int r = 0; r < tp.n_ranges; ++r) {
         int tiles_r;
-        FusedArgs s = range_args(b, g, r, tiles_r);
+        FusedArgs s = range_args(b, g, tp, r, tiles_r);
+        const SweepPlan sp = cx.plan(tiles_r);
         hipError_t e;
         if (g.KB <= 16) {
             s.tk_part = part;
-            // (the name tells whether the closing round of this range was launched apart: launch_score_sweep asks the same question)
-            ScopedTimer tm(tail_split(tiles_r, g.Bpad, cu_count()).split > 1 ? "fused_tile_topk_tail" : "fused_tile_topk", st);
-            e = launch_score_sweep(g, s, tiles_r, st, MODE_TOPK);
+            // (the name tells whether the closing round of this range was launched apart)
+            ScopedTimer tm(sp.tail_split > 1 ? "fused_tile_topk_tail" : "fused_tile_topk", st);
+            e = launch_sweep(g, sp, s, st, MODE_TOPK);
             if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<topk>");
         } else {
-            s.X = reinterpret_cast<float *>(ws + tg.off_X);
-            s.ldx = g.range_n;
+            s.X = reinterpret_cast<float *>(ws + tp.off_X);
+            s.ldx = tp.range_n;
             {
                 ScopedTimer tm("fused_tile_score", st);
-                e = launch_score_sweep(g, s, tiles_r, st, MODE_SCORE);
+                e = launch_sweep(g, sp, s, st, MODE_SCORE);
                 if (e != hipSuccess) return fail_hip(e, "fused_tile64k_kernel<score>");
             }
             ScopedTimer tm("topk_cut", st);
@@ -506,7 +338,7 @@ int topk_pass(const Geometry &g, const TopkGeometry &tg, const FusedArgs &base, 
         m.L = tiles_r; m.rows_ld = g.Bpad; m.kq = k; m.B = g.B; m.k = k;
         m.first = r == 0;
         m.out_sc = out_scores; m.out_cl = out_cols;
-        if (r == g.n_ranges - 1 && out_ids) { m.out_id = out_ids; m.cand_ids = base.cand_ids; m.cand_first = base.cand_first; }
+        if (r == tp.n_ranges - 1 && out_ids) { m.out_id = out_ids; m.cand_ids = base.cand_ids; m.cand_first = base.cand_first; }
         e = launch_topk_merge(m, st);
         if (e != hipSuccess) return fail_hip(e, "topk_merge");
     }
@@ -542,23 +374,22 @@ const char *okge_last_error(void) { return g_err.c_str(); }
 
 size_t okge_train_workspace_bytes(int32_t B, int32_t N, int32_t d)
 {
-    Geometry g;
-    if (!make_geometry(B, N, d, g)) return 0;
-    return g.total;
+    Shape s;
+    if (!make_shape(B, N, d, s)) return 0;
+    return train_layout(s, plan_train(s, cu_count(), read_knobs())).total;
 }
 
 size_t okge_score_workspace_bytes(int32_t B, int32_t d)
 {
-    Geometry g;
-    if (!make_geometry(B, 1, d, g)) return 0;
-    return g.score_bytes;
+    Shape s;
+    return make_shape(B, 1, d, s) ? score_layout(s).total : 0;
 }
 
 size_t okge_lse_workspace_bytes(int32_t B, int32_t N, int32_t d)
 {
-    Geometry g;
-    if (!make_geometry(B, N, d, g)) return 0;
-    return g.lse_bytes;
+    Shape s;
+    if (!make_shape(B, N, d, s)) return 0;
+    return lse_layout(s, plan_ranges(s, cu_count(), read_knobs())).lse_bytes;
 }
 
 int okge_score_prefixes(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
@@ -566,28 +397,27 @@ int okge_score_prefixes(const okge_tables *t, const okge_prefix_batch *batch, co
 {
     if (int rc = check_common(t, batch, cand)) return rc;
     if (!scores || ld_scores < cand->n) return fail(OKGE_ERR_INVALID, "bad scores buffer");
-    Geometry g;
-    make_geometry(batch->n_po + batch->n_sp, cand->n, t->d, g);
-    const size_t need = g.score_bytes;   // only the query block
-    if (!workspace || workspace_bytes < need) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    Shape g;
+    if (!make_shape(batch->n_po + batch->n_sp, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
+    const ScoreLayout l = score_layout(g);   // only the query block
+    if (!workspace || workspace_bytes < l.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace);
+    float *Q = reinterpret_cast<float *>(static_cast<char *>(workspace) + l.off_Q);
     const PrefixDev p = to_dev(*batch, t);
     {
         ScopedTimer tm("encode_queries", st);
-        hipError_t e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + g.off_Q),
-                                             g.ldq, g.Bpad, nullptr, nullptr, 0, nullptr, g.tiles, NT, 0, st);
+        hipError_t e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, Q, g.ldq, g.Bpad, nullptr, nullptr, 0, nullptr, g.tiles, NT,
+                                             0, st);
         if (e != hipSuccess) return fail_hip(e, "encode_queries");
     }
     FusedArgs a;
-    fill_fused_common(a, g, t, cand, ws);
+    fill_fused_common(a, g, t, cand, Q);     // (all rows per workgroup: rows are independent in score mode, but one pass per tile keeps C resident)
     a.X = scores;
     a.ldx = ld_scores;
     a.x_vec_ok = (ld_scores % 4 == 0) && (reinterpret_cast<uintptr_t>(scores) % 16 == 0);
-    a.b_per_block = g.Bpad;     // rows are independent in score mode, but one pass per tile keeps C resident
     {
         ScopedTimer tm("fused_tile_score", st);
-        hipError_t e = launch_score_sweep(g, a, g.tiles, st);
+        hipError_t e = launch_sweep(g, plan_sweep(g, g.tiles, cu_count(), read_knobs()), a, st);
         if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<score>");
     }
     return OKGE_OK;
@@ -610,9 +440,12 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
     if (cand->table) return fail(OKGE_ERR_INVALID, "training needs candidates from the entity table");
     if (!(normalizer > 0)) return fail(OKGE_ERR_INVALID, "normalizer must be positive");
     if (scores && ld_scores < cand->n) return fail(OKGE_ERR_INVALID, "bad scores buffer");
-    Geometry g;
-    make_geometry(B, cand->n, t->d, g);
-    if (!workspace || workspace_bytes < g.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    Shape g;
+    if (!make_shape(B, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
+    const SweepCtx cx = {g, cu_count(), read_knobs()};
+    const TrainPlan pl = plan_train(g, cx.cus, cx.knobs);
+    const TrainLayout l = train_layout(g, pl);
+    if (!workspace || workspace_bytes < l.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
     if (q_ext && ldq_ext != g.ldq) return fail(OKGE_ERR_INVALID, "query block leading dimension must be okge_query_ld(d)");
     const bool clear_grads = (flags & OKGE_TRAIN_CLEAR_GRADS) != 0 && !loss_only;
     if (clear_grads) {
@@ -634,7 +467,7 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
         // log-sum-exp) or by kl_count_pos (sharded: the log-sum-exp arrives from the exchange).  Not with hipMemsetAsync: inside a
         // captured HIP graph the memset node was not re-executed / ordered on replay (ROCm 7.2), the mass doubled every replay
         const bool kl_own_lse = loss_kind == OKGE_LOSS_KL;
-        if (kl_own_lse) { clr.p[3] = reinterpret_cast<float *>(ws + g.off_ysum); clr.n[3] = g.Bpad; }
+        if (kl_own_lse) { clr.p[3] = reinterpret_cast<float *>(ws + l.off_ysum); clr.n[3] = g.Bpad; }
         if (clear_grads) {                        // all of dR; the rows of dE in front of and behind the candidate range
             const int64_t d64 = t->d, hi = (int64_t)cand->first_id + cand->n;
             clr.p[0] = dR;                      clr.n[0] = (int64_t)t->n_rel * d64;
@@ -643,10 +476,10 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
         }
         // the tile kernel's gradient product reads Q as three bf16 planes: written by the launch that folds the rows, or from
         // the caller's block by a launch of its own
-        v8bf *q_planes = tile_grad_split(g.KB) && !loss_only ? reinterpret_cast<v8bf *>(ws + g.off_Qp) : nullptr;
-        e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + g.off_Q), g.ldq,
+        v8bf *q_planes = tile_grad_split(g.KB) && !loss_only ? reinterpret_cast<v8bf *>(ws + l.off_Qp) : nullptr;
+        e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + l.off_Q), g.ldq,
                                   q_ext ? 0 : g.Bpad, nullptr, pos->col, pos->nnz,
-                                  reinterpret_cast<int32_t *>(ws + g.off_tptr), g.tiles, NT, cand_col0, st,
+                                  reinterpret_cast<int32_t *>(ws + l.off_tptr), g.tiles, NT, cand_col0, st,
                                   (clear_grads || kl_own_lse) ? &clr : nullptr, q_planes, g.KB);
         if (e != hipSuccess) return fail_hip(e, "encode_queries");
         if (q_ext && q_planes) {
@@ -655,23 +488,24 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
         }
     }
     FusedArgs a;
-    fill_fused_common(a, g, t, cand, ws);
-    if (q_ext) a.Q = q_ext;
+    fill_fused_common(a, g, t, cand, q_ext ? q_ext : reinterpret_cast<const float *>(ws + l.off_Q));
+    a.ldg = pl.ldg;
+    a.b_per_block = pl.b_per_block;
     a.cand_col0 = cand_col0;
     a.pos_col = pos->col; a.pos_row = pos->row; a.nnz = pos->nnz;
-    a.tile_ptr = reinterpret_cast<const int32_t *>(ws + g.off_tptr);
+    a.tile_ptr = reinterpret_cast<const int32_t *>(ws + l.off_tptr);
     a.grads_zero = (flags & OKGE_TRAIN_GRADS_ZERO) ? 1 : 0;
     // an explicit id list may name an entity twice (precompute_batch_shared_inputs takes any list): its rows are then
     // accumulated with atomics unless the caller vouches for uniqueness (the collator's lists are unique)
     a.cand_exclusive = (!cand->ids || (flags & OKGE_TRAIN_UNIQUE_CANDIDATES)) ? 1 : 0;
     a.loss_only = loss_only ? 1 : 0;
-    a.G = reinterpret_cast<float *>(ws + g.off_GT);
-    if (g.KB <= 13) a.Cplanes = reinterpret_cast<v8bf *>(ws + g.off_Cm);
-    else a.Cm = reinterpret_cast<float *>(ws + g.off_Cm);
-    if (tile_grad_split(g.KB)) a.Qplanes = reinterpret_cast<const v8bf *>(ws + g.off_Qp);
+    a.G = reinterpret_cast<float *>(ws + l.off_GT);
+    if (g.KB <= 13) a.Cplanes = reinterpret_cast<v8bf *>(ws + l.off_Cm);
+    else a.Cm = reinterpret_cast<float *>(ws + l.off_Cm);
+    if (tile_grad_split(g.KB)) a.Qplanes = reinterpret_cast<const v8bf *>(ws + l.off_Qp);
     a.dE = dE;
-    a.dC_slab = (g.b_split > 1 || g.sk_wgs > 0 || g.tail_split > 1) ? reinterpret_cast<float *>(ws + g.off_dcs) : nullptr;
-    a.loss_partial = reinterpret_cast<double *>(ws + g.off_loss);
+    a.dC_slab = pl.dc_slabs > 0 ? reinterpret_cast<float *>(ws + l.off_dcs) : nullptr;
+    a.loss_partial = reinterpret_cast<double *>(ws + l.off_loss);
     a.loss_kind = loss_kind;
     a.inv_norm = (float)(1.0 / normalizer);
     // label smoothing (trainer.py:103-105): y <- (y + 1/N) * (1 - eps), bce branch only; N = all candidates
@@ -687,7 +521,7 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
         s.x_vec_ok = (ld_scores % 4 == 0) && (reinterpret_cast<uintptr_t>(scores) % 16 == 0);
         s.b_per_block = g.Bpad;
         ScopedTimer tm("fused_tile_score", st);
-        e = launch_score_sweep(g, s, g.tiles, st);
+        e = launch_sweep(g, cx.plan(g.tiles), s, st);
         if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<score>");
     }
     if (loss_kind == OKGE_LOSS_KL) {
@@ -696,16 +530,16 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
         if (!row_lse_ext) {
             // (the label mass per row, trainer.py:99-101, is counted by extra workgroups of the pass' first kl_row_lse launch;
             //  its buffer was cleared by the encode launch above)
-            if (int rc = lse_pass(g, a, ws, reinterpret_cast<float *>(ws + g.off_lse), st, pos->row, pos->nnz,
-                                  reinterpret_cast<float *>(ws + g.off_ysum)))
+            if (int rc = lse_pass(cx, pl, l, a, ws, reinterpret_cast<float *>(ws + l.off_lse), st, pos->row, pos->nnz,
+                                  reinterpret_cast<float *>(ws + l.off_ysum)))
                 return rc;
         } else {
             ScopedTimer tm("kl_count_pos", st);   // label mass per row (trainer.py:99-101: y is not normalised)
-            e = launch_kl_count_pos(pos->row, pos->nnz, g.Bpad, reinterpret_cast<float *>(ws + g.off_ysum), st);
+            e = launch_kl_count_pos(pos->row, pos->nnz, g.Bpad, reinterpret_cast<float *>(ws + l.off_ysum), st);
             if (e != hipSuccess) return fail_hip(e, "kl_count_pos");
         }
-        a.row_lse = row_lse_ext ? row_lse_ext : reinterpret_cast<const float *>(ws + g.off_lse);
-        a.row_ysum = reinterpret_cast<const float *>(ws + g.off_ysum);
+        a.row_lse = row_lse_ext ? row_lse_ext : reinterpret_cast<const float *>(ws + l.off_lse);
+        a.row_ysum = reinterpret_cast<const float *>(ws + l.off_ysum);
     }
 #ifdef OKGE_STAMPS
     if (const char *sp = std::getenv("OKGE_STAMPS_PTR")) a.stamps_dbg = reinterpret_cast<unsigned long long *>(std::strtoull(sp, nullptr, 0));
@@ -713,24 +547,21 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
     DqArgs q;
     std::memset(&q, 0, sizeof(q));
     q.G = a.G; q.Cm = a.Cm; q.Cplanes = a.Cplanes;
-    q.slab = reinterpret_cast<float *>(ws + g.off_slab);
-    q.d = g.d; q.KB = g.KB; q.LDK = g.LDK; q.Bpad = g.Bpad; q.ldq = g.ldq; q.ldg = g.ldg;
-    q.nsplit = g.nsplit;
+    q.slab = reinterpret_cast<float *>(ws + l.off_slab);
+    q.d = g.d; q.KB = g.KB; q.LDK = g.LDK; q.Bpad = g.Bpad; q.ldq = g.ldq; q.ldg = pl.ldg;
+    q.nsplit = pl.nsplit;
     const int mode = loss_kind == OKGE_LOSS_KL ? MODE_TRAIN_KL : MODE_TRAIN_BCE;
-    // (tail split: the tail launch's partials of row split y > 0 follow the per-tile ones -- index y * tail + x from the tail's
-    //  first tile is contiguous with them)
-    const int n_loss_partials = g.sk_wgs > 0 ? g.sk_wgs : g.tiles * g.b_split + g.tail_tiles * std::max(0, g.tail_split - 1);
-    for (int r = 0; r < g.n_ranges; ++r) {
+    for (int r = 0; r < pl.n_ranges; ++r) {
         int tiles_r;
-        const FusedArgs ar = range_args(a, g, r, tiles_r);
-        const int tail_r = (r == g.n_ranges - 1 && g.tail_split > 1) ? g.tail_tiles : 0;     // tiles of this range launched apart
+        const FusedArgs ar = range_args(a, g, pl, r, tiles_r, pl.b_split);
+        const int tail_r = (r == pl.n_ranges - 1 && pl.tail_split > 1) ? pl.tail_tiles : 0;     // tiles of this range launched apart
         FusedArgs at = ar;
         {
             ScopedTimer tm("fused_tile_train", st);
-            if (g.sk_wgs > 0) {                     // stream-K: a.sk_tiles tiles x sk_chunks chunks over sk_wgs workgroups
+            if (pl.sk_wgs > 0) {                     // stream-K: a.sk_tiles tiles x sk_chunks chunks over sk_wgs workgroups
                 FusedArgs as = ar;
                 as.sk_tiles = tiles_r;
-                e = launch_fused64(mode, as, g.sk_wgs, 1, st);
+                e = launch_fused64(mode, as, pl.sk_wgs, 1, st);
             } else if (tail_r > 0) {
                 const int main_r = tiles_r - tail_r;
                 e = hipSuccess;
@@ -741,29 +572,29 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
                 }
                 if (e == hipSuccess) {
                     at = tile_window(ar, g, main_r);
-                    at.b_per_block = g.tail_b_per_block;
-                    e = launch_fused64(mode, at, tail_r, g.tail_split, st);
+                    at.b_per_block = pl.tail_b_per_block;
+                    e = launch_fused64(mode, at, tail_r, pl.tail_split, st);
                 }
             } else {
-                e = launch_fused64(mode, ar, tiles_r, g.b_split, st);
+                e = launch_fused64(mode, ar, tiles_r, pl.b_split, st);
             }
             if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<train>");
         }
         if (loss_only) continue;
         if (tail_r > 0) {
             ScopedTimer tm("dc_reduce", st);
-            e = launch_dc_reduce(a.dC_slab, g.tail_split, tail_r * NT, g.D16, at.N, g.d, at.cand_ids, at.cand_first, a.cand_exclusive,
+            e = launch_dc_reduce(a.dC_slab, pl.dc_slabs, pl.dc_slab_rows, g.D16, at.N, g.d, at.cand_ids, at.cand_first, a.cand_exclusive,
                                  a.grads_zero, dE, a.n_table_rows, a.id_err, st);
             if (e != hipSuccess) return fail_hip(e, "dc_reduce");
         }
-        if (g.sk_wgs > 0) {
+        if (pl.sk_wgs > 0) {
             ScopedTimer tm("dc_reduce", st);
-            e = launch_dc_reduce_streamk(a.dC_slab, tiles_r, g.sk_chunks, g.sk_wgs, g.D16, ar.N, g.d, cand->ids, cand->first_id,
+            e = launch_dc_reduce_streamk(a.dC_slab, tiles_r, pl.sk_chunks, pl.sk_wgs, g.D16, ar.N, g.d, cand->ids, cand->first_id,
                                          a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err, st);
             if (e != hipSuccess) return fail_hip(e, "dc_reduce_streamk");
-        } else if (g.b_split > 1) {                 // (few candidate tiles: always a single range)
+        } else if (pl.b_split > 1) {                 // (few candidate tiles: always a single range)
             ScopedTimer tm("dc_reduce", st);
-            e = launch_dc_reduce(a.dC_slab, g.b_split, g.tiles * NT, g.D16, g.N, g.d, cand->ids, cand->first_id, a.cand_exclusive,
+            e = launch_dc_reduce(a.dC_slab, pl.dc_slabs, pl.dc_slab_rows, g.D16, g.N, g.d, cand->ids, cand->first_id, a.cand_exclusive,
                                  a.grads_zero, dE, a.n_table_rows, a.id_err, st);
             if (e != hipSuccess) return fail_hip(e, "dc_reduce");
         }
@@ -771,19 +602,19 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
             ScopedTimer tm("dq", st);
             q.N = ar.N;
             q.accumulate = r > 0 ? 1 : 0;           // later ranges add to the slabs of the first
-            e = launch_dq(q, (g.Bpad / BC) * g.nsplit, st);
+            e = launch_dq(q, (g.Bpad / BC) * pl.nsplit, st);
             if (e != hipSuccess) return fail_hip(e, "dq_kernel");
         }
     }
     if (loss_only) {
         ScopedTimer tm("loss_reduce", st);
-        e = launch_loss_reduce(a.loss_partial, n_loss_partials, loss_out, st);
+        e = launch_loss_reduce(a.loss_partial, pl.n_loss_partials, loss_out, st);
         if (e != hipSuccess) return fail_hip(e, "loss_reduce");
         return OKGE_OK;
     }
     if (dq_out) {
         ScopedTimer tm("slab_reduce", st);          // + the deterministic loss reduction (one extra workgroup)
-        e = launch_slab_reduce(q.slab, g.nsplit, (int64_t)g.Bpad * g.ldq, dq_out, a.loss_partial, n_loss_partials,
+        e = launch_slab_reduce(q.slab, pl.nsplit, (int64_t)g.Bpad * g.ldq, dq_out, a.loss_partial, pl.n_loss_partials,
                                loss_out, st);
         if (e != hipSuccess) return fail_hip(e, "slab_reduce");
         return OKGE_OK;
@@ -791,8 +622,8 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
     {
         ScopedTimer tm("prefix_backward", st);      // + the deterministic loss reduction (one extra workgroup)
         const PrefixDev p = to_dev(*batch, t, sh);
-        e = launch_prefix_backward(t->E, t->R, t->d, t->scorer, p, q.slab, g.nsplit, g.Bpad, g.ldq, nullptr, dE, dR,
-                                   a.loss_partial, n_loss_partials, loss_out, st, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr,
+        e = launch_prefix_backward(t->E, t->R, t->d, t->scorer, p, q.slab, pl.nsplit, g.Bpad, g.ldq, nullptr, dE, dR,
+                                   a.loss_partial, pl.n_loss_partials, loss_out, st, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr,
                                    (flags & OKGE_TRAIN_DISTINCT_PREFIX_ROWS) ? 1 : 0);
         if (e != hipSuccess) return fail_hip(e, "prefix_backward");
     }
@@ -805,23 +636,11 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
 // 0 .. N-1 and OKGE_TRAIN_DISTINCT_PREFIX_ROWS, the path the encoded-row ("virtual table") models take.  Every gradient row is
 // then STORED once, at its position; the tile kernels are the ones every other caller runs, untouched.  Dropout counters are
 // keyed by position (okge_dropout), so the masks are the dense step's.
-struct RowGradsLayout { size_t off_EV, off_RV, off_ids, total; };
-static RowGradsLayout row_grads_layout(const Geometry &g)
-{
-    RowGradsLayout l;
-    size_t off = align_up(g.total, 256);
-    l.off_EV = off;  off += align_up((size_t)(g.N + g.B) * g.d * sizeof(float), 256);
-    l.off_RV = off;  off += align_up((size_t)g.B * g.d * sizeof(float), 256);
-    l.off_ids = off; off += align_up((size_t)2 * g.B * sizeof(int32_t), 256);
-    l.total = off;
-    return l;
-}
-
 size_t okge_train_row_grads_workspace_bytes(int32_t B, int32_t N, int32_t d)
 {
-    Geometry g;
-    if (!make_geometry(B, N, d, g)) return 0;
-    return row_grads_layout(g).total;
+    Shape s;
+    if (!make_shape(B, N, d, s)) return 0;
+    return row_grads_layout(s, train_layout(s, plan_train(s, cu_count(), read_knobs())).total).total;
 }
 
 static int train_row_grads(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, const okge_positives *pos,
@@ -833,9 +652,10 @@ static int train_row_grads(const okge_tables *t, const okge_prefix_batch *batch,
     if (!dE || !dR) return fail(OKGE_ERR_INVALID, "null output");
     if (int rc = refuse_bias(t->scorer, "okge_train_forward_backward(OKGE_TRAIN_ROW_GRADS)", "the unused slot's rows have no gradient to store")) return rc;
     const int B = batch->n_po + batch->n_sp, N = cand->n;
-    Geometry g;
-    make_geometry(B, N, t->d, g);
-    const RowGradsLayout l = row_grads_layout(g);
+    Shape g;
+    if (!make_shape(B, N, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
+    const size_t train_total = train_layout(g, plan_train(g, cu_count(), read_knobs())).total;
+    const RowGradsLayout l = row_grads_layout(g, train_total);
     if (!workspace || workspace_bytes < l.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_train_row_grads_workspace_bytes)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace);
@@ -863,7 +683,7 @@ static int train_row_grads(const okge_tables *t, const okge_prefix_batch *batch,
     vc.ids = nullptr; vc.first_id = 0;
     return train_core(&tv, nullptr, &vb, nullptr, 0, B, &vc, pos, loss_kind, label_smoothing, normalizer, N,
                       OKGE_TRAIN_GRADS_ZERO | OKGE_TRAIN_UNIQUE_CANDIDATES | OKGE_TRAIN_DISTINCT_PREFIX_ROWS, loss_out, dE, dR, nullptr,
-                      scores, ld_scores, nullptr, workspace, g.total, stream);
+                      scores, ld_scores, nullptr, workspace, train_total, stream);
 }
 
 int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
@@ -885,11 +705,15 @@ int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *b
 // ---- entity-sharded phases ---------------------------------------------------------------------------------------
 int64_t okge_query_ld(int32_t d)
 {
-    Geometry g;
-    return make_geometry(1, 1, d, g) ? g.ldq : 0;
+    Shape s;
+    return make_shape(1, 1, d, s) ? s.ldq : 0;
 }
 
-int32_t okge_query_rows(int32_t B) { return B > 0 ? (B + BC - 1) / BC * BC : 0; }
+int32_t okge_query_rows(int32_t B)
+{
+    Shape s;
+    return make_shape(B, 1, 1, s) ? s.Bpad : 0;
+}
 
 static int check_shard(const okge_tables *t, const okge_shard *sh)
 {
@@ -971,19 +795,17 @@ int okge_score_queries(const okge_tables *t, const okge_shard *sh, const float *
 {
     if (int rc = check_query_call(t, sh, Q, ldq, B, cand)) return rc;
     if (!scores || ld_scores < cand->n) return fail(OKGE_ERR_INVALID, "bad scores buffer");
-    Geometry g;
-    make_geometry(B, cand->n, t->d, g);
+    Shape g;
+    if (!make_shape(B, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     FusedArgs a;
-    fill_fused_common(a, g, t, cand, nullptr);
-    a.Q = Q;
+    fill_fused_common(a, g, t, cand, Q);
     a.cand_col0 = sh->cand_col0;
     a.X = scores;
     a.ldx = ld_scores;
     a.x_vec_ok = (ld_scores % 4 == 0) && (reinterpret_cast<uintptr_t>(scores) % 16 == 0);
-    a.b_per_block = g.Bpad;
     ScopedTimer tm("fused_tile_score", st);
-    hipError_t e = launch_score_sweep(g, a, g.tiles, st);
+    hipError_t e = launch_sweep(g, plan_sweep(g, g.tiles, cu_count(), read_knobs()), a, st);
     if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<score>");
     return OKGE_OK;
 }
@@ -994,23 +816,24 @@ int okge_row_logsumexp(const okge_tables *t, const okge_shard *sh, const float *
 {
     if (int rc = check_query_call(t, sh, Q, ldq, B, cand)) return rc;
     if (!row_lse) return fail(OKGE_ERR_INVALID, "null output");
-    Geometry g;
-    make_geometry(B, cand->n, t->d, g);
-    if (!workspace || workspace_bytes < g.lse_bytes) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    Shape g;
+    if (!make_shape(B, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
+    const SweepCtx cx = {g, cu_count(), read_knobs()};
+    const Ranges rg = plan_ranges(g, cx.cus, cx.knobs);
+    const LseLayout l = lse_layout(g, rg);
+    if (!workspace || workspace_bytes < l.lse_bytes) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace);
     FusedArgs a;
-    fill_fused_common(a, g, t, cand, ws);
-    a.Q = Q;
+    fill_fused_common(a, g, t, cand, Q);
     a.cand_col0 = sh->cand_col0;
-    return lse_pass(g, a, ws, row_lse, st);
+    return lse_pass(cx, rg, l, a, static_cast<char *>(workspace), row_lse, st);
 }
 
 size_t okge_topk_workspace_bytes(int32_t B, int32_t N, int32_t d, int32_t k, int32_t range_n)
 {
-    Geometry g;
-    TopkGeometry tg;
-    return make_topk_geometry(B, N, d, k, range_n, g, tg) ? tg.total : 0;
+    Shape s;
+    TopkPlan tp;
+    return make_shape(B, N, d, s) && plan_topk(s, k, range_n, cu_count(), tp) ? tp.total : 0;
 }
 
 int okge_topk_prefixes(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, int32_t k,
@@ -1021,22 +844,25 @@ int okge_topk_prefixes(const okge_tables *t, const okge_prefix_batch *batch, con
     if (int rc = refuse_bias(t->scorer, "okge_topk_prefixes", "predictions are built for the ComplEx and DistMult scorers")) return rc;
     if (int rc = check_topk(k, batch, cand, filt_ptr, filt_col, n_filter, range_n, out_scores, out_cols)) return rc;
     if (!out_ids) return fail(OKGE_ERR_INVALID, "null output");
-    Geometry g;
-    TopkGeometry tg;
-    if (!make_topk_geometry(batch->n_po + batch->n_sp, cand->n, t->d, k, range_n, g, tg)) return fail(OKGE_ERR_INVALID, "bad shape");
-    if (!workspace || workspace_bytes < tg.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    Shape g;
+    if (!make_shape(batch->n_po + batch->n_sp, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
+    const SweepCtx cx = {g, cu_count(), read_knobs()};
+    TopkPlan tp;
+    if (!plan_topk(g, k, range_n, cx.cus, tp)) return fail(OKGE_ERR_INVALID, "bad shape");
+    if (!workspace || workspace_bytes < tp.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace);
+    float *Q = reinterpret_cast<float *>(ws + tp.off_Q);
     const PrefixDev p = to_dev(*batch, t);
     {
         ScopedTimer tm("encode_queries", st);
-        hipError_t e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + g.off_Q),
-                                             g.ldq, g.Bpad, nullptr, nullptr, 0, nullptr, g.tiles, NT, 0, st);
+        hipError_t e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, Q, g.ldq, g.Bpad, nullptr, nullptr, 0, nullptr, g.tiles, NT,
+                                             0, st);
         if (e != hipSuccess) return fail_hip(e, "encode_queries");
     }
     FusedArgs a;
-    fill_fused_common(a, g, t, cand, ws);
-    return topk_pass(g, tg, a, ws, k, n_filter > 0 ? filt_ptr : nullptr, filt_col, out_scores, out_cols, out_ids, st);
+    fill_fused_common(a, g, t, cand, Q);
+    return topk_pass(cx, tp, a, ws, k, n_filter > 0 ? filt_ptr : nullptr, filt_col, out_scores, out_cols, out_ids, st);
 }
 
 int okge_topk_queries(const okge_tables *t, const okge_shard *sh, const float *Q, int64_t ldq, int32_t B,
@@ -1046,17 +872,17 @@ int okge_topk_queries(const okge_tables *t, const okge_shard *sh, const float *Q
     if (cand && cand->table) return fail(OKGE_ERR_UNSUPPORTED, "top-k takes its candidates from the entity table");
     if (int rc = check_query_call(t, sh, Q, ldq, B, cand)) return rc;
     if (int rc = check_topk(k, nullptr, cand, filt_ptr, filt_col, n_filter, range_n, out_scores, out_cols)) return rc;
-    Geometry g;
-    TopkGeometry tg;
-    if (!make_topk_geometry(B, cand->n, t->d, k, range_n, g, tg)) return fail(OKGE_ERR_INVALID, "bad shape");
-    if (!workspace || workspace_bytes < tg.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    Shape g;
+    if (!make_shape(B, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
+    const SweepCtx cx = {g, cu_count(), read_knobs()};
+    TopkPlan tp;
+    if (!plan_topk(g, k, range_n, cx.cus, tp)) return fail(OKGE_ERR_INVALID, "bad shape");
+    if (!workspace || workspace_bytes < tp.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace);
     FusedArgs a;
-    fill_fused_common(a, g, t, cand, ws);
-    a.Q = Q;
+    fill_fused_common(a, g, t, cand, Q);
     a.cand_col0 = sh->cand_col0;
-    return topk_pass(g, tg, a, ws, k, n_filter > 0 ? filt_ptr : nullptr, filt_col, out_scores, out_cols, nullptr, st);
+    return topk_pass(cx, tp, a, static_cast<char *>(workspace), k, n_filter > 0 ? filt_ptr : nullptr, filt_col, out_scores, out_cols, nullptr, st);
 }
 
 int okge_topk_merge(const float *scores, const int32_t *cols, int32_t n_lists, int32_t B, int32_t k, float *out_scores,
@@ -1567,23 +1393,26 @@ int okge_adagrad_multi(const okge_adagrad_tensor *tensors, int32_t n_tensors, fl
 
 // ---- okge_adagrad_rows: torch's sparse Adagrad on occurrence rows ---------------------------------------------------------------
 constexpr int64_t ROWS_MAX_N = (int64_t)1 << 20;
-static size_t rows_keys_bytes(int64_t n) { return n > 0 ? align_up((size_t)n * sizeof(uint64_t), 256) : 0; }
 
 size_t okge_adagrad_rows_workspace_bytes(int64_t n0, int64_t n1)
 {
     if (n0 < 0 || n1 < 0 || n0 > ROWS_MAX_N || n1 > ROWS_MAX_N) return 0;
-    return 2 * rows_keys_bytes(n0) + 2 * rows_keys_bytes(n1);
+    Arena ar;
+    if (n0 > 0) take_rows_keys(ar, n0);
+    if (n1 > 0) take_rows_keys(ar, n1);
+    return ar.total();
 }
 
 // one segment per tensor with n > 0, its two key buffers cut from the workspace; steps: the table's row_steps (deferred decay) or null
-static void rows_segment(RowsSegs &segs, char *&ws, float *p, float *state_sum, const int32_t *ids, const float *g, int64_t ld_g, int32_t n,
+static void rows_segment(RowsSegs &segs, char *ws, Arena &ar, float *p, float *state_sum, const int32_t *ids, const float *g, int64_t ld_g, int32_t n,
                          int32_t table_rows, int32_t row_len, int32_t *steps)
 {
     RowsSeg &sg = segs.s[segs.n_segs++];
     sg.p = p; sg.s = state_sum; sg.g = g; sg.ids = ids; sg.ld_g = ld_g;
     sg.n = n; sg.table_rows = table_rows; sg.row_len = row_len; sg.steps = steps;
-    sg.keys[0] = reinterpret_cast<uint64_t *>(ws); ws += rows_keys_bytes(n);
-    sg.keys[1] = reinterpret_cast<uint64_t *>(ws); ws += rows_keys_bytes(n);
+    const RowsKeys keys = take_rows_keys(ar, n);
+    sg.keys[0] = reinterpret_cast<uint64_t *>(ws + keys.off[0]);
+    sg.keys[1] = reinterpret_cast<uint64_t *>(ws + keys.off[1]);
     sg.vec = (row_len % 4 == 0 && ld_g % 4 == 0 &&
               (reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(state_sum) | reinterpret_cast<uintptr_t>(g)) % 16 == 0) ? 1 : 0;
     // lanes per run: one per 16-byte column group up to 16 (rows of 64 floats and more: 4 runs in flight per wave, each
@@ -1599,7 +1428,7 @@ int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float 
     if (n_tensors < 0 || n_tensors > ROWS_MAX_SEGS || (n_tensors > 0 && !tensors)) return fail(OKGE_ERR_INVALID, "one or two tensors");
     RowsSegs segs;
     std::memset(&segs, 0, sizeof(segs));
-    size_t need = 0;
+    Arena need;
     for (int k = 0; k < n_tensors; ++k) {
         const okge_rows_tensor &x = tensors[k];
         if (x.n < 0) return fail(OKGE_ERR_INVALID, "negative occurrence count");
@@ -1607,14 +1436,15 @@ int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float 
         if (x.n == 0) continue;
         if (!x.p || !x.state_sum || !x.ids || !x.g) return fail(OKGE_ERR_INVALID, "null tensor");
         if (x.table_rows <= 0 || x.row_len <= 0 || x.ld_g < x.row_len) return fail(OKGE_ERR_INVALID, "bad table shape / leading dimension");
-        need += 2 * rows_keys_bytes(x.n);
+        take_rows_keys(need, x.n);
     }
-    if (need == 0) return OKGE_OK;
-    if (!workspace || workspace_bytes < need) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_adagrad_rows_workspace_bytes)");
+    if (need.total() == 0) return OKGE_OK;
+    if (!workspace || workspace_bytes < need.total()) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_adagrad_rows_workspace_bytes)");
     char *ws = static_cast<char *>(workspace);
+    Arena ar;
     for (int k = 0; k < n_tensors; ++k) {
         const okge_rows_tensor &x = tensors[k];
-        if (x.n > 0) rows_segment(segs, ws, x.p, x.state_sum, x.ids, x.g, x.ld_g, x.n, x.table_rows, x.row_len, nullptr);
+        if (x.n > 0) rows_segment(segs, ws, ar, x.p, x.state_sum, x.ids, x.g, x.ld_g, x.n, x.table_rows, x.row_len, nullptr);
     }
     segs.id_err = id_err_ptr();
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1666,7 +1496,7 @@ int okge_adagrad_rows_decay(const okge_rows_decay_tensor *tensors, int32_t n_ten
 {
     if (n_tensors <= 0 || n_tensors > ROWS_MAX_SEGS || !tensors) return fail(OKGE_ERR_INVALID, "one or two tensors");
     if (!counters || window < 1) return fail(OKGE_ERR_INVALID, "okge_adagrad_rows_decay needs the counters and window >= 1");
-    size_t need = 0;
+    Arena need;
     for (int k = 0; k < n_tensors; ++k) {
         const okge_rows_decay_tensor &x = tensors[k];
         if (int rc = rows_decay_table(x, "okge_adagrad_rows_decay")) return rc;
@@ -1674,16 +1504,17 @@ int okge_adagrad_rows_decay(const okge_rows_decay_tensor *tensors, int32_t n_ten
         if (!x.g || x.ld_g < x.row_len) return fail(OKGE_ERR_INVALID, "null gradient rows / bad leading dimension");
         if (x.ld_g % 4 || reinterpret_cast<uintptr_t>(x.g) % 16)
             return fail(OKGE_ERR_UNSUPPORTED, "deferred weight decay needs ld_g % 4 == 0 and 16-byte aligned gradient rows");
-        need += 2 * rows_keys_bytes(x.n);
+        take_rows_keys(need, x.n);
     }
-    if (need && (!workspace || workspace_bytes < need)) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_adagrad_rows_workspace_bytes)");
+    if (need.total() && (!workspace || workspace_bytes < need.total())) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_adagrad_rows_workspace_bytes)");
     RowsSegs segs;
     std::memset(&segs, 0, sizeof(segs));
     LazySeg sweep[ROWS_MAX_SEGS];
     char *ws = static_cast<char *>(workspace);
+    Arena ar;
     for (int k = 0; k < n_tensors; ++k) {
         const okge_rows_decay_tensor &x = tensors[k];
-        if (x.n > 0) rows_segment(segs, ws, x.p, x.state_sum, x.ids, x.g, x.ld_g, x.n, x.table_rows, x.row_len, x.row_steps);
+        if (x.n > 0) rows_segment(segs, ws, ar, x.p, x.state_sum, x.ids, x.g, x.ld_g, x.n, x.table_rows, x.row_len, x.row_steps);
         // no row of the sweep is stamped, so its gradient operand is never read: the accumulator stands in (as in the pool catch-up)
         sweep[k] = LazySeg{x.p, x.state_sum, x.state_sum, x.row_steps, nullptr, x.table_rows, x.row_len, 0};
     }
@@ -1853,42 +1684,15 @@ int okge_evaluate_batch(const okge_tables *t, const okge_prefix_batch *batch, co
     return OKGE_OK;
 }
 
-// ---- fused evaluation: no (B, N) score block ------------------------------------------------------------------------
-namespace {
-struct EvalGeometry { size_t off_Q, off_true, off_filt, off_rps, off_gshift, off_grow, off_counts, total; bool slab; };
-constexpr size_t EVAL_SLAB_MAX = (size_t)256 << 20;      // per-tile count slabs up to 256 MB; beyond that: atomics
-bool eval_geometry(int B, int N, int d, int64_t n_groups, int64_t n_filter, Geometry &g, EvalGeometry &e)
-{
-    if (!make_geometry(B, N, d, g) || n_groups < 0 || n_filter < 0) return false;
-    size_t off = 0;
-    e.off_Q = off;      off += align_up((size_t)g.Bpad * g.ldq * sizeof(float), 256);
-    e.off_true = off;   off += align_up((size_t)std::max<int64_t>(n_groups, 1) * sizeof(float), 256);
-    e.off_filt = off;   off += align_up((size_t)std::max<int64_t>(n_filter, 1) * sizeof(float), 256);
-    e.off_rps = off;    off += align_up((size_t)(g.Bpad + 1) * sizeof(int64_t), 256);       // row_ptr of the batch sorted by group count
-    e.off_gshift = off; off += align_up((size_t)g.Bpad * sizeof(int64_t), 256);             // original -> sorted group index, per row
-    e.off_grow = off;   off += align_up((size_t)std::max<int64_t>(n_groups, 1) * sizeof(int32_t), 256);     // row of every group
-    const size_t slab_bytes = (size_t)g.tiles * std::max<int64_t>(n_groups, 1) * sizeof(uint32_t);
-    e.slab = slab_bytes <= EVAL_SLAB_MAX;
-    e.off_counts = off; off += align_up(e.slab ? slab_bytes : (size_t)std::max<int64_t>(n_groups, 1) * 2 * sizeof(int32_t), 256);
-    e.total = off;
-    return true;
-}
-}  // namespace
-
-size_t okge_eval_workspace_bytes(int32_t B, int32_t N, int32_t d, int64_t n_groups, int64_t n_filter)
-{
-    Geometry g;
-    EvalGeometry e;
-    return eval_geometry(B, N, d, n_groups, n_filter, g, e) ? e.total : 0;
-}
-
+// ---- fused evaluation: no (B, N) score block (workspace: eval_layout) -----------------------------------------------
 // phases: 1 = point scores (+ queries), 2 = tile sweep, 4 = ranks + meters; okge_evaluate_fused runs all three on one
 // stream, okge_evaluate_fused_phase one at a time, okge_evaluate_fused_batches pairs phase 4 of a batch with phase 1 of
 // the next in one launch.
 namespace {
 struct EvalCall {                      // one batch's launch arguments, built once and used by whichever phases run
-    Geometry g;
-    EvalGeometry eg;
+    Shape g;
+    SweepPlan sweep_plan;
+    EvalLayout eg;
     EvalPointsArgs pts;
     EvalRanksArgs rk;
     FusedArgs sweep;
@@ -1896,6 +1700,13 @@ struct EvalCall {                      // one batch's launch arguments, built on
     int64_t n_groups;
 };
 }  // namespace
+
+size_t okge_eval_workspace_bytes(int32_t B, int32_t N, int32_t d, int64_t n_groups, int64_t n_filter)
+{
+    Shape s;
+    EvalLayout e;
+    return make_shape(B, N, d, s) && eval_layout(s, n_groups, n_filter, e) ? e.total : 0;
+}
 
 // Candidate-sharded call (okge_evaluate_fused_shard): folded queries from outside, the shard's candidate columns, the
 // true scores in a caller-owned buffer (they are exchanged between the phases), counts instead of ranks.
@@ -1924,9 +1735,10 @@ static int eval_call(EvalCall &c, const okge_tables *t, const okge_prefix_batch 
     c.n_groups = n_groups;
     if (n_groups == 0) return OKGE_OK;
     const int32_t B = es ? es->B : batch->n_po + batch->n_sp;
-    Geometry &g = c.g;
-    EvalGeometry &eg = c.eg;
-    eval_geometry(B, cand->n, t->d, n_groups, n_filter, g, eg);
+    Shape &g = c.g;
+    EvalLayout &eg = c.eg;
+    if (!make_shape(B, cand->n, t->d, g) || !eval_layout(g, n_groups, n_filter, eg)) return fail(OKGE_ERR_INVALID, "bad shape");
+    c.sweep_plan = plan_sweep(g, g.tiles, cu_count(), read_knobs());
     if (!workspace || workspace_bytes < eg.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
     char *ws = static_cast<char *>(workspace);
     float *Q = reinterpret_cast<float *>(ws + eg.off_Q), *tru = es ? es->true_scores : reinterpret_cast<float *>(ws + eg.off_true);
@@ -1951,12 +1763,10 @@ static int eval_call(EvalCall &c, const okge_tables *t, const okge_prefix_batch 
     p.table_rows = t->n_ent; p.d = t->d; p.scorer = t->scorer; p.ldq = g.ldq; p.KB = g.KB; p.Bpad = g.Bpad;
     p.cand_first = cand->first_id; p.n_cand = cand->n;
     FusedArgs &a = c.sweep;
-    fill_fused_common(a, g, t, cand, ws);
-    a.Q = Q;
+    fill_fused_common(a, g, t, cand, Q);
     a.rk_row_ptr = rps; a.rk_true = tru; a.rk_ngroups = n_groups;          // the sweep works on the sorted batch
     a.rk_counts = eg.slab ? nullptr : c.counts;
     a.rk_slab = eg.slab ? reinterpret_cast<uint32_t *>(c.counts) : nullptr;
-    a.b_per_block = g.Bpad;
     EvalRanksArgs &r = c.rk;
     r.counts = a.rk_counts; r.slab = a.rk_slab; r.true_scores = tru; r.filt_x = fx; r.filt_ptr = filt_ptr; r.gshift = gshift;
     r.group_row = grow; r.ranks = ranks; r.acc = acc; r.n_groups = n_groups; r.tiles = g.tiles; r.B = B;
@@ -1980,7 +1790,7 @@ static int eval_issue(int phases, const EvalCall &c, hipStream_t st)
     if (phases & 2) {
         ScopedTimer tm("fused_tile_count", st);
         // (slot sizes above 256: the register-tile kernel's counting mode in a stream-K launch)
-        e = launch_score_sweep(c.g, c.sweep, c.g.tiles, st, MODE_COUNT);
+        e = launch_sweep(c.g, c.sweep_plan, c.sweep, st, MODE_COUNT);
         if (e != hipSuccess) return fail_hip(e, "fused_tile_kernel<count>");
     }
     if (phases & 4) {

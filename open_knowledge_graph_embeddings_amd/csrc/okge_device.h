@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "okge_consts.h"      // NT, BC, lds_ld, ...
 
 namespace okge {
 
@@ -355,10 +356,5 @@ __device__ __forceinline__ void lazy_rows(uint64_t mask, int64_t row, int n_deca
         j = jn; base = base_n; n = n_n; wg = wg_n; pv = pn; sv = sn; gv = gn;
     }
 }
-
-// Padded leading dimension (floats) of an LDS tile whose rows hold D16 floats: D16 + 4 = 4 * odd, so
-// (a) ds_read_b128 of 16 different rows at one column lands on 16 different 16-byte slots and
-// (b) ds_read_b32 of rows r and r+4 at 16 consecutive columns lands on disjoint bank halves.
-__host__ __device__ constexpr int lds_ld(int D16) { return D16 + 4; }
 
 }  // namespace okge

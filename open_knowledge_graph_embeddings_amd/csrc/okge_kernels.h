@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
+#include "okge_consts.h"      // NT, BC, plane_cells_per_tile, tile_grad_split, lds_ld
 #include "okge_device.h"
 #include "okge_topk.h"
 #include "../../include/okge.h"
@@ -41,15 +42,8 @@ inline hipError_t launch_with_lds(dim3 grid, dim3 block, size_t shmem, hipStream
 }
 #endif
 
-constexpr int NT = 64;             // candidate rows per tile
-constexpr int BC = 64;             // batch rows per chunk
 constexpr int LDG = 68;            // leading dimension of the 64x64 G / X tile in LDS (4*odd)
 constexpr int FUSED_THREADS = 512; // 8 waves, two per SIMD (fused_tile_kernel: score / stats / count sweep)
-// 16-byte cells of the three bf16 planes of one 64-candidate tile of D16 columns (layout: okge_dq_split.h)
-constexpr int plane_cells_per_tile(int D16) { return 3 * NT * D16 / 8; }
-// the instances of fused_tile64_kernel whose gradient product dC = G^T . Q runs on the bf16 matrix cores, from three bf16 planes
-// of Q made once per step (okge_tile_grad_split.h)
-constexpr bool tile_grad_split(int KB) { return KB == 13; }
 constexpr int POS_CACHE = 512;     // positives of one candidate tile cached in LDS (more spill to global reads)
 
 enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4, MODE_TOPK = 5 };

@@ -191,6 +191,14 @@ class HotPath:
         idx = self.device.index
         return ctypes.c_void_p(_raw_stream(torch.cuda.current_device() if idx is None else idx))
 
+    def _grow(self, need):
+        """the one workspace, reallocated only when a call needs more than it holds (the old block is dropped first)"""
+        if need > self._ws_bytes:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._ws_bytes = need
+        return self._ws
+
     def workspace(self, B, n_cand, d, kind="train"):
         """scratch for one call; kind 'score' (query block only) and 'lse' are much smaller than 'train'"""
         if kind == "score":
@@ -203,11 +211,7 @@ class HotPath:
             need = int(self.lib.okge_train_workspace_bytes(B, n_cand, d))
         if need == 0:
             raise N.OkgeError(f"invalid problem size B={B} N={n_cand} d={d}")
-        if need > self._ws_bytes:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
-        return self._ws
+        return self._grow(need)
 
     def _check(self, batch, E, R):
         if VALIDATE:
@@ -401,11 +405,7 @@ class HotPath:
         need = int(self.lib.okge_topk_workspace_bytes(B, n, d, int(k), int(range_n)))
         if need == 0:
             raise N.OkgeError(f"invalid top-k problem B={B} N={n} d={d} k={k} range_n={range_n} (1 <= k <= 64, d <= 512)")
-        if need > self._ws_bytes:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
-        return self._ws
+        return self._grow(need)
 
     def _filter(self, filt_ptr, filt_col):
         """-> (filt_ptr int64, filt_col int32, n_filter) on the device, or (None, None, 0)"""
@@ -717,10 +717,7 @@ class HotPath:
         t = self._tables(E, R, scorer)
         n_groups, n_filter = int(grp_ptr.numel()) - 1, int(filt_col.numel())
         need = int(self.lib.okge_eval_workspace_bytes(batch.B, c.n, t.d, n_groups, n_filter))
-        if need > self._ws_bytes:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
+        self._grow(need)
         if ranks is None:
             ranks = torch.empty(max(n_groups, 1), dtype=torch.int64, device=self.device)
         if acc is None:

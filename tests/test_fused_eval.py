@@ -319,7 +319,7 @@ def test_pipelined_evaluator_many_small_batches_lose_no_group(okge_lib):
 @pytest.mark.parametrize("d,scorer", [(32, "complex"), (200, "distmult"), (256, "complex")])
 def test_tail_split_sweeps(okge_lib, monkeypatch, d, scorer):
     """more candidate tiles than CUs (275 = 256 + 19): the score sweep and the counting sweep launch the leftover tiles apart,
-    rows split across workgroups (okge_api.hip tail_split) -- rows are independent, so scores and ranks are BIT-EQUAL to the
+    rows split across workgroups (okge_plan.h plan_sweep) -- rows are independent, so scores and ranks are BIT-EQUAL to the
     plain launch (OKGE_TAIL_SPLIT=0), and both equal the materialising path and the oracle's rank rule"""
     from open_knowledge_graph_embeddings_amd import hotpath as H
     hp = H.HotPath("cuda:0")

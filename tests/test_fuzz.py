@@ -93,7 +93,7 @@ def test_random_shape(okge_lib, monkeypatch, i):
 @pytest.mark.parametrize("i", range(8))
 def test_random_shape_more_tiles_than_cus(okge_lib, monkeypatch, i):
     """the same sweep where the candidate tiles outnumber the CUs (N 16.5 k .. 40 k, B 192 .. 700): rounds of one workgroup
-    per CU, the leftover tiles launched apart with the rows split across workgroups (okge_api.hip tail_split), candidate
+    per CU, the leftover tiles launched apart with the rows split across workgroups (okge_plan.h tail_split), candidate
     ranges of whole rounds when the G^T budget is forced small -- against the oracle, both losses, dropout, id lists"""
     from open_knowledge_graph_embeddings_amd import hotpath as H
     rng = np.random.default_rng(8100 + i)

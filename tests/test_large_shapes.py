@@ -1,6 +1,6 @@
 """BASELINE configs[3] at its real size: |E| = 2.5 M (and one of eight row shards, 312 500 candidates), |R| = 100 k,
 d = 256, B = 4096 -- B x N = 1.0e10 score elements, beyond 2^32, so every size_t index of the tile / dQ / score
-kernels and the candidate-range sweep of the training workspace (okge_api.hip: make_geometry) is exercised.
+kernels and the candidate-range sweep of the training workspace (okge_plan.h: plan_ranges) is exercised.
 
 Nothing of that size can be recomputed densely on the host, so parity is SAMPLED against the NumPy oracle in float64:
   scores  : whole rows of `all_outputs` for a few batch rows + a random block of columns for all rows
@@ -240,7 +240,7 @@ def test_candidate_ranges_match_single_range(okge_lib, monkeypatch):
 @pytest.mark.parametrize("d,kind,ids", [(32, "bce", False), (200, "kl", False), (256, "bce", True), (200, "bce", True)])
 def test_tail_split_matches_plain_launch(okge_lib, monkeypatch, d, kind, ids):
     """more candidate tiles than CUs: the tiles left over after whole rounds (275 tiles = 256 + 19 here) are launched apart
-    with the batch rows split across workgroups (okge_api.hip, make_geometry "tail split").  Same loss and gradients as the
+    with the batch rows split across workgroups (okge_plan.h, plan_train "tail split").  Same loss and gradients as the
     plain launch (OKGE_TAIL_SPLIT=0), up to the order the tail's partial candidate gradients are added in; also with the
     candidate ranges forced to 256 tiles, where the last range is ALL tail, and with an explicit candidate id list."""
     from open_knowledge_graph_embeddings_amd import hotpath as H

@@ -1,4 +1,6 @@
 #!/bin/sh
 # diagnostic build of the C-ABI library with s_memtime phase stamps (never shipped, never benchmarked)
+# the sources are the library's own list (_native.SOURCES)
 cd "$(dirname "$0")/../open_knowledge_graph_embeddings_amd/csrc" && \
-hipcc -O3 --offload-arch=gfx950 -std=c++17 -DOKGE_STAMPS -shared -fPIC -o ../libokge_hip_stamps.so okge_api.hip okge_train.hip okge_dq_split.hip okge_train64.hip okge_train64k.hip okge_misc.hip okge_pool.hip okge_collate.cpp okge_dataset.cpp
+hipcc -O3 --offload-arch=gfx950 -std=c++17 -DOKGE_STAMPS -shared -fPIC -o ../libokge_hip_stamps.so \
+    $(python3 -c "import sys; sys.path.insert(0, '..'); import _native; print(' '.join(_native.SOURCES))")
