@@ -16,6 +16,14 @@
  *     the last failing call on the calling thread;
  *   - ids are int32 (reference: dataset.py:891,932), tables/scores/gradients fp32 row-major;
  *   - batch rows are ordered po-rows first, then sp-rows (trainer.py:69-71,91); either may be empty.
+ *   - slot sizes (okge_tables.d): 1 .. 512 on the fused tile kernels, every entry point.  513 .. 4096 ("wide", ComplEx and
+ *     DistMult): okge_score_prefixes (cand->table included), okge_train_forward_backward with dense gradients (every flag but
+ *     OKGE_TRAIN_ROW_GRADS) and okge_evaluate_batch run on a kernel that loops over d, with the two backward products on the fp32
+ *     GEMM of okge_prefix_score_backward; okge_train_workspace_bytes / okge_score_workspace_bytes / okge_lse_workspace_bytes size
+ *     their workspaces.  Every other entry point -- OKGE_TRAIN_ROW_GRADS, the sharded phases (okge_encode_queries,
+ *     okge_fold_queries, okge_train_tiles, okge_score_queries, okge_row_logsumexp, okge_prefix_backward*), the fused evaluation
+ *     (okge_evaluate_fused*), top-k, the data-bias scorers -- answers OKGE_ERR_UNSUPPORTED above 512, and every one above 4096
+ *     (the workspace functions return 0 there).
  */
 #ifndef OKGE_H
 #define OKGE_H
@@ -32,7 +40,7 @@ extern "C" {
 enum okge_status {
     OKGE_OK = 0,
     OKGE_ERR_INVALID = -1,      /* bad argument (shape, NULL pointer, unsupported size)            */
-    OKGE_ERR_UNSUPPORTED = -2,  /* configuration outside the fused path (e.g. slot size too large) */
+    OKGE_ERR_UNSUPPORTED = -2,  /* configuration outside the path (e.g. slot size above 4096 / 512)     */
     OKGE_ERR_WORKSPACE = -3,    /* workspace too small; call okge_train_workspace_bytes()          */
     OKGE_ERR_HIP = -4           /* a HIP runtime call or kernel launch failed                      */
 };
@@ -241,8 +249,9 @@ int okge_prefix_backward_segmented(const okge_tables *t, const okge_shard *shard
                                    void *stream);
 
 /* Bytes of scratch okge_train_forward_backward / okge_train_tiles need for a batch of B rows against N candidates with
- * slot size d (0 on invalid arguments).  Training sweeps the candidates in ranges (default: G^T of one range <= 1 GiB,
- * environment OKGE_GT_MBYTES), so this grows with B x min(N, range), not with B x N: the reference's autograd graph
+ * slot size d (0 on invalid arguments, and above slot size 4096).  Training sweeps the candidates in ranges (default: G^T of
+ * one range <= 1 GiB, environment OKGE_GT_MBYTES; slot sizes above 512: G plus the range's gathered rows and their gradient
+ * rows), so this grows with B x min(N, range), not with B x N: the reference's autograd graph
  * keeps several (B, N) fp32 tensors alive instead (trainer.py:75-106). */
 size_t okge_train_workspace_bytes(int32_t B, int32_t N, int32_t d);
 /* The same for okge_train_forward_backward(OKGE_TRAIN_ROW_GRADS): the above plus the gathered occurrence rows. */

@@ -15,6 +15,7 @@
 #include "../../include/okge.h"
 #include "okge_kernels.h"
 #include "okge_plan.h"
+#include "okge_wide.h"
 
 using namespace okge;
 
@@ -169,14 +170,21 @@ int refuse_bias(int32_t scorer, const char *entry, const char *why)
     return fail(OKGE_ERR_UNSUPPORTED, std::string(entry) + " does not take the " + scorer_name(scorer) + " scorer: " + why);
 }
 
-int check_common(const okge_tables *t, const okge_prefix_batch *b, const okge_candidates *c)
+// wide_ok: the entry point has a wide path (slot sizes 513 .. 4096: okge_score_prefixes, okge_train_forward_backward,
+// okge_evaluate_batch); every other one stops at 512
+int check_common(const okge_tables *t, const okge_prefix_batch *b, const okge_candidates *c, bool wide_ok = false)
 {
     if (!t || !b || !c) return fail(OKGE_ERR_INVALID, "null descriptor");
     if (!t->E || !t->R) return fail(OKGE_ERR_INVALID, "null embedding table");
     if (t->d <= 0 || t->n_ent <= 0 || t->n_rel <= 0) return fail(OKGE_ERR_INVALID, "bad table shape");
     if (!known_scorer(t->scorer)) return fail(OKGE_ERR_INVALID, "unknown scorer");
     if (t->scorer == OKGE_COMPLEX && (t->d & 1)) return fail(OKGE_ERR_INVALID, "ComplEx needs an even slot size");
-    if (t->d > 512) return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels");
+    if (t->d > WIDE_MAX_D) return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 4096 are not supported");
+    if (t->d > 512 && !wide_ok)
+        return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels: slot sizes 513 to 4096 run through "
+                                          "okge_score_prefixes, okge_train_forward_backward (dense gradients) and okge_evaluate_batch");
+    if (t->d > 512 && sc_is_bias(t->scorer))
+        return fail(OKGE_ERR_UNSUPPORTED, "the data-bias scorers stop at slot size 512: the wide path is built for ComplEx and DistMult");
     if (b->n_po < 0 || b->n_sp < 0 || b->n_po + b->n_sp <= 0) return fail(OKGE_ERR_INVALID, "empty batch");
     if (b->n_po > 0 && (!b->po_rel || !b->po_obj)) return fail(OKGE_ERR_INVALID, "null po ids");
     if (b->n_sp > 0 && (!b->sp_subj || !b->sp_rel)) return fail(OKGE_ERR_INVALID, "null sp ids");
@@ -362,6 +370,243 @@ int check_topk(int32_t k, const okge_prefix_batch *b, const okge_candidates *c, 
     return OKGE_OK;
 }
 
+// ---- the wide path: slot sizes 513 .. 4096 (okge_wide.hip; shapes, plan and layouts: okge_plan.h) ---------------------------
+// the arguments every wide tile launch shares
+void fill_wide_common(FusedArgs &a, const WideShape &s, const okge_tables *t, const okge_candidates *c, const float *Q)
+{
+    std::memset(&a, 0, sizeof(a));
+    a.E = c->table ? c->table : t->E;
+    a.n_table_rows = c->table ? c->table_rows : t->n_ent;
+    a.id_err = id_err_ptr();
+    a.cand_ids = c->ids;
+    a.cand_first = c->first_id;
+    a.Q = Q;
+    a.drop_c = to_dev(c->drop);
+    a.d = s.d; a.N = s.N; a.B = s.B; a.Bpad = s.Bpad; a.ldq = s.ldq;
+    a.b_per_block = s.Bpad;
+}
+
+// arguments of the candidates [n_lo, n_lo + n) of the call (n_lo a multiple of the tile width): local candidate 0 of the
+// launch is candidate n_lo of the call; positives and dropout keep their global columns through cand_col0
+FusedArgs wide_range_args(const FusedArgs &base, const WideShape &s, int n_lo, int n)
+{
+    FusedArgs a = base;
+    a.N = n;
+    a.cand_first += n_lo;
+    if (a.cand_ids) a.cand_ids += n_lo;
+    a.cand_col0 += n_lo;
+    if (a.tile_ptr) a.tile_ptr += n_lo / WIDE_TN;
+    if (a.loss_partial) a.loss_partial += (size_t)(n_lo / WIDE_TN) * s.row_blocks;
+    return a;
+}
+
+int wide_score(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, float *scores, int64_t ld_scores,
+               void *workspace, size_t workspace_bytes, void *stream)
+{
+    WideShape g;
+    if (!make_wide_shape(batch->n_po + batch->n_sp, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
+    const WideScoreLayout l = wide_score_layout(g);
+    if (!workspace || workspace_bytes < l.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float *Q = reinterpret_cast<float *>(static_cast<char *>(workspace) + l.off_Q);
+    const PrefixDev p = to_dev(*batch, t);
+    {
+        ScopedTimer tm("encode_queries", st);
+        hipError_t e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, Q, g.ldq, g.Bpad, nullptr, nullptr, 0, nullptr, g.tiles,
+                                             WIDE_TN, 0, st);
+        if (e != hipSuccess) return fail_hip(e, "encode_queries");
+    }
+    FusedArgs a;
+    fill_wide_common(a, g, t, cand, Q);
+    a.X = scores;
+    a.ldx = ld_scores;
+    // (grid.y carries the tiles: sweep the candidates in launches of at most 32768 tiles)
+    constexpr int MAX_TILES = 32768;
+    for (int t0 = 0; t0 < g.tiles; t0 += MAX_TILES) {
+        FusedArgs s = wide_range_args(a, g, t0 * WIDE_TN, std::min(g.N - t0 * WIDE_TN, MAX_TILES * WIDE_TN));
+        s.X = scores + (size_t)t0 * WIDE_TN;
+        ScopedTimer tm("wide_tile_score", st);
+        hipError_t e = launch_wide_tile(MODE_SCORE, s, g.row_blocks, std::min(g.tiles - t0, MAX_TILES), st);
+        if (e != hipSuccess) return fail_hip(e, "wide_tile_kernel<score>");
+    }
+    return OKGE_OK;
+}
+
+// okge_train_forward_backward at slot sizes 513 .. 4096.  Per call: fold the queries (+ tile offsets of the positives, + the
+// clears); KL: a statistics pass over all ranges -> row log-sum-exp.  Per candidate range: the train tile launch (loss partials,
+// G), dC = G^T . Q -> dE, dQ (+)= G . Cm.  Then the prefix backward with the loss reduction.  No host synchronisation, no
+// allocation, no memset node: capturable.
+int wide_core(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, const okge_positives *pos,
+              int32_t loss_kind, float label_smoothing, double normalizer, int32_t flags, double *loss_out, float *dE, float *dR,
+              float *scores, int64_t ld_scores, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!pos || pos->nnz < 0 || (pos->nnz > 0 && (!pos->col || !pos->row))) return fail(OKGE_ERR_INVALID, "bad positives");
+    if (loss_kind != OKGE_LOSS_BCE && loss_kind != OKGE_LOSS_KL) return fail(OKGE_ERR_INVALID, "unknown loss");
+    const bool loss_only = (flags & OKGE_TRAIN_LOSS_ONLY) != 0;
+    if (!loss_out || (!loss_only && !dE)) return fail(OKGE_ERR_INVALID, "null output");
+    if (cand->table) return fail(OKGE_ERR_INVALID, "training needs candidates from the entity table");
+    if (!(normalizer > 0)) return fail(OKGE_ERR_INVALID, "normalizer must be positive");
+    if (scores && ld_scores < cand->n) return fail(OKGE_ERR_INVALID, "bad scores buffer");
+    const int B = batch->n_po + batch->n_sp;
+    WideShape g;
+    if (!make_wide_shape(B, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
+    const WidePlan pl = plan_wide(g, read_knobs());
+    const WideTrainLayout l = wide_train_layout(g, pl);
+    if (!workspace || workspace_bytes < l.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    if (pl.range_tiles > 65535) return fail(OKGE_ERR_UNSUPPORTED, "candidate range too long for one launch: lower OKGE_GT_MBYTES");
+    const bool clear_grads = (flags & OKGE_TRAIN_CLEAR_GRADS) != 0 && !loss_only;
+    if (clear_grads) {
+        if (cand->ids || !dR) return fail(OKGE_ERR_INVALID, "OKGE_TRAIN_CLEAR_GRADS needs a contiguous candidate range on an unsharded table");
+        flags |= OKGE_TRAIN_GRADS_ZERO;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    float *Q = reinterpret_cast<float *>(ws + l.off_Q);
+    const bool kl = loss_kind == OKGE_LOSS_KL;
+    hipError_t e;
+    {
+        // folded queries + per-tile offsets into the column-sorted positives + the clears (see train_core: no memset nodes)
+        ScopedTimer tm("encode_queries", st);
+        const PrefixDev p = to_dev(*batch, t);
+        ClearSpec clr = {};
+        if (kl) { clr.p[3] = reinterpret_cast<float *>(ws + l.off_ysum); clr.n[3] = g.Bpad; }
+        if (clear_grads) {
+            const int64_t d64 = t->d, hi = (int64_t)cand->first_id + cand->n;
+            clr.p[0] = dR;                      clr.n[0] = (int64_t)t->n_rel * d64;
+            clr.p[1] = dE;                      clr.n[1] = (int64_t)cand->first_id * d64;
+            clr.p[2] = dE + hi * d64;           clr.n[2] = ((int64_t)t->n_ent - hi) * d64;
+        }
+        e = launch_encode_queries(t->E, t->R, t->d, t->scorer, p, Q, g.ldq, g.Bpad, nullptr, pos->col, pos->nnz,
+                                  reinterpret_cast<int32_t *>(ws + l.off_tptr), g.tiles, WIDE_TN, 0, st,
+                                  (clear_grads || kl) ? &clr : nullptr);
+        if (e != hipSuccess) return fail_hip(e, "encode_queries");
+    }
+    FusedArgs a;
+    fill_wide_common(a, g, t, cand, Q);
+    a.ldg = pl.ldg;
+    a.pos_col = pos->col; a.pos_row = pos->row; a.nnz = pos->nnz;
+    a.tile_ptr = reinterpret_cast<const int32_t *>(ws + l.off_tptr);
+    a.grads_zero = (flags & OKGE_TRAIN_GRADS_ZERO) ? 1 : 0;
+    a.cand_exclusive = (!cand->ids || (flags & OKGE_TRAIN_UNIQUE_CANDIDATES)) ? 1 : 0;
+    a.loss_only = loss_only ? 1 : 0;
+    a.G = reinterpret_cast<float *>(ws + l.off_G);
+    a.dE = dE;
+    a.loss_partial = reinterpret_cast<double *>(ws + l.off_loss);
+    a.loss_kind = loss_kind;
+    a.inv_norm = (float)(1.0 / normalizer);
+    a.y_pos = 1.f; a.y_neg = 0.f;
+    if (loss_kind == OKGE_LOSS_BCE && label_smoothing > 0.f) {       // trainer.py:103-105, as train_core
+        const float invn = 1.0f / (float)cand->n;
+        a.y_pos = (1.0f + invn) * (1.0f - label_smoothing);
+        a.y_neg = (0.0f + invn) * (1.0f - label_smoothing);
+    }
+    auto range_of = [&](int r, int &n_lo, int &n_r, int &tiles_r) {
+        n_lo = r * pl.range_n;
+        n_r = std::min(pl.range_n, g.N - n_lo);
+        tiles_r = (n_r + WIDE_TN - 1) / WIDE_TN;
+    };
+    if (scores) {
+        for (int r = 0; r < pl.n_ranges; ++r) {
+            int n_lo, n_r, tiles_r;
+            range_of(r, n_lo, n_r, tiles_r);
+            FusedArgs s = wide_range_args(a, g, n_lo, n_r);
+            s.tile_ptr = nullptr; s.loss_partial = nullptr;
+            s.X = scores + n_lo; s.ldx = ld_scores;
+            ScopedTimer tm("wide_tile_score", st);
+            e = launch_wide_tile(MODE_SCORE, s, g.row_blocks, tiles_r, st);
+            if (e != hipSuccess) return fail_hip(e, "wide_tile_kernel<score>");
+        }
+    }
+    if (kl) {
+        // row log-sum-exp over ALL candidates first: (max, sum-exp) per (tile, row) of a range, merged in tile and range order
+        float *row_lse = reinterpret_cast<float *>(ws + l.off_lse), *ysum = reinterpret_cast<float *>(ws + l.off_ysum);
+        for (int r = 0; r < pl.n_ranges; ++r) {
+            int n_lo, n_r, tiles_r;
+            range_of(r, n_lo, n_r, tiles_r);
+            FusedArgs s = wide_range_args(a, g, n_lo, n_r);
+            s.tile_ptr = nullptr; s.loss_partial = nullptr;
+            s.stats = reinterpret_cast<float *>(ws + l.off_stats);
+            {
+                ScopedTimer tm("wide_tile_stats", st);
+                e = launch_wide_tile(MODE_STATS, s, g.row_blocks, tiles_r, st);
+                if (e != hipSuccess) return fail_hip(e, "wide_tile_kernel<stats>");
+            }
+            ScopedTimer tm("kl_row_lse", st);
+            e = launch_kl_row_lse(s.stats, tiles_r, g.B, g.Bpad, reinterpret_cast<float *>(ws + l.off_run), r == 0, r == pl.n_ranges - 1,
+                                  row_lse, st, r == 0 ? pos->row : nullptr, pos->nnz, r == 0 ? ysum : nullptr);
+            if (e != hipSuccess) return fail_hip(e, "kl_row_lse");
+        }
+        a.row_lse = row_lse;
+        a.row_ysum = ysum;
+    }
+    const int mode = kl ? MODE_TRAIN_KL : MODE_TRAIN_BCE;
+    const bool dropping = cand->drop.p > 0.f;
+    const bool slice = !cand->ids && !dropping;              // the range's masked rows ARE a slice of the table
+    float *Cm = reinterpret_cast<float *>(ws + l.off_Cm), *dC = reinterpret_cast<float *>(ws + l.off_dC);
+    float *dQ = reinterpret_cast<float *>(ws + l.off_dQ), *slab = reinterpret_cast<float *>(ws + l.off_slab);
+    for (int r = 0; r < pl.n_ranges; ++r) {
+        int n_lo, n_r, tiles_r;
+        range_of(r, n_lo, n_r, tiles_r);
+        const FusedArgs ar = wide_range_args(a, g, n_lo, n_r);
+        {
+            ScopedTimer tm("wide_tile_train", st);
+            e = launch_wide_tile(mode, ar, g.row_blocks, tiles_r, st);
+            if (e != hipSuccess) return fail_hip(e, "wide_tile_kernel<train>");
+        }
+        if (loss_only) continue;
+        const float *c_op = t->E + (size_t)(cand->first_id + n_lo) * t->d;
+        int64_t ld_c = t->d;
+        if (!slice) {
+            ScopedTimer tm("wide_gather", st);
+            e = launch_wide_gather(t->E, ar.cand_ids, ar.cand_first, n_lo, n_r, t->d, g.ldq, a.drop_c, a.n_table_rows, Cm, st);
+            if (e != hipSuccess) return fail_hip(e, "wide_gather");
+            c_op = Cm; ld_c = g.ldq;
+        }
+        {
+            // dC = G^T . Q.  A plain slice on zero gradients: the product's rows ARE the rows of dE
+            const bool direct = slice && a.grads_zero;
+            {
+                ScopedTimer tm("wide_dc_gemm", st);
+                e = launch_gemm_f32(true, a.G, pl.ldg, Q, g.ldq, direct ? dE + (size_t)(cand->first_id + n_lo) * t->d : dC,
+                                    direct ? (int64_t)t->d : (int64_t)g.ldq, n_r, t->d, g.B, 1, g.B, 0, st);
+                if (e != hipSuccess) return fail_hip(e, "gemm_f32_kernel<dC>");
+            }
+            if (!direct) {
+                ScopedTimer tm("wide_dc_scatter", st);
+                e = launch_wide_dc_scatter(dC, g.ldq, ar.cand_ids, ar.cand_first, n_lo, n_r, t->d, a.drop_c, a.cand_exclusive,
+                                           a.grads_zero, dE, a.n_table_rows, st);
+                if (e != hipSuccess) return fail_hip(e, "wide_dc_scatter");
+            }
+        }
+        {
+            ScopedTimer tm("wide_dq_gemm", st);
+            e = launch_gemm_f32(false, a.G, pl.ldg, c_op, ld_c, slab, g.ldq, g.B, t->d, n_r, pl.dq_splits, pl.dq_k_per,
+                                (int64_t)g.Bpad * g.ldq, st);
+            if (e != hipSuccess) return fail_hip(e, "gemm_f32_kernel<dQ>");
+        }
+        {
+            ScopedTimer tm("wide_dq_reduce", st);
+            e = launch_wide_dq_reduce(slab, pl.dq_splits, (int64_t)g.Bpad * g.ldq, g.B, t->d, g.ldq, r > 0, dQ, st);
+            if (e != hipSuccess) return fail_hip(e, "wide_dq_reduce");
+        }
+    }
+    if (loss_only) {
+        ScopedTimer tm("loss_reduce", st);
+        e = launch_loss_reduce(a.loss_partial, pl.n_loss_partials, loss_out, st);
+        if (e != hipSuccess) return fail_hip(e, "loss_reduce");
+        return OKGE_OK;
+    }
+    {
+        ScopedTimer tm("prefix_backward", st);      // + the deterministic loss reduction
+        const PrefixDev p = to_dev(*batch, t);
+        e = launch_prefix_backward(t->E, t->R, t->d, t->scorer, p, dQ, 1, g.Bpad, g.ldq, nullptr, dE, dR, a.loss_partial,
+                                   pl.n_loss_partials, loss_out, st, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                                   (flags & OKGE_TRAIN_DISTINCT_PREFIX_ROWS) ? 1 : 0);
+        if (e != hipSuccess) return fail_hip(e, "prefix_backward");
+    }
+    return OKGE_OK;
+}
+
 }  // namespace
 
 int okge::report_error(int code, const std::string &msg) { return fail(code, msg); }
@@ -374,6 +619,10 @@ const char *okge_last_error(void) { return g_err.c_str(); }
 
 size_t okge_train_workspace_bytes(int32_t B, int32_t N, int32_t d)
 {
+    if (d > 512) {
+        WideShape w;
+        return make_wide_shape(B, N, d, w) ? wide_train_layout(w, plan_wide(w, read_knobs())).total : 0;
+    }
     Shape s;
     if (!make_shape(B, N, d, s)) return 0;
     return train_layout(s, plan_train(s, cu_count(), read_knobs())).total;
@@ -381,12 +630,20 @@ size_t okge_train_workspace_bytes(int32_t B, int32_t N, int32_t d)
 
 size_t okge_score_workspace_bytes(int32_t B, int32_t d)
 {
+    if (d > 512) {
+        WideShape w;
+        return make_wide_shape(B, 1, d, w) ? wide_score_layout(w).total : 0;
+    }
     Shape s;
     return make_shape(B, 1, d, s) ? score_layout(s).total : 0;
 }
 
 size_t okge_lse_workspace_bytes(int32_t B, int32_t N, int32_t d)
 {
+    if (d > 512) {
+        WideShape w;
+        return make_wide_shape(B, N, d, w) ? wide_train_layout(w, plan_wide(w, read_knobs())).lse_bytes : 0;
+    }
     Shape s;
     if (!make_shape(B, N, d, s)) return 0;
     return lse_layout(s, plan_ranges(s, cu_count(), read_knobs())).lse_bytes;
@@ -395,8 +652,9 @@ size_t okge_lse_workspace_bytes(int32_t B, int32_t N, int32_t d)
 int okge_score_prefixes(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
                         float *scores, int64_t ld_scores, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (int rc = check_common(t, batch, cand)) return rc;
+    if (int rc = check_common(t, batch, cand, true)) return rc;
     if (!scores || ld_scores < cand->n) return fail(OKGE_ERR_INVALID, "bad scores buffer");
+    if (is_wide(t->d)) return wide_score(t, batch, cand, scores, ld_scores, workspace, workspace_bytes, stream);
     Shape g;
     if (!make_shape(batch->n_po + batch->n_sp, cand->n, t->d, g)) return fail(OKGE_ERR_INVALID, "bad shape");
     const ScoreLayout l = score_layout(g);   // only the query block
@@ -639,7 +897,7 @@ static int train_core(const okge_tables *t, const okge_shard *sh, const okge_pre
 size_t okge_train_row_grads_workspace_bytes(int32_t B, int32_t N, int32_t d)
 {
     Shape s;
-    if (!make_shape(B, N, d, s)) return 0;
+    if (d > 512 || !make_shape(B, N, d, s)) return 0;     // (the row-sparse step stops at slot size 512)
     return row_grads_layout(s, train_layout(s, plan_train(s, cu_count(), read_knobs())).total).total;
 }
 
@@ -692,8 +950,14 @@ int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *b
                                 float *scores, int64_t ld_scores, void *workspace, size_t workspace_bytes,
                                 void *stream)
 {
-    if (int rc = check_common(t, batch, cand)) return rc;
+    if (int rc = check_common(t, batch, cand, true)) return rc;
     if (!(flags & OKGE_TRAIN_LOSS_ONLY) && !dR) return fail(OKGE_ERR_INVALID, "null output");
+    if (is_wide(t->d)) {
+        if (flags & OKGE_TRAIN_ROW_GRADS)
+            return fail(OKGE_ERR_UNSUPPORTED, "OKGE_TRAIN_ROW_GRADS stops at slot size 512: slot sizes 513 to 4096 train with dense gradients");
+        return wide_core(t, batch, cand, pos, loss_kind, label_smoothing, normalizer, flags, loss_out, dE, dR, scores, ld_scores,
+                         workspace, workspace_bytes, stream);
+    }
     if (flags & OKGE_TRAIN_ROW_GRADS)
         return train_row_grads(t, batch, cand, pos, loss_kind, label_smoothing, normalizer, flags, loss_out, dE, dR, scores, ld_scores,
                                workspace, workspace_bytes, stream);
@@ -767,7 +1031,9 @@ int okge_train_tiles(const okge_tables *t, const okge_shard *sh, const float *Q,
                      float *dE, float *dQ, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!t || !cand || !t->E || t->d <= 0 || t->n_ent <= 0) return fail(OKGE_ERR_INVALID, "bad tables");
-    if (t->d > 512) return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels");
+    if (t->d > 512)
+        return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels: the sharded phases stop there, "
+                                          "the unsharded okge_train_forward_backward takes slot sizes up to 4096");
     if (int rc = check_shard(t, sh)) return rc;
     if (!Q || !dQ || B <= 0 || cand->n <= 0) return fail(OKGE_ERR_INVALID, "bad query block / candidates");
     if (!cand->ids && (cand->first_id < 0 || (int64_t)cand->first_id + cand->n > t->n_ent))
@@ -780,7 +1046,9 @@ static int check_query_call(const okge_tables *t, const okge_shard *sh, const fl
                             const okge_candidates *cand)
 {
     if (!t || !cand || !t->E || t->d <= 0 || t->n_ent <= 0) return fail(OKGE_ERR_INVALID, "bad tables");
-    if (t->d > 512) return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels");
+    if (t->d > 512)
+        return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels: the sharded phases stop there, "
+                                          "the unsharded okge_score_prefixes / okge_train_forward_backward take slot sizes up to 4096");
     if (int rc = check_shard(t, sh)) return rc;
     if (!Q || B <= 0 || cand->n <= 0 || ldq != okge_query_ld(t->d))
         return fail(OKGE_ERR_INVALID, "bad query block / candidates");
@@ -1728,7 +1996,9 @@ static int eval_call(EvalCall &c, const okge_tables *t, const okge_prefix_batch 
     if (!filt_ptr || !row_ptr || !grp_ptr || (n_groups > 0 && !ids) || (!es && (!ranks || !acc)) || n_groups < 0 || n_filter < 0 ||
         (n_filter > 0 && !filt_col))                      // (a batch without answer groups has no ids array)
         return fail(OKGE_ERR_INVALID, "bad evaluate arguments");
-    if (t->d > 512) return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels");
+    if (t->d > 512)
+        return fail(OKGE_ERR_UNSUPPORTED, "slot sizes above 512 are not supported by the tile kernels: fused evaluation stops there, "
+                                          "okge_evaluate_batch (PipelinedEvaluator) takes slot sizes up to 4096");
     if (cand->table || cand->drop.p > 0.f || (batch && (batch->drop_po_ent.p > 0.f || batch->drop_sp_ent.p > 0.f ||
         batch->drop_po_rel.p > 0.f || batch->drop_sp_rel.p > 0.f)))
         return fail(OKGE_ERR_UNSUPPORTED, "fused evaluation is the eval-mode path (no dropout, candidates from the entity table)");

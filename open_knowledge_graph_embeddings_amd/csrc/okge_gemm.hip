@@ -19,6 +19,7 @@
 #include "okge_device.h"
 #include "okge_eval_device.h"
 #include "okge_kernels.h"
+#include "okge_wide.h"
 
 namespace okge {
 
@@ -235,6 +236,18 @@ hipError_t launch_score_backward(int scorer, int sp, const float *G, int64_t ld_
         }
         hipLaunchKernelGGL(fold_backward_kernel, dim3(b), dim3(128), 0, st, scorer, sp, ent, ld_ent, rel, ld_rel, dq, d, d_ent, d_rel);
     }
+    return hipGetLastError();
+}
+
+// the GEMM on its own, for the wide path's two backward products (okge_wide.h)
+hipError_t launch_gemm_f32(bool ta, const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc, int M, int N, int K,
+                           int splits, int k_per_split, int64_t slab_stride, hipStream_t st)
+{
+    if (M <= 0 || N <= 0 || K <= 0 || splits <= 0) return hipSuccess;
+    const dim3 grid((M + GM - 1) / GM, (N + GN - 1) / GN, splits);
+    if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
+    if (ta) hipLaunchKernelGGL(gemm_f32_kernel<true>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, k_per_split, slab_stride);
+    else hipLaunchKernelGGL(gemm_f32_kernel<false>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, k_per_split, slab_stride);
     return hipGetLastError();
 }
 

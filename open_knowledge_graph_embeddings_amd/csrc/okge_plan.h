@@ -375,5 +375,98 @@ inline RowsKeys take_rows_keys(Arena &ar, int64_t n)
     return k;
 }
 
+// ---- the wide path: slot sizes 513 .. 4096 (okge_wide.hip) ------------------------------------------
+// Unfused: wide_tile_kernel contracts over d in LDS-staged chunks and leaves G = dLoss/dScore / normalizer of one candidate
+// range in the workspace; the two backward products run on gemm_f32_kernel (okge_gemm.hip), where d is a free dimension.
+// Nothing above this line changes for it: a wide call has its own shape, plan and layouts.
+constexpr int WIDE_MAX_D = 4096;                 // slot sizes 513 .. WIDE_MAX_D take the wide path
+constexpr int WIDE_TM = 128, WIDE_TN = 128;      // output tile of wide_tile_kernel: batch rows x candidates per workgroup
+constexpr int WIDE_KC = 16;                      // columns of d per LDS-staged chunk (and the padding unit of ldq)
+constexpr int WIDE_GEMM_TILE = 64, WIDE_GEMM_K = 16;   // gemm_f32_kernel's output tile and K chunk (okge_gemm.hip)
+inline bool is_wide(int d) { return d > 512 && d <= WIDE_MAX_D; }
+
+struct WideShape {
+    int B, N, d, Bpad, ldq, tiles, row_blocks;
+};
+inline bool make_wide_shape(int B, int N, int d, WideShape &s)
+{
+    if (B <= 0 || N <= 0 || !is_wide(d)) return false;
+    s.B = B; s.N = N; s.d = d;
+    s.row_blocks = (B + WIDE_TM - 1) / WIDE_TM;
+    s.Bpad = s.row_blocks * WIDE_TM;
+    s.ldq = (d + WIDE_KC - 1) / WIDE_KC * WIDE_KC;
+    s.tiles = (N + WIDE_TN - 1) / WIDE_TN;
+    return true;
+}
+
+// Candidate ranges of whole 128-candidate tiles: G [Bpad][range_n], the gathered masked rows Cm [range_n][ldq] and their
+// gradient dC [range_n][ldq] of ONE range stay under OKGE_GT_MBYTES (a range is never shorter than one tile).  The dQ product of
+// a range is split over K = the range's candidates into dq_splits slabs of dq_k_per candidates, added in split order.
+struct WidePlan : Ranges {
+    int    ldg;                  // leading dimension of G: the candidates of one range
+    int    dq_splits, dq_k_per;
+    int    n_loss_partials;      // one double per (candidate tile, row block)
+    size_t tile_bytes;           // G + Cm + dC of one tile of a range
+};
+inline WidePlan plan_wide(const WideShape &s, const Knobs &k)
+{
+    WidePlan p;
+    const int64_t budget = (int64_t)std::max(1, k.gt_mbytes.value_or(1024)) << 20;
+    p.tile_bytes = (size_t)WIDE_TN * ((size_t)s.Bpad + 2 * (size_t)s.ldq) * sizeof(float);
+    int64_t rt = budget / (int64_t)p.tile_bytes;
+    rt = std::max<int64_t>(1, std::min<int64_t>(rt, s.tiles));
+    p.n_ranges = (s.tiles + (int)rt - 1) / (int)rt;
+    p.range_tiles = (s.tiles + p.n_ranges - 1) / p.n_ranges;      // even out the ranges
+    p.n_ranges = (s.tiles + p.range_tiles - 1) / p.range_tiles;
+    p.range_n = p.range_tiles * WIDE_TN;
+    p.ldg = p.range_n;
+    // dQ = G . Cm has few output tiles and a long contraction: split it, at most 1024 workgroups and 64 slabs
+    const int out_tiles = ((s.B + WIDE_GEMM_TILE - 1) / WIDE_GEMM_TILE) * ((s.d + WIDE_GEMM_TILE - 1) / WIDE_GEMM_TILE);
+    const int kn = std::min(p.range_n, s.N);
+    int splits = std::max(1, std::min(64, std::min(1024 / out_tiles, (kn + 4 * WIDE_GEMM_K - 1) / (4 * WIDE_GEMM_K))));
+    p.dq_k_per = ((kn + splits - 1) / splits + WIDE_GEMM_K - 1) / WIDE_GEMM_K * WIDE_GEMM_K;
+    p.dq_splits = (kn + p.dq_k_per - 1) / p.dq_k_per;
+    p.n_loss_partials = s.tiles * s.row_blocks;
+    return p;
+}
+
+struct WideScoreLayout { size_t off_Q, total; };
+inline WideScoreLayout wide_score_layout(const WideShape &s)
+{
+    Arena ar;
+    WideScoreLayout l;
+    l.off_Q = ar.take((size_t)s.Bpad * s.ldq * sizeof(float));
+    l.total = ar.total();
+    return l;
+}
+
+struct WideTrainLayout {
+    size_t off_Q, off_tptr, off_stats, off_lse, off_ysum, off_run;      // the score / row log-sum-exp part
+    size_t score_bytes, lse_bytes;
+    size_t off_loss, off_G, off_Cm, off_dC, off_dQ, off_slab;           // the training part
+    size_t total;
+};
+inline WideTrainLayout wide_train_layout(const WideShape &s, const WidePlan &p)
+{
+    Arena ar;
+    WideTrainLayout l;
+    l.off_Q = ar.take((size_t)s.Bpad * s.ldq * sizeof(float));
+    l.score_bytes = ar.total();
+    l.off_tptr = ar.take((size_t)(s.tiles + 1) * sizeof(int32_t));
+    l.off_stats = ar.take((size_t)p.range_tiles * s.Bpad * 2 * sizeof(float));
+    l.off_lse = ar.take((size_t)s.Bpad * sizeof(float));
+    l.off_ysum = ar.take((size_t)s.Bpad * sizeof(float));
+    l.off_run = ar.take((size_t)s.Bpad * 2 * sizeof(float));
+    l.lse_bytes = ar.total();
+    l.off_loss = ar.take((size_t)p.n_loss_partials * sizeof(double));
+    l.off_G = ar.take((size_t)s.Bpad * p.ldg * sizeof(float));
+    l.off_Cm = ar.take((size_t)p.range_n * s.ldq * sizeof(float));
+    l.off_dC = ar.take((size_t)p.range_n * s.ldq * sizeof(float));
+    l.off_dQ = ar.take((size_t)s.Bpad * s.ldq * sizeof(float));
+    l.off_slab = ar.take((size_t)p.dq_splits * s.Bpad * s.ldq * sizeof(float));
+    l.total = ar.total();
+    return l;
+}
+
 }  // namespace okge
 #pragma GCC visibility pop

@@ -37,6 +37,9 @@ class FusedEvaluator:
     (materialised scores) covers dropout and candidate tables."""
 
     def __init__(self, E, R, scorer, engine=None, run_len=48, two_streams=True, n_streams=None, collect_ranks=False):
+        if E.shape[1] > H.TILE_MAX_SLOT:
+            raise NotImplementedError(f"FusedEvaluator: the fused evaluation stops at slot size {H.TILE_MAX_SLOT}; PipelinedEvaluator "
+                                      f"evaluates slot sizes up to {H.WIDE_MAX_SLOT}")
         self.E, self.R, self.scorer = E, R, scorer
         # collect_ranks: keep every answer group's rank (self.ranks after run(): int64, batches in order, groups in the
         # batch's row / group order) instead of treating the ranks as scratch -- for parity tests and error analysis
@@ -118,7 +121,7 @@ class FusedEvaluator:
 
 class PipelinedEvaluator:
     """The evaluation loop on the MATERIALISING path (okge_evaluate_batch: scores into a (B, N) block, then filtered ranks
-    and meters) -- any slot size, dropout, candidate tables; FusedEvaluator is the path without the score block in
+    and meters) -- slot sizes up to 4096 (above 512 on the wide path), dropout, candidate tables; FusedEvaluator is the path without the score block in
     eval mode.  Batch i runs on stream i % n_streams with that stream's own score block, rank buffer and query workspace:
     independent chains [scores] [ranks] [meters], no cross-stream wait per batch (each costs ~10 us of queue latency on
     this hardware; the first version ordered a scoring and a ranking stream with two events per batch), so the ranking of

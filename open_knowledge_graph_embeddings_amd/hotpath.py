@@ -45,6 +45,11 @@ class DropoutSpec:
 
 NO_DROP = DropoutSpec()
 
+# slot sizes: the fused tile kernels (and everything built on them: the row-sparse step, the fused evaluation, top-k, the
+# sharded phases) stop at TILE_MAX_SLOT; okge_score_prefixes, okge_train_forward_backward with dense gradients and
+# okge_evaluate_batch go on to WIDE_MAX_SLOT on the wide path (csrc/okge_wide.hip)
+TILE_MAX_SLOT, WIDE_MAX_SLOT = 512, 4096
+
 # OKGE_VALIDATE=1: check every id tensor against the table sizes before a call (one host sync per call).  The kernels
 # trust their ids -- they live in device memory -- so a bad id is an out-of-bounds access; use this while integrating.
 VALIDATE = os.environ.get("OKGE_VALIDATE") == "1"

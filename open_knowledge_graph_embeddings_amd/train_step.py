@@ -39,6 +39,11 @@ class FusedTrainStep:
         self.decay_window = None if decay_window is None else int(decay_window)
         if self.decay_window is not None and (not self.sparse or self.decay_window < 1):
             raise ValueError("decay_window (deferred weight decay) belongs to the sparse step and is >= 1")
+        if E.shape[1] > H.WIDE_MAX_SLOT:
+            raise NotImplementedError(f"FusedTrainStep: slot sizes above {H.WIDE_MAX_SLOT}")
+        if self.sparse and E.shape[1] > H.TILE_MAX_SLOT:
+            raise NotImplementedError(f"FusedTrainStep(sparse=True): the row-sparse step stops at slot size {H.TILE_MAX_SLOT}; slot "
+                                      f"sizes up to {H.WIDE_MAX_SLOT} train with dense gradients (sparse=False)")
         if self.sparse:
             if weight_decay != 0 and self.decay_window is None:
                 raise ValueError("weight_decay option is not compatible with sparse gradients")
