@@ -1,4 +1,4 @@
-// The host-side planner of the tile kernels' entry points (okge_api.hip): plain integer arithmetic on
+// The host-side planner of the tile kernels' entry points (okge_api_*.hip): plain integer arithmetic on
 // (B, N, d, the device's CU count, the five OKGE_* overrides), no HIP header, no global state -- it compiles with any
 // C++17 compiler and tests/test_launch_plan.py drives it on the CPU (tests/plan_driver.cpp).  Three kinds of answer:
 //   Shape                          the padded problem (make_shape)
@@ -16,7 +16,7 @@
 #pragma GCC visibility push(hidden)   // inline functions of namespace okge, but none of them an export of the library
 namespace okge {
 
-constexpr size_t PLANE_CELL_BYTES = 16;   // sizeof(v8bf): one cell of a bf16 plane    } okge_api.hip asserts both against
+constexpr size_t PLANE_CELL_BYTES = 16;   // sizeof(v8bf): one cell of a bf16 plane    } okge_core.hip asserts both against
 constexpr size_t TOPK_REC_BYTES = 8;      // sizeof(TopkRec): (score, column)          } the device-side types
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

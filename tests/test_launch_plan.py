@@ -1,7 +1,8 @@
 """CPU-only: the launch planner (csrc/okge_plan.h) -- shapes, launch plans and workspace layouts as plain integer arithmetic
 on (B, N, d, CU count, the five OKGE_* overrides).  tests/plan_driver.cpp includes nothing but that header, is compiled here with
 the host compiler, and prints every plan field as JSON; the tests check the invariants the launches rely on, a table of plans
-pinned from the code before the planner was cut out of okge_api.hip, and that the built library answers the same sizes."""
+pinned from the code before the planner was cut out of the C ABI's host layer (now csrc/okge_api_*.hip), and that the built library
+answers the same sizes."""
 import itertools
 import json
 import os

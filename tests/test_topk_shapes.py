@@ -155,7 +155,7 @@ def test_topk_ties_zero_table_and_nan(hp, scorer, d):
 
 def test_topk_tail_split_launch(hp):
     """more 64-candidate tiles than compute units and three 64-row blocks: the closing round of the sweep is launched apart with
-    the rows split (okge_api.hip launch_sweep), so the records' per-tile pointer must move with the window.  The N = 1500 cases above
+    the rows split (okge_api_train.hip launch_sweep), so the records' per-tile pointer must move with the window.  The N = 1500 cases above
     have 24 tiles and never take that launch; the library's timing name says whether this one did."""
     dev = torch.device("cuda:0")
     cus = torch.cuda.get_device_properties(0).multi_processor_count

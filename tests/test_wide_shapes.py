@@ -1,4 +1,4 @@
-"""The wide path (slot sizes 513 .. 4096: csrc/okge_wide.hip, wide_core in csrc/okge_api.hip) on the GPU against float64, at the
+"""The wide path (slot sizes 513 .. 4096: csrc/okge_wide.hip, wide_core in csrc/okge_api_train.hip) on the GPU against float64, at the
 smallest shapes at which it can go wrong.  Truth and fp32 yardstick: tests/wide_reference.py (pinned by test_wide_reference.py);
 rule: lstm_reference.band_check -- per |want| band max error <= 3 x and rms error <= 1.6 x the fp32 restatement's error against
 float64, floor 1e-7 max|want| -- on scores, dE and dR; the loss within 3e-5 relative (test_hip_parity.py's bound).

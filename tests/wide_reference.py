@@ -1,5 +1,5 @@
 """A plain numpy / torch-CPU restatement of okge_train_forward_backward at slot sizes 513 .. 4096 (csrc/okge_wide.hip +
-wide_core in csrc/okge_api.hip).  Not a conftest: the tests import it.
+wide_core in csrc/okge_api_train.hip).  Not a conftest: the tests import it.
 
 Two restatements of one step on fp32 inputs:
   truth      float64 through oracle.kge_oracle.step_forward_backward (masks from dropout_keep_mask or given explicitly)
