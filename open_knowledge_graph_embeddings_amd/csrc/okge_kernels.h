@@ -151,16 +151,6 @@ hipError_t launch_kl_row_lse(const float *stats, int tiles, int B, int Bpad, flo
                              hipStream_t st, const int32_t *pos_row = nullptr, int nnz = 0, float *row_ysum = nullptr);
 hipError_t launch_encode_rows(const float *table, int64_t table_rows, int d, const int32_t *ids, int first_id, int n,
                               const DropDev &drop, float *out, int64_t ld_out, int *id_err, hipStream_t st);
-hipError_t launch_scale(float *x, int64_t n, const float *alpha_dev, hipStream_t st);
-hipError_t launch_rescale2(float *x0, int64_t n0, float *x1, int64_t n1, const float *alpha_dev, float applied, hipStream_t st);
-hipError_t launch_adagrad(float *p, float *g, float *sum, int64_t n, float lr, float wd, float eps, int zero_grad,
-                          hipStream_t st);
-hipError_t launch_adagrad2(float *p0, float *g0, float *s0, int64_t n0, float *p1, float *g1, float *s1, int64_t n1,
-                           float lr, float wd, float eps, int zero_grad, hipStream_t st);
-// torch.nn.utils.clip_grad_norm_ over two gradient tensors: coef = min(1, max_norm / (||g|| + 1e-6)) -> coef_dev (fp32),
-// ||g|| -> norm_dev (double); the caller scales with launch_scale (trainer.py:236-240)
-hipError_t launch_clip_coef(const float *g0, int64_t n0, const float *g1, int64_t n1, float max_norm, double *partial,
-                            int n_partial, float *coef_dev, double *norm_dev, hipStream_t st);
 // log-sum-exp over `world` per-shard row log-sum-exps: out[b] = log sum_r exp(parts[r][b])  (sharded KL loss)
 hipError_t launch_merge_lse(const float *parts, int world, int B, float *out, hipStream_t st);
 // backward of the prefix scores from a dense (b, n) gradient block, and the scatter of encoded-row gradients (okge_gemm.hip)
@@ -233,12 +223,23 @@ hipError_t launch_tucker3_apply(const float *M, int64_t ld_m, const float *x, in
                                 int64_t ld_out, hipStream_t st);
 hipError_t launch_tucker3_outer(const float *u, int64_t ld_u, const float *v, int64_t ld_v, int n, int d, float *out, int64_t ld_out,
                                 hipStream_t st);
+// ---- okge_optim.hip: the dense optimizer, clipping and scaling launches -----------------------------------------------------
+hipError_t launch_scale(float *x, int64_t n, const float *alpha_dev, hipStream_t st);
+hipError_t launch_rescale2(float *x0, int64_t n0, float *x1, int64_t n1, const float *alpha_dev, float applied, hipStream_t st);
+hipError_t launch_adagrad(float *p, float *g, float *sum, int64_t n, float lr, float wd, float eps, int zero_grad,
+                          hipStream_t st);
+hipError_t launch_adagrad2(float *p0, float *g0, float *s0, int64_t n0, float *p1, float *g1, float *s1, int64_t n1,
+                           float lr, float wd, float eps, int zero_grad, hipStream_t st);
+// torch.nn.utils.clip_grad_norm_ over two gradient tensors: coef = min(1, max_norm / (||g|| + 1e-6)) -> coef_dev (fp32),
+// ||g|| -> norm_dev (double); the caller scales with launch_scale (trainer.py:236-240)
+hipError_t launch_clip_coef(const float *g0, int64_t n0, const float *g1, int64_t n1, float max_norm, double *partial,
+                            int n_partial, float *coef_dev, double *norm_dev, hipStream_t st);
 // dense Adagrad over up to four tensors in one launch; a tensor may come with a touched-row byte map (rows whose byte differs
 // from `stamp` hold an all-zero gradient by contract: it is neither read nor cleared)
 constexpr int ADAGRAD_MAX_SEGS = 4;
 struct AdagradSegM { float *p, *g, *s; int64_t n; const uint8_t *touched; int32_t row_len, stamp, zero_grad; };
 hipError_t launch_adagrad_multi(const AdagradSegM *segs, int n_segs, float lr, float wd, float eps, hipStream_t st);
-// deferred weight-decay-only updates (okge_adagrad_lazy; okge_misc.hip): steps == nullptr: a plain dense tensor of rows * row_len floats
+// deferred weight-decay-only updates (okge_adagrad_lazy): steps == nullptr: a plain dense tensor of rows * row_len floats
 constexpr int LAZY_STEP = 0, LAZY_FLUSH = 1;
 struct LazySeg { float *p, *g, *s; int32_t *steps; uint8_t *touched; int64_t rows; int32_t row_len, stamp; };
 hipError_t launch_adagrad_lazy(const LazySeg *segs, int n_segs, int32_t *counters, int window, int mode, float lr, float wd,
@@ -288,9 +289,10 @@ hipError_t launch_dc_reduce_streamk(const float *slab, int tiles, int chunks_per
                                     int64_t table_rows, int *id_err, hipStream_t st);
 hipError_t launch_score_triples(const float *S, int64_t lds_, const float *Rr, int64_t ldr, const float *O, int64_t ldo,
                                 int n, int d, int scorer, float *out, hipStream_t st);
+// ---- okge_rank.hip: evaluation's rank launches --------------------------------------------------------------------------------
 hipError_t launch_rank_metrics(const int64_t *ranks, int64_t n, double *acc, hipStream_t st);
 // fused evaluation (okge_evaluate_fused): point scores in the tile kernel's summation order, then ranks from the counts
-// fused evaluation: the two small kernels around the tile sweep (okge_misc.hip)
+// fused evaluation: the two small kernels around the tile sweep
 struct EvalPointsArgs {
     const float   *E, *R;
     PrefixDev      p;

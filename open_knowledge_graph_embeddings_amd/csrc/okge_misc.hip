@@ -1,15 +1,22 @@
-// Small HBM-bound kernels around the fused tile kernels (gfx950):
-//   encode_queries_kernel   gather + dropout + fold (s,r)/(r,o) into one query row   model.py:455-510, :205-216, :269-272
-//   prefix_backward_kernel  sum dQ slabs, chain rule to s/r/o rows, scatter-add       autograd of the above + embedding_dense_backward
-//   loss_reduce_kernel      deterministic sum of per-workgroup loss partials           trainer.py:106 (reduction='sum')
-//   kl_* kernels            log-sum-exp per row from tile partials, positives per row  trainer.py:99-100
-//   adagrad_kernel          dense Adagrad sweep (+ zero_grad)                          utils/optim.py:139-160 / torch.optim.Adagrad
-//   ranks_kernel            filtered ranks, exact integer counts                       dataset.py:423-446
+// The prefix path's small HBM-bound kernels around the fused tile kernels (gfx950).  The optimizer kernels are in okge_optim.hip,
+// evaluation's rank kernels in okge_rank.hip.
+//   encode_queries_kernel        gather + dropout + fold (s,r)/(r,o) into one query row; extra workgroups: tile offsets of the
+//                                positives, gradient clears                                 model.py:455-510, :205-216, :269-272
+//   query_planes_kernel          the bf16 planes of a query block folded elsewhere
+//   fold_queries_kernel          the fold alone, from already masked entity rows (sharded path)
+//   slab_reduce_kernel           dQ = sum of the dQ kernel's slabs (sharded path)
+//   dc_reduce_kernel             dE[candidates] (+)= sum of the tile kernel's candidate-gradient slabs
+//   dc_reduce_streamk_kernel     the same for a stream-K launch of fused_tile64k_kernel
+//   prefix_backward_kernel       sum dQ slabs, chain rule to s/r/o rows, scatter-add        autograd of the fold + embedding_dense_backward
+//   prefix_backward_vec_kernel   its float4 form (and the loss reduction)
+//   row_segment_sum_kernel       stored gradient rows added per relation / entity, no float atomics
+//   loss_reduce_kernel           deterministic sum of per-workgroup loss partials           trainer.py:106 (reduction='sum')
+//   kl_count_pos_kernel, kl_row_lse_kernel, merge_lse_kernel
+//                                label mass and log-sum-exp per row, from tile partials / from the shards   trainer.py:99-100
+//   encode_rows_kernel           table rows by id, with dropout (okge_encode_rows)
+//   score_triples_kernel         per-triple score of encoded rows                           model.py:231-238, :276
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
-#include "okge_device.h"
 #include "okge_kernels.h"
 #include "okge_tile.h"
 #include "okge_eval_device.h"
@@ -544,42 +551,16 @@ __global__ __launch_bounds__(256) void kl_row_lse_kernel(const float *__restrict
     }
 }
 
-__global__ __launch_bounds__(256) void adagrad_kernel(float *__restrict__ p, float *__restrict__ g,
-                                                      float *__restrict__ sum, int64_t n, float lr, float wd,
-                                                      float eps, int zero_grad)
+// log-sum-exp over the shards' row log-sum-exps (sharded KL loss)
+__global__ __launch_bounds__(256) void merge_lse_kernel(const float *__restrict__ parts, int world, int B, float *__restrict__ out)
 {
-    const int64_t n4 = n >> 2;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    float4 *p4 = reinterpret_cast<float4 *>(p), *g4 = reinterpret_cast<float4 *>(g), *s4 = reinterpret_cast<float4 *>(sum);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 pv = p4[i], gv = g4[i], sv = s4[i];
-        const float4 p_old = pv, s_old = sv;
-        float *pp = &pv.x, *gg = &gv.x, *ss = &sv.x;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float gj = fmaf(wd, pp[j], gg[j]);
-            ss[j] = fmaf(gj, gj, ss[j]);
-            pp[j] = pp[j] - lr * (gj / (sqrtf(ss[j]) + eps));
-        }
-        // store only what changed.  A row no gradient reached still moves by the weight-decay term (the reference applies
-        // wd = 1e-10 to ALL rows, utils/optim.py:139-160) -- but once its accumulator has seen a real gradient, that term is
-        // below half an ulp of both the accumulator and the parameter and the arithmetic above returns the old bits: such
-        // rows (most token rows of a token-pooled step, the entities outside a sampled candidate list) then cost three
-        // read streams instead of three reads + two writes.  Memory ends up bit-identical to the unconditional stores.
-        if (bits_differ(pv, p_old)) p4[i] = pv;
-        if (bits_differ(sv, s_old)) s4[i] = sv;
-        // (clear only what is not clear already: rows no gradient reached -- most token rows of a token-pooled step, the
-        //  entities outside a sampled candidate list -- cost one store stream less: a sixth of this HBM-bound sweep)
-        if (zero_grad && ((__float_as_uint(gv.x) | __float_as_uint(gv.y) | __float_as_uint(gv.z) | __float_as_uint(gv.w)) != 0u))
-            g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = (n4 << 2) + threadIdx.x;
-        const float gj = fmaf(wd, p[i], g[i]);
-        sum[i] = fmaf(gj, gj, sum[i]);
-        p[i] = p[i] - lr * (gj / (sqrtf(sum[i]) + eps));
-        if (zero_grad) g[i] = 0.f;
-    }
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float m = -INFINITY;
+    for (int r = 0; r < world; ++r) m = fmaxf(m, parts[(size_t)r * B + b]);
+    float sacc = 0.f;
+    for (int r = 0; r < world; ++r) sacc += expf(parts[(size_t)r * B + b] - m);
+    out[b] = m > -INFINITY ? m + logf(sacc) : -INFINITY;
 }
 
 __global__ __launch_bounds__(128) void encode_rows_kernel(const float *__restrict__ table, int64_t table_rows, int d,
@@ -591,448 +572,6 @@ __global__ __launch_bounds__(128) void encode_rows_kernel(const float *__restric
     const float *src = table + row * d;
     float *dst = out + (size_t)i * ld_out;
     for (int k = threadIdx.x; k < d; k += blockDim.x) dst[k] = src[k] * drop_mult1(drop, (uint32_t)i, k, d);
-}
-
-__global__ __launch_bounds__(256) void scale_kernel(float *__restrict__ x, int64_t n, const float *__restrict__ alpha)
-{
-    const float a = *alpha;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) x[i] *= a;
-}
-
-// The drop-in path's gradients come out of the fused step already multiplied by `applied` = the 1 / normalizer the reference
-// Trainer is known to divide by (trainer.py:221); autograd later hands over the factor it really used (*alpha).  Both
-// tensors in one launch, and nothing but the scalar is read when the two agree (the normal case): x *= alpha / applied.
-__global__ __launch_bounds__(256) void rescale2_kernel(float *__restrict__ x0, int64_t n0, float *__restrict__ x1, int64_t n1,
-                                                       const float *__restrict__ alpha, float applied)
-{
-    const float r = *alpha / applied;
-    if (r == 1.0f) return;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n0; i += stride) x0[i] *= r;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n1; i += stride) x1[i] *= r;
-}
-
-struct AdagradSeg { float *p, *g, *s; int64_t n; };
-
-__device__ __forceinline__ void adagrad_sweep(const AdagradSeg sg, float lr, float wd, float eps, int zero_grad,
-                                              int64_t first, int64_t stride)
-{
-    const int64_t n4 = sg.n >> 2;
-    float4 *p4 = reinterpret_cast<float4 *>(sg.p), *g4 = reinterpret_cast<float4 *>(sg.g), *s4 = reinterpret_cast<float4 *>(sg.s);
-    for (int64_t i = first; i < n4; i += stride) {
-        float4 pv = p4[i], gv = g4[i], sv = s4[i];
-        const float4 p_old = pv, s_old = sv;
-        float *pp = &pv.x, *gg = &gv.x, *ss = &sv.x;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float gj = fmaf(wd, pp[j], gg[j]);
-            ss[j] = fmaf(gj, gj, ss[j]);
-            pp[j] = pp[j] - lr * (gj / (sqrtf(ss[j]) + eps));
-        }
-        // store only what changed.  A row no gradient reached still moves by the weight-decay term (the reference applies
-        // wd = 1e-10 to ALL rows, utils/optim.py:139-160) -- but once its accumulator has seen a real gradient, that term is
-        // below half an ulp of both the accumulator and the parameter and the arithmetic above returns the old bits: such
-        // rows (most token rows of a token-pooled step, the entities outside a sampled candidate list) then cost three
-        // read streams instead of three reads + two writes.  Memory ends up bit-identical to the unconditional stores.
-        if (bits_differ(pv, p_old)) p4[i] = pv;
-        if (bits_differ(sv, s_old)) s4[i] = sv;
-        // (clear only what is not clear already: rows no gradient reached -- most token rows of a token-pooled step, the
-        //  entities outside a sampled candidate list -- cost one store stream less: a sixth of this HBM-bound sweep)
-        if (zero_grad && ((__float_as_uint(gv.x) | __float_as_uint(gv.y) | __float_as_uint(gv.z) | __float_as_uint(gv.w)) != 0u))
-            g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if (first < (sg.n & 3)) {
-        const int64_t i = (n4 << 2) + first;
-        const float gj = fmaf(wd, sg.p[i], sg.g[i]);
-        sg.s[i] = fmaf(gj, gj, sg.s[i]);
-        sg.p[i] = sg.p[i] - lr * (gj / (sqrtf(sg.s[i]) + eps));
-        if (zero_grad) sg.g[i] = 0.f;
-    }
-}
-
-__global__ __launch_bounds__(256) void adagrad2_kernel(const AdagradSeg a, const AdagradSeg b, float lr, float wd,
-                                                       float eps, int zero_grad)
-{
-    const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-    adagrad_sweep(a, lr, wd, eps, zero_grad == 1, first, stride);      // zero_grad: 0 none, 1 both, 2 second tensor only
-    adagrad_sweep(b, lr, wd, eps, zero_grad != 0, first, stride);
-}
-
-// Up to four tensors in one launch (token tables + batch-norm parameters of a token-pooled step: one launch instead of two),
-// each optionally with a touched-row byte map: a row whose byte differs from the segment's stamp holds an all-zero gradient
-// by contract (the pooling backward stamps every row it writes, okge_pool.hip pass 4), so its gradient is neither read nor
-// cleared -- such rows still run through the arithmetic (the reference's wd * p reaches ALL rows) on p and sum alone.
-// The stamp is never erased: the caller moves to another stamp after every update (a stale byte that meets its stamp again
-// 255 updates later only costs the read of a gradient row that is zero).
-struct AdagradSegsDev { AdagradSegM s[ADAGRAD_MAX_SEGS]; int n; };
-
-// (U iterations of the grid-stride loop side by side: the map byte decides whether the gradient is loaded at all, so one
-//  iteration is TWO dependent round trips -- run one at a time the sweep was latency-bound, slower than the map-less one)
-template <int U, bool MAP>
-__device__ __forceinline__ void adagrad_sweep_map(const AdagradSegM sg, float lr, float wd, float eps, int64_t first, int64_t stride)
-{
-    const int64_t n4 = sg.n >> 2;
-    float4 *p4 = reinterpret_cast<float4 *>(sg.p), *g4 = reinterpret_cast<float4 *>(sg.g), *s4 = reinterpret_cast<float4 *>(sg.s);
-    const uint32_t row4 = MAP ? (uint32_t)(sg.row_len >> 2) : 1u;
-    const int shift = (row4 & (row4 - 1)) == 0 ? 31 - __clz(row4) : -1;
-    const uint8_t stamp = (uint8_t)sg.stamp;
-    for (int64_t i0 = first; i0 < n4; i0 += U * stride) {
-        bool ok[U], live[U];
-        float4 pv[U], sv[U], gv[U];
-        uint8_t mb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {                            // the U map bytes first, no branch between the loads
-            const int64_t i = min(i0 + u * stride, n4 - 1);
-            ok[u] = i0 + u * stride < n4;
-            mb[u] = stamp;
-            if (MAP) mb[u] = sg.touched[shift >= 0 ? (uint32_t)i >> shift : (uint32_t)i / row4];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) live[u] = ok[u] && mb[u] == stamp;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t i = i0 + u * stride;
-            pv[u] = sv[u] = gv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ok[u]) { pv[u] = p4[i]; sv[u] = s4[i]; }
-            if (live[u]) gv[u] = g4[i];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (!ok[u]) continue;
-            const int64_t i = i0 + u * stride;
-            const float4 p_old = pv[u], s_old = sv[u];
-            float *pp = &pv[u].x, *gg = &gv[u].x, *ss = &sv[u].x;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float gj = fmaf(wd, pp[j], gg[j]);
-                ss[j] = fmaf(gj, gj, ss[j]);
-                pp[j] = pp[j] - lr * (gj / (sqrtf(ss[j]) + eps));
-            }
-            if (bits_differ(pv[u], p_old)) p4[i] = pv[u];            // (store only what changed: see adagrad_sweep)
-            if (bits_differ(sv[u], s_old)) s4[i] = sv[u];
-            if (live[u] && sg.zero_grad && ((__float_as_uint(gv[u].x) | __float_as_uint(gv[u].y) | __float_as_uint(gv[u].z) | __float_as_uint(gv[u].w)) != 0u))
-                g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    if (first < (sg.n & 3)) {                                    // (tail: only tensors without a map have one)
-        const int64_t i = (n4 << 2) + first;
-        const float gj = fmaf(wd, sg.p[i], sg.g[i]);
-        sg.s[i] = fmaf(gj, gj, sg.s[i]);
-        sg.p[i] = sg.p[i] - lr * (gj / (sqrtf(sg.s[i]) + eps));
-        if (sg.zero_grad) sg.g[i] = 0.f;
-    }
-}
-
-__global__ __launch_bounds__(256) void adagrad_multi_kernel(const AdagradSegsDev segs, float lr, float wd, float eps)
-{
-    const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-#pragma unroll
-    for (int k = 0; k < ADAGRAD_MAX_SEGS; ++k)
-        if (k < segs.n) {
-            if (segs.s[k].touched) adagrad_sweep_map<4, true>(segs.s[k], lr, wd, eps, first, stride);
-            else adagrad_sweep_map<1, false>(segs.s[k], lr, wd, eps, first, stride);
-        }
-}
-
-// ---- okge_adagrad_lazy: the weight-decay-only updates of rows no batch names, deferred ------------------------------------
-// The reference's Adagrad reaches every row of a table every step (weight_decay 1e-10 makes every gradient row non-zero,
-// utils/optim.py:139-160): at BASELINE configs[4] 85 % of the token rows are read, moved by their own decay term and written
-// back per step -- 1 GB of HBM traffic, 175 us of a 0.78 ms step.  Such a row's update depends on (p, sum) of that row alone,
-// so it can be applied LATER, all pending steps at once in registers, as long as it has happened before anything reads the row:
-//   row_steps[r]   number of optimizer steps row r has seen; counters[0] = T, the steps taken
-//   STEP           rows the backward stamped: their T - row_steps[r] pending decay steps, then this step with the gradient;
-//                  rows with r % window == T % window: their T + 1 - row_steps[r] pending decay steps; T += 1 (last workgroup)
-//   catch-up       (okge_pool.hip, before the pooling forward) brings the rows the batch's tokens name to T
-//   FLUSH          every row to T (before anything else reads the tables: evaluation, checkpoints, the host)
-// Per step the sweep touches the stamped rows and 1 / window of the others: the traffic falls by ~window, the arithmetic
-// (correctly rounded sqrt and division per element and pending step) stays and becomes the bound.  Same operations in the
-// same order per element as the eager sweep: the tables are bit-identical after a FLUSH (tests/test_token_pooled.py).
-struct LazySegsDev { LazySeg s[ADAGRAD_MAX_SEGS]; int n; int64_t batch0[ADAGRAD_MAX_SEGS + 1]; };
-
-constexpr int LAZY_BATCH = 16;         // rows per wave and turn: many short turns hide the rows' load latency
-
-__device__ __forceinline__ void adagrad_lazy_body(const LazySegsDev &segs, int32_t *counters, int window, int mode, float lr, float wd,
-                                                  float eps, int lazy_batch)
-{
-    const int T = counters[0], target = mode == LAZY_STEP ? T + 1 : T;
-    const int lane = threadIdx.x & 63;
-    const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * 4;
-    const int phase = T % window;
-    // tensors with a row_steps array: batches of LAZY_BATCH rows, one per wave at a time; lane = row while the batch's bytes
-    // and counters are read, lane = column quad while a row is updated
-    for (int64_t b = gw; b < segs.batch0[segs.n]; b += nw) {
-        int k = 0;
-        while (b >= segs.batch0[k + 1]) ++k;
-        const LazySeg &sg = segs.s[k];
-        const int64_t r = (b - segs.batch0[k]) * lazy_batch + (lane & (lazy_batch - 1));
-        const bool in = lane < lazy_batch && r < sg.rows;
-        const int up = in ? sg.steps[r] : target;
-        const bool stamped = mode == LAZY_STEP && in && sg.touched && sg.touched[r] == (uint8_t)sg.stamp;
-        const bool due = in && (mode == LAZY_FLUSH || (int)((uint32_t)r % (uint32_t)window) == phase);      // (rows < 2^31: okge_api.hip)
-        const bool need = stamped || (due && up < target);
-        lazy_rows(__ballot(need), r, max(0, (stamped ? T : target) - up), stamped, sg.p, sg.s, sg.g, sg.row_len, lane, lr, wd, eps);
-        if (need) {
-            sg.steps[r] = target;
-            if (stamped) sg.touched[r] = 0;              // the map is clean again: a stamp never has to move on
-        }
-    }
-    // plain dense tensors (batch-norm parameters): every element every step
-    if (mode == LAZY_STEP) {
-        const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-        for (int k = 0; k < segs.n; ++k) {
-            const LazySeg &sg = segs.s[k];
-            if (sg.steps) continue;
-            const int64_t n = sg.rows * sg.row_len;
-            for (int64_t i = first; i < n; i += stride) {
-                const float gj = fmaf(wd, sg.p[i], sg.g[i]);
-                sg.s[i] = fmaf(gj, gj, sg.s[i]);
-                sg.p[i] = sg.p[i] - lr * (gj / (sqrtf(sg.s[i]) + eps));
-                sg.g[i] = 0.f;
-            }
-        }
-        // every workgroup has read T by the time the last one arrives here
-        __shared__ int last;
-        __syncthreads();
-        if (threadIdx.x == 0) last = atomicAdd(&counters[1], 1) == (int)gridDim.x - 1;
-        __syncthreads();
-        if (last && threadIdx.x == 0) { counters[1] = 0; counters[0] = T + 1; }
-    }
-}
-
-// 93 registers = 5 waves per SIMD.  Budgets of 80 / 64 registers (6 / 8 waves) spill inside the replay loops: 85 / 130 us against
-// 70 us at configs[4] (profiles/round4_ablation.md section 6)
-__global__ __launch_bounds__(256, 5) void adagrad_lazy_kernel(const LazySegsDev segs, int32_t *counters, int window, int mode, float lr,
-                                                           float wd, float eps, int lazy_batch)
-{
-    adagrad_lazy_body(segs, counters, window, mode, lr, wd, eps, lazy_batch);
-}
-
-constexpr int RANK_GROUPS = 8;
-
-// Count, for NG answer groups of one row at once, how many (filter-corrected) scores are greater than / equal to
-// each group's true score.  NG is the compile-time number of live groups (1, 2, 4 or 8): the sweep is VALU-bound
-// on the compares, and most rows have one or two groups.
-template <int NG>
-__device__ __forceinline__ void rank_sweep(const float *__restrict__ row, int64_t ld_is_vec, int N,
-                                           const int32_t *__restrict__ filt_col, int64_t f_lo, int64_t f_hi, int col0,
-                                           const float *tv, int tid, int (&gt)[RANK_GROUPS], int (&eq)[RANK_GROUPS])
-{
-    float t[NG];
-#pragma unroll
-    for (int j = 0; j < NG; ++j) t[j] = tv[j];
-    int g[NG], e[NG];
-#pragma unroll
-    for (int j = 0; j < NG; ++j) { g[j] = 0; e[j] = 0; }
-    const int n4 = ld_is_vec ? (N >> 2) : 0;
-    const float4 *row4 = reinterpret_cast<const float4 *>(row);
-    // 16-byte loads, four in flight per thread: a row is 58 KB at the FB15k-237 size and the sweep is a chain of memory
-    // round trips, not compares
-    for (int i = tid; i < n4; i += 1024) {
-        float4 xv[4];
-        bool has[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            has[u] = i + 256 * u < n4;
-            xv[u] = has[u] ? row4[i + 256 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (!has[u]) continue;
-            const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-#pragma unroll
-                for (int j = 0; j < NG; ++j) { g[j] += xs[k] > t[j]; e[j] += xs[k] == t[j]; }
-            }
-        }
-    }
-    for (int n = 4 * n4 + tid; n < N; n += 256) {
-        const float x = row[n];
-#pragma unroll
-        for (int j = 0; j < NG; ++j) { g[j] += x > t[j]; e[j] += x == t[j]; }
-    }
-    // filtered positions count as -1e8 instead of their score (dataset.py:441)
-    for (int64_t f = f_lo + tid; f < f_hi; f += 256) {
-        const int col = filt_col[f] - col0;                     // a shard only sees its own candidate columns
-        if (col < 0 || col >= N) continue;
-        const float x = row[col];
-#pragma unroll
-        for (int j = 0; j < NG; ++j) {
-            g[j] += (-1e8f > t[j]) - (x > t[j]);
-            e[j] += (-1e8f == t[j]) - (x == t[j]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < RANK_GROUPS; ++j) { gt[j] = j < NG ? g[j < NG ? j : 0] : 0; eq[j] = j < NG ? e[j < NG ? j : 0] : 0; }
-}
-
-// The same counts with the thread's part of the row already in registers (rows up to RANK_REG_ROW floats): the row
-// loads are issued at kernel entry and overlap the dependent-load chain that finds the true scores
-// (row_ptr -> grp_ptr -> ids -> score), and several group chunks reuse them.
-constexpr int RANK_REG_F4 = 16, RANK_REG_ROW = 256 * 4 * RANK_REG_F4;
-
-template <int NG>
-__device__ __forceinline__ void rank_sweep_regs(const float4 (&rv)[RANK_REG_F4], int n4, float tail_x, bool has_tail, float filt_x,
-                                                bool has_filt, const float *__restrict__ row, int N,
-                                                const int32_t *__restrict__ filt_col, int64_t f_lo, int64_t f_hi, int col0,
-                                                const float *tv, int tid, int (&gt)[RANK_GROUPS], int (&eq)[RANK_GROUPS])
-{
-    float t[NG];
-    int g[NG], e[NG];
-#pragma unroll
-    for (int j = 0; j < NG; ++j) { t[j] = tv[j]; g[j] = 0; e[j] = 0; }
-#pragma unroll
-    for (int u = 0; u < RANK_REG_F4; ++u) {
-        if (tid + 256 * u >= n4) continue;
-        const float xs[4] = {rv[u].x, rv[u].y, rv[u].z, rv[u].w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int j = 0; j < NG; ++j) { g[j] += xs[k] > t[j]; e[j] += xs[k] == t[j]; }
-        }
-    }
-    if (has_tail) {
-#pragma unroll
-        for (int j = 0; j < NG; ++j) { g[j] += tail_x > t[j]; e[j] += tail_x == t[j]; }
-    }
-    // filtered positions count as -1e8 instead of their score (dataset.py:441); the first 256 were fetched at entry
-    if (has_filt) {
-#pragma unroll
-        for (int j = 0; j < NG; ++j) {
-            g[j] += (-1e8f > t[j]) - (filt_x > t[j]);
-            e[j] += (-1e8f == t[j]) - (filt_x == t[j]);
-        }
-    }
-    for (int64_t f = f_lo + 256 + tid; f < f_hi; f += 256) {
-        const int col = filt_col[f] - col0;
-        if (col < 0 || col >= N) continue;
-        const float x = row[col];
-#pragma unroll
-        for (int j = 0; j < NG; ++j) {
-            g[j] += (-1e8f > t[j]) - (x > t[j]);
-            e[j] += (-1e8f == t[j]) - (x == t[j]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < RANK_GROUPS; ++j) { gt[j] = j < NG ? g[j < NG ? j : 0] : 0; eq[j] = j < NG ? e[j < NG ? j : 0] : 0; }
-}
-
-__global__ __launch_bounds__(256) void ranks_kernel(const float *__restrict__ scores, int64_t ld, int N,
-                                                    const int64_t *__restrict__ filt_ptr,
-                                                    const int32_t *__restrict__ filt_col,
-                                                    const int64_t *__restrict__ row_ptr,
-                                                    const int64_t *__restrict__ grp_ptr, const int32_t *__restrict__ ids,
-                                                    int64_t *__restrict__ ranks, int col0,
-                                                    const float *__restrict__ true_in, float *__restrict__ true_out,
-                                                    int64_t *__restrict__ counts_out)
-{
-    // Whole candidate list (col0 = 0, true_in = true_out = counts_out = null): ranks.
-    // Candidate-sharded evaluation runs it twice around two tiny all-reduces:
-    //   true_out   : the shard's maximum over each group's ids that fall in [col0, col0 + N)   -> all-reduce(max)
-    //   true_in    : global true scores in, counts_out[g] = {#greater, #equal} of this shard   -> all-reduce(sum)
-    // blockIdx.y strides over the row's chunks of 8 answer groups: rows with many answers (they set the kernel's
-    // duration) are spread over gridDim.y workgroups, the others leave at once
-    __shared__ float tv[RANK_GROUPS];
-    __shared__ int cnt[4][2 * RANK_GROUPS];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int64_t g_lo = row_ptr[b] + (int64_t)RANK_GROUPS * blockIdx.y, g_hi = row_ptr[b + 1];
-    if (g_lo >= g_hi) return;
-    const float *row = scores + (size_t)b * ld;
-    const int64_t f_lo = filt_ptr[b], f_hi = filt_ptr[b + 1];
-    const int64_t vec = ((ld & 3) == 0) && ((reinterpret_cast<uintptr_t>(scores) & 15) == 0);
-    const bool in_regs = vec && N <= RANK_REG_ROW && !true_out;
-    const int n4 = N >> 2;
-    float4 rv[RANK_REG_F4];
-    float tail_x = 0.f, filt_x = 0.f;
-    bool has_tail = false, has_filt = false;
-    if (in_regs) {
-        // everything that does not depend on the true scores is requested now: the row, its (< 4) tail elements and
-        // the scores under the first 256 filter entries
-#pragma unroll
-        for (int u = 0; u < RANK_REG_F4; ++u)
-            rv[u] = tid + 256 * u < n4 ? reinterpret_cast<const float4 *>(row)[tid + 256 * u] : make_float4(0.f, 0.f, 0.f, 0.f);
-        has_tail = 4 * n4 + tid < N;
-        if (has_tail) tail_x = row[4 * n4 + tid];
-        if (f_lo + tid < f_hi) {
-            const int col = filt_col[f_lo + tid] - col0;
-            has_filt = col >= 0 && col < N;
-            if (has_filt) filt_x = row[col];
-        }
-    }
-    for (int64_t g0 = g_lo; g0 < g_hi; g0 += (int64_t)RANK_GROUPS * gridDim.y) {
-        const int ng = (int)min((int64_t)RANK_GROUPS, g_hi - g0);
-        if (tid < RANK_GROUPS) {
-            float t = __builtin_nanf("");                       // unused slots never compare true
-            if (tid < ng) {
-                if (true_in) {
-                    t = true_in[g0 + tid];
-                } else {
-                    t = -INFINITY;
-                    for (int64_t j = grp_ptr[g0 + tid]; j < grp_ptr[g0 + tid + 1]; ++j) {
-                        const int col = ids[j] - col0;
-                        if (col >= 0 && col < N) t = fmaxf(t, row[col]);
-                    }
-                    if (true_out) true_out[g0 + tid] = t;
-                }
-            }
-            tv[tid] = t;
-        }
-        if (true_out) continue;                                 // uniform: phase 1 of the sharded evaluation
-        __syncthreads();
-        int gt[RANK_GROUPS], eq[RANK_GROUPS];
-        if (in_regs) {
-            if (ng == 1)      rank_sweep_regs<1>(rv, n4, tail_x, has_tail, filt_x, has_filt, row, N, filt_col, f_lo, f_hi, col0, tv, tid, gt, eq);
-            else if (ng == 2) rank_sweep_regs<2>(rv, n4, tail_x, has_tail, filt_x, has_filt, row, N, filt_col, f_lo, f_hi, col0, tv, tid, gt, eq);
-            else if (ng <= 4) rank_sweep_regs<4>(rv, n4, tail_x, has_tail, filt_x, has_filt, row, N, filt_col, f_lo, f_hi, col0, tv, tid, gt, eq);
-            else              rank_sweep_regs<8>(rv, n4, tail_x, has_tail, filt_x, has_filt, row, N, filt_col, f_lo, f_hi, col0, tv, tid, gt, eq);
-        } else if (ng == 1)   rank_sweep<1>(row, vec, N, filt_col, f_lo, f_hi, col0, tv, tid, gt, eq);
-        else if (ng == 2)     rank_sweep<2>(row, vec, N, filt_col, f_lo, f_hi, col0, tv, tid, gt, eq);
-        else if (ng <= 4)     rank_sweep<4>(row, vec, N, filt_col, f_lo, f_hi, col0, tv, tid, gt, eq);
-        else                  rank_sweep<8>(row, vec, N, filt_col, f_lo, f_hi, col0, tv, tid, gt, eq);
-#pragma unroll
-        for (int j = 0; j < RANK_GROUPS; ++j) {
-            const int a = wave_sum(gt[j]), e = wave_sum(eq[j]);
-            if ((tid & 63) == 0) { cnt[tid >> 6][2 * j] = a; cnt[tid >> 6][2 * j + 1] = e; }
-        }
-        __syncthreads();
-        if (tid < ng) {
-            const int64_t a = (int64_t)cnt[0][2 * tid] + cnt[1][2 * tid] + cnt[2][2 * tid] + cnt[3][2 * tid];
-            const int64_t e = (int64_t)cnt[0][2 * tid + 1] + cnt[1][2 * tid + 1] + cnt[2][2 * tid + 1] + cnt[3][2 * tid + 1];
-            if (counts_out) {
-                counts_out[2 * (g0 + tid)] = a;
-                counts_out[2 * (g0 + tid) + 1] = e;
-            } else {
-                ranks[g0 + tid] = a + e / 2;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// acc[0..6] += {#groups, sum 1/(rank+1), sum rank, #rank<1, #rank<3, #rank<10, #rank<50}: the meters of compute_metrics
-// (dataset.py:447-452) kept on the device, so that evaluation batches need no host round trip
-__global__ __launch_bounds__(256) void rank_metrics_kernel(const int64_t *__restrict__ ranks, int64_t n, double *__restrict__ acc)
-{
-    __shared__ double red[4][7];
-    double v[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int64_t i = threadIdx.x; i < n; i += 256) {
-        const int64_t r = ranks[i];
-        v[0] += 1.0;
-        v[1] += (double)(1.0f / (float)(r + 1));       // fp32 reciprocal like the reference's (1/(rank+1).float())
-        v[2] += (double)r;
-        v[3] += r < 1; v[4] += r < 3; v[5] += r < 10; v[6] += r < 50;
-    }
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        const double t = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = t;
-    }
-    __syncthreads();
-    // atomic: launches of independent stream chains may share one `acc` (PipelinedEvaluator hands every chain its own
-    // and sums them after the join, which also keeps the double sums order-deterministic)
-    if (threadIdx.x < 7)
-        atomicAdd(acc + threadIdx.x, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
 // Per-triple score of already encoded rows, Hadamard form (model.py:231-238, :276): one wave per triple.
@@ -1056,59 +595,6 @@ __global__ __launch_bounds__(256) void score_triples_kernel(const float *__restr
     }
     acc = wave_sum(acc);
     if (lane == 0) out[i] = acc;
-}
-
-// ---- gradient clipping (trainer.py:236-240: torch.nn.utils.clip_grad_norm_) and the sharded KL loss' row log-sum-exp --
-__global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float *__restrict__ g0, int64_t n0, const float *__restrict__ g1,
-                                                             int64_t n1, double *__restrict__ partial)
-{
-    __shared__ double red[4];
-    double acc = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t i = first; i < n0; i += stride) acc += (double)g0[i] * (double)g0[i];
-    for (int64_t i = first; i < n1; i += stride) acc += (double)g1[i] * (double)g1[i];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ __launch_bounds__(256) void clip_coef_kernel(const double *__restrict__ partial, int n, float max_norm,
-                                                        float *__restrict__ coef, double *__restrict__ norm_out)
-{
-    __shared__ double red[4];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partial[i];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float total = (float)sqrt(red[0] + red[1] + red[2] + red[3]);        // torch keeps the norm in fp32
-        const float c = max_norm / (total + 1e-6f);
-        coef[0] = c < 1.f ? c : 1.f;
-        if (norm_out) norm_out[0] = (double)total;
-    }
-}
-
-__global__ __launch_bounds__(256) void merge_lse_kernel(const float *__restrict__ parts, int world, int B, float *__restrict__ out)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    float m = -INFINITY;
-    for (int r = 0; r < world; ++r) m = fmaxf(m, parts[(size_t)r * B + b]);
-    float sacc = 0.f;
-    for (int r = 0; r < world; ++r) sacc += expf(parts[(size_t)r * B + b] - m);
-    out[b] = m > -INFINITY ? m + logf(sacc) : -INFINITY;
-}
-
-// ---- fused evaluation (okge_evaluate_fused): the side work (okge_eval_device.h) ------------------------------------
-// The two small kernels of the fused evaluation in ONE launch: workgroups [0, n_points) take the rows of `pts`, the rest
-// the groups of `rk`.  In a run of batches the points of batch i+1 ride with the ranks of batch i (independent work of
-// two batches; either part may be empty).
-__global__ __launch_bounds__(256) void eval_side_kernel(const EvalPointsArgs pts, const EvalRanksArgs rk, int n_points)
-{
-    if ((int)blockIdx.x < n_points) eval_points_block(pts, blockIdx.x);
-    else eval_ranks_block(rk, (int)blockIdx.x - n_points);
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------
@@ -1254,13 +740,10 @@ hipError_t launch_kl_row_lse(const float *stats, int tiles, int B, int Bpad, flo
     return hipGetLastError();
 }
 
-hipError_t launch_adagrad(float *p, float *g, float *sum, int64_t n, float lr, float wd, float eps, int zero_grad,
-                          hipStream_t st)
+hipError_t launch_merge_lse(const float *parts, int world, int B, float *out, hipStream_t st)
 {
-    if (n <= 0) return hipSuccess;
-    const int64_t n4 = (n + 3) / 4;
-    const int blocks = (int)min((int64_t)16384, (n4 + 255) / 256);
-    hipLaunchKernelGGL(adagrad_kernel, dim3(blocks), dim3(256), 0, st, p, g, sum, n, lr, wd, eps, zero_grad);
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(merge_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, parts, world, B, out);
     return hipGetLastError();
 }
 
@@ -1269,124 +752,6 @@ hipError_t launch_encode_rows(const float *table, int64_t table_rows, int d, con
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(encode_rows_kernel, dim3(n), dim3(128), 0, st, table, table_rows, d, ids, first_id, drop, out, ld_out, id_err);
-    return hipGetLastError();
-}
-
-hipError_t launch_scale(float *x, int64_t n, const float *alpha_dev, hipStream_t st)
-{
-    if (n <= 0) return hipSuccess;
-    const int blocks = (int)std::min((int64_t)4096, (n + 255) / 256);
-    hipLaunchKernelGGL(scale_kernel, dim3(blocks), dim3(256), 0, st, x, n, alpha_dev);
-    return hipGetLastError();
-}
-
-hipError_t launch_rescale2(float *x0, int64_t n0, float *x1, int64_t n1, const float *alpha_dev, float applied, hipStream_t st)
-{
-    const int64_t n = std::max(n0, n1);
-    if (n <= 0) return hipSuccess;
-    const int blocks = (int)std::min((int64_t)2048, (n + 255) / 256);
-    hipLaunchKernelGGL(rescale2_kernel, dim3(blocks), dim3(256), 0, st, x0, n0, x1, n1, alpha_dev, applied);
-    return hipGetLastError();
-}
-
-hipError_t launch_adagrad2(float *p0, float *g0, float *s0, int64_t n0, float *p1, float *g1, float *s1, int64_t n1,
-                           float lr, float wd, float eps, int zero_grad, hipStream_t st)
-{
-    const int64_t n4 = (std::max(n0, n1) + 3) / 4;
-    if (n4 <= 0) return hipSuccess;
-    const int blocks = (int)std::min((int64_t)16384, (n4 + 255) / 256);
-    const AdagradSeg a{p0, g0, s0, n0}, b{p1, g1, s1, n1};
-    hipLaunchKernelGGL(adagrad2_kernel, dim3(blocks), dim3(256), 0, st, a, b, lr, wd, eps, zero_grad);
-    return hipGetLastError();
-}
-
-hipError_t launch_adagrad_multi(const AdagradSegM *segs, int n_segs, float lr, float wd, float eps, hipStream_t st)
-{
-    if (n_segs <= 0) return hipSuccess;
-    if (n_segs > ADAGRAD_MAX_SEGS) return hipErrorInvalidValue;
-    AdagradSegsDev a;
-    std::memset(&a, 0, sizeof(a));
-    a.n = n_segs;
-    int64_t n4 = 0;
-    for (int k = 0; k < n_segs; ++k) {
-        a.s[k] = segs[k];
-        n4 = std::max(n4, (segs[k].n + 3) / 4);
-    }
-    if (n4 <= 0) return hipSuccess;
-    const int blocks = (int)std::min((int64_t)16384, (n4 + 255) / 256);
-    hipLaunchKernelGGL(adagrad_multi_kernel, dim3(blocks), dim3(256), 0, st, a, lr, wd, eps);
-    return hipGetLastError();
-}
-
-hipError_t launch_adagrad_lazy(const LazySeg *segs, int n_segs, int32_t *counters, int window, int mode, float lr, float wd,
-                               float eps, hipStream_t st)
-{
-    if (n_segs <= 0) return hipSuccess;
-    if (n_segs > ADAGRAD_MAX_SEGS || window < 1 || !counters) return hipErrorInvalidValue;
-    LazySegsDev a;
-    std::memset(&a, 0, sizeof(a));
-    a.n = n_segs;
-    static const int lazy_batch_env = getenv("OKGE_LAZY_BATCH") ? atoi(getenv("OKGE_LAZY_BATCH")) : LAZY_BATCH;
-    const int lazy_batch = (lazy_batch_env == 8 || lazy_batch_env == 32 || lazy_batch_env == 64) ? lazy_batch_env : LAZY_BATCH;
-    for (int k = 0; k < n_segs; ++k) {
-        a.s[k] = segs[k];
-        a.batch0[k + 1] = a.batch0[k] + (segs[k].steps ? (segs[k].rows + lazy_batch - 1) / lazy_batch : 0);
-    }
-    // (every wave resident: 5 per SIMD; a wave takes batch after batch)
-    const int64_t wgs = std::max<int64_t>(1, std::min<int64_t>((a.batch0[n_segs] + 3) / 4, 256 * 5));
-    hipLaunchKernelGGL(adagrad_lazy_kernel, dim3((unsigned)wgs), dim3(256), 0, st, a, counters, window, mode, lr, wd, eps, lazy_batch);
-    return hipGetLastError();
-}
-
-hipError_t launch_rank_metrics(const int64_t *ranks, int64_t n, double *acc, hipStream_t st)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rank_metrics_kernel, dim3(1), dim3(256), 0, st, ranks, n, acc);
-    return hipGetLastError();
-}
-
-hipError_t launch_ranks(const float *scores, int64_t ld, int B, int N, const int64_t *filt_ptr,
-                        const int32_t *filt_col, const int64_t *row_ptr, const int64_t *grp_ptr, const int32_t *ids,
-                        int64_t *ranks, int col0, const float *true_in, float *true_out, int64_t *counts_out,
-                        hipStream_t st)
-{
-    if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ranks_kernel, dim3(B, 4), dim3(256), 0, st, scores, ld, N, filt_ptr, filt_col, row_ptr, grp_ptr,
-                       ids, ranks, col0, true_in, true_out, counts_out);
-    return hipGetLastError();
-}
-
-}  // namespace okge
-
-namespace okge {
-
-hipError_t launch_eval_side(const EvalPointsArgs *pts, const EvalRanksArgs *rk, hipStream_t st)
-{
-    const int n_points = pts ? pts->Bpad : 0;
-    const int n_ranks = rk && rk->n_groups > 0 ? (int)((rk->n_groups + 3) / 4) : 0;
-    if (n_points + n_ranks <= 0) return hipSuccess;
-    static const EvalPointsArgs no_pts = {};
-    static const EvalRanksArgs no_rk = {};
-    hipLaunchKernelGGL(eval_side_kernel, dim3(n_points + n_ranks), dim3(256), 0, st, pts ? *pts : no_pts, rk ? *rk : no_rk, n_points);
-    return hipGetLastError();
-}
-
-}  // namespace okge
-
-namespace okge {
-
-hipError_t launch_clip_coef(const float *g0, int64_t n0, const float *g1, int64_t n1, float max_norm, double *partial,
-                            int n_partial, float *coef_dev, double *norm_dev, hipStream_t st)
-{
-    hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(n_partial), dim3(256), 0, st, g0, n0, g1, n1, partial);
-    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, st, partial, n_partial, max_norm, coef_dev, norm_dev);
-    return hipGetLastError();
-}
-
-hipError_t launch_merge_lse(const float *parts, int world, int B, float *out, hipStream_t st)
-{
-    if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(merge_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, parts, world, B, out);
     return hipGetLastError();
 }
 

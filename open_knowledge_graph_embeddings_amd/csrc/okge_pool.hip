@@ -14,6 +14,7 @@
 
 #include "okge_device.h"
 #include "okge_kernels.h"
+#include "okge_adagrad_device.h"
 
 namespace okge {
 
@@ -356,10 +357,10 @@ __global__ __launch_bounds__(256) void pool_stats_kernel(const PoolBatch pb, int
     }
 }
 
-// Catch-up of the deferred decay-only Adagrad steps (okge_adagrad_lazy, okge_misc.hip): every token row this batch names is
+// Catch-up of the deferred decay-only Adagrad steps (okge_adagrad_lazy, okge_optim.hip): every token row this batch names is
 // brought to the current step BEFORE the pooling forward reads it.  Lane = (row, position) pair; a pair whose token row lags
 // claims it with an integer atomicMax on the row's step counter (the first claim wins: one owner per row however many pairs
-// name it), then the wave replays its claimed rows, lane = column quad (lazy_rows, okge_device.h).  Rows named every step (the
+// name it), then the wave replays its claimed rows, lane = column quad (lazy_rows, okge_adagrad_device.h).  Rows named every step (the
 // frequent tokens) never lag.  Token 0 -- the padding id of every short sequence (model.py:579-586): half the pairs at
 // configs[4], and a row the backward never stamps -- is claimed by ONE lane per call instead (tens of thousands of atomics on
 // one address took 0.4 ms).

@@ -6,7 +6,7 @@
 //                                                       position, sequentially in fp32, then the Adagrad update of that one table row
 //   okge_rows_catch_up                                  rows_catch_up_kernel: the rows a batch names take the decay-only steps they owe
 //   okge_adagrad_rows_decay                             rows_update_decay_kernel: the same walk with the weight-decay term, per-row step
-//                                                       counters kept (deferred weight decay; the rotating sweep is okge_misc.hip's)
+//                                                       counters kept (deferred weight decay; the rotating sweep is okge_optim.hip's)
 // Nothing here is proportional to the table: the sort is O(n log n) on 8-byte keys, the update touches the n gradient rows and
 // the distinct table rows they name.  No float atomics, no host synchronisation; the launch sequence depends on the n alone.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "okge_kernels.h"
+#include "okge_adagrad_device.h"
 
 namespace okge {
 
@@ -118,20 +119,13 @@ __global__ __launch_bounds__(256) void rows_merge_kernel(const RowsSegs segs, in
     }
 }
 
-// the arithmetic of adagrad_kernel (okge_misc.hip) at weight_decay = 0, element for element: no decay term at all
-__device__ __forceinline__ void adagrad1_rows(float &p, float g, float &s, float lr, float eps)
-{
-    s = fmaf(g, g, s);
-    p = p - lr * (g / (sqrtf(s) + eps));
-}
-
 // V floats per access (4: 16-byte loads and stores; 1: row lengths / leading dimensions / bases that do not allow them).
 // `lanes` lanes share the head of one run of equal ids: each walks the run for its columns, adding the gradient rows in
 // ascending position, and updates its columns of the table row.  Runs are short in training batches (a candidate list names
 // an entity once, a batch repeats a prefix entity a few times), so a lane's chain is a handful of dependent loads; several
 // runs are in flight per wave (64 / lanes) and the waves of a CU hide the rest.
 // DECAY (V == 4 only; okge_adagrad_rows_decay): the row first takes the `lag` decay-only steps it still owes, then the update
-// carries the weight-decay term -- adagrad4, the dense kernel's expression.
+// carries the weight-decay term -- adagrad4, the dense sweep's expression.  Without DECAY: adagrad1_rows, no decay term at all.
 template <int V, bool DECAY = false>
 __device__ __forceinline__ void rows_update_run(const RowsSeg &sg, const uint64_t *__restrict__ keys, int i, uint32_t id, uint32_t pos,
                                                 int lane, int lanes, float lr, float eps, float wd = 0.f, int lag = 0)

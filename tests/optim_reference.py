@@ -1,5 +1,6 @@
-"""A plain numpy restatement of the dense optimizer, clipping, scaling and metric kernels of csrc/okge_misc.hip (adagrad_kernel,
-adagrad2_kernel, adagrad_multi_kernel, sqnorm_partial_kernel / clip_coef_kernel, score_triples_kernel, rank_metrics_kernel) at
+"""A plain numpy restatement of the dense optimizer and clipping kernels of csrc/okge_optim.hip (adagrad_kernel, adagrad2_kernel,
+adagrad_multi_kernel, sqnorm_partial_kernel / clip_coef_kernel), of score_triples_kernel (csrc/okge_misc.hip) and of
+rank_metrics_kernel (csrc/okge_rank.hip) at
 float64, with the hard caps an fp32 evaluation of the same chain has to stay inside.  Not a conftest: the tests import it.
 
   adagrad64      gj = wd p + g;  s' = s + gj^2;  delta = lr gj / (sqrt(s') + eps);  p' = p - delta      (lr, wd, eps as fp32)

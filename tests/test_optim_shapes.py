@@ -1,9 +1,10 @@
-"""The dense optimizer, clipping, scaling and metric kernels of csrc/okge_misc.hip through their C-ABI entry points, at the
-shapes where their branches change, against the float64 restatement of tests/optim_reference.py.
+"""The dense optimizer, clipping and scaling kernels of csrc/okge_optim.hip, the metric kernel of csrc/okge_rank.hip and two
+small kernels of csrc/okge_misc.hip through their C-ABI entry points, at the shapes where their branches change, against the
+float64 restatement of tests/optim_reference.py.
 
 Every optimizer bit-equality test of the suite (okge_adagrad_rows, okge_adagrad_rows_decay, okge_adagrad_lazy, the touched-row
-map) ends at the eager sweeps adagrad_kernel, adagrad2_kernel / adagrad_sweep and adagrad_multi_kernel / adagrad_sweep_map.  Here
-those are held, element by element, to adagrad64 under adagrad_caps (|p - p'| <= 2u|p'| + 8u|delta|, |s - s'| <= 4u s'): below and
+map) ends at the eager entry points adagrad_kernel, adagrad2_kernel and adagrad_multi_kernel, all three over adagrad_sweep<U, MAP>.
+Here those are held, element by element, to adagrad64 under adagrad_caps (|p - p'| <= 2u|p'| + 8u|delta|, |s - s'| <= 4u s'): below and
 above the launchers' grid cap of 16384 x 256 threads (16 777 216 floats per pass of the grid-stride loop), with the n & 3 tail
 next to other memory, with unequal tensors in both orders, every zero_grad mode, and the touched-row map at row lengths that take
 the shift and the division path, 46 float4 above the cap where the unrolled lanes u = 1..3 and the clamp run.  test_optim_reference.py
@@ -204,6 +205,36 @@ def test_multi_sizes_and_per_tensor_zero_grad(hp, ns, acc, wd):
     drive(hp, "multi-%s-%s-wd%g" % ("-".join(map(str, ns)), acc, wd), "multi", segs, wd, [(0, 1, 0, 1), (1, 0, 1, 1)])
     one = [make_seg(ns[1], 24, acc == "warm")]
     drive(hp, "multi-one-n%d-%s-wd%g" % (ns[1], acc, wd), "multi", one, wd, [(0,), (1,)])
+
+
+@pytest.mark.parametrize("acc,wd", CONFIGS, ids=["cold-wd1e-10", "cold-wd1e-3", "warm-wd1e-10", "warm-wd1e-3"])
+@pytest.mark.parametrize("n", [1, 3, 4, 7, 1027, 262_147])
+def test_entry_points_agree_bit_for_bit(hp, n, acc, wd):
+    """okge_adagrad_step, okge_adagrad_step2 (the tensor in either slot, a one-element dummy in the other) and okge_adagrad_multi
+    without a map, on copies of the same p, g and state_sum, under every zero_grad setting: the same bits in p and in state_sum
+    from all of them; the gradient +0 wherever the setting clears this tensor, its own bits wherever it does not"""
+    src = R.sweep_inputs(n, 170, acc == "warm")
+    dummy_src = R.sweep_inputs(1, 171, acc == "warm")
+    variants = [("step", None, (z,)) for z in (0, 1)] + [("multi", None, (z,)) for z in (0, 1)] + \
+               [("step2", slot, zero) for slot in (0, 1) for zero in ((0, 0), (1, 1), (0, 1))]
+    want = None
+    for entry, slot, zero in variants:
+        sg = Seg(*src)
+        segs = [sg] if slot is None else ([sg, Seg(*dummy_src)] if slot == 0 else [Seg(*dummy_src), sg])
+        g0 = sg.g.v.clone()
+        assert launch(hp, entry, segs, wd, zero) == 0, (entry, slot, zero, hp.lib.okge_last_error())
+        torch.cuda.synchronize()
+        where = (n, acc, wd, entry, slot, zero)
+        if want is None:
+            want = (sg.p.v.clone(), sg.s.v.clone())
+            assert not same_bits(want[0], torch.from_numpy(np.array(src[0], np.float32)).cuda()), where + ("the step moved nothing",)
+        assert same_bits(sg.p.v, want[0]), where + ("p differs from okge_adagrad_step's",)
+        assert same_bits(sg.s.v, want[1]), where + ("state_sum differs from okge_adagrad_step's",)
+        if zero[slot or 0]:
+            assert not bool(bits(sg.g.v).any()), where + ("gradient not cleared to +0",)
+        else:
+            assert same_bits(sg.g.v, g0), where + ("gradient touched without zero_grad",)
+        assert all(x.intact() for x in segs), where + ("guard words overwritten",)
 
 
 @pytest.mark.parametrize("entry,acc,wd", [("step", "cold", 1e-3), ("step2", "warm", 1e-10), ("multi", "cold", 1e-10)])

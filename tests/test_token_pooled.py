@@ -454,7 +454,7 @@ def test_module_readers_flush_the_training_driver(okge_lib):
 @pytest.mark.parametrize("window", [1, 5])
 def test_fast_decay_arithmetic_is_the_generic_one(okge_lib, window):
     """the replay of deferred decay steps runs packed, branch-free copies of the compiler's correctly rounded sqrt / division
-    where every operand of a row is an ordinary number (okge_device.h, decay_step4_ordinary) and the generic code elsewhere:
+    where every operand of a row is an ordinary number (okge_adagrad_device.h, decay_step4_ordinary) and the generic code elsewhere:
     against the eager sweep (okge_adagrad_multi: generic code throughout) the tables must be bit-equal -- rows of ordinary
     numbers over twelve orders of magnitude (fast path), rows with zeros, denormal-range accumulators, tiny and huge
     parameters (generic path), several steps deep"""

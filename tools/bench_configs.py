@@ -218,7 +218,7 @@ def main():
             return
         # the same step on the Adagrad state of a run IN PROGRESS: once a row's accumulator has seen a real gradient, the
         # weight-decay-only update of a step that does not touch the row leaves its bits unchanged and the sweep skips the
-        # two stores (okge_misc.hip adagrad_sweep).  Two resident batches touch ~15 % of the token rows; in the line above
+        # two stores (okge_adagrad_device.h adagrad_commit4).  Two resident batches touch ~15 % of the token rows; in the line above
         # the other rows' accumulators are still ~1e-22 and move every step, as in the first steps of a run.
         step.flush()
         for sl in (ent, rel):
