@@ -261,6 +261,40 @@ size_t okge_score_workspace_bytes(int32_t B, int32_t d);
 /* Scratch of okge_row_logsumexp: query block + one range of (max, sum-exp) tile statistics. */
 size_t okge_lse_workspace_bytes(int32_t B, int32_t N, int32_t d);
 
+/* ---- the N3 regulariser of the lookup embedder (`l2_reg`) beside the fused step -------------------------------------------
+ * Replaces the hook LookupBaseRelationEmbedder._encode accumulates in training mode (model.py:444-453, :471-479) and its share
+ * of `((loss + hook) / normalizer).backward()` (trainer.py:217-221).  The reference's rule, not the textbook N3: every
+ * _encode call adds  l2_reg * sum |x|^3  over the rows it returns, x = the row after BOTH dropouts, divided by `dropout`
+ * (the probability, entity and relation rows alike) when that is > 0.  With x = m s e (m: keep flag, s = 1 / (1 - p) of the
+ * okge_dropout that gathers the row, e: the stored element):
+ *   value    coef * (cand_passes * sum over the candidate rows + sum over the n_po + n_sp prefix entity rows and the n_po + n_sp
+ *            relation rows, one term per occurrence) of |x|^3      -> reg_out (device double[1]; the Trainer's `hook`)
+ *   gradient 3 coef x |x| m s / normalizer (zero at x == 0), times cand_passes for a candidate row -> ADDED to dE / dR
+ *   coef     l2_reg / dropout^3 if dropout > 0, else l2_reg (the caller's arithmetic)
+ *   cand_passes  how often the reference encodes the candidate block: 1 with a shared list (trainer.py:75-84), the number of
+ *            directions present with batch_shared_entities None (trainer.py:86-87), 0 to leave the candidates out.  The fused
+ *            step draws ONE candidate mask for both directions, so 2 means twice one term: exact without dropout, equal in
+ *            expectation with it.  A list that repeats an id counts it as often as it is listed; rows in front of
+ *            cand->first_id are never part of it.
+ * Masks are the ones okge_train_forward_backward draws for the same descriptors (Philox keyed by row position, column / 8,
+ * stream, step; or the explicit `keep` masks).  The call ACCUMULATES: issue it after okge_train_forward_backward on the same
+ * stream, with the same tables, batch, candidates, normalizer and flags:
+ *   OKGE_TRAIN_LOSS_ONLY             value only; dE / dR are not touched and may be NULL
+ *   OKGE_TRAIN_UNIQUE_CANDIDATES     candidate rows of an id list are read-modify-written (as a range always is); without it the
+ *                                    list may repeat ids and the rows are added with float atomics
+ *   OKGE_TRAIN_DISTINCT_PREFIX_ROWS  prefix rows are read-modify-written; without it they are added with float atomics
+ *   OKGE_TRAIN_ROW_GRADS             dE (cand->n + n_po + n_sp, d) / dR (n_po + n_sp, d) are the occurrence rows of the step: both
+ *                                    parts add into them by position, no atomics
+ *   (GRADS_ZERO / CLEAR_GRADS are ignored: the step has already stored or cleared what it had to.)
+ * The value is summed in a fixed order (one double per workgroup, then one workgroup): bit-reproducible; so are the gradients
+ * wherever no atomics run.  Slot sizes 1 .. 4096; 16-byte accesses when d % 4 == 0 and the buffers are 16-byte aligned.
+ * cand->table, cand_passes outside 0 .. 2 -> OKGE_ERR_INVALID; d > 4096 and the data-bias scorers -> OKGE_ERR_UNSUPPORTED; all
+ * before any launch.  No host synchronisation, no allocation.  Workspace: okge_n3_workspace_bytes (0 on invalid arguments). */
+size_t okge_n3_workspace_bytes(int32_t B, int32_t N, int32_t d);
+int okge_n3_forward_backward(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, double coef,
+                             int32_t cand_passes, double normalizer, int32_t flags, double *reg_out, float *dE, float *dR,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- embedder --------------------------------------------------------------------------------------
  * Replaces LookupBaseRelationEmbedder._encode for the lookup embedder with batch-norm / projection /
  * normalisation off (model.py:455-480): out[i][:] = dropout(table[ids ? ids[i] : first_id + i][:]).

@@ -14,7 +14,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_i
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libokge_hip.so")
-SOURCES = ["okge_core.hip", "okge_api_train.hip", "okge_api_eval.hip", "okge_api_encoders.hip", "okge_api_optim.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_wide.hip", "okge_misc.hip", "okge_optim.hip", "okge_rank.hip", "okge_topk.hip", "okge_bias.hip", "okge_sparse.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
+SOURCES = ["okge_core.hip", "okge_api_train.hip", "okge_api_eval.hip", "okge_api_encoders.hip", "okge_api_optim.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_wide.hip", "okge_misc.hip", "okge_optim.hip", "okge_rank.hip", "okge_topk.hip", "okge_bias.hip", "okge_sparse.hip", "okge_n3.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
 # every header a source may include: all of csrc/*.h (listed by the directory, so a new header cannot be forgotten) + the ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "okge.h")]
 
@@ -54,6 +54,7 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_topk_workspace_bytes", "okge_topk_prefixes", "okge_topk_queries", "okge_topk_merge",
            "okge_train_row_grads_workspace_bytes", "okge_adagrad_rows", "okge_adagrad_rows_workspace_bytes",
            "okge_rows_catch_up", "okge_adagrad_rows_decay",
+           "okge_n3_workspace_bytes", "okge_n3_forward_backward",
            "okge_timing_reset", "okge_timing_collect"]
 
 
@@ -237,6 +238,11 @@ def lib():
     L.okge_adagrad_rows_decay.restype = c_int32
     L.okge_adagrad_rows_decay.argtypes = [POINTER(RowsDecayTensor), c_int32, c_void_p, c_int32, c_float, c_float, c_float, c_void_p,
                                           c_size_t, c_void_p]
+    L.okge_n3_workspace_bytes.restype = c_size_t
+    L.okge_n3_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.okge_n3_forward_backward.restype = c_int32
+    L.okge_n3_forward_backward.argtypes = [POINTER(Tables), POINTER(PrefixBatch), POINTER(Candidates), c_double, c_int32, c_double,
+                                           c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     L.okge_score_workspace_bytes.restype = c_size_t
     L.okge_score_workspace_bytes.argtypes = [c_int32, c_int32]
     L.okge_lse_workspace_bytes.restype = c_size_t

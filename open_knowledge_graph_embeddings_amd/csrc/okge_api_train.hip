@@ -710,6 +710,57 @@ int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *b
                       workspace_bytes, stream);
 }
 
+// ---- the N3 regulariser beside the step (okge_n3.hip; grid and workspace: plan_n3) --------------------------------
+size_t okge_n3_workspace_bytes(int32_t B, int32_t N, int32_t d)
+{
+    N3Plan p;
+    return plan_n3(B, N, d, p) ? p.total : 0;
+}
+
+int okge_n3_forward_backward(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand, double coef,
+                             int32_t cand_passes, double normalizer, int32_t flags, double *reg_out, float *dE, float *dR,
+                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_common(t, batch, cand, true)) return rc;
+    if (int rc = refuse_bias(t->scorer, "okge_n3_forward_backward", "the reference's l2_reg belongs to the lookup ComplEx / DistMult embedder")) return rc;
+    if (cand->table) return fail(OKGE_ERR_INVALID, "the regulariser needs candidates from the entity table");
+    if (cand_passes < 0 || cand_passes > 2) return fail(OKGE_ERR_INVALID, "cand_passes must be 0, 1 or 2");
+    if (!(coef >= 0) || !(coef <= 3.0e38)) return fail(OKGE_ERR_INVALID, "coef must be a finite non-negative number");
+    if (!(normalizer > 0)) return fail(OKGE_ERR_INVALID, "normalizer must be positive");
+    const bool loss_only = (flags & OKGE_TRAIN_LOSS_ONLY) != 0, row_grads = (flags & OKGE_TRAIN_ROW_GRADS) != 0;
+    if (!reg_out || (!loss_only && (!dE || !dR))) return fail(OKGE_ERR_INVALID, "null output");
+    if (loss_only && row_grads) return fail(OKGE_ERR_INVALID, "OKGE_TRAIN_ROW_GRADS asks for gradients: not with OKGE_TRAIN_LOSS_ONLY");
+    const int B = batch->n_po + batch->n_sp;
+    N3Plan pl;
+    if (!plan_n3(B, cand->n, t->d, pl)) return fail(OKGE_ERR_INVALID, "bad shape");
+    if (!workspace || workspace_bytes < pl.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_n3_workspace_bytes)");
+    hipStream_t st = as_stream(stream);
+    N3Args a;
+    std::memset(&a, 0, sizeof(a));
+    a.E = t->E; a.R = t->R;
+    a.dE = loss_only ? nullptr : dE; a.dR = loss_only ? nullptr : dR;
+    a.partial = static_cast<double *>(workspace);
+    a.cand_ids = cand->ids; a.cand_first = cand->first_id; a.N = cand->n;
+    a.p = to_dev(*batch, t);
+    a.drop_c = to_dev(cand->drop);
+    a.value_cand = coef * cand_passes; a.value_prefix = coef;
+    a.grad_cand = 3.0 * coef * cand_passes / normalizer; a.grad_prefix = 3.0 * coef / normalizer;
+    a.n_ent = t->n_ent; a.d = t->d; a.n_oct = pl.n_oct; a.rows_per_wg = pl.rows_per_wg;
+    a.cand_wgs = cand_passes ? pl.cand_wgs : 0;
+    a.vec = (t->d % 4 == 0 && aligned16(t->E, t->R) && (loss_only || aligned16(dE, dR))) ? 1 : 0;
+    a.loss_only = loss_only ? 1 : 0;
+    a.row_grads = row_grads ? 1 : 0;
+    // one lane owns every element it adds to -- a candidate range, a list the caller vouches for, distinct prefix rows,
+    // occurrence rows -- or an id may repeat: float atomics
+    a.cand_atomic = (row_grads || !cand->ids || (flags & OKGE_TRAIN_UNIQUE_CANDIDATES)) ? 0 : 1;
+    a.prefix_atomic = (row_grads || (flags & OKGE_TRAIN_DISTINCT_PREFIX_ROWS)) ? 0 : 1;
+    // a prefix entity may be a candidate: plain candidate updates and atomic prefix updates of one row must not meet in a launch
+    const int n_wgs = a.cand_wgs + pl.prefix_wgs, first = (!loss_only && !a.cand_atomic && a.prefix_atomic) ? a.cand_wgs : n_wgs;
+    if (int rc = OKGE_TIMED("n3", "n3_kernel", st, launch_n3(a, 0, first, st))) return rc;
+    if (int rc = OKGE_TIMED("n3", "n3_kernel", st, launch_n3(a, first, n_wgs - first, st))) return rc;
+    return OKGE_TIMED("loss_reduce", "loss_reduce", st, launch_loss_reduce(a.partial, a.cand_wgs + pl.prefix_wgs, reg_out, st));
+}
+
 // ---- entity-sharded phases ---------------------------------------------------------------------------------------
 int64_t okge_query_ld(int32_t d)
 {

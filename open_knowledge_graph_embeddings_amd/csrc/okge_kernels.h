@@ -146,6 +146,22 @@ hipError_t launch_bias_prefix_rows(int d, int scorer, const PrefixDev &p, const 
                                    const double *loss_partials, int n_partials, double *loss_out, float *dr_rows, float *de_rows,
                                    int distinct, hipStream_t st);
 hipError_t launch_loss_reduce(const double *partials, int n, double *loss_out, hipStream_t st);
+// the N3 regulariser (okge_n3.hip): value partials + gradient of c sum |x|^3 over the candidate rows (cand_wgs workgroups,
+// none at cand_passes == 0) and the 2 B prefix rows; the caller reduces the partials (launch_loss_reduce)
+struct N3Args {
+    const float   *E, *R;
+    float         *dE, *dR;          // the tables' gradients; row_grads: the occurrence rows gE [N + B][d] / gR [B][d]
+    double        *partial;          // [cand_wgs + prefix_wgs]
+    const int32_t *cand_ids;
+    PrefixDev      p;
+    DropDev        drop_c;
+    double         value_cand, value_prefix;   // c * passes, c: what a workgroup's sum of |x|^3 is multiplied by
+    double         grad_cand, grad_prefix;     // 3 c passes / normalizer, 3 c / normalizer (the mask scale joins in the kernel)
+    int32_t        cand_first, N, n_ent, d, n_oct, rows_per_wg, cand_wgs, wg0;
+    int32_t        vec;              // d % 4 == 0 and every base 16-byte aligned: float4 accesses
+    int32_t        loss_only, row_grads, cand_atomic, prefix_atomic;
+};
+hipError_t launch_n3(const N3Args &a, int wg0, int n_wgs, hipStream_t st);     // workgroups [wg0, wg0 + n_wgs) of the call
 hipError_t launch_kl_count_pos(const int32_t *pos_row, int nnz, int Bpad, float *row_ysum, hipStream_t st);
 hipError_t launch_kl_row_lse(const float *stats, int tiles, int B, int Bpad, float *run, int first, int last, float *row_lse,
                              hipStream_t st, const int32_t *pos_row = nullptr, int nnz = 0, float *row_ysum = nullptr);

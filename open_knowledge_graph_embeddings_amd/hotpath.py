@@ -147,6 +147,12 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def n3_coef(l2_reg, dropout):
+    """the factor of sum |x|^3 in the reference's hook: the rows are divided by `dropout` -- the probability, not the keep
+    rate -- before the cube when it is > 0 (model.py:473-475)"""
+    return float(l2_reg) / float(dropout) ** 3 if dropout > 0 else float(l2_reg)
+
+
 def _i32(t, dev):
     if t is None:
         return None
@@ -310,6 +316,36 @@ class HotPath:
             ws.data_ptr(), self._ws_bytes, self._stream()), "okge_train_forward_backward")
         del keep, keep_pos
         return loss_out
+
+    def n3_workspace(self, B, n_cand, d):
+        """scratch of okge_n3_forward_backward: it runs after the step on the same stream, so it shares the step's workspace"""
+        need = int(self.lib.okge_n3_workspace_bytes(B, n_cand, d))
+        if need == 0:
+            raise N.OkgeError(f"invalid problem size B={B} N={n_cand} d={d}")
+        return self._grow(need)
+
+    def n3_forward_backward(self, E, R, scorer, batch: PrefixBatch, dE, dR, coef, cand_passes=1, normalizer=None, reg_out=None,
+                            loss_only=False, distinct_prefix_rows=False, row_grads=False):
+        """The N3 regulariser (`l2_reg`, model.py:471-479) of the batch's rows under the batch's dropout masks:
+        reg_out (device double[1]) = coef * (cand_passes * sum over the candidate rows + sum over the prefix rows) of |x|^3, and
+        its gradient / normalizer ADDED to dE / dR -- issue it after forward_backward with the same batch and buffers
+        (okge.h, okge_n3_forward_backward).  coef = n3_coef(l2_reg, dropout)."""
+        self._check(batch, E, R)
+        pb, c, keep = self._batch(batch)
+        t = self._tables(E, R, scorer)
+        B, n = batch.B, c.n
+        ws = self.n3_workspace(B, n, min(t.d, WIDE_MAX_SLOT))
+        if normalizer is None:
+            normalizer = float(B) * float(n)
+        if reg_out is None:
+            reg_out = torch.empty(1, dtype=torch.float64, device=self.device)
+        flags = (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) | (N.OKGE_TRAIN_UNIQUE_CANDIDATES if batch.cand_unique else 0) | \
+            (N.OKGE_TRAIN_DISTINCT_PREFIX_ROWS if distinct_prefix_rows else 0) | (N.OKGE_TRAIN_ROW_GRADS if row_grads else 0)
+        N.check(self.lib.okge_n3_forward_backward(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), float(coef), int(cand_passes),
+                                                  float(normalizer), flags, reg_out.data_ptr(), _ptr(dE), _ptr(dR), ws.data_ptr(),
+                                                  self._ws_bytes, self._stream()), "okge_n3_forward_backward")
+        del keep
+        return reg_out
 
     # -- entity-sharded phases (include/okge.h: okge_encode_queries / okge_train_tiles / okge_prefix_backward) ----
     def query_shape(self, B, d):

@@ -372,6 +372,8 @@ class ReplicaTrainStep(FusedTrainStep):
     (trainer.py:143-145) is the closest counterpart."""
 
     def __init__(self, E, R, scorer, group=None, **kw):
+        if kw.get("l2_reg"):
+            raise NotImplementedError("ReplicaTrainStep: l2_reg (the N3 regulariser) is built for the single-device FusedTrainStep")
         super().__init__(E, R, scorer, **kw)
         self.group = group
         self.world = dist.get_world_size(group)

@@ -18,7 +18,8 @@ class FusedTrainStep:
     def __init__(self, E: torch.Tensor, R: torch.Tensor, scorer: str, loss: str = "bce", lr: float = 0.3,
                  weight_decay: float = 1e-10, eps: float = 1e-8, label_smoothing: float = 0.0,
                  input_dropout: float = 0.0, relation_input_dropout: float = 0.0, seed: int = 0, engine=None,
-                 grad_clip: float = 0.0, accumulate: int = 1, sparse: bool = False, decay_window=None):
+                 grad_clip: float = 0.0, accumulate: int = 1, sparse: bool = False, decay_window=None,
+                 l2_reg: float = 0.0, l2_reg_dropout: float = 0.0, l2_reg_per_direction: bool = False):
         """Defaults follow config/fb15k237/fb15k237-complex-kge.yaml and the optimizer OptimRegime actually
         builds (utils/optim.py:29,139-160): Adagrad(lr, weight_decay=1e-10, eps=1e-8 leaked from Adam).
 
@@ -33,7 +34,15 @@ class FusedTrainStep:
         flush() tables and accumulators are bit-identical to the dense step's wherever that step's atomics are order-free.
         CONTRACT: between steps, rows no batch named may lag by up to decay_window - 1 decay-only steps -- call flush() before
         reading .E / .sumE / .R / .sumR or handing them to an evaluator (state_tensors() and the checkpoint writer do), and
-        before discarding a step object whose tables live on.  Needs d % 4 == 0."""
+        before discarding a step object whose tables live on.  Needs d % 4 == 0.
+
+        l2_reg (LookupBaseRelationEmbedder's keyword, model.py:444-453, :471-479; 0: off, nothing is launched): the N3
+        regulariser as the reference spells it -- l2_reg * sum |x|^3 over the rows every _encode call of the batch returns,
+        after dropout -- added to each batch's gradients before clipping (okge_n3_forward_backward, issued behind the step's own
+        call).  `reg_out` (device double[1], beside `loss_out`) receives the term's value, the Trainer's `hook`; the loss
+        excludes it.  l2_reg_dropout: the embedder's `dropout`, by which the reference divides the rows before the cube when it
+        is > 0 (the probability; a divisor only, this step applies input_dropout).  l2_reg_per_direction: the candidate block
+        counts once per direction present (batch_shared_entities None, trainer.py:86-87) instead of once (a shared list)."""
         N.refuse_bias_scorer(scorer, type(self).__name__)
         self.sparse = bool(sparse)
         self.decay_window = None if decay_window is None else int(decay_window)
@@ -76,6 +85,11 @@ class FusedTrainStep:
         self._grads_zero = True           # fresh buffers; kept true by the zero_grad fused into Adagrad
         self._dE_stale = False            # dE holds last step's values (they get overwritten, not accumulated)
         self.loss_out = torch.zeros(1, dtype=torch.float64, device=E.device)
+        self.l2_reg, self.l2_reg_dropout = float(l2_reg or 0.0), float(l2_reg_dropout or 0.0)
+        self.l2_reg_per_direction = bool(l2_reg_per_direction)
+        if self.l2_reg < 0 or self.l2_reg_dropout < 0:
+            raise ValueError("l2_reg and l2_reg_dropout are non-negative")
+        self.reg_out = torch.zeros(1, dtype=torch.float64, device=E.device)   # value of the l2_reg term of the last batch
         # trainer.py:229-244: gradients of `accumulate` consecutive batches are summed before one optimizer step
         # (batch_size_for_backward = accumulate x batch_size), clipped to `grad_clip` (global 2-norm) if > 0
         self.grad_clip, self.accumulate = float(grad_clip or 0.0), max(1, int(accumulate))
@@ -199,8 +213,24 @@ class FusedTrainStep:
                 return False
         return batch.pos_row is not None and batch.cand_table is None
 
+    def _regularise(self, batch: H.PrefixBatch, normalizer, dE, dR, row_grads=False):
+        """the l2_reg term of this batch, added to the gradients the step's call just left (same masks: same seed, streams, step)"""
+        self._set_dropout(batch)
+        passes = (int(batch.n_po > 0) + int(batch.n_sp > 0)) if self.l2_reg_per_direction else 1
+        self.engine.n3_forward_backward(self.E, self.R, self.scorer, batch, dE, dR, H.n3_coef(self.l2_reg, self.l2_reg_dropout),
+                                        cand_passes=passes, normalizer=normalizer, reg_out=self.reg_out, row_grads=row_grads)
+
     def forward_backward(self, batch: H.PrefixBatch, normalizer=None):
         """trainer.py:206-234.  Returns the summed loss (device double[1], valid after stream sync)."""
+        loss = self._forward_backward(batch, normalizer)
+        if self.l2_reg > 0:
+            if self.sparse:
+                self._regularise(batch, normalizer, self._cur_rows["gE"], self._cur_rows["gR"], row_grads=True)
+            else:
+                self._regularise(batch, normalizer, self.dE, self.dR)
+        return loss
+
+    def _forward_backward(self, batch: H.PrefixBatch, normalizer=None):
         if self.sparse:
             rb = self._cur_rows = self._row_buffers(batch)
             H.occurrence_ids(self.E.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,

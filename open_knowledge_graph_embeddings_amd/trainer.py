@@ -52,6 +52,22 @@ class _FusedLossFn(torch.autograd.Function):
         return g_e, g_r, None, None, None, None, None, None
 
 
+class _FusedLossHookFn(torch.autograd.Function):
+    """_FusedLossFn with the l2_reg hook as a second output (AddLossModule(fused_l2_reg=True)): the fused calls left the
+    gradient of loss + hook, times `applied`, in g_e / g_r, so the reference Trainer's `(loss.sum() + hook) / normalizer`
+    (trainer.py:217-221) hands both outputs the same upstream scalar; the loss's is the one compared with `applied`."""
+
+    @staticmethod
+    def forward(ctx, e_weight, r_weight, loss, reg, g_e, g_r, engine, applied, row_ids):
+        ctx.g_e, ctx.g_r, ctx.engine, ctx.applied = g_e, g_r, engine, applied
+        ctx.row_ids, ctx.shapes = row_ids, (e_weight.shape, r_weight.shape)
+        return loss.to(torch.float32).reshape(()), reg.to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_loss, grad_hook):
+        return _FusedLossFn.backward(ctx, grad_loss) + (None,)
+
+
 def _flat(t):
     return None if t is None else t.reshape(-1)
 
@@ -106,7 +122,7 @@ class AddLossModule(nn.Module):
     returns None in its place: the reference's Trainer reads the predictions only in evaluation (trainer.py:258-272), and
     the (B, N) block is the one thing the fused training kernels never need to write (29.8 MB per step at FB15k-237)."""
 
-    def __init__(self, model, loss, bce_label_smoothing=0.0, training_outputs=True, sparse_grads=False):
+    def __init__(self, model, loss, bce_label_smoothing=0.0, training_outputs=True, sparse_grads=False, fused_l2_reg=False):
         super().__init__()
         self.model = model
         self.loss = loss
@@ -116,8 +132,24 @@ class AddLossModule(nn.Module):
         # mode the two embedding weights receive UNCOALESCED sparse gradients -- one value row per candidate / prefix occurrence,
         # stored by the fused step -- for an optimizer with a sparse branch (OkgeAdagrad, weight_decay = 0)
         self.sparse_grads = bool(sparse_grads)
+        # fused_l2_reg (not in the reference's signature; opt-in as sparse_grads is): a lookup ComplEx / DistMult model whose ONLY
+        # _encode variant is l2_reg (model.py:471-479) takes the fused step instead of the torch fall-through; the hook's value
+        # and gradient come from okge_n3_forward_backward, issued behind the step on the same buffers, and `hook_loss` is
+        # returned attached to the graph.  With batch_shared_entities None the fused step draws ONE candidate mask for both
+        # directions where the reference draws one per direction: the hook is then twice one term -- exact without dropout,
+        # equal in expectation with it.
+        self.fused_l2_reg = bool(fused_l2_reg)
+        if self.fused_l2_reg and (hasattr(model, "entity_token_ids") or getattr(model, "fused_step_model", False)
+                                  or not hasattr(model, "entity_embedding") or not hasattr(model, "l2_reg")
+                                  or getattr(model, "scorer_name", None) not in ("complex", "distmult")
+                                  or getattr(model, "batch_norm", False) or getattr(model, "project_entity", False)
+                                  or getattr(model, "normalize", "")):
+            raise NotImplementedError("fused_l2_reg=True is built for the ComplEx / DistMult lookup models with l2_reg as their only "
+                                      "_encode variant (no batch-norm, projection or normalisation; Tucker3 regularises its "
+                                      "projected rows, the token embedders have no such keyword)")
         if self.sparse_grads and (hasattr(model, "entity_token_ids") or getattr(model, "fused_step_model", False)
-                                  or getattr(model, "encode_in_torch", False) or not hasattr(model, "entity_embedding")
+                                  or (getattr(model, "encode_in_torch", False) and not self.fused_l2_reg)
+                                  or not hasattr(model, "entity_embedding")
                                   or getattr(model, "scorer_name", None) not in ("complex", "distmult")):
             raise NotImplementedError("sparse_grads=True is built for the ComplEx / DistMult lookup models without batch-norm, "
                                       "projection or normalisation (the encoded-row and token models return dense gradients)")
@@ -126,6 +158,17 @@ class AddLossModule(nn.Module):
             # the fused kernels produce exactly that sum -- any other reduction would be silently different
             raise NotImplementedError(f"loss.reduction={loss.reduction!r}: the fused path implements reduction='sum' "
                                       f"(scripts/train.py:92-99)")
+
+    def _in_torch(self, m):
+        """the model's embedder falls through to torch for the encode (model.py): not on the fused_l2_reg route"""
+        return getattr(m, "encode_in_torch", False) and not self.fused_l2_reg
+
+    def _n3_term(self, m, n_po, n_sp, batch_shared_entities):
+        """(coef, cand_passes) of the fused l2_reg hook, or None when the model adds none (model.py:471: training mode only)"""
+        if not (self.fused_l2_reg and m.training and m.l2_reg > 0):
+            return None
+        passes = (int(n_po > 0) + int(n_sp > 0)) if batch_shared_entities is None else 1
+        return H.n3_coef(m.l2_reg, m.dropout), passes
 
     def _loss_kind(self):
         if isinstance(self.loss, KLDivLoss):
@@ -150,7 +193,7 @@ class AddLossModule(nn.Module):
         n_ent, first = m.train_data.entities_size, m.train_data.min_entities_size
         po, sp = inputs
         if FAST_CALL and not token_model and m.training and torch.is_grad_enabled() and isinstance(labels, tuple) \
-                and not getattr(m, "encode_in_torch", False) and not H.VALIDATE:
+                and not self._in_torch(m) and not H.VALIDATE:
             fast = self._fast_training_call(m, eng, dev, po, sp, labels, use_batch_shared_entities, batch_shared_entities, kind, epoch)
             if fast is not None:
                 return fast
@@ -187,7 +230,7 @@ class AddLossModule(nn.Module):
         if self.training_outputs or not m.training:
             all_outputs = torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :n]
         smoothing = self.bce_label_smoothing if kind == "bce" else 0.0
-        if getattr(m, "encode_in_torch", False):
+        if self._in_torch(m):
             return self._variant_result(m, batch, kind, smoothing, want_grad, all_outputs, epoch,
                                         all_entities=not use_batch_shared_entities and not m.training,
                                         per_direction=batch_shared_entities is None)
@@ -200,6 +243,7 @@ class AddLossModule(nn.Module):
         batch.drop_cand = m.dropout_spec(H.STREAM_CAND)
         batch.drop_po_ent, batch.drop_sp_ent = m.dropout_spec(H.STREAM_PO_ENT), m.dropout_spec(H.STREAM_SP_ENT)
         batch.drop_po_rel, batch.drop_sp_rel = m.dropout_spec(H.STREAM_PO_REL, True), m.dropout_spec(H.STREAM_SP_REL, True)
+        n3 = self._n3_term(m, batch.n_po, batch.n_sp, batch_shared_entities)
         if want_grad:
             E, R = m.E, m.R
             # a contiguous candidate range: the call stores the candidate rows and clears the rest itself (all of dR, the
@@ -221,12 +265,21 @@ class AddLossModule(nn.Module):
             loss = eng.forward_backward(E, R, m.scorer_name, batch, g_e, g_r, loss=kind, label_smoothing=smoothing,
                                         normalizer=1.0 / float(applied), scores=all_outputs, grads_zero=True, clear_grads=clear,
                                         row_grads=self.sparse_grads)
-            result = _FusedLossFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, g_e, g_r, eng,
-                                        float(applied), row_ids)
+            if n3 is not None:
+                reg = eng.n3_forward_backward(E, R, m.scorer_name, batch, g_e, g_r, n3[0], cand_passes=n3[1],
+                                              normalizer=1.0 / float(applied), row_grads=self.sparse_grads)
+                result, hook_loss = _FusedLossHookFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, reg, g_e,
+                                                           g_r, eng, float(applied), row_ids)
+            else:
+                result = _FusedLossFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, g_e, g_r, eng,
+                                            float(applied), row_ids)
         else:
             loss = eng.forward_backward(m.E, m.R, m.scorer_name, batch, None, None, loss=kind, label_smoothing=smoothing,
                                         normalizer=1.0, scores=all_outputs, loss_only=True)
             result = loss.to(torch.float32).reshape(())
+            if n3 is not None:
+                hook_loss = eng.n3_forward_backward(m.E, m.R, m.scorer_name, batch, None, None, n3[0], cand_passes=n3[1],
+                                                    normalizer=1.0, loss_only=True).to(torch.float32).reshape(())
         return result, hook_loss, all_outputs
 
     def _fast_training_call(self, m, eng, dev, po, sp, labels, use_batch_shared_entities, batch_shared_entities, kind, epoch):
@@ -304,8 +357,20 @@ class AddLossModule(nn.Module):
             flags, loss.data_ptr(), g_e.data_ptr(), g_r.data_ptr(),
             None if all_outputs is None else all_outputs.data_ptr(), 0 if all_outputs is None else all_outputs.stride(0),
             ws.data_ptr(), eng._ws_bytes, eng._stream()), "okge_train_forward_backward")
+        n3 = self._n3_term(m, n_po, n_sp, batch_shared_entities)
+        if n3 is not None:                                                     # the l2_reg hook, behind the step on the same structs
+            reg = torch.empty(1, dtype=torch.float64, device=dev)
+            ws = eng.n3_workspace(B, n, t.d)
+            N.check(eng.lib.okge_n3_forward_backward(
+                ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), n3[0], n3[1], 1.0 / float(applied),
+                N.OKGE_TRAIN_ROW_GRADS if self.sparse_grads else 0, reg.data_ptr(), g_e.data_ptr(), g_r.data_ptr(), ws.data_ptr(),
+                eng._ws_bytes, eng._stream()), "okge_n3_forward_backward")
         if CALLER_THREAD_BACKWARD and torch.autograd.is_multithreading_enabled():
             torch.autograd.set_multithreading_enabled(False)                   # (see forward below)
+        if n3 is not None:
+            result, hook_loss = _FusedLossHookFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, reg, g_e, g_r,
+                                                       eng, float(applied), row_ids)
+            return result, hook_loss, all_outputs
         result = _FusedLossFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, g_e, g_r, eng, float(applied),
                                     row_ids)
         return result, hook_loss, all_outputs
