@@ -829,6 +829,43 @@ typedef struct okge_eval_batch {
 } okge_eval_batch;
 int okge_evaluate_fused_batches(const okge_tables *t, const okge_eval_batch *batches, int32_t n_batches, int64_t *ranks,
                                 double *acc, void *workspace, size_t workspace_bytes, void *const *streams, int32_t n_streams);
+/* ---- the validation loss of an evaluation batch -------------------------------------------------------------------
+ * Trainer.compute_one_batch(training=False) also reports the batch's loss (trainer.py:93-106, :263-271): eval mode, the
+ * UNFILTERED scores x[b][n] of all N candidates, labels y[b][n] = 1 for every candidate column named by any answer group
+ * of row b (the union of the row's ids: a column named twice counts once).
+ *   OKGE_LOSS_BCE  L = sum_{b,n} max(x,0) - x y' + log1p(e^-|x|),  y' = (y + 1/N)(1 - label_smoothing) if label_smoothing > 0
+ *                  else y.  Per row: S_b - (1 - eps)(P_b + X_b / N), S_b = sum_n softplus(x), X_b = sum_n x, P_b = sum of x
+ *                  over the row's positives.
+ *   OKGE_LOSS_KL   L = sum_b npos_b lse_b - P_b (unnormalised labels, no smoothing; a row without positives adds 0).
+ * out[i] (DEVICE double) receives L of batch i of the call -- a plain store per batch, no atomics; the reference's meter is
+ * loss.update(L / (B N), B N), i.e. sum L / sum B N over a pass.  The entry points below are their namesakes with this one
+ * more argument: ranks and meters are bit-equal to the call without it, and a batch without answer groups still has a loss.
+ *   okge_evaluate_fused_loss / okge_evaluate_fused_batches_loss: the counting sweep also leaves one float2 per (tile, row)
+ *     -- (sum softplus, sum x) or (max, sum-exp) over the tile's candidates --, the points launch the label term P_b / npos_b
+ *     from the point scores it computes anyway, and one more small launch merges a row's tiles in tile order and adds the
+ *     rows in row order: the same bits on every run, for any n_streams and for a batch alone or in a run.  No (B, N) block,
+ *     no second sweep.  Workspace (each slot of a run): okge_eval_loss_workspace_bytes.
+ *   okge_evaluate_batch_loss: the same quantities reduced from the materialised score block (every slot size up to 4096,
+ *     dropout, candidate tables), in the rank stream's order.  Workspace: okge_evaluate_batch_loss_workspace_bytes. */
+typedef struct okge_eval_loss {
+    int32_t kind;              /* OKGE_LOSS_BCE or OKGE_LOSS_KL */
+    float   label_smoothing;   /* BCE only, in [0, 1) */
+    double *out;               /* DEVICE: one double per batch of the call */
+} okge_eval_loss;
+size_t okge_eval_loss_workspace_bytes(int32_t B, int32_t N, int32_t d, int64_t n_groups, int64_t n_filter);
+int okge_evaluate_fused_loss(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
+                             const int64_t *filt_ptr, const int32_t *filt_col, int64_t n_filter, const int64_t *row_ptr,
+                             const int64_t *grp_ptr, const int32_t *ids, int64_t n_groups, int64_t *ranks, double *acc,
+                             void *workspace, size_t workspace_bytes, void *stream, const okge_eval_loss *loss);
+int okge_evaluate_fused_batches_loss(const okge_tables *t, const okge_eval_batch *batches, int32_t n_batches, int64_t *ranks,
+                                     double *acc, void *workspace, size_t workspace_bytes, void *const *streams, int32_t n_streams,
+                                     const okge_eval_loss *loss);
+size_t okge_evaluate_batch_loss_workspace_bytes(int32_t B, int32_t d);
+int okge_evaluate_batch_loss(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
+                             const int64_t *filt_ptr, const int32_t *filt_col, const int64_t *row_ptr,
+                             const int64_t *grp_ptr, const int32_t *ids, int64_t n_groups, float *scores, int64_t ld_scores,
+                             int64_t *ranks, double *acc, void *workspace, size_t workspace_bytes, void *stream,
+                             void *rank_stream, const okge_eval_loss *loss);
 /* The same rank rule with the candidate columns [col0, col0 + n_local) of every row held by this rank
  * (scores: B x n_local; filter columns and group ids stay positions in the FULL candidate list):
  * true_out[g] = max over the group's ids inside the local range (-inf if none)       -> all-reduce(max)

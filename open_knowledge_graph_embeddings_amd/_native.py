@@ -55,6 +55,8 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_train_row_grads_workspace_bytes", "okge_adagrad_rows", "okge_adagrad_rows_workspace_bytes",
            "okge_rows_catch_up", "okge_adagrad_rows_decay",
            "okge_n3_workspace_bytes", "okge_n3_forward_backward",
+           "okge_eval_loss_workspace_bytes", "okge_evaluate_fused_loss", "okge_evaluate_fused_batches_loss",
+           "okge_evaluate_batch_loss_workspace_bytes", "okge_evaluate_batch_loss",
            "okge_timing_reset", "okge_timing_collect"]
 
 
@@ -82,6 +84,19 @@ class EvalBatch(Structure):
     _fields_ = [("batch", PrefixBatch), ("cand", Candidates), ("filt_ptr", c_void_p), ("filt_col", c_void_p),
                 ("n_filter", c_int64), ("row_ptr", c_void_p), ("grp_ptr", c_void_p), ("ids", c_void_p),
                 ("n_groups", c_int64), ("rank_offset", c_int64)]
+
+
+class EvalLoss(Structure):
+    _fields_ = [("kind", c_int32), ("label_smoothing", c_float), ("out", c_void_p)]
+
+
+def eval_loss(loss, label_smoothing, out_ptr):
+    """okge_eval_loss of a validation loss 'bce' / 'kl' (or an OKGE_LOSS_* value) that writes to out_ptr"""
+    if isinstance(loss, str) and loss not in LOSSES:
+        raise ValueError(f"unknown loss {loss!r}: 'bce' or 'kl'")
+    x = EvalLoss()
+    x.kind, x.label_smoothing, x.out = LOSSES[loss] if isinstance(loss, str) else int(loss), float(label_smoothing), out_ptr
+    return x
 
 
 class Tables(Structure):
@@ -323,6 +338,16 @@ def lib():
     L.okge_evaluate_fused_batches.restype = c_int32
     L.okge_evaluate_fused_batches.argtypes = [POINTER(Tables), POINTER(EvalBatch), c_int32, c_void_p, c_void_p, c_void_p,
                                               c_size_t, POINTER(c_void_p), c_int32]
+    L.okge_evaluate_fused_loss.restype = c_int32
+    L.okge_evaluate_fused_loss.argtypes = L.okge_evaluate_fused.argtypes + [POINTER(EvalLoss)]
+    L.okge_evaluate_fused_batches_loss.restype = c_int32
+    L.okge_evaluate_fused_batches_loss.argtypes = L.okge_evaluate_fused_batches.argtypes + [POINTER(EvalLoss)]
+    L.okge_evaluate_batch_loss.restype = c_int32
+    L.okge_evaluate_batch_loss.argtypes = L.okge_evaluate_batch.argtypes + [POINTER(EvalLoss)]
+    L.okge_eval_loss_workspace_bytes.restype = c_size_t
+    L.okge_eval_loss_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int64, c_int64]
+    L.okge_evaluate_batch_loss_workspace_bytes.restype = c_size_t
+    L.okge_evaluate_batch_loss_workspace_bytes.argtypes = [c_int32, c_int32]
     L.okge_eval_workspace_bytes.restype = c_size_t
     L.okge_eval_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int64, c_int64]
     L.okge_pool_workspace_bytes.restype = c_size_t

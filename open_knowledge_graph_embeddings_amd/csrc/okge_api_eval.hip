@@ -48,7 +48,21 @@ struct EvalCall {                      // one batch's launch arguments, built on
     FusedArgs sweep;
     int32_t *counts;
     int64_t n_groups;
+    // the validation loss (okge_evaluate_fused_loss / _batches_loss): a batch is then swept even without answer groups
+    bool live;                         // something is launched for this batch
+    int  loss_mode;                    // MODE_COUNT, or MODE_COUNT_BCE / MODE_COUNT_KL
+    EvalLossPoints lpts;
+    EvalLossReduce lred;
 };
+
+int check_eval_loss(const okge_eval_loss *loss)
+{
+    if (!loss->out) return fail(OKGE_ERR_INVALID, "okge_eval_loss: out is NULL");
+    if (loss->kind != OKGE_LOSS_BCE && loss->kind != OKGE_LOSS_KL) return fail(OKGE_ERR_INVALID, "unknown loss");
+    if (!(loss->label_smoothing >= 0.f && loss->label_smoothing < 1.f))
+        return fail(OKGE_ERR_INVALID, "label smoothing must be in [0, 1)");
+    return OKGE_OK;
+}
 
 // Candidate-sharded call (okge_evaluate_fused_shard): folded queries from outside, the shard's candidate columns, the
 // true scores in a caller-owned buffer (they are exchanged between the phases), counts instead of ranks.
@@ -62,7 +76,8 @@ struct EvalShard {
 int eval_call(EvalCall &c, const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
               const int64_t *filt_ptr, const int32_t *filt_col, int64_t n_filter, const int64_t *row_ptr,
               const int64_t *grp_ptr, const int32_t *ids, int64_t n_groups, int64_t *ranks, double *acc,
-              void *workspace, size_t workspace_bytes, const EvalShard *es = nullptr)
+              void *workspace, size_t workspace_bytes, const EvalShard *es = nullptr, const okge_eval_loss *loss = nullptr,
+              double *loss_out = nullptr)
 {
     if (!es) {
         if (int rc = check_common(t, batch, cand)) return rc;
@@ -76,13 +91,16 @@ int eval_call(EvalCall &c, const okge_tables *t, const okge_prefix_batch *batch,
     if (cand->table || any_dropout(batch, cand))
         return fail(OKGE_ERR_UNSUPPORTED, "fused evaluation is the eval-mode path (no dropout, candidates from the entity table)");
     c.n_groups = n_groups;
-    if (n_groups == 0) return OKGE_OK;
+    c.live = n_groups > 0 || loss;
+    c.loss_mode = !loss ? MODE_COUNT : loss->kind == OKGE_LOSS_KL ? MODE_COUNT_KL : MODE_COUNT_BCE;
+    if (!c.live) return OKGE_OK;
     const int32_t B = es ? es->B : batch->n_po + batch->n_sp;
     Shape &g = c.g;
     EvalLayout &eg = c.eg;
     if (!make_shape(B, cand->n, t->d, g) || !eval_layout(g, n_groups, n_filter, eg)) return fail(OKGE_ERR_INVALID, "bad shape");
     c.sweep_plan = plan_sweep(g, g.tiles, cu_count(), read_knobs());
-    if (!workspace || workspace_bytes < eg.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    const EvalLossLayout ll = eval_loss_layout(g, eg.total);
+    if (!workspace || workspace_bytes < (loss ? ll.total : eg.total)) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
     char *ws = static_cast<char *>(workspace);
     float *Q = reinterpret_cast<float *>(ws + eg.off_Q), *tru = es ? es->true_scores : reinterpret_cast<float *>(ws + eg.off_true);
     float *fx = reinterpret_cast<float *>(ws + eg.off_filt);
@@ -114,7 +132,31 @@ int eval_call(EvalCall &c, const okge_tables *t, const okge_prefix_batch *batch,
     r.counts = a.rk_counts; r.slab = a.rk_slab; r.true_scores = tru; r.filt_x = fx; r.filt_ptr = filt_ptr; r.gshift = gshift;
     r.group_row = grow; r.ranks = ranks; r.acc = acc; r.n_groups = n_groups; r.tiles = g.tiles; r.B = B;
     r.counts_out = es ? es->counts_out : nullptr;
+    if (loss) {
+        a.stats = reinterpret_cast<float *>(ws + ll.off_part);
+        c.lpts.pos_sum = reinterpret_cast<double *>(ws + ll.off_pos);
+        c.lpts.npos = reinterpret_cast<int32_t *>(ws + ll.off_npos);
+        EvalLossReduce &q = c.lred;
+        q.part = reinterpret_cast<const float2 *>(a.stats); q.pos_sum = c.lpts.pos_sum; q.npos = c.lpts.npos;
+        q.rows = reinterpret_cast<double *>(ws + ll.off_rows); q.out = loss_out;
+        q.smoothing = loss->kind == OKGE_LOSS_BCE ? (double)loss->label_smoothing : 0.0;
+        q.tiles = g.tiles; q.B = B; q.Bpad = g.Bpad; q.N = cand->n; q.kind = loss->kind == OKGE_LOSS_KL ? LOSS_KL : LOSS_BCE;
+    }
     return OKGE_OK;
+}
+
+// points of `pts` and ranks of `rk` (batches of one chain; either may be absent) in one launch, the points with the label
+// term of the validation loss if their batch has one
+hipError_t launch_side(const EvalCall *pts, const EvalCall *rk, hipStream_t st)
+{
+    if (pts && pts->loss_mode != MODE_COUNT) return launch_eval_side_loss(&pts->pts, &pts->lpts, rk ? &rk->rk : nullptr, st);
+    return launch_eval_side(pts ? &pts->pts : nullptr, rk ? &rk->rk : nullptr, st);
+}
+// the batch's loss, after its sweep and its points
+int eval_loss_issue(const EvalCall &c, hipStream_t st)
+{
+    if (c.loss_mode == MODE_COUNT) return OKGE_OK;
+    return OKGE_TIMED("eval_loss_reduce", "eval_loss_reduce", st, launch_eval_loss_reduce(c.lred, st));
 }
 
 // the rank counters of a batch start at zero (atomics path of very large batches only: the slabs are stored whole)
@@ -126,28 +168,32 @@ int clear_counts(const EvalCall &c, hipStream_t st)
 
 int eval_issue(int phases, const EvalCall &c, hipStream_t st)
 {
-    if (c.n_groups == 0) return OKGE_OK;
+    if (!c.live) return OKGE_OK;
     if (phases & 1) {
         if (int rc = clear_counts(c, st)) return rc;
-        if (int rc = OKGE_TIMED("eval_points", "eval_points", st, launch_eval_side(&c.pts, nullptr, st))) return rc;
+        if (int rc = OKGE_TIMED("eval_points", "eval_points", st, launch_side(&c, nullptr, st))) return rc;
     }
     // (slot sizes above 256: the register-tile kernel's counting mode in a stream-K launch)
     if (phases & 2)
         if (int rc = OKGE_TIMED("fused_tile_count", "fused_tile_kernel<count>", st,
-                                launch_sweep(c.g, c.sweep_plan, c.sweep, st, MODE_COUNT))) return rc;
-    if (phases & 4)
-        if (int rc = OKGE_TIMED("eval_ranks", "eval_ranks", st, launch_eval_side(nullptr, &c.rk, st))) return rc;
+                                launch_sweep(c.g, c.sweep_plan, c.sweep, st, c.loss_mode))) return rc;
+    if (phases & 4) {
+        if (int rc = OKGE_TIMED("eval_ranks", "eval_ranks", st, launch_side(nullptr, &c, st))) return rc;
+        if (int rc = eval_loss_issue(c, st)) return rc;
+    }
     return OKGE_OK;
 }
 
 int evaluate_fused_impl(int phases, const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
                         const int64_t *filt_ptr, const int32_t *filt_col, int64_t n_filter, const int64_t *row_ptr,
                         const int64_t *grp_ptr, const int32_t *ids, int64_t n_groups, int64_t *ranks, double *acc,
-                        void *workspace, size_t workspace_bytes, void *stream)
+                        void *workspace, size_t workspace_bytes, void *stream, const okge_eval_loss *loss = nullptr)
 {
     EvalCall c;
+    if (loss)
+        if (int rc = check_eval_loss(loss)) return rc;
     if (int rc = eval_call(c, t, batch, cand, filt_ptr, filt_col, n_filter, row_ptr, grp_ptr, ids, n_groups, ranks, acc, workspace,
-                           workspace_bytes))
+                           workspace_bytes, nullptr, loss, loss ? loss->out : nullptr))
         return rc;
     return eval_issue(phases, c, as_stream(stream));
 }
@@ -172,6 +218,75 @@ hipError_t eval_events(hipEvent_t **out)
     }
     *out = ev[dev];
     return hipSuccess;
+}
+
+// okge_evaluate_fused_batches; loss != nullptr: okge_evaluate_fused_batches_loss (batch i's loss -> loss->out[i])
+int evaluate_fused_batches_impl(const okge_tables *t, const okge_eval_batch *batches, int32_t n_batches, int64_t *ranks,
+                                double *acc, void *workspace, size_t workspace_bytes, void *const *streams, int32_t n_streams,
+                                const okge_eval_loss *loss)
+{
+    if (!batches || n_batches < 0 || !ranks || !acc || !workspace || !streams || n_streams < 1 || n_streams > EVAL_MAX_STREAMS)
+        return fail(OKGE_ERR_INVALID, "bad evaluate arguments (1 to 4 streams)");
+    if (n_batches == 0) return OKGE_OK;
+    hipStream_t st[EVAL_MAX_STREAMS];
+    for (int i = 0; i < n_streams; ++i) {
+        st[i] = as_stream(streams[i]);
+        for (int j = 0; j < i; ++j)
+            if (st[j] == st[i]) return fail(OKGE_ERR_INVALID, "okge_evaluate_fused_batches: the streams must differ");
+    }
+    const int S = n_streams, slots = 2 * S;
+    const size_t slot_bytes = (workspace_bytes / slots) & ~(size_t)255;
+    char *ws = static_cast<char *>(workspace);
+    // everything that can be refused is refused before the first launch.  Stream, workspace slot and position in the chain
+    // come from the batch's index IN THE CALL -- the caller numbers its rank regions by that index too --, so a batch without
+    // answer groups keeps its place and simply launches nothing (dropping it would shift the batches behind it onto other
+    // chains while their rank regions stay where the caller put them: two unordered chains writing one region).  With a loss
+    // every batch is live: the label-free part of its loss needs the sweep.
+    std::vector<EvalCall> calls((size_t)n_batches);
+    int live = 0;
+    for (int i = 0; i < n_batches; ++i) {
+        const okge_eval_batch &b = batches[i];
+        if (b.rank_offset < 0) return fail(OKGE_ERR_INVALID, "negative rank_offset");
+        if (int rc = eval_call(calls[i], t, &b.batch, &b.cand, b.filt_ptr, b.filt_col, b.n_filter, b.row_ptr, b.grp_ptr, b.ids,
+                               b.n_groups, ranks + b.rank_offset, acc, ws + (size_t)(i % slots) * slot_bytes, slot_bytes, nullptr, loss,
+                               loss ? loss->out + i : nullptr))
+            return rc;
+        live += calls[i].live;
+    }
+    const int n = n_batches;
+    if (live == 0) return OKGE_OK;
+    // Batch i runs on stream i % S; each stream is an independent chain [points i] [sweep i] [ranks i + points i+S]
+    // [sweep i+S] ... with no dependency on the others, so the device fills one chain's small latency-bound launches (and
+    // the CUs a sweep's tile grid leaves empty) with the other chains' work.  2 S workspace slots: two batches in flight
+    // per chain.
+    hipEvent_t *ev = nullptr;
+    if (S > 1) {
+        if (int rc = hip_ok(eval_events(&ev), "create evaluation events")) return rc;
+        if (int rc = hip_ok(hipEventRecord(ev[0], st[0]), "record fork")) return rc;       // the other streams join behind whatever
+        for (int k = 1; k < S; ++k)                                                        // produced the tables / batches on the first
+            if (int rc = hip_ok(hipStreamWaitEvent(st[k], ev[0], 0), "fork")) return rc;
+    }
+    for (int i = 0; i < n; ++i) {
+        hipStream_t s = st[i % S];
+        const bool has = calls[i].live;
+        if (i < S && has)                                              // head of a chain
+            if (int rc = eval_issue(1, calls[i], s)) return rc;
+        if (has)
+            if (int rc = eval_issue(2, calls[i], s)) return rc;
+        const EvalCall *nx = (i + S < n && calls[i + S].live) ? &calls[i + S] : nullptr;      // the chain's next batch
+        if (nx)
+            if (int rc = clear_counts(*nx, s)) return rc;
+        if (!nx && !has) continue;
+        if (int rc = OKGE_TIMED("eval_ranks+points", "eval_side", s,
+                                launch_side(nx, has ? &calls[i] : nullptr, s))) return rc;
+        if (has)
+            if (int rc = eval_loss_issue(calls[i], s)) return rc;
+    }
+    for (int k = 1; k < S; ++k) {
+        if (int rc = hip_ok(hipEventRecord(ev[k], st[k]), "record join")) return rc;
+        if (int rc = hip_ok(hipStreamWaitEvent(st[0], ev[k], 0), "join")) return rc;
+    }
+    return OKGE_OK;
 }
 
 }  // namespace
@@ -268,62 +383,85 @@ int okge_evaluate_fused_shard(int32_t phase, const okge_tables *t, const okge_sh
 int okge_evaluate_fused_batches(const okge_tables *t, const okge_eval_batch *batches, int32_t n_batches, int64_t *ranks,
                                 double *acc, void *workspace, size_t workspace_bytes, void *const *streams, int32_t n_streams)
 {
-    if (!batches || n_batches < 0 || !ranks || !acc || !workspace || !streams || n_streams < 1 || n_streams > EVAL_MAX_STREAMS)
-        return fail(OKGE_ERR_INVALID, "bad evaluate arguments (1 to 4 streams)");
-    if (n_batches == 0) return OKGE_OK;
-    hipStream_t st[EVAL_MAX_STREAMS];
-    for (int i = 0; i < n_streams; ++i) {
-        st[i] = as_stream(streams[i]);
-        for (int j = 0; j < i; ++j)
-            if (st[j] == st[i]) return fail(OKGE_ERR_INVALID, "okge_evaluate_fused_batches: the streams must differ");
-    }
-    const int S = n_streams, slots = 2 * S;
-    const size_t slot_bytes = (workspace_bytes / slots) & ~(size_t)255;
-    char *ws = static_cast<char *>(workspace);
-    // everything that can be refused is refused before the first launch.  Stream, workspace slot and position in the chain
-    // come from the batch's index IN THE CALL -- the caller numbers its rank regions by that index too --, so a batch without
-    // answer groups keeps its place and simply launches nothing (dropping it would shift the batches behind it onto other
-    // chains while their rank regions stay where the caller put them: two unordered chains writing one region).
-    std::vector<EvalCall> calls((size_t)n_batches);
-    int live = 0;
-    for (int i = 0; i < n_batches; ++i) {
-        const okge_eval_batch &b = batches[i];
-        if (b.rank_offset < 0) return fail(OKGE_ERR_INVALID, "negative rank_offset");
-        if (int rc = eval_call(calls[i], t, &b.batch, &b.cand, b.filt_ptr, b.filt_col, b.n_filter, b.row_ptr, b.grp_ptr, b.ids,
-                               b.n_groups, ranks + b.rank_offset, acc, ws + (size_t)(i % slots) * slot_bytes, slot_bytes))
+    return evaluate_fused_batches_impl(t, batches, n_batches, ranks, acc, workspace, workspace_bytes, streams, n_streams, nullptr);
+}
+
+int okge_evaluate_fused_batches_loss(const okge_tables *t, const okge_eval_batch *batches, int32_t n_batches, int64_t *ranks,
+                                     double *acc, void *workspace, size_t workspace_bytes, void *const *streams, int32_t n_streams,
+                                     const okge_eval_loss *loss)
+{
+    if (!loss) return fail(OKGE_ERR_INVALID, "okge_evaluate_fused_batches_loss: loss is NULL");
+    if (int rc = check_eval_loss(loss)) return rc;
+    return evaluate_fused_batches_impl(t, batches, n_batches, ranks, acc, workspace, workspace_bytes, streams, n_streams, loss);
+}
+
+size_t okge_eval_loss_workspace_bytes(int32_t B, int32_t N, int32_t d, int64_t n_groups, int64_t n_filter)
+{
+    Shape s;
+    EvalLayout e;
+    return make_shape(B, N, d, s) && eval_layout(s, n_groups, n_filter, e) ? eval_loss_layout(s, e.total).total : 0;
+}
+
+int okge_evaluate_fused_loss(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
+                             const int64_t *filt_ptr, const int32_t *filt_col, int64_t n_filter, const int64_t *row_ptr,
+                             const int64_t *grp_ptr, const int32_t *ids, int64_t n_groups, int64_t *ranks, double *acc,
+                             void *workspace, size_t workspace_bytes, void *stream, const okge_eval_loss *loss)
+{
+    if (!loss) return fail(OKGE_ERR_INVALID, "okge_evaluate_fused_loss: loss is NULL");
+    return evaluate_fused_impl(7, t, batch, cand, filt_ptr, filt_col, n_filter, row_ptr, grp_ptr, ids, n_groups, ranks, acc,
+                               workspace, workspace_bytes, stream, loss);
+}
+
+size_t okge_evaluate_batch_loss_workspace_bytes(int32_t B, int32_t d)
+{
+    const size_t base = okge_score_workspace_bytes(B, d);
+    return base ? block_loss_layout(B, base).total : 0;
+}
+
+int okge_evaluate_batch_loss(const okge_tables *t, const okge_prefix_batch *batch, const okge_candidates *cand,
+                             const int64_t *filt_ptr, const int32_t *filt_col, const int64_t *row_ptr, const int64_t *grp_ptr,
+                             const int32_t *ids, int64_t n_groups, float *scores, int64_t ld_scores, int64_t *ranks, double *acc,
+                             void *workspace, size_t workspace_bytes, void *stream, void *rank_stream, const okge_eval_loss *loss)
+{
+    if (!loss) return fail(OKGE_ERR_INVALID, "okge_evaluate_batch_loss: loss is NULL");
+    if (int rc = check_eval_loss(loss)) return rc;
+    if (!t || !batch || !cand || !row_ptr || !grp_ptr || (n_groups > 0 && !ids)) return fail(OKGE_ERR_INVALID, "bad evaluate arguments");
+    const int32_t B = batch->n_po + batch->n_sp;
+    const size_t base = okge_score_workspace_bytes(B, t->d);
+    const BlockLossLayout l = block_loss_layout(B, base);
+    if (!base || !workspace || workspace_bytes < l.total) return fail(OKGE_ERR_WORKSPACE, "workspace too small");
+    // scores, ranks and meters as without a loss; then, in the rank stream's order (the score block is intact until the next
+    // call that uses it, which waits for this stream), the rows' losses from the block and their sum
+    hipStream_t s0 = as_stream(stream), s1 = as_stream(rank_stream);
+    if (n_groups > 0) {
+        if (int rc = okge_evaluate_batch(t, batch, cand, filt_ptr, filt_col, row_ptr, grp_ptr, ids, n_groups, scores, ld_scores, ranks,
+                                         acc, workspace, base, stream, rank_stream))
             return rc;
-        live += calls[i].n_groups > 0;
+    } else {
+        // no answer group, nothing to rank (okge_filtered_ranks wants ids): the scores, and the loss behind them on `stream`
+        if (n_groups < 0 || !scores) return fail(OKGE_ERR_INVALID, "bad evaluate arguments");
+        if (s0 != s1) {
+            std::lock_guard<std::mutex> lk(g_eval_mu);
+            EvalSlot &sl = eval_slot(scores);
+            if (sl.used)
+                if (int rc = hip_ok(hipStreamWaitEvent(s0, sl.ranked, 0), "wait for the buffer's previous ranks")) return rc;
+        }
+        if (int rc = okge_score_prefixes(t, batch, cand, scores, ld_scores, workspace, base, stream)) return rc;
+        s1 = s0;
     }
-    const int n = n_batches;
-    if (live == 0) return OKGE_OK;
-    // Batch i runs on stream i % S; each stream is an independent chain [points i] [sweep i] [ranks i + points i+S]
-    // [sweep i+S] ... with no dependency on the others, so the device fills one chain's small latency-bound launches (and
-    // the CUs a sweep's tile grid leaves empty) with the other chains' work.  2 S workspace slots: two batches in flight
-    // per chain.
-    hipEvent_t *ev = nullptr;
-    if (S > 1) {
-        if (int rc = hip_ok(eval_events(&ev), "create evaluation events")) return rc;
-        if (int rc = hip_ok(hipEventRecord(ev[0], st[0]), "record fork")) return rc;       // the other streams join behind whatever
-        for (int k = 1; k < S; ++k)                                                        // produced the tables / batches on the first
-            if (int rc = hip_ok(hipStreamWaitEvent(st[k], ev[0], 0), "fork")) return rc;
-    }
-    for (int i = 0; i < n; ++i) {
-        hipStream_t s = st[i % S];
-        const bool has = calls[i].n_groups > 0;
-        if (i < S && has)                                              // head of a chain
-            if (int rc = eval_issue(1, calls[i], s)) return rc;
-        if (has)
-            if (int rc = eval_issue(2, calls[i], s)) return rc;
-        const EvalCall *nx = (i + S < n && calls[i + S].n_groups > 0) ? &calls[i + S] : nullptr;      // the chain's next batch
-        if (nx)
-            if (int rc = clear_counts(*nx, s)) return rc;
-        if (!nx && !has) continue;
-        if (int rc = OKGE_TIMED("eval_ranks+points", "eval_side", s,
-                                launch_eval_side(nx ? &nx->pts : nullptr, has ? &calls[i].rk : nullptr, s))) return rc;
-    }
-    for (int k = 1; k < S; ++k) {
-        if (int rc = hip_ok(hipEventRecord(ev[k], st[k]), "record join")) return rc;
-        if (int rc = hip_ok(hipStreamWaitEvent(st[0], ev[k], 0), "join")) return rc;
+    double *rows = reinterpret_cast<double *>(static_cast<char *>(workspace) + l.off_rows);
+    const int kind = loss->kind == OKGE_LOSS_KL ? LOSS_KL : LOSS_BCE;
+    if (int rc = OKGE_TIMED("block_loss_rows", "block_loss_rows", s1,
+                            launch_block_loss_rows(scores, ld_scores, B, cand->n, row_ptr, grp_ptr, ids, kind,
+                                                   kind == LOSS_BCE ? (double)loss->label_smoothing : 0.0, rows, s1)))
+        return rc;
+    EvalLossReduce q;
+    std::memset(&q, 0, sizeof(q));
+    q.rows = rows; q.out = loss->out; q.B = B; q.N = cand->n; q.kind = kind;
+    if (int rc = OKGE_TIMED("eval_loss_reduce", "eval_loss_reduce", s1, launch_eval_loss_reduce(q, s1))) return rc;
+    if (s0 != s1) {                              // the buffer's next use waits for the loss as it waits for the ranks
+        std::lock_guard<std::mutex> lk(g_eval_mu);
+        if (int rc = hip_ok(hipEventRecord(eval_slot(scores).ranked, s1), "record loss done")) return rc;
     }
     return OKGE_OK;
 }

@@ -107,7 +107,13 @@ __device__ __forceinline__ float point_score(const float *__restrict__ q /* LDS,
 // that issue everything whose address is known before waiting: (A) the row's CSR bounds and prefix ids, (B) the fold
 // operands, the group bounds / filter column of the thread's first item and the row-order counts, (C) the first answer
 // id, (D) the candidate rows.  Eval mode (no dropout: the entry point refuses it); 256 threads fold up to 512 columns.
-__device__ __forceinline__ void eval_points_block(const EvalPointsArgs &a, int b)
+//
+// LOSS (the validation loss, okge_evaluate_fused_loss): the label term of the row's loss from the same point scores.  The
+// row's labels are the UNION of its groups' ids (a column named twice counts once: an id is counted where it first occurs in
+// the row's id range, found by scanning the ids in front of it); their score sum (double) and number go to the row's SORTED
+// position, where the sweep leaves the row's other partials.
+template <bool LOSS>
+__device__ __forceinline__ void eval_points_block(const EvalPointsArgs &a, int b, const EvalLossPoints &el)
 {
     __shared__ float qs[512];
     __shared__ int red_pos[4];
@@ -204,12 +210,24 @@ __device__ __forceinline__ void eval_points_block(const EvalPointsArgs &a, int b
         const int64_t cid = cand_table_row(a.cand_ids, a.cand_first, loc, a.table_rows, p.id_err);
         return a.E + cid * d;
     };
+    double lpos = 0.0;
+    int lnpos = 0;
+    const int64_t row_j0 = LOSS && g_lo < g_hi ? a.grp_ptr[g_lo] : 0;      // the row's first id
     for (int64_t g = g0; g < g_hi; g += nthr) {
         float t = -INFINITY;                                 // (sharded: the maximum over THIS shard's ids; -inf if it has none)
         const int64_t lo = g == g0 ? j_lo : a.grp_ptr[g], hi = g == g0 ? j_hi : a.grp_ptr[g + 1];
         for (int64_t j = lo; j < hi; ++j) {
-            const float *row = cand_row(g == g0 && j == lo ? id0 : a.ids[j]);
-            if (row) t = fmaxf(t, point_score(qs, row, d, KB, vec_ok));
+            const int col = g == g0 && j == lo ? id0 : a.ids[j];
+            const float *row = cand_row(col);
+            if (row) {
+                const float x = point_score(qs, row, d, KB, vec_ok);
+                t = fmaxf(t, x);
+                if (LOSS) {
+                    bool first = true;
+                    for (int64_t jj = row_j0; jj < j; ++jj) first = first && a.ids[jj] != col;
+                    if (first) { lpos += (double)x; ++lnpos; }
+                }
+            }
         }
         a.true_out[g + (start - g_lo)] = t;                  // sorted group index
         a.group_row[g] = b;
@@ -217,6 +235,18 @@ __device__ __forceinline__ void eval_points_block(const EvalPointsArgs &a, int b
     for (int64_t f = f0; f < f_hi; f += nthr) {
         const float *row = cand_row(f == f0 ? fcol0 : a.filt_col[f]);
         a.filt_x[f] = row ? point_score(qs, row, d, KB, vec_ok) : __builtin_nanf("");      // NaN: not this shard's column
+    }
+    if (LOSS) {                                              // the threads' sums in a fixed order: lanes, then the four waves
+        __shared__ double red_lpos[4];
+        __shared__ int red_lnpos[4];
+        lpos = wave_sum(lpos);
+        lnpos = wave_sum(lnpos);
+        if ((tid & 63) == 0) { red_lpos[tid >> 6] = lpos; red_lnpos[tid >> 6] = lnpos; }
+        __syncthreads();
+        if (tid == 0) {
+            el.pos_sum[pos] = ((red_lpos[0] + red_lpos[1]) + red_lpos[2]) + red_lpos[3];
+            el.npos[pos] = red_lnpos[0] + red_lnpos[1] + red_lnpos[2] + red_lnpos[3];
+        }
     }
 }
 

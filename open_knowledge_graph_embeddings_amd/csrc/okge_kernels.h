@@ -46,7 +46,11 @@ constexpr int LDG = 68;            // leading dimension of the 64x64 G / X tile 
 constexpr int FUSED_THREADS = 512; // 8 waves, two per SIMD (fused_tile_kernel: score / stats / count sweep)
 constexpr int POS_CACHE = 512;     // positives of one candidate tile cached in LDS (more spill to global reads)
 
-enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4, MODE_TOPK = 5 };
+enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4, MODE_TOPK = 5,
+       // MODE_COUNT that also leaves, in `stats`, one float2 per (tile, row): the row's validation-loss partial over the tile
+       MODE_COUNT_BCE = 6, MODE_COUNT_KL = 7 };
+__host__ __device__ constexpr bool mode_counts(int mode) { return mode == MODE_COUNT || mode == MODE_COUNT_BCE || mode == MODE_COUNT_KL; }
+__host__ __device__ constexpr bool mode_count_loss(int mode) { return mode == MODE_COUNT_BCE || mode == MODE_COUNT_KL; }
 enum { LOSS_BCE = 0, LOSS_KL = 1 };
 enum { SC_COMPLEX = 0, SC_DISTMULT = 1, SC_BIAS_RELATION = 2, SC_BIAS_ENTITY = 3 };   // = enum okge_scorer
 // the data-bias scorers (model.py:281-350): the folded query row is a copy of ONE masked row
@@ -65,7 +69,7 @@ struct FusedArgs {
     float         *dC_slab;    // [gridDim.y][64 * tiles][16*KB] partial candidate gradients when the batch is split over blockIdx.y
     double        *loss_partial;
     float         *X;          // score mode
-    float         *stats;      // stats mode: float2 [tiles][Bpad]
+    float         *stats;      // stats mode: float2 [tiles][Bpad]; MODE_COUNT_BCE / _KL: the rows' loss partials, same layout
     // count mode (fused evaluation): per answer group of every row, how many of the tile's scores are greater than /
     // equal to the group's true score -> atomically added to rk_counts[group][2]
     const int64_t *rk_row_ptr; // [B + 1] groups of each row
@@ -340,6 +344,28 @@ struct EvalRanksArgs {
 };
 // either part may be absent (nullptr): points of one batch and ranks of ANOTHER share a launch in a run of batches
 hipError_t launch_eval_side(const EvalPointsArgs *pts, const EvalRanksArgs *rk, hipStream_t st);
+// ---- the validation loss of an evaluation batch (okge_evaluate_*_loss) ----
+// the label term, left by the points launch at the rows' SORTED positions: sum of the scores of the row's distinct positive
+// columns and their number
+struct EvalLossPoints { double *pos_sum; int32_t *npos; };
+// the same launch as launch_eval_side with the loss variant of the points part (a kernel of its own: the no-loss launch is
+// what it was)
+hipError_t launch_eval_side_loss(const EvalPointsArgs *pts, const EvalLossPoints *el, const EvalRanksArgs *rk, hipStream_t st);
+// Per row, the tiles' partials merged in tile order and joined with the label term (a launch over the rows; part == nullptr:
+// rows[] holds the rows' losses already); then, in a one-workgroup launch, the rows added in row order into *out.
+struct EvalLossReduce {
+    const float2  *part;        // [tiles][Bpad] (sum softplus, sum x) or (max, sum-exp) per (tile, row)
+    const double  *pos_sum;     // [B]
+    const int32_t *npos;        // [B]
+    double        *rows;        // [B] scratch: the rows' losses
+    double        *out;
+    double         smoothing;   // BCE label smoothing
+    int32_t        tiles, B, Bpad, N, kind;   // kind: LOSS_BCE / LOSS_KL
+};
+hipError_t launch_eval_loss_reduce(const EvalLossReduce &a, hipStream_t st);
+// the rows' losses of a materialised score block (one workgroup per row) -> rows[B]; launch_eval_loss_reduce adds them up
+hipError_t launch_block_loss_rows(const float *scores, int64_t ld, int B, int N, const int64_t *row_ptr, const int64_t *grp_ptr,
+                                  const int32_t *ids, int kind, double smoothing, double *rows, hipStream_t st);
 hipError_t launch_ranks(const float *scores, int64_t ld, int B, int N, const int64_t *filt_ptr,
                         const int32_t *filt_col, const int64_t *row_ptr, const int64_t *grp_ptr, const int32_t *ids,
                         int64_t *ranks, int col0, const float *true_in, float *true_out, int64_t *counts_out,

@@ -365,6 +365,32 @@ inline bool eval_layout(const Shape &s, int64_t n_groups, int64_t n_filter, Eval
     return true;
 }
 
+// The validation loss of an evaluation batch (okge_evaluate_*_loss) keeps its scratch BEHIND the call's own workspace, so
+// that eval_layout / score_layout answer as they do without a loss.  Fused: one float2 per (tile, row) from the sweep, the
+// label term (sum and number of the positives' scores) per row from the points launch, the rows' losses.  Materialising:
+// the rows' losses only.
+struct EvalLossLayout { size_t off_part, off_pos, off_npos, off_rows, total; };
+inline EvalLossLayout eval_loss_layout(const Shape &s, size_t eval_total)
+{
+    Arena ar(eval_total);
+    EvalLossLayout l;
+    l.off_part = ar.take((size_t)s.tiles * s.Bpad * 2 * sizeof(float));
+    l.off_pos = ar.take((size_t)s.Bpad * sizeof(double));
+    l.off_npos = ar.take((size_t)s.Bpad * sizeof(int32_t));
+    l.off_rows = ar.take((size_t)s.Bpad * sizeof(double));
+    l.total = ar.total();
+    return l;
+}
+struct BlockLossLayout { size_t off_rows, total; };
+inline BlockLossLayout block_loss_layout(int B, size_t score_total)
+{
+    Arena ar(score_total);
+    BlockLossLayout l;
+    l.off_rows = ar.take((size_t)std::max(B, 1) * sizeof(double));
+    l.total = ar.total();
+    return l;
+}
+
 // okge_adagrad_rows: the two sort-key buffers of a tensor of n > 0 occurrence rows
 struct RowsKeys { size_t off[2]; };
 inline RowsKeys take_rows_keys(Arena &ar, int64_t n)

@@ -3,6 +3,8 @@
 //                         also the two phases of the candidate-sharded evaluation            dataset.py:423-446
 //   rank_metrics_kernel   the meters of compute_metrics, kept on the device                   dataset.py:447-452
 //   eval_side_kernel      the fused evaluation's point scores and ranks-from-counts in one launch (okge_eval_device.h)
+//   eval_side_loss_kernel, eval_loss_rows_kernel, eval_loss_reduce_kernel, block_loss_rows_kernel
+//                         the validation loss of an evaluation batch (trainer.py:93-106, :263-271), fused and from a score block
 #include "okge_kernels.h"
 #include "okge_eval_device.h"
 
@@ -241,8 +243,136 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const int64_t *__rest
 // two batches; either part may be empty).
 __global__ __launch_bounds__(256) void eval_side_kernel(const EvalPointsArgs pts, const EvalRanksArgs rk, int n_points)
 {
-    if ((int)blockIdx.x < n_points) eval_points_block(pts, blockIdx.x);
+    if ((int)blockIdx.x < n_points) eval_points_block<false>(pts, blockIdx.x, EvalLossPoints{});
     else eval_ranks_block(rk, (int)blockIdx.x - n_points);
+}
+// ... and with the validation loss' label term from the points part
+__global__ __launch_bounds__(256) void eval_side_loss_kernel(const EvalPointsArgs pts, const EvalLossPoints el, const EvalRanksArgs rk,
+                                                             int n_points)
+{
+    if ((int)blockIdx.x < n_points) eval_points_block<true>(pts, blockIdx.x, el);
+    else eval_ranks_block(rk, (int)blockIdx.x - n_points);
+}
+
+// ---- the validation loss of an evaluation batch (trainer.py:93-106 in eval mode, unfiltered scores) ---------------------------
+// A row's loss from its label-free sums and its label term.  BCE (smoothing eps): S - (1 - eps) (P + X / N), S - P at eps = 0,
+// S = sum softplus(x), X = sum x, P = sum of x over the row's positives.  KL (unnormalised labels): npos lse - P; a row without
+// positives adds 0.
+__device__ __forceinline__ double eval_row_loss(int kind, double s_or_lse, double xsum, double pos_sum, int npos, int N, double eps)
+{
+    if (kind == LOSS_BCE) return eps > 0.0 ? s_or_lse - (1.0 - eps) * (pos_sum + xsum / (double)N) : s_or_lse - pos_sum;
+    return npos > 0 ? (double)npos * s_or_lse - pos_sum : 0.0;
+}
+
+// The rows' losses of a fused batch: thread b takes row b (the batch's sorted position: the sum below runs over all rows) and
+// merges the tiles' partials in tile order -- BCE in double; KL as a running (max, sum-exp) like kl_row_lse_kernel.  One
+// wave per workgroup, the loads of EVAL_LOSS_UNROLL tiles in flight ahead of their (ordered) adds: the merge is a chain of
+// memory round trips, not arithmetic.
+constexpr int EVAL_LOSS_UNROLL = 16;
+__global__ __launch_bounds__(64) void eval_loss_rows_kernel(const EvalLossReduce a)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    double S = 0.0, X = 0.0;
+    float m = -INFINITY, se = 0.f;
+    for (int t0 = 0; t0 < a.tiles; t0 += EVAL_LOSS_UNROLL) {
+        float2 p[EVAL_LOSS_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EVAL_LOSS_UNROLL; ++u)
+            p[u] = t0 + u < a.tiles ? a.part[(size_t)(t0 + u) * a.Bpad + b] : make_float2(a.kind == LOSS_BCE ? 0.f : -INFINITY, 0.f);
+#pragma unroll
+        for (int u = 0; u < EVAL_LOSS_UNROLL; ++u) {
+            if (t0 + u >= a.tiles) {
+                // (past the last tile: nothing to merge)
+            } else if (a.kind == LOSS_BCE) {
+                S += (double)p[u].x;
+                X += (double)p[u].y;
+            } else {
+                const float mn = fmaxf(m, p[u].x);
+                se = (m > -INFINITY ? se * __expf(m - mn) : 0.f) + (p[u].x > -INFINITY ? p[u].y * __expf(p[u].x - mn) : 0.f);
+                m = mn;
+            }
+        }
+    }
+    a.rows[b] = a.kind == LOSS_BCE ? eval_row_loss(LOSS_BCE, S, X, a.pos_sum[b], 0, a.N, a.smoothing)
+                                   : eval_row_loss(LOSS_KL, (double)m + log((double)se), 0.0, a.pos_sum[b], a.npos[b], a.N, 0.0);
+}
+
+// rows[0 .. B) added in row order into *out by ONE thread, from LDS (the workgroup stages 1024 rows at a time: the sum is a
+// chain of dependent adds, the loads must not be).  No atomics: the value is the same bits on every run.
+__global__ __launch_bounds__(256) void eval_loss_reduce_kernel(const EvalLossReduce a)
+{
+    constexpr int CH = 1024;
+    __shared__ double rs[CH];
+    double tot = 0.0;
+    for (int b0 = 0; b0 < a.B; b0 += CH) {
+        const int n = min(CH, a.B - b0);
+        for (int i = threadIdx.x; i < n; i += 256) rs[i] = a.rows[b0 + i];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < n; ++i) tot += rs[i];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *a.out = tot;
+}
+
+// The same row losses from a materialised score block: one workgroup per row.  Thread t sums columns t, t + 256, ... (double),
+// the threads are added lanes first, then the four waves: a fixed order.  Positives: the union of the row's group ids, an id
+// counted where it first occurs in the row's id range.
+__device__ __forceinline__ double block_sum256(double v, double *red)
+{
+    v = wave_sum(v);
+    __syncthreads();                                         // (red is reused)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__global__ __launch_bounds__(256) void block_loss_rows_kernel(const float *__restrict__ scores, int64_t ld, int N,
+                                                              const int64_t *__restrict__ row_ptr, const int64_t *__restrict__ grp_ptr,
+                                                              const int32_t *__restrict__ ids, int kind, double smoothing,
+                                                              double *__restrict__ rows)
+{
+    __shared__ double red[4];
+    __shared__ float redm[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float *row = scores + (size_t)b * ld;
+    const int64_t g_lo = row_ptr[b], g_hi = row_ptr[b + 1];
+    const int64_t j_lo = g_lo < g_hi ? grp_ptr[g_lo] : 0, j_hi = g_lo < g_hi ? grp_ptr[g_hi] : 0;
+    double pos = 0.0, np = 0.0;
+    for (int64_t j = j_lo + tid; j < j_hi; j += 256) {
+        const int col = ids[j];
+        if (col < 0 || col >= N) continue;                   // (ids are positions in the candidate list)
+        bool first = true;
+        for (int64_t jj = j_lo; jj < j; ++jj) first = first && ids[jj] != col;
+        if (first) { pos += (double)row[col]; np += 1.0; }
+    }
+    pos = block_sum256(pos, red);
+    np = block_sum256(np, red);
+    double v;
+    if (kind == LOSS_BCE) {
+        double S = 0.0, X = 0.0;
+        for (int n = tid; n < N; n += 256) {
+            const float x = row[n];
+            S += (double)(fmaxf(x, 0.f) + __builtin_amdgcn_logf(bce_terms(x).ope) * TILE_LN2);
+            X += (double)x;
+        }
+        S = block_sum256(S, red);
+        X = block_sum256(X, red);
+        v = eval_row_loss(LOSS_BCE, S, X, pos, 0, N, smoothing);
+    } else {
+        float m = -INFINITY;
+        for (int n = tid; n < N; n += 256) m = fmaxf(m, row[n]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        if ((tid & 63) == 0) redm[tid >> 6] = m;
+        __syncthreads();
+        m = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));
+        double se = 0.0;
+        for (int n = tid; n < N; n += 256) se += (double)__expf(row[n] - m);
+        se = block_sum256(se, red);
+        v = eval_row_loss(LOSS_KL, (double)m + log(se), 0.0, pos, (int)np, N, 0.0);
+    }
+    if (tid == 0) rows[b] = v;
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------
@@ -272,6 +402,37 @@ hipError_t launch_eval_side(const EvalPointsArgs *pts, const EvalRanksArgs *rk, 
     static const EvalPointsArgs no_pts = {};
     static const EvalRanksArgs no_rk = {};
     hipLaunchKernelGGL(eval_side_kernel, dim3(n_points + n_ranks), dim3(256), 0, st, pts ? *pts : no_pts, rk ? *rk : no_rk, n_points);
+    return hipGetLastError();
+}
+
+hipError_t launch_eval_side_loss(const EvalPointsArgs *pts, const EvalLossPoints *el, const EvalRanksArgs *rk, hipStream_t st)
+{
+    const int n_points = pts && el ? pts->Bpad : 0;
+    const int n_ranks = rk && rk->n_groups > 0 ? (int)((rk->n_groups + 3) / 4) : 0;
+    if (n_points + n_ranks <= 0) return hipSuccess;
+    static const EvalPointsArgs no_pts = {};
+    static const EvalLossPoints no_el = {};
+    static const EvalRanksArgs no_rk = {};
+    hipLaunchKernelGGL(eval_side_loss_kernel, dim3(n_points + n_ranks), dim3(256), 0, st, n_points ? *pts : no_pts, n_points ? *el : no_el,
+                       rk ? *rk : no_rk, n_points);
+    return hipGetLastError();
+}
+
+hipError_t launch_eval_loss_reduce(const EvalLossReduce &a, hipStream_t st)
+{
+    if (a.part && a.B > 0) {
+        hipLaunchKernelGGL(eval_loss_rows_kernel, dim3((a.B + 63) / 64), dim3(64), 0, st, a);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(eval_loss_reduce_kernel, dim3(1), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_loss_rows(const float *scores, int64_t ld, int B, int N, const int64_t *row_ptr, const int64_t *grp_ptr,
+                                  const int32_t *ids, int kind, double smoothing, double *rows, hipStream_t st)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(block_loss_rows_kernel, dim3(B), dim3(256), 0, st, scores, ld, N, row_ptr, grp_ptr, ids, kind, smoothing, rows);
     return hipGetLastError();
 }
 

@@ -98,6 +98,49 @@ __device__ __forceinline__ LossTerm loss_element(const FusedArgs &a, float xv, b
     return {l, gg * a.inv_norm};
 }
 
+// ---- validation loss of the counting sweep (MODE_COUNT_BCE / MODE_COUNT_KL) ---------------------------------------------------
+// The label-free part of a row's loss over the candidates a lane holds, as one float2 partial: BCE (sum softplus(x), sum x),
+// softplus(x) = max(x, 0) + log(1 + e^-|x|) from the BCE element's own bce_terms; KL (max, sum e^(x - max)) as MODE_STATS
+// forms it.  xm: the lane's scores with -inf at padding columns, which add nothing to either sum.
+template <int MODE, int NV>
+__device__ __forceinline__ float2 eval_loss_lane(const float (&xm)[NV])
+{
+    static_assert(MODE == MODE_COUNT_BCE || MODE == MODE_COUNT_KL, "a counting mode with a loss");
+    if (MODE == MODE_COUNT_BCE) {
+        float sp = 0.f, sx = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const bool v = xm[i] > -INFINITY;
+            sp += v ? fmaxf(xm[i], 0.f) + __builtin_amdgcn_logf(bce_terms(xm[i]).ope) * TILE_LN2 : 0.f;
+            sx += v ? xm[i] : 0.f;
+        }
+        return make_float2(sp, sx);
+    }
+    float m = -INFINITY, se = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) m = fmaxf(m, xm[i]);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) se += xm[i] > -INFINITY ? __expf(xm[i] - m) : 0.f;
+    return make_float2(m, se);
+}
+
+// two partials of one row -> one.  Symmetric bit for bit (a + b == b + a), so lanes that exchange partials agree.
+template <int MODE>
+__device__ __forceinline__ float2 eval_loss_merge(float2 p, float2 q)
+{
+    if (MODE == MODE_COUNT_BCE) return make_float2(p.x + q.x, p.y + q.y);
+    const float m = fmaxf(p.x, q.x);
+    return make_float2(m, (p.x > -INFINITY ? p.y * __expf(p.x - m) : 0.f) + (q.x > -INFINITY ? q.y * __expf(q.x - m) : 0.f));
+}
+
+// the four lanes c, c + 16, c + 32, c + 48 of a wave hold one row: all four leave with the row's partial of the wave
+template <int MODE>
+__device__ __forceinline__ float2 eval_loss_row4(float2 p)
+{
+    p = eval_loss_merge<MODE>(p, make_float2(__shfl_xor(p.x, 16), __shfl_xor(p.y, 16)));
+    return eval_loss_merge<MODE>(p, make_float2(__shfl_xor(p.x, 32), __shfl_xor(p.y, 32)));
+}
+
 // Loss partial of a workgroup of 8 waves: every wave's sum (in double) into red[8], thread 0 adds them up and stores.
 __device__ __forceinline__ void store_loss_partial(float lsum, double *red, double *dst, int tid)
 {

@@ -7,6 +7,7 @@
 //     MODE_STATS writes per-row (max, sum-exp) partials for the KL loss' log_softmax (openkge/trainer.py:99-100).
 //     MODE_COUNT (fused evaluation) compares X in registers with each row's true answer scores and adds the tile's
 //     {#greater, #equal} to per-group counters: the rank rule of dataset.py:436-446 without the (B, N) score block.
+//     MODE_COUNT_BCE / MODE_COUNT_KL: MODE_COUNT that also leaves each row's validation-loss partial over the tile.
 //     MODE_TOPK (link prediction) stages X as MODE_SCORE does -- the same bits -- and leaves per (tile, row) the tile's best k
 //     unfiltered candidates as (score, column) records (okge_topk.h); topk_merge_kernel (okge_topk.hip) folds them per row.
 //     The training step (score -> loss -> dCand) is fused_tile64_kernel (okge_train64.hip) up to slot size 256 and
@@ -164,6 +165,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
     float *Cs = reinterpret_cast<float *>(smem);              // [NT][LDK]
     float *Qs = Cs + NT * LDK;                                // [BC][LDK]
     float *Xs = Qs + BC * LDK;                                // [BC][LDG]   X tile staging (score mode), counters, stats partials
+    constexpr bool COUNT = mode_counts(MODE), COUNT_LOSS = mode_count_loss(MODE);
+    float2 *lpart = reinterpret_cast<float2 *>(Xs + BC * LDG);   // [BC] COUNT_LOSS only (fused_shmem_bytes): a row's loss partial of the wave pair's second half
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, s = lane >> 4;
     const int wq = w & 3, nh = w >> 2;
@@ -195,7 +198,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
     int rk_ng = 0, rk_ng_n = 0;
     float rk_t[RK_PRE];
     auto rk_fetch_rows = [&](int b0) {
-        if (MODE != MODE_COUNT) return;
+        if (!COUNT) return;
         const int b = b0 + 16 * wq + c;
         rk_glo_n = 0; rk_ng_n = 0;
         if (b < b_end) {
@@ -213,7 +216,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
         for (int it = 0; it < NQIT; ++it)
             if (qq + 8 * it < NQ) *reinterpret_cast<v4f *>(Qs + qr * LDK + 4 * (qq + 8 * it)) = qreg[it];
         if (b0 + BC < b_end) fetch_chunk(b0 + BC);
-        if (MODE == MODE_COUNT) {
+        if (COUNT) {
             rk_glo = rk_glo_n; rk_ng = rk_ng_n;
 #pragma unroll
             for (int jj = 0; jj < RK_PRE; ++jj)
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
                     for (int nb = 0; nb < NBW; ++nb)
-                        x[nb] = MODE == MODE_COUNT ? mfma16(bv[nb][j], av[j], x[nb])     // X^T block: lane = batch row
+                        x[nb] = COUNT ? mfma16(bv[nb][j], av[j], x[nb])     // X^T block: lane = batch row
                                                    : mfma16(av[j], bv[nb][j], x[nb]);
                 av = an;
 #pragma unroll
@@ -293,7 +296,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
                 }
             }
             __syncthreads();
-        } else if (MODE == MODE_COUNT) {
+        } else if (COUNT) {
             // fused evaluation: compare the block against the true scores of each row's answer groups and add the
             // {#greater, #equal} of this tile to the group's counters; the (B, N) score block is never written.
             // (dataset.py:436-446; the filter correction is applied by eval_ranks_block from point scores.)
@@ -313,6 +316,22 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
                 for (int i = 0; i < 4; ++i) xm[nb][i] = n0 + 16 * (nb0 + nb) + 4 * s + i < a.N ? x[nb][i] : -INFINITY;
             const int64_t g_lo = rk_glo;
             const int ng = rk_ng;
+            // the validation loss (COUNT_LOSS): the lane's partial of its row over its eight candidates, merged over the four
+            // lanes of the row in this wave; the second wave of the pair parks its partial, the first merges the two after the
+            // counting's barrier and stores one float2 per (tile, row) -- whichever way the counts themselves leave
+            float2 lp = make_float2(0.f, 0.f);
+            if (COUNT_LOSS) {
+                constexpr int LM = COUNT_LOSS ? MODE : MODE_COUNT_BCE;
+                const float xf[4 * NBW] = {xm[0][0], xm[0][1], xm[0][2], xm[0][3], xm[1][0], xm[1][1], xm[1][2], xm[1][3]};
+                lp = eval_loss_row4<LM>(eval_loss_lane<LM>(xf));
+                if (nh == 1 && s == 0) lpart[16 * wq + c] = lp;
+            }
+            auto loss_store = [&]() {
+                constexpr int LM = COUNT_LOSS ? MODE : MODE_COUNT_BCE;
+                const int b = b0 + 16 * wq + c;
+                if (COUNT_LOSS && nh == 0 && s == 0 && b < b_end)
+                    reinterpret_cast<float2 *>(a.stats)[(size_t)blockIdx.x * a.Bpad + b] = eval_loss_merge<LM>(lp, lpart[16 * wq + c]);
+            };
             // a row's 64 candidates of this tile sit in eight lanes: c, c+16, c+32, c+48 of the waves (wq, 0) and (wq, 1).
             // Counters in LDS: all eight add atomically.  Otherwise (a chunk with more groups than the LDS tile holds, or
             // the atomics path of very large batches): the wave pair takes turns -- first half stores, second half adds.
@@ -361,9 +380,11 @@ __global__ __launch_bounds__(FUSED_THREADS) void fused_tile_kernel(const FusedAr
                 count_pass(false);
                 __syncthreads();
                 for (int k = tid; k < (int)(gc_hi - gc_lo); k += FUSED_THREADS) slab_row[gc_lo + k] = cnt[k];
+                loss_store();
             } else {
                 if (nh == 0) count_pass(false);
                 __syncthreads();
+                loss_store();
                 if (nh == 1) count_pass(true);
                 __syncthreads();
             }
@@ -539,6 +560,8 @@ static hipError_t launch_fused_m(int mode, const FusedArgs &a, dim3 grid, size_t
         case MODE_SCORE: return launch_fused_t<KB, MODE_SCORE>(a, grid, shmem, st);
         case MODE_STATS: return launch_fused_t<KB, MODE_STATS>(a, grid, shmem, st);
         case MODE_COUNT: return launch_fused_t<KB, MODE_COUNT>(a, grid, shmem, st);
+        case MODE_COUNT_BCE: return launch_fused_t<KB, MODE_COUNT_BCE>(a, grid, shmem + BC * sizeof(float2), st);   // + lpart
+        case MODE_COUNT_KL:  return launch_fused_t<KB, MODE_COUNT_KL>(a, grid, shmem + BC * sizeof(float2), st);
         case MODE_TOPK:  return launch_fused_t<KB, MODE_TOPK>(a, grid, shmem, st);
         default:         return hipErrorInvalidValue;      // training: fused_tile64_kernel
     }

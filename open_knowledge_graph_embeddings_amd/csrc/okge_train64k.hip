@@ -60,7 +60,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
     constexpr int D16 = 16 * KB, KH = 16 * KBW;                 // padded slot size, columns of one half
     constexpr int NQ = 4 * KB, QG = 16, NQIT = NQ / QG;         // float4 per row; staging: 16 column groups per row
     static_assert(KB % 8 == 0, "the column split needs whole quads of 16-column blocks per wave");
-    static_assert(MODE == MODE_TRAIN_BCE || MODE == MODE_TRAIN_KL || MODE == MODE_SCORE || MODE == MODE_STATS || MODE == MODE_COUNT,
+    static_assert(MODE == MODE_TRAIN_BCE || MODE == MODE_TRAIN_KL || MODE == MODE_SCORE || MODE == MODE_STATS || mode_counts(MODE),
                   "training kernel, or the score / statistics / counting sweep");
     // MODE_SCORE / MODE_STATS: the same sweep stops after the score blocks and writes X, or per (16-candidate block, row) the
     // (max, sum-exp) pairs of the KL loss' log-softmax (kl_row_lse_kernel merges them).
@@ -69,7 +69,10 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
     // is lane-local; the chunk's packed {#greater | #equal << 16} counters are summed in LDS (the training modes' keep-flag /
     // positives cache is free here) and leave as one coalesced store per (tile, chunk), as in fused_tile_kernel<count>.
     // Same products in the same k order as MODE_SCORE: the counts equal those of the materialised scores bit for bit.
+    // MODE_COUNT_BCE / MODE_COUNT_KL: MODE_COUNT that also leaves, per (tile, row), the row's validation-loss partial over the
+    // tile's candidates in a.stats (the label bit words are free in the counting modes: they carry the partials between waves).
     constexpr bool TRAIN = MODE == MODE_TRAIN_BCE || MODE == MODE_TRAIN_KL;
+    constexpr bool COUNT = mode_counts(MODE), COUNT_LOSS = mode_count_loss(MODE);
     const int d = a.d;
     float *Qb = reinterpret_cast<float *>(smem);                              // [2][32][LDK]  (end: [64][LDK] gradient stage)
     v4f *xs = reinterpret_cast<v4f *>(Qb + 2 * BCK * LDK);                    // [8 waves][2 row groups][64 lanes]
@@ -79,6 +82,8 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
     uint32_t *posc = reinterpret_cast<uint32_t *>(keepb + NTK * KEEP_LD);     // [POS_CACHE] (row << 6 | col)
     uint32_t *cnt = reinterpret_cast<uint32_t *>(keepb);                      // MODE_COUNT: [CNT_CAP] packed counters of a chunk's groups
     constexpr int CNT_CAP = (NTK * KEEP_LD) / 4 + POS_CACHE;
+    float2 *lpart = reinterpret_cast<float2 *>(ybits3);                      // COUNT_LOSS: [3 waves blk = 1 .. 3][32 rows] loss partials
+    static_assert(3 * BCK * sizeof(float2) <= 3 * 2 * BCK * sizeof(uint32_t), "the loss partials fit the label bit words");
 
     const bool vec_ok = (d & 3) == 0;
     const uint32_t dstep = a.drop_c.enabled ? drop_step(a.drop_c) : 0u;   // before the loads whose latency hides the masks
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
     int rk_ng = 0, rk_ng_n = 0;
     float rk_t[RK_PRE];
     auto rk_fetch_rows = [&](int b0) {
-        if (MODE != MODE_COUNT) return;
+        if (!COUNT) return;
         const int b = b0 + 16 * ks + c;
         rk_glo_n = 0; rk_ng_n = 0;
         if (b < b_end) {
@@ -242,7 +247,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
         const float *Qc = Qb + buf * (BCK * LDK);
         float *Qn = Qb + (buf ^ 1) * (BCK * LDK);
         if (b0 > b_begin) __syncthreads();   // chunk parked by everyone (during the previous chunk); the other buffer is free
-        if (MODE == MODE_COUNT) {
+        if (COUNT) {
             rk_glo = rk_glo_n; rk_ng = rk_ng_n;
 #pragma unroll
             for (int jj = 0; jj < RK_PRE; ++jj)
@@ -275,7 +280,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (MODE == MODE_COUNT) {           // X^T blocks: lane (c, s) = row c (+ 16), candidates 4 s + i
+                    if (COUNT) {                        // X^T blocks: lane (c, s) = row c (+ 16), candidates 4 s + i
                         x0 = mfma16(breg[r][j], a00[j], x0);
                         x1 = mfma16(breg[r][j], a01[j], x1);
                     } else {
@@ -294,7 +299,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
         __syncthreads();
         x0 += xs[((w ^ 4) * 2 + 0) * 64 + lane];             // a + b == b + a: both partners hold the same bits
         x1 += xs[((w ^ 4) * 2 + 1) * 64 + lane];
-        if (MODE == MODE_COUNT) {
+        if (COUNT) {
             // partner ks takes row group ks: row b0 + 16 ks + c against candidates n0 + 16 blk + 4 s + i; the row's 64
             // candidates of this tile sit in 16 lanes (s = 0 .. 3 of the four waves blk = 0 .. 3 of this ks)
             const v4f xv = ks == 0 ? x0 : x1;
@@ -305,6 +310,25 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
             const int ng = rk_ng;
             const bool in_lds = a.rk_slab && gc_hi - gc_lo <= CNT_CAP;
             uint32_t *slab_row = a.rk_slab ? a.rk_slab + (size_t)tile * a.rk_ngroups : nullptr;
+            // the validation loss (COUNT_LOSS): the lane's partial of its row over its four candidates, merged over the four
+            // lanes of the row in this wave; waves blk = 1 .. 3 park theirs, wave blk = 0 merges them in that order after the
+            // counting's first barrier and stores one float2 per (tile, row) -- whichever way the counts themselves leave
+            float2 lp = make_float2(0.f, 0.f);
+            if (COUNT_LOSS) {
+                constexpr int LM = COUNT_LOSS ? MODE : MODE_COUNT_BCE;
+                lp = eval_loss_row4<LM>(eval_loss_lane<LM>(xm));
+                if (blk > 0 && s == 0) lpart[(blk - 1) * BCK + 16 * ks + c] = lp;
+            }
+            auto loss_store = [&]() {
+                constexpr int LM = COUNT_LOSS ? MODE : MODE_COUNT_BCE;
+                const int b = b0 + 16 * ks + c;
+                if (COUNT_LOSS && blk == 0 && s == 0 && b < b_end) {
+                    float2 v = lp;
+#pragma unroll
+                    for (int o = 0; o < 3; ++o) v = eval_loss_merge<LM>(v, lpart[o * BCK + 16 * ks + c]);
+                    reinterpret_cast<float2 *>(a.stats)[(size_t)tile * a.Bpad + b] = v;
+                }
+            };
             auto count_pass = [&](bool add) {
                 for (int j = 0; __builtin_amdgcn_ballot_w64(j < ng) != 0; ++j) {
                     float t = j < ng && j >= RK_PRE ? a.rk_true[g_lo + j] : __builtin_nanf("");
@@ -334,6 +358,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
                 count_pass(false);
                 __syncthreads();
                 for (int k = tid; k < (int)(gc_hi - gc_lo); k += TK_THREADS) slab_row[gc_lo + k] = cnt[k];
+                loss_store();
             } else {
                 // more groups in the chunk than the LDS counters hold (or the atomics path of very large batches): the four
                 // waves that share a row take turns -- the first stores, the others add
@@ -341,6 +366,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
                 for (int turn = 0; turn < 4; ++turn) {
                     if (blk == turn) count_pass(turn > 0);
                     __syncthreads();
+                    if (turn == 0) loss_store();
                 }
             }
             if (b0 + BCK < b_end) {
@@ -490,10 +516,12 @@ static hipError_t launch64k_t(const FusedArgs &a, dim3 grid, hipStream_t st)
 hipError_t launch_fused64k(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st)
 {
     const dim3 grid(grid_x, grid_y);
-    if ((mode != MODE_TRAIN_BCE && mode != MODE_TRAIN_KL && mode != MODE_SCORE && mode != MODE_STATS && mode != MODE_COUNT) || a.KB != 32)
+    if ((mode != MODE_TRAIN_BCE && mode != MODE_TRAIN_KL && mode != MODE_SCORE && mode != MODE_STATS && !mode_counts(mode)) || a.KB != 32)
         return hipErrorInvalidValue;
     if (mode == MODE_SCORE) return launch64k_t<32, MODE_SCORE>(a, grid, st);
     if (mode == MODE_COUNT) return launch64k_t<32, MODE_COUNT>(a, grid, st);
+    if (mode == MODE_COUNT_BCE) return launch64k_t<32, MODE_COUNT_BCE>(a, grid, st);
+    if (mode == MODE_COUNT_KL) return launch64k_t<32, MODE_COUNT_KL>(a, grid, st);
     if (mode == MODE_STATS) return launch64k_t<32, MODE_STATS>(a, grid, st);
     return mode == MODE_TRAIN_KL ? launch64k_t<32, MODE_TRAIN_KL>(a, grid, st) : launch64k_t<32, MODE_TRAIN_BCE>(a, grid, st);
 }

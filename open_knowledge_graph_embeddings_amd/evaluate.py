@@ -24,6 +24,28 @@ def _meters(a):
     return out, n
 
 
+def _check_loss(who, loss, scorer):
+    """the `loss` keyword of the evaluators: None (the `loss` meter stays empty, as without the keyword), 'bce' or 'kl'"""
+    if loss is None:
+        return None
+    if loss not in N.LOSSES:
+        raise ValueError(f"{who}: unknown loss {loss!r} ('bce', 'kl' or None)")
+    if isinstance(scorer, str) and scorer not in N.SCORERS:
+        raise NotImplementedError(f"{who}: no validation loss for the {scorer!r} scorer (the lookup scorers {sorted(N.SCORERS)} have one)")
+    return loss
+
+
+def _loss_meter(out, batch_losses, elems):
+    """MetricResult['loss'] as Trainer.compute_one_batch(training=False) fills it over a pass: loss.update(L / (B N), B N) per
+    batch, i.e. the average sum L / sum B N with count sum B N.  The per-batch sums are added on the host in batch order."""
+    total = 0.0
+    for v in batch_losses.cpu().tolist():
+        total += v
+    n = sum(elems)
+    if n:
+        out["loss"].update(total / n, n)
+
+
 class FusedEvaluator:
     """The evaluation loop on okge_evaluate_fused_batches: no (B, N) score block, no host read until the end.  The library
     issues a run of batches per call (`run_len`; the first runs are short so that the device starts early): batch i on
@@ -34,9 +56,13 @@ class FusedEvaluator:
     (those cost ~10 us each; round 2's first design paid one per batch).  Measured per batch at the FB15k-237 shape:
     1 chain 0.056 ms, 2 chains 0.046, 3 chains 0.043, 4 chains 0.043-0.048.
     Slot sizes up to 512 (round 4: above 256 on the register-tile kernel's counting mode), eval mode; PipelinedEvaluator
-    (materialised scores) covers dropout and candidate tables."""
+    (materialised scores) covers dropout and candidate tables.
+    loss='bce' / 'kl' (label_smoothing: BCE's): the same sweep also yields every batch's validation loss -- run() then fills
+    MetricResult['loss'] like the reference's compute_one_batch(training=False) and keeps the per-batch sums in
+    self.batch_losses (float64, batches in order).  Bit-identical from run to run and across n_streams / run_len."""
 
-    def __init__(self, E, R, scorer, engine=None, run_len=48, two_streams=True, n_streams=None, collect_ranks=False):
+    def __init__(self, E, R, scorer, engine=None, run_len=48, two_streams=True, n_streams=None, collect_ranks=False,
+                 loss=None, label_smoothing=0.0):
         if E.shape[1] > H.TILE_MAX_SLOT:
             raise NotImplementedError(f"FusedEvaluator: the fused evaluation stops at slot size {H.TILE_MAX_SLOT}; PipelinedEvaluator "
                                       f"evaluates slot sizes up to {H.WIDE_MAX_SLOT}")
@@ -44,6 +70,8 @@ class FusedEvaluator:
         # collect_ranks: keep every answer group's rank (self.ranks after run(): int64, batches in order, groups in the
         # batch's row / group order) instead of treating the ranks as scratch -- for parity tests and error analysis
         self.collect_ranks, self.ranks, self._kept = bool(collect_ranks), None, []
+        self.loss, self.label_smoothing = _check_loss("FusedEvaluator", loss, scorer), float(label_smoothing)
+        self.batch_losses, self._losses, self._elems = None, [], []
         self.device = E.device
         self.engine = engine or H.HotPath(self.device)
         self.run_len = int(run_len)
@@ -63,7 +91,10 @@ class FusedEvaluator:
         x.batch, x.cand = pb, c
         x.filt_ptr, x.filt_col, x.n_filter = cb.filt_ptr.data_ptr(), (cb.filt_col.data_ptr() if n_filter else None), n_filter
         x.row_ptr, x.grp_ptr, x.ids, x.n_groups = cb.row_ptr.data_ptr(), cb.grp_ptr.data_ptr(), cb.ids.data_ptr(), n_groups
-        need = int(eng.lib.okge_eval_workspace_bytes(b.B, c.n, self._t.d, n_groups, n_filter))
+        size = eng.lib.okge_eval_workspace_bytes if self.loss is None else eng.lib.okge_eval_loss_workspace_bytes
+        need = int(size(b.B, c.n, self._t.d, n_groups, n_filter))
+        if self.loss is not None:
+            self._elems.append(b.B * c.n)
         return need, n_groups, keep
 
     def _issue(self, n, need, n_groups, acc, stream_h):
@@ -89,6 +120,15 @@ class FusedEvaluator:
         handles = (ctypes.c_void_p * self.n_streams)(stream_h, *[ctypes.c_void_p(x.cuda_stream) for x in self.sides])
         # (the library orders the current stream behind the other streams' share at the end of every call; letting the
         #  chains run on across calls instead measured no faster)
+        if self.loss is not None:                            # batch i of the run stores its loss in element i
+            out = torch.zeros(n, dtype=torch.float64, device=self.device)
+            self._losses.append(out)
+            el = N.eval_loss(self.loss, self.label_smoothing, out.data_ptr())
+            N.check(self.engine.lib.okge_evaluate_fused_batches_loss(ctypes.byref(self._t), self._arr, n, ranks.data_ptr(),
+                                                                     acc.data_ptr(), self._ws.data_ptr(), self._ws.numel(), handles,
+                                                                     self.n_streams, ctypes.byref(el)),
+                    "okge_evaluate_fused_batches_loss")
+            return
         N.check(self.engine.lib.okge_evaluate_fused_batches(ctypes.byref(self._t), self._arr, n, ranks.data_ptr(),
                                                             acc.data_ptr(), self._ws.data_ptr(), self._ws.numel(), handles,
                                                             self.n_streams), "okge_evaluate_fused_batches")
@@ -96,7 +136,7 @@ class FusedEvaluator:
     def run(self, batches):
         """batches: iterable of dataset.CollatedBatch built with is_training_data=False -> (MetricResult, #groups)"""
         acc = torch.zeros(7, dtype=torch.float64, device=self.device)
-        self._kept = []
+        self._kept, self._losses, self._elems = [], [], []
         main = torch.cuda.current_stream(self.device)
         stream_h = ctypes.c_void_p(main.cuda_stream)
         n, need, n_groups, run = 0, 0, 0, min(2 * self.n_streams, self.run_len)   # two batches per chain, then x4:
@@ -116,6 +156,10 @@ class FusedEvaluator:
         if self.collect_ranks:
             self.ranks = torch.cat(self._kept) if self._kept else torch.zeros(0, dtype=torch.int64, device=self.device)
             self._kept = []
+        if self.loss is not None:
+            self.batch_losses = torch.cat(self._losses) if self._losses else torch.zeros(0, dtype=torch.float64, device=self.device)
+            _loss_meter(out[0], self.batch_losses, self._elems)
+            self._losses = []
         return out
 
 
@@ -125,11 +169,14 @@ class PipelinedEvaluator:
     eval mode.  Batch i runs on stream i % n_streams with that stream's own score block, rank buffer and query workspace:
     independent chains [scores] [ranks] [meters], no cross-stream wait per batch (each costs ~10 us of queue latency on
     this hardware; the first version ordered a scoring and a ranking stream with two events per batch), so the ranking of
-    one batch runs beside the scoring of the next ones.  Meters accumulate on the device; one host read at the end."""
+    one batch runs beside the scoring of the next ones.  Meters accumulate on the device; one host read at the end.
+    loss / label_smoothing: as FusedEvaluator; the loss is reduced from the batch's score block (okge_evaluate_batch_loss)."""
 
-    def __init__(self, E, R, scorer, engine=None, n_streams=3, collect_ranks=False):
+    def __init__(self, E, R, scorer, engine=None, n_streams=3, collect_ranks=False, loss=None, label_smoothing=0.0):
         self.E, self.R, self.scorer = E, R, scorer
         self.collect_ranks, self.ranks = bool(collect_ranks), None          # as FusedEvaluator
+        self.loss, self.label_smoothing = _check_loss("PipelinedEvaluator", loss, scorer), float(label_smoothing)
+        self.batch_losses = None
         self.device = E.device
         self.engine = engine or H.HotPath(self.device)
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(max(1, int(n_streams)))]
@@ -164,6 +211,7 @@ class PipelinedEvaluator:
         for st in self.streams:
             st.wait_stream(main)                             # tables / batches were produced on the current stream
         keep, kept = [], []                                  # every batch stays referenced until the chains have joined
+        losses, elems, el = [], [], None                     # one double per batch, in blocks of 64 (batch i: element i % 64)
         for i, cb in enumerate(batches):
             slot = i % len(self.streams)
             st = self.streams[slot]
@@ -185,12 +233,29 @@ class PipelinedEvaluator:
             pb.n_po, pb.n_sp = b.n_po, b.n_sp
             c.ids = b.cand_ids.data_ptr() if b.cand_ids is not None else None
             c.first_id, c.n = b.cand_first, cb.n_cand
-            need = int(eng.lib.okge_score_workspace_bytes(b.B, self._t.d))
+            need = int(eng.lib.okge_score_workspace_bytes(b.B, self._t.d) if self.loss is None else
+                       eng.lib.okge_evaluate_batch_loss_workspace_bytes(b.B, self._t.d))
             if self._ws[slot] is None or self._ws[slot].numel() < need:
                 st.synchronize()
                 self._ws[slot] = torch.empty(need, dtype=torch.uint8, device=self.device)
                 self._ws[slot].record_stream(st)
             sh = ctypes.c_void_p(st.cuda_stream)
+            if self.loss is not None:
+                if i % 64 == 0:
+                    losses.append(torch.zeros(64, dtype=torch.float64, device=self.device))
+                    for s2 in self.streams:
+                        losses[-1].record_stream(s2)
+                        s2.wait_stream(main)                 # (the block is cleared on the current stream)
+                elems.append(b.B * cb.n_cand)
+                el = N.eval_loss(self.loss, self.label_smoothing, losses[-1][i % 64:].data_ptr())
+                N.check(eng.lib.okge_evaluate_batch_loss(ctypes.byref(self._t), ctypes.byref(pb), ctypes.byref(c),
+                                                         cb.filt_ptr.data_ptr(), cb.filt_col.data_ptr() if cb.filt_col.numel() else None,
+                                                         cb.row_ptr.data_ptr(), cb.grp_ptr.data_ptr(), cb.ids.data_ptr(), n_groups,
+                                                         x.data_ptr(), x.stride(0), rk.data_ptr(), acc[slot].data_ptr(),
+                                                         self._ws[slot].data_ptr(), self._ws[slot].numel(), sh, sh, ctypes.byref(el)),
+                        "okge_evaluate_batch_loss")
+                keep.append(cb)
+                continue
             # one library call: scores, ranks and meters of the batch, all in the chain's stream order
             N.check(eng.lib.okge_evaluate_batch(ctypes.byref(self._t), ctypes.byref(pb), ctypes.byref(c),
                                                 cb.filt_ptr.data_ptr(), cb.filt_col.data_ptr() if cb.filt_col.numel() else None,
@@ -204,4 +269,9 @@ class PipelinedEvaluator:
         if self.collect_ranks:
             self.ranks = torch.cat(kept) if kept else torch.zeros(0, dtype=torch.int64, device=self.device)
         del keep
-        return _meters(a)
+        out = _meters(a)
+        if self.loss is not None:
+            self.batch_losses = (torch.cat(losses)[:len(elems)] if losses else
+                                 torch.zeros(0, dtype=torch.float64, device=self.device))
+            _loss_meter(out[0], self.batch_losses, elems)
+        return out

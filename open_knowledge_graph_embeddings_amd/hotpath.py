@@ -737,13 +737,30 @@ class HotPath:
         return ranks
 
     def evaluate_batch(self, E, R, scorer, batch: PrefixBatch, filt_ptr, filt_col, row_ptr, grp_ptr, ids, scores, ranks,
-                       acc, rank_stream):
+                       acc, rank_stream, loss=None, label_smoothing=0.0):
         """score (current stream) -> filtered ranks -> meters (rank_stream) in one library call; `scores` (B, >=N) and
-        `ranks` (>= n_groups int64) are caller buffers, `acc` 7 device doubles."""
+        `ranks` (>= n_groups int64) are caller buffers, `acc` 7 device doubles.  loss 'bce' / 'kl': also the batch's
+        validation loss (okge_evaluate_batch_loss), returned as a one-element float64 device tensor written in rank_stream's
+        order; None otherwise."""
         pb, c, keep = self._batch(batch)
         t = self._tables(E, R, scorer)
-        ws = self.workspace(batch.B, c.n, t.d, "score")
         n_groups = int(grp_ptr.numel()) - 1
+        if loss is not None:
+            need = int(self.lib.okge_evaluate_batch_loss_workspace_bytes(batch.B, t.d))
+            if need == 0:
+                raise N.OkgeError(f"invalid problem size B={batch.B} N={c.n} d={t.d}")
+            ws = self._grow(need)
+            out = torch.zeros(1, dtype=torch.float64, device=self.device)
+            el = N.eval_loss(loss, label_smoothing, out.data_ptr())
+            N.check(self.lib.okge_evaluate_batch_loss(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), filt_ptr.data_ptr(),
+                                                      _ptr(filt_col), row_ptr.data_ptr(), grp_ptr.data_ptr(), ids.data_ptr(),
+                                                      n_groups, scores.data_ptr(), scores.stride(0), ranks.data_ptr(),
+                                                      acc.data_ptr(), ws.data_ptr(), self._ws_bytes, self._stream(),
+                                                      ctypes.c_void_p(rank_stream.cuda_stream), ctypes.byref(el)),
+                    "okge_evaluate_batch_loss")
+            del keep
+            return out
+        ws = self.workspace(batch.B, c.n, t.d, "score")
         N.check(self.lib.okge_evaluate_batch(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), filt_ptr.data_ptr(),
                                              _ptr(filt_col), row_ptr.data_ptr(), grp_ptr.data_ptr(), ids.data_ptr(),
                                              n_groups, scores.data_ptr(), scores.stride(0), ranks.data_ptr(),
@@ -751,18 +768,32 @@ class HotPath:
                                              ctypes.c_void_p(rank_stream.cuda_stream)), "okge_evaluate_batch")
         del keep
 
-    def evaluate_fused(self, E, R, scorer, batch: PrefixBatch, filt_ptr, filt_col, row_ptr, grp_ptr, ids, ranks=None, acc=None):
+    def evaluate_fused(self, E, R, scorer, batch: PrefixBatch, filt_ptr, filt_col, row_ptr, grp_ptr, ids, ranks=None, acc=None,
+                       loss=None, label_smoothing=0.0):
         """filtered ranks + meters of one evaluation batch without the (B, N) score block (okge_evaluate_fused): ranks
-        (int64 per answer group, bit-equal to score() + filtered_ranks()) and acc (7 device doubles, accumulated)."""
+        (int64 per answer group, bit-equal to score() + filtered_ranks()) and acc (7 device doubles, accumulated).
+        loss 'bce' / 'kl': the same sweep also yields the batch's validation loss (okge_evaluate_fused_loss; the sum over the
+        (B, N) elements, not divided) -> (ranks, acc, loss) with loss a one-element float64 device tensor."""
         pb, c, keep = self._batch(batch)
         t = self._tables(E, R, scorer)
         n_groups, n_filter = int(grp_ptr.numel()) - 1, int(filt_col.numel())
-        need = int(self.lib.okge_eval_workspace_bytes(batch.B, c.n, t.d, n_groups, n_filter))
+        size = self.lib.okge_eval_workspace_bytes if loss is None else self.lib.okge_eval_loss_workspace_bytes
+        need = int(size(batch.B, c.n, t.d, n_groups, n_filter))
         self._grow(need)
         if ranks is None:
             ranks = torch.empty(max(n_groups, 1), dtype=torch.int64, device=self.device)
         if acc is None:
             acc = torch.zeros(7, dtype=torch.float64, device=self.device)
+        if loss is not None:
+            out = torch.zeros(1, dtype=torch.float64, device=self.device)
+            el = N.eval_loss(loss, label_smoothing, out.data_ptr())
+            N.check(self.lib.okge_evaluate_fused_loss(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), filt_ptr.data_ptr(),
+                                                      _ptr(filt_col) if n_filter else None, n_filter, row_ptr.data_ptr(),
+                                                      grp_ptr.data_ptr(), _ptr(ids), n_groups, ranks.data_ptr(), acc.data_ptr(),
+                                                      self._ws.data_ptr(), self._ws_bytes, self._stream(), ctypes.byref(el)),
+                    "okge_evaluate_fused_loss")
+            del keep
+            return ranks[:n_groups], acc, out
         N.check(self.lib.okge_evaluate_fused(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), filt_ptr.data_ptr(),
                                              _ptr(filt_col) if n_filter else None, n_filter, row_ptr.data_ptr(),
                                              grp_ptr.data_ptr(), ids.data_ptr(), n_groups, ranks.data_ptr(), acc.data_ptr(),

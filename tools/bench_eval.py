@@ -1,20 +1,34 @@
 #!/usr/bin/env python3
-"""Per-kernel timing of one evaluation batch (S-FB shape) on the fused and the materialising path."""
+"""Per-kernel timing of one evaluation batch (S-FB shape) on the fused and the materialising path, with and without the
+validation loss.  `--root PATH` measures the package of another checkout (built there) with this script, for A/B runs; legs
+that checkout cannot run (no `loss` keyword) are skipped.  Legs:
+  fused / fused-one-group / pipelined          the evaluators without a loss
+  fused-bce / fused-kl / pipelined-bce         the same with loss=...
+  fused+loss_only                              what a caller without the keyword does: the fused evaluator, then
+                                               forward_backward(loss_only=True) of every batch (a second sweep)
+ms_per_batch_640: steady state over 640 batches; windows_640: `--windows` repeats of it (their spread is the noise floor)."""
+import argparse
+import dataclasses
+import inspect
 import json
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+ap = argparse.ArgumentParser()
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--windows", type=int, default=5)
+ap.add_argument("--legs", default="")
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
 import bench  # noqa: E402
 from open_knowledge_graph_embeddings_amd import hotpath as H, synthetic  # noqa: E402
 from open_knowledge_graph_embeddings_amd.dataset import CollatedBatch  # noqa: E402
 from open_knowledge_graph_embeddings_amd.evaluate import FusedEvaluator, PipelinedEvaluator  # noqa: E402
 
-import dataclasses  # noqa: E402
 w = synthetic.WORKLOADS["S-FB"]
 if os.environ.get("OKGE_EVAL_D"):            # e.g. OKGE_EVAL_D=512 OKGE_EVAL_SCORER=distmult: configs[2]'s table shape
     w = dataclasses.replace(w, d=int(os.environ["OKGE_EVAL_D"]), scorer=os.environ.get("OKGE_EVAL_SCORER", w.scorer))
@@ -27,29 +41,48 @@ t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
 csr = [t(hb[k]) for k in ("filt_ptr", "filt_col", "row_ptr", "grp_ptr", "ids")]
 cb = CollatedBatch(eb, float(w.B * w.N), float(hb["n_pos"]), w.N, row_ptr=csr[2], grp_ptr=csr[3], ids=csr[4], filt_ptr=csr[0], filt_col=csr[1])
 eng = H.HotPath(dev)
-import numpy as np  # noqa: E402
 # floor of the sweep: one group in the whole batch (the counting loop runs for one row only)
 one = CollatedBatch(eb, 1.0, 1.0, w.N, row_ptr=t(np.concatenate([[0], np.ones(w.B, np.int64)])), grp_ptr=t(np.asarray([0, 1], np.int64)),
                     ids=t(np.asarray([5], np.int32)), filt_ptr=t(np.zeros(w.B + 1, np.int64)), filt_col=t(np.zeros(0, np.int32)))
-for name, cls in (("fused", FusedEvaluator), ("fused-one-group", FusedEvaluator), ("pipelined", PipelinedEvaluator)):
-    if name == "fused-one-group":
-        cb_keep, cb = cb, one
-    elif name == "pipelined":
-        cb = cb_keep
-    ev = cls(Et, Rt, w.scorer, engine=eng)
-    ev.run([cb] * 192)          # fresh streams are slow until the runtime's per-queue pools have grown to a full run's depth
+# the labels of the loss_only leg: the union of each row's answer ids, as forward_backward takes them (sorted by column)
+rp, gp, ids = (hb[k] for k in ("row_ptr", "grp_ptr", "ids"))
+coords = np.unique(np.stack([ids, np.repeat(np.arange(w.B), gp[rp[1:]] - gp[rp[:-1]])], 1), axis=0)
+labelled = dataclasses.replace(eb, pos_row=t(coords[:, 1].astype(np.int32)), pos_col=t(coords[:, 0].astype(np.int32)))
+has_loss = "loss" in inspect.signature(FusedEvaluator.__init__).parameters
+
+LEGS = [("fused", FusedEvaluator, cb, {}), ("fused-one-group", FusedEvaluator, one, {}), ("pipelined", PipelinedEvaluator, cb, {}),
+        ("fused+loss_only", FusedEvaluator, cb, {})]
+if has_loss:
+    LEGS += [("fused-bce", FusedEvaluator, cb, {"loss": "bce"}), ("fused-kl", FusedEvaluator, cb, {"loss": "kl"}),
+             ("pipelined-bce", PipelinedEvaluator, cb, {"loss": "bce"})]
+for name, cls, batch, kw in LEGS:
+    if args.legs and name not in args.legs.split(","):
+        continue
+    ev = cls(Et, Rt, w.scorer, engine=eng, **kw)
+    loss_out = torch.zeros(1, dtype=torch.float64, device=dev)
+
+    def run(n):
+        ev.run([batch] * n)
+        if name == "fused+loss_only":
+            for _ in range(n):
+                eng.forward_backward(Et, Rt, w.scorer, labelled, None, None, loss="bce", loss_only=True, loss_out=loss_out)
+
+    run(192)                    # fresh streams are slow until the runtime's per-queue pools have grown to a full run's depth
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    ev.run([cb] * 40)
+    run(40)
     torch.cuda.synchronize()
     ms = 1e3 * (time.perf_counter() - t0) / 40
-    t0 = time.perf_counter()
-    ev.run([cb] * 640)               # steady state: start-up (first launches, the final host read) amortised
-    torch.cuda.synchronize()
-    ms_long = 1e3 * (time.perf_counter() - t0) / 640
+    windows = []
+    for _ in range(max(1, args.windows)):
+        t0 = time.perf_counter()
+        run(640)                     # steady state: start-up (first launches, the final host read) amortised
+        torch.cuda.synchronize()
+        windows.append(round(1e3 * (time.perf_counter() - t0) / 640, 4))
     eng.timing(True)
-    ev.run([cb] * 10)
+    run(10)
     torch.cuda.synchronize()
     per = {k: round(v[0] / v[1] * 1e3, 2) for k, v in eng.timing_collect().items()}
     eng.timing(False)
-    print(json.dumps({"path": name, "ms_per_batch": round(ms, 4), "ms_per_batch_640": round(ms_long, 4), "kernels_us": per}))
+    print(json.dumps({"path": name, "ms_per_batch": round(ms, 4), "ms_per_batch_640": min(windows), "windows_640": windows,
+                      "kernels_us": per}), flush=True)
