@@ -655,6 +655,50 @@ int okge_rows_catch_up(const okge_rows_decay_tensor *tensors, int32_t n_tensors,
 int okge_adagrad_rows_decay(const okge_rows_decay_tensor *tensors, int32_t n_tensors, int32_t *counters, int32_t window, float lr,
                             float weight_decay, float eps, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Adam, dense and on occurrence rows ----------------------------------------------------------------------------------------
+ * Replaces torch.optim.Adam.step (amsgrad = False, maximize = False, coupled L2 weight decay: _single_tensor_adam's non-capturable
+ * branch) -- the optimizer OptimRegime is born with (utils/optim.py:29) and the class `optimization_config.optimizer: Adam` names
+ * (utils/optim.py:143-145) -- and optimizer.zero_grad() (trainer.py:229-244):
+ *     g' = g + wd * p   (absent at wd == 0, not multiplied by zero);   m += (g' - m) * (1 - beta1);
+ *     v = v * beta2 + (1 - beta2) * g' * g';   p -= c1 * (m / (sqrt(v) / c2 + eps)),   c1 = lr / (1 - beta1^t),  c2 = sqrt(1 - beta2^t)
+ * in fp32 with correctly rounded sqrt and division; 1 - beta, c1 and c2 are formed in double and rounded to fp32 once.
+ *   state     : per tensor a DEVICE int32[4], all zero before the first step.  [0] = t, the steps taken; [1..3] = scratch (the
+ *               fp32 bits of c1, c2 and the row-sparse step size of the current t).  Every call first advances t of each tensor
+ *               by one on the device (a one-workgroup launch; two tensors that share one state advance it once) -- nothing is
+ *               read back, the launches are fixed by the n, and a captured HIP graph replays the count with the update.  To resume
+ *               from a checkpoint write t into [0]; to start over clear it.
+ *   zero_grad : as okge_adagrad_step2 -- 0 = keep both gradient buffers, 1 = clear both, 2 = clear only the second tensor's.
+ * One or two tensors per call, n >= 0 each (n = 0: only t advances); p, g, exp_avg, exp_avg_sq 16-byte aligned. */
+typedef struct okge_adam_tensor {
+    float   *p, *g, *exp_avg, *exp_avg_sq;
+    int32_t *state;
+    int64_t  n;
+} okge_adam_tensor;
+int okge_adam_step(const okge_adam_tensor *tensors, int32_t n_tensors /* 1..2 */, float lr, float beta1, float beta2, float eps,
+                   float weight_decay, int32_t zero_grad, void *stream);
+
+/* Replaces torch.optim.SparseAdam.step (torch.optim._functional.sparse_adam) on the row-sparse gradients model_config.sparse leaves
+ * (model.py:390-391), without its coalesce() (whose float atomics are not reproducible from run to run).  Occurrence rows, ids,
+ * coalescing (ascending position, sequentially in fp32), untouched rows, bad ids, cost and graph behaviour are exactly
+ * okge_adagrad_rows'; on the coalesced row g
+ *     m += (g - m) * (1 - beta1);   v += (g * g - v) * (1 - beta2);   p -= step * (m / (sqrt(v) + eps)),
+ *     step = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
+ * with no weight-decay term (SparseAdam has none).  state as okge_adam_step; it must not be NULL even for n = 0: that tensor's
+ * tables are left alone but its t still advances (SparseAdam.step counts the step before it skips an empty gradient).  One or two
+ * tensors, n up to 2^20 each (beyond: OKGE_ERR_UNSUPPORTED).  16-byte accesses when row_len and ld_g are multiples of 4 and p,
+ * exp_avg, exp_avg_sq and g are 16-byte aligned, single floats otherwise.  The result is bit-reproducible from run to run. */
+typedef struct okge_adam_rows_tensor {
+    float         *p, *exp_avg, *exp_avg_sq;
+    int32_t       *state;
+    const int32_t *ids;
+    const float   *g;
+    int64_t        ld_g;
+    int32_t        n, table_rows, row_len, _pad;
+} okge_adam_rows_tensor;
+size_t okge_adam_rows_workspace_bytes(int64_t n0, int64_t n1);         /* n of the first / second tensor (0: absent) */
+int okge_adam_rows(const okge_adam_rows_tensor *tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- batch producer (HOST pointers; no device work) ---------------------------------------------------
  * Replaces OneToNMentionRelationDataset_collate_func (dataset.py:724-940) and the packed answer-group decoding
  * it uses (utils/misc.py:72-89).  The dataset is the reference's three int32 tensors (dataset.py:567-710):

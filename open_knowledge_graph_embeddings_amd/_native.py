@@ -14,7 +14,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_i
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libokge_hip.so")
-SOURCES = ["okge_core.hip", "okge_api_train.hip", "okge_api_eval.hip", "okge_api_encoders.hip", "okge_api_optim.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_wide.hip", "okge_misc.hip", "okge_optim.hip", "okge_rank.hip", "okge_topk.hip", "okge_bias.hip", "okge_sparse.hip", "okge_n3.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
+SOURCES = ["okge_core.hip", "okge_api_train.hip", "okge_api_eval.hip", "okge_api_encoders.hip", "okge_api_optim.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_wide.hip", "okge_misc.hip", "okge_optim.hip", "okge_adam.hip", "okge_rank.hip", "okge_topk.hip", "okge_bias.hip", "okge_sparse.hip", "okge_n3.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
 # every header a source may include: all of csrc/*.h (listed by the directory, so a new header cannot be forgotten) + the ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "okge.h")]
 
@@ -54,6 +54,7 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_topk_workspace_bytes", "okge_topk_prefixes", "okge_topk_queries", "okge_topk_merge",
            "okge_train_row_grads_workspace_bytes", "okge_adagrad_rows", "okge_adagrad_rows_workspace_bytes",
            "okge_rows_catch_up", "okge_adagrad_rows_decay",
+           "okge_adam_step", "okge_adam_rows_workspace_bytes", "okge_adam_rows",
            "okge_n3_workspace_bytes", "okge_n3_forward_backward",
            "okge_eval_loss_workspace_bytes", "okge_evaluate_fused_loss", "okge_evaluate_fused_batches_loss",
            "okge_evaluate_batch_loss_workspace_bytes", "okge_evaluate_batch_loss",
@@ -162,6 +163,15 @@ class RowsDecayTensor(Structure):
                 ("row_steps", c_void_p), ("n", c_int32), ("table_rows", c_int32), ("row_len", c_int32), ("_pad", c_int32)]
 
 
+class AdamTensor(Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("state", c_void_p), ("n", c_int64)]
+
+
+class AdamRowsTensor(Structure):
+    _fields_ = [("p", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("state", c_void_p), ("ids", c_void_p), ("g", c_void_p),
+                ("ld_g", c_int64), ("n", c_int32), ("table_rows", c_int32), ("row_len", c_int32), ("_pad", c_int32)]
+
+
 class LazyTensor(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("state_sum", c_void_p), ("rows", c_int64), ("row_steps", c_void_p),
                 ("row_touched", c_void_p), ("row_len", c_int32), ("touched_stamp", c_int32)]
@@ -253,6 +263,12 @@ def lib():
     L.okge_adagrad_rows_decay.restype = c_int32
     L.okge_adagrad_rows_decay.argtypes = [POINTER(RowsDecayTensor), c_int32, c_void_p, c_int32, c_float, c_float, c_float, c_void_p,
                                           c_size_t, c_void_p]
+    L.okge_adam_step.restype = c_int32
+    L.okge_adam_step.argtypes = [POINTER(AdamTensor), c_int32, c_float, c_float, c_float, c_float, c_float, c_int32, c_void_p]
+    L.okge_adam_rows_workspace_bytes.restype = c_size_t
+    L.okge_adam_rows_workspace_bytes.argtypes = [c_int64, c_int64]
+    L.okge_adam_rows.restype = c_int32
+    L.okge_adam_rows.argtypes = [POINTER(AdamRowsTensor), c_int32, c_float, c_float, c_float, c_float, c_void_p, c_size_t, c_void_p]
     L.okge_n3_workspace_bytes.restype = c_size_t
     L.okge_n3_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     L.okge_n3_forward_backward.restype = c_int32

@@ -1,6 +1,6 @@
 // C ABI (include/okge.h), host side: the optimizers and the gradient scaling around them.  Dense Adagrad (one, two, up to four
 // tensors), the row-sparse Adagrad with and without deferred weight decay, the lazy (deferred decay) dense step and its pool
-// catch-up, scaling, clipping, and the merge of per-shard row log-sum-exps.
+// catch-up, dense and row-sparse Adam, scaling, clipping, and the merge of per-shard row log-sum-exps.
 #include "okge_host.h"
 
 using namespace okge;
@@ -30,15 +30,16 @@ int check_rows_count(const void *tensors, int32_t n_tensors, int32_t at_least)
 
 // one segment per tensor with n > 0, its two key buffers cut from the workspace; steps: the table's row_steps (deferred decay) or null
 void rows_segment(RowsSegs &segs, char *ws, Arena &ar, float *p, float *state_sum, const int32_t *ids, const float *g, int64_t ld_g, int32_t n,
-                  int32_t table_rows, int32_t row_len, int32_t *steps)
+                  int32_t table_rows, int32_t row_len, int32_t *steps, float *second_moment = nullptr, const int32_t *adam_state = nullptr)
 {
     RowsSeg &sg = segs.s[segs.n_segs++];
     sg.p = p; sg.s = state_sum; sg.g = g; sg.ids = ids; sg.ld_g = ld_g;
     sg.n = n; sg.table_rows = table_rows; sg.row_len = row_len; sg.steps = steps;
+    sg.s2 = second_moment; sg.state = adam_state;                  // (okge_adam_rows: state_sum is exp_avg)
     const RowsKeys keys = take_rows_keys(ar, n);
     sg.keys[0] = reinterpret_cast<uint64_t *>(ws + keys.off[0]);
     sg.keys[1] = reinterpret_cast<uint64_t *>(ws + keys.off[1]);
-    sg.vec = (row_len % 4 == 0 && ld_g % 4 == 0 && aligned16(p, state_sum, g)) ? 1 : 0;
+    sg.vec = (row_len % 4 == 0 && ld_g % 4 == 0 && aligned16(p, state_sum, g, second_moment)) ? 1 : 0;
     // lanes per run: one per 16-byte column group up to 16 (rows of 64 floats and more: 4 runs in flight per wave, each
     // lane several independent column groups)
     const int groups = sg.vec ? row_len / 4 : row_len;
@@ -61,6 +62,14 @@ int rows_decay_table(const okge_rows_decay_tensor &x, const char *who)
     if (x.n > 0 && !x.ids) return fail(OKGE_ERR_INVALID, "null ids");
     if (x.row_len % 4 || !aligned16(x.p, x.state_sum))
         return fail(OKGE_ERR_UNSUPPORTED, "deferred weight decay needs row_len % 4 == 0 and 16-byte aligned tables");
+    return OKGE_OK;
+}
+
+// (written so that a NaN fails every comparison it takes part in)
+int check_adam_hyper(float lr, float beta1, float beta2, float eps)
+{
+    if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && lr >= 0.f))
+        return fail(OKGE_ERR_INVALID, "adam needs 0 <= beta1, beta2 < 1, eps >= 0 and lr >= 0");
     return OKGE_OK;
 }
 
@@ -171,6 +180,68 @@ int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float 
     int sorted_in = 0;
     if (int rc = rows_sort(segs, &sorted_in, st)) return rc;
     return OKGE_TIMED("rows_update", "rows_update", st, launch_rows_update(segs, sorted_in, lr, eps, st));
+}
+
+// ---- Adam: torch.optim.Adam's dense update and torch.optim.SparseAdam's on occurrence rows --------------------------------------
+int okge_adam_step(const okge_adam_tensor *tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
+                   int32_t zero_grad, void *stream)
+{
+    if (!tensors || n_tensors < 1 || n_tensors > ADAM_MAX_SEGS) return fail(OKGE_ERR_INVALID, "one or two tensors");
+    AdamSeg segs[ADAM_MAX_SEGS] = {};
+    int32_t *states[ADAM_MAX_SEGS] = {};
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_adam_tensor &x = tensors[k];
+        if (!x.p || !x.g || !x.exp_avg || !x.exp_avg_sq || !x.state || x.n < 0) return fail(OKGE_ERR_INVALID, "bad adam arguments");
+        if (!aligned16(x.p, x.g, x.exp_avg, x.exp_avg_sq)) return fail(OKGE_ERR_INVALID, "adam buffers must be 16-byte aligned");
+        segs[k] = AdamSeg{x.p, x.g, x.exp_avg, x.exp_avg_sq, x.state, x.n};
+        states[k] = x.state;
+    }
+    if (int rc = check_adam_hyper(lr, beta1, beta2, eps)) return rc;
+    if (!(weight_decay >= 0.f)) return fail(OKGE_ERR_INVALID, "adam needs weight_decay >= 0");
+    if (zero_grad < 0 || zero_grad > 2) return fail(OKGE_ERR_INVALID, "zero_grad is 0 (none), 1 (both) or 2 (second tensor only)");
+    hipStream_t st = as_stream(stream);
+    if (int rc = OKGE_TIMED("adam_prologue", "adam_prologue", st, launch_adam_prologue(states, n_tensors, lr, beta1, beta2, st))) return rc;
+    return OKGE_TIMED("adam", "adam", st, launch_adam2(segs[0], segs[1], beta1, beta2, eps, weight_decay, zero_grad, st));
+}
+
+size_t okge_adam_rows_workspace_bytes(int64_t n0, int64_t n1) { return okge_adagrad_rows_workspace_bytes(n0, n1); }
+
+int okge_adam_rows(const okge_adam_rows_tensor *tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps, void *workspace,
+                   size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_rows_count(tensors, n_tensors, 1)) return rc;
+    Arena need;
+    int32_t *states[ROWS_MAX_SEGS] = {};
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_adam_rows_tensor &x = tensors[k];
+        if (x.n < 0) return fail(OKGE_ERR_INVALID, "negative occurrence count");
+        if (x.n > ROWS_MAX_N) return fail(OKGE_ERR_UNSUPPORTED, "okge_adam_rows takes up to 2^20 occurrence rows per tensor");
+        if (!x.state) return fail(OKGE_ERR_INVALID, "null tensor");          // (t advances whatever n is)
+        states[k] = x.state;
+        if (x.n == 0) continue;
+        if (!x.p || !x.exp_avg || !x.exp_avg_sq || !x.ids || !x.g) return fail(OKGE_ERR_INVALID, "null tensor");
+        if (x.table_rows <= 0 || x.row_len <= 0 || x.ld_g < x.row_len) return fail(OKGE_ERR_INVALID, "bad table shape / leading dimension");
+        take_rows_keys(need, x.n);
+    }
+    if (int rc = check_adam_hyper(lr, beta1, beta2, eps)) return rc;
+    if (need.total() && (!workspace || workspace_bytes < need.total()))
+        return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_adam_rows_workspace_bytes)");
+    RowsSegs segs;
+    std::memset(&segs, 0, sizeof(segs));
+    char *ws = static_cast<char *>(workspace);
+    Arena ar;
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_adam_rows_tensor &x = tensors[k];
+        if (x.n > 0) rows_segment(segs, ws, ar, x.p, x.exp_avg, x.ids, x.g, x.ld_g, x.n, x.table_rows, x.row_len, nullptr, x.exp_avg_sq, x.state);
+    }
+    hipStream_t st = as_stream(stream);
+    // SparseAdam.step counts the step before it skips an empty gradient: every tensor's t advances, whatever its n
+    if (int rc = OKGE_TIMED("adam_prologue", "adam_prologue", st, launch_adam_prologue(states, n_tensors, lr, beta1, beta2, st))) return rc;
+    if (!segs.n_segs) return OKGE_OK;
+    segs.id_err = id_err_ptr();
+    int sorted_in = 0;
+    if (int rc = rows_sort(segs, &sorted_in, st)) return rc;
+    return OKGE_TIMED("rows_update_adam", "rows_update_adam", st, launch_rows_update_adam(segs, sorted_in, beta1, beta2, eps, st));
 }
 
 int okge_rows_catch_up(const okge_rows_decay_tensor *tensors, int32_t n_tensors, const int32_t *counters, float lr, float weight_decay,

@@ -264,6 +264,13 @@ constexpr int LAZY_STEP = 0, LAZY_FLUSH = 1;
 struct LazySeg { float *p, *g, *s; int32_t *steps; uint8_t *touched; int64_t rows; int32_t row_len, stamp; };
 hipError_t launch_adagrad_lazy(const LazySeg *segs, int n_segs, int32_t *counters, int window, int mode, float lr, float wd,
                                float eps, hipStream_t st);
+// ---- okge_adam.hip: dense Adam over one or two tensors.  state: device int32[4] per tensor = { t, bits of c1 / c2 / the sparse
+// step size }; the prologue (one workgroup) advances every distinct state by one step and forms the three scalars of the new t
+constexpr int ADAM_MAX_SEGS = 2;
+struct AdamSeg { float *p, *g, *m, *v; const int32_t *state; int64_t n; };
+struct AdamStates { int32_t *state[ADAM_MAX_SEGS]; int n; };
+hipError_t launch_adam_prologue(int32_t *const *states, int n_states, float lr, float beta1, float beta2, hipStream_t st);
+hipError_t launch_adam2(const AdamSeg &a, const AdamSeg &b, float beta1, float beta2, float eps, float wd, int zero_grad, hipStream_t st);
 // row-sparse training (okge_sparse.hip).  Gather: the occurrence rows of one batch -- candidates, prefix entities, relations --
 // as the two small tables EV (N + B rows) / RV (B rows) of the relabelled problem, and the position ids that name them
 // (pos_ids[0..B) = N + i, pos_ids[B..2B) = i).
@@ -287,10 +294,14 @@ struct RowsSeg {
     int64_t        ld_g;
     int32_t        n, table_rows, row_len, vec, lane_shift;      // 1 << lane_shift lanes share one run of equal ids
     int32_t       *steps;                                        // okge_adagrad_rows_decay: [table_rows] optimizer steps each row has seen
+    float         *s2;                                           // okge_adam_rows: s = exp_avg, s2 = exp_avg_sq,
+    const int32_t *state;                                        //   state = the tensor's device state (AdamSeg)
 };
 struct RowsSegs { RowsSeg s[ROWS_MAX_SEGS]; int n_segs; int *id_err; };
 hipError_t launch_rows_sort(const RowsSegs &segs, int *sorted_in, hipStream_t st);
 hipError_t launch_rows_update(const RowsSegs &segs, int sorted_in, float lr, float eps, hipStream_t st);
+// okge_adam_rows: the same heads and the same walk with the sparse Adam body; the step size is read from each segment's state
+hipError_t launch_rows_update_adam(const RowsSegs &segs, int sorted_in, float beta1, float beta2, float eps, hipStream_t st);
 // deferred weight decay on the row-sparse step (okge_rows_catch_up / okge_adagrad_rows_decay): every segment 16-byte accessible
 // (vec) with a step counter per table row; counters[0] = T, the optimizer steps taken
 hipError_t launch_rows_update_decay(const RowsSegs &segs, int sorted_in, const int32_t *counters, float lr, float wd, float eps,

@@ -2,11 +2,12 @@
 // model.py:390-391).  Kernels of
 //   okge_train_forward_backward(OKGE_TRAIN_ROW_GRADS)   rows_gather_kernel: the occurrence rows of one batch as two small tables
 //   okge_adagrad_rows                                   rows_sort_chunk_kernel / rows_merge_kernel: occurrences ordered by (id, position)
-//                                                       rows_update_kernel: per distinct id, its gradient rows added up in ascending
-//                                                       position, sequentially in fp32, then the Adagrad update of that one table row
+//                                                       rows_update_kernel<AdagradRows>: per distinct id, its gradient rows added up in
+//                                                       ascending position, sequentially in fp32, then the Adagrad update of that table row
 //   okge_rows_catch_up                                  rows_catch_up_kernel: the rows a batch names take the decay-only steps they owe
 //   okge_adagrad_rows_decay                             rows_update_decay_kernel: the same walk with the weight-decay term, per-row step
 //                                                       counters kept (deferred weight decay; the rotating sweep is okge_optim.hip's)
+//   okge_adam_rows                                      rows_update_kernel<AdamRows>: the same sort and walk, torch's sparse Adam on the row
 // Nothing here is proportional to the table: the sort is O(n log n) on 8-byte keys, the update touches the n gradient rows and
 // the distinct table rows they name.  No float atomics, no host synchronisation; the launch sequence depends on the n alone.
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 
 #include "okge_kernels.h"
 #include "okge_adagrad_device.h"
+#include "okge_adam_device.h"
 
 namespace okge {
 
@@ -124,73 +126,136 @@ __global__ __launch_bounds__(256) void rows_merge_kernel(const RowsSegs segs, in
 // ascending position, and updates its columns of the table row.  Runs are short in training batches (a candidate list names
 // an entity once, a batch repeats a prefix entity a few times), so a lane's chain is a handful of dependent loads; several
 // runs are in flight per wave (64 / lanes) and the waves of a CU hide the rest.
-// DECAY (V == 4 only; okge_adagrad_rows_decay): the row first takes the `lag` decay-only steps it still owes, then the update
-// carries the weight-decay term -- adagrad4, the dense sweep's expression.  Without DECAY: adagrad1_rows, no decay term at all.
-template <int V, bool DECAY = false>
+// The walk is stated once; what happens to the table row is the Body's: Body::Row<V> holds one column group of the row's state
+// (loaded BEFORE the walk, so these loads are in flight while the gradient rows are added), takes the coalesced gradient and
+// stores what it updated.
+//   AdagradRows       adagrad1_rows, no decay term at all (okge_adagrad_rows)
+//   AdagradRowsDecay  (V == 4 only; okge_adagrad_rows_decay) the row first takes the `lag` decay-only steps it still owes, then
+//                     the update carries the weight-decay term -- adagrad4, the dense sweep's expression
+//   AdamRows          adam1_rows (okge_adam_rows): two moment rows, the step size from the segment's device state
+template <int V> struct RowVec { typedef float type; };
+template <> struct RowVec<4> { typedef float4 type; };
+template <int V> __device__ __forceinline__ typename RowVec<V>::type *row_ptr(float *x) { return reinterpret_cast<typename RowVec<V>::type *>(x); }
+__device__ __forceinline__ void row_add(float &acc, float b) { acc += b; }
+__device__ __forceinline__ void row_add(float4 &acc, const float4 &b) { acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w; }
+
+struct AdagradRows {
+    float lr, eps;
+    template <int V> struct Row {
+        typename RowVec<V>::type pv, sv;
+        __device__ __forceinline__ void load(const RowsSeg &sg, size_t i) { pv = row_ptr<V>(sg.p)[i]; sv = row_ptr<V>(sg.s)[i]; }
+        __device__ __forceinline__ void update(const AdagradRows &b, const RowsSeg &, const typename RowVec<V>::type &acc)
+        {
+            if constexpr (V == 4) {
+                adagrad1_rows(pv.x, acc.x, sv.x, b.lr, b.eps);
+                adagrad1_rows(pv.y, acc.y, sv.y, b.lr, b.eps);
+                adagrad1_rows(pv.z, acc.z, sv.z, b.lr, b.eps);
+                adagrad1_rows(pv.w, acc.w, sv.w, b.lr, b.eps);
+            } else {
+                adagrad1_rows(pv, acc, sv, b.lr, b.eps);
+            }
+        }
+        __device__ __forceinline__ void store(const RowsSeg &sg, size_t i) { row_ptr<V>(sg.p)[i] = pv; row_ptr<V>(sg.s)[i] = sv; }
+    };
+};
+
+struct AdagradRowsDecay {
+    float lr, wd, eps;
+    int lag;
+    template <int V> struct Row {
+        float4 pv, sv;
+        __device__ __forceinline__ void load(const RowsSeg &sg, size_t i) { pv = row_ptr<4>(sg.p)[i]; sv = row_ptr<4>(sg.s)[i]; }
+        __device__ __forceinline__ void update(const AdagradRowsDecay &b, const RowsSeg &, const float4 &acc)
+        {
+            // decay_replay4 votes across the wave.  Here the wave's lanes belong to different runs, lanes that are no head
+            // of a run have returned and only the lanes of lagging rows enter (lag differs from run to run): the votes see
+            // an arbitrary subset of the wave.  Both are used in the safe direction only -- "every active lane's operands
+            // are ordinary" picks the short sqrt / div sequences, which return the generic bits on such operands, and one
+            // lane that is not sends all to the generic code; "no active lane moved" skips steps that would return the bits
+            // they were given, and one lane that moved makes the others repeat a step that changes nothing.  Either way
+            // every lane ends with the bits of `lag` plain steps, whoever else took part in the vote.
+            if (b.lag > 0) decay_replay4(pv, sv, b.lag, b.lr, b.wd, b.eps);
+            adagrad4(pv, acc, sv, b.lr, b.wd, b.eps);
+        }
+        __device__ __forceinline__ void store(const RowsSeg &sg, size_t i) { row_ptr<4>(sg.p)[i] = pv; row_ptr<4>(sg.s)[i] = sv; }
+    };
+};
+
+struct AdamRows {
+    AdamHyper h;
+    template <int V> struct Row {
+        typename RowVec<V>::type pv, mv, vv;
+        __device__ __forceinline__ void load(const RowsSeg &sg, size_t i)
+        {
+            pv = row_ptr<V>(sg.p)[i]; mv = row_ptr<V>(sg.s)[i]; vv = row_ptr<V>(sg.s2)[i];
+        }
+        __device__ __forceinline__ void update(const AdamRows &b, const RowsSeg &sg, const typename RowVec<V>::type &acc)
+        {
+            const float step = __int_as_float(sg.state[ADAM_STEP]);
+            if constexpr (V == 4) {
+                adam1_rows(pv.x, acc.x, mv.x, vv.x, step, b.h);
+                adam1_rows(pv.y, acc.y, mv.y, vv.y, step, b.h);
+                adam1_rows(pv.z, acc.z, mv.z, vv.z, step, b.h);
+                adam1_rows(pv.w, acc.w, mv.w, vv.w, step, b.h);
+            } else {
+                adam1_rows(pv, acc, mv, vv, step, b.h);
+            }
+        }
+        __device__ __forceinline__ void store(const RowsSeg &sg, size_t i)
+        {
+            row_ptr<V>(sg.p)[i] = pv; row_ptr<V>(sg.s)[i] = mv; row_ptr<V>(sg.s2)[i] = vv;
+        }
+    };
+};
+
+template <int V, class Body>
 __device__ __forceinline__ void rows_update_run(const RowsSeg &sg, const uint64_t *__restrict__ keys, int i, uint32_t id, uint32_t pos,
-                                                int lane, int lanes, float lr, float eps, float wd = 0.f, int lag = 0)
+                                                int lane, int lanes, const Body &body)
 {
+    typedef typename RowVec<V>::type vec_t;
     const int cols = sg.row_len / V;
     const int64_t ldg = sg.ld_g / V;
     const size_t prow = (size_t)id * cols;
+    const vec_t *gv = reinterpret_cast<const vec_t *>(sg.g);
     for (int c = lane; c < cols; c += lanes) {
-        if constexpr (V == 4) {
-            float4 *p4 = reinterpret_cast<float4 *>(sg.p), *s4 = reinterpret_cast<float4 *>(sg.s);
-            const float4 *g4 = reinterpret_cast<const float4 *>(sg.g);
-            float4 pv = p4[prow + c], sv = s4[prow + c];
-            float4 acc = g4[(size_t)pos * ldg + c];
-            for (int j = i + 1; j < sg.n; ++j) {
-                const uint64_t kj = keys[j];
-                if ((uint32_t)(kj >> 32) != id) break;
-                const float4 b = g4[(size_t)(uint32_t)kj * ldg + c];
-                acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
-            }
-            if constexpr (DECAY) {
-                // decay_replay4 votes across the wave.  Here the wave's lanes belong to different runs, lanes that are no head
-                // of a run have returned and only the lanes of lagging rows enter (lag differs from run to run): the votes see
-                // an arbitrary subset of the wave.  Both are used in the safe direction only -- "every active lane's operands
-                // are ordinary" picks the short sqrt / div sequences, which return the generic bits on such operands, and one
-                // lane that is not sends all to the generic code; "no active lane moved" skips steps that would return the bits
-                // they were given, and one lane that moved makes the others repeat a step that changes nothing.  Either way
-                // every lane ends with the bits of `lag` plain steps, whoever else took part in the vote.
-                if (lag > 0) decay_replay4(pv, sv, lag, lr, wd, eps);
-                adagrad4(pv, acc, sv, lr, wd, eps);
-            } else {
-                adagrad1_rows(pv.x, acc.x, sv.x, lr, eps);
-                adagrad1_rows(pv.y, acc.y, sv.y, lr, eps);
-                adagrad1_rows(pv.z, acc.z, sv.z, lr, eps);
-                adagrad1_rows(pv.w, acc.w, sv.w, lr, eps);
-            }
-            p4[prow + c] = pv;
-            s4[prow + c] = sv;
-        } else {
-            float pv = sg.p[prow + c], sv = sg.s[prow + c];
-            float acc = sg.g[(size_t)pos * ldg + c];
-            for (int j = i + 1; j < sg.n; ++j) {
-                const uint64_t kj = keys[j];
-                if ((uint32_t)(kj >> 32) != id) break;
-                acc += sg.g[(size_t)(uint32_t)kj * ldg + c];
-            }
-            adagrad1_rows(pv, acc, sv, lr, eps);
-            sg.p[prow + c] = pv;
-            sg.s[prow + c] = sv;
+        typename Body::template Row<V> row;
+        row.load(sg, prow + c);
+        vec_t acc = gv[(size_t)pos * ldg + c];
+        for (int j = i + 1; j < sg.n; ++j) {
+            const uint64_t kj = keys[j];
+            if ((uint32_t)(kj >> 32) != id) break;
+            row_add(acc, gv[(size_t)(uint32_t)kj * ldg + c]);
         }
+        row.update(body, sg, acc);
+        row.store(sg, prow + c);
     }
 }
 
-__global__ __launch_bounds__(256) void rows_update_kernel(const RowsSegs segs, int sorted_in, float lr, float eps)
+// the head of the run that thread (i, lane) works on, or false: past the end, an id outside the table (counted by the sort, never
+// written), or not the first occurrence of its id
+__device__ __forceinline__ bool rows_run_head(const RowsSeg &sg, const uint64_t *__restrict__ keys, int &i, int &lane, uint32_t &id, uint32_t &pos)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    i = t >> sg.lane_shift;
+    lane = t & ((1 << sg.lane_shift) - 1);
+    if (i >= sg.n) return false;
+    const uint64_t key = keys[i];
+    if (key == KEY_SKIP) return false;
+    id = (uint32_t)(key >> 32);
+    pos = (uint32_t)key;
+    return !(i > 0 && (uint32_t)(keys[i - 1] >> 32) == id);
+}
+
+template <class Body>
+__global__ __launch_bounds__(256) void rows_update_kernel(const RowsSegs segs, int sorted_in, const Body body)
 {
     const RowsSeg &sg = segs.s[blockIdx.y];
     const uint64_t *__restrict__ keys = sg.keys[sorted_in];
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int i = t >> sg.lane_shift, lane = t & ((1 << sg.lane_shift) - 1);
-    if (i >= sg.n) return;
-    const uint64_t key = keys[i];
-    if (key == KEY_SKIP) return;                                                  // id outside the table: counted, never written
-    const uint32_t id = (uint32_t)(key >> 32);
-    if (i > 0 && (uint32_t)(keys[i - 1] >> 32) == id) return;                     // not the head of its run
-    if (sg.vec) rows_update_run<4>(sg, keys, i, id, (uint32_t)key, lane, 1 << sg.lane_shift, lr, eps);
-    else rows_update_run<1>(sg, keys, i, id, (uint32_t)key, lane, 1 << sg.lane_shift, lr, eps);
+    int i, lane;
+    uint32_t id, pos;
+    if (!rows_run_head(sg, keys, i, lane, id, pos)) return;
+    if (sg.vec) rows_update_run<4>(sg, keys, i, id, pos, lane, 1 << sg.lane_shift, body);
+    else rows_update_run<1>(sg, keys, i, id, pos, lane, 1 << sg.lane_shift, body);
 }
 
 // okge_adagrad_rows_decay: the same heads and the same walk; sg.vec holds by the entry point's preconditions.  T = the steps
@@ -202,16 +267,12 @@ __global__ __launch_bounds__(256) void rows_update_decay_kernel(const RowsSegs s
 {
     const RowsSeg &sg = segs.s[blockIdx.y];
     const uint64_t *__restrict__ keys = sg.keys[sorted_in];
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int i = t >> sg.lane_shift, lane = t & ((1 << sg.lane_shift) - 1);
-    if (i >= sg.n) return;
-    const uint64_t key = keys[i];
-    if (key == KEY_SKIP) return;                                                  // id outside the table: counted, never written
-    const uint32_t id = (uint32_t)(key >> 32);
-    if (i > 0 && (uint32_t)(keys[i - 1] >> 32) == id) return;                     // not the head of its run
+    int i, lane;
+    uint32_t id, pos;
+    if (!rows_run_head(sg, keys, i, lane, id, pos)) return;
     const int T = counters[0];
     const int lag = max(0, T - sg.steps[id]);
-    rows_update_run<4, true>(sg, keys, i, id, (uint32_t)key, lane, 1 << sg.lane_shift, lr, eps, wd, lag);
+    rows_update_run<4>(sg, keys, i, id, pos, lane, 1 << sg.lane_shift, AdagradRowsDecay{lr, wd, eps, lag});
     if (lane == 0) sg.steps[id] = T + 1;
 }
 
@@ -277,7 +338,21 @@ hipError_t launch_rows_update(const RowsSegs &segs, int sorted_in, float lr, flo
     int64_t threads = 0;
     for (int k = 0; k < segs.n_segs; ++k) threads = std::max<int64_t>(threads, (int64_t)segs.s[k].n << segs.s[k].lane_shift);
     if (threads <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rows_update_kernel, dim3((unsigned)((threads + 255) / 256), segs.n_segs), dim3(256), 0, st, segs, sorted_in, lr, eps);
+    hipLaunchKernelGGL(rows_update_kernel<AdagradRows>, dim3((unsigned)((threads + 255) / 256), segs.n_segs), dim3(256), 0, st, segs, sorted_in,
+                       AdagradRows{lr, eps});
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_update_adam(const RowsSegs &segs, int sorted_in, float beta1, float beta2, float eps, hipStream_t st)
+{
+    int64_t threads = 0;
+    for (int k = 0; k < segs.n_segs; ++k) {
+        if (!segs.s[k].s2 || !segs.s[k].state) return hipErrorInvalidValue;
+        threads = std::max<int64_t>(threads, (int64_t)segs.s[k].n << segs.s[k].lane_shift);
+    }
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rows_update_kernel<AdamRows>, dim3((unsigned)((threads + 255) / 256), segs.n_segs), dim3(256), 0, st, segs, sorted_in,
+                       AdamRows{adam_hyper(beta1, beta2, eps, 0.f)});
     return hipGetLastError();
 }
 

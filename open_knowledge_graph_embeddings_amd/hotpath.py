@@ -646,6 +646,59 @@ class HotPath:
         N.check(self.lib.okge_adagrad_rows(arr, len(tensors), float(lr), float(eps), self._rows_ws.data_ptr(), self._rows_ws.numel(),
                                            self._stream()), "okge_adagrad_rows")
 
+    @staticmethod
+    def adam_state(device, step=0):
+        """the device state of one Adam tensor (okge_adam_tensor.state): int32[4] = [steps taken, scratch x 3]"""
+        st = torch.zeros(4, dtype=torch.int32, device=device)
+        if step:
+            st[0] = int(step)
+        return st
+
+    def adam(self, tensors, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, zero_grad=True):
+        """okge_adam_step: torch.optim.Adam's update (no amsgrad, coupled weight decay) on one or two (p, g, exp_avg, exp_avg_sq,
+        state) tuples in one sweep; each state (adam_state) advances by one step on the device.  zero_grad as adagrad2."""
+        arr = (N.AdamTensor * len(tensors))()
+        for a, (p, g, m, v, st) in zip(arr, tensors):
+            for x in (p, g, m, v):
+                if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous():
+                    raise N.OkgeError("adam: contiguous fp32 tensors on the engine's device")
+            if g.numel() != p.numel() or m.numel() != p.numel() or v.numel() != p.numel():
+                raise N.OkgeError("adam: p, g, exp_avg and exp_avg_sq must have one size")
+            if st.dtype != torch.int32 or st.numel() != 4 or st.device != self.device or not st.is_contiguous():
+                raise N.OkgeError("adam: the state is a contiguous int32[4] tensor on the engine's device (HotPath.adam_state)")
+            a.p, a.g, a.exp_avg, a.exp_avg_sq, a.state, a.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), st.data_ptr(), p.numel()
+        N.check(self.lib.okge_adam_step(arr, len(tensors), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                        int(zero_grad), self._stream()), "okge_adam_step")
+
+    def adam_rows(self, tensors, lr, betas=(0.9, 0.999), eps=1e-8):
+        """okge_adam_rows: torch.optim.SparseAdam's update on one or two (p, exp_avg, exp_avg_sq, state, ids, g) tuples -- the
+        occurrence rows g (n, row_len) of the int32 device ids are coalesced per id in ascending position and only the named rows
+        of p and the two moments move; every state advances by one step, also where n = 0."""
+        arr = (N.AdamRowsTensor * len(tensors))()
+        for a, (p_, m_, v_, st_, i_, g_) in zip(arr, tensors):
+            n = int(i_.numel())
+            for x in (i_, st_):
+                if x.dtype != torch.int32 or not x.is_contiguous() or x.device != self.device:
+                    raise N.OkgeError("adam_rows: ids and state must be contiguous int32 tensors on the engine's device")
+            for x in (p_, m_, v_, g_):
+                if x.dtype != torch.float32 or x.device != self.device:
+                    raise N.OkgeError("adam_rows: fp32 tensors on the engine's device")
+            if p_.dim() != 2 or not (p_.is_contiguous() and m_.is_contiguous() and v_.is_contiguous()) or m_.shape != p_.shape or \
+                    v_.shape != p_.shape or st_.numel() != 4:
+                raise N.OkgeError("adam_rows: p, exp_avg and exp_avg_sq must be contiguous (rows, row_len) tensors of one shape, state int32[4]")
+            if n and (g_.dim() != 2 or g_.shape[0] != n or g_.shape[1] != p_.shape[1] or g_.stride(1) != 1):
+                raise N.OkgeError("adam_rows: g must hold one row of row_len floats per id, last dim contiguous")
+            a.p, a.exp_avg, a.exp_avg_sq, a.state = p_.data_ptr(), m_.data_ptr(), v_.data_ptr(), st_.data_ptr()
+            a.ids, a.g = i_.data_ptr(), g_.data_ptr()
+            a.ld_g = int(g_.stride(0)) if n > 1 else int(p_.shape[1])
+            a.n, a.table_rows, a.row_len = n, int(p_.shape[0]), int(p_.shape[1])
+        ns = [int(a.n) for a in arr] + [0]
+        need = int(self.lib.okge_adam_rows_workspace_bytes(ns[0], ns[1]))
+        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < need:
+            self._rows_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        N.check(self.lib.okge_adam_rows(arr, len(tensors), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                        self._rows_ws.data_ptr(), self._rows_ws.numel(), self._stream()), "okge_adam_rows")
+
     def _rows_decay_tensors(self, tensors, who):
         """(p, state_sum, ids, g or None, row_steps) tuples -> the okge_rows_decay_tensor array"""
         arr = (N.RowsDecayTensor * len(tensors))()

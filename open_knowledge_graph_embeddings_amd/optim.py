@@ -7,7 +7,11 @@ The reference names its optimizer in YAML (`optimization_config.optimizer`) and 
 how Adam's eps = 1e-8 leaks into Adagrad.  Importing this module registers the class there, so
 `optimizer: OkgeAdagrad` in a config selects it and the leaked keys are honoured the same way (torch's Optimizer keeps
 keys a group already has).  State layout = torch.optim.Adagrad's ({'step', 'sum'} per parameter), so checkpoints move
-between the two."""
+between the two.
+
+`OkgeAdam` / `OkgeSparseAdam`: the same for `optimizer: Adam` -- torch.optim.Adam's dense update (coupled weight decay, no
+amsgrad) on okge_adam_step and torch.optim.SparseAdam's on okge_adam_rows, registered the same way, state layout
+{'step', 'exp_avg', 'exp_avg_sq'}."""
 from __future__ import annotations
 
 import torch
@@ -136,5 +140,136 @@ def _global_step_hooks():
 OkgeAdagrad.step.hooked = True          # Optimizer._patch_step_function leaves a step marked like this alone
 
 
+DEVICE_STATE = "okge_state"             # per-parameter key of the device step count; never part of state_dict()
+
+
+class _OkgeAdamBase(torch.optim.Optimizer):
+    """What OkgeAdam and OkgeSparseAdam share: torch's state layout {'step', 'exp_avg', 'exp_avg_sq'} (created on a parameter's
+    first step, as torch does) plus the tiny device state the kernels count their steps in -- an extra per-parameter key that
+    state_dict() leaves out and that is rebuilt from 'step' after load_state_dict(), so checkpoints move between these classes and
+    torch.optim.Adam / SparseAdam.  Group keys the previous optimizer of an OptimRegime leaked (utils/optim.py:145: lr_decay,
+    initial_accumulator_value ...) stay in the group unread, as in OkgeAdagrad."""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        self._engines = {}
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise NotImplementedError(f"{type(self).__name__}: amsgrad and maximize are not implemented")
+            b1, b2 = group["betas"]
+            if not (0.0 <= group["lr"] and 0.0 <= group["eps"] and 0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+                raise ValueError(f"Invalid Adam hyper-parameters: lr {group['lr']}, eps {group['eps']}, betas {group['betas']}")
+
+    _engine = OkgeAdagrad._engine
+    zero_grad = OkgeAdagrad.zero_grad
+
+    def step(self, closure=None):
+        """(OkgeAdagrad.step's opt-out from torch's hooked wrapper: the profiler scope and hook dispatch are paid only when step
+        hooks are registered)"""
+        if self._optimizer_step_pre_hooks or self._optimizer_step_post_hooks or _global_step_hooks():
+            return torch.optim.Optimizer.profile_hook_step(type(self)._step)(self, closure)
+        return self._step(closure)
+
+    def _state(self, p):
+        st = self.state[p]
+        if "step" not in st:
+            st["step"] = torch.tensor(0.0, dtype=torch.float32)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        for k in ("exp_avg", "exp_avg_sq"):
+            if st[k].device != p.device or not st[k].is_contiguous():
+                st[k] = st[k].to(p.device).contiguous()
+        if DEVICE_STATE not in st or st[DEVICE_STATE].device != p.device:
+            st[DEVICE_STATE] = H.HotPath.adam_state(p.device, int(float(st["step"])))
+        return st
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["state"] = {k: {kk: vv for kk, vv in v.items() if kk != DEVICE_STATE} for k, v in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for st in self.state.values():              # the device count follows the loaded 'step' (rebuilt at the next step)
+            st.pop(DEVICE_STATE, None)
+            if "step" in st and torch.is_tensor(st["step"]):
+                st["step"] = st["step"].detach().to("cpu", torch.float32).clone()     # (never the tensor of the optimizer it came from)
+
+    def _params(self, group, sparse):
+        out = []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            g = p.grad
+            if g.is_sparse != sparse:
+                raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead" if g.is_sparse else
+                                   "SparseAdam does not support dense gradients, please consider Adam instead")
+            if p.dtype != torch.float32 or g.dtype != torch.float32 or p.device.type != "cuda" or not p.is_contiguous():
+                raise RuntimeError(f"{type(self).__name__} updates dense contiguous fp32 parameters on the GPU")
+            if sparse and (p.dim() != 2 or g.sparse_dim() != 1):
+                raise RuntimeError(f"{type(self).__name__} takes row-sparse gradients (one sparse dimension) of 2-d parameters")
+            st = self._state(p)
+            st["step"] += 1
+            out.append((p, g, st))
+        return out
+
+
+class OkgeAdam(_OkgeAdamBase):
+    """torch.optim.Adam's dense update (amsgrad = False, maximize = False, coupled weight decay) on okge_adam_step: one launch per
+    PAIR of parameters of a group (they share its hyper-parameters; each keeps its own state) instead of ATen's foreach chain."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False):
+        if amsgrad or maximize:
+            raise NotImplementedError("OkgeAdam: amsgrad and maximize are not implemented")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False))
+
+    @torch.no_grad()
+    def _step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            todo = [(p.data, g if g.is_contiguous() else g.contiguous(), st["exp_avg"], st["exp_avg_sq"], st[DEVICE_STATE])
+                    for p, g, st in self._params(group, sparse=False)]
+            for i in range(0, len(todo), 2):
+                self._engine(todo[i][0].device).adam(todo[i:i + 2], group["lr"], group["betas"], group["eps"], group["weight_decay"],
+                                                     zero_grad=False)
+        return loss
+
+
+class OkgeSparseAdam(_OkgeAdamBase):
+    """torch.optim.SparseAdam on okge_adam_rows: the row-sparse gradients nn.Embedding(sparse=True) / AddLossModule(sparse_grads=True)
+    leave (uncoalesced) are coalesced per index in ascending position and only the rows they name move -- reproducibly, where
+    SparseAdam's coalesce() is not.  The moments stay dense (torch's layout).  Two parameters of a group share the launches."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, maximize=False):
+        if maximize:
+            raise NotImplementedError("OkgeSparseAdam: maximize is not implemented")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, maximize=False))
+
+    @torch.no_grad()
+    def _step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            if group.get("weight_decay", 0) != 0:       # (a key leaked from a dense optimizer; torch's sparse refusal and text)
+                raise RuntimeError("weight_decay option is not compatible with sparse gradients")
+            todo = [(p.data, st["exp_avg"], st["exp_avg_sq"], st[DEVICE_STATE], _row_ids(g), _row_values(g))
+                    for p, g, st in self._params(group, sparse=True)]
+            for i in range(0, len(todo), 2):
+                self._engine(todo[i][0].device).adam_rows(todo[i:i + 2], group["lr"], group["betas"], group["eps"])
+        return loss
+
+
+_OkgeAdamBase.step.hooked = True
+
+
 # nameable from the reference's YAML: `optimizer: OkgeAdagrad` -> torch.optim.__dict__["OkgeAdagrad"] (utils/optim.py:143)
 torch.optim.OkgeAdagrad = OkgeAdagrad
+torch.optim.OkgeAdam = OkgeAdam
+torch.optim.OkgeSparseAdam = OkgeSparseAdam

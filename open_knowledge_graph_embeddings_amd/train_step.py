@@ -19,7 +19,8 @@ class FusedTrainStep:
                  weight_decay: float = 1e-10, eps: float = 1e-8, label_smoothing: float = 0.0,
                  input_dropout: float = 0.0, relation_input_dropout: float = 0.0, seed: int = 0, engine=None,
                  grad_clip: float = 0.0, accumulate: int = 1, sparse: bool = False, decay_window=None,
-                 l2_reg: float = 0.0, l2_reg_dropout: float = 0.0, l2_reg_per_direction: bool = False):
+                 l2_reg: float = 0.0, l2_reg_dropout: float = 0.0, l2_reg_per_direction: bool = False,
+                 optimizer: str = "adagrad", betas=(0.9, 0.999)):
         """Defaults follow config/fb15k237/fb15k237-complex-kge.yaml and the optimizer OptimRegime actually
         builds (utils/optim.py:29,139-160): Adagrad(lr, weight_decay=1e-10, eps=1e-8 leaked from Adam).
 
@@ -42,8 +43,27 @@ class FusedTrainStep:
         call).  `reg_out` (device double[1], beside `loss_out`) receives the term's value, the Trainer's `hook`; the loss
         excludes it.  l2_reg_dropout: the embedder's `dropout`, by which the reference divides the rows before the cube when it
         is > 0 (the probability; a divisor only, this step applies input_dropout).  l2_reg_per_direction: the candidate block
-        counts once per direction present (batch_shared_entities None, trainer.py:86-87) instead of once (a shared list)."""
+        counts once per direction present (batch_shared_entities None, trainer.py:86-87) instead of once (a shared list).
+
+        optimizer ("adagrad", the default: the object described above; or "adam", `optimization_config.optimizer: Adam`,
+        utils/optim.py:143-145): torch.optim.Adam(lr, betas, eps, weight_decay) with coupled weight decay and no amsgrad
+        (okge_adam_step).  The accumulators sumE / sumR give way to the moments mE / vE / mR / vR and one device state per table
+        (adam_stateE / adam_stateR, int32[4], [0] = t: optimizer steps taken, counted on the device so that a captured graph
+        replays it; `adam_t` reads it back).  Works with the dense and the wide step, accumulate, grad_clip and l2_reg.  With
+        sparse=True it is torch.optim.SparseAdam on the occurrence rows (okge_adam_rows), which has no weight decay:
+        weight_decay != 0 and decay_window raise ValueError.  `betas` is read by Adam only."""
         N.refuse_bias_scorer(scorer, type(self).__name__)
+        self.optimizer = str(optimizer).lower()
+        if self.optimizer not in ("adagrad", "adam"):
+            raise ValueError(f"optimizer {optimizer!r}: 'adagrad' or 'adam'")
+        self.betas = (float(betas[0]), float(betas[1]))
+        if self.optimizer == "adam":
+            if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0):
+                raise ValueError(f"Invalid beta parameters: {betas}")
+            if decay_window is not None:
+                raise ValueError("decay_window (deferred weight decay) belongs to the Adagrad step: SparseAdam has no weight decay")
+            if sparse and weight_decay != 0:
+                raise ValueError("weight_decay option is not compatible with sparse gradients (SparseAdam has no weight decay)")
         self.sparse = bool(sparse)
         self.decay_window = None if decay_window is None else int(decay_window)
         if self.decay_window is not None and (not self.sparse or self.decay_window < 1):
@@ -72,7 +92,11 @@ class FusedTrainStep:
         # dense .grad (model_config.sparse False); the sparse step keeps per-shape occurrence-row buffers instead (_row_buffers)
         self.dE, self.dR = (None, None) if self.sparse else (torch.zeros_like(E), torch.zeros_like(R))
         self._rows = {}
-        self.sumE, self.sumR = torch.zeros_like(E), torch.zeros_like(R)   # Adagrad state 'sum' (init 0)
+        if self.optimizer == "adam":      # Adam state 'exp_avg' / 'exp_avg_sq' (init 0) and the device step counts
+            self.mE, self.vE, self.mR, self.vR = torch.zeros_like(E), torch.zeros_like(E), torch.zeros_like(R), torch.zeros_like(R)
+            self.adam_stateE, self.adam_stateR = H.HotPath.adam_state(E.device), H.HotPath.adam_state(R.device)
+        else:
+            self.sumE, self.sumR = torch.zeros_like(E), torch.zeros_like(R)   # Adagrad state 'sum' (init 0)
         if self.decay_window is not None:
             # deferred weight decay: optimizer steps every row has seen, [steps taken, scratch] on the device (a captured graph
             # replays them), and the (lr, weight_decay, eps) of the steps rows still owe -- None: every row is current
@@ -97,12 +121,26 @@ class FusedTrainStep:
 
     def state_tensors(self):
         """every tensor a step mutates (GraphedTrainStep snapshots them around its warm-up)"""
+        if self.optimizer == "adam":       # (the two device states with them: restoring a snapshot restores t)
+            grads = [] if self.sparse else [self.dE, self.dR]
+            return [self.E, self.R] + grads + [self.mE, self.vE, self.mR, self.vR, self.adam_stateE, self.adam_stateR]
         if self.decay_window is not None:  # (a caller that restores a snapshot restores the step counters with it)
             self.flush()
             return [self.E, self.R, self.sumE, self.sumR, self.rowsE, self.rowsR, self._counters]
         if self.sparse:                   # (the row buffers are written whole before they are read, every step)
             return [self.E, self.R, self.sumE, self.sumR]
         return [self.E, self.R, self.dE, self.dR, self.sumE, self.sumR]
+
+    @property
+    def adam_t(self):
+        """optimizer steps the Adam state has taken (read back from the device: synchronises)"""
+        return int(self.adam_stateE[0].item())
+
+    def set_adam_t(self, t):
+        """both tables' device step counts (a loaded checkpoint, a reset)"""
+        for st in (self.adam_stateE, self.adam_stateR):
+            st.zero_()
+            st[0] = int(t)
 
     # -- sparse step with deferred weight decay (decay_window) ----------------------------------------------------------
     def _hparams(self):
@@ -264,6 +302,16 @@ class FusedTrainStep:
         every row it uses; it is cleared on demand if a sampled candidate list comes next.
         Sparse step: torch's sparse Adagrad on the occurrence rows of the last forward_backward -- nothing to clear; with a
         decay_window the same rows take the dense step's expression, then the due slice of the deferred decay-only steps."""
+        if self.optimizer == "adam":
+            if self.sparse:               # torch.optim.SparseAdam on the occurrence rows; nothing to clear
+                rb = self._cur_rows
+                self.engine.adam_rows([(self.E, self.mE, self.vE, self.adam_stateE, rb["idE"], rb["gE"]),
+                                       (self.R, self.mR, self.vR, self.adam_stateR, rb["idR"], rb["gR"])], self.lr, self.betas, self.eps)
+                return
+            self.engine.adam([(self.E, self.dE, self.mE, self.vE, self.adam_stateE), (self.R, self.dR, self.mR, self.vR, self.adam_stateR)],
+                             self.lr, self.betas, self.eps, self.weight_decay, zero_grad=2 if lazy_zero else 1)
+            self._dE_stale = bool(lazy_zero)
+            return
         if self.decay_window is not None:
             rb = self._cur_rows
             self._settle_hparams()

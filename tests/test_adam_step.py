@@ -1,0 +1,397 @@
+"""Adam through the Python surface: FusedTrainStep(optimizer="adam") dense, wide, row-sparse and under GraphedTrainStep, the drop-in
+optimizers OkgeAdam / OkgeSparseAdam, and the checkpoint layout.
+
+The training-step checks are ONE STEP AHEAD: optimizer_step is wrapped so that the state it starts from -- tables, moments, t and the
+gradients the device itself left (after accumulation and clipping) -- is read back, adam64 / sparse_adam64 (tests/adam_reference.py)
+is applied to exactly that on the host, and the tables after the call are held to adam_caps.  Errors do not compound, so no
+trajectory tolerance is guessed.  The end-to-end test at the bottom is the loose one; its bound is measured, not chosen."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import adam_reference as A
+from oracle import kge_oracle as ko
+from test_n3_step import _bits, _problems, dev
+
+pytestmark = pytest.mark.gpu
+
+LR, BETAS, EPS = 1e-2, (0.9, 0.999), 1e-8
+
+
+def _step(E, R, **kw):
+    from open_knowledge_graph_embeddings_amd.train_step import FusedTrainStep
+    kw.setdefault("lr", LR)
+    kw.setdefault("weight_decay", 0.0)
+    return FusedTrainStep(dev(E.copy()), dev(R.copy()), kw.pop("scorer", "complex"), optimizer="adam", betas=BETAS, eps=EPS, **kw)
+
+
+def _np(t):
+    return t.detach().cpu().numpy().copy()
+
+
+class Spy:
+    """wraps step.optimizer_step: (state before, state after) of every call, on the host"""
+
+    NAMES = ("E", "R", "mE", "vE", "mR", "vR")
+
+    def __init__(self, s):
+        self.s, self.records = s, []
+        inner = s.optimizer_step
+
+        def wrapped(lazy_zero=False):
+            pre = self.snapshot(True)
+            inner(lazy_zero=lazy_zero)
+            self.records.append((pre, self.snapshot(False)))
+        s.optimizer_step = wrapped
+
+    def snapshot(self, grads):
+        s = self.s
+        torch.cuda.synchronize()
+        out = {k: _np(getattr(s, k)) for k in self.NAMES}
+        out["tE"], out["tR"] = int(s.adam_stateE[0].item()), int(s.adam_stateR[0].item())
+        if grads and s.sparse:
+            out.update({k: _np(v) for k, v in s._cur_rows.items()})
+        elif grads:
+            out["dE"], out["dR"] = _np(s.dE), _np(s.dR)
+        return out
+
+
+def _hold(case, got, r, m, v, sparse=False):
+    """prints the RATIO lines of one table, then asserts; the few elements whose b g^2 underflows fp32 are outside the caps' statement"""
+    ok = ~A.underflowed(r)
+    assert (~ok).sum() <= 8, (case, int((~ok).sum()))
+    sub = A.Step64(*[x[ok] if isinstance(x, np.ndarray) and x.shape == ok.shape else x for x in r])
+    ratios = A.cap_ratios([x[ok] for x in got], sub, m[ok], v[ok], sparse)
+    print("RATIO %s p %.3f m %.3f v %.3f" % (case, *ratios))
+    assert all(np.isfinite(x).all() for x in got) and max(ratios) <= 1.0, (case, ratios)
+
+
+def check_dense_records(case, s, records):
+    for k, (pre, post) in enumerate(records):
+        for tab, mk, vk, gk, tk in (("E", "mE", "vE", "dE", "tE"), ("R", "mR", "vR", "dR", "tR")):
+            assert post[tk] == pre[tk] + 1 == k + 1, (case, k, tab, "t counts optimizer steps")
+            r = A.adam64(pre[tab], pre[gk], pre[mk], pre[vk], post[tk], s.lr, s.betas, s.eps, s.weight_decay)
+            assert np.abs(pre[gk]).max() > 0
+            _hold("%s step%d %s" % (case, k, tab), [post[tab], post[mk], post[vk]], r, pre[mk], pre[vk])
+
+
+DENSE = {
+    "bce-1vsall-d24": dict(d=24, loss="bce", n_cand=None),
+    "kl-sampled-d200": dict(d=200, loss="kl", n_cand=300, weight_decay=1e-2),
+    "bce-sampled-wide-d516-clip": dict(d=516, loss="bce", n_cand=130, grad_clip=1e-3),
+    "kl-1vsall-d24-accumulate2": dict(d=24, loss="kl", n_cand=None, accumulate=2),
+    "bce-1vsall-d200-l2reg": dict(d=200, loss="bce", n_cand=None, l2_reg=0.05, weight_decay=1e-10),
+    "bce-sampled-d24-all": dict(d=24, loss="bce", n_cand=100, accumulate=2, grad_clip=1e-3, l2_reg=0.05, input_dropout=0.3),
+}
+
+
+@pytest.mark.parametrize("name", list(DENSE))
+def test_dense_step_one_step_ahead(okge_lib, name):
+    cfg = dict(DENSE[name])
+    d, n_cand = cfg.pop("d"), cfg.pop("n_cand")
+    n_batches = 6 * cfg.get("accumulate", 1)
+    E, R, probs = _problems(n_batches, d, 300, 20, 9, 8, seed=len(name), n_cand=n_cand)
+    s = _step(E, R, seed=3, **cfg)
+    spy = Spy(s)
+    for p in probs:
+        s.step(p[0])
+    assert len(spy.records) == 6 and s.adam_t == 6 and s.steps == n_batches
+    check_dense_records(name, s, spy.records)
+    if cfg.get("grad_clip"):                                   # (the clip did bite: the optimizer saw a norm AT the bound)
+        pre = spy.records[0][0]
+        norm = np.sqrt((pre["dE"].astype(np.float64) ** 2).sum() + (pre["dR"].astype(np.float64) ** 2).sum())
+        assert 0.99 * cfg["grad_clip"] <= norm <= 1.0001 * cfg["grad_clip"], norm
+    assert not bool(s.dR.any())                                # gradients cleared in the sweep
+
+
+@pytest.mark.parametrize("d,loss", [(24, "bce"), (200, "kl")])
+def test_sparse_step_one_step_ahead(okge_lib, d, loss):
+    """sparse=True: torch.optim.SparseAdam on the occurrence rows the device left, coalesced on the host in ascending position;
+    rows no id names keep their bits"""
+    E, R, probs = _problems(6, d, 700, 20, 70, 60, seed=d, n_cand=200)
+    s = _step(E, R, sparse=True, loss=loss)
+    spy = Spy(s)
+    for p in probs:
+        s.step(p[0])
+    assert len(spy.records) == 6 and s.adam_t == 6
+    for k, (pre, post) in enumerate(spy.records):
+        for tab, mk, vk, gk, ik, tk in (("E", "mE", "vE", "gE", "idE", "tE"), ("R", "mR", "vR", "gR", "idR", "tR")):
+            assert post[tk] == k + 1
+            named, acc, bad = A.coalesce32(pre[ik], pre[gk], pre[tab].shape[0])
+            assert bad == 0 and named.size < pre[ik].size       # (ids repeat)
+            r = A.sparse_adam64(pre[tab][named], acc, pre[mk][named], pre[vk][named], post[tk], s.lr, s.betas, s.eps)
+            _hold("sparse-d%d-%s step%d %s" % (d, loss, k, tab), [post[x][named] for x in (tab, mk, vk)], r, pre[mk][named], pre[vk][named], True)
+            rest = np.ones(pre[tab].shape[0], bool)
+            rest[named] = False
+            assert rest.any()
+            for x in (tab, mk, vk):
+                assert np.array_equal(post[x][rest].view(np.uint32), pre[x][rest].view(np.uint32)), (k, x, "a row no id names moved")
+
+
+def test_refusals(okge_lib):
+    from open_knowledge_graph_embeddings_amd.train_step import FusedTrainStep
+    E, R, _ = _problems(1, 24, 60, 10, 3, 3, seed=1)
+    with pytest.raises(ValueError, match="weight_decay"):
+        _step(E, R, sparse=True, weight_decay=1e-10)
+    with pytest.raises(ValueError, match="decay_window"):
+        _step(E, R, sparse=True, weight_decay=1e-10, decay_window=4)
+    with pytest.raises(ValueError, match="decay_window"):
+        _step(E, R, sparse=True, decay_window=4)
+    with pytest.raises(ValueError, match="beta"):
+        FusedTrainStep(dev(E), dev(R), "complex", optimizer="adam", betas=(1.0, 0.999))
+    with pytest.raises(ValueError, match="optimizer"):
+        FusedTrainStep(dev(E), dev(R), "complex", optimizer="sgd")
+
+
+def test_graphed_step_replays_equal_eager_steps(okge_lib):
+    """eight replays of a captured Adam step = eight eager steps, bit for bit: tables, moments and t (every row named once per
+    batch, so the step's float atomics are order-free); the capture's warm-up steps leave t where it was"""
+    from open_knowledge_graph_embeddings_amd.train_step import GraphedTrainStep
+    E, R, probs = _problems(8, 200, 400, 30, 6, 5, seed=61, once=True, n_cand=130)
+    batches = [p[0] for p in probs]
+    eager, graphed = _step(E, R, weight_decay=1e-4), _step(E, R, weight_decay=1e-4)
+    for s in (eager, graphed):                                 # both start from three eager steps: t = 3 at capture
+        for b in batches[:3]:
+            s.step(b)
+    gs = GraphedTrainStep(graphed, batches[0], pos_capacity=max(b.nnz for b in batches) + 3)
+    torch.cuda.synchronize()
+    assert graphed.adam_t == 3 and int(graphed.adam_stateR[0].item()) == 3
+    for name in Spy.NAMES:
+        assert torch.equal(_bits(getattr(eager, name)), _bits(getattr(graphed, name))), ("after the warm-up", name)
+    for b in batches:
+        le, lg = eager.step(b).clone(), gs.step(b).clone()
+        assert torch.equal(_bits(le), _bits(lg))
+    torch.cuda.synchronize()
+    assert eager.adam_t == graphed.adam_t == 11
+    for name in Spy.NAMES + ("adam_stateE", "adam_stateR"):
+        a, b = getattr(eager, name), getattr(graphed, name)
+        assert torch.equal(a if a.dtype == torch.int32 else _bits(a), b if b.dtype == torch.int32 else _bits(b)), name
+
+
+def test_adagrad_keyword_is_the_default_object(okge_lib):
+    from open_knowledge_graph_embeddings_amd.train_step import FusedTrainStep
+    E, R, probs = _problems(3, 24, 90, 30, 7, 6, seed=41, once=True, n_cand=50)
+    a = FusedTrainStep(dev(E.copy()), dev(R.copy()), "complex", lr=0.3, seed=5)
+    b = FusedTrainStep(dev(E.copy()), dev(R.copy()), "complex", lr=0.3, seed=5, optimizer="adagrad", betas=(0.5, 0.5))
+    assert not hasattr(a, "mE") and not hasattr(b, "mE") and a.optimizer == b.optimizer == "adagrad"
+    assert [t.shape for t in a.state_tensors()] == [t.shape for t in b.state_tensors()] and len(a.state_tensors()) == 6
+    for p in probs:
+        a.step(p[0])
+        b.step(p[0])
+    for name in ("E", "R", "dE", "dR", "sumE", "sumR"):
+        assert torch.equal(_bits(getattr(a, name)), _bits(getattr(b, name))), name
+
+
+# ---- the drop-in optimizers -----------------------------------------------------------------------------------------------------
+def _params(shapes, seed):
+    rng = np.random.default_rng(seed)
+    return [torch.nn.Parameter(dev((0.1 * rng.standard_normal(sh)).astype(np.float32))) for sh in shapes]
+
+
+# Hyper-parameters fp32 holds exactly.  The C ABI carries lr, the betas, eps and weight_decay as fp32 and forms 1 - beta from the fp32
+# value; torch keeps the Python doubles for 1 - beta and the bias corrections and rounds beta itself to fp32 for v * beta2.  At
+# beta2 = 0.999 the two readings of 1 - beta2 differ by 1.3e-5 of it (2^-24 / (1 - beta2)): far outside caps that count fp32
+# roundings, though either is Adam at a beta2 within 2^-24 of the other's.  With values fp32 holds exactly both see the same numbers
+# and adam64 is the restatement of both.
+X_LR, X_BETAS, X_EPS, X_WD = 2.0 ** -7, (0.875, 1.0 - 2.0 ** -10), 2.0 ** -27, 2.0 ** -7
+
+
+@pytest.mark.parametrize("wd", [0.0, X_WD], ids=["wd0", "wd2^-7"])
+def test_okge_adam_against_torch_adam(okge_lib, wd):
+    """5 steps on three parameters (a pair shares a launch, the third goes alone).  Before every step the state travels through
+    state_dict() into a fresh torch.optim.Adam on copies of the parameters (torch accepts it as its own); both take the same
+    gradients; each must land within adam_caps of adam64 of the common starting point.  Then torch's state_dict travels back."""
+    from open_knowledge_graph_embeddings_amd.optim import DEVICE_STATE, OkgeAdam
+    assert torch.optim.__dict__["OkgeAdam"] is OkgeAdam
+    shapes = [(37, 24), (5, 7), (1025,)]
+    ps = _params(shapes, 3)
+    opt = OkgeAdam(ps, lr=X_LR, betas=X_BETAS, eps=X_EPS, weight_decay=wd)
+    rng = np.random.default_rng(4)
+    for t in range(1, 6):
+        twins = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+        ref = torch.optim.Adam(twins, lr=X_LR, betas=X_BETAS, eps=X_EPS, weight_decay=wd)
+        sd = opt.state_dict()
+        assert all(DEVICE_STATE not in st and set(st) == {"step", "exp_avg", "exp_avg_sq"} for st in sd["state"].values())
+        ref.load_state_dict(copy.deepcopy(sd))              # (state_dict() hands out the live tensors, torch's own does too)
+        pre = [(_np(p), _np(opt.state[p]["exp_avg"]) if t > 1 else np.zeros(p.shape, np.float32),
+                _np(opt.state[p]["exp_avg_sq"]) if t > 1 else np.zeros(p.shape, np.float32)) for p in ps]
+        grads = [(rng.standard_normal(sh) * 10.0 ** rng.integers(-4, 0, sh)).astype(np.float32) for sh in shapes]
+        for p, q, g in zip(ps, twins, grads):
+            p.grad, q.grad = dev(g), dev(g)
+        opt.step()
+        ref.step()
+        torch.cuda.synchronize()
+        for k, (p, q, g, (p0, m0, v0)) in enumerate(zip(ps, twins, grads, pre)):
+            r = A.adam64(p0, g, m0, v0, t, X_LR, X_BETAS, X_EPS, wd)
+            st, rt = opt.state[p], ref.state[q]
+            assert float(st["step"]) == float(rt["step"]) == t and int(st[DEVICE_STATE][0].item()) == t
+            _hold("OkgeAdam wd%g step%d p%d" % (wd, t, k), [_np(p), _np(st["exp_avg"]), _np(st["exp_avg_sq"])], r, m0, v0)
+            _hold("torch.Adam wd%g step%d p%d" % (wd, t, k), [_np(q), _np(rt["exp_avg"]), _np(rt["exp_avg_sq"])], r, m0, v0)
+    # torch's state back into a fresh OkgeAdam: the device count is rebuilt from 'step'; one more step agrees with adam64 at t = 6
+    back = OkgeAdam(ps, lr=X_LR, betas=X_BETAS, eps=X_EPS, weight_decay=wd)
+    twins = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+    ref = torch.optim.Adam(twins, lr=X_LR, betas=X_BETAS, eps=X_EPS, weight_decay=wd)
+    ref.load_state_dict(copy.deepcopy(opt.state_dict()))
+    back.load_state_dict(ref.state_dict())                 # (no copy: OkgeAdam takes its own 'step')
+    pre = [(_np(p), _np(opt.state[p]["exp_avg"]), _np(opt.state[p]["exp_avg_sq"])) for p in ps]
+    for p, sh in zip(ps, shapes):
+        p.grad = dev((rng.standard_normal(sh) * 1e-2).astype(np.float32))
+    grads = [_np(p.grad) for p in ps]
+    back.step()
+    for k, (p, g, (p0, m0, v0)) in enumerate(zip(ps, grads, pre)):
+        st = back.state[p]
+        assert float(st["step"]) == 6 and int(st[DEVICE_STATE][0].item()) == 6
+        _hold("OkgeAdam reloaded p%d" % k, [_np(p), _np(st["exp_avg"]), _np(st["exp_avg_sq"])], A.adam64(p0, g, m0, v0, 6, X_LR, X_BETAS, X_EPS, wd), m0, v0)
+
+
+def test_okge_adam_refusals(okge_lib):
+    from open_knowledge_graph_embeddings_amd.optim import OkgeAdam, OkgeSparseAdam
+    ps = _params([(9, 4)], 5)
+    for kw in (dict(amsgrad=True), dict(maximize=True)):
+        with pytest.raises(NotImplementedError):
+            OkgeAdam(ps, **kw)
+    with pytest.raises(NotImplementedError):
+        OkgeSparseAdam(ps, maximize=True)
+    with pytest.raises(NotImplementedError):                   # (a group that carries the key, as OptimRegime re-wraps param_groups)
+        OkgeAdam([dict(params=ps, amsgrad=True)])
+    # keys the previous optimizer of an OptimRegime leaked stay in the group, unread
+    leaked = torch.optim.Adagrad(ps, lr=0.5, weight_decay=0.0).param_groups
+    opt = OkgeAdam(leaked)
+    assert opt.param_groups[0]["lr"] == 0.5 and "lr_decay" in opt.param_groups[0] and opt.param_groups[0]["betas"] == (0.9, 0.999)
+    ps[0].grad = torch.sparse_coo_tensor(dev(np.array([[1, 1]])), dev(np.ones((2, 4), np.float32)), (9, 4))
+    with pytest.raises(RuntimeError, match="Adam does not support sparse gradients, please consider SparseAdam instead"):
+        opt.step()
+    sp = OkgeSparseAdam(ps)
+    ps[0].grad = dev(np.ones((9, 4), np.float32))
+    with pytest.raises(RuntimeError, match="SparseAdam does not support dense gradients"):
+        sp.step()
+    assert getattr(OkgeAdam.step, "hooked", False) and getattr(OkgeSparseAdam.step, "hooked", False)
+
+
+def test_okge_sparse_adam_against_sparse_adam64(okge_lib):
+    """5 steps of uncoalesced row-sparse gradients on two parameters that share the launches; a state_dict round trip through
+    torch.optim.SparseAdam in the middle"""
+    from open_knowledge_graph_embeddings_amd.optim import DEVICE_STATE, OkgeSparseAdam
+    assert torch.optim.__dict__["OkgeSparseAdam"] is OkgeSparseAdam
+    shapes = [(300, 24), (40, 8)]
+    ps = _params(shapes, 6)
+    opt = OkgeSparseAdam(ps, lr=LR, betas=BETAS, eps=EPS)
+    rng = np.random.default_rng(7)
+    for t in range(1, 6):
+        if t == 3:
+            mid = torch.optim.SparseAdam(ps, lr=LR, betas=BETAS, eps=EPS)
+            mid.load_state_dict(copy.deepcopy(opt.state_dict()))
+            opt = OkgeSparseAdam(ps, lr=LR, betas=BETAS, eps=EPS)
+            opt.load_state_dict(mid.state_dict())
+        pre = [(_np(p), _np(opt.state[p]["exp_avg"]) if opt.state[p] else np.zeros(p.shape, np.float32),
+                _np(opt.state[p]["exp_avg_sq"]) if opt.state[p] else np.zeros(p.shape, np.float32)) for p in ps]
+        occ = []
+        for p, (rows, d) in zip(ps, shapes):
+            ids = rng.integers(0, rows - 5, 3 * rows // 4)
+            vals = (rng.standard_normal((ids.size, d)) * 10.0 ** rng.integers(-4, 0, (ids.size, d))).astype(np.float32)
+            p.grad = torch.sparse_coo_tensor(dev(ids[None, :].astype(np.int64)), dev(vals), (rows, d))
+            occ.append((ids, vals))
+        opt.step()
+        torch.cuda.synchronize()
+        for k, (p, (ids, vals), (p0, m0, v0)) in enumerate(zip(ps, occ, pre)):
+            st = opt.state[p]
+            assert float(st["step"]) == t and int(st[DEVICE_STATE][0].item()) == t
+            named, acc, _ = A.coalesce32(ids, vals, p.shape[0])
+            r = A.sparse_adam64(p0[named], acc, m0[named], v0[named], t, LR, BETAS, EPS)
+            got = [_np(p), _np(st["exp_avg"]), _np(st["exp_avg_sq"])]
+            _hold("OkgeSparseAdam step%d p%d" % (t, k), [x[named] for x in got], r, m0[named], v0[named], True)
+            rest = np.ones(p.shape[0], bool)
+            rest[named] = False
+            for x, x0 in zip(got, (p0, m0, v0)):
+                assert np.array_equal(x[rest].view(np.uint32), x0[rest].view(np.uint32))
+
+
+# ---- checkpoints ------------------------------------------------------------------------------------------------------------------
+def test_checkpoint_round_trip_and_refusals(okge_lib, tmp_path):
+    from open_knowledge_graph_embeddings_amd import checkpoint as C
+    from open_knowledge_graph_embeddings_amd.train_step import FusedTrainStep
+    E, R, probs = _problems(6, 24, 120, 20, 6, 5, seed=71, once=True, n_cand=60)
+    batches = [p[0] for p in probs]
+    kw = dict(weight_decay=1e-3, input_dropout=0.3, seed=9, accumulate=2)
+    whole = _step(E, R, **kw)
+    for b in batches:
+        whole.step(b)
+    first = _step(E, R, **kw)
+    for b in batches[:4]:
+        first.step(b)
+    path = str(tmp_path / "adam.pt")
+    ckpt = C.save_checkpoint(path, first)
+    assert ckpt["optimizer_state_dict"][0]["regime"][0]["optimizer"] == "Adam"
+    st0 = ckpt["optimizer_state_dict"][0]["optimizer_state"]["state"][0]
+    assert set(st0) == {"step", "exp_avg", "exp_avg_sq"} and float(st0["step"]) == 2.0        # t counts optimizer steps, not batches
+    # ... the file loads into a real torch.optim.Adam
+    twins = [torch.nn.Parameter(torch.zeros(E.shape)), torch.nn.Parameter(torch.zeros(R.shape))]
+    ref = torch.optim.Adam(twins, lr=1.0)
+    ref.load_state_dict(torch.load(path, map_location="cpu", weights_only=True)["optimizer_state_dict"][0]["optimizer_state"])
+    assert torch.equal(ref.state[twins[0]]["exp_avg_sq"], first.vE.cpu()) and ref.param_groups[0]["lr"] == LR
+    # ... and into a fresh Adam step: one more optimizer step (two batches) = the uninterrupted run, bit for bit
+    second = _step(E * 0, R * 0, lr=7.0, input_dropout=0.3, seed=9, accumulate=2)
+    C.load_reference_checkpoint(second, path)
+    assert second.adam_t == 2 and second.steps == 4 and second.lr == LR and second.weight_decay == 1e-3
+    for b in batches[4:]:
+        second.step(b)
+        first.step(b)
+    assert second.adam_t == whole.adam_t == 3
+    for name in Spy.NAMES + ("dE", "dR"):
+        assert torch.equal(_bits(getattr(first, name)), _bits(getattr(second, name))), name
+        assert torch.equal(_bits(getattr(whole, name)), _bits(getattr(second, name))), name
+    # cross-optimizer loads are refused both ways unless the optimizer is reset
+    adagrad = FusedTrainStep(dev(E.copy()), dev(R.copy()), "complex", lr=0.3)
+    adagrad.step(batches[0])
+    with pytest.raises(ValueError, match="adam optimizer state and this step trains with adagrad"):
+        C.load_reference_checkpoint(adagrad, path)
+    with pytest.raises(ValueError, match="adagrad optimizer state and this step trains with adam"):
+        C.load_reference_checkpoint(second, C.to_reference_checkpoint(adagrad))
+    C.load_reference_checkpoint(second, C.to_reference_checkpoint(adagrad), reset_optimizer=True)
+    assert second.adam_t == 0 and second.steps == 0 and int(second.adam_stateR[0].item()) == 0
+    assert torch.equal(second.E, adagrad.E) and not any(bool(getattr(second, k).any()) for k in ("mE", "vE", "mR", "vR"))
+    C.load_reference_checkpoint(adagrad, path, reset_optimizer=True)
+    assert torch.equal(adagrad.E.cpu(), ckpt["state_dict"][C.ENTITY_KEY]) and not bool(adagrad.sumE.any()) and adagrad.steps == 0
+
+
+# ---- end to end (loose) ---------------------------------------------------------------------------------------------------------
+def _twin(dtype, E, R, probs, lr):
+    """the oracle's step (numpy, forward and hand-written backward, in `dtype`) driven by torch.optim.Adam on the CPU.  The loss is
+    the reference's own call on the twin's scores, in the twin's dtype -- BCEWithLogitsLoss(reduction="sum"), trainer.py:48-113 --
+    because the oracle's `loss` entry accumulates in float64 whatever the dtype: an fp32 run that reports an fp32 loss, as the
+    reference does, cannot be closer than half an ulp of it (2.4e-4 at 5490)"""
+    ps = [torch.nn.Parameter(torch.tensor(E, dtype=dtype)), torch.nn.Parameter(torch.tensor(R, dtype=dtype))]
+    opt = torch.optim.Adam(ps, lr=lr, betas=BETAS, eps=EPS)
+    loss = None
+    for (_, po, sp, cand, y) in probs:
+        out = ko.step_forward_backward(ko.COMPLEX, ps[0].detach().numpy(), ps[1].detach().numpy(), po, sp, cand, y.astype(ps[0].detach().numpy().dtype))
+        ps[0].grad, ps[1].grad = torch.tensor(out["dE"], dtype=dtype), torch.tensor(out["dR"], dtype=dtype)
+        opt.step()
+        loss = float(torch.nn.functional.binary_cross_entropy_with_logits(torch.tensor(out["outputs"], dtype=dtype), torch.tensor(y, dtype=dtype),
+                                                                          reduction="sum"))
+    return loss, ps[0].detach().numpy().astype(np.float64), ps[1].detach().numpy().astype(np.float64)
+
+
+def test_thirty_steps_against_the_oracle_twin(okge_lib):
+    """30 Adam steps at d = 24, 1-vs-all BCE, no dropout.  Reference: the oracle's twin in float64.  Bound: 4x the distance of the
+    SAME twin run in fp32 from it (measured here, on the CPU) -- on the last batch's loss and on the tables; the factor covers a
+    different summation order in the products.  The table distance is the Frobenius norm: where a gradient element is near zero
+    Adam's update is sign-like, so a single element's deviation is heavy-tailed while the norm is stable.
+    Measured (profiles/adam.md): the fp32 twin's drift 1.52e-4 on the loss (5489.8; an fp32 half-ulp there is 2.4e-4), 9.97e-7 on E and
+    2.07e-7 on R; the HIP step 1.57e-4, 9.93e-7 and 1.95e-7; the run moves E by 0.534."""
+    E, R, probs = _problems(30, 24, 200, 12, 20, 20, seed=91)
+    l64, E64, R64 = _twin(torch.float64, E, R, probs, 1e-3)
+    l32, E32, R32 = _twin(torch.float32, E, R, probs, 1e-3)
+    s = _step(E, R, lr=1e-3)
+    for p in probs:
+        loss = s.step(p[0])
+    torch.cuda.synchronize()
+    drift = (abs(l32 - l64), np.linalg.norm(E32 - E64), np.linalg.norm(R32 - R64))
+    mine = (abs(float(loss) - l64), np.linalg.norm(_np(s.E).astype(np.float64) - E64), np.linalg.norm(_np(s.R).astype(np.float64) - R64))
+    print("DRIFT twin fp32 vs float64: loss %.3e E %.3e R %.3e | HIP vs float64: loss %.3e E %.3e R %.3e | moved E %.3e"
+          % (*drift, *mine, np.linalg.norm(E64 - E)))
+    assert np.linalg.norm(E64 - E) > 1000 * drift[1]           # (the run moves the tables far more than the bound allows for)
+    for name, a, b in zip(("loss", "E", "R"), mine, drift):
+        assert a <= 4 * b, (name, a, b)
