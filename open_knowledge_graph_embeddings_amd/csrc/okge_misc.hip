@@ -348,7 +348,8 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const double *__restri
 
 // One batch row per 128-thread workgroup: lane = (column group g = tid >> 2, split quarter sq = tid & 3).  The four
 // lanes of a column group sum disjoint quarters of the nsplit dQ slabs (all their loads are issued at once) and
-// combine with two shuffles; sq == 0 then applies the chain rule and scatters.  Needs d % 8 == 0 (ComplEx) or
+// combine with two shuffles; sq == 0 then applies the chain rule and stores its four columns, or -- on the atomic path -- hands
+// one column to each lane of the group, so that a wave adds 256 contiguous bytes at a time.  Needs d % 8 == 0 (ComplEx) or
 // d % 4 == 0 (DistMult).  The last workgroup (blockIdx.x == gridDim.x - 1) instead sums the loss partials.
 // NB: slab loads kept in flight per lane (8 for the single-device step's 32 split-K slabs; 1 for the sharded step, whose dQ
 // arrives already reduced: 89 instead of 149 registers = 5 instead of 3 waves per SIMD, which is what bounds a launch of
@@ -387,13 +388,25 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
     const int s_lo = (nsplit * sq) >> 2, s_hi = (nsplit * (sq + 1)) >> 2;
     // distinct (OKGE_TRAIN_DISTINCT_PREFIX_ROWS): every prefix id occurs once in the batch: the table's gradient row itself is
     // a row of its own
-    auto put_r = [&](float *pr, float4 v) {      // relation gradient: a row of its own (plain store) or an atomic add into dR
-        if (dr_rows || distinct) *reinterpret_cast<float4 *>(pr) = v;
-        else atomic_add4(pr, v);
+    // v: the lead lane's (sq == 0) four columns.  Stored by the lead lane, or added by all four lanes of the column group, one
+    // column each, so that a wave adds 64 consecutive floats per instruction (quad_lead_component): every lane of the workgroup
+    // calls put; act: the lane's group stands on columns of the row
+    const bool store_r = dr_rows || distinct, store_e = de_rows || distinct;
+    auto put = [&](bool store, float *dst, float4 v, bool act) {      // a row of its own (plain store) or an atomic add into dR / dE
+        if (store) {
+            if (act && sq == 0) *reinterpret_cast<float4 *>(dst) = v;
+        } else {
+            const float c = quad_lead_component(v, sq);
+            if (act) atomicAdd(dst + sq, c);
+        }
     };
-    auto put_e = [&](float *pe, float4 v) {
-        if (de_rows || distinct) *reinterpret_cast<float4 *>(pe) = v;
-        else atomic_add4(pe, v);
+    auto put2 = [&](bool store, float *dst, int h, float4 v1, float4 v2, bool act) {      // ComplEx: the same columns of both halves
+        if (store) {
+            if (act && sq == 0) { *reinterpret_cast<float4 *>(dst) = v1; *reinterpret_cast<float4 *>(dst + h) = v2; }
+        } else {
+            const float c1 = quad_lead_component(v1, sq), c2 = quad_lead_component(v2, sq);
+            if (act) { atomicAdd(dst + sq, c1); atomicAdd(dst + h + sq, c2); }
+        }
     };
     auto dq_sum = [&](int k, bool active) { return dq_quad_sum<NB>(sl, split_stride, s_lo, s_hi, k, active); };
     // The keep nibbles of a column group: lane sq computes ONE of the (up to four) Philox calls the group needs and the
@@ -414,18 +427,19 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
         for (int k0 = 128 * blockIdx.y; k0 < d; k0 += 128 * gridDim.y) {
             const int k = k0 + 4 * grp;
             const bool act = k < d, lead = act && sq == 0;
+            if (!__any(act)) continue;                   // a wave past the row's last column group (a scalar branch)
             const float4 ev0 = lead ? *reinterpret_cast<const float4 *>(e + k) : zero4;
             const float4 rv0 = lead ? *reinterpret_cast<const float4 *>(r + k) : zero4;
             const uint32_t nib = nibble((sq & 1) ? dr : de, k, act && sq < 2);
             const uint32_t nib_e = __shfl(nib, lane0), nib_r = __shfl(nib, lane0 + 1);
             const float4 dq = dq_sum(act ? k : 0, act);
-            if (lead) {
-                const float4 me = mult4(de, nib_e), mr = mult4(dr, nib_r);
-                const float4 ev = e_masked ? ev0 : f4mul(ev0, me);
-                const float4 rv = f4mul(rv0, mr);
-                if (rs.owned) put_e(ge + k, f4mul(f4mul(dq, rv), me));
-                put_r(gr + k, f4mul(f4mul(dq, ev), mr));
-            }
+            // (every lane runs the chain rule -- on zero rows where it is not the lead lane -- so that no branch stands
+            //  between the slab sums and the group's adds; only the lead lane's result is used)
+            const float4 me = mult4(de, nib_e), mr = mult4(dr, nib_r);
+            const float4 ev = e_masked ? ev0 : f4mul(ev0, me);
+            const float4 rv = f4mul(rv0, mr);
+            if (rs.owned) put(store_e, ge + k, f4mul(f4mul(dq, rv), me), act);
+            put(store_r, gr + k, f4mul(f4mul(dq, ev), mr), act);
         }
         return;
     }
@@ -433,6 +447,7 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
     for (int k0 = 128 * blockIdx.y; k0 < h; k0 += 128 * gridDim.y) {
         const int k = k0 + 4 * grp;
         const bool act = k < h, lead = act && sq == 0;
+        if (!__any(act)) continue;                   // a wave past the row's last column group (a scalar branch)
         float4 e1 = zero4, e2 = zero4, r1 = zero4, r2 = zero4;
         if (lead) {
             e1 = *reinterpret_cast<const float4 *>(e + k);  e2 = *reinterpret_cast<const float4 *>(e + h + k);
@@ -442,7 +457,6 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
         const uint32_t n_e1 = __shfl(nib, lane0), n_e2 = __shfl(nib, lane0 + 1);
         const uint32_t n_r1 = __shfl(nib, lane0 + 2), n_r2 = __shfl(nib, lane0 + 3);
         const float4 q1 = dq_sum(act ? k : 0, act), q2 = dq_sum(act ? h + k : 0, act);
-        if (!lead) continue;
         const float4 me1 = mult4(de, n_e1), me2 = mult4(de, n_e2), mr1 = mult4(dr, n_r1), mr2 = mult4(dr, n_r2);
         if (!e_masked) { e1 = f4mul(e1, me1); e2 = f4mul(e2, me2); }
         r1 = f4mul(r1, mr1);
@@ -455,12 +469,8 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
             de1 = f4fma(q1, r1, f4neg(f4mul(q2, r2)));    de2 = f4fma(q1, r2, f4mul(q2, r1));
             dr1 = f4fma(q1, e1, f4mul(q2, e2));           dr2 = f4fma(q1, e2, f4neg(f4mul(q2, e1)));
         }
-        if (rs.owned) {
-            put_e(ge + k, f4mul(de1, me1));
-            put_e(ge + h + k, f4mul(de2, me2));
-        }
-        put_r(gr + k, f4mul(dr1, mr1));
-        put_r(gr + h + k, f4mul(dr2, mr2));
+        if (rs.owned) put2(store_e, ge + k, h, f4mul(de1, me1), f4mul(de2, me2), act);
+        put2(store_r, gr + k, h, f4mul(dr1, mr1), f4mul(dr2, mr2), act);
     }
 }
 

@@ -17,6 +17,16 @@ __device__ __forceinline__ void atomic_add4(float *p, float4 v)
     atomicAdd(p, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
 }
 
+// Component sq of the float4 that the lead lane (sq == 0) of a 4-lane column group holds; every lane of the group must call it.
+// The group then adds p[sq] += component, one column per lane, so that the 64 lanes of a wave whose groups stand on consecutive
+// column quads add 64 consecutive floats: one 256-byte global_atomic_add_f32 in place of four with 16 lanes, 16 bytes apart,
+// each (float atomics execute at the memory side one 64-byte request at a time: four full requests, not sixteen quarter-filled).
+__device__ __forceinline__ float quad_lead_component(float4 v, int sq)
+{
+    const float x = dpp_mov<0x00>(v.x), y = dpp_mov<0x00>(v.y), z = dpp_mov<0x00>(v.z), w = dpp_mov<0x00>(v.w);
+    return sq == 0 ? x : sq == 1 ? y : sq == 2 ? z : w;
+}
+
 // deterministic sum of the per-workgroup loss partials by ONE workgroup (the order depends on its size)
 __device__ __forceinline__ void loss_reduce_block(const double *__restrict__ partials, int n, double *__restrict__ out)
 {
