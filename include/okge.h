@@ -677,6 +677,25 @@ typedef struct okge_adam_tensor {
 int okge_adam_step(const okge_adam_tensor *tensors, int32_t n_tensors /* 1..2 */, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int32_t zero_grad, void *stream);
 
+/* The same update -- okge_adam_step's arithmetic element for element -- on up to four tensors in ONE sweep launch behind the
+ * same one-workgroup step count (every distinct state advances once), gradients cleared in the sweep (zero_grad is implied, as in
+ * okge_adagrad_multi): the token tables, encoder tensors and batch-norm parameters of the token-encoded steps, Tucker3's E / R / W.
+ * row_touched (optional; needs n % row_len == 0, row_len % 4 == 0, touched_stamp in 1..255): a byte per row of row_len floats,
+ * okge_adagrad_multi's map.  A row whose byte equals touched_stamp takes the update with its gradient row, which is cleared; every
+ * other row holds an all-zero gradient BY CONTRACT and takes the update with g = 0 without its gradient row being read or written
+ * -- bit-identical to the dense update on a zero gradient: exp_avg and exp_avg_sq still decay and p still moves, as under
+ * torch.optim.Adam.  The map is not erased: use another stamp for the next update.  n >= 0 each (n = 0: only t advances);
+ * p, g, exp_avg, exp_avg_sq 16-byte aligned. */
+typedef struct okge_adam_multi_tensor {
+    float   *p, *g, *exp_avg, *exp_avg_sq;
+    int32_t *state;
+    int64_t  n;
+    const uint8_t *row_touched;
+    int32_t  row_len, touched_stamp;
+} okge_adam_multi_tensor;
+int okge_adam_multi(const okge_adam_multi_tensor *tensors, int32_t n_tensors /* 1..4 */, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, void *stream);
+
 /* Replaces torch.optim.SparseAdam.step (torch.optim._functional.sparse_adam) on the row-sparse gradients model_config.sparse leaves
  * (model.py:390-391), without its coalesce() (whose float atomics are not reproducible from run to run).  Occurrence rows, ids,
  * coalescing (ascending position, sequentially in fp32), untouched rows, bad ids, cost and graph behaviour are exactly
@@ -978,6 +997,23 @@ int okge_id_errors(int64_t *n_out);
  * workspace: 8448 bytes. */
 int okge_clip_grad_norm(float *g0, int64_t n0, float *g1, int64_t n1, float max_norm, double *norm_out_dev, void *workspace,
                         size_t workspace_bytes, void *stream);
+
+/* The same over up to eight gradient tensors (every parameter of a token-encoded or Tucker3 step): squares summed in double, the
+ * norm kept as fp32 like torch's, coef = min(1, max_norm / (norm + 1e-6f)) in fp32, every tensor scaled in place.  Three launches,
+ * nothing read back, capturable: partial sums over a fixed grid (which workgroup sums which element depends on the sizes alone,
+ * the partials are added in index order: the norm is bit-identical from run to run), the coefficient, the scaling -- which reads
+ * nothing but the coefficient when it is 1.  row_touched / row_len / touched_stamp (optional): okge_adagrad_multi's map; rows it
+ * does not stamp are neither read nor written (they hold zeros by the maps' contract, so the norm is the dense one).  A mapped
+ * tensor needs n % row_len == 0, row_len % 4 == 0, touched_stamp in 1..255 and a 16-byte aligned g.  n >= 0 each. */
+typedef struct okge_grad_tensor {
+    float   *g;
+    int64_t  n;
+    const uint8_t *row_touched;
+    int32_t  row_len, touched_stamp;
+} okge_grad_tensor;
+size_t okge_clip_grad_norm_multi_workspace_bytes(void);
+int okge_clip_grad_norm_multi(const okge_grad_tensor *tensors, int32_t n_tensors /* 1..8 */, float max_norm, double *norm_out_dev,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 /* out[b] = log sum_r exp(parts[r][b]): the global log_softmax denominator of the sharded KL loss from the all-gathered
  * per-shard row log-sum-exps of okge_row_logsumexp (trainer.py:99-101). */

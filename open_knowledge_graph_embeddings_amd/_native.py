@@ -55,6 +55,7 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_train_row_grads_workspace_bytes", "okge_adagrad_rows", "okge_adagrad_rows_workspace_bytes",
            "okge_rows_catch_up", "okge_adagrad_rows_decay",
            "okge_adam_step", "okge_adam_rows_workspace_bytes", "okge_adam_rows",
+           "okge_adam_multi", "okge_clip_grad_norm_multi", "okge_clip_grad_norm_multi_workspace_bytes",
            "okge_n3_workspace_bytes", "okge_n3_forward_backward",
            "okge_eval_loss_workspace_bytes", "okge_evaluate_fused_loss", "okge_evaluate_fused_batches_loss",
            "okge_evaluate_batch_loss_workspace_bytes", "okge_evaluate_batch_loss",
@@ -167,6 +168,15 @@ class AdamTensor(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("state", c_void_p), ("n", c_int64)]
 
 
+class AdamMultiTensor(Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("state", c_void_p), ("n", c_int64),
+                ("row_touched", c_void_p), ("row_len", c_int32), ("touched_stamp", c_int32)]
+
+
+class GradTensor(Structure):
+    _fields_ = [("g", c_void_p), ("n", c_int64), ("row_touched", c_void_p), ("row_len", c_int32), ("touched_stamp", c_int32)]
+
+
 class AdamRowsTensor(Structure):
     _fields_ = [("p", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("state", c_void_p), ("ids", c_void_p), ("g", c_void_p),
                 ("ld_g", c_int64), ("n", c_int32), ("table_rows", c_int32), ("row_len", c_int32), ("_pad", c_int32)]
@@ -265,6 +275,12 @@ def lib():
                                           c_size_t, c_void_p]
     L.okge_adam_step.restype = c_int32
     L.okge_adam_step.argtypes = [POINTER(AdamTensor), c_int32, c_float, c_float, c_float, c_float, c_float, c_int32, c_void_p]
+    L.okge_adam_multi.restype = c_int32
+    L.okge_adam_multi.argtypes = [POINTER(AdamMultiTensor), c_int32, c_float, c_float, c_float, c_float, c_float, c_void_p]
+    L.okge_clip_grad_norm_multi_workspace_bytes.restype = c_size_t
+    L.okge_clip_grad_norm_multi_workspace_bytes.argtypes = []
+    L.okge_clip_grad_norm_multi.restype = c_int32
+    L.okge_clip_grad_norm_multi.argtypes = [POINTER(GradTensor), c_int32, c_float, c_void_p, c_void_p, c_size_t, c_void_p]
     L.okge_adam_rows_workspace_bytes.restype = c_size_t
     L.okge_adam_rows_workspace_bytes.argtypes = [c_int64, c_int64]
     L.okge_adam_rows.restype = c_int32

@@ -133,7 +133,7 @@ class BigramTrainStep(EncoderTrainStep):
         ps.backward(sl, calls, dV, sl.dW, sl.d_conv, sl.d_bn)
 
     def optimizer_step(self):
-        self.engine.adagrad_multi(self.entity.optimizer_tensors() + self.relation.optimizer_tensors(), self.lr, self.weight_decay, self.eps)
+        self._update(self._param_groups())
 
 
 BigramEncodeFn = EncodeFn                          # (the shared Function: BigramSlot says what its encode takes)
@@ -249,13 +249,15 @@ class BigramPoolingRelationEmbedder(TokenEncoderEmbedder):
             grads += [sl.dW, sl.d_conv] + ([sl.d_bn[:sl.d], sl.d_bn[sl.d:]] if sl.bn is not None else [])
         return params, grads
 
-    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0):
+    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
+                   grad_clip=0.0):
         """The training driver for this model: shares the module's parameters (updated in place).  The conv weight and the
-        batch-norm parameters of each slot become views of one flat buffer (one optimizer segment)."""
+        batch-norm parameters of each slot become views of one flat buffer (one optimizer segment).  optimizer / betas /
+        grad_clip: as on FusedTrainStep."""
         slots = self._bigram_slots(share=True)
         return BigramTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
                                label_smoothing=label_smoothing, dropout=self.entity_dropout, relation_dropout=self.relation_dropout,
-                               seed=self.dropout_seed)
+                               seed=self.dropout_seed, optimizer=optimizer, betas=betas, grad_clip=grad_clip)
 
 
 class BigramPoolingComplexRelationModel(ComplexRelationScorer, BigramPoolingRelationEmbedder):

@@ -1,6 +1,7 @@
 // C ABI (include/okge.h), host side: the optimizers and the gradient scaling around them.  Dense Adagrad (one, two, up to four
 // tensors), the row-sparse Adagrad with and without deferred weight decay, the lazy (deferred decay) dense step and its pool
-// catch-up, dense and row-sparse Adam, scaling, clipping, and the merge of per-shard row log-sum-exps.
+// catch-up, dense (two or up to four tensors) and row-sparse Adam, scaling, clipping (two or up to eight tensors), and the merge of
+// per-shard row log-sum-exps.
 #include "okge_host.h"
 
 using namespace okge;
@@ -13,6 +14,15 @@ int check_stamp(const void *row_touched, int32_t touched_stamp)
 {
     if (row_touched && (touched_stamp < 1 || touched_stamp > 255)) return fail(OKGE_ERR_INVALID, "touched_stamp must lie in 1..255");
     return OKGE_OK;
+}
+
+// the touched-row map of a dense tensor of n floats (okge_adagrad_multi, okge_adam_multi, okge_clip_grad_norm_multi)
+int check_touched_rows(const void *row_touched, int32_t row_len, int32_t touched_stamp, int64_t n)
+{
+    if (!row_touched) return OKGE_OK;
+    if (row_len <= 0 || row_len % 4 || n % row_len || n / row_len > INT32_MAX)
+        return fail(OKGE_ERR_INVALID, "a touched-row map needs rows of a multiple of 4 floats that tile the tensor");
+    return check_stamp(row_touched, touched_stamp);
 }
 
 int check_adagrad(const float *p, const float *g, const float *state_sum, int64_t n)
@@ -130,9 +140,7 @@ int okge_adagrad_multi(const okge_adagrad_tensor *tensors, int32_t n_tensors, fl
         const okge_adagrad_tensor &t = tensors[i];
         if (int rc = check_adagrad(t.p, t.g, t.state_sum, t.n)) return rc;
         if (t.row_touched) {
-            if (t.row_len <= 0 || t.row_len % 4 || t.n % t.row_len || t.n / t.row_len > INT32_MAX)
-                return fail(OKGE_ERR_INVALID, "a touched-row map needs rows of a multiple of 4 floats that tile the tensor");
-            if (int rc = check_stamp(t.row_touched, t.touched_stamp)) return rc;
+            if (int rc = check_touched_rows(t.row_touched, t.row_len, t.touched_stamp, t.n)) return rc;
             if (!t.zero_grad) return fail(OKGE_ERR_INVALID, "a touched-row map needs zero_grad (rows not stamped must hold zero gradients)");
         }
         segs[i] = AdagradSegM{t.p, t.g, t.state_sum, t.n, t.row_touched, t.row_len, t.touched_stamp, t.zero_grad};
@@ -202,6 +210,27 @@ int okge_adam_step(const okge_adam_tensor *tensors, int32_t n_tensors, float lr,
     hipStream_t st = as_stream(stream);
     if (int rc = OKGE_TIMED("adam_prologue", "adam_prologue", st, launch_adam_prologue(states, n_tensors, lr, beta1, beta2, st))) return rc;
     return OKGE_TIMED("adam", "adam", st, launch_adam2(segs[0], segs[1], beta1, beta2, eps, weight_decay, zero_grad, st));
+}
+
+int okge_adam_multi(const okge_adam_multi_tensor *tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, void *stream)
+{
+    if (!tensors || n_tensors < 1 || n_tensors > ADAM_MULTI_MAX_SEGS) return fail(OKGE_ERR_INVALID, "1 to 4 tensors per adam launch");
+    AdamSegM segs[ADAM_MULTI_MAX_SEGS] = {};
+    int32_t *states[ADAM_MULTI_MAX_SEGS] = {};
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_adam_multi_tensor &x = tensors[k];
+        if (!x.p || !x.g || !x.exp_avg || !x.exp_avg_sq || !x.state || x.n < 0) return fail(OKGE_ERR_INVALID, "bad adam arguments");
+        if (!aligned16(x.p, x.g, x.exp_avg, x.exp_avg_sq)) return fail(OKGE_ERR_INVALID, "adam buffers must be 16-byte aligned");
+        if (int rc = check_touched_rows(x.row_touched, x.row_len, x.touched_stamp, x.n)) return rc;
+        segs[k] = AdamSegM{x.p, x.g, x.exp_avg, x.exp_avg_sq, x.state, x.n, x.row_touched, x.row_len, x.touched_stamp};
+        states[k] = x.state;
+    }
+    if (int rc = check_adam_hyper(lr, beta1, beta2, eps)) return rc;
+    if (!(weight_decay >= 0.f)) return fail(OKGE_ERR_INVALID, "adam needs weight_decay >= 0");
+    hipStream_t st = as_stream(stream);
+    if (int rc = OKGE_TIMED("adam_prologue", "adam_prologue", st, launch_adam_prologue(states, n_tensors, lr, beta1, beta2, st))) return rc;
+    return OKGE_TIMED("adam", "adam_multi", st, launch_adam_multi(segs, n_tensors, beta1, beta2, eps, weight_decay, st));
 }
 
 size_t okge_adam_rows_workspace_bytes(int64_t n0, int64_t n1) { return okge_adagrad_rows_workspace_bytes(n0, n1); }
@@ -359,6 +388,32 @@ int okge_clip_grad_norm(float *g0, int64_t n0, float *g1, int64_t n1, float max_
         if (e == hipSuccess && g1 && n1 > 0) e = launch_scale(g1, n1, coef, st);
     }
     return hip_ok(e, "scale gradients");
+}
+
+constexpr int CLIP_MULTI_PARTIALS = 1024;       // the fixed grid of the partial sums
+
+size_t okge_clip_grad_norm_multi_workspace_bytes(void) { return CLIP_MULTI_PARTIALS * sizeof(double) + 256; }
+
+int okge_clip_grad_norm_multi(const okge_grad_tensor *tensors, int32_t n_tensors, float max_norm, double *norm_out_dev, void *workspace,
+                              size_t workspace_bytes, void *stream)
+{
+    if (!tensors || n_tensors < 1 || n_tensors > CLIP_MAX_SEGS) return fail(OKGE_ERR_INVALID, "1 to 8 tensors per clip_grad_norm launch");
+    GradSeg segs[CLIP_MAX_SEGS] = {};
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_grad_tensor &x = tensors[k];
+        if (!x.g || x.n < 0) return fail(OKGE_ERR_INVALID, "bad clip_grad_norm arguments");
+        if (int rc = check_touched_rows(x.row_touched, x.row_len, x.touched_stamp, x.n)) return rc;
+        if (x.row_touched && !aligned16(x.g)) return fail(OKGE_ERR_INVALID, "gradient rows under a touched-row map must be 16-byte aligned");
+        segs[k] = GradSeg{x.g, x.n, x.row_touched, x.row_len, x.touched_stamp};
+    }
+    if (!(max_norm > 0.f)) return fail(OKGE_ERR_INVALID, "clip_grad_norm needs max_norm > 0");
+    if (!workspace || workspace_bytes < okge_clip_grad_norm_multi_workspace_bytes())
+        return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_clip_grad_norm_multi_workspace_bytes)");
+    hipStream_t st = as_stream(stream);
+    double *partial = static_cast<double *>(workspace);
+    float *coef = reinterpret_cast<float *>(static_cast<char *>(workspace) + CLIP_MULTI_PARTIALS * sizeof(double));
+    return OKGE_TIMED("clip_grad_norm", "clip_grad_norm_multi", st,
+                      launch_clip_multi(segs, n_tensors, max_norm, partial, CLIP_MULTI_PARTIALS, coef, norm_out_dev, st));
 }
 
 int okge_merge_logsumexp(const float *parts, int32_t world, int32_t B, float *out, void *stream)

@@ -254,6 +254,13 @@ hipError_t launch_adagrad2(float *p0, float *g0, float *s0, int64_t n0, float *p
 // ||g|| -> norm_dev (double); the caller scales with launch_scale (trainer.py:236-240)
 hipError_t launch_clip_coef(const float *g0, int64_t n0, const float *g1, int64_t n1, float max_norm, double *partial,
                             int n_partial, float *coef_dev, double *norm_dev, hipStream_t st);
+// the same over up to eight gradient tensors, three launches: n_partial partial sums (a fixed grid: which workgroup sums which
+// element depends on the sizes alone), the coefficient, the scaling (nothing but the coefficient is read when it is 1).  A tensor
+// may come with a touched-row byte map: rows whose byte differs from `stamp` are neither read nor written
+constexpr int CLIP_MAX_SEGS = 8;
+struct GradSeg { float *g; int64_t n; const uint8_t *touched; int32_t row_len, stamp; };
+hipError_t launch_clip_multi(const GradSeg *segs, int n_segs, float max_norm, double *partial, int n_partial, float *coef_dev,
+                             double *norm_dev, hipStream_t st);
 // dense Adagrad over up to four tensors in one launch; a tensor may come with a touched-row byte map (rows whose byte differs
 // from `stamp` hold an all-zero gradient by contract: it is neither read nor cleared)
 constexpr int ADAGRAD_MAX_SEGS = 4;
@@ -268,9 +275,14 @@ hipError_t launch_adagrad_lazy(const LazySeg *segs, int n_segs, int32_t *counter
 // step size }; the prologue (one workgroup) advances every distinct state by one step and forms the three scalars of the new t
 constexpr int ADAM_MAX_SEGS = 2;
 struct AdamSeg { float *p, *g, *m, *v; const int32_t *state; int64_t n; };
-struct AdamStates { int32_t *state[ADAM_MAX_SEGS]; int n; };
+constexpr int ADAM_MULTI_MAX_SEGS = 4;
+struct AdamStates { int32_t *state[ADAM_MULTI_MAX_SEGS]; int n; };
 hipError_t launch_adam_prologue(int32_t *const *states, int n_states, float lr, float beta1, float beta2, hipStream_t st);
 hipError_t launch_adam2(const AdamSeg &a, const AdamSeg &b, float beta1, float beta2, float eps, float wd, int zero_grad, hipStream_t st);
+// dense Adam over up to four tensors in one launch, gradients cleared in the sweep; a tensor may come with a touched-row byte map
+// (AdagradSegM's contract: a row whose byte differs from `stamp` takes the update with g = 0, its gradient row neither read nor cleared)
+struct AdamSegM { float *p, *g, *m, *v; const int32_t *state; int64_t n; const uint8_t *touched; int32_t row_len, stamp; };
+hipError_t launch_adam_multi(const AdamSegM *segs, int n_segs, float beta1, float beta2, float eps, float wd, hipStream_t st);
 // row-sparse training (okge_sparse.hip).  Gather: the occurrence rows of one batch -- candidates, prefix entities, relations --
 // as the two small tables EV (N + B rows) / RV (B rows) of the relabelled problem, and the position ids that name them
 // (pos_ids[0..B) = N + i, pos_ids[B..2B) = i).

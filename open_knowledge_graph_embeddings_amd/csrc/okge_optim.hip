@@ -3,7 +3,8 @@
 //                                                           dense sweep (+ zero_grad)        utils/optim.py:139-160 / torch.optim.Adagrad
 //   adagrad_lazy_kernel                                     the weight-decay-only updates of rows no batch names, deferred
 //   sqnorm_partial_kernel, clip_coef_kernel                 clip_grad_norm_'s coefficient     trainer.py:236-240
-//   scale_kernel, rescale2_kernel                           x *= a device scalar
+//   sqnorm_multi_kernel, scale_multi_kernel                 the same over up to eight tensors, touched-row maps honoured
+//   scale_kernel, rescale2_kernel                          x *= a device scalar
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -221,6 +222,68 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const double *__restrict
     }
 }
 
+// ---- okge_clip_grad_norm_multi: the same over up to eight tensors, a tensor optionally with a touched-row byte map -------------
+// One walk for the sum and the scaling: thread `first` of the grid owns the quads first, first + stride, ... of every tensor
+// (elements 4q .. 4q + 3, in that order) and, below n & 3, one tail element.  Which thread sees which element is fixed by the
+// sizes and the grid, so with a fixed grid the partial sums -- and the norm -- come out bit-identical from run to run, whether a
+// quad is read as one 16-byte access (base 16-byte aligned) or as four floats.  With a map, a row whose byte differs from the
+// stamp is skipped whole (zeros by the maps' contract: neither read nor written); rows are whole quads, there is no tail.
+struct GradSegsDev { GradSeg s[CLIP_MAX_SEGS]; int n; };
+
+template <typename F>
+__device__ __forceinline__ void grad_walk(const GradSeg &sg, int64_t first, int64_t stride, F &&f)
+{
+    const int64_t n4 = sg.n >> 2;
+    const bool vec = (reinterpret_cast<uintptr_t>(sg.g) & 15) == 0;
+    const uint32_t row4 = sg.touched ? (uint32_t)(sg.row_len >> 2) : 1u;
+    const uint8_t stamp = (uint8_t)sg.stamp;
+    for (int64_t i = first; i < n4; i += stride) {
+        if (sg.touched && sg.touched[i >> 32 ? i / row4 : (int64_t)((uint32_t)i / row4)] != stamp) continue;
+        float *x = sg.g + (i << 2);
+        if (vec) {
+            float4 v = *reinterpret_cast<float4 *>(x);
+            if (f(v.x, v.y, v.z, v.w)) *reinterpret_cast<float4 *>(x) = v;
+        } else if (f(x[0], x[1], x[2], x[3])) {
+            // (f wrote through the references)
+        }
+    }
+    if (first < (sg.n & 3)) {
+        float pad0 = 0.f, pad1 = 0.f, pad2 = 0.f;
+        f(sg.g[(n4 << 2) + first], pad0, pad1, pad2);
+    }
+}
+
+__global__ __launch_bounds__(256) void sqnorm_multi_kernel(const GradSegsDev segs, double *__restrict__ partial)
+{
+    __shared__ double red[4];
+    double acc = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int k = 0; k < segs.n; ++k)
+        grad_walk(segs.s[k], first, stride, [&acc](float &a, float &b, float &c, float &d) {
+            acc += (double)a * (double)a;
+            acc += (double)b * (double)b;
+            acc += (double)c * (double)c;
+            acc += (double)d * (double)d;
+            return false;
+        });
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ __launch_bounds__(256) void scale_multi_kernel(const GradSegsDev segs, const float *__restrict__ coef)
+{
+    const float c = *coef;
+    if (c == 1.0f) return;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int k = 0; k < segs.n; ++k)
+        grad_walk(segs.s[k], first, stride, [c](float &a, float &b, float &d, float &e) {
+            a *= c; b *= c; d *= c; e *= c;
+            return true;
+        });
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------
 hipError_t launch_adagrad(float *p, float *g, float *sum, int64_t n, float lr, float wd, float eps, int zero_grad,
                           hipStream_t st)
@@ -303,6 +366,25 @@ hipError_t launch_clip_coef(const float *g0, int64_t n0, const float *g1, int64_
 {
     hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(n_partial), dim3(256), 0, st, g0, n0, g1, n1, partial);
     hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, st, partial, n_partial, max_norm, coef_dev, norm_dev);
+    return hipGetLastError();
+}
+
+hipError_t launch_clip_multi(const GradSeg *segs, int n_segs, float max_norm, double *partial, int n_partial, float *coef_dev,
+                             double *norm_dev, hipStream_t st)
+{
+    if (n_segs <= 0 || n_segs > CLIP_MAX_SEGS) return hipErrorInvalidValue;
+    GradSegsDev a;
+    std::memset(&a, 0, sizeof(a));
+    a.n = n_segs;
+    int64_t n4 = 0;
+    for (int k = 0; k < n_segs; ++k) {
+        a.s[k] = segs[k];
+        n4 = std::max(n4, (segs[k].n + 3) / 4);
+    }
+    hipLaunchKernelGGL(sqnorm_multi_kernel, dim3(n_partial), dim3(256), 0, st, a, partial);
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, st, partial, n_partial, max_norm, coef_dev, norm_dev);
+    const int blocks = (int)std::max<int64_t>(1, std::min((int64_t)4096, (n4 + 255) / 256));
+    hipLaunchKernelGGL(scale_multi_kernel, dim3(blocks), dim3(256), 0, st, a, coef_dev);
     return hipGetLastError();
 }
 

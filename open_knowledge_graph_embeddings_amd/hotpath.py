@@ -670,6 +670,43 @@ class HotPath:
         N.check(self.lib.okge_adam_step(arr, len(tensors), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                         int(zero_grad), self._stream()), "okge_adam_step")
 
+    def adam_multi(self, tensors, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """okge_adam_multi: okge_adam_step's update on up to four (p, g, exp_avg, exp_avg_sq, state[, touched_map, stamp]) tuples in
+        one sweep, gradients cleared; a tensor with a touched-row byte map takes g = 0 on the rows the map does not stamp, whose
+        gradient rows are neither read nor cleared.  Every distinct state advances by one step on the device."""
+        arr = (N.AdamMultiTensor * len(tensors))()
+        for a, t in zip(arr, tensors):
+            p, g, m, v, st = t[:5]
+            for x in (p, g, m, v):
+                if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous():
+                    raise N.OkgeError("adam_multi: contiguous fp32 tensors on the engine's device")
+            if g.numel() != p.numel() or m.numel() != p.numel() or v.numel() != p.numel():
+                raise N.OkgeError("adam_multi: p, g, exp_avg and exp_avg_sq must have one size")
+            if st.dtype != torch.int32 or st.numel() != 4 or st.device != self.device or not st.is_contiguous():
+                raise N.OkgeError("adam_multi: the state is a contiguous int32[4] tensor on the engine's device (HotPath.adam_state)")
+            a.p, a.g, a.exp_avg, a.exp_avg_sq, a.state, a.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), st.data_ptr(), p.numel()
+            if len(t) > 5 and t[5] is not None:
+                a.row_touched, a.row_len, a.touched_stamp = t[5].data_ptr(), p.shape[1], int(t[6])
+        N.check(self.lib.okge_adam_multi(arr, len(tensors), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                         self._stream()), "okge_adam_multi")
+
+    def clip_grad_norm_multi_(self, tensors, max_norm, norm_out=None):
+        """okge_clip_grad_norm_multi: torch.nn.utils.clip_grad_norm_ over up to eight gradient tensors, in place; tensors: g or
+        (g, touched_map, stamp) -- gradient rows a map does not stamp are neither read nor written.  norm_out: device double[1]."""
+        arr = (N.GradTensor * len(tensors))()
+        for a, t in zip(arr, tensors):
+            g, touched, stamp = t if isinstance(t, (tuple, list)) else (t, None, 0)
+            if g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous():
+                raise N.OkgeError("clip_grad_norm_multi: contiguous fp32 tensors on the engine's device")
+            a.g, a.n = g.data_ptr(), g.numel()
+            if touched is not None:
+                a.row_touched, a.row_len, a.touched_stamp = touched.data_ptr(), g.shape[1], int(stamp)
+        if getattr(self, "_clip_multi_ws", None) is None:
+            self._clip_multi_ws = torch.empty(int(self.lib.okge_clip_grad_norm_multi_workspace_bytes()), dtype=torch.uint8, device=self.device)
+        ws = self._clip_multi_ws
+        N.check(self.lib.okge_clip_grad_norm_multi(arr, len(tensors), float(max_norm), _ptr(norm_out), ws.data_ptr(), ws.numel(),
+                                                   self._stream()), "okge_clip_grad_norm_multi")
+
     def adam_rows(self, tensors, lr, betas=(0.9, 0.999), eps=1e-8):
         """okge_adam_rows: torch.optim.SparseAdam's update on one or two (p, exp_avg, exp_avg_sq, state, ids, g) tuples -- the
         occurrence rows g (n, row_len) of the int32 device ids are coalesced per id in ascending position and only the named rows

@@ -127,9 +127,7 @@ class LSTMTrainStep(EncoderTrainStep):
             ps.backward(sl, calls, X, dV, sl.dW, sl.dlstm, sl.d_bn if sl.bn is not None else None)
 
     def optimizer_step(self):
-        tensors = self.entity.optimizer_tensors() + ([] if self.relation_unused else self.relation.optimizer_tensors())
-        for i in range(0, len(tensors), 4):                       # (okge_adagrad_multi: up to four tensors per launch)
-            self.engine.adagrad_multi(tensors[i:i + 4], self.lr, self.weight_decay, self.eps)
+        self._update(self._param_groups())                         # (up to four tensors per launch; an unused relation slot: none)
         self._sync_module_batchnorms()
 
 
@@ -231,13 +229,14 @@ class LSTMRelationEmbedder(TokenEncoderEmbedder):
             grads += sl.dlstm
         return params, grads
 
-    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0):
+    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
+                   grad_clip=0.0):
         """The training driver for this model: shares the module's parameters (updated in place).  The four LSTM tensors of
-        each slot become views of one flat buffer (one optimizer segment)."""
+        each slot become views of one flat buffer (one optimizer segment).  optimizer / betas / grad_clip: as on FusedTrainStep."""
         slots = self._lstm_slots(flat=True)
         st = LSTMTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
                            label_smoothing=label_smoothing, dropout=self.entity_dropout, relation_dropout=self.relation_dropout,
-                           seed=self.dropout_seed)
+                           seed=self.dropout_seed, optimizer=optimizer, betas=betas, grad_clip=grad_clip)
         if self.entity_batchnorm is not None:
             st.module_batchnorms = ((slots[0], self.entity_batchnorm), (slots[1], self.relation_batchnorm))
         return st

@@ -32,6 +32,7 @@ import torch.distributed as dist
 
 from . import _native as N
 from . import hotpath as H
+from .step_optim import refuse_for_replicas
 from .train_step import FusedTrainStep
 
 
@@ -426,6 +427,7 @@ class ReplicaStep:
 
     def __init__(self, inner, group=None, sparse=True):
         N.refuse_bias_scorer(getattr(inner, "scorer", None), type(self).__name__)
+        refuse_for_replicas(inner, type(self).__name__)
         self.inner, self.group = inner, group
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
         self.grads, self.stats = list(inner.grad_tensors()), list(inner.stat_tensors())

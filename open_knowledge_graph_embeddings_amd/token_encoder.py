@@ -95,7 +95,14 @@ class EncoderTrainStep(VT.VirtualTableStep):
             out += [sl.W, sl.dW, sl.sumW, sl.flat, sl.d_flat, sl.sum_flat]
             if sl.bn is not None:
                 out += self._bn_state(sl)
-        return out
+        return out + self._optimizer_state()
+
+    def _param_groups(self, every=False):
+        """the slots' optimizer_tensors(); every=False: without those of a slot the scorer leaves unused"""
+        return [t for sl in (self.entity, self.relation) if every or not self._unused(sl) for t in sl.optimizer_tensors()]
+
+    def _unused(self, sl):
+        return False
 
     def flush(self):
         """(no deferred updates here: every parameter is current after every step)"""

@@ -205,9 +205,17 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
     (Trainer.compute_one_batch, trainer.py:181-257, over model.py:762-796)."""
 
     def __init__(self, entity: TokenSlot, relation: TokenSlot, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8,
-                 label_smoothing=0.0, dropout=0.0, seed=0, engine=None, decay_window=None):
+                 label_smoothing=0.0, dropout=0.0, seed=0, engine=None, decay_window=None, optimizer="adagrad", betas=(0.9, 0.999),
+                 grad_clip=0.0):
         super().__init__(entity, relation, scorer, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
-                         label_smoothing=label_smoothing, dropout=dropout, seed=seed, engine=engine)
+                         label_smoothing=label_smoothing, dropout=dropout, seed=seed, engine=engine, optimizer=optimizer, betas=betas,
+                         grad_clip=grad_clip)
+        # optimizer="adam": every row's moments decay every step, so there is no decay-only update to defer -- the window is 1,
+        # whatever the table size or OKGE_LAZY_DECAY; the sweep still skips the gradient rows the maps do not stamp
+        if self.optimizer == "adam":
+            if decay_window not in (None, 1):
+                raise ValueError("decay_window (deferred weight decay) belongs to the Adagrad step: Adam moves every row every step")
+            decay_window = 1
         # decay_window (OKGE_LAZY_DECAY; 1 = every row every step): the reference's Adagrad moves EVERY token row in
         # every step by its weight-decay term (utils/optim.py:139-160) -- 1 GB of read-modify-write at configs[4], 175 us of a
         # 0.78 ms step, for rows nothing reads.  With a window W > 1 a row no batch names takes its pending decay-only steps
@@ -242,7 +250,13 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
                 out += [sl.bn, sl.d_bn, sl.sum_bn, sl.running_mean, sl.running_var]
         if self.decay_window > 1:         # (a caller that restores a snapshot restores the step counters with it)
             out += [self.entity.row_steps, self.relation.row_steps, self._counters]
-        return out
+        return out + self._optimizer_state()
+
+    def _param_groups(self, every=False):
+        """token tables (with the maps the pooling backward stamps) + batch-norm parameters"""
+        e, r = self.entity, self.relation
+        return [(sl.W, sl.dW, sl.sumW, getattr(sl, "touched", None), getattr(sl, "stamp", 0)) for sl in (e, r)] + \
+            [(sl.bn, sl.d_bn, sl.sum_bn) for sl in (e, r) if sl.bn is not None]
 
     # -- deferred weight-decay-only updates (decay_window > 1) ---------------------------------------------------------
     def _hparams(self):
@@ -349,14 +363,13 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
             self._settle_hparams()
             lr, wd, eps = self._hparams()
             tensors = self._lazy_tables() + [(sl.bn, sl.d_bn, sl.sum_bn) for sl in (e, r) if sl.bn is not None]
+            self._clip(self._param_groups())          # (only stamped rows carry a gradient: the deferred rows are not its business)
             eng.adagrad_lazy(tensors, self._counters, self.decay_window, False, lr, wd, eps)
             self._pending = (lr, wd, eps)
             self._after_update()
             return
         # one launch: token tables (gradient rows the backward did not stamp are neither read nor cleared) + batch-norm parameters
-        tensors = [(sl.W, sl.dW, sl.sumW, sl.touched, sl.stamp) for sl in (e, r)]
-        tensors += [(sl.bn, sl.d_bn, sl.sum_bn) for sl in (e, r) if sl.bn is not None]
-        eng.adagrad_multi(tensors, self.lr, self.weight_decay, self.eps)
+        self._update(self._param_groups())
         self._after_update()
 
     def _after_update(self):
@@ -603,12 +616,15 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
         return eng.forward_backward(EV, RV, self.scorer_name, vb, None, None, loss=loss, label_smoothing=label_smoothing,
                                     normalizer=1.0, scores=scores, loss_only=True)
 
-    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0):
-        """The training driver for this model: shares the module's parameters (updated in place)."""
+    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
+                   grad_clip=0.0):
+        """The training driver for this model: shares the module's parameters (updated in place).  optimizer / betas /
+        grad_clip: as on FusedTrainStep."""
         self.flush_steps()                 # an earlier driver (another epoch's learning rate, ...) may still owe decay-only steps
         slots = self._module_slots()
         st = TokenPooledTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
-                                  label_smoothing=label_smoothing, dropout=self.entity_dropout, seed=self.dropout_seed)
+                                  label_smoothing=label_smoothing, dropout=self.entity_dropout, seed=self.dropout_seed,
+                                  optimizer=optimizer, betas=betas, grad_clip=grad_clip)
         if self.entity_batchnorm is not None:
             st.module_batchnorms = ((slots[0], self.entity_batchnorm), (slots[1], self.relation_batchnorm))
         import weakref

@@ -16,6 +16,7 @@ import torch
 
 from . import _native as N
 from . import hotpath as H
+from .step_optim import StepOptimizer, check_optimizer
 from .model import LookupBaseRelationEmbedder, Models, PAD, RelationEmbedder, RelationScorer, _wants_grad
 
 MAX_SLOT = 256                                     # d and r_e the fold / backward kernels take
@@ -89,14 +90,16 @@ class Tucker3Kernels:
         return out
 
 
-class Tucker3TrainStep:
+class Tucker3TrainStep(StepOptimizer):
     """forward + loss + backward + Adagrad for LookupTucker3RelationModel (Trainer.compute_one_batch, trainer.py:181-257):
     encode rows -> fold -> train tiles -> tucker3 backward -> scatter -> one dense Adagrad launch over (E, R, W).
     E (|E|, d), R (|R|, r_e), W (d^2, r_e) are updated in place.  dropout = the entity rows' and candidates' drop probability
-    (input_dropout and dropout combined), relation_dropout = the relation rows' (relation_input_dropout)."""
+    (input_dropout and dropout combined), relation_dropout = the relation rows' (relation_input_dropout).  optimizer / betas /
+    grad_clip: as on FusedTrainStep (step_optim.py), over E, R and W."""
 
     def __init__(self, E, R, W, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, dropout=0.0,
-                 relation_dropout=0.0, seed=0, engine=None):
+                 relation_dropout=0.0, seed=0, engine=None, optimizer="adagrad", betas=(0.9, 0.999), grad_clip=0.0):
+        check_optimizer(optimizer, betas)
         for t in (E, R, W):
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise N.OkgeError("tucker3: parameters must be contiguous fp32 tensors")
@@ -117,9 +120,13 @@ class Tucker3TrainStep:
         self.loss_out = torch.zeros(1, dtype=torch.float64, device=self.device)
         self.shard = H.Shard(0, E.shape[0], 0)
         self._B = -1
+        self._init_optimizer(optimizer, betas, grad_clip)
 
     def state_tensors(self):
-        return [self.E, self.R, self.W, self.dE, self.dR, self.dW, self.sumE, self.sumR, self.sumW]
+        return [self.E, self.R, self.W, self.dE, self.dR, self.dW, self.sumE, self.sumR, self.sumW] + self._optimizer_state()
+
+    def _param_groups(self, every=False):
+        return [(self.E, self.dE, self.sumE), (self.R, self.dR, self.sumR), (self.W, self.dW, self.sumW)]
 
     def flush(self):
         """(no deferred updates here: every parameter is current after every step)"""
@@ -211,8 +218,7 @@ class Tucker3TrainStep:
         return self._tiles(cb, B, normalizer, loss_only=True)
 
     def optimizer_step(self):
-        self.engine.adagrad_multi([(self.E, self.dE, self.sumE), (self.R, self.dR, self.sumR), (self.W, self.dW, self.sumW)],
-                                  self.lr, self.weight_decay, self.eps)
+        self._update(self._param_groups())
 
     # -- evaluation ------------------------------------------------------------------------------------------------------
     def scores(self, batch: H.PrefixBatch, out=None):
@@ -515,11 +521,14 @@ class ProjectedLookupRelationEmbedder(LookupBaseRelationEmbedder):
             return Tucker3PrefixScoreFn.apply(flat(ent), flat(rel), flat(cand), weight, self.kernels(), sp)
 
     # -- training drivers ----------------------------------------------------------------------------------------------
-    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0):
-        """The fused training driver: shares the module's parameters (updated in place)"""
+    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
+                   grad_clip=0.0):
+        """The fused training driver: shares the module's parameters (updated in place).  optimizer / betas / grad_clip: as on
+        FusedTrainStep."""
         return Tucker3TrainStep(self.E, self.R, self.W, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
                                 label_smoothing=label_smoothing, dropout=1.0 - (1.0 - self.input_dropout) * (1.0 - self.dropout),
-                                relation_dropout=self.relation_input_dropout, seed=self.dropout_seed, engine=self.engine())
+                                relation_dropout=self.relation_input_dropout, seed=self.dropout_seed, engine=self.engine(),
+                                optimizer=optimizer, betas=betas, grad_clip=grad_clip)
 
     def autograd_step(self, loss, label_smoothing):
         """the cached Tucker3TrainStep behind AddLossModule: shares the module's parameters; its optimizer is NOT used (the

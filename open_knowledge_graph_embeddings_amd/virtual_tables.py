@@ -15,6 +15,7 @@ import torch
 
 from . import _native as N
 from . import hotpath as H
+from .step_optim import StepOptimizer, check_optimizer
 
 
 def row_ranges(n_cand, n_po, n_sp):
@@ -64,20 +65,23 @@ class VirtualTables:
         return tuple(b[:n] for b, n in zip(self._bufs, rows))
 
 
-class VirtualTableStep:
+class VirtualTableStep(StepOptimizer):
     """Skeleton of a training step that encodes a batch's rows into virtual tables: count the step, get the buffers, `_encode`,
     the fused call on the virtual tables, `_backward`.  A subclass brings optimizer_step() and the two hooks:
         _encode(batch, bufs) -> saved  fill EX / RX (and EV / RV behind a batch-norm) with the batch's rows
         _backward(batch, bufs, saved)  carry dEV / dRV back through the encoder into the slots' gradients
     entity / relation are its slots (.W, .d, .bn or None).  dropout is the entity streams', relation_dropout (default: the
-    same) the relation streams' drop probability."""
+    same) the relation streams' drop probability.  optimizer / betas / grad_clip: as on FusedTrainStep (step_optim.py) -- "adam"
+    is torch.optim.Adam's update (coupled weight decay, no amsgrad) over every tensor the step's Adagrad moves, grad_clip > 0
+    clips their gradients' global norm at the head of optimizer_step(); a subclass lists the tensors in _param_groups()."""
 
     bias_scorers = False              # a subclass that leaves a data-bias scorer's unused slot untouched says True
 
     def __init__(self, entity, relation, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0,
-                 dropout=0.0, relation_dropout=None, seed=0, engine=None):
+                 dropout=0.0, relation_dropout=None, seed=0, engine=None, optimizer="adagrad", betas=(0.9, 0.999), grad_clip=0.0):
         if not self.bias_scorers:
             N.refuse_bias_scorer(scorer, type(self).__name__)
+        check_optimizer(optimizer, betas)
         self.entity, self.relation, self.scorer, self.loss = entity, relation, scorer, loss
         self.lr, self.weight_decay, self.eps, self.label_smoothing = lr, weight_decay, eps, label_smoothing
         self.dropout = dropout
@@ -89,6 +93,7 @@ class VirtualTableStep:
         self.loss_out = torch.zeros(1, dtype=torch.float64, device=self.device)
         self.step_dev = None              # device step counter, attached by GraphedTrainStep
         self.module_batchnorms = ()       # ((slot, nn.BatchNorm1d), ...) of an attached module, set by its train_step()
+        self._init_optimizer(optimizer, betas, grad_clip)
 
     def step(self, batch: H.PrefixBatch, normalizer=None):
         """`batch` carries ENTITY / RELATION ids exactly as for the lookup models."""
