@@ -456,9 +456,9 @@ int train_core(const okge_tables *t, const okge_shard *sh, const okge_prefix_bat
         PrefixDev p;
         std::memset(&p, 0, sizeof(p));
         if (!q_ext) p = to_dev(*batch, t, sh);
-        // the tile kernel's gradient product reads Q as three bf16 planes: written by the launch that folds the rows, or from
-        // the caller's block by a launch of its own
-        v8bf *q_planes = tile_grad_split(g.KB) && !loss_only ? reinterpret_cast<v8bf *>(ws + l.off_Qp) : nullptr;
+        // the tile kernel's two products read Q as three bf16 planes (and nothing else): written by the launch that folds the
+        // rows, or from the caller's block by a launch of its own
+        v8bf *q_planes = tile_grad_split(g.KB) ? reinterpret_cast<v8bf *>(ws + l.off_Qp) : nullptr;
         if (int rc = hip_ok(launch_encode_queries(t->E, t->R, t->d, t->scorer, p, reinterpret_cast<float *>(ws + l.off_Q), g.ldq,
                                                   q_ext ? 0 : g.Bpad, nullptr, pos->col, pos->nnz, tptr, g.tiles, NT, cand_col0, st, clear,
                                                   q_planes, g.KB),

@@ -36,8 +36,8 @@ __device__ __forceinline__ void cache_tile_positives(const FusedArgs &a, uint32_
 
 // Label bits of the chunk of ROWS batch rows that starts at row bb (bit = candidate column of the tile, word = candidate
 // half x batch row) from the tile's positives: the cached ones, then whatever did not fit the cache from global memory.
-// ROWS: the chunk height of the caller (64 / 32).
-template <int ROWS>
+// ROWS: the chunk height of the caller (64 / 32); CACHE: how many positives the caller cached.
+template <int ROWS, int CACHE = POS_CACHE>
 __device__ __forceinline__ void set_label_bits(const FusedArgs &a, const uint32_t *posc, int pos_lo, int pos_hi, int pos_cached,
                                                int n0, int bb, uint32_t *yb, int tid)
 {
@@ -46,7 +46,7 @@ __device__ __forceinline__ void set_label_bits(const FusedArgs &a, const uint32_
         const int row = (int)(v >> 6) - bb;
         if (row >= 0 && row < ROWS) atomicOr(&yb[ROWS * ((v >> 5) & 1u) + row], 1u << (v & 31u));
     }
-    for (int q = pos_lo + POS_CACHE + tid; q < pos_hi; q += TILE_THREADS) {      // overflow: rare
+    for (int q = pos_lo + CACHE + tid; q < pos_hi; q += TILE_THREADS) {      // overflow: rare
         const int row = a.pos_row[q] - bb;
         const int col = a.pos_col[q] - a.cand_col0 - n0;
         if (row >= 0 && row < ROWS) atomicOr(&yb[ROWS * (col >> 5) + row], 1u << (col & 31));
@@ -158,15 +158,15 @@ __device__ __forceinline__ void store_loss_partial(float lsum, double *red, doub
 }
 
 // ---- write-back ---------------------------------------------------------------------------------------------------------
-// A tile's 64 gradient rows, staged in LDS as stage[64][LDK], leave: masked with the cached dropout flags keepb[64][KEEP_LD],
+// A tile's 64 gradient rows, staged in LDS as stage[64][LDK], leave: masked with the cached dropout flags keepb[64][KEEP_LDS],
 // then either into slab_rows[64][16*KB] (a workgroup that holds only part of the tile's batch rows: plain 16-byte stores; a
 // reduce kernel sums the slabs into dE) or, slab_rows == nullptr, into dE.  Thread (tid >> 3, tid & 7): row, octets q8 + 8 it.
-template <int KB>
+template <int KB, int KEEP_LDS = TileCfg<KB>::KEEP_LD>
 __device__ __forceinline__ void store_tile_gradient(const FusedArgs &a, const float *stage, const uint8_t *keepb, float *slab_rows,
                                                     int n0, int tid)
 {
     using Cfg = TileCfg<KB>;
-    constexpr int LDK = Cfg::LDK, NO = Cfg::NO, KEEP_LD = Cfg::KEEP_LD, NOIT = (NO + 7) / 8;
+    constexpr int LDK = Cfg::LDK, NO = Cfg::NO, NOIT = (NO + 7) / 8;
     const int d = a.d, r8 = tid >> 3, q8 = tid & 7, n = n0 + r8;
     const bool vec_ok = (d & 3) == 0;
     if (a.loss_only || n >= a.N) return;
@@ -182,7 +182,7 @@ __device__ __forceinline__ void store_tile_gradient(const FusedArgs &a, const fl
         v[0] = *reinterpret_cast<const v4f *>(stage + r8 * LDK + k);
         v[1] = *reinterpret_cast<const v4f *>(stage + r8 * LDK + k + 4);
         if (a.drop_c.enabled) {
-            const uint32_t bits = keepb[r8 * KEEP_LD + o];
+            const uint32_t bits = keepb[r8 * KEEP_LDS + o];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 v[0][e] *= (bits >> e & 1u) ? a.drop_c.scale : 0.f;

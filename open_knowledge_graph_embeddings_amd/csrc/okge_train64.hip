@@ -10,6 +10,7 @@
 //   score product : the wave's two 16x16 blocks X[rows of group][candidates of blk], ONE candidate operand
 //                   (ds_read_b128, four contraction steps) feeds both blocks; the two accumulator chains alternate
 //                   (40-cycle dependent latency of v_mfma_f32_16x16x4_f32 behind a 32-cycle issue).
+//                   KB = 13 (GSPLIT below): on the bf16 matrix cores, the query operand read transposed from the plane chunk.
 //   loss epilogue : on the accumulator registers (8 elements per lane); label bits from an LDS bitmask.
 //   dC product    : dC[candidates of blk][all columns] += G^T . Q over the wave's 32 batch rows; the G blocks are the A
 //                   operands straight from the epilogue's registers (the MFMA result layout of X is the A layout of
@@ -33,6 +34,9 @@
 namespace okge {
 
 constexpr int NT64 = TILE_N, BC64 = 64, T64_THREADS = TILE_THREADS;
+// LDS sizes of the small arrays: the two-plane-buffer instance has 4 096 B for them
+constexpr int t64_keep_lds(int KB) { return tile_grad_split(KB) ? 2 * KB : (2 * KB < 32 ? 32 : 2 * KB); }
+constexpr int t64_posc(int KB) { return tile_grad_split(KB) ? 192 : POS_CACHE; }
 
 #ifdef OKGE_STAMPS
 // diagnostic build (tools/build_stamps.sh): workgroup placement + per-chunk phase timeline of wave 0
@@ -65,25 +69,22 @@ constexpr int NT64 = TILE_N, BC64 = 64, T64_THREADS = TILE_THREADS;
 // chunk buffer: chunk i+1 is parked while chunk i is being worked on, so a chunk has ONE barrier and no staging phase
 // (with one buffer every wave parks, requests and waits between two barriers while the MFMA pipes idle: ~1.3 K of a
 // chunk's 17.9 K cycles), and the score product reads a third less from LDS.
-// SHORTK (with REGC; the launcher picks it for slot sizes 193..200 at KB = 13, i.e. the d = 200 of BASELINE configs[1]): the
-// contraction needs only 200 of the 208 padded columns.  In the normal k order MFMA j of a round takes the columns
-// 16 r + 4 s + j of lane slot s, so all four MFMAs of the last round touch a padding column; here the LAST round is fed in the
-// order 16 r + 4 j + s (two ds_read_b32 per block instead of one ds_read_b128, the candidate operand read that way once in
-// the prologue), which puts columns 200..207 into MFMAs 2 and 3 -- and those are not issued: 50 instead of 52 score MFMAs
-// per block.  (The gradient product still writes all 208 columns: its OUTPUT is padded, not its contraction.)
-template <int KB, int MODE, bool SHORTK = false>
+template <int KB, int MODE>
 __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const FusedArgs a)
 {
     constexpr bool REGC = KB <= 13;   // candidate operand in registers + two query chunk buffers: 4 KB more registers per lane
-    static_assert(!SHORTK || (REGC && KB >= 3), "the short last round comes with the register-resident candidate operand");
-    // GSPLIT (okge_tile_grad_split.h): the gradient product on the bf16 matrix cores.  LDS then holds ONE fp32 query chunk (the
-    // tile's region, once every wave has taken its candidate operand from it) and ONE chunk of query planes, and a chunk has
-    // two barriers with each park running under the other phase:
-    //   barrier; score product of chunk i, planes of chunk i landing beside it (global -> LDS, no registers); epilogue;
-    //   barrier; gradient product of chunk i, fp32 chunk i+1 parked beside it.
+    // GSPLIT (okge_tile_grad_split.h): BOTH products on the bf16 matrix cores, from three bf16 planes per operand.  The query
+    // chunk exists in LDS as ONE image, the plane chunk, which the gradient product reads by cells and the score product
+    // transposed; the fp32 query block is not read at all.  LDS holds two plane chunks, chunk i+1 landing (global -> LDS, no
+    // registers) during the whole of chunk i, and a chunk has one barrier:
+    //   vmcnt(0); barrier; score product; copy of chunk i+1 issued; epilogue; gradient product.
+    // The gathered tile lives in the second buffer until every wave has taken its candidate operand (three planes, in
+    // registers) from it, chunk 0 lands in the first meanwhile.  Padding columns are zero planes: slot sizes 193 .. 200 need no
+    // instance of their own (the fp32 loop had one that skipped two MFMAs of the last round).
     constexpr bool GSPLIT = tile_grad_split(KB);
-    static_assert(!GSPLIT || REGC, "the plane buffer takes the place of the second fp32 chunk buffer");
+    static_assert(!GSPLIT || REGC, "the candidate operand is register-resident");
     using TGS = TileGradSplit<KB>;
+    using TSS = TileScoreSplit<KB>;
 #ifdef OKGE_STAMPS
     unsigned long long wg_t0;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wg_t0)::"memory");
@@ -91,22 +92,26 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
 #endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using Cfg = TileCfg<KB>;
-    constexpr int LDK = Cfg::LDK, NO = Cfg::NO, KEEP_LD = Cfg::KEEP_LD;
+    constexpr int LDK = Cfg::LDK, NO = Cfg::NO;
     constexpr int KQ = KB / 4, KR = KB % 4;
     constexpr int QG = 8;                                       // staging: column groups per row (512 threads / 64 rows)
     constexpr int NOIT = (NO + QG - 1) / QG;
     constexpr int NQ = 4 * KB, NQIT = (NQ + QG - 1) / QG;       // float4 per row
     static_assert(MODE == MODE_TRAIN_BCE || MODE == MODE_TRAIN_KL, "training kernel");
     const int d = a.d;
-    float *Cs = reinterpret_cast<float *>(smem);              // [64][LDK]
-    float *Qs = Cs + NT64 * LDK;                              // [64][LDK]
-    v8bf *Pl = reinterpret_cast<v8bf *>(Qs);                  // GSPLIT: [TGS::CHUNK_CELLS] query planes; its head is Qs in the write-back
-    static_assert(!GSPLIT || (size_t)TGS::CHUNK_CELLS * sizeof(v8bf) >= (size_t)BC64 * LDK * sizeof(float), "Qs fits the plane buffer");
-    uint32_t *ybits3 = GSPLIT ? reinterpret_cast<uint32_t *>(Pl + TGS::CHUNK_CELLS)
+    // GSPLIT: two plane chunks of TGS::CHUNK_CELLS cells; the tile (Cs) and the write-back's second stage are the head of the
+    // second, the write-back's first stage (Qs) the head of the first.  To fit 160 KiB beside them this instance keeps its keep
+    // flags at a row stride of NO bytes and caches fewer positives (T64_KEEP_LDS, T64_POSC).
+    v8bf *Pl = reinterpret_cast<v8bf *>(smem);
+    float *Cs = GSPLIT ? reinterpret_cast<float *>(Pl + TGS::CHUNK_CELLS) : reinterpret_cast<float *>(smem);   // [64][LDK]
+    float *Qs = GSPLIT ? reinterpret_cast<float *>(smem) : Cs + NT64 * LDK;                                    // [64][LDK]
+    static_assert(!GSPLIT || (size_t)TGS::CHUNK_CELLS * sizeof(v8bf) >= (size_t)BC64 * LDK * sizeof(float), "a stage fits a plane buffer");
+    constexpr int KEEP_LDS = t64_keep_lds(KB), POSC = t64_posc(KB);
+    uint32_t *ybits3 = GSPLIT ? reinterpret_cast<uint32_t *>(Pl + 2 * TGS::CHUNK_CELLS)
                               : reinterpret_cast<uint32_t *>(Qs + BC64 * LDK);    // [3][2 halves][64 rows] label bits, three chunks in rotation
     double *red = reinterpret_cast<double *>(ybits3 + 3 * BC64 * 2);     // [8]
-    uint8_t *keepb = reinterpret_cast<uint8_t *>(red + 8);               // [64][KEEP_LD] keep flags of the tile
-    uint32_t *posc = reinterpret_cast<uint32_t *>(keepb + NT64 * KEEP_LD);   // [POS_CACHE] (row << 6 | col)
+    uint8_t *keepb = reinterpret_cast<uint8_t *>(red + 8);               // [64][KEEP_LDS] keep flags of the tile
+    uint32_t *posc = reinterpret_cast<uint32_t *>(keepb + NT64 * KEEP_LDS);  // [POSC] (row << 6 | col)
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, s = lane >> 4;
     const int blk = w & 3, h = w >> 2;
@@ -135,11 +140,15 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         }
     };
     const uint32_t dstep = a.drop_c.enabled ? drop_step(a.drop_c) : 0u;   // before the loads whose latency hides the masks
-    fetch_chunk(b_begin);
+    if constexpr (GSPLIT) {
+        if (b_begin < b_end) TGS::copy_chunk(a.Qplanes + (size_t)(b_begin >> 6) * TGS::CHUNK_CELLS, Pl, w, lane);
+    } else {
+        fetch_chunk(b_begin);
+    }
 
     // positives of this tile: offsets requested before the gather (their loads overlap the candidate rows')
     const int pos_lo = a.tile_ptr[blockIdx.x], pos_hi = a.tile_ptr[blockIdx.x + 1];
-    const int pos_cached = min(pos_hi - pos_lo, POS_CACHE);
+    const int pos_cached = min(pos_hi - pos_lo, POSC);
 
     // ---- candidate tile: gather, dropout, LDS; masked copy for the dQ kernel --------------------------------------------
     {
@@ -199,7 +208,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
                 }
                 *reinterpret_cast<v4f *>(Cs + r8 * LDK + k) = v0[it];
                 *reinterpret_cast<v4f *>(Cs + r8 * LDK + k + 4) = v1[it];
-                keepb[r8 * KEEP_LD + o] = (uint8_t)bits[it];
+                keepb[r8 * KEEP_LDS + o] = (uint8_t)bits[it];
             }
         }
     }
@@ -234,36 +243,38 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     int cm_done = 0;
     // REGC: the lane's candidate operand (row 16blk + c, columns 16r + 4s .. + 3 of every round r) into registers and the
     // first query chunk parked -- then the tile's LDS is free for the odd chunks
-    v4f breg[REGC ? KB : 1];
-    if (REGC) {
+    v4f breg[REGC && !GSPLIT ? KB : 1];
+    typename TSS::BOp bop;
+    if constexpr (GSPLIT) {
+        TSS::load_b(bop, Cs + (16 * blk + c) * LDK, s);
+        cm_done = NOIT;                 // (left as planes, above)
+    } else if (REGC) {
 #pragma unroll
         for (int r = 0; r < KB; ++r) breg[r] = *reinterpret_cast<const v4f *>(Cs + (16 * blk + c) * LDK + 16 * r + 4 * s);
-        if (SHORTK) {                   // last round in the order 16 r + 4 j + s, j = 0, 1
-            breg[KB - 1][0] = Cs[(16 * blk + c) * LDK + 16 * (KB - 1) + s];
-            breg[KB - 1][1] = Cs[(16 * blk + c) * LDK + 16 * (KB - 1) + 4 + s];
-        }
         cm_done = NOIT;                 // (left as planes, above)
-        if (GSPLIT) {                   // the first chunk goes where the tile is: once every wave has read its operand (and the planes)
-            __syncthreads();
-            park_chunk(Cs);
-        } else {
-            park_chunk(Qs);
-        }
+        park_chunk(Qs);
         if (b_begin + BC64 < b_end) fetch_chunk(b_begin + BC64);
     }
 
     // Label bits of a chunk (bit = candidate column of the tile, word = candidate half x batch row) from the tile's positives.
-    // Three buffers in rotation: chunk i's bits are SET while chunk i-1's score product runs (they need no barrier of their
-    // own: two lie between the set and the epilogue that reads them) and the buffer chunk i-1 used is cleared then too --
-    // in the staging phase, between the two barriers of a chunk, nothing overlaps these dependent LDS round trips.
-    auto set_chunk_labels = [&](int bb, uint32_t *yb) { set_label_bits<BC64>(a, posc, pos_lo, pos_hi, pos_cached, n0, bb, yb, tid); };
+    // Three buffers in rotation: chunk i's bits are SET while chunk i-1's score product runs and the buffer chunk i-2 used is
+    // CLEARED then too, so neither needs a barrier of its own.  One barrier per chunk is enough for that: the set of chunk i
+    // (during chunk i-1) and its read (epilogue of chunk i) have chunk i's opening barrier between them; the clear of a buffer
+    // (during chunk i-1) comes behind chunk i-1's opening barrier, which every wave passes only after its epilogue of chunk i-2,
+    // the buffer's last reader; and the next set of that buffer (during chunk i, for chunk i+1) comes behind chunk i's opening
+    // barrier, after the clear.  (Where a chunk has a staging phase between two barriers, nothing there overlaps these
+    // dependent LDS round trips: hence under the score product.)
+    auto set_chunk_labels = [&](int bb, uint32_t *yb) { set_label_bits<BC64, POSC>(a, posc, pos_lo, pos_hi, pos_cached, n0, bb, yb, tid); };
     set_chunk_labels(b_begin, ybits3);        // chunk 0 (the three buffers were cleared before the prologue's barrier)
     int par = 0;
     for (int b0 = b_begin; b0 < b_end; b0 += BC64, par = par == 2 ? 0 : par + 1) {
         uint32_t *ybits = ybits3 + par * (2 * BC64);
         // query chunk buffer of this chunk / of the next (REGC: the two LDS tiles alternate)
-        float *Qc = GSPLIT || (REGC && (((b0 - b_begin) >> 6) & 1)) ? Cs : Qs;
+        float *Qc = REGC && (((b0 - b_begin) >> 6) & 1) ? Cs : Qs;
         float *Qn = REGC ? (Qc == Qs ? Cs : Qs) : Qs;
+        // GSPLIT: the plane chunk of this chunk / where the next one lands
+        const v8bf *Pc = Pl + (((b0 - b_begin) >> 6) & 1) * TGS::CHUNK_CELLS;
+        v8bf *Pn = Pl + ((((b0 - b_begin) >> 6) & 1) ^ 1) * TGS::CHUNK_CELLS;
         TL_STAMP_AT(48 + ((b0 - b_begin) >> 6));   // chunk entered (the previous chunk's closing barrier passed)
         if (!REGC) {
             // ---- phase A: park the prefetched chunk, prefetch the next chunk -------------------------------------
@@ -273,9 +284,11 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             TL_STAMP_AT(72 + ((b0 - b_begin) >> 6));   // next chunk requested
         }
         TL_STAMP();   // [0] staged, before the barrier
+        // GSPLIT: this wave's pieces of the chunk have landed (and nothing of its is in flight: the barrier below is a bare
+        // s_barrier); behind the barrier everybody's have, and the other buffer -- the tile, or chunk i-1 -- has no reader left
+        if (GSPLIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();   // REGC: this chunk's rows are parked (during the previous chunk) and the other buffer is free
         TL_STAMP();   // [1] start of score product
-        if (GSPLIT && !a.loss_only) TGS::copy_chunk(a.Qplanes + (size_t)(b0 >> 6) * TGS::CHUNK_CELLS, Pl, w, lane);
         {   // under the score product: the next chunk's label bits, the buffer after that cleared, one group of masked rows out
             const int pn = par == 2 ? 0 : par + 1, pc = pn == 2 ? 0 : pn + 1;
             if (tid < 2 * BC64) ybits3[pc * (2 * BC64) + tid] = 0u;
@@ -285,7 +298,11 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
 
         // ---- score blocks (rows 32h + 16rg + 4s + i, columns 16blk + c), rg = 0, 1 -----------------------------------
         v4f x0 = (v4f){0.f, 0.f, 0.f, 0.f}, x1 = (v4f){0.f, 0.f, 0.f, 0.f};
-        {
+        if constexpr (GSPLIT) {
+            v4f xs[2];
+            TSS::score(xs, bop, Pc, h, lane);
+            x0 = xs[0]; x1 = xs[1];
+        } else {
             const float *qa0 = Qc + (32 * h + c) * LDK + 4 * s;
             const float *qa1 = qa0 + 16 * LDK;
             const float *cb = Cs + (16 * blk + c) * LDK + 4 * s;
@@ -302,37 +319,27 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
 #pragma unroll
             for (int r = 0; r < KB; ++r) {
                 v4f a20 = a10, a21 = a11, b2v = b1v;
-                const bool short_next = SHORTK && r + 2 == KB - 1;          // the round being requested is the short one
                 if (r + 2 < KB) {
-                    if (short_next) {
-                        const float *q0 = Qc + (32 * h + c) * LDK + 16 * (KB - 1) + s, *q1 = q0 + 16 * LDK;
-                        a20[0] = q0[0]; a20[1] = q0[4];
-                        a21[0] = q1[0]; a21[1] = q1[4];
-                    } else {
-                        a20 = *reinterpret_cast<const v4f *>(qa0 + 16 * (r + 2));
-                        a21 = *reinterpret_cast<const v4f *>(qa1 + 16 * (r + 2));
-                    }
+                    a20 = *reinterpret_cast<const v4f *>(qa0 + 16 * (r + 2));
+                    a21 = *reinterpret_cast<const v4f *>(qa1 + 16 * (r + 2));
                     b2v = REGC ? breg[r + 2 < KB ? r + 2 : 0] : *reinterpret_cast<const v4f *>(cb + 16 * (r + 2));
                 }
-                constexpr int NJ_FULL = 4;
-                const int nj = (SHORTK && r == KB - 1) ? 2 : NJ_FULL;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (j < nj) {
-                        x0 = mfma16(a00[j], b0v[j], x0);
-                        x1 = mfma16(a01[j], b0v[j], x1);
-                    }
+                    x0 = mfma16(a00[j], b0v[j], x0);
+                    x1 = mfma16(a01[j], b0v[j], x1);
                 }
                 a00 = a10; a01 = a11; b0v = b1v;
                 a10 = a20; a11 = a21; b1v = b2v;
-                if (short_next) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);   // ds_reads of round r+2
-                else __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
-                if (nj == 2) __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);      // the MFMAs of round r
-                else __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);                 // ds_reads of round r+2
+                __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);                   // the MFMAs of round r
             }
         }
 
         TL_STAMP();   // [2] end of score product
+        // GSPLIT: the next chunk's planes are requested here, in front of the VALU-only epilogue, not in front of the score
+        // product: issued among its MFMAs and transposed reads the pieces cost more (profiles/tile_score_split.md, part (d))
+        if (GSPLIT && b0 + BC64 < b_end) TGS::copy_chunk(a.Qplanes + (size_t)((b0 >> 6) + 1) * TGS::CHUNK_CELLS, Pn, w, lane);
         // B operands (query rows) of the dC product's first step: requested now, consumed after the epilogue
         const float *qb = Qc + (32 * h + 4 * s) * LDK;
         v4f pb[KQ > 0 ? KQ : 1];
@@ -389,15 +396,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             }
             if (MODE == MODE_TRAIN_BCE && LOGPROD) lsum += lin + __builtin_amdgcn_logf(prod) * TILE_LN2;
         }
-        if (GSPLIT) {
-            // this wave's pieces of the planes have landed; behind the barrier everybody's have, and the fp32 chunk has no reader left
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (b0 + BC64 < b_end) {
-                park_chunk(Cs);
-                if (b0 + 2 * BC64 < b_end) fetch_chunk(b0 + 2 * BC64);
-            }
-        } else if (REGC && b0 + BC64 < b_end) {
+        if (REGC && !GSPLIT && b0 + BC64 < b_end) {
             // park the next chunk in the other buffer (its last readers finished before this chunk's barrier) and request the
             // chunk after it: by now the waves of a SIMD are a phase apart, so this runs beside the other wave's MFMAs
             park_chunk(Qn);
@@ -416,7 +415,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             // sub-step u = 4 rg + t, slot s  <->  batch row 32h + 16rg + 4s + t ; A = G[row][n = 16blk + c] = g4[rg][t]
             if constexpr (GSPLIT) {
                 v4f none[1];
-                TGS::template product<true>(dc, none, TGS::a_planes(g4), Pl, h, lane);
+                TGS::template product<true>(dc, none, TGS::a_planes(g4, s), Pc, h, lane);
             } else
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -493,7 +492,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     TL_STAMP_AT(44);       // loss partial out
     // batch split over blockIdx.y: every workgroup stores ITS partial rows into a slab (plain 16-byte stores);
     // dc_reduce_kernel sums the slabs into dE
-    store_tile_gradient<KB>(a, Cs, keepb, gridDim.y > 1 ? a.dC_slab + ((size_t)blockIdx.y * gridDim.x * NT64 + n0) * (16 * KB) : nullptr,
+    store_tile_gradient<KB, KEEP_LDS>(a, Cs, keepb, gridDim.y > 1 ? a.dC_slab + ((size_t)blockIdx.y * gridDim.x * NT64 + n0) * (16 * KB) : nullptr,
                             n0, tid);
 #ifdef OKGE_STAMPS
     if (a.stamps_dbg && tid == 0) {
@@ -513,17 +512,14 @@ template <int KB>
 static size_t shmem64()
 {
     using Cfg = TileCfg<KB>;
-    const size_t chunk = tile_grad_split(KB) ? (size_t)TileGradSplit<KB>::CHUNK_CELLS * sizeof(v8bf) : (size_t)BC64 * Cfg::LDK * sizeof(float);
-    return (size_t)NT64 * Cfg::LDK * sizeof(float) + chunk + 3 * BC64 * 2 * sizeof(uint32_t) + 8 * sizeof(double) +
-           NT64 * Cfg::KEEP_LD + POS_CACHE * sizeof(uint32_t);
+    const size_t tiles = tile_grad_split(KB) ? (size_t)2 * TileGradSplit<KB>::CHUNK_CELLS * sizeof(v8bf)
+                                             : (size_t)(NT64 + BC64) * Cfg::LDK * sizeof(float);
+    return tiles + 3 * BC64 * 2 * sizeof(uint32_t) + 8 * sizeof(double) + NT64 * t64_keep_lds(KB) + t64_posc(KB) * sizeof(uint32_t);
 }
 
 template <int KB, int MODE>
 static hipError_t launch64_t(const FusedArgs &a, dim3 grid, hipStream_t st)
 {
-    // slot sizes 16 (KB - 1) + 1 .. + 8: the last contraction round needs two of its four MFMAs
-    if (KB == 13 && a.d > 16 * (KB - 1) && a.d <= 16 * (KB - 1) + 8)
-        return launch_with_lds<fused_tile64_kernel<KB, MODE, (KB == 13)>>(grid, dim3(T64_THREADS), shmem64<KB>(), st, a);
     return launch_with_lds<fused_tile64_kernel<KB, MODE>>(grid, dim3(T64_THREADS), shmem64<KB>(), st, a);
 }
 

@@ -38,7 +38,7 @@ traffic["_command"] = "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes)
 traffic["_commit"] = os.environ.get("OKGE_COMMIT")          # stamped by tools/publish_profiles.py in the build container
 json.dump(traffic, open(os.path.join(root, "pmc_traffic.json"), "w"), indent=1)
 with open(os.path.join(root, "pmc_summary.txt"), "w") as out:
-    for sub in ("pmc_sq1", "pmc_sq2", "pmc_fetch", "pmc_write"):
+    for sub in ("pmc_sq1", "pmc_sq2", "pmc_sq3", "pmc_fetch", "pmc_write"):
         out.write(f"== {sub}\n")
         for k, d in sorted(pmc(sub).items()):
             if any(x in k for x in ("fused", "dq", "prefix", "adagrad", "encode", "eval_", "pool", "bn_", "col_", "dc_reduce")):

@@ -14,6 +14,13 @@
 //      cells read from the plane image) with the corrections folded per chunk or in an accumulator of their own, each without
 //      and with the next chunk's planes copied global -> LDS beside it.  Floors per SIMD (two waves): 2 x 3328 cycles fp32,
 //      2 x 1248 bf16; the LDS reads of the bf16 form are 8 waves x 39 KiB per chunk.
+//  (d) The train tile's score phase X = Q . C^T per 64-row chunk at KB = 13 and both phases together: the fp32 loop
+//      fused_tile64_kernel ran (a frozen copy: 2 x 50 v_mfma_f32_16x16x4_f32 per wave from an fp32 chunk in LDS, the candidate
+//      operand in registers, the short last round of slot sizes 193 .. 200) against TileScoreSplit::score (72
+//      v_mfma_f32_16x16x32_bf16 + 12 v_mfma_f32_16x16x16_bf16 per wave, the query operand read transposed from the plane
+//      image), and score + gradient phase per chunk from two plane buffers with the next chunk's copy beside them and one
+//      barrier per chunk -- the loop the kernel runs now, without its loss epilogue.  The gate of profiles/tile_score_split.md
+//      compares the last against the sum of the fp32 score loop and part (c)'s "folded + copy" gradient loop of the same run.
 // Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -o mfma_bf16_split.bin mfma_bf16_split.hip
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -260,7 +267,7 @@ __global__ __launch_bounds__(512, 2) void grad_phase_kernel(const float *src, co
         } else {
             const int buf = COPY ? it & 1 : 0;
             if (COPY) T::copy_chunk(planes + (size_t)(it & 7) * T::CHUNK_CELLS, lds + (buf ^ 1) * T::CHUNK_CELLS, w, lane);
-            const Planes a = T::a_planes(g4);
+            const Planes a = T::a_planes(g4, s);
             T::template product<FOLD>(dc, corr, a, lds + buf * T::CHUNK_CELLS, h, lane);
         }
     }
@@ -294,6 +301,131 @@ static int run_phase(const char *name, const float *src, const v8bf *planes, flo
     for (auto v : hc) { mx = v > mx ? v : mx; mean += (double)v / hc.size(); }
     printf("%-58s %8.3f ms  %7.1f ns/chunk   s_memtime ticks/chunk: mean %.1f max %.1f\n", name, ms, ms * 1e6 / iters, mean / iters,
            (double)mx / iters);
+    return 0;
+}
+
+// ---- (d) ------------------------------------------------------------------------------------------------------------
+// MODE 0: the fp32 score loop (frozen copy); 1: the plane score loop; 2: score + gradient phase + the next chunk's copy issued
+// in front of the score phase; 3: the copy issued between the phases (where the kernel has its VALU-only loss epilogue); 4: half
+// of it in front, half between
+template <int MODE>
+__global__ __launch_bounds__(512, 2) void score_phase_kernel(const float *src, const v8bf *planes, float *out, unsigned long long *cyc, int iters)
+{
+    constexpr int KB = 13, LDK = lds_ld(16 * KB);
+    using T = TileGradSplit<KB>;
+    using S = TileScoreSplit<KB>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    v8bf *lds = reinterpret_cast<v8bf *>(smem);           // two plane chunks; the fp32 loop reads the first as [64][LDK] floats
+    const float *Qc = reinterpret_cast<const float *>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, s = lane >> 4, h = w >> 2;
+    if (MODE == 0) {
+        for (int i = tid; i < 64 * LDK; i += 512) reinterpret_cast<float *>(smem)[i] = src[i & 16383];
+    } else {
+        for (int i = tid; i < 2 * T::CHUNK_CELLS; i += 512) {
+            float x[8];
+            for (int k = 0; k < 8; ++k) x[k] = src[(8 * i + k) & 16383];
+            lds[i] = split3(x).hi;
+        }
+    }
+    v4f breg[KB];
+    typename S::BOp bop;
+    if (MODE == 0) {
+        for (int r = 0; r < KB; ++r) breg[r] = *reinterpret_cast<const v4f *>(src + ((16 * tid + 4 * r) & 16383));
+    } else {
+        S::load_b(bop, src + ((212 * tid) & 8191), s);
+    }
+    v4f dc[KB], none[1];
+    for (int kb = 0; kb < KB; ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
+    v4f xsum = (v4f){0.f, 0.f, 0.f, 0.f};
+    __syncthreads();
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int it = 0; it < iters; ++it) {
+        if (MODE >= 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if constexpr (MODE == 0) {
+            // a FROZEN COPY of the fp32 score loop fused_tile64_kernel<13, ., true> ran before TileScoreSplit: the baseline of the
+            // comparison, not shared code
+            v4f x0 = (v4f){0.f, 0.f, 0.f, 0.f}, x1 = (v4f){0.f, 0.f, 0.f, 0.f};
+            const float *qa0 = Qc + (32 * h + c) * LDK + 4 * s;
+            const float *qa1 = qa0 + 16 * LDK;
+            v4f a00 = *reinterpret_cast<const v4f *>(qa0), a01 = *reinterpret_cast<const v4f *>(qa1);
+            v4f b0v = breg[0];
+            v4f a10 = *reinterpret_cast<const v4f *>(qa0 + 16), a11 = *reinterpret_cast<const v4f *>(qa1 + 16), b1v = breg[1];
+            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+            for (int r = 0; r < KB; ++r) {
+                v4f a20 = a10, a21 = a11, b2v = b1v;
+                const bool short_next = r + 2 == KB - 1;
+                if (r + 2 < KB) {
+                    if (short_next) {
+                        const float *q0 = Qc + (32 * h + c) * LDK + 16 * (KB - 1) + s, *q1 = q0 + 16 * LDK;
+                        a20[0] = q0[0]; a20[1] = q0[4];
+                        a21[0] = q1[0]; a21[1] = q1[4];
+                    } else {
+                        a20 = *reinterpret_cast<const v4f *>(qa0 + 16 * (r + 2));
+                        a21 = *reinterpret_cast<const v4f *>(qa1 + 16 * (r + 2));
+                    }
+                    b2v = breg[r + 2 < KB ? r + 2 : 0];
+                }
+                const int nj = r == KB - 1 ? 2 : 4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j < nj) {
+                        x0 = mfma16(a00[j], b0v[j], x0);
+                        x1 = mfma16(a01[j], b0v[j], x1);
+                    }
+                }
+                a00 = a10; a01 = a11; b0v = b1v;
+                a10 = a20; a11 = a21; b1v = b2v;
+                if (short_next) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+                else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                if (nj == 2) __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                else __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+            }
+            xsum += x0 + x1;
+        } else {
+            const int buf = MODE >= 2 ? it & 1 : 0;
+            const v8bf *csrc = planes + (size_t)(it & 7) * T::CHUNK_CELLS;
+            v8bf *cdst = lds + (buf ^ 1) * T::CHUNK_CELLS;
+            if (MODE == 2) T::copy_chunk(csrc, cdst, w, lane);
+            if (MODE == 4) T::template copy_chunk<0, 5>(csrc, cdst, w, lane);
+            v4f x[2];
+            S::score(x, bop, lds + buf * T::CHUNK_CELLS, h, lane);
+            xsum += x[0] + x[1];
+            if (MODE == 3) T::copy_chunk(csrc, cdst, w, lane);
+            if (MODE == 4) T::template copy_chunk<5>(csrc, cdst, w, lane);
+            if (MODE >= 2) {
+                // G is a function of the scores, as in the kernel: the gradient phase cannot start before the score phase ends
+                const v4f g4[2] = {x[0] * 1e-3f, x[1] * 1e-3f};
+                T::template product<true>(dc, none, T::a_planes(g4, s), lds + buf * T::CHUNK_CELLS, h, lane);
+            }
+        }
+    }
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    float sum = xsum[0] + xsum[1] + xsum[2] + xsum[3];
+    for (int kb = 0; kb < KB; ++kb) for (int i = 0; i < 4; ++i) sum += dc[kb][i];
+    out[blockIdx.x * 512 + tid] = sum;
+    if (lane == 0) cyc[blockIdx.x * 8 + w] = t1 - t0;
+}
+
+template <int MODE>
+static int run_score(const char *name, const float *src, const v8bf *planes, float *out, unsigned long long *cyc, int blocks, int iters, double *ns)
+{
+    auto k = score_phase_kernel<MODE>;
+    const size_t shmem = (size_t)2 * TileGradSplit<13>::CHUNK_CELLS * 16;
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(512), shmem, 0, src, planes, out, cyc, iters);   // warm-up
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(e0));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(512), shmem, 0, src, planes, out, cyc, iters);
+    CK(hipEventRecord(e1));
+    CK(hipDeviceSynchronize());
+    float ms = 0.f;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    *ns = ms * 1e6 / iters;
+    printf("%-58s %8.3f ms  %7.1f ns/chunk\n", name, ms, *ns);
     return 0;
 }
 
@@ -362,10 +494,38 @@ int main()
     CK(hipMalloc(&planes, hp.size() * sizeof(v8bf)));
     CK(hipMemcpy(planes, hp.data(), hp.size() * sizeof(v8bf), hipMemcpyHostToDevice));
     printf("== (c) KB = 13 gradient phase of the train tile, %d workgroups x 512 threads, %d chunks each, one barrier per chunk\n", blocks, iters);
-    if (run_phase<0>("today: fp32, 104 MFMAs per wave", src, planes, out, cyc, blocks, iters)) return 1;
+    if (run_phase<0>("before: fp32, 104 MFMAs per wave", src, planes, out, cyc, blocks, iters)) return 1;
     if (run_phase<1>("three planes, corrections folded per chunk", src, planes, out, cyc, blocks, iters)) return 1;
     if (run_phase<2>("three planes, corrections in their own accumulator", src, planes, out, cyc, blocks, iters)) return 1;
     if (run_phase<3>("folded + next chunk's planes copied beside it", src, planes, out, cyc, blocks, iters)) return 1;
     if (run_phase<4>("own accumulator + next chunk's planes copied beside it", src, planes, out, cyc, blocks, iters)) return 1;
+
+    // (d)
+    printf("== (d) KB = 13 score phase of the train tile and both phases together, %d workgroups x 512 threads, %d chunks each\n", blocks, iters);
+    double ns_fp32 = 0, ns_planes = 0, ns_both = 0, ns_grad = 0;
+    if (run_score<0>("before: fp32 score loop, 2 x 50 MFMAs per wave", src, planes, out, cyc, blocks, iters, &ns_fp32)) return 1;
+    if (run_score<1>("three planes, transposed reads: 84 MFMAs per wave", src, planes, out, cyc, blocks, iters, &ns_planes)) return 1;
+    double ns_mid = 0, ns_halves = 0;
+    if (run_score<2>("score + gradient phase, copy issued in front", src, planes, out, cyc, blocks, iters, &ns_both)) return 1;
+    if (run_score<3>("score + gradient phase, copy issued between the phases", src, planes, out, cyc, blocks, iters, &ns_mid)) return 1;
+    if (run_score<4>("score + gradient phase, copy half in front, half between", src, planes, out, cyc, blocks, iters, &ns_halves)) return 1;
+
+    {   // the gradient loop of the kernel before, once more in this part's own run order
+        hipEvent_t e0, e1;
+        CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+        auto k = grad_phase_kernel<3>;
+        const size_t shmem = (size_t)2 * T::CHUNK_CELLS * 16;
+        CK(hipEventRecord(e0));
+        hipLaunchKernelGGL(k, dim3(blocks), dim3(512), shmem, 0, src, planes, out, cyc, iters);
+        CK(hipEventRecord(e1));
+        CK(hipDeviceSynchronize());
+        float ms = 0.f;
+        CK(hipEventElapsedTime(&ms, e0, e1));
+        ns_grad = ms * 1e6 / iters;
+    }
+    const double bar = 0.75 * (ns_fp32 + ns_grad);
+    printf("gate: 0.75 x (fp32 score %.1f + folded gradient with copy %.1f) = %.1f ns/chunk; copy in front %.1f (%.3f), between %.1f (%.3f), "
+           "halves %.1f (%.3f) of the sum -- single samples, compare several runs\n", ns_fp32, ns_grad, bar, ns_both,
+           ns_both / (ns_fp32 + ns_grad), ns_mid, ns_mid / (ns_fp32 + ns_grad), ns_halves, ns_halves / (ns_fp32 + ns_grad));
     return 0;
 }
