@@ -313,7 +313,8 @@ int okge_encode_rows(const float *table, int32_t table_rows, int32_t d, const in
  * okge_pool_encode : raw[n][ld] = pooled rows (kept for backward), out[n][ld] = normalised rows (== raw allowed
  *                    without batch-norm), saved[4*d] = {mean, rstd, scratch, scratch} of this call.
  * okge_pool_backward: d_out[n][ld] -> batch-norm backward (d_bn_weight / d_bn_bias += this call's sums)
- *                    -> scatter-add into the dense token-table gradient dW (vocab x d; row 0 untouched). */
+ *                    -> scatter-add into the dense token-table gradient dW (vocab x d; row 0 untouched).
+ * A token outside [0, vocab) is read as token 0 (row 0, padding: no gradient) and counted once per encode in okge_id_errors. */
 typedef struct okge_token_embedder {
     const float *W;              /* token embedding table (vocab x d) */
     const int32_t *token_ids;    /* (n_ids x max_len) */

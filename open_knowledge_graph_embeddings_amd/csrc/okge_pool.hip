@@ -92,7 +92,8 @@ struct ScatterGroup {                  // one token table of the batch (calls wi
     float    *dW;
     uint8_t  *touched;                 // [vocab] or nullptr
     int32_t  *cnt;                     // STATE [vocab]: pairs per token, zero between calls
-    int32_t  *ctr;                     // STATE [16]: 0 tokens with several pairs, 1 pairs allotted, 2 long segments, 3 tokens with one pair (zero between calls); 4, 5, 6: copies of 0, 2, 3 for pass 4
+    int32_t  *ctr;                     // STATE [16]: 0 tokens with several pairs, 1 pairs allotted, 2 long segments, 3 tokens with one pair (zero between calls)
+    int32_t  *tot;                     // [16] (scratch, so that the state is left all-zero): 4, 5, 6 = copies of ctr 0, 2, 3 for pass 4
     int2     *cold;                    // [hist_blocks][SC_HIST_PAIRS] (token, pair index) of the cold pairs each pass-1 workgroup met
     int32_t  *cold_n;                  // [hist_blocks] how many
     int2     *single;                  // [cap] (token, its only pair index)
@@ -254,8 +255,10 @@ __global__ __launch_bounds__(256) void pool_stats_kernel(const PoolBatch pb, int
     int lb;
     const PoolCall &q = pb.c[locate_call(pb, blockIdx.x, lb)];
     const int L = q.L, d = q.d, r0 = lb * STAT_ROWS, nr = min(q.n, r0 + STAT_ROWS) - r0;
+    // (a token outside the vocabulary reads row 0 and counts as padding, like sc_tok below; each is counted once: one thread per pair)
     for (int i = threadIdx.x; i < nr * L; i += blockDim.x)
-        toks[i / L][i % L] = q.tokens[(size_t)row_id(q.ids, q.first_id, r0 + i / L, q.n_ids, (i % L) ? nullptr : pb.id_err) * L + i % L];
+        toks[i / L][i % L] = (int32_t)checked_row(
+            q.tokens[(size_t)row_id(q.ids, q.first_id, r0 + i / L, q.n_ids, (i % L) ? nullptr : pb.id_err) * L + i % L], q.vocab, pb.id_err);
     __syncthreads();
     if (threadIdx.x < nr) {
         int len = 0;
@@ -614,7 +617,7 @@ __global__ __launch_bounds__(256) void pool_backward_kernel(const PoolBatch pb)
     const int r0 = lb * POOL_BWD_ROWS, nr = min(n, r0 + POOL_BWD_ROWS) - r0;
     for (int i = threadIdx.x; i < HOT_TOKENS * d; i += blockDim.x) hot[i] = 0.f;
     for (int i = threadIdx.x; i < nr * L; i += blockDim.x)
-        toks[i / L][i % L] = q.tokens[(size_t)row_id(q.ids, q.first_id, r0 + i / L, q.n_ids, nullptr) * L + i % L];
+        toks[i / L][i % L] = sc_tok(q.tokens[(size_t)row_id(q.ids, q.first_id, r0 + i / L, q.n_ids, nullptr) * L + i % L], q.vocab);
     if (threadIdx.x == 0) hot_seen = 0;
     __syncthreads();
     if (threadIdx.x < nr) {
@@ -714,8 +717,8 @@ __global__ __launch_bounds__(256) void pool_dx_kernel(const PoolBatch pb, const 
     if (blk == pb.cum[pb.n_calls]) {
         if (threadIdx.x == 0)
             for (int gi = 0; gi < sb.n_groups; ++gi) {   // passes 1 and 2 are over: hand their counts to pass 4, zero the state
-                int32_t *ctr = sb.g[gi].ctr;
-                ctr[4] = ctr[0]; ctr[5] = ctr[2]; ctr[6] = ctr[3];
+                int32_t *ctr = sb.g[gi].ctr, *tot = sb.g[gi].tot;
+                tot[4] = ctr[0]; tot[5] = ctr[2]; tot[6] = ctr[3];
                 ctr[0] = ctr[1] = ctr[2] = ctr[3] = 0;
             }
         for (int c = 0; c < pb.n_calls; ++c) {
@@ -922,7 +925,7 @@ __global__ __launch_bounds__(256, 4) void pool_sum_kernel(const ScatterBatch sb,
         const int lw = (int)blockIdx.x - n_hot;
         for (int gi = 0; gi < sb.n_groups; ++gi) {
             const ScatterGroup &g = sb.g[gi];
-            const int n_l = min(g.ctr[5], g.cap), d = g.d, L = g.L, P = g.P;
+            const int n_l = min(g.tot[5], g.cap), d = g.d, L = g.L, P = g.P;
             for (int li = lw; li < n_l; li += n_long) {
                 const int si = min((int)g.long_list[li], g.cap - 1), tok = sc_tok(g.seg[4 * si], g.vocab), base = g.seg[4 * si + 1];
                 const int n = ((unsigned)base < (unsigned)P) ? min((int)g.seg[4 * si + 2], P - base) : 0;
@@ -986,7 +989,7 @@ __global__ __launch_bounds__(256, 4) void pool_sum_kernel(const ScatterBatch sb,
     // tokens with one pair (four in five): dW[token] += DX[row], four tokens per wave side by side
     for (int gi = 0; gi < sb.n_groups; ++gi) {
         const ScatterGroup &g = sb.g[gi];
-        const int n_s = min(g.ctr[6], g.cap), d = g.d, L = g.L;
+        const int n_s = min(g.tot[6], g.cap), d = g.d, L = g.L;
         int2 first[4];                                   // (requested before n_s is known: one dependent round trip less)
 #pragma unroll
         for (int u = 0; u < 4; ++u) first[u] = g.single[min(4 * wave + u, g.cap - 1)];
@@ -1018,7 +1021,7 @@ __global__ __launch_bounds__(256, 4) void pool_sum_kernel(const ScatterBatch sb,
     }
     for (int gi = 0; gi < sb.n_groups; ++gi) {
         const ScatterGroup &g = sb.g[gi];
-        const int n_t = min(g.ctr[4], g.cap), d = g.d, L = g.L;
+        const int n_t = min(g.tot[4], g.cap), d = g.d, L = g.L;
         const int4 *seg4 = reinterpret_cast<const int4 *>(g.seg);
         // (half a grid away from the waves that the single-pair tokens keep busy: all workgroups are resident at once)
         const int rwave = (wave + n_waves / 2) % n_waves;
@@ -1165,7 +1168,7 @@ bool scatter_layout(const PoolCall *calls, int n_calls, ScatterLayout &lo)
         lo.state_off[g] = lo.state_bytes;
         lo.state_bytes += al256(sizeof(int32_t) * (16 + (size_t)r.vocab));
         const size_t P = (size_t)lo.n_rows[g] * r.L, cap = std::min<size_t>(P, (size_t)r.vocab);
-        lo.scratch_bytes += al256(sizeof(int32_t) * (size_t)r.vocab) + al256(sizeof(int32_t) * P) + al256(16 * cap) + al256(4 * cap) + al256(8 * cap);
+        lo.scratch_bytes += al256(sizeof(int32_t) * (size_t)r.vocab) + al256(sizeof(int32_t) * P) + al256(16 * cap) + al256(4 * cap) + al256(8 * cap) + al256(16 * sizeof(int32_t));
     }
     return true;
 }
@@ -1253,6 +1256,7 @@ hipError_t launch_pool_backward_calls(const PoolCall *calls, int n_calls, int *i
         G.seg = reinterpret_cast<int32_t *>(take(16 * cap));
         G.long_list = reinterpret_cast<int32_t *>(take(4 * cap));
         G.single = reinterpret_cast<int2 *>(take(8 * cap));
+        G.tot = reinterpret_cast<int32_t *>(take(16 * sizeof(int32_t)));
         G.hot_slab = reinterpret_cast<float *>(take(sizeof(float) * blocks * SC_HOT * r.d));
         G.hot_seen = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * blocks));
         G.DX = reinterpret_cast<float *>(take(sizeof(float) * (size_t)lo.n_rows[g] * r.d));
