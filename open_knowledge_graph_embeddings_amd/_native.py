@@ -33,6 +33,16 @@ LOSSES = {"bce": OKGE_LOSS_BCE, "kl": OKGE_LOSS_KL}
 BIAS_SCORERS = ("bias_relation", "bias_entity")
 
 
+def scorer_id(scorer):
+    """a scorer's name or its OKGE_* value -> the value"""
+    return SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
+
+
+def loss_id(loss):
+    """'bce' / 'kl' or an OKGE_LOSS_* value -> the value"""
+    return LOSSES[loss] if isinstance(loss, str) else int(loss)
+
+
 def refuse_bias_scorer(scorer, who):
     """The data-bias scorers leave one slot without a gradient (model.py:281-350).  A step driver whose optimizer moves every
     parameter would step that slot on a zero gradient -- weight decay and the accumulator make that a real move -- so drivers
@@ -97,7 +107,7 @@ def eval_loss(loss, label_smoothing, out_ptr):
     if isinstance(loss, str) and loss not in LOSSES:
         raise ValueError(f"unknown loss {loss!r}: 'bce' or 'kl'")
     x = EvalLoss()
-    x.kind, x.label_smoothing, x.out = LOSSES[loss] if isinstance(loss, str) else int(loss), float(label_smoothing), out_ptr
+    x.kind, x.label_smoothing, x.out = loss_id(loss), float(label_smoothing), out_ptr
     return x
 
 

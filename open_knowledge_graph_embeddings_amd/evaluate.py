@@ -183,8 +183,8 @@ class PipelinedEvaluator:
         k = len(self.streams)
         self._bufs, self._ranks, self._ws = [None] * k, [None] * k, [None] * k
         # the descriptors of a call are built once and only their per-batch pointers change
-        self._t = self.engine._tables(E, R, scorer)
-        self._pb, self._c = N.PrefixBatch(), N.Candidates()
+        self._call = H.PrefixCall()
+        self._t = self._call.fill_tables(E, R, scorer, self.engine.device)
 
     def _buffer(self, slot, B, n):
         """score block of a chain: grown (never shrunk) to the largest B x ld seen.  Allocated and freed on the caller's
@@ -227,12 +227,8 @@ class PipelinedEvaluator:
                     self._ranks[slot] = torch.empty(max(n_groups, 1024), dtype=torch.int64, device=self.device)
                     self._ranks[slot].record_stream(st)
                 rk = self._ranks[slot]
-            b, pb, c = cb.batch, self._pb, self._c
-            pb.po_rel, pb.po_obj = (b.po_rel.data_ptr(), b.po_obj.data_ptr()) if b.po_rel is not None else (None, None)
-            pb.sp_subj, pb.sp_rel = (b.sp_subj.data_ptr(), b.sp_rel.data_ptr()) if b.sp_subj is not None else (None, None)
-            pb.n_po, pb.n_sp = b.n_po, b.n_sp
-            c.ids = b.cand_ids.data_ptr() if b.cand_ids is not None else None
-            c.first_id, c.n = b.cand_first, cb.n_cand
+            b, pb, c = cb.batch, self._call.pb, self._call.c
+            self._call.fill_ids(b.po_rel, b.po_obj, b.sp_subj, b.sp_rel, b.cand_ids, b.cand_first, cb.n_cand)
             need = int(eng.lib.okge_score_workspace_bytes(b.B, self._t.d) if self.loss is None else
                        eng.lib.okge_evaluate_batch_loss_workspace_bytes(b.B, self._t.d))
             if self._ws[slot] is None or self._ws[slot].numel() < need:

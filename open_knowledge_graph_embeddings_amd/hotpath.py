@@ -32,8 +32,8 @@ class DropoutSpec:
     keep: Optional[torch.Tensor] = None
     step_dev: Optional[torch.Tensor] = None   # int32[1] on the device: the kernels read the step from it (graph replay)
 
-    def c(self) -> N.Dropout:
-        d = N.Dropout()
+    def fill(self, d: N.Dropout) -> N.Dropout:
+        """every field of `d`, None included: a struct refilled in place keeps nothing of its last use"""
         d.p = float(self.p)
         d.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
         d.stream = int(self.stream) & 0xFFFFFFFF
@@ -41,6 +41,9 @@ class DropoutSpec:
         d.keep = self.keep.data_ptr() if (self.keep is not None and self.p > 0) else None
         d.step_dev = self.step_dev.data_ptr() if self.step_dev is not None else None
         return d
+
+    def c(self) -> N.Dropout:
+        return self.fill(N.Dropout())
 
 
 NO_DROP = DropoutSpec()
@@ -78,13 +81,13 @@ def validate_ids(batch, n_ent, n_rel):
         check("pos_row", batch.pos_row[live], batch.B)
 
 # Philox stream ids: one per place the reference draws an independent Bernoulli mask
-STREAM_CAND, STREAM_PO_ENT, STREAM_PO_REL, STREAM_SP_ENT, STREAM_SP_REL = 0, 1, 2, 3, 4
+STREAMS = STREAM_CAND, STREAM_PO_ENT, STREAM_PO_REL, STREAM_SP_ENT, STREAM_SP_REL = 0, 1, 2, 3, 4
 
 
 def dropout_specs(p_ent, p_rel, seed, step, step_dev=None):
     """the five masks of one step in stream order: the entity streams drop with p_ent, the relation streams with p_rel"""
     return tuple(DropoutSpec(p_rel if stream in (STREAM_PO_REL, STREAM_SP_REL) else p_ent, seed, stream, step, step_dev=step_dev)
-                 for stream in (STREAM_CAND, STREAM_PO_ENT, STREAM_PO_REL, STREAM_SP_ENT, STREAM_SP_REL))
+                 for stream in STREAMS)
 
 
 @dataclass
@@ -107,6 +110,11 @@ class PrefixBatch:
     drop_sp_ent: DropoutSpec = field(default_factory=DropoutSpec)
     drop_sp_rel: DropoutSpec = field(default_factory=DropoutSpec)
     drop_cand: DropoutSpec = field(default_factory=DropoutSpec)
+
+    def set_dropout(self, specs):
+        """the five masks of one step, in the stream order dropout_specs(...) returns them"""
+        self.drop_cand, self.drop_po_ent, self.drop_po_rel, self.drop_sp_ent, self.drop_sp_rel = specs
+        return self
 
     @property
     def n_po(self):
@@ -184,6 +192,109 @@ def occurrence_ids(dev, cand_ids, cand_first, n, po_obj, sp_subj, po_rel, sp_rel
     return ids_e, ids_r
 
 
+def _need_f32(dev, tensors, message, contiguous=True):
+    for t in tensors:
+        if t.dtype != torch.float32 or t.device != dev or (contiguous and not t.is_contiguous()):
+            raise N.OkgeError(message)
+
+
+def _need_i32(dev, tensors, message):
+    for t in tensors:
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise N.OkgeError(message)
+
+
+def train_flags(grads_zero=False, loss_only=False, unique_candidates=False, distinct_prefix_rows=False, clear_grads=False,
+                row_grads=False):
+    """the OKGE_TRAIN_* word of okge_train_forward_backward / okge_n3_forward_backward / okge_train_tiles (include/okge.h)"""
+    return (N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0) | (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) | \
+        (N.OKGE_TRAIN_UNIQUE_CANDIDATES if unique_candidates else 0) | (N.OKGE_TRAIN_DISTINCT_PREFIX_ROWS if distinct_prefix_rows else 0) | \
+        (N.OKGE_TRAIN_CLEAR_GRADS if clear_grads else 0) | (N.OKGE_TRAIN_ROW_GRADS if row_grads else 0)
+
+
+class PrefixCall:
+    """The four argument structs of a prefix call (include/okge.h: okge_tables, okge_prefix_batch, okge_candidates,
+    okge_positives) and the only Python code that knows their fields.  The step drivers keep one and refill it per call -- a
+    0.14 ms step leaves the host ~100 us for everything, and building five dropout and four argument structs anew is a
+    measurable part of that -- so every fill writes ALL the fields it owns, None and 0 included: nothing survives from the
+    previous batch.  The fills read data_ptr(), shapes and numbers only (no engine, no GPU); the two launches take an engine.
+    The tensors a fill was handed must live until the launch is issued."""
+
+    def __init__(self):
+        self.t, self.pb, self.c, self.pos = N.Tables(), N.PrefixBatch(), N.Candidates(), N.Positives()
+        pb = self.pb
+        self.drops = (self.c.drop, pb.drop_po_ent, pb.drop_po_rel, pb.drop_sp_ent, pb.drop_sp_rel)     # in STREAMS order
+        self.n_po = self.n_sp = self.B = self.n = 0        # the shape fill_ids last wrote (B = n_po + n_sp rows, n candidates)
+
+    def fill_tables(self, E, R, scorer, device):
+        # (spelled out, not _need_f32: the step drivers pay for this fill on every step)
+        if E.dtype != torch.float32 or R.dtype != torch.float32 or E.device != device or R.device != device \
+                or not (E.is_contiguous() and R.is_contiguous()):
+            raise N.OkgeError("embedding tables must be contiguous fp32 tensors on the engine's device")
+        t = self.t
+        t.E, t.R, t.n_ent, t.n_rel, t.d, t.scorer = E.data_ptr(), R.data_ptr(), E.shape[0], R.shape[0], E.shape[1], N.scorer_id(scorer)
+        return t
+
+    def fill_dropout(self, p_ent, p_rel, seed, step, step_dev=None):
+        """the five Philox masks of one step (dropout_specs(...) in place)"""
+        p_ent, p_rel, seed, step = float(p_ent), float(p_rel), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF
+        sd = None if step_dev is None else step_dev.data_ptr()
+        for d, stream, p in zip(self.drops, STREAMS, (p_ent, p_ent, p_rel, p_ent, p_rel)):       # (cand, po_ent, po_rel, sp_ent, sp_rel)
+            d.p, d.seed, d.stream, d.step, d.keep, d.step_dev = p, seed, stream, step, None, sd
+
+    def fill_dropout_specs(self, specs):
+        """five DropoutSpec objects in STREAMS order (they may carry replayed `keep` masks)"""
+        for d, spec in zip(self.drops, specs):
+            spec.fill(d)
+
+    def fill_ids(self, po_rel, po_obj, sp_subj, sp_rel, cand_ids, cand_first, n_cand, pos_row=None, pos_col=None, cand_table=None):
+        """the batch's ids: contiguous int32 tensors on the device or None; candidates are the list cand_ids or the range
+        cand_first .. cand_first + n_cand - 1, gathered from cand_table (fp32 (rows, d)) instead of E when one is given"""
+        pb, c, pos = self.pb, self.c, self.pos
+        n_po = 0 if po_rel is None else po_rel.numel()
+        n_sp = 0 if sp_subj is None else sp_subj.numel()
+        pb.po_rel, pb.po_obj = (po_rel.data_ptr(), po_obj.data_ptr()) if n_po else (None, None)
+        pb.sp_subj, pb.sp_rel = (sp_subj.data_ptr(), sp_rel.data_ptr()) if n_sp else (None, None)
+        pb.n_po, pb.n_sp = n_po, n_sp
+        n = int(n_cand) if cand_ids is None else cand_ids.numel()
+        c.ids, c.first_id, c.n = (None if cand_ids is None else cand_ids.data_ptr()), int(cand_first), n
+        c.table, c.table_rows = (None, 0) if cand_table is None else (cand_table.data_ptr(), cand_table.shape[0])
+        nnz = 0 if pos_row is None else pos_row.numel()
+        pos.row, pos.col, pos.nnz = (pos_row.data_ptr(), pos_col.data_ptr(), nnz) if nnz else (None, None, 0)
+        self.n_po, self.n_sp, self.B, self.n = n_po, n_sp, n_po + n_sp, n
+
+    def fill_batch(self, b: PrefixBatch, device):
+        """ids and masks of a PrefixBatch of anything (host tensors, int64 ids, `keep` masks); -> the tensors the structs
+        point into, to be held until the launch is issued"""
+        keep = [_i32(x, device) for x in (b.po_rel, b.po_obj, b.sp_subj, b.sp_rel, b.cand_ids, b.pos_row, b.pos_col)]
+        if b.cand_table is not None:
+            _need_f32(device, (b.cand_table,), "candidate table must be a contiguous fp32 tensor on the engine's device")
+        self.fill_ids(*keep[:5], b.cand_first, b.n_cand, keep[5], keep[6], b.cand_table)
+        self.fill_dropout_specs((b.drop_cand, b.drop_po_ent, b.drop_po_rel, b.drop_sp_ent, b.drop_sp_rel))
+        return keep
+
+    def train(self, engine, loss, label_smoothing, normalizer, flags, loss_out, dE, dR, scores=None):
+        """okge_train_forward_backward on the filled structs; normalizer None: B x N"""
+        ws = engine.workspace(self.B, self.n, self.t.d, "train_rows" if flags & N.OKGE_TRAIN_ROW_GRADS else "train")
+        if normalizer is None:
+            normalizer = float(self.B) * float(self.n)
+        N.check(engine.lib.okge_train_forward_backward(
+            ctypes.byref(self.t), ctypes.byref(self.pb), ctypes.byref(self.c), ctypes.byref(self.pos), N.loss_id(loss),
+            float(label_smoothing), float(normalizer), flags, loss_out.data_ptr(), _ptr(dE), _ptr(dR), _ptr(scores),
+            0 if scores is None else scores.stride(0), ws.data_ptr(), engine._ws_bytes, engine._stream()), "okge_train_forward_backward")
+        return loss_out
+
+    def n3(self, engine, coef, cand_passes, normalizer, flags, reg_out, dE, dR):
+        """okge_n3_forward_backward on the structs a train() call was just issued from (same rows, same masks)"""
+        ws = engine.n3_workspace(self.B, self.n, min(self.t.d, WIDE_MAX_SLOT))
+        if normalizer is None:
+            normalizer = float(self.B) * float(self.n)
+        N.check(engine.lib.okge_n3_forward_backward(
+            ctypes.byref(self.t), ctypes.byref(self.pb), ctypes.byref(self.c), float(coef), int(cand_passes), float(normalizer),
+            flags, reg_out.data_ptr(), _ptr(dE), _ptr(dR), ws.data_ptr(), engine._ws_bytes, engine._stream()), "okge_n3_forward_backward")
+        return reg_out
+
+
 class HotPath:
     """Owns the scratch workspace for one device and issues the C-ABI calls on torch's current stream."""
 
@@ -194,6 +305,8 @@ class HotPath:
         self.lib = N.lib()
         self._ws = None
         self._ws_bytes = 0
+        # side scratch: buffers that outlive a call or run beside the one workspace (_side grows them)
+        self._rows_ws = self._sb_ws = self._clip_ws = self._clip_multi_ws = self._ews = self._grad_rows = None
 
     # -- plumbing ------------------------------------------------------------------------------------
     def _stream(self):
@@ -209,6 +322,14 @@ class HotPath:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._ws_bytes = need
         return self._ws
+
+    def _side(self, name, need):
+        """the side scratch buffer `name` with at least `need` bytes: grown, never shrunk"""
+        buf = getattr(self, name)
+        if buf is None or buf.numel() * buf.element_size() < need:
+            buf = torch.empty(need, dtype=torch.uint8, device=self.device)
+            setattr(self, name, buf)
+        return buf
 
     def workspace(self, B, n_cand, d, kind="train"):
         """scratch for one call; kind 'score' (query block only) and 'lse' are much smaller than 'train'"""
@@ -229,43 +350,20 @@ class HotPath:
             validate_ids(batch, E.shape[0], R.shape[0])
 
     def _tables(self, E, R, scorer):
-        for t in (E, R):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
-                raise N.OkgeError("embedding tables must be contiguous fp32 tensors on the engine's device")
-        t = N.Tables()
-        t.E, t.R = E.data_ptr(), R.data_ptr()
-        t.n_ent, t.n_rel, t.d = E.shape[0], R.shape[0], E.shape[1]
-        t.scorer = N.SCORERS[scorer] if isinstance(scorer, str) else int(scorer)
-        return t
+        return PrefixCall().fill_tables(E, R, scorer, self.device)
+
+    def _filled(self, b: PrefixBatch):
+        """-> (a fresh PrefixCall holding the batch, the int32 tensors it points into)"""
+        call = PrefixCall()
+        return call, call.fill_batch(b, self.device)
 
     def _batch(self, b: PrefixBatch):
-        dev = self.device
-        keep = [_i32(b.po_rel, dev), _i32(b.po_obj, dev), _i32(b.sp_subj, dev), _i32(b.sp_rel, dev),
-                _i32(b.cand_ids, dev)]
-        pb = N.PrefixBatch()
-        pb.po_rel, pb.po_obj, pb.sp_subj, pb.sp_rel = (_ptr(x) for x in keep[:4])
-        pb.n_po, pb.n_sp = b.n_po, b.n_sp
-        pb.drop_po_ent, pb.drop_po_rel = b.drop_po_ent.c(), b.drop_po_rel.c()
-        pb.drop_sp_ent, pb.drop_sp_rel = b.drop_sp_ent.c(), b.drop_sp_rel.c()
-        c = N.Candidates()
-        c.ids = _ptr(keep[4])
-        c.first_id = int(b.cand_first)
-        c.n = int(b.n_cand if keep[4] is None else keep[4].numel())
-        c.drop = b.drop_cand.c()
-        if b.cand_table is not None:
-            ct = b.cand_table
-            if ct.dtype != torch.float32 or not ct.is_contiguous() or ct.device != dev:
-                raise N.OkgeError("candidate table must be a contiguous fp32 tensor on the engine's device")
-            c.table, c.table_rows = ct.data_ptr(), ct.shape[0]
-            keep.append(ct)
-        return pb, c, keep
+        call, keep = self._filled(b)
+        return call.pb, call.c, keep
 
     def _positives(self, b: PrefixBatch):
-        """-> (okge_positives, the int32 tensors it points into)"""
-        keep = [_i32(b.pos_row, self.device), _i32(b.pos_col, self.device)]
-        pos = N.Positives()
-        pos.row, pos.col, pos.nnz = _ptr(keep[0]), _ptr(keep[1]), b.nnz
-        return pos, keep
+        call, keep = self._filled(b)
+        return call.pos, keep
 
     # -- entry points -------------------------------------------------------------------------------
     def score(self, E, R, scorer, batch: PrefixBatch, out=None):
@@ -291,30 +389,19 @@ class HotPath:
         call itself clears, okge.h OKGE_TRAIN_CLEAR_GRADS); returns the summed loss as a device double[1] tensor (no host sync).
         row_grads: dE (N + B, d) / dR (B, d) are occurrence-row buffers, every row stored once (okge.h OKGE_TRAIN_ROW_GRADS)."""
         self._check(batch, E, R)
-        pb, c, keep = self._batch(batch)
-        t = self._tables(E, R, scorer)
-        B, n = batch.B, c.n
+        call, keep = self._filled(batch)
+        d = call.fill_tables(E, R, scorer, self.device).d
+        B, n = call.B, call.n
         if row_grads:
-            if loss_only or dE is None or dR is None or tuple(dE.shape) != (n + B, t.d) or tuple(dR.shape) != (B, t.d) \
+            if loss_only or dE is None or dR is None or tuple(dE.shape) != (n + B, d) or tuple(dR.shape) != (B, d) \
                     or not dE.is_contiguous() or not dR.is_contiguous():
-                raise N.OkgeError(f"row_grads: dE must be a contiguous ({n + B}, {t.d}) and dR a ({B}, {t.d}) fp32 buffer")
-        ws = self.workspace(B, n, t.d, "train_rows" if row_grads else "train")
-        pos, keep_pos = self._positives(batch)
-        if normalizer is None:
-            normalizer = float(B) * float(n)
+                raise N.OkgeError(f"row_grads: dE must be a contiguous ({n + B}, {d}) and dR a ({B}, {d}) fp32 buffer")
         if loss_out is None:
             loss_out = torch.empty(1, dtype=torch.float64, device=self.device)
-        N.check(self.lib.okge_train_forward_backward(
-            ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), ctypes.byref(pos),
-            N.LOSSES[loss] if isinstance(loss, str) else int(loss), float(label_smoothing), float(normalizer),
-            (N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0) | (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) |
-            (N.OKGE_TRAIN_UNIQUE_CANDIDATES if batch.cand_unique else 0) |
-            (N.OKGE_TRAIN_DISTINCT_PREFIX_ROWS if distinct_prefix_rows else 0) |
-            (N.OKGE_TRAIN_CLEAR_GRADS if clear_grads else 0) | (N.OKGE_TRAIN_ROW_GRADS if row_grads else 0),
-            loss_out.data_ptr(), _ptr(dE), _ptr(dR),
-            None if scores is None else scores.data_ptr(), 0 if scores is None else scores.stride(0),
-            ws.data_ptr(), self._ws_bytes, self._stream()), "okge_train_forward_backward")
-        del keep, keep_pos
+        flags = train_flags(grads_zero=grads_zero, loss_only=loss_only, unique_candidates=batch.cand_unique,
+                            distinct_prefix_rows=distinct_prefix_rows, clear_grads=clear_grads, row_grads=row_grads)
+        call.train(self, loss, label_smoothing, normalizer, flags, loss_out, dE, dR, scores)
+        del keep
         return loss_out
 
     def n3_workspace(self, B, n_cand, d):
@@ -331,19 +418,13 @@ class HotPath:
         its gradient / normalizer ADDED to dE / dR -- issue it after forward_backward with the same batch and buffers
         (okge.h, okge_n3_forward_backward).  coef = n3_coef(l2_reg, dropout)."""
         self._check(batch, E, R)
-        pb, c, keep = self._batch(batch)
-        t = self._tables(E, R, scorer)
-        B, n = batch.B, c.n
-        ws = self.n3_workspace(B, n, min(t.d, WIDE_MAX_SLOT))
-        if normalizer is None:
-            normalizer = float(B) * float(n)
+        call, keep = self._filled(batch)
+        call.fill_tables(E, R, scorer, self.device)
         if reg_out is None:
             reg_out = torch.empty(1, dtype=torch.float64, device=self.device)
-        flags = (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) | (N.OKGE_TRAIN_UNIQUE_CANDIDATES if batch.cand_unique else 0) | \
-            (N.OKGE_TRAIN_DISTINCT_PREFIX_ROWS if distinct_prefix_rows else 0) | (N.OKGE_TRAIN_ROW_GRADS if row_grads else 0)
-        N.check(self.lib.okge_n3_forward_backward(ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), float(coef), int(cand_passes),
-                                                  float(normalizer), flags, reg_out.data_ptr(), _ptr(dE), _ptr(dR), ws.data_ptr(),
-                                                  self._ws_bytes, self._stream()), "okge_n3_forward_backward")
+        flags = train_flags(loss_only=loss_only, unique_candidates=batch.cand_unique, distinct_prefix_rows=distinct_prefix_rows,
+                            row_grads=row_grads)
+        call.n3(self, coef, cand_passes, normalizer, flags, reg_out, dE, dR)
         del keep
         return reg_out
 
@@ -396,11 +477,10 @@ class HotPath:
         """Local candidates only: batch.cand_first / n_cand are LOCAL row indices, batch.pos_col GLOBAL columns.
         KL loss: `row_lse` = log-sum-exp of every row's scores over ALL shards' candidates.  loss_only: no gradients.
         B: query rows in Q, for a batch that names candidates and positives only (default: the batch's rows)."""
-        pb, c, keep = self._batch(batch)
-        t = self._tables(E_local, R, scorer)
+        call, keep = self._filled(batch)
+        t, c, pos = call.fill_tables(E_local, R, scorer, self.device), call.c, call.pos
         B, n = batch.B if B is None else int(B), c.n
         ws = self.workspace(B, n, t.d)
-        pos, keep_pos = self._positives(batch)
         if normalizer is None:
             normalizer = float(B) * float(n_cand_global)
         if loss_out is None:
@@ -408,11 +488,10 @@ class HotPath:
         sh = shard.c()
         N.check(self.lib.okge_train_tiles(
             ctypes.byref(t), ctypes.byref(sh), Q.data_ptr(), Q.stride(0), B, ctypes.byref(c), ctypes.byref(pos),
-            N.LOSSES[loss] if isinstance(loss, str) else int(loss), float(label_smoothing), float(normalizer),
-            int(n_cand_global), (N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0) | (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) |
-            (N.OKGE_TRAIN_UNIQUE_CANDIDATES if batch.cand_unique else 0), _ptr(row_lse), loss_out.data_ptr(),
-            dE.data_ptr(), dQ.data_ptr(), ws.data_ptr(), self._ws_bytes, self._stream()), "okge_train_tiles")
-        del keep, keep_pos
+            N.loss_id(loss), float(label_smoothing), float(normalizer), int(n_cand_global),
+            train_flags(grads_zero=grads_zero, loss_only=loss_only, unique_candidates=batch.cand_unique), _ptr(row_lse),
+            loss_out.data_ptr(), dE.data_ptr(), dQ.data_ptr(), ws.data_ptr(), self._ws_bytes, self._stream()), "okge_train_tiles")
+        del keep
         return loss_out
 
     def score_queries(self, E_local, R, scorer, Q, B, batch: PrefixBatch, shard: Shard, out=None):
@@ -512,14 +591,13 @@ class HotPath:
         sh = shard.c()
         if rel_segments is not None:
             sg = rel_segments
-            if getattr(self, "_grad_rows", None) is None or self._grad_rows.shape[1:] != dQ.shape:
-                self._grad_rows = torch.empty((2,) + tuple(dQ.shape), dtype=dQ.dtype, device=dQ.device)
+            grad_rows = self._side("_grad_rows", 2 * dQ.shape[0] * dQ.stride(0) * dQ.element_size())     # [2][rows][ld] as dQ
             r_o, r_p = sg.rel if sg.rel is not None else (None, None)
             e_o, e_p = sg.ent if sg.ent is not None else (None, None)
             N.check(self.lib.okge_prefix_backward_segmented(ctypes.byref(t), ctypes.byref(sh), ctypes.byref(pb), dQ.data_ptr(),
                                                             dQ.stride(0), _ptr(ent_rows), _ptr(r_o), _ptr(r_p),
                                                             0 if r_p is None else int(r_p.numel()) - 1, _ptr(e_o), _ptr(e_p),
-                                                            0 if e_p is None else int(e_p.numel()) - 1, self._grad_rows.data_ptr(),
+                                                            0 if e_p is None else int(e_p.numel()) - 1, grad_rows.data_ptr(),
                                                             dE.data_ptr(), dR.data_ptr(), self._stream()),
                     "okge_prefix_backward_segmented")
             del keep
@@ -533,12 +611,12 @@ class HotPath:
         """(b, 1) scores of b encoded triples (rows (b, d), last dim contiguous): triple_score (model.py:178-179)."""
         rows = [x.reshape(-1, x.shape[-1]) for x in (subj, rel, obj)]
         b, d = rows[0].shape
-        for x in rows:
-            if x.dtype != torch.float32 or x.stride(1) != 1 or x.device != self.device or x.shape != (b, d):
-                raise N.OkgeError("triple rows must be fp32 (b, d) on the engine's device with a contiguous last dim")
+        message = "triple rows must be fp32 (b, d) on the engine's device with a contiguous last dim"
+        _need_f32(self.device, rows, message, contiguous=False)
+        if any(x.stride(1) != 1 or x.shape != (b, d) for x in rows):
+            raise N.OkgeError(message)
         out = torch.empty((b, 1), dtype=torch.float32, device=self.device)
-        N.check(self.lib.okge_score_triples(N.SCORERS[scorer] if isinstance(scorer, str) else int(scorer),
-                                            rows[0].data_ptr(), rows[0].stride(0), rows[1].data_ptr(), rows[1].stride(0),
+        N.check(self.lib.okge_score_triples(N.scorer_id(scorer), rows[0].data_ptr(), rows[0].stride(0), rows[1].data_ptr(), rows[1].stride(0),
                                             rows[2].data_ptr(), rows[2].stride(0), b, d, out.data_ptr(), self._stream()),
                 "okge_score_triples")
         return out
@@ -560,16 +638,13 @@ class HotPath:
         """(d_ent, d_rel, d_cand) of scores = fold(ent, rel) . cand^T from the dense (b, n) gradient g (okge_prefix_score_backward)"""
         b, n = g.shape
         d = cand.shape[1]
-        need = int(self.lib.okge_prefix_score_backward_workspace_bytes(b, n, d))
-        if getattr(self, "_sb_ws", None) is None or self._sb_ws.numel() < need:
-            self._sb_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._side("_sb_ws", int(self.lib.okge_prefix_score_backward_workspace_bytes(b, n, d)))
         out = [torch.empty((b, d), dtype=torch.float32, device=self.device) if need_ent else None,
                torch.empty((b, d), dtype=torch.float32, device=self.device) if need_rel else None,
                torch.empty((n, d), dtype=torch.float32, device=self.device) if need_cand else None]
-        N.check(self.lib.okge_prefix_score_backward(N.SCORERS[scorer] if isinstance(scorer, str) else int(scorer), 1 if sp else 0,
-                                                    g.data_ptr(), g.stride(0), b, n, ent.data_ptr(), ent.stride(0), rel.data_ptr(),
-                                                    rel.stride(0), cand.data_ptr(), cand.stride(0), d, _ptr(out[0]), _ptr(out[1]),
-                                                    _ptr(out[2]), self._sb_ws.data_ptr(), self._sb_ws.numel(), self._stream()),
+        N.check(self.lib.okge_prefix_score_backward(N.scorer_id(scorer), 1 if sp else 0, g.data_ptr(), g.stride(0), b, n, ent.data_ptr(),
+                                                    ent.stride(0), rel.data_ptr(), rel.stride(0), cand.data_ptr(), cand.stride(0), d,
+                                                    _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), ws.data_ptr(), ws.numel(), self._stream()),
                 "okge_prefix_score_backward")
         return out
 
@@ -626,25 +701,31 @@ class HotPath:
         tensors = [(p, state_sum, ids, g)] + ([tuple(second)] if second is not None else [])
         arr = (N.RowsTensor * len(tensors))()
         for a, (p_, s_, i_, g_) in zip(arr, tensors):
-            n = int(i_.numel())
-            if i_.dtype != torch.int32 or not i_.is_contiguous() or i_.device != self.device:
-                raise N.OkgeError("adagrad_rows: ids must be a contiguous int32 tensor on the engine's device")
-            for x in (p_, s_, g_):
-                if x.dtype != torch.float32 or x.device != self.device:
-                    raise N.OkgeError("adagrad_rows: fp32 tensors on the engine's device")
+            _need_i32(self.device, (i_,), "adagrad_rows: ids must be a contiguous int32 tensor on the engine's device")
+            _need_f32(self.device, (p_, s_, g_), "adagrad_rows: fp32 tensors on the engine's device", contiguous=False)
             if p_.dim() != 2 or not p_.is_contiguous() or not s_.is_contiguous() or s_.shape != p_.shape:
                 raise N.OkgeError("adagrad_rows: p and state_sum must be contiguous (rows, row_len) tensors of one shape")
-            if n and (g_.dim() != 2 or g_.shape[0] != n or g_.shape[1] != p_.shape[1] or g_.stride(1) != 1):
-                raise N.OkgeError("adagrad_rows: g must hold one row of row_len floats per id, last dim contiguous")
-            a.p, a.state_sum, a.ids, a.g = p_.data_ptr(), s_.data_ptr(), i_.data_ptr(), g_.data_ptr()
-            a.ld_g = int(g_.stride(0)) if n > 1 else int(p_.shape[1])
-            a.n, a.table_rows, a.row_len = n, int(p_.shape[0]), int(p_.shape[1])
+            a.p, a.state_sum = p_.data_ptr(), s_.data_ptr()
+            self._fill_rows(a, "adagrad_rows", p_, i_, g_)
+        ws = self._rows_scratch(arr, self.lib.okge_adagrad_rows_workspace_bytes)
+        N.check(self.lib.okge_adagrad_rows(arr, len(tensors), float(lr), float(eps), ws.data_ptr(), ws.numel(), self._stream()),
+                "okge_adagrad_rows")
+
+    def _fill_rows(self, a, who, p, ids, g):
+        """the (ids, g, ld_g, n, table_rows, row_len) block the three row-tensor structs share; g None: no gradient rows"""
+        n, row_len = int(ids.numel()), int(p.shape[1])
+        a.ids, a.n, a.table_rows, a.row_len, a.ld_g = ids.data_ptr(), n, int(p.shape[0]), row_len, row_len
+        if g is not None:
+            if n and (g.dim() != 2 or g.shape[0] != n or g.shape[1] != row_len or g.stride(1) != 1):
+                raise N.OkgeError(f"{who}: g must hold one row of row_len floats per id, last dim contiguous")
+            a.g = g.data_ptr()
+            if n > 1:
+                a.ld_g = int(g.stride(0))
+
+    def _rows_scratch(self, arr, size):
+        """the sort-key scratch of a row-tensor array of one or two tensors (size: the entry point's *_workspace_bytes)"""
         ns = [int(a.n) for a in arr] + [0]
-        need = int(self.lib.okge_adagrad_rows_workspace_bytes(ns[0], ns[1]))
-        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < need:
-            self._rows_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        N.check(self.lib.okge_adagrad_rows(arr, len(tensors), float(lr), float(eps), self._rows_ws.data_ptr(), self._rows_ws.numel(),
-                                           self._stream()), "okge_adagrad_rows")
+        return self._side("_rows_ws", max(int(size(ns[0], ns[1])), 256))
 
     @staticmethod
     def adam_state(device, step=0):
@@ -654,19 +735,25 @@ class HotPath:
             st[0] = int(step)
         return st
 
+    def _adam_tensors(self, struct, tensors, who):
+        """(p, g, exp_avg, exp_avg_sq, state, ...) tuples -> an array of `struct` with the fields okge_adam_tensor and
+        okge_adam_multi_tensor share"""
+        arr = (struct * len(tensors))()
+        state_message = f"{who}: the state is a contiguous int32[4] tensor on the engine's device (HotPath.adam_state)"
+        for a, (p, g, m, v, st) in zip(arr, (t[:5] for t in tensors)):
+            _need_f32(self.device, (p, g, m, v), f"{who}: contiguous fp32 tensors on the engine's device")
+            if g.numel() != p.numel() or m.numel() != p.numel() or v.numel() != p.numel():
+                raise N.OkgeError(f"{who}: p, g, exp_avg and exp_avg_sq must have one size")
+            _need_i32(self.device, (st,), state_message)
+            if st.numel() != 4:
+                raise N.OkgeError(state_message)
+            a.p, a.g, a.exp_avg, a.exp_avg_sq, a.state, a.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), st.data_ptr(), p.numel()
+        return arr
+
     def adam(self, tensors, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, zero_grad=True):
         """okge_adam_step: torch.optim.Adam's update (no amsgrad, coupled weight decay) on one or two (p, g, exp_avg, exp_avg_sq,
         state) tuples in one sweep; each state (adam_state) advances by one step on the device.  zero_grad as adagrad2."""
-        arr = (N.AdamTensor * len(tensors))()
-        for a, (p, g, m, v, st) in zip(arr, tensors):
-            for x in (p, g, m, v):
-                if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous():
-                    raise N.OkgeError("adam: contiguous fp32 tensors on the engine's device")
-            if g.numel() != p.numel() or m.numel() != p.numel() or v.numel() != p.numel():
-                raise N.OkgeError("adam: p, g, exp_avg and exp_avg_sq must have one size")
-            if st.dtype != torch.int32 or st.numel() != 4 or st.device != self.device or not st.is_contiguous():
-                raise N.OkgeError("adam: the state is a contiguous int32[4] tensor on the engine's device (HotPath.adam_state)")
-            a.p, a.g, a.exp_avg, a.exp_avg_sq, a.state, a.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), st.data_ptr(), p.numel()
+        arr = self._adam_tensors(N.AdamTensor, tensors, "adam")
         N.check(self.lib.okge_adam_step(arr, len(tensors), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                         int(zero_grad), self._stream()), "okge_adam_step")
 
@@ -674,19 +761,10 @@ class HotPath:
         """okge_adam_multi: okge_adam_step's update on up to four (p, g, exp_avg, exp_avg_sq, state[, touched_map, stamp]) tuples in
         one sweep, gradients cleared; a tensor with a touched-row byte map takes g = 0 on the rows the map does not stamp, whose
         gradient rows are neither read nor cleared.  Every distinct state advances by one step on the device."""
-        arr = (N.AdamMultiTensor * len(tensors))()
+        arr = self._adam_tensors(N.AdamMultiTensor, tensors, "adam_multi")
         for a, t in zip(arr, tensors):
-            p, g, m, v, st = t[:5]
-            for x in (p, g, m, v):
-                if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous():
-                    raise N.OkgeError("adam_multi: contiguous fp32 tensors on the engine's device")
-            if g.numel() != p.numel() or m.numel() != p.numel() or v.numel() != p.numel():
-                raise N.OkgeError("adam_multi: p, g, exp_avg and exp_avg_sq must have one size")
-            if st.dtype != torch.int32 or st.numel() != 4 or st.device != self.device or not st.is_contiguous():
-                raise N.OkgeError("adam_multi: the state is a contiguous int32[4] tensor on the engine's device (HotPath.adam_state)")
-            a.p, a.g, a.exp_avg, a.exp_avg_sq, a.state, a.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), st.data_ptr(), p.numel()
             if len(t) > 5 and t[5] is not None:
-                a.row_touched, a.row_len, a.touched_stamp = t[5].data_ptr(), p.shape[1], int(t[6])
+                a.row_touched, a.row_len, a.touched_stamp = t[5].data_ptr(), t[0].shape[1], int(t[6])
         N.check(self.lib.okge_adam_multi(arr, len(tensors), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                          self._stream()), "okge_adam_multi")
 
@@ -696,14 +774,11 @@ class HotPath:
         arr = (N.GradTensor * len(tensors))()
         for a, t in zip(arr, tensors):
             g, touched, stamp = t if isinstance(t, (tuple, list)) else (t, None, 0)
-            if g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous():
-                raise N.OkgeError("clip_grad_norm_multi: contiguous fp32 tensors on the engine's device")
+            _need_f32(self.device, (g,), "clip_grad_norm_multi: contiguous fp32 tensors on the engine's device")
             a.g, a.n = g.data_ptr(), g.numel()
             if touched is not None:
                 a.row_touched, a.row_len, a.touched_stamp = touched.data_ptr(), g.shape[1], int(stamp)
-        if getattr(self, "_clip_multi_ws", None) is None:
-            self._clip_multi_ws = torch.empty(int(self.lib.okge_clip_grad_norm_multi_workspace_bytes()), dtype=torch.uint8, device=self.device)
-        ws = self._clip_multi_ws
+        ws = self._side("_clip_multi_ws", int(self.lib.okge_clip_grad_norm_multi_workspace_bytes()))
         N.check(self.lib.okge_clip_grad_norm_multi(arr, len(tensors), float(max_norm), _ptr(norm_out), ws.data_ptr(), ws.numel(),
                                                    self._stream()), "okge_clip_grad_norm_multi")
 
@@ -713,50 +788,27 @@ class HotPath:
         of p and the two moments move; every state advances by one step, also where n = 0."""
         arr = (N.AdamRowsTensor * len(tensors))()
         for a, (p_, m_, v_, st_, i_, g_) in zip(arr, tensors):
-            n = int(i_.numel())
-            for x in (i_, st_):
-                if x.dtype != torch.int32 or not x.is_contiguous() or x.device != self.device:
-                    raise N.OkgeError("adam_rows: ids and state must be contiguous int32 tensors on the engine's device")
-            for x in (p_, m_, v_, g_):
-                if x.dtype != torch.float32 or x.device != self.device:
-                    raise N.OkgeError("adam_rows: fp32 tensors on the engine's device")
+            _need_i32(self.device, (i_, st_), "adam_rows: ids and state must be contiguous int32 tensors on the engine's device")
+            _need_f32(self.device, (p_, m_, v_, g_), "adam_rows: fp32 tensors on the engine's device", contiguous=False)
             if p_.dim() != 2 or not (p_.is_contiguous() and m_.is_contiguous() and v_.is_contiguous()) or m_.shape != p_.shape or \
                     v_.shape != p_.shape or st_.numel() != 4:
                 raise N.OkgeError("adam_rows: p, exp_avg and exp_avg_sq must be contiguous (rows, row_len) tensors of one shape, state int32[4]")
-            if n and (g_.dim() != 2 or g_.shape[0] != n or g_.shape[1] != p_.shape[1] or g_.stride(1) != 1):
-                raise N.OkgeError("adam_rows: g must hold one row of row_len floats per id, last dim contiguous")
             a.p, a.exp_avg, a.exp_avg_sq, a.state = p_.data_ptr(), m_.data_ptr(), v_.data_ptr(), st_.data_ptr()
-            a.ids, a.g = i_.data_ptr(), g_.data_ptr()
-            a.ld_g = int(g_.stride(0)) if n > 1 else int(p_.shape[1])
-            a.n, a.table_rows, a.row_len = n, int(p_.shape[0]), int(p_.shape[1])
-        ns = [int(a.n) for a in arr] + [0]
-        need = int(self.lib.okge_adam_rows_workspace_bytes(ns[0], ns[1]))
-        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < need:
-            self._rows_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        N.check(self.lib.okge_adam_rows(arr, len(tensors), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                        self._rows_ws.data_ptr(), self._rows_ws.numel(), self._stream()), "okge_adam_rows")
+            self._fill_rows(a, "adam_rows", p_, i_, g_)
+        ws = self._rows_scratch(arr, self.lib.okge_adam_rows_workspace_bytes)
+        N.check(self.lib.okge_adam_rows(arr, len(tensors), float(lr), float(betas[0]), float(betas[1]), float(eps), ws.data_ptr(),
+                                        ws.numel(), self._stream()), "okge_adam_rows")
 
     def _rows_decay_tensors(self, tensors, who):
         """(p, state_sum, ids, g or None, row_steps) tuples -> the okge_rows_decay_tensor array"""
         arr = (N.RowsDecayTensor * len(tensors))()
         for a, (p_, s_, i_, g_, st_) in zip(arr, tensors):
-            n = int(i_.numel())
-            for x in (i_, st_):
-                if x.dtype != torch.int32 or not x.is_contiguous() or x.device != self.device:
-                    raise N.OkgeError(f"{who}: ids and row_steps must be contiguous int32 tensors on the engine's device")
-            for x in (p_, s_) + (() if g_ is None else (g_,)):
-                if x.dtype != torch.float32 or x.device != self.device:
-                    raise N.OkgeError(f"{who}: fp32 tensors on the engine's device")
+            _need_i32(self.device, (i_, st_), f"{who}: ids and row_steps must be contiguous int32 tensors on the engine's device")
+            _need_f32(self.device, (p_, s_) + (() if g_ is None else (g_,)), f"{who}: fp32 tensors on the engine's device", contiguous=False)
             if p_.dim() != 2 or not p_.is_contiguous() or not s_.is_contiguous() or s_.shape != p_.shape or st_.numel() != p_.shape[0]:
                 raise N.OkgeError(f"{who}: p and state_sum must be contiguous (rows, row_len) tensors of one shape, row_steps (rows,)")
-            a.p, a.state_sum, a.ids, a.row_steps = p_.data_ptr(), s_.data_ptr(), i_.data_ptr(), st_.data_ptr()
-            a.n, a.table_rows, a.row_len, a.ld_g = n, int(p_.shape[0]), int(p_.shape[1]), int(p_.shape[1])
-            if g_ is not None:
-                if n and (g_.dim() != 2 or g_.shape[0] != n or g_.shape[1] != p_.shape[1] or g_.stride(1) != 1):
-                    raise N.OkgeError(f"{who}: g must hold one row of row_len floats per id, last dim contiguous")
-                a.g = g_.data_ptr()
-                if n > 1:
-                    a.ld_g = int(g_.stride(0))
+            a.p, a.state_sum, a.row_steps = p_.data_ptr(), s_.data_ptr(), st_.data_ptr()
+            self._fill_rows(a, who, p_, i_, g_)
         return arr
 
     def rows_catch_up(self, tensors, counters, lr, weight_decay=1e-10, eps=1e-8):
@@ -770,13 +822,9 @@ class HotPath:
         """okge_adagrad_rows_decay: okge_adagrad_rows with the dense step's weight-decay term on the named rows, then the due
         slice of the deferred decay-only steps and T += 1.  tensors: one or two (p, state_sum, ids, g, row_steps)."""
         arr = self._rows_decay_tensors(tensors, "adagrad_rows_decay")
-        ns = [int(a.n) for a in arr] + [0]
-        need = int(self.lib.okge_adagrad_rows_workspace_bytes(ns[0], ns[1]))
-        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < need:
-            self._rows_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        ws = self._rows_scratch(arr, self.lib.okge_adagrad_rows_workspace_bytes)
         N.check(self.lib.okge_adagrad_rows_decay(arr, len(tensors), counters.data_ptr(), int(window), float(lr), float(weight_decay),
-                                                 float(eps), self._rows_ws.data_ptr(), self._rows_ws.numel(), self._stream()),
-                "okge_adagrad_rows_decay")
+                                                 float(eps), ws.data_ptr(), ws.numel(), self._stream()), "okge_adagrad_rows_decay")
 
     @staticmethod
     def lazy_tensors(tensors):
@@ -802,11 +850,9 @@ class HotPath:
 
     def clip_grad_norm_(self, g0, g1, max_norm, norm_out=None):
         """torch.nn.utils.clip_grad_norm_ over two dense gradient tensors, in place (trainer.py:236-240)"""
-        if getattr(self, "_clip_ws", None) is None:
-            self._clip_ws = torch.empty(8448, dtype=torch.uint8, device=self.device)
+        ws = self._side("_clip_ws", 8448)
         N.check(self.lib.okge_clip_grad_norm(g0.data_ptr(), g0.numel(), _ptr(g1), 0 if g1 is None else g1.numel(), float(max_norm),
-                                             _ptr(norm_out), self._clip_ws.data_ptr(), self._clip_ws.numel(), self._stream()),
-                "okge_clip_grad_norm")
+                                             _ptr(norm_out), ws.data_ptr(), ws.numel(), self._stream()), "okge_clip_grad_norm")
 
     def merge_logsumexp(self, parts, out=None):
         """parts (world, B) fp32 per-shard row log-sum-exps -> (B,) log-sum-exp over the shards"""
@@ -901,14 +947,13 @@ class HotPath:
         t = self._tables(E_local, R, scorer)
         n_groups, n_filter = int(grp_ptr.numel()) - 1, int(filt_col.numel())
         need = int(self.lib.okge_eval_workspace_bytes(B, c.n, t.d, n_groups, n_filter))
-        if phase == 1 and (getattr(self, "_ews", None) is None or self._ews.numel() < need):
-            self._ews = torch.empty(need, dtype=torch.uint8, device=self.device)       # lives across the three phases
+        ews = self._side("_ews", need) if phase == 1 else self._ews                    # lives across the three phases
         sh = shard.c()
         N.check(self.lib.okge_evaluate_fused_shard(int(phase), ctypes.byref(t), ctypes.byref(sh), Q.data_ptr(), Q.stride(0), int(B),
                                                    ctypes.byref(c), int(n_cand_global), filt_ptr.data_ptr(),
                                                    _ptr(filt_col) if n_filter else None, n_filter, row_ptr.data_ptr(),
                                                    grp_ptr.data_ptr(), _ptr(ids), n_groups, true_scores.data_ptr(),
-                                                   counts.data_ptr(), self._ews.data_ptr(), self._ews.numel(), self._stream()),
+                                                   counts.data_ptr(), ews.data_ptr(), ews.numel(), self._stream()),
                 "okge_evaluate_fused_shard")
         del cid
 

@@ -151,16 +151,6 @@ class ShardedTrainStep:
         """every tensor a step mutates (train_step.GraphedTrainStep snapshots them around its warm-up)"""
         return [self.E, self.R, self.dE, self.dR, self.sumE, self.sumR]
 
-    def _set_dropout(self, batch):
-        # step_dev (attached by GraphedTrainStep): the kernels read the step from a device counter the graph increments, so a
-        # replay of the captured step -- collectives included -- draws fresh masks
-        pe, pr, s, t, sd = self.input_dropout, self.relation_input_dropout, self.seed, self.steps, getattr(self, "step_dev", None)
-        batch.drop_cand = H.DropoutSpec(pe, s, H.STREAM_CAND, t, step_dev=sd)
-        batch.drop_po_ent = H.DropoutSpec(pe, s, H.STREAM_PO_ENT, t, step_dev=sd)
-        batch.drop_sp_ent = H.DropoutSpec(pe, s, H.STREAM_SP_ENT, t, step_dev=sd)
-        batch.drop_po_rel = H.DropoutSpec(pr, s, H.STREAM_PO_REL, t, step_dev=sd)
-        batch.drop_sp_rel = H.DropoutSpec(pr, s, H.STREAM_SP_REL, t, step_dev=sd)
-
     def _entity_rows(self, batch, plan):
         """masked prefix entity rows of ALL prefixes on every rank: all-gather of the owned rows (plan) or all-reduce"""
         eng = self.engine
@@ -184,14 +174,17 @@ class ShardedTrainStep:
         if batch.cand_ids is not None:
             raise NotImplementedError("batch-shared sampled candidates are too few to shard: use replicas")
         self.steps += 1
-        self._set_dropout(batch)
+        # step_dev (attached by GraphedTrainStep): the kernels read the step from a device counter the graph increments, so a
+        # replay of the captured step -- collectives included -- draws fresh masks
+        drops = H.dropout_specs(self.input_dropout, self.relation_input_dropout, self.seed, self.steps, getattr(self, "step_dev", None))
+        batch.set_dropout(drops)
+        # the batch against this rank's candidates
+        local = H.PrefixBatch(po_rel=batch.po_rel, po_obj=batch.po_obj, sp_subj=batch.sp_subj, sp_rel=batch.sp_rel,
+                              pos_row=batch.pos_row, pos_col=batch.pos_col, cand_first=self.cand_first_local,
+                              n_cand=self.n_cand_local).set_dropout(drops)
         eng = self.engine
         if self.world == 1 and isinstance(eng, H.HotPath) and not self.force_exchange:
             # one rank owns everything: the fused single-device call (no slab reduction, no exchange buffers)
-            local = H.PrefixBatch(po_rel=batch.po_rel, po_obj=batch.po_obj, sp_subj=batch.sp_subj, sp_rel=batch.sp_rel,
-                                  pos_row=batch.pos_row, pos_col=batch.pos_col, cand_first=self.cand_first_local,
-                                  n_cand=self.n_cand_local, drop_cand=batch.drop_cand, drop_po_ent=batch.drop_po_ent,
-                                  drop_sp_ent=batch.drop_sp_ent, drop_po_rel=batch.drop_po_rel, drop_sp_rel=batch.drop_sp_rel)
             eng.forward_backward(self.E, self.R, self.scorer, local, self.dE, self.dR, loss=self.loss,
                                  label_smoothing=self.label_smoothing, normalizer=float(batch.B) * float(self.n_cand_global),
                                  loss_out=self.loss_out, grads_zero=True)
@@ -202,9 +195,6 @@ class ShardedTrainStep:
         er = self._entity_rows(batch, plan)
         qe = (eng.fold_queries(self.E, self.R, self.scorer, batch, er), er)
         # 2. local candidates: loss partial, local entity gradients, partial query gradients
-        local = H.PrefixBatch(po_rel=batch.po_rel, po_obj=batch.po_obj, sp_subj=batch.sp_subj, sp_rel=batch.sp_rel,
-                              pos_row=batch.pos_row, pos_col=batch.pos_col, cand_first=self.cand_first_local,
-                              n_cand=self.n_cand_local, drop_cand=batch.drop_cand)
         dq = torch.empty_like(qe[0])
         row_lse = None
         if self.loss == "kl":

@@ -6,8 +6,6 @@ accumulators) and sequences the C-ABI calls on the current stream.  No host sync
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _native as N
@@ -89,6 +87,7 @@ class FusedTrainStep:
         self.input_dropout, self.relation_input_dropout = input_dropout, relation_input_dropout
         self.seed = seed
         self.engine = engine or H.HotPath(E.device)
+        self._call = H.PrefixCall()       # persistent argument structs of the per-step call (_fast_forward_backward)
         # dense .grad (model_config.sparse False); the sparse step keeps per-shape occurrence-row buffers instead (_row_buffers)
         self.dE, self.dR = (None, None) if self.sparse else (torch.zeros_like(E), torch.zeros_like(R))
         self._rows = {}
@@ -181,66 +180,26 @@ class FusedTrainStep:
                                         idR=torch.empty(B, dtype=torch.int32, device=dev))
         return rb
 
-    def _set_dropout(self, batch: H.PrefixBatch, training=True):
-        pe = self.input_dropout if training else 0.0
-        pr = self.relation_input_dropout if training else 0.0
-        s, t, sd = self.seed, self.steps, self.step_dev
-        batch.drop_cand = H.DropoutSpec(pe, s, H.STREAM_CAND, t, step_dev=sd)
-        batch.drop_po_ent = H.DropoutSpec(pe, s, H.STREAM_PO_ENT, t, step_dev=sd)
-        batch.drop_sp_ent = H.DropoutSpec(pe, s, H.STREAM_SP_ENT, t, step_dev=sd)
-        batch.drop_po_rel = H.DropoutSpec(pr, s, H.STREAM_PO_REL, t, step_dev=sd)
-        batch.drop_sp_rel = H.DropoutSpec(pr, s, H.STREAM_SP_REL, t, step_dev=sd)
-
     def _covers_all_rows(self, batch: H.PrefixBatch):
         """1-vs-all: the candidate range is every row from cand_first on, so the step overwrites all of dE it uses"""
         return batch.cand_ids is None and batch.cand_first + batch.n_cand == self.E.shape[0]
 
-    # -- the per-step call with persistent descriptors ----------------------------------------------------------------
-    # A 0.14 ms step leaves the host ~100 us for everything; building five dropout and four argument structs per step
-    # in Python (and doing it next to a producer thread that shares the interpreter lock) is a measurable part of that.
-    def _descriptors(self):
-        if getattr(self, "_desc", None) is None:
-            t = self.engine._tables(self.E, self.R, self.scorer)
-            pb, c, pos = N.PrefixBatch(), N.Candidates(), N.Positives()
-            for d_, p_, stream in ((pb.drop_po_ent, self.input_dropout, H.STREAM_PO_ENT), (pb.drop_sp_ent, self.input_dropout, H.STREAM_SP_ENT),
-                                   (pb.drop_po_rel, self.relation_input_dropout, H.STREAM_PO_REL),
-                                   (pb.drop_sp_rel, self.relation_input_dropout, H.STREAM_SP_REL), (c.drop, self.input_dropout, H.STREAM_CAND)):
-                d_.p, d_.seed, d_.stream = float(p_), int(self.seed) & 0xFFFFFFFFFFFFFFFF, stream
-            self._desc = (t, pb, c, pos, (pb.drop_po_ent, pb.drop_sp_ent, pb.drop_po_rel, pb.drop_sp_rel, c.drop))
-        return self._desc
+    def _set_dropout(self, batch: H.PrefixBatch):
+        batch.set_dropout(H.dropout_specs(self.input_dropout, self.relation_input_dropout, self.seed, self.steps, self.step_dev))
 
-    def _fast_forward_backward(self, batch: H.PrefixBatch, normalizer):
-        """same call as HotPath.forward_backward for int32 device tensors (what the batch producer emits)"""
+    def _fast_forward_backward(self, batch: H.PrefixBatch, normalizer, dE, dR):
+        """same call as HotPath.forward_backward for int32 device tensors (what the batch producer emits), issued from the
+        step's persistent argument structs (H.PrefixCall)"""
         if H.VALIDATE:
             H.validate_ids(batch, self.E.shape[0], self.R.shape[0])
-        t, pb, c, pos, drops = self._descriptors()
-        sd = self.step_dev.data_ptr() if self.step_dev is not None else None
-        for d_ in drops:
-            d_.step, d_.step_dev = self.steps & 0xFFFFFFFF, sd
-        n_po, n_sp = batch.n_po, batch.n_sp
-        pb.po_rel, pb.po_obj = (batch.po_rel.data_ptr(), batch.po_obj.data_ptr()) if n_po else (None, None)
-        pb.sp_subj, pb.sp_rel = (batch.sp_subj.data_ptr(), batch.sp_rel.data_ptr()) if n_sp else (None, None)
-        pb.n_po, pb.n_sp = n_po, n_sp
-        n = batch.n_candidates
-        c.ids, c.first_id, c.n = (batch.cand_ids.data_ptr() if batch.cand_ids is not None else None), int(batch.cand_first), n
-        pos.row, pos.col, pos.nnz = batch.pos_row.data_ptr(), batch.pos_col.data_ptr(), batch.nnz
-        eng = self.engine
-        ws = eng.workspace(n_po + n_sp, n, t.d)
-        if self.sparse:
-            rb = self._cur_rows
-            ws = eng.workspace(n_po + n_sp, n, t.d, "train_rows")
-            N.check(eng.lib.okge_train_forward_backward(
-                ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), ctypes.byref(pos), N.LOSSES[self.loss], float(self.label_smoothing),
-                float(normalizer if normalizer is not None else (n_po + n_sp) * n), N.OKGE_TRAIN_ROW_GRADS, self.loss_out.data_ptr(),
-                rb["gE"].data_ptr(), rb["gR"].data_ptr(), None, 0, ws.data_ptr(), eng._ws_bytes, eng._stream()),
-                "okge_train_forward_backward")
-            return self.loss_out
-        flags = (N.OKGE_TRAIN_GRADS_ZERO if self._grads_zero else 0) | (N.OKGE_TRAIN_UNIQUE_CANDIDATES if batch.cand_unique else 0)
-        N.check(eng.lib.okge_train_forward_backward(
-            ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), ctypes.byref(pos), N.LOSSES[self.loss], float(self.label_smoothing),
-            float(normalizer if normalizer is not None else (n_po + n_sp) * n), flags, self.loss_out.data_ptr(), self.dE.data_ptr(),
-            self.dR.data_ptr(), None, 0, ws.data_ptr(), eng._ws_bytes, eng._stream()), "okge_train_forward_backward")
-        return self.loss_out
+        call = self._call
+        call.fill_tables(self.E, self.R, self.scorer, self.engine.device)
+        call.fill_ids(batch.po_rel, batch.po_obj, batch.sp_subj, batch.sp_rel, batch.cand_ids, batch.cand_first, batch.n_cand,
+                      batch.pos_row, batch.pos_col)
+        call.fill_dropout(self.input_dropout, self.relation_input_dropout, self.seed, self.steps, self.step_dev)
+        flags = H.train_flags(row_grads=True) if self.sparse else \
+            H.train_flags(grads_zero=self._grads_zero, unique_candidates=batch.cand_unique)
+        return call.train(self.engine, self.loss, self.label_smoothing, normalizer, flags, self.loss_out, dE, dR)
 
     def _plain(self, batch: H.PrefixBatch):
         """int32 contiguous tensors ON THE ENGINE'S DEVICE everywhere and no replayed masks: nothing for the generic path
@@ -251,24 +210,20 @@ class FusedTrainStep:
                 return False
         return batch.pos_row is not None and batch.cand_table is None
 
-    def _regularise(self, batch: H.PrefixBatch, normalizer, dE, dR, row_grads=False):
-        """the l2_reg term of this batch, added to the gradients the step's call just left (same masks: same seed, streams, step)"""
-        self._set_dropout(batch)
+    def _regularise(self, batch: H.PrefixBatch, normalizer, fast, dE, dR):
+        """the l2_reg term of this batch, added to the gradients the step's call just left (same masks: same seed, streams, step;
+        `fast`: the structs that call was issued from still hold them)"""
+        coef = H.n3_coef(self.l2_reg, self.l2_reg_dropout)
         passes = (int(batch.n_po > 0) + int(batch.n_sp > 0)) if self.l2_reg_per_direction else 1
-        self.engine.n3_forward_backward(self.E, self.R, self.scorer, batch, dE, dR, H.n3_coef(self.l2_reg, self.l2_reg_dropout),
-                                        cand_passes=passes, normalizer=normalizer, reg_out=self.reg_out, row_grads=row_grads)
+        if fast:
+            flags = H.train_flags(unique_candidates=batch.cand_unique, row_grads=self.sparse)
+            self._call.n3(self.engine, coef, passes, normalizer, flags, self.reg_out, dE, dR)
+        else:
+            self.engine.n3_forward_backward(self.E, self.R, self.scorer, batch, dE, dR, coef, cand_passes=passes, normalizer=normalizer,
+                                            reg_out=self.reg_out, row_grads=self.sparse)
 
     def forward_backward(self, batch: H.PrefixBatch, normalizer=None):
         """trainer.py:206-234.  Returns the summed loss (device double[1], valid after stream sync)."""
-        loss = self._forward_backward(batch, normalizer)
-        if self.l2_reg > 0:
-            if self.sparse:
-                self._regularise(batch, normalizer, self._cur_rows["gE"], self._cur_rows["gR"], row_grads=True)
-            else:
-                self._regularise(batch, normalizer, self.dE, self.dR)
-        return loss
-
-    def _forward_backward(self, batch: H.PrefixBatch, normalizer=None):
         if self.sparse:
             rb = self._cur_rows = self._row_buffers(batch)
             H.occurrence_ids(self.E.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
@@ -279,22 +234,24 @@ class FusedTrainStep:
                 lr, wd, eps = self._hparams()
                 self.engine.rows_catch_up([(self.E, self.sumE, rb["idE"], self.rowsE), (self.R, self.sumR, rb["idR"], self.rowsR)],
                                           self._counters, lr, wd, eps)
-            if isinstance(self.engine, H.HotPath) and self._plain(batch):
-                return self._fast_forward_backward(batch, normalizer)
+            dE, dR = rb["gE"], rb["gR"]
+        else:
+            if self._dE_stale and not (self._grads_zero and self._covers_all_rows(batch)):
+                self.dE.zero_()           # a sampled candidate list leaves rows untouched: they must read as zero
+                self._dE_stale = False
+            self._last_full = self._covers_all_rows(batch)
+            dE, dR = self.dE, self.dR
+        fast = isinstance(self.engine, H.HotPath) and self._plain(batch)
+        if fast:
+            loss = self._fast_forward_backward(batch, normalizer, dE, dR)
+        else:
             self._set_dropout(batch)
-            return self.engine.forward_backward(self.E, self.R, self.scorer, batch, rb["gE"], rb["gR"], loss=self.loss,
-                                                label_smoothing=self.label_smoothing, normalizer=normalizer,
-                                                loss_out=self.loss_out, row_grads=True)
-        if self._dE_stale and not (self._grads_zero and self._covers_all_rows(batch)):
-            self.dE.zero_()               # a sampled candidate list leaves rows untouched: they must read as zero
-            self._dE_stale = False
-        self._last_full = self._covers_all_rows(batch)
-        if isinstance(self.engine, H.HotPath) and self._plain(batch):
-            return self._fast_forward_backward(batch, normalizer)
-        self._set_dropout(batch)
-        return self.engine.forward_backward(self.E, self.R, self.scorer, batch, self.dE, self.dR, loss=self.loss,
-                                            label_smoothing=self.label_smoothing, normalizer=normalizer,
-                                            loss_out=self.loss_out, grads_zero=self._grads_zero)
+            how = dict(row_grads=True) if self.sparse else dict(grads_zero=self._grads_zero)
+            loss = self.engine.forward_backward(self.E, self.R, self.scorer, batch, dE, dR, loss=self.loss,
+                                                label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out, **how)
+        if self.l2_reg > 0:
+            self._regularise(batch, normalizer, fast, dE, dR)
+        return loss
 
     def optimizer_step(self, lazy_zero=False):
         """trainer.py:240-244: optimizer.step() then zero_grad() -- one sweep per table.  lazy_zero (used by step()

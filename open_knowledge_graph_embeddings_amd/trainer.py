@@ -13,10 +13,8 @@ import torch
 import torch.nn as nn
 from torch.nn import BCEWithLogitsLoss, KLDivLoss
 
-import ctypes
 import os
 
-from . import _native as N
 from . import hotpath as H
 from .metrics import MetricResult
 from .virtual_tables import VirtualTables
@@ -240,9 +238,7 @@ class AddLossModule(nn.Module):
             return self._token_result(m, batch, kind, smoothing, want_grad, all_outputs, hook_loss)
         if m.training:
             m.dropout_step += 1
-        batch.drop_cand = m.dropout_spec(H.STREAM_CAND)
-        batch.drop_po_ent, batch.drop_sp_ent = m.dropout_spec(H.STREAM_PO_ENT), m.dropout_spec(H.STREAM_SP_ENT)
-        batch.drop_po_rel, batch.drop_sp_rel = m.dropout_spec(H.STREAM_PO_REL, True), m.dropout_spec(H.STREAM_SP_REL, True)
+        batch.set_dropout([m.dropout_spec(stream, stream in (H.STREAM_PO_REL, H.STREAM_SP_REL)) for stream in H.STREAMS])
         n3 = self._n3_term(m, batch.n_po, batch.n_sp, batch_shared_entities)
         if want_grad:
             E, R = m.E, m.R
@@ -284,10 +280,11 @@ class AddLossModule(nn.Module):
 
     def _fast_training_call(self, m, eng, dev, po, sp, labels, use_batch_shared_entities, batch_shared_entities, kind, epoch):
         """The call the reference Trainer makes thousands of times per epoch -- lookup model in training mode, coordinate labels,
-        int32 id tensors on the device -- with PERSISTENT argument structs: the general path below builds a PrefixBatch, ten
-        DropoutSpec objects and four ctypes structs per call, ~35 us of Python on a step whose kernels take 130 us (the path is
-        host-bound).  Same library call, same flags, same buffers: test_dropin_path.py compares the two
-        bit for bit.  Returns None when an input is not in that form (the general path then converts it)."""
+        int32 id tensors on the device -- with PERSISTENT argument structs (`_fd`, a hotpath.PrefixCall refilled in place): the
+        general path builds a PrefixBatch, ten DropoutSpec objects and four ctypes structs per call, ~35 us of Python on a step
+        whose kernels take 130 us (the path is host-bound).  Same library call, same flags, same
+        buffers: test_dropin_path.py compares the two bit for bit.  Returns None when an input is not in that form (the general
+        path then converts it)."""
         prow, pcol = labels
         ids = []
         for pair in (po, sp):
@@ -307,34 +304,21 @@ class AddLossModule(nn.Module):
             n = cand.numel()
             if n == n_ent - first and not use_batch_shared_entities:
                 cand = None                                         # arange(vocab)[offset:] (dataset.py:872)
-        fd = getattr(self, "_fd", None)
-        if fd is None:
-            t, pb, c, pos = N.Tables(), N.PrefixBatch(), N.Candidates(), N.Positives()
-            pb.drop_po_ent.stream, pb.drop_sp_ent.stream, c.drop.stream = H.STREAM_PO_ENT, H.STREAM_SP_ENT, H.STREAM_CAND
-            pb.drop_po_rel.stream, pb.drop_sp_rel.stream = H.STREAM_PO_REL, H.STREAM_SP_REL
-            fd = self._fd = (t, pb, c, pos, (pb.drop_po_ent, pb.drop_sp_ent, c.drop), (pb.drop_po_rel, pb.drop_sp_rel))
-        t, pb, c, pos, ent_drops, rel_drops = fd
         E, R = m.E, m.R
         if E.dtype != torch.float32 or not E.is_contiguous() or not R.is_contiguous() or R.dtype != torch.float32:
             return None
-        t.E, t.R, t.n_ent, t.n_rel, t.d, t.scorer = E.data_ptr(), R.data_ptr(), E.shape[0], R.shape[0], E.shape[1], N.SCORERS[m.scorer_name]
+        if getattr(self, "_fd", None) is None:
+            self._fd = H.PrefixCall()
+        fd = self._fd
+        fd.fill_tables(E, R, m.scorer_name, eng.device)
         hook_loss = m.after_batch_loss_hook(epoch) if hasattr(m, "after_batch_loss_hook") else None
         m.dropout_step += 1
-        seed, step = int(m.dropout_seed) & 0xFFFFFFFFFFFFFFFF, int(m.dropout_step) & 0xFFFFFFFF
-        p_ent = float(m.keep_prob_dropout(m.input_dropout, m.dropout))
-        p_rel = float(m.keep_prob_dropout(m.relation_input_dropout, m.relation_dropout))
-        for d_ in ent_drops:
-            d_.p, d_.seed, d_.step = p_ent, seed, step
-        for d_ in rel_drops:
-            d_.p, d_.seed, d_.step = p_rel, seed, step
-        n_po = po[0].numel() if po is not None else 0
-        n_sp = sp[0].numel() if sp is not None else 0
-        pb.po_rel, pb.po_obj = (po[0].data_ptr(), po[1].data_ptr()) if n_po else (None, None)
-        pb.sp_subj, pb.sp_rel = (sp[0].data_ptr(), sp[1].data_ptr()) if n_sp else (None, None)
-        pb.n_po, pb.n_sp = n_po, n_sp
-        c.ids, c.first_id, c.n = (None if cand is None else cand.data_ptr()), int(first), int(n)
-        pos.row, pos.col, pos.nnz = prow.data_ptr(), pcol.data_ptr(), prow.numel()
-        B = n_po + n_sp
+        fd.fill_dropout(m.keep_prob_dropout(m.input_dropout, m.dropout), m.keep_prob_dropout(m.relation_input_dropout, m.relation_dropout),
+                        m.dropout_seed, m.dropout_step)
+        po_rel, po_obj = po if po is not None else (None, None)
+        sp_subj, sp_rel = sp if sp is not None else (None, None)
+        fd.fill_ids(po_rel, po_obj, sp_subj, sp_rel, cand, first, n, prow, pcol)
+        n_po, n_sp, B = fd.n_po, fd.n_sp, fd.B
         all_outputs = None
         if self.training_outputs:
             all_outputs = torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :n]
@@ -344,27 +328,17 @@ class AddLossModule(nn.Module):
             g_e, g_r = E.new_empty((n + B, E.shape[1])), R.new_empty((B, R.shape[1]))
             row_ids = H.occurrence_ids(dev, cand, first, n, po[1] if n_po else None, sp[0] if n_sp else None,
                                       po[0] if n_po else None, sp[1] if n_sp else None)
-            flags = N.OKGE_TRAIN_ROW_GRADS
         else:
             g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
-            flags = N.OKGE_TRAIN_GRADS_ZERO | (N.OKGE_TRAIN_CLEAR_GRADS if clear else 0)
+        flags = H.train_flags(grads_zero=not self.sparse_grads, clear_grads=clear, row_grads=self.sparse_grads)
         applied = np.float32(1.0) / np.float32(float(B) * float(n))           # (see forward below)
-        loss = torch.empty(1, dtype=torch.float64, device=dev)
-        ws = eng.workspace(B, n, t.d, "train_rows" if self.sparse_grads else "train")
         smoothing = self.bce_label_smoothing if kind == "bce" else 0.0
-        N.check(eng.lib.okge_train_forward_backward(
-            ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), ctypes.byref(pos), N.LOSSES[kind], float(smoothing), 1.0 / float(applied),
-            flags, loss.data_ptr(), g_e.data_ptr(), g_r.data_ptr(),
-            None if all_outputs is None else all_outputs.data_ptr(), 0 if all_outputs is None else all_outputs.stride(0),
-            ws.data_ptr(), eng._ws_bytes, eng._stream()), "okge_train_forward_backward")
+        loss = fd.train(eng, kind, smoothing, 1.0 / float(applied), flags, torch.empty(1, dtype=torch.float64, device=dev), g_e, g_r,
+                        all_outputs)
         n3 = self._n3_term(m, n_po, n_sp, batch_shared_entities)
         if n3 is not None:                                                     # the l2_reg hook, behind the step on the same structs
-            reg = torch.empty(1, dtype=torch.float64, device=dev)
-            ws = eng.n3_workspace(B, n, t.d)
-            N.check(eng.lib.okge_n3_forward_backward(
-                ctypes.byref(t), ctypes.byref(pb), ctypes.byref(c), n3[0], n3[1], 1.0 / float(applied),
-                N.OKGE_TRAIN_ROW_GRADS if self.sparse_grads else 0, reg.data_ptr(), g_e.data_ptr(), g_r.data_ptr(), ws.data_ptr(),
-                eng._ws_bytes, eng._stream()), "okge_n3_forward_backward")
+            reg = fd.n3(eng, n3[0], n3[1], 1.0 / float(applied), H.train_flags(row_grads=self.sparse_grads),
+                        torch.empty(1, dtype=torch.float64, device=dev), g_e, g_r)
         if CALLER_THREAD_BACKWARD and torch.autograd.is_multithreading_enabled():
             torch.autograd.set_multithreading_enabled(False)                   # (see forward below)
         if n3 is not None:

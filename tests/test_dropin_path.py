@@ -351,3 +351,58 @@ def test_fast_training_call_is_the_general_path(okge_lib, monkeypatch, case):
             np.testing.assert_allclose(x.cpu().numpy(), y.cpu().numpy(), rtol=0, atol=2e-6 * float(y.abs().max()))
         assert float((a[2] != b[2]).float().mean()) < 0.02
     assert not torch.equal(out[True][0][2], out[True][1][2])             # (the dropout counter moved on between the steps)
+
+
+# Four batch shapes in a row over n_ent = 50, n_rel = 12: (po = (rel, obj), sp = (subj, rel), candidate id list or None for the
+# 1-vs-all range, positives (row, col) sorted by col).  Order-free on purpose: the relation ids of a batch are distinct, so are its
+# prefix entities, a list names every candidate once and none of the batch's prefix entities -- every gradient element then has
+# at most two addends per launch, and two float addends commute, so two runs of the same route are bit-equal.
+_STEP_SHAPES = [
+    (([2, 3, 4], [5, 6, 7]), ([8, 9, 10, 11], [5, 6, 7, 8]), None, ([0, 3, 6, 2, 1, 5, 4], [1, 4, 9, 20, 33, 40, 47])),
+    (None, ([12, 13, 14], [2, 3, 4]), [4, 9, 17, 30, 41, 22, 3], ([0, 1, 1, 2], [0, 2, 4, 6])),      # a direction became empty
+    (([9, 10], [20, 21]), None, None, ([1], [7])),                                                    # back to the range
+    (([6], [22]), ([23, 24], [7, 8]), None, ([0, 2, 1], [3, 5, 30])),                                 # step_dev, other p
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["dense_adagrad", "sparse_l2_reg", "adam_l2_reg"])
+def test_fused_step_fast_route_is_the_general_route_over_changing_batches(okge_lib, variant):
+    """FusedTrainStep's persistent argument structs over four batch shapes in a row (no GraphedTrainStep): int32 device ids take
+    the fast route, the same ids as int64 the general one.  After every step loss, l2_reg term, tables and optimizer state are
+    bit-equal -- general against general first (the inputs are order-free), then fast against general (nothing of the previous
+    batch survives in the structs: a pointer, a count, a candidate id list, a step_dev, a dropout probability)."""
+    from open_knowledge_graph_embeddings_amd import hotpath as H
+    from open_knowledge_graph_embeddings_amd.train_step import FusedTrainStep
+    n_ent, n_rel, d = 50, 12, 16
+    g = torch.Generator().manual_seed(5)
+    E0, R0 = (torch.randn((n_ent, d), generator=g) * 0.3).cuda(), (torch.randn((n_rel, d), generator=g) * 0.3).cuda()
+    kw = dict(dense_adagrad={}, sparse_l2_reg=dict(sparse=True, weight_decay=0.0, l2_reg=0.05),
+              adam_l2_reg=dict(optimizer="adam", l2_reg=0.05))[variant]
+
+    def run(fast):
+        dt = torch.int32 if fast else torch.int64
+        ids = lambda x: None if x is None else torch.tensor(x, dtype=dt, device="cuda")      # noqa: E731
+        st = FusedTrainStep(E0.clone(), R0.clone(), "complex", input_dropout=0.3, relation_input_dropout=0.2, seed=11, **kw)
+        seen = []
+        for i, (po, sp, cand, pos) in enumerate(_STEP_SHAPES):
+            po, sp = po or (None, None), sp or (None, None)
+            b = H.PrefixBatch(po_rel=ids(po[0]), po_obj=ids(po[1]), sp_subj=ids(sp[0]), sp_rel=ids(sp[1]), pos_row=ids(pos[0]),
+                              pos_col=ids(pos[1]), cand_ids=ids(cand), cand_first=2, n_cand=0 if cand else n_ent - 2,
+                              cand_unique=cand is not None)
+            if i == 3:       # the kernels read the step from the device counter once one is attached (it holds this step's number)
+                st.step_dev = torch.tensor([st.steps + 1], dtype=torch.int32, device="cuda")
+                st.input_dropout, st.relation_input_dropout = 0.1, 0.4
+            assert st._plain(b) == fast
+            st.step(b)
+            seen.append([t.clone() for t in [st.loss_out, st.reg_out] + st.state_tensors()])
+        torch.cuda.synchronize()
+        return seen
+
+    fast, general, again = run(True), run(False), run(False)
+    for i, (f, a, b) in enumerate(zip(fast, general, again)):
+        assert len(f) == len(a) == len(b)
+        for k, (x, y, z) in enumerate(zip(f, a, b)):
+            assert torch.equal(y, z), f"step {i}, tensor {k}: two runs of the general route differ -- the ids are not order-free"
+            assert torch.equal(x, y), f"step {i}, tensor {k}: the fast route differs from the general route"
+    assert all(torch.isfinite(t).all() for t in fast[-1]) and not torch.equal(fast[0][2], fast[-1][2])      # (E moved)
