@@ -249,6 +249,15 @@ class BigramPoolingRelationEmbedder(TokenEncoderEmbedder):
             grads += [sl.dW, sl.d_conv] + ([sl.d_bn[:sl.d], sl.d_bn[sl.d:]] if sl.bn is not None else [])
         return params, grads
 
+    def _state_segments(self, sl, relation):
+        """optimizer_params_and_state: the token table, then the slot's flat buffer [conv | bn weight | bn bias]"""
+        emb, tok, conv, bn = self._parts(relation)
+        d, flat = sl.d, (sl.flat, sl.sum_flat)
+        out = [(emb.weight, (sl.W, sl.sumW), 0), (conv.weight, flat, 0)]
+        if bn is not None:
+            out += [(bn.weight, flat, 2 * d * d), (bn.bias, flat, 2 * d * d + d)]
+        return out
+
     def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
                    grad_clip=0.0):
         """The training driver for this model: shares the module's parameters (updated in place).  The conv weight and the

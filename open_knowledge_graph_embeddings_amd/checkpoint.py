@@ -15,6 +15,12 @@ writes and reads torch.optim.Adam's state instead ({"step", "exp_avg", "exp_avg_
 is refused by an Adam step and the other way round unless `reset_optimizer` is set.  Files written here
 contain tensors and plain containers only, so they load with `torch.load(..., weights_only=True)`; the reference's own
 `results` entry (a pickled ResultsLog object) is never written and never read.
+
+The models whose rows are encoded from tokens and the Tucker3 model train more than two tensors: model_checkpoint /
+save_model_checkpoint / load_model_checkpoint (below) move the same layout -- the module's whole state_dict, one optimizer state
+entry per parameter in model.parameters() order -- between a module and the driver its train_step() returned.  Which part of
+which buffer of the step belongs to which parameter is the embedders' knowledge (optimizer_params_and_state); nothing else of
+a step's optimizer state is read here.
 """
 from __future__ import annotations
 
@@ -168,3 +174,146 @@ def _load_adam_state(step, st, ckpt):
     step.steps = int(ckpt.get("training_steps", int(float(state[0]["step"]))))
     step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
     step.betas = (float(group["betas"][0]), float(group["betas"][1]))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The token-encoded and Tucker3 models: a module and the driver its train_step() returned
+# ------------------------------------------------------------------------------------------------------------------
+CHECKPOINT_FORMAT = 1
+_OPTIMIZER_MISMATCH = ("the checkpoint holds {have} optimizer state and this step trains with {want}: its accumulators do "
+                       "not carry over -- load with reset_optimizer=True to take the tables alone")
+
+
+def _model_and_step(model, step):
+    from .step_optim import StepOptimizer
+    if not isinstance(step, StepOptimizer) or not hasattr(model, "optimizer_params_and_state"):
+        raise TypeError(f"model_checkpoint / load_model_checkpoint take a token-encoded or Tucker3 model and the driver its "
+                        f"train_step() returned, not {type(step).__name__}: the two-table lookup steps go through "
+                        f"to_reference_checkpoint / load_reference_checkpoint")
+    return model.optimizer_params_and_state(step)
+
+
+def _state_names(step):
+    return ("exp_avg", "exp_avg_sq") if _is_adam(step) else ("sum",)
+
+
+def model_checkpoint(model, step, epoch=0, training_steps=None):
+    """The dict `Trainer.save` would write for `model` trained by `step` (= model.train_step(...)), tensors on the CPU:
+    state_dict = the module's own (integer buffers as int64, the reference's token-id dtype), taken once the step has settled its
+    deferred updates and brought the module's batch-norm modules up to date; optimizer_state = what torch.optim.Adagrad /
+    torch.optim.Adam over model.parameters() would return from state_dict(), every entry a copy in its parameter's shape; and one
+    extra top-level key "okge" (Trainer.save appends its save_info the same way): plain numbers a resumed run needs to draw the
+    same dropout masks and that torch's optimizer state has no place for."""
+    entries, word = _model_and_step(model, step)
+    step.sync_module()
+    cpu = lambda t: t.detach().cpu().clone()                   # noqa: E731
+    state_dict = {k: cpu(v) if v.is_floating_point() else cpu(v).to(torch.int64) for k, v in model.state_dict().items()}
+    adam = _is_adam(step)
+    t = float(int(word[0].item())) if adam else float(step.steps)
+    state = {}
+    for i, (p, views, moved) in enumerate(entries):
+        if adam and not moved:                                  # torch.optim.Adam creates a parameter's state at its first step
+            continue
+        state[i] = {"step": torch.tensor(t if moved else 0.0)}
+        state[i].update({name: cpu(v) for name, v in zip(_state_names(step), views)})
+    group = {"lr": step.lr, "betas": tuple(step.betas) if adam else (0.9, 0.999), "eps": step.eps, "weight_decay": step.weight_decay,
+             "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+             "decoupled_weight_decay": False}
+    if not adam:
+        group.update({"lr_decay": 0, "initial_accumulator_value": 0})
+    group["params"] = list(range(len(entries)))
+    regime = [{"optimizer": "Adam" if adam else "Adagrad", "epoch": 0, "lr": step.lr, "weight_decay": step.weight_decay}]
+    return {"epoch": int(epoch), "training_steps": int(step.steps if training_steps is None else training_steps),
+            "state_dict": state_dict,
+            "optimizer_state_dict": [{"optimizer_state": {"state": state, "param_groups": [group]}, "regime": regime}],
+            "validation_results": None,
+            "okge": {"format": CHECKPOINT_FORMAT, "steps": int(step.steps), "dropout_step": int(model.dropout_step),
+                     "dropout_seed": int(model.dropout_seed), "grad_clip": float(step.grad_clip)}}
+
+
+def save_model_checkpoint(path, model, step, epoch=0, training_steps=None):
+    """model_checkpoint(...) written with torch.save; -> the dict"""
+    ckpt = model_checkpoint(model, step, epoch, training_steps)
+    torch.save(ckpt, path)
+    return ckpt
+
+
+def _check_model_checkpoint(model, step, entries, ckpt, reset_optimizer):
+    """every refusal of load_model_checkpoint, before anything is written"""
+    sd, own = ckpt["state_dict"], model.state_dict()
+    for k, v in own.items():
+        if k not in sd:
+            raise ValueError(f"the checkpoint's state_dict has no {k!r}")
+        if tuple(sd[k].shape) != tuple(v.shape):
+            raise ValueError(f"checkpoint tensor {k!r} has shape {tuple(sd[k].shape)}, the model's has {tuple(v.shape)}")
+    for k in sd:
+        if k not in own:
+            raise ValueError(f"the checkpoint's state_dict holds {k!r}, which this model does not have")
+    extra = ckpt.get("okge")
+    if extra is not None and int(extra.get("format", 0)) != CHECKPOINT_FORMAT:
+        raise ValueError(f"checkpoint 'okge' format {extra.get('format')!r}: this package reads format {CHECKPOINT_FORMAT}")
+    if reset_optimizer:
+        return
+    want, have = ("adam" if _is_adam(step) else "adagrad"), _checkpoint_optimizer(ckpt)
+    if want != have:
+        raise ValueError(_OPTIMIZER_MISMATCH.format(have=have, want=want))
+    st = ckpt["optimizer_state_dict"][0]["optimizer_state"]
+    group, state = st["param_groups"][0], st["state"]
+    if len(group["params"]) != len(entries):
+        raise ValueError(f"the checkpoint's optimizer holds {len(group['params'])} parameters, this model has {len(entries)}")
+    for i, (p, views, moved) in enumerate(entries):
+        for name in _state_names(step) if i in state else ():
+            if name not in state[i] or tuple(state[i][name].shape) != tuple(p.shape):
+                got = tuple(state[i][name].shape) if name in state[i] else None
+                raise ValueError(f"optimizer state {name!r} of parameter {i} has shape {got}, the parameter's is {tuple(p.shape)}")
+    if float(group.get("lr_decay", 0)) != 0 or float(group.get("initial_accumulator_value", 0)) != 0:
+        raise NotImplementedError("Adagrad lr_decay / initial_accumulator_value are not used by the reference configs")
+    if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
+        raise NotImplementedError("amsgrad, maximize and decoupled weight decay (AdamW) are not implemented")
+
+
+def load_model_checkpoint(model, step, ckpt_or_path, reset_optimizer=False):
+    """Load what model_checkpoint or the reference's `Trainer.save` wrote into `model` and its driver `step`, so that the next
+    step() continues the run.  reset_optimizer (the reference's `Trainer.load(reset_optimizer=...)` switch): the state_dict
+    alone is taken; accumulators / moments, the Adam step count and the step counter start from zero, the step keeps its own
+    hyper-parameters.  Without the "okge" key (a file the reference wrote) the step counter is the file's training_steps."""
+    entries, word = _model_and_step(model, step)
+    ckpt = ckpt_or_path
+    if not isinstance(ckpt, dict):
+        ckpt = torch.load(ckpt_or_path, map_location="cpu", weights_only=True)
+    _check_model_checkpoint(model, step, entries, ckpt, reset_optimizer)
+    step.flush()                                                 # no row may owe decay-only steps to the loaded tables
+    model.load_state_dict(ckpt["state_dict"])
+    if getattr(model, "entity_embedding_from_tokens", None) is not None:      # tables precomputed from the tokens: stale now
+        model.entity_embedding_from_tokens = model.relations_embedding_from_tokens = None
+    step.adopt_module()
+    step.reset_gradients()
+    st = None if reset_optimizer else ckpt["optimizer_state_dict"][0]["optimizer_state"]
+    state = {} if st is None else st["state"]
+    for i, (p, views, moved) in enumerate(entries):
+        for name, v in zip(_state_names(step), views):
+            if i in state:
+                v.copy_(state[i][name])
+            else:                                                # (reset, or a parameter torch's Adam has not stepped yet)
+                v.zero_()
+    taken = [int(float(state[i]["step"])) for i, e in enumerate(entries) if e[2] and i in state]
+    if _is_adam(step):
+        step.set_adam_t(taken[0] if taken else 0)
+    if st is None:
+        step.steps = 0
+        return ckpt
+    group = st["param_groups"][0]
+    step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
+    if _is_adam(step):
+        step.betas = (float(group["betas"][0]), float(group["betas"][1]))
+    extra = ckpt.get("okge")
+    if extra is None:
+        step.steps = int(ckpt.get("training_steps", taken[0] if taken else 0))
+        return ckpt
+    step.steps = int(extra["steps"])
+    model.dropout_step, model.dropout_seed = int(extra["dropout_step"]), int(extra["dropout_seed"])
+    step.seed = model.dropout_seed
+    step.grad_clip = float(extra["grad_clip"])
+    if step.grad_clip > 0 and step.grad_norm is None:
+        step.grad_norm = torch.zeros(1, dtype=torch.float64, device=step.device)
+    return ckpt

@@ -40,6 +40,7 @@ class LSTMSlot:
     gradients and Adagrad accumulators."""
 
     what, has_raw, pass_class = "LSTM", True, LstmPass
+    bn_calls = 0      # training-mode batch-norm encode calls of a train step since VirtualTableStep.sync_module (host count)
 
     def __init__(self, W, token_ids, lstm, bn=None, running=None, flat=None, view=False):
         """lstm: [weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0]; bn: [weight, bias] or None; running: (mean, var);
@@ -120,6 +121,8 @@ class LSTMTrainStep(EncoderTrainStep):
     def _encode_slot(self, ps, sl, calls, V, X):
         if not self._unused(sl) or sl.bn is not None:                     # (unused: only for the running statistics)
             ps.encode(sl, calls, True, X, V)
+            if sl.bn is not None:
+                sl.bn_calls += len(calls)
 
     def _backward_slot(self, ps, sl, calls, X, dV):
         """batch-norm and the LSTM backward through time -> the slot's dW, d_flat (dlstm), d_bn ([d weight | d bias])"""
@@ -228,6 +231,18 @@ class LSTMRelationEmbedder(TokenEncoderEmbedder):
             params += self._lstm_tensors(lstm)
             grads += sl.dlstm
         return params, grads
+
+    def _state_segments(self, sl, relation):
+        """optimizer_params_and_state: the token table, the four LSTM tensors one after the other in the slot's flat buffer, the
+        batch-norm's [weight | bias]"""
+        emb, tok, lstm, bn = self._parts(relation)
+        out, offset = [(emb.weight, (sl.W, sl.sumW), 0)], 0
+        for q in self._lstm_tensors(lstm):
+            out.append((q, (sl.flat, sl.sum_flat), offset))
+            offset += q.numel()
+        if bn is not None:
+            out += [(bn.weight, (sl.bn, sl.sum_bn), 0), (bn.bias, (sl.bn, sl.sum_bn), sl.d)]
+        return out
 
     def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
                    grad_clip=0.0):

@@ -33,6 +33,11 @@ def refuse_for_replicas(inner, who):
         raise NotImplementedError(f"{who}: optimizer='adam' and grad_clip are built for the single-device steps")
 
 
+def state_views(states, offset, param):
+    """the part of each flat state tensor that belongs to `param`: `param.numel()` elements from `offset`, in its shape (views)"""
+    return tuple(s.reshape(-1)[offset:offset + param.numel()].view(param.shape) for s in states)
+
+
 class StepOptimizer:
     """mixin: needs self.engine, self.device, self.lr / weight_decay / eps and _param_groups()"""
 
@@ -70,6 +75,33 @@ class StepOptimizer:
         for _, _, st in self._adam.values():
             st.zero_()
             st[0] = int(t)
+
+    # -- what checkpoint.py needs (through the embedders' optimizer_params_and_state) -----------------------------------
+    def optimizer_state_of(self, p, state_sum):
+        """the optimizer's state tensors of one entry (p, g, state_sum, ...) of _param_groups(): (state_sum,) under Adagrad,
+        (exp_avg, exp_avg_sq) under Adam -- each of p's shape"""
+        if self.optimizer == "adam":
+            return self._adam[p.data_ptr()][:2]
+        return (state_sum,)
+
+    def adam_word(self):
+        """the device state word the Adam kernels count their steps in ([0] = t; every tensor's holds the same count), or None"""
+        return next(iter(self._adam.values()))[2] if self.optimizer == "adam" else None
+
+    def reset_gradients(self):
+        """gradient buffers and touched-row maps as the head of a step expects them: all zero"""
+        for t in self._param_groups(every=True):
+            t[1].zero_()
+            if len(t) > 3 and t[3] is not None:
+                t[3].zero_()
+
+    def sync_module(self):
+        """before an attached module's state_dict is read: deferred updates settled; a step that keeps copies of module state
+        (virtual_tables.VirtualTableStep) brings the module up to date"""
+        self.flush()
+
+    def adopt_module(self):
+        """after an attached module's state_dict was loaded: such copies follow the module (none here)"""
 
     def _clip(self, groups):
         """trainer.py:236-240: clip_grad_norm_ over exactly the gradients the update that follows reads, maps included"""

@@ -16,6 +16,7 @@ import torch
 from . import _native as N
 from . import hotpath as H
 from . import virtual_tables as VT
+from .step_optim import state_views
 from .token_pooled import BN_EPS, BN_MOMENTUM, UnigramPoolingRelationEmbedder, token_id_matrix
 
 MAX_SLOT = 512                                     # the fused tile kernels' largest slot size
@@ -263,6 +264,17 @@ class TokenEncoderEmbedder(UnigramPoolingRelationEmbedder):
             with torch.no_grad():
                 self.entity_embedding_from_tokens = table(self.train_data.entities_size, False)
                 self.relations_embedding_from_tokens = table(self.train_data.relations_size, True)
+
+    def optimizer_params_and_state(self, st):
+        """For checkpoint.py, as the token-pooled embedder's: the subclass says in _state_segments(slot, relation) ->
+        [(parameter, (step tensor, its Adagrad accumulator), offset into them)] which part of which flat buffer is whose; a slot
+        the scorer leaves unused (bias_entity) is listed as not moved."""
+        found = {}
+        for sl, relation in ((st.entity, False), (st.relation, True)):
+            moved = not st._unused(sl)
+            for p, (buf, acc), offset in self._state_segments(sl, relation):
+                found[p] = (state_views(st.optimizer_state_of(buf, acc), offset, p), moved)
+        return [(p,) + found[p] for p in self.parameters()], st.adam_word()
 
     def _cached_autograd_step(self, loss, label_smoothing, make_slots):
         """the cached train step behind AddLossModule (trainer.py:142, 206-234): rebuilt when the loss, the smoothing or the

@@ -19,6 +19,7 @@ from . import _native as N
 from . import hotpath as H
 from . import virtual_tables as VT
 from .model import ComplexRelationScorer, DistmultRelationScorer, Models, RelationEmbedder
+from .step_optim import state_views
 
 POOLS = {"sum": 0, "mean": 1, "max": 2}
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1                     # torch.nn.BatchNorm1d(momentum=0.1, eps=1e-5), model.py:611-612
@@ -36,6 +37,8 @@ def token_id_matrix(id_to_tokens_map, max_len, device="cpu"):
 
 class TokenSlot:
     """One embedder slot (entity or relation): token table, token-id matrix, optional batch-norm, gradients."""
+
+    bn_calls = 0      # training-mode batch-norm encode calls of a train step since VirtualTableStep.sync_module (host count)
 
     def __init__(self, W, token_ids, pool="sum", batchnorm=False, bn_weight=None, bn_bias=None):
         self.W, self.token_ids, self.pool = W, token_ids.to(torch.int32).contiguous(), pool
@@ -343,6 +346,9 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
             lr, wd, eps = self._hparams()
             pe.catch_up_calls(enc_calls, self.engine.lazy_tensors(self._lazy_tables()), self._counters, lr, wd, eps)
         pe.encode_calls(enc_calls, True)
+        for c_ in calls:
+            if c_[3] > 0 and c_[0].bn is not None:
+                c_[0].bn_calls += 1
         return calls
 
     def _backward(self, batch, bufs, calls):
@@ -594,6 +600,19 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
                 params += [bn.weight, bn.bias]
                 grads += [sl.d_bn[:sl.d], sl.d_bn[sl.d:]]
         return params, grads
+
+    def optimizer_params_and_state(self, st):
+        """For checkpoint.py, `st` = the driver train_step() returned: ([(parameter, views of the step's optimizer state that
+        belong to it -- (sum,) under Adagrad, (exp_avg, exp_avg_sq) under Adam, each of the parameter's shape --, whether the step
+        moves it), ...] in self.parameters() order, the Adam device state word or None)."""
+        found = {}
+        for sl, emb, bn in ((st.entity, self.entity_embedding, self.entity_batchnorm),
+                            (st.relation, self.relation_embedding, self.relation_batchnorm)):
+            found[emb.weight] = state_views(st.optimizer_state_of(sl.W, sl.sumW), 0, emb.weight)
+            if bn is not None:
+                states = st.optimizer_state_of(sl.bn, sl.sum_bn)                 # [weight | bias]
+                found[bn.weight], found[bn.bias] = state_views(states, 0, bn.weight), state_views(states, sl.d, bn.bias)
+        return [(p, found[p], True) for p in self.parameters()], st.adam_word()
 
     def loss_only(self, batch: H.PrefixBatch, loss, label_smoothing, scores=None):
         """eval-mode loss (+ scores) of AddLossModule: rows encoded with the running statistics, no dropout"""

@@ -548,6 +548,15 @@ class ProjectedLookupRelationEmbedder(LookupBaseRelationEmbedder):
     def autograd_params_and_grads(self, st):
         return [self.entity_embedding.weight, self.relation_embedding.weight, self.relation_projection[0].weight], [st.dE, st.dR, st.dW]
 
+    def optimizer_params_and_state(self, st):
+        """For checkpoint.py, `st` = the driver train_step() returned: ([(parameter, the step's optimizer state tensors of it --
+        (sum,) under Adagrad, (exp_avg, exp_avg_sq) under Adam --, True: the step moves it), ...] in self.parameters() order, the
+        Adam device state word or None)."""
+        found = {self.entity_embedding.weight: st.optimizer_state_of(st.E, st.sumE),
+                 self.relation_embedding.weight: st.optimizer_state_of(st.R, st.sumR),
+                 self.relation_projection[0].weight: st.optimizer_state_of(st.W, st.sumW)}
+        return [(p, tuple(found[p]), True) for p in self.parameters()], st.adam_word()
+
     def loss_only(self, batch, kind, smoothing, all_outputs):
         """summed validation loss without gradients or dropout (AddLossModule under torch.no_grad(), trainer.py:363-369)"""
         step = self.dropout_step

@@ -127,3 +127,25 @@ class VirtualTableStep(StepOptimizer):
             if sl.running_mean.data_ptr() != bn.running_mean.data_ptr():
                 bn.running_mean.copy_(sl.running_mean)
                 bn.running_var.copy_(sl.running_var)
+
+    def sync_module(self):
+        """before the attached module's state_dict is read (checkpoint.py): deferred updates settled, batch-norm parameters and
+        running statistics copied, and num_batches_tracked moved on by the training-mode encode calls the slots counted on the
+        host since the last call (`bn_calls`; torch's BatchNorm1d counts one per training-mode forward)"""
+        self.flush()
+        self._sync_module_batchnorms()
+        for sl, bn in self.module_batchnorms:
+            if sl.bn_calls:
+                bn.num_batches_tracked += sl.bn_calls
+                sl.bn_calls = 0
+
+    def adopt_module(self):
+        """after the attached module's state_dict was loaded: the slots' own copies of batch-norm parameters (and running
+        statistics that no longer share the module's storage) follow the module"""
+        for sl, bn in self.module_batchnorms:
+            sl.bn[:sl.d].copy_(bn.weight.data)
+            sl.bn[sl.d:].copy_(bn.bias.data)
+            if sl.running_mean.data_ptr() != bn.running_mean.data_ptr():
+                sl.running_mean.copy_(bn.running_mean)
+                sl.running_var.copy_(bn.running_var)
+            sl.bn_calls = 0
