@@ -614,6 +614,28 @@ size_t okge_adagrad_rows_workspace_bytes(int64_t n0, int64_t n1);      /* n of t
 int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float lr, float eps, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* ---- the deterministic dense gradient: occurrence rows coalesced into dense gradient tables -------------------------------------
+ * CONTRACT.  The deterministic dense gradient of table row `id` is the sequential fp32 sum of its occurrence rows in ASCENDING
+ * occurrence position, ((g_a + g_b) + g_c) ... -- positions as OKGE_TRAIN_ROW_GRADS lays the rows out: entities [candidates | po
+ * rows | sp rows], relations [po rows | sp rows] -- which is exactly the order okge_adagrad_rows coalesces in.  Accumulating over
+ * micro-batches, the row the table already holds comes first: acc = dE[id]; acc += g_a; acc += g_b; ...; dE[id] = acc.  A row no
+ * occurrence names is not written.
+ * okge_rows_to_dense writes these sums for up to two tensors in one call; per tensor p is the DENSE GRADIENT table (table_rows x
+ * row_len, contiguous), state_sum is not read (pass NULL), ids / g / ld_g / n as for okge_adagrad_rows.
+ *   OKGE_ROWS_STORE       the named rows of p are overwritten with their sums (a run's first row is copied, not added to zero:
+ *                         the sign of a zero survives); the caller guarantees that every other row is zero
+ *   OKGE_ROWS_ACCUMULATE  the named rows continue the chain from what they hold, as in the contract
+ * Everything else is okge_adagrad_rows': the same key sort and the same walk (one owner per distinct id, no float atomics), ids
+ * outside [0, table_rows) skipped and counted (okge_id_errors), n = 0 a no-op, n up to 2^20 per tensor (beyond:
+ * OKGE_ERR_UNSUPPORTED), 16-byte accesses when row_len and ld_g are multiples of 4 and p and g are 16-byte aligned and single
+ * floats otherwise, no host synchronisation, launches fixed by (n of each tensor).  One lane group sums one run, so a single id
+ * repeated thousands of times stays one serial chain: the order is the contract.  The two tensors must not overlap. */
+#define OKGE_ROWS_STORE      0
+#define OKGE_ROWS_ACCUMULATE 1
+size_t okge_rows_to_dense_workspace_bytes(int64_t n0, int64_t n1);     /* n of the first / second tensor (0: absent) */
+int okge_rows_to_dense(const okge_rows_tensor *tensors, int32_t n_tensors, int32_t mode, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 /* ---- row-sparse Adagrad WITH weight decay: the decay-only updates of the rows no batch names, deferred ------------------------
  * The reference trains with weight_decay = 1e-10 on DENSE Adagrad (utils/optim.py:139-160): every row of a table moves in every
  * step, by its own decay term when no gradient reached it.  That update depends on the row's (p, state_sum) alone, so it can be

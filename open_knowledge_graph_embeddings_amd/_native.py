@@ -27,6 +27,7 @@ OKGE_TRAIN_UNIQUE_CANDIDATES = 4
 OKGE_TRAIN_DISTINCT_PREFIX_ROWS = 8
 OKGE_TRAIN_CLEAR_GRADS = 16
 OKGE_TRAIN_ROW_GRADS = 32
+OKGE_ROWS_STORE, OKGE_ROWS_ACCUMULATE = 0, 1       # okge_rows_to_dense's mode
 SCORERS = {"complex": OKGE_COMPLEX, "distmult": OKGE_DISTMULT, "bias_relation": OKGE_BIAS_RELATION,
            "bias_entity": OKGE_BIAS_ENTITY}
 LOSSES = {"bce": OKGE_LOSS_BCE, "kl": OKGE_LOSS_KL}
@@ -64,6 +65,7 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_topk_workspace_bytes", "okge_topk_prefixes", "okge_topk_queries", "okge_topk_merge",
            "okge_train_row_grads_workspace_bytes", "okge_adagrad_rows", "okge_adagrad_rows_workspace_bytes",
            "okge_rows_catch_up", "okge_adagrad_rows_decay",
+           "okge_rows_to_dense", "okge_rows_to_dense_workspace_bytes",
            "okge_adam_step", "okge_adam_rows_workspace_bytes", "okge_adam_rows",
            "okge_adam_multi", "okge_clip_grad_norm_multi", "okge_clip_grad_norm_multi_workspace_bytes",
            "okge_n3_workspace_bytes", "okge_n3_forward_backward",
@@ -278,6 +280,10 @@ def lib():
     L.okge_adagrad_rows_workspace_bytes.argtypes = [c_int64, c_int64]
     L.okge_adagrad_rows.restype = c_int32
     L.okge_adagrad_rows.argtypes = [POINTER(RowsTensor), c_int32, c_float, c_float, c_void_p, c_size_t, c_void_p]
+    L.okge_rows_to_dense_workspace_bytes.restype = c_size_t
+    L.okge_rows_to_dense_workspace_bytes.argtypes = [c_int64, c_int64]
+    L.okge_rows_to_dense.restype = c_int32
+    L.okge_rows_to_dense.argtypes = [POINTER(RowsTensor), c_int32, c_int32, c_void_p, c_size_t, c_void_p]
     L.okge_rows_catch_up.restype = c_int32
     L.okge_rows_catch_up.argtypes = [POINTER(RowsDecayTensor), c_int32, c_void_p, c_float, c_float, c_float, c_void_p]
     L.okge_adagrad_rows_decay.restype = c_int32

@@ -1,5 +1,6 @@
 // C ABI (include/okge.h), host side: the optimizers and the gradient scaling around them.  Dense Adagrad (one, two, up to four
-// tensors), the row-sparse Adagrad with and without deferred weight decay, the lazy (deferred decay) dense step and its pool
+// tensors), the row-sparse Adagrad with and without deferred weight decay, the occurrence rows coalesced into dense gradient
+// tables (okge_rows_to_dense), the lazy (deferred decay) dense step and its pool
 // catch-up, dense (two or up to four tensors) and row-sparse Adam, scaling, clipping (two or up to eight tensors), and the merge of
 // per-shard row log-sum-exps.
 #include "okge_host.h"
@@ -188,6 +189,40 @@ int okge_adagrad_rows(const okge_rows_tensor *tensors, int32_t n_tensors, float 
     int sorted_in = 0;
     if (int rc = rows_sort(segs, &sorted_in, st)) return rc;
     return OKGE_TIMED("rows_update", "rows_update", st, launch_rows_update(segs, sorted_in, lr, eps, st));
+}
+
+// ---- okge_rows_to_dense: the occurrence rows coalesced into dense gradient tables, order fixed ----------------------------------
+size_t okge_rows_to_dense_workspace_bytes(int64_t n0, int64_t n1) { return okge_adagrad_rows_workspace_bytes(n0, n1); }
+
+int okge_rows_to_dense(const okge_rows_tensor *tensors, int32_t n_tensors, int32_t mode, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = check_rows_count(tensors, n_tensors, 0)) return rc;
+    if (mode != OKGE_ROWS_STORE && mode != OKGE_ROWS_ACCUMULATE) return fail(OKGE_ERR_INVALID, "mode is OKGE_ROWS_STORE or OKGE_ROWS_ACCUMULATE");
+    Arena need;
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_rows_tensor &x = tensors[k];
+        if (x.n < 0) return fail(OKGE_ERR_INVALID, "negative occurrence count");
+        if (x.n > ROWS_MAX_N) return fail(OKGE_ERR_UNSUPPORTED, "okge_rows_to_dense takes up to 2^20 occurrence rows per tensor");
+        if (x.n == 0) continue;
+        if (!x.p || !x.ids || !x.g) return fail(OKGE_ERR_INVALID, "null tensor");
+        if (x.table_rows <= 0 || x.row_len <= 0 || x.ld_g < x.row_len) return fail(OKGE_ERR_INVALID, "bad table shape / leading dimension");
+        take_rows_keys(need, x.n);
+    }
+    if (need.total() == 0) return OKGE_OK;
+    if (!workspace || workspace_bytes < need.total()) return fail(OKGE_ERR_WORKSPACE, "workspace too small (okge_rows_to_dense_workspace_bytes)");
+    RowsSegs segs;
+    std::memset(&segs, 0, sizeof(segs));
+    char *ws = static_cast<char *>(workspace);
+    Arena ar;
+    for (int k = 0; k < n_tensors; ++k) {
+        const okge_rows_tensor &x = tensors[k];
+        if (x.n > 0) rows_segment(segs, ws, ar, x.p, nullptr, x.ids, x.g, x.ld_g, x.n, x.table_rows, x.row_len, nullptr);   // (state_sum is not read)
+    }
+    segs.id_err = id_err_ptr();
+    hipStream_t st = as_stream(stream);
+    int sorted_in = 0;
+    if (int rc = rows_sort(segs, &sorted_in, st)) return rc;
+    return OKGE_TIMED("rows_to_dense", "rows_to_dense", st, launch_rows_to_dense(segs, sorted_in, mode == OKGE_ROWS_ACCUMULATE, st));
 }
 
 // ---- Adam: torch.optim.Adam's dense update and torch.optim.SparseAdam's on occurrence rows --------------------------------------

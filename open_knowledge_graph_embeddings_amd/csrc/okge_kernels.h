@@ -314,6 +314,9 @@ hipError_t launch_rows_sort(const RowsSegs &segs, int *sorted_in, hipStream_t st
 hipError_t launch_rows_update(const RowsSegs &segs, int sorted_in, float lr, float eps, hipStream_t st);
 // okge_adam_rows: the same heads and the same walk with the sparse Adam body; the step size is read from each segment's state
 hipError_t launch_rows_update_adam(const RowsSegs &segs, int sorted_in, float beta1, float beta2, float eps, hipStream_t st);
+// okge_rows_to_dense: the same heads and the same walk; the coalesced row is stored to (accumulate: continued from) row `id` of the
+// dense gradient table seg.p -- seg.s is not read
+hipError_t launch_rows_to_dense(const RowsSegs &segs, int sorted_in, int accumulate, hipStream_t st);
 // deferred weight decay on the row-sparse step (okge_rows_catch_up / okge_adagrad_rows_decay): every segment 16-byte accessible
 // (vec) with a step counter per table row; counters[0] = T, the optimizer steps taken
 hipError_t launch_rows_update_decay(const RowsSegs &segs, int sorted_in, const int32_t *counters, float lr, float wd, float eps,

@@ -8,6 +8,8 @@
 //   okge_adagrad_rows_decay                             rows_update_decay_kernel: the same walk with the weight-decay term, per-row step
 //                                                       counters kept (deferred weight decay; the rotating sweep is okge_optim.hip's)
 //   okge_adam_rows                                      rows_update_kernel<AdamRows>: the same sort and walk, torch's sparse Adam on the row
+//   okge_rows_to_dense                                  rows_update_kernel<DenseRows<ACC>>: the same sort and walk, the coalesced row written to
+//                                                       (ACC: continued from) the row of a DENSE gradient table -- the order-fixed dense gradient
 // Nothing here is proportional to the table: the sort is O(n log n) on 8-byte keys, the update touches the n gradient rows and
 // the distinct table rows they name.  No float atomics, no host synchronisation; the launch sequence depends on the n alone.
 #include <hip/hip_runtime.h>
@@ -133,6 +135,10 @@ __global__ __launch_bounds__(256) void rows_merge_kernel(const RowsSegs segs, in
 //   AdagradRowsDecay  (V == 4 only; okge_adagrad_rows_decay) the row first takes the `lag` decay-only steps it still owes, then
 //                     the update carries the weight-decay term -- adagrad4, the dense sweep's expression
 //   AdamRows          adam1_rows (okge_adam_rows): two moment rows, the step size from the segment's device state
+//   DenseRows<ACC>    no update at all (okge_rows_to_dense): the coalesced row IS the result, stored to row `id` of the dense
+//                     gradient table sg.p.  ACC: the chain starts from the row the table holds -- (dE[id] + g_a) + g_b ..., not
+//                     dE[id] + (g_a + g_b ...) -- which is what Row::first is for: it takes the run's first gradient row and
+//                     returns the value the walk continues from (the other bodies return it as it is)
 template <int V> struct RowVec { typedef float type; };
 template <> struct RowVec<4> { typedef float4 type; };
 template <int V> __device__ __forceinline__ typename RowVec<V>::type *row_ptr(float *x) { return reinterpret_cast<typename RowVec<V>::type *>(x); }
@@ -144,6 +150,7 @@ struct AdagradRows {
     template <int V> struct Row {
         typename RowVec<V>::type pv, sv;
         __device__ __forceinline__ void load(const RowsSeg &sg, size_t i) { pv = row_ptr<V>(sg.p)[i]; sv = row_ptr<V>(sg.s)[i]; }
+        __device__ __forceinline__ typename RowVec<V>::type first(const typename RowVec<V>::type &g) const { return g; }
         __device__ __forceinline__ void update(const AdagradRows &b, const RowsSeg &, const typename RowVec<V>::type &acc)
         {
             if constexpr (V == 4) {
@@ -165,6 +172,7 @@ struct AdagradRowsDecay {
     template <int V> struct Row {
         float4 pv, sv;
         __device__ __forceinline__ void load(const RowsSeg &sg, size_t i) { pv = row_ptr<4>(sg.p)[i]; sv = row_ptr<4>(sg.s)[i]; }
+        __device__ __forceinline__ float4 first(const float4 &g) const { return g; }
         __device__ __forceinline__ void update(const AdagradRowsDecay &b, const RowsSeg &, const float4 &acc)
         {
             // decay_replay4 votes across the wave.  Here the wave's lanes belong to different runs, lanes that are no head
@@ -189,6 +197,7 @@ struct AdamRows {
         {
             pv = row_ptr<V>(sg.p)[i]; mv = row_ptr<V>(sg.s)[i]; vv = row_ptr<V>(sg.s2)[i];
         }
+        __device__ __forceinline__ typename RowVec<V>::type first(const typename RowVec<V>::type &g) const { return g; }
         __device__ __forceinline__ void update(const AdamRows &b, const RowsSeg &sg, const typename RowVec<V>::type &acc)
         {
             const float step = __int_as_float(sg.state[ADAM_STEP]);
@@ -208,6 +217,25 @@ struct AdamRows {
     };
 };
 
+template <bool ACC> struct DenseRows {
+    template <int V> struct Row {
+        typename RowVec<V>::type pv;
+        __device__ __forceinline__ void load(const RowsSeg &sg, size_t i) { if constexpr (ACC) pv = row_ptr<V>(sg.p)[i]; }
+        __device__ __forceinline__ typename RowVec<V>::type first(const typename RowVec<V>::type &g) const
+        {
+            if constexpr (ACC) {
+                typename RowVec<V>::type acc = pv;
+                row_add(acc, g);
+                return acc;
+            } else {
+                return g;
+            }
+        }
+        __device__ __forceinline__ void update(const DenseRows &, const RowsSeg &, const typename RowVec<V>::type &acc) { pv = acc; }
+        __device__ __forceinline__ void store(const RowsSeg &sg, size_t i) { row_ptr<V>(sg.p)[i] = pv; }
+    };
+};
+
 template <int V, class Body>
 __device__ __forceinline__ void rows_update_run(const RowsSeg &sg, const uint64_t *__restrict__ keys, int i, uint32_t id, uint32_t pos,
                                                 int lane, int lanes, const Body &body)
@@ -220,7 +248,7 @@ __device__ __forceinline__ void rows_update_run(const RowsSeg &sg, const uint64_
     for (int c = lane; c < cols; c += lanes) {
         typename Body::template Row<V> row;
         row.load(sg, prow + c);
-        vec_t acc = gv[(size_t)pos * ldg + c];
+        vec_t acc = row.first(gv[(size_t)pos * ldg + c]);
         for (int j = i + 1; j < sg.n; ++j) {
             const uint64_t kj = keys[j];
             if ((uint32_t)(kj >> 32) != id) break;
@@ -353,6 +381,17 @@ hipError_t launch_rows_update_adam(const RowsSegs &segs, int sorted_in, float be
     if (threads <= 0) return hipSuccess;
     hipLaunchKernelGGL(rows_update_kernel<AdamRows>, dim3((unsigned)((threads + 255) / 256), segs.n_segs), dim3(256), 0, st, segs, sorted_in,
                        AdamRows{adam_hyper(beta1, beta2, eps, 0.f)});
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_to_dense(const RowsSegs &segs, int sorted_in, int accumulate, hipStream_t st)
+{
+    int64_t threads = 0;
+    for (int k = 0; k < segs.n_segs; ++k) threads = std::max<int64_t>(threads, (int64_t)segs.s[k].n << segs.s[k].lane_shift);
+    if (threads <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((threads + 255) / 256), segs.n_segs);
+    if (accumulate) hipLaunchKernelGGL(rows_update_kernel<DenseRows<true>>, grid, dim3(256), 0, st, segs, sorted_in, DenseRows<true>{});
+    else hipLaunchKernelGGL(rows_update_kernel<DenseRows<false>>, grid, dim3(256), 0, st, segs, sorted_in, DenseRows<false>{});
     return hipGetLastError();
 }
 

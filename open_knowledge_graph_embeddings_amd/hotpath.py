@@ -52,6 +52,7 @@ NO_DROP = DropoutSpec()
 # sharded phases) stop at TILE_MAX_SLOT; okge_score_prefixes, okge_train_forward_backward with dense gradients and
 # okge_evaluate_batch go on to WIDE_MAX_SLOT on the wide path (csrc/okge_wide.hip)
 TILE_MAX_SLOT, WIDE_MAX_SLOT = 512, 4096
+ROWS_MAX_N = 1 << 20      # occurrence rows per tensor of the row calls (okge_adagrad_rows, okge_rows_to_dense, ...)
 
 # OKGE_VALIDATE=1: check every id tensor against the table sizes before a call (one host sync per call).  The kernels
 # trust their ids -- they live in device memory -- so a bad id is an out-of-bounds access; use this while integrating.
@@ -710,6 +711,23 @@ class HotPath:
         ws = self._rows_scratch(arr, self.lib.okge_adagrad_rows_workspace_bytes)
         N.check(self.lib.okge_adagrad_rows(arr, len(tensors), float(lr), float(eps), ws.data_ptr(), ws.numel(), self._stream()),
                 "okge_adagrad_rows")
+
+    def rows_to_dense(self, tensors, accumulate=False):
+        """okge_rows_to_dense: one or two (dense, ids, g) -- the occurrence rows g (n, row_len) of the int32 device ids are added
+        per id in ascending position, sequentially in fp32, and written to the named rows of the dense gradient table `dense`
+        (rows, row_len).  accumulate=False: those rows are overwritten (every other row must already be zero); True: each named
+        row continues the chain from what it holds.  Rows no id names are not written; no float atomics."""
+        arr = (N.RowsTensor * len(tensors))()
+        for a, (p_, i_, g_) in zip(arr, tensors):
+            _need_i32(self.device, (i_,), "rows_to_dense: ids must be a contiguous int32 tensor on the engine's device")
+            _need_f32(self.device, (p_, g_), "rows_to_dense: fp32 tensors on the engine's device", contiguous=False)
+            if p_.dim() != 2 or not p_.is_contiguous():
+                raise N.OkgeError("rows_to_dense: the dense gradient must be a contiguous (rows, row_len) tensor")
+            a.p = p_.data_ptr()
+            self._fill_rows(a, "rows_to_dense", p_, i_, g_)
+        ws = self._rows_scratch(arr, self.lib.okge_rows_to_dense_workspace_bytes)
+        N.check(self.lib.okge_rows_to_dense(arr, len(tensors), N.OKGE_ROWS_ACCUMULATE if accumulate else N.OKGE_ROWS_STORE,
+                                            ws.data_ptr(), ws.numel(), self._stream()), "okge_rows_to_dense")
 
     def _fill_rows(self, a, who, p, ids, g):
         """the (ids, g, ld_g, n, table_rows, row_len) block the three row-tensor structs share; g None: no gradient rows"""

@@ -365,6 +365,10 @@ class ReplicaTrainStep(FusedTrainStep):
     def __init__(self, E, R, scorer, group=None, **kw):
         if kw.get("l2_reg"):
             raise NotImplementedError("ReplicaTrainStep: l2_reg (the N3 regulariser) is built for the single-device FusedTrainStep")
+        if kw.get("deterministic"):
+            raise NotImplementedError("ReplicaTrainStep: deterministic=True is built for the single-device FusedTrainStep (the "
+                                      "all-reduce adds the replicas' gradients in an order of its own); train the replicas with "
+                                      "deterministic=False")
         super().__init__(E, R, scorer, **kw)
         self.group = group
         self.world = dist.get_world_size(group)

@@ -31,6 +31,9 @@ def refuse_for_replicas(inner, who):
     """sharded.ReplicaStep: the exchange is built for the Adagrad step without clipping"""
     if isinstance(inner, StepOptimizer) and (inner.optimizer != "adagrad" or inner.grad_clip > 0):
         raise NotImplementedError(f"{who}: optimizer='adam' and grad_clip are built for the single-device steps")
+    if getattr(inner, "deterministic", False):
+        raise NotImplementedError(f"{who}: a deterministic inner step is built for a single device (the exchange adds the replicas' "
+                                  f"gradients in an order of its own); build the inner step with deterministic=False")
 
 
 def state_views(states, offset, param):

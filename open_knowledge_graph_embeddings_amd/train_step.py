@@ -18,7 +18,7 @@ class FusedTrainStep:
                  input_dropout: float = 0.0, relation_input_dropout: float = 0.0, seed: int = 0, engine=None,
                  grad_clip: float = 0.0, accumulate: int = 1, sparse: bool = False, decay_window=None,
                  l2_reg: float = 0.0, l2_reg_dropout: float = 0.0, l2_reg_per_direction: bool = False,
-                 optimizer: str = "adagrad", betas=(0.9, 0.999)):
+                 optimizer: str = "adagrad", betas=(0.9, 0.999), deterministic: bool = False):
         """Defaults follow config/fb15k237/fb15k237-complex-kge.yaml and the optimizer OptimRegime actually
         builds (utils/optim.py:29,139-160): Adagrad(lr, weight_decay=1e-10, eps=1e-8 leaked from Adam).
 
@@ -49,7 +49,18 @@ class FusedTrainStep:
         (adam_stateE / adam_stateR, int32[4], [0] = t: optimizer steps taken, counted on the device so that a captured graph
         replays it; `adam_t` reads it back).  Works with the dense and the wide step, accumulate, grad_clip and l2_reg.  With
         sparse=True it is torch.optim.SparseAdam on the occurrence rows (okge_adam_rows), which has no weight decay:
-        weight_decay != 0 and decay_window raise ValueError.  `betas` is read by Adam only."""
+        weight_decay != 0 and decay_window raise ValueError.  `betas` is read by Adam only.
+
+        deterministic (False: the step above, launch for launch): dense gradients with the ORDER of every row's additions fixed
+        (okge.h, okge_rows_to_dense).  forward_backward runs the occurrence-row call (OKGE_TRAIN_ROW_GRADS: every gradient
+        contribution stored once, no atomics) with the masks of the default step, then writes each table row's sequential fp32
+        sum in ascending occurrence position into dE / dR -- stored on the first micro-batch of an accumulation window, continued
+        from the row's value on the later ones -- and the dense tail runs unchanged: grad_clip (its norm stays in `grad_norm`,
+        device double[1]), accumulate, dense Adagrad / Adam with weight_decay, GraphedTrainStep, checkpoints.  Two runs from one
+        state and seed are bit-identical on ANY batch; at weight_decay = 0 the Adagrad step is bit-equal to sparse=True, and at
+        weight_decay > 0 to sparse=True with a decay_window after flush().  Costs the (N + 2 B) x d occurrence-row traffic and
+        a key sort per step.  Refused: sparse=True (already reproducible), l2_reg > 0 (the N3 kernel's gradient rows go through
+        float atomics), slot sizes above 512 and N + n_po + n_sp > 2^20 (the occurrence-row call's limits)."""
         N.refuse_bias_scorer(scorer, type(self).__name__)
         self.optimizer = str(optimizer).lower()
         if self.optimizer not in ("adagrad", "adam"):
@@ -63,6 +74,18 @@ class FusedTrainStep:
             if sparse and weight_decay != 0:
                 raise ValueError("weight_decay option is not compatible with sparse gradients (SparseAdam has no weight decay)")
         self.sparse = bool(sparse)
+        self.deterministic = bool(deterministic)
+        self._row_grads = self.sparse or self.deterministic      # the step's call leaves occurrence rows (OKGE_TRAIN_ROW_GRADS)
+        if self.deterministic:
+            if self.sparse:
+                raise ValueError("FusedTrainStep(deterministic=True, sparse=True): the row-sparse step is already bit-reproducible; "
+                                 "use sparse=True alone, or deterministic=True alone for dense gradients")
+            if float(l2_reg or 0.0) > 0:
+                raise NotImplementedError("FusedTrainStep(deterministic=True): the N3 regulariser adds its gradient rows with float "
+                                          "atomics; train with l2_reg=0, or with deterministic=False")
+            if E.shape[1] > H.TILE_MAX_SLOT:
+                raise NotImplementedError(f"FusedTrainStep(deterministic=True): the occurrence-row call stops at slot size "
+                                          f"{H.TILE_MAX_SLOT}; slot sizes up to {H.WIDE_MAX_SLOT} train with deterministic=False")
         self.decay_window = None if decay_window is None else int(decay_window)
         if self.decay_window is not None and (not self.sparse or self.decay_window < 1):
             raise ValueError("decay_window (deferred weight decay) belongs to the sparse step and is >= 1")
@@ -117,6 +140,8 @@ class FusedTrainStep:
         # (batch_size_for_backward = accumulate x batch_size), clipped to `grad_clip` (global 2-norm) if > 0
         self.grad_clip, self.accumulate = float(grad_clip or 0.0), max(1, int(accumulate))
         self._accumulated = 0
+        # deterministic: the global 2-norm of the last clipped gradient (okge_clip_grad_norm: fixed grid, fixed reduction tree)
+        self.grad_norm = torch.zeros(1, dtype=torch.float64, device=E.device) if self.deterministic and self.grad_clip > 0 else None
 
     def state_tensors(self):
         """every tensor a step mutates (GraphedTrainStep snapshots them around its warm-up)"""
@@ -197,7 +222,7 @@ class FusedTrainStep:
         call.fill_ids(batch.po_rel, batch.po_obj, batch.sp_subj, batch.sp_rel, batch.cand_ids, batch.cand_first, batch.n_cand,
                       batch.pos_row, batch.pos_col)
         call.fill_dropout(self.input_dropout, self.relation_input_dropout, self.seed, self.steps, self.step_dev)
-        flags = H.train_flags(row_grads=True) if self.sparse else \
+        flags = H.train_flags(row_grads=True) if self._row_grads else \
             H.train_flags(grads_zero=self._grads_zero, unique_candidates=batch.cand_unique)
         return call.train(self.engine, self.loss, self.label_smoothing, normalizer, flags, self.loss_out, dE, dR)
 
@@ -224,6 +249,8 @@ class FusedTrainStep:
 
     def forward_backward(self, batch: H.PrefixBatch, normalizer=None):
         """trainer.py:206-234.  Returns the summed loss (device double[1], valid after stream sync)."""
+        if self.deterministic:                # (a method of its own: the default step is host-bound, its path stays as short as it was)
+            return self._deterministic_forward_backward(batch, normalizer)
         if self.sparse:
             rb = self._cur_rows = self._row_buffers(batch)
             H.occurrence_ids(self.E.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
@@ -251,6 +278,31 @@ class FusedTrainStep:
                                                 label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out, **how)
         if self.l2_reg > 0:
             self._regularise(batch, normalizer, fast, dE, dR)
+        return loss
+
+    def _deterministic_forward_backward(self, batch: H.PrefixBatch, normalizer):
+        """the occurrence-row call into the per-shape row buffers, then okge_rows_to_dense into dE / dR (class docstring)"""
+        if batch.n_candidates + batch.B > H.ROWS_MAX_N:            # (before anything is launched or allocated)
+            raise N.OkgeError(f"okge_rows_to_dense takes up to 2^20 occurrence rows per tensor: this batch has "
+                              f"{batch.n_candidates} + {batch.B}; train it with deterministic=False")
+        rb = self._cur_rows = self._row_buffers(batch)
+        H.occurrence_ids(self.E.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
+                         batch.po_rel, batch.sp_rel, out=(rb["idE"], rb["idR"]))
+        # a store names -- and so overwrites -- every row of dE only when the candidate range is the whole table from row 0
+        names_all = self._covers_all_rows(batch) and batch.cand_first == 0
+        if self._dE_stale and not (self._grads_zero and names_all):
+            self.dE.zero_()               # rows this batch does not name must read as zero
+            self._dE_stale = False
+        self._last_full = names_all
+        if isinstance(self.engine, H.HotPath) and self._plain(batch):
+            loss = self._fast_forward_backward(batch, normalizer, rb["gE"], rb["gR"])
+        else:
+            self._set_dropout(batch)
+            loss = self.engine.forward_backward(self.E, self.R, self.scorer, batch, rb["gE"], rb["gR"], loss=self.loss,
+                                                label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out,
+                                                row_grads=True)
+        # cleared tables (a fresh window): the named rows are stored; later micro-batches continue each row's chain
+        self.engine.rows_to_dense([(self.dE, rb["idE"], rb["gE"]), (self.dR, rb["idR"], rb["gR"])], accumulate=not self._grads_zero)
         return loss
 
     def optimizer_step(self, lazy_zero=False):
@@ -298,7 +350,7 @@ class FusedTrainStep:
             return loss                      # trainer.py:233-234, 246-248: no optimizer step yet, gradients keep adding up
         self._accumulated = 0
         if self.grad_clip > 0:
-            self.engine.clip_grad_norm_(self.dE, self.dR, self.grad_clip)
+            self.engine.clip_grad_norm_(self.dE, self.dR, self.grad_clip, self.grad_norm)
         self.optimizer_step(lazy_zero=self._last_full and self.accumulate == 1)
         self._grads_zero = True
         return loss
