@@ -454,6 +454,64 @@ int okge_bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call
                                int64_t ld, const int32_t *pos_tok, const int32_t *pos_order, float *dW, float *d_conv,
                                float *d_bn_weight, float *d_bn_bias, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Lookup embedder variants: batch_norm / project_entity / normalize='norm' ----------------------------------
+ * Replaces LookupBaseRelationEmbedder._encode (openkge/model.py:455-480) up to and excluding its final dropout and the
+ * l2_reg hook (model.py:469-479: the fused call's masks on the virtual tables and okge_n3_forward_backward), and autograd's
+ * walk back through it.  Per call, in this order:
+ *   gather rows of the entity / relation table by id list or id range (model.py:457-460; an id outside its table reads row 0
+ *          and is counted, okge_id_errors)
+ *   -> input dropout (model.py:461-462; okge_dropout `input_drop`, keyed by the row's position in the call; training only)
+ *   -> BatchNorm1d, one forward per call (model.py:463-464; bn_e for entity calls, bn_r for relation calls; eps bn_eps;
+ *          training: the call's biased batch statistics, running statistics moved once per call in call order with
+ *          bn_momentum and the unbiased variance; eval: the running statistics)
+ *   -> entity calls only: rows . W^T [-> ReLU] (model.py:465-466; W_obj for `subj == 0` calls, W_subj for `subj != 0`)
+ *   -> x / max(||x||_2, 1e-12) (model.py:467-468, F.normalize).
+ * A PASS is up to 8 calls -- the five encode calls of a batch (trainer.py:75-91) are one.  The rows of its entity calls
+ * follow one another in EV and those of its relation calls in RV, each in call order; with a projection the `subj == 0`
+ * entity calls come before the `subj != 0` ones.  At most one id RANGE (ids == NULL) per table.  d <= 512, else
+ * OKGE_ERR_UNSUPPORTED.  A training call of exactly one row under batch-norm is OKGE_ERR_INVALID (torch raises there).
+ * Input-dropout stream ids of the five calls of a batch: 16 candidates, 17 po objects, 18 po relations, 19 sp subjects,
+ * 20 sp relations (OKGE_LOOKUP_STREAM_*) -- apart from 0 .. 4, which the final dropout's five masks use.
+ * okge_lookup_encode_calls  : EV / RV = the encoded rows; training != 0 keeps what the backward needs in the workspace.
+ * okge_lookup_backward_calls: after a training encode with the same arguments, workspace and EV / RV.  dEV / dRV = the
+ *                             gradient of EV / RV.  d_bn_*, dW_obj, dW_subj are WRITTEN (sums over the calls in call
+ *                             order); dE / dR += the table rows' gradients: a range adds row for row, id lists are summed per
+ *                             (table, id) in the order of list_order = the pass's id-list rows (numbered entity calls first,
+ *                             then relation calls) sorted by (table, id), stable (index plumbing by the caller; n_list of them).
+ *                             Row 0, the padding row, receives nothing.
+ * No float atomics: bit-reproducible.  Workspace: okge_lookup_workspace_bytes(entity rows, relation rows, d, training). */
+enum { OKGE_LOOKUP_STREAM_CAND = 16, OKGE_LOOKUP_STREAM_PO_ENT = 17, OKGE_LOOKUP_STREAM_PO_REL = 18,
+       OKGE_LOOKUP_STREAM_SP_ENT = 19, OKGE_LOOKUP_STREAM_SP_REL = 20 };
+typedef struct okge_lookup_encoder {
+    const float *E, *R;                    /* entity (n_ent x d) and relation (n_rel x d) tables */
+    int32_t n_ent, n_rel, d;
+    int32_t normalize;                     /* 0: none; 1: F.normalize */
+    int32_t activation;                    /* behind the projection: 0 none, 1 ReLU */
+    int32_t _pad;
+    const float *bn_e_weight, *bn_e_bias;  /* NULL weight: no batch-norm (then all eight are NULL) */
+    float *bn_e_running_mean, *bn_e_running_var;
+    const float *bn_r_weight, *bn_r_bias;
+    float *bn_r_running_mean, *bn_r_running_var;
+    const float *W_obj, *W_subj;           /* (d x d) row-major nn.Linear weights; NULL: no projection (then both) */
+    float bn_eps, bn_momentum;
+} okge_lookup_encoder;
+typedef struct okge_lookup_call {
+    const int32_t *ids;                    /* NULL: rows first_id .. first_id + n - 1 */
+    int32_t first_id, n;                   /* n == 0: an empty call */
+    int32_t relation;                      /* 0: entity table, bn_e; 1: relation table, bn_r */
+    int32_t subj;                          /* entity calls: 0 obj_projection, 1 subj_projection */
+    okge_dropout input_drop;
+} okge_lookup_call;
+size_t okge_lookup_workspace_bytes(int32_t ent_rows, int32_t rel_rows, int32_t d, int32_t training);
+int okge_lookup_encode_calls(const okge_lookup_encoder *e, const okge_lookup_call *calls, int32_t n_calls, int32_t training,
+                             float *EV, int64_t ld_e, float *RV, int64_t ld_r, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int okge_lookup_backward_calls(const okge_lookup_encoder *e, const okge_lookup_call *calls, int32_t n_calls, const float *EV,
+                               int64_t ld_e, const float *RV, int64_t ld_r, const float *dEV, int64_t ld_de, const float *dRV,
+                               int64_t ld_dr, const int32_t *list_order, int32_t n_list, float *dE, float *dR,
+                               float *d_bn_e_weight, float *d_bn_e_bias, float *d_bn_r_weight, float *d_bn_r_bias, float *dW_obj,
+                               float *dW_subj, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Tucker3 / RESCAL scorer with a projected relation --------------------------------------------------------
  * Replaces, for LookupTucker3RelationModel, encode_rel's Linear (model.py:402-408, :482-490: M_b = reshape(W rho_b, (d, d)),
  * W = relation_projection.0.weight (d^2, r_e) row-major) together with the two bmm of RescalRelationScorer._score

@@ -14,7 +14,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_i
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libokge_hip.so")
-SOURCES = ["okge_core.hip", "okge_api_train.hip", "okge_api_eval.hip", "okge_api_encoders.hip", "okge_api_optim.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_wide.hip", "okge_misc.hip", "okge_optim.hip", "okge_adam.hip", "okge_rank.hip", "okge_topk.hip", "okge_bias.hip", "okge_sparse.hip", "okge_n3.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
+SOURCES = ["okge_core.hip", "okge_api_train.hip", "okge_api_eval.hip", "okge_api_encoders.hip", "okge_api_optim.hip", "okge_gemm.hip", "okge_train.hip", "okge_dq_split.hip", "okge_train64.hip", "okge_train64k.hip", "okge_wide.hip", "okge_misc.hip", "okge_optim.hip", "okge_adam.hip", "okge_rank.hip", "okge_topk.hip", "okge_bias.hip", "okge_sparse.hip", "okge_n3.hip", "okge_pool.hip", "okge_lstm.hip", "okge_bigram.hip", "okge_lookup_encode.hip", "okge_tucker3.hip", "okge_collate.cpp", "okge_dataset.cpp"]
 # every header a source may include: all of csrc/*.h (listed by the directory, so a new header cannot be forgotten) + the ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "okge.h")]
 
@@ -59,6 +59,7 @@ EXPORTS = ["okge_abi_version", "okge_last_error", "okge_score_prefixes", "okge_t
            "okge_rank_counts", "okge_rank_metrics", "okge_evaluate_batch", "okge_evaluate_fused", "okge_evaluate_fused_shard", "okge_evaluate_fused_batches", "okge_eval_workspace_bytes", "okge_score_triples", "okge_pool_workspace_bytes", "okge_pool_encode", "okge_pool_backward", "okge_pool_encode_calls", "okge_pool_backward_calls", "okge_pool_scatter_state_bytes", "okge_pool_backward_workspace_bytes", "okge_adagrad_multi", "okge_adagrad_lazy", "okge_pool_catch_up_calls", "okge_prefix_score_backward", "okge_prefix_score_backward_workspace_bytes", "okge_scatter_rows",
            "okge_lstm_workspace_bytes", "okge_lstm_encode_calls", "okge_lstm_backward_calls",
            "okge_bigram_workspace_bytes", "okge_bigram_encode_calls", "okge_bigram_backward_calls",
+           "okge_lookup_workspace_bytes", "okge_lookup_encode_calls", "okge_lookup_backward_calls",
            "okge_tucker3_workspace_bytes", "okge_tucker3_fold", "okge_tucker3_backward", "okge_tucker3_score_triples", "okge_tucker3_apply", "okge_tucker3_outer",
            "okge_collate_batch", "okge_collate_batches", "okge_dataset_open", "okge_dataset_sizes",
            "okge_dataset_copy", "okge_dataset_close", "okge_encode_rows", "okge_scale_inplace", "okge_rescale_gradients", "okge_adagrad_step", "okge_adagrad_step2", "okge_id_errors", "okge_clip_grad_norm", "okge_merge_logsumexp", "okge_filtered_ranks", "okge_timing_enable",
@@ -159,6 +160,19 @@ class BigramSlot(Structure):
                 ("max_len", c_int32), ("conv_weight", c_void_p), ("pool", c_int32), ("normalize", c_int32),
                 ("bn_weight", c_void_p), ("bn_bias", c_void_p), ("bn_running_mean", c_void_p), ("bn_running_var", c_void_p),
                 ("bn_num_batches_tracked", c_void_p), ("bn_eps", c_float), ("_pad", c_int32)]
+
+
+class LookupEncoder(Structure):
+    _fields_ = [("E", c_void_p), ("R", c_void_p), ("n_ent", c_int32), ("n_rel", c_int32), ("d", c_int32), ("normalize", c_int32),
+                ("activation", c_int32), ("_pad", c_int32), ("bn_e_weight", c_void_p), ("bn_e_bias", c_void_p),
+                ("bn_e_running_mean", c_void_p), ("bn_e_running_var", c_void_p), ("bn_r_weight", c_void_p), ("bn_r_bias", c_void_p),
+                ("bn_r_running_mean", c_void_p), ("bn_r_running_var", c_void_p), ("W_obj", c_void_p), ("W_subj", c_void_p),
+                ("bn_eps", c_float), ("bn_momentum", c_float)]
+
+
+class LookupCall(Structure):
+    _fields_ = [("ids", c_void_p), ("first_id", c_int32), ("n", c_int32), ("relation", c_int32), ("subj", c_int32),
+                ("input_drop", Dropout)]
 
 
 class AdagradTensor(Structure):
@@ -438,6 +452,15 @@ def lib():
     L.okge_bigram_backward_calls.restype = c_int32
     L.okge_bigram_backward_calls.argtypes = [POINTER(BigramSlot), POINTER(BigramCall), c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.okge_lookup_workspace_bytes.restype = c_size_t
+    L.okge_lookup_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
+    L.okge_lookup_encode_calls.restype = c_int32
+    L.okge_lookup_encode_calls.argtypes = [POINTER(LookupEncoder), POINTER(LookupCall), c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                                           c_int64, c_void_p, c_size_t, c_void_p]
+    L.okge_lookup_backward_calls.restype = c_int32
+    L.okge_lookup_backward_calls.argtypes = [POINTER(LookupEncoder), POINTER(LookupCall), c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                             c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32] + [c_void_p] * 9 + \
+                                            [c_size_t, c_void_p]
     L.okge_tucker3_workspace_bytes.restype = c_size_t
     L.okge_tucker3_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     L.okge_tucker3_fold.restype = c_int32

@@ -16,7 +16,8 @@ is refused by an Adam step and the other way round unless `reset_optimizer` is s
 contain tensors and plain containers only, so they load with `torch.load(..., weights_only=True)`; the reference's own
 `results` entry (a pickled ResultsLog object) is never written and never read.
 
-The models whose rows are encoded from tokens and the Tucker3 model train more than two tensors: model_checkpoint /
+The models whose rows are encoded from tokens, the Tucker3 model and the lookup models with an `_encode` variant on
+(lookup_variants.LookupVariantTrainStep) train more than two tensors: model_checkpoint /
 save_model_checkpoint / load_model_checkpoint (below) move the same layout -- the module's whole state_dict, one optimizer state
 entry per parameter in model.parameters() order -- between a module and the driver its train_step() returned.  Which part of
 which buffer of the step belongs to which parameter is the embedders' knowledge (optimizer_params_and_state); nothing else of

@@ -267,6 +267,32 @@ int okge_bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call
                                  workspace_bytes, id_err_ptr(), stream);
 }
 
+// ---- Lookup embedder variants (okge_lookup_encode.hip) ----------------------------------------------------------------
+size_t okge_lookup_workspace_bytes(int32_t ent_rows, int32_t rel_rows, int32_t d, int32_t training)
+{
+    return lookup_workspace_bytes(ent_rows, rel_rows, d, training);
+}
+
+int okge_lookup_encode_calls(const okge_lookup_encoder *e, const okge_lookup_call *calls, int32_t n_calls, int32_t training,
+                             float *EV, int64_t ld_e, float *RV, int64_t ld_r, void *workspace, size_t workspace_bytes,
+                             void *stream)
+{
+    ScopedTimer tm("lookup_encode", as_stream(stream));
+    return lookup_encode_calls(e, calls, n_calls, training, EV, ld_e, RV, ld_r, workspace, workspace_bytes, id_err_ptr(), stream);
+}
+
+int okge_lookup_backward_calls(const okge_lookup_encoder *e, const okge_lookup_call *calls, int32_t n_calls, const float *EV,
+                               int64_t ld_e, const float *RV, int64_t ld_r, const float *dEV, int64_t ld_de, const float *dRV,
+                               int64_t ld_dr, const int32_t *list_order, int32_t n_list, float *dE, float *dR,
+                               float *d_bn_e_weight, float *d_bn_e_bias, float *d_bn_r_weight, float *d_bn_r_bias, float *dW_obj,
+                               float *dW_subj, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ScopedTimer tm("lookup_backward", as_stream(stream));
+    return lookup_backward_calls(e, calls, n_calls, EV, ld_e, RV, ld_r, dEV, ld_de, dRV, ld_dr, list_order, n_list, dE, dR,
+                                 d_bn_e_weight, d_bn_e_bias, d_bn_r_weight, d_bn_r_bias, dW_obj, dW_subj, workspace, workspace_bytes,
+                                 id_err_ptr(), stream);
+}
+
 // ---- LSTM token encoder (okge_lstm.hip) ----------------------------------------------------------------------------
 size_t okge_lstm_workspace_bytes(int32_t rows, int32_t max_len, int32_t d, int32_t training)
 {

@@ -229,6 +229,15 @@ int bigram_encode_calls(const okge_bigram_slot *s, const okge_bigram_call *calls
 int bigram_backward_calls(const okge_bigram_slot *s, const okge_bigram_call *calls, int32_t n_calls, const float *d_out, int64_t ld,
                           const int32_t *pos_tok, const int32_t *pos_order, float *dW, float *d_conv, float *d_bn_weight,
                           float *d_bn_bias, void *workspace, size_t workspace_bytes, int *err, void *stream);
+// Lookup embedder variants (okge_lookup_encode.hip): the bodies of the C ABI's okge_lookup_* (okge.h), err = the device's id-error word
+size_t lookup_workspace_bytes(int32_t ent_rows, int32_t rel_rows, int32_t d, int32_t training);
+int lookup_encode_calls(const okge_lookup_encoder *e, const okge_lookup_call *calls, int32_t n_calls, int32_t training, float *EV,
+                        int64_t ld_e, float *RV, int64_t ld_r, void *workspace, size_t workspace_bytes, int *err, void *stream);
+int lookup_backward_calls(const okge_lookup_encoder *e, const okge_lookup_call *calls, int32_t n_calls, const float *EV, int64_t ld_e,
+                          const float *RV, int64_t ld_r, const float *dEV, int64_t ld_de, const float *dRV, int64_t ld_dr,
+                          const int32_t *list_order, int32_t n_list, float *dE, float *dR, float *d_bn_e_weight, float *d_bn_e_bias,
+                          float *d_bn_r_weight, float *d_bn_r_bias, float *dW_obj, float *dW_subj, void *workspace,
+                          size_t workspace_bytes, int *err, void *stream);
 // Tucker3 / RESCAL fold and backward (okge_tucker3.hip); cus = compute units of the device (split of the long contractions)
 int tucker3_splits(int B, int Nn, int outer, int cus);
 size_t tucker3_workspace_bytes(int B, int d, int r, int cus);

@@ -518,5 +518,49 @@ inline bool plan_n3(int B, int N, int d, N3Plan &p)
     return true;
 }
 
+// ---- the lookup embedder variants' encode (okge_lookup_encode.hip) ------------------------------------
+// One pass = the encode calls of a batch; their rows are numbered entity calls first, then relation calls.  Batch-norm column
+// sums are taken over chunks of LOOKUP_BN_CHUNK rows of one call and added in chunk order; the projection's weight gradients
+// over at most LOOKUP_MAX_SPLITS slabs of rows, added in slab order.  Eval mode keeps the forward's regions only.
+constexpr int LOOKUP_MAX_CALLS = 8, LOOKUP_BN_CHUNK = 128, LOOKUP_MAX_SPLITS = 16, LOOKUP_MAX_D = 512;
+struct LookupLayout {
+    size_t off_X;        // [rows][d]  gathered rows behind the input dropout
+    size_t off_saved;    // [LOOKUP_MAX_CALLS][4 d]  per call, at 2 d: the call's d weight, d bias (the layout enc_bn_grad_kernel reads)
+    size_t off_stat;     // [LOOKUP_MAX_CALLS][2 d] doubles: per call the batch mean and rstd
+    size_t off_part;     // [max_chunks][2 d] doubles: the chunks' column sums
+    size_t off_norm;     // [rows] doubles: row norms (normalize='norm')
+    size_t off_Wt;       // [2][d][d]  the two projection weights, transposed
+    size_t off_P;        // [entity rows][d]  projected rows in front of the normalisation
+    size_t off_G1;       // training: [rows][d]  gradient behind the normalisation / activation backward
+    size_t off_G2;       // training: [entity rows][d]  gradient behind the projection backward
+    size_t off_slab;     // training: [2][LOOKUP_MAX_SPLITS][d][d]  partial weight gradients
+    size_t off_Xbn;      // training: [entity rows][d]  the batch-normed rows the projection read
+    size_t total;
+    int    max_chunks;   // chunks of a pass at most: every call may end in a partial chunk
+};
+inline bool lookup_layout(int64_t ent_rows, int64_t rel_rows, int d, bool training, LookupLayout &l)
+{
+    const int64_t rows = ent_rows + rel_rows;
+    if (ent_rows < 0 || rel_rows < 0 || rows <= 0 || d <= 0 || d > LOOKUP_MAX_D || rows * d > INT32_MAX) return false;
+    Arena ar;
+    l.max_chunks = (int)((rows + LOOKUP_BN_CHUNK - 1) / LOOKUP_BN_CHUNK) + LOOKUP_MAX_CALLS;
+    l.off_X = ar.take((size_t)rows * d * sizeof(float));
+    l.off_saved = ar.take((size_t)LOOKUP_MAX_CALLS * 4 * d * sizeof(float));
+    l.off_stat = ar.take((size_t)LOOKUP_MAX_CALLS * 2 * d * sizeof(double));
+    l.off_part = ar.take((size_t)l.max_chunks * 2 * d * sizeof(double));
+    l.off_norm = ar.take((size_t)rows * sizeof(double));
+    l.off_Wt = ar.take((size_t)2 * d * d * sizeof(float));
+    l.off_P = ar.take((size_t)ent_rows * d * sizeof(float));
+    l.off_G1 = l.off_G2 = l.off_slab = l.off_Xbn = ar.total();
+    if (training) {
+        l.off_G1 = ar.take((size_t)rows * d * sizeof(float));
+        l.off_G2 = ar.take((size_t)ent_rows * d * sizeof(float));
+        l.off_slab = ar.take((size_t)2 * LOOKUP_MAX_SPLITS * d * d * sizeof(float));
+        l.off_Xbn = ar.take((size_t)ent_rows * d * sizeof(float));
+    }
+    l.total = ar.total();
+    return true;
+}
+
 }  // namespace okge
 #pragma GCC visibility pop

@@ -1,8 +1,10 @@
-// Host and device code shared by the token encoders that run on the virtual-table step: the LSTM (okge_lstm.hip) and the
-// bigram convolution (okge_bigram.hip).  ONE definition of the call list of a pass, the workspace carving, the split-K choice,
-// the batch-norm column sum and parameter-gradient sum, the token-gradient scatter and the 64 x 128 exact-fp32 GEMM tile, so
-// that a further encoder brings only what is its own: its operand fetches, its epilogues, its statistics.  Everything here has
-// internal linkage (two translation units include it); nothing branches on which encoder it runs in.
+// Host and device code shared by the encoders that run on the virtual-table step: the LSTM (okge_lstm.hip), the bigram
+// convolution (okge_bigram.hip) and the lookup embedder's variants (okge_lookup_encode.hip: the call list, the column sum, the
+// parameter-gradient sum, the split-K choice and the GEMM tile).  ONE definition of the call list of a pass, the workspace
+// carving, the split-K choice, the batch-norm column sum and parameter-gradient sum, the token-gradient scatter and the 64 x 128
+// exact-fp32 GEMM tile, so that a further encoder brings only what is its own: its operand fetches, its epilogues, its
+// statistics.  Everything here has internal linkage (three translation units include it); nothing branches on which encoder it
+// runs in.
 #pragma once
 #include <algorithm>
 #include <cstdint>

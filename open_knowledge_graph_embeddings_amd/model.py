@@ -12,9 +12,12 @@ ids are int32 ``(b, 1)`` (or ``(N,)`` for candidates), scores come back ``(b, N)
   (``autograd_score``: HIP forward, GEMM + chain-rule backward); under ``torch.no_grad()`` they take the fused id path;
 * the fused path (gather + dropout inside the tile kernels) covers the lookup embedder with batch_norm / projection /
   normalize / l2_reg off -- every BASELINE config.  With one of those `_encode` variants on (model.py:463-479) the
-  embedder FALLS THROUGH to torch for the encode (the reference's own op sequence, differentiable) and the encoded rows
-  go through the HIP scorer / loss / backward as two small virtual tables (trainer.AddLossModule); sparse gradients and
-  the relation projection of the non-"Simple" embedder raise NotImplementedError at construction;
+  embedder by default FALLS THROUGH to torch for the encode (the reference's own op sequence, differentiable) and the
+  encoded rows go through the HIP scorer / loss / backward as two small virtual tables (trainer.AddLossModule).  The same
+  encode and its backward exist on HIP (csrc/okge_lookup_encode.hip, lookup_variants.py): `train_step(...)` returns the
+  driver LookupVariantTrainStep, and AddLossModule(fused_variants=True) takes it for every batch with one shared candidate
+  block.  Direct encode_* / *_prefix_score calls, top-k and the fused evaluator keep the torch encode for these models;
+  sparse gradients and the relation projection of the non-"Simple" embedder raise NotImplementedError at construction;
 * the two dropouts the reference applies in sequence (input_dropout, dropout; model.py:461-470) draw from a
   counter-based Philox stream instead of torch's global generator.
 """
@@ -362,6 +365,35 @@ class LookupBaseRelationEmbedder(RelationEmbedder):
             batch.n_cand = self.E.shape[0] - batch.cand_first
         scores, cols, ids = self.engine().topk_prefixes(self.E, self.R, self.scorer_name, batch, k, filt_ptr, filt_col)
         return scores, ids, cols
+
+    # -- the _encode variants on HIP (lookup_variants.py) ----------------------------------------------------------
+    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
+                   grad_clip=0.0):
+        """The training driver of a model with batch_norm / project_entity / normalize / l2_reg on: LookupVariantTrainStep over
+        the module's parameters (updated in place).  optimizer / betas / grad_clip: as on FusedTrainStep.  A plain lookup model
+        raises ValueError: its driver is train_step.FusedTrainStep."""
+        from . import lookup_variants as LV
+        return LV.make_step(self, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps, label_smoothing=label_smoothing,
+                            optimizer=optimizer, betas=betas, grad_clip=grad_clip)
+
+    def autograd_step(self, loss, label_smoothing):
+        """the cached LookupVariantTrainStep behind AddLossModule(fused_variants=True)"""
+        from . import lookup_variants as LV
+        return LV.autograd_step(self, loss, label_smoothing)
+
+    def autograd_params_and_grads(self, st):
+        from . import lookup_variants as LV
+        return LV.autograd_params_and_grads(self, st)
+
+    def loss_only(self, batch, kind, smoothing, all_outputs):
+        """summed validation loss of an eval-mode batch through the HIP encode (AddLossModule(fused_variants=True))"""
+        from . import lookup_variants as LV
+        return LV.loss_only(self, batch, kind, smoothing, all_outputs)
+
+    def optimizer_params_and_state(self, st):
+        """For checkpoint.py, `st` = the driver train_step() returned"""
+        from . import lookup_variants as LV
+        return LV.optimizer_params_and_state(self, st)
 
 
 class LookupSimpleRelationEmbedder(LookupBaseRelationEmbedder):

@@ -27,8 +27,16 @@ def check_optimizer(optimizer, betas):
     return name, b
 
 
+def refuse_single_device(inner, who):
+    """a step that is built for eager single-device use says so in `single_device` (what to use instead): no wrapper takes it"""
+    why = getattr(inner, "single_device", None)
+    if why:
+        raise NotImplementedError(f"{who}: {why}")
+
+
 def refuse_for_replicas(inner, who):
     """sharded.ReplicaStep: the exchange is built for the Adagrad step without clipping"""
+    refuse_single_device(inner, who)
     if isinstance(inner, StepOptimizer) and (inner.optimizer != "adagrad" or inner.grad_clip > 0):
         raise NotImplementedError(f"{who}: optimizer='adam' and grad_clip are built for the single-device steps")
     if getattr(inner, "deterministic", False):

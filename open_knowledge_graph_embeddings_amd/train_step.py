@@ -10,6 +10,7 @@ import torch
 
 from . import _native as N
 from . import hotpath as H
+from .step_optim import refuse_single_device
 
 
 class FusedTrainStep:
@@ -370,6 +371,7 @@ class GraphedTrainStep:
     PAD_COL = 2 ** 31 - 1
 
     def __init__(self, inner, example: H.PrefixBatch, pos_capacity, normalizer=None, counter=None):
+        refuse_single_device(inner, type(self).__name__)
         self.inner = inner
         dev = example.pos_row.device
         self.device = dev

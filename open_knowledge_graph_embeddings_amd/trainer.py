@@ -120,7 +120,8 @@ class AddLossModule(nn.Module):
     returns None in its place: the reference's Trainer reads the predictions only in evaluation (trainer.py:258-272), and
     the (B, N) block is the one thing the fused training kernels never need to write (29.8 MB per step at FB15k-237)."""
 
-    def __init__(self, model, loss, bce_label_smoothing=0.0, training_outputs=True, sparse_grads=False, fused_l2_reg=False):
+    def __init__(self, model, loss, bce_label_smoothing=0.0, training_outputs=True, sparse_grads=False, fused_l2_reg=False,
+                 fused_variants=False):
         super().__init__()
         self.model = model
         self.loss = loss
@@ -137,6 +138,24 @@ class AddLossModule(nn.Module):
         # directions where the reference draws one per direction: the hook is then twice one term -- exact without dropout,
         # equal in expectation with it.
         self.fused_l2_reg = bool(fused_l2_reg)
+        # fused_variants (not in the reference's signature; opt-in as sparse_grads and fused_l2_reg are): a lookup ComplEx /
+        # DistMult model with batch_norm, project_entity, normalize='norm' or l2_reg on takes the HIP encode and its backward
+        # (lookup_variants.LookupVariantTrainStep) for every batch that has ONE shared candidate block -- batch_shared_entities
+        # given, or eval mode.  A training batch with batch_shared_entities None (one candidate block per direction) keeps the
+        # torch fall-through below.
+        self.fused_variants = bool(fused_variants)
+        if self.fused_variants:
+            if self.fused_l2_reg or self.sparse_grads:
+                raise NotImplementedError("fused_variants=True goes with neither fused_l2_reg (l2_reg is part of it) nor sparse_grads "
+                                          "(the HIP encode returns dense gradients)")
+            if hasattr(model, "entity_token_ids") or getattr(model, "fused_step_model", False) \
+                    or not getattr(model, "encode_in_torch", False) or getattr(model, "scorer_name", None) not in ("complex", "distmult"):
+                raise NotImplementedError("fused_variants=True is built for the ComplEx / DistMult lookup models with batch_norm, "
+                                          "project_entity, normalize='norm' or l2_reg on (a plain lookup model takes the fused step as it "
+                                          "is; Tucker3 and the token models bring their own)")
+            from . import lookup_variants as LV
+            LV.refuse_unsupported(model)
+            LV.activation_name(model)
         if self.fused_l2_reg and (hasattr(model, "entity_token_ids") or getattr(model, "fused_step_model", False)
                                   or not hasattr(model, "entity_embedding") or not hasattr(model, "l2_reg")
                                   or getattr(model, "scorer_name", None) not in ("complex", "distmult")
@@ -228,6 +247,8 @@ class AddLossModule(nn.Module):
         if self.training_outputs or not m.training:
             all_outputs = torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :n]
         smoothing = self.bce_label_smoothing if kind == "bce" else 0.0
+        if self.fused_variants and (not m.training or (want_grad and batch_shared_entities is not None)):
+            return self._fused_variant_result(m, batch, kind, smoothing, want_grad, all_outputs)
         if self._in_torch(m):
             return self._variant_result(m, batch, kind, smoothing, want_grad, all_outputs, epoch,
                                         all_entities=not use_batch_shared_entities and not m.training,
@@ -418,6 +439,20 @@ class AddLossModule(nn.Module):
                                             loss=kind, label_smoothing=smoothing, normalizer=1.0, scores=out,
                                             loss_only=True).to(torch.float32).reshape(())
             result = part if result is None else result + part
+        return result, hook_loss, all_outputs
+
+    def _fused_variant_result(self, m, batch, kind, smoothing, want_grad, all_outputs):
+        """AddLossModule(fused_variants=True): the lookup embedder's variants on the HIP encode, through the protocol of the token
+        models (autograd_step / autograd_params_and_grads / loss_only).  The step's normalizer is 1 and the hook's gradient is
+        part of the gradients it leaves, so `(loss.sum() + hook) / normalizer` (trainer.py:217-221) scales both by the upstream
+        scalar of the loss; the hook's value is returned beside it (model.py:447-453: training mode, l2_reg > 0)."""
+        if not want_grad:
+            return m.loss_only(batch, kind, smoothing, all_outputs).to(torch.float32).reshape(()), None, all_outputs
+        st = m.autograd_step(kind, smoothing)
+        loss = st.forward_backward(batch, normalizer=1.0, scores=all_outputs)
+        params, grads = m.autograd_params_and_grads(st)
+        result = _TokenPooledLossFn.apply(loss, m.engine(), grads, *params)
+        hook_loss = st.reg_out.to(torch.float32).reshape(()) if m.l2_reg > 0 else None
         return result, hook_loss, all_outputs
 
     def _token_result(self, m, batch, kind, smoothing, want_grad, all_outputs, hook_loss):
