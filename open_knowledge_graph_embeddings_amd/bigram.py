@@ -18,7 +18,7 @@ import torch
 from . import _native as N
 from .model import ComplexRelationScorer, DistmultRelationScorer, Models
 from .token_encoder import PRECOMPUTE_CHUNK, EncodeFn, EncoderPass, EncoderTrainStep, TokenEncoderEmbedder, bn_grad_pointers
-from .token_pooled import BN_EPS
+from .token_embedder import BN_EPS
 
 MAX_LEN = 64
 POOL_SUM, POOL_MAX = 0, 1
@@ -148,15 +148,15 @@ class BigramPoolingRelationEmbedder(TokenEncoderEmbedder):
     masks), slot sizes up to 512, max_length 2..64; not implemented (raise at construction): gates=True, normalize='norm',
     encoder_activiation, project_relation, sparse, unequal slot sizes, slot sizes above 512, max_length below 2.  Training:
     BigramTrainStep (fused, own dense Adagrad) or trainer.AddLossModule (autograd bridge: any torch optimizer over the
-    module's parameters).  The evaluation surface (get_all_* / get_*, prefix scores, loss_only) is the token-pooled
-    embedder's."""
+    module's parameters)."""
 
     what, _train_step_class = "bigram", BigramTrainStep
+    step_copies_batchnorm = False      # (train_step(): the module's batch-norm parameters ARE views of the slots' buffers)
 
     def __init__(self, entity_slot_size, relation_slot_size, train_data, normalize='', pool='', dropout=0.0, entity_dropout=None,
                  relation_dropout=None, encoder_activiation=None, sparse=False, init_std=0.01, gates=False, project_relation=False,
                  seed=0):
-        torch.nn.Module.__init__(self)
+        super().__init__()
         if gates:
             raise NotImplementedError("gates=True is not implemented for the bigram embedder")
         if normalize == 'norm':
@@ -209,9 +209,9 @@ class BigramPoolingRelationEmbedder(TokenEncoderEmbedder):
         return PRECOMPUTE_CHUNK                        # (this module's: a test shrinks it)
 
     # -- AddLossModule / autograd bridge (the reference Trainer's path: trainer.py:142, 206-234) ---------------------
-    def _bigram_slots(self, share):
-        """the two slots over the module's parameters; share: conv weight and batch-norm parameters of the module become
-        views of the slot's flat buffer (an optimizer step on the slot moves the module)"""
+    def _train_slots(self, share=True):
+        """the two slots over the module's parameters; share (train_step()): conv weight and batch-norm parameters of the
+        module become views of the slot's flat buffer (one optimizer segment; a step on the slot moves the module)"""
         slots = []
         for relation in (False, True):
             emb, tok, conv, bn = self._parts(relation)
@@ -228,19 +228,13 @@ class BigramPoolingRelationEmbedder(TokenEncoderEmbedder):
     def autograd_step(self, loss, label_smoothing):
         """the cached BigramTrainStep behind AddLossModule: reads the module's parameters; its optimizer is NOT used (the
         caller's torch optimizer steps the module parameters)"""
-        st = self._cached_autograd_step(loss, label_smoothing, lambda: self._bigram_slots(share=False))
+        st = self._cached_autograd_step(loss, label_smoothing, lambda: self._train_slots(share=False))
         for sl, relation in ((st.entity, False), (st.relation, True)):
             emb, tok, conv, bn = self._parts(relation)
             sl.conv.copy_(conv.weight.data)                                    # the module's parameters may have been stepped outside
             if bn is not None:
-                sl.bn[:sl.d].copy_(bn.weight.data)
-                sl.bn[sl.d:].copy_(bn.bias.data)
                 sl.running_mean, sl.running_var, sl.num_batches_tracked = bn.running_mean, bn.running_var, bn.num_batches_tracked
-            sl.dW = torch.zeros_like(sl.W)                                     # fresh gradient buffers: the last ones went to autograd
-            sl.fresh_grads()
-        st.steps = self.dropout_step
-        self.dropout_step += 1
-        return st
+        return self._refresh_autograd_step(st)
 
     def autograd_params_and_grads(self, st):
         params, grads = [], []
@@ -257,16 +251,6 @@ class BigramPoolingRelationEmbedder(TokenEncoderEmbedder):
         if bn is not None:
             out += [(bn.weight, flat, 2 * d * d), (bn.bias, flat, 2 * d * d + d)]
         return out
-
-    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
-                   grad_clip=0.0):
-        """The training driver for this model: shares the module's parameters (updated in place).  The conv weight and the
-        batch-norm parameters of each slot become views of one flat buffer (one optimizer segment).  optimizer / betas /
-        grad_clip: as on FusedTrainStep."""
-        slots = self._bigram_slots(share=True)
-        return BigramTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
-                               label_smoothing=label_smoothing, dropout=self.entity_dropout, relation_dropout=self.relation_dropout,
-                               seed=self.dropout_seed, optimizer=optimizer, betas=betas, grad_clip=grad_clip)
 
 
 class BigramPoolingComplexRelationModel(ComplexRelationScorer, BigramPoolingRelationEmbedder):

@@ -15,7 +15,7 @@ import torch
 from . import _native as N
 from .model import ComplexRelationScorer, DistmultRelationScorer, Models
 from .token_encoder import PRECOMPUTE_CHUNK, EncodeFn, EncoderPass, EncoderTrainStep, TokenEncoderEmbedder, bn_grad_pointers
-from .token_pooled import BN_EPS, BN_MOMENTUM
+from .token_embedder import BN_EPS, BN_MOMENTUM
 
 
 class LstmPass(EncoderPass):
@@ -58,16 +58,17 @@ class LSTMSlot:
             return
         self.dW = torch.zeros_like(W)
         self.sumW = torch.zeros_like(W)
-        self.fresh_lstm_grads()
+        self.fresh_grads()
         self.sum_flat = torch.zeros_like(self.d_flat)
         if bn is not None:
-            self.d_bn = torch.zeros(2 * self.d, dtype=torch.float32, device=dev)
-            self.sum_bn = torch.zeros(2 * self.d, dtype=torch.float32, device=dev)
+            self.sum_bn = torch.zeros_like(self.d_bn)
 
-    def fresh_lstm_grads(self):
-        """d_flat: one zeroed gradient buffer; dlstm: the four LSTM tensors' gradients as views of it"""
+    def fresh_grads(self):
+        """d_flat: one zeroed gradient buffer; dlstm: the four LSTM tensors' gradients as views of it; d_bn ([w | b])"""
         self.d_flat = torch.zeros(sum(p.numel() for p in self.lstm), dtype=torch.float32, device=self.W.device)
         self.dlstm = [g.view_as(p) for g, p in zip(self.d_flat.split([p.numel() for p in self.lstm]), self.lstm)]
+        if self.bn is not None:
+            self.d_bn = torch.zeros_like(self.bn)
 
     def encoder_grads(self):
         dl = [torch.empty_like(p) for p in self.lstm]
@@ -144,14 +145,13 @@ class LSTMRelationEmbedder(TokenEncoderEmbedder):
     """openkge/model.py:912-998.  Implemented: normalize None|''|'batchnorm', dropout / entity_dropout / relation_dropout
     (Philox masks), slot sizes up to 512; not implemented (raise at construction): encoder_activiation, project_relation,
     sparse, relation_slot_size != entity_slot_size.  Training: LSTMTrainStep (fused, own dense Adagrad) or
-    trainer.AddLossModule (autograd bridge: any torch optimizer over the module's parameters).  The evaluation surface
-    (precompute_embeddings_from_tokens, get_all_* / get_*, prefix scores, loss_only) is the token-pooled embedder's."""
+    trainer.AddLossModule (autograd bridge: any torch optimizer over the module's parameters)."""
 
     what, _train_step_class = "LSTM", LSTMTrainStep
 
     def __init__(self, entity_slot_size, relation_slot_size, train_data, dropout=0.0, entity_dropout=None, relation_dropout=None,
                  encoder_activiation=None, sparse=False, init_std=0.1, normalize='', project_relation=False, seed=0):
-        torch.nn.Module.__init__(self)
+        super().__init__()
         relation_slot_size = self._refuse_unsupported(entity_slot_size, relation_slot_size, encoder_activiation, project_relation, sparse)
         if normalize not in (None, '', 'batchnorm'):
             raise NotImplementedError(f"normalize={normalize!r}")
@@ -189,9 +189,9 @@ class LSTMRelationEmbedder(TokenEncoderEmbedder):
         return PRECOMPUTE_CHUNK                        # (this module's: a test shrinks it)
 
     # -- AddLossModule / autograd bridge (the reference Trainer's path: trainer.py:142, 206-234) ---------------------
-    def _lstm_slots(self, flat):
-        """the two slots over the module's parameters; flat: the four LSTM tensors of each slot become views of one flat
-        buffer (one optimizer segment)"""
+    def _train_slots(self, flat=True):
+        """the two slots over the module's parameters; flat (train_step()): the four LSTM tensors of each slot become views
+        of one flat buffer (one optimizer segment)"""
         slots = []
         for relation in (False, True):
             emb, tok, lstm, bn = self._parts(relation)
@@ -207,19 +207,10 @@ class LSTMRelationEmbedder(TokenEncoderEmbedder):
     def autograd_step(self, loss, label_smoothing):
         """the cached LSTMTrainStep behind AddLossModule: shares the module's parameters; its optimizer is NOT used (the
         caller's torch optimizer steps the module parameters)"""
-        st = self._cached_autograd_step(loss, label_smoothing, lambda: self._lstm_slots(flat=False))
+        st = self._cached_autograd_step(loss, label_smoothing, lambda: self._train_slots(flat=False))
         for sl, relation in ((st.entity, False), (st.relation, True)):
-            emb, tok, lstm, bn = self._parts(relation)
-            sl.lstm = [q.data for q in self._lstm_tensors(lstm)]             # (a torch optimizer may have replaced nothing, but
-            sl.dW = torch.zeros_like(sl.W)                                     #  the gradient buffers went to autograd: fresh ones)
-            sl.fresh_lstm_grads()
-            if bn is not None:                                                 # the module's parameters may have been stepped outside
-                sl.bn[:sl.d].copy_(bn.weight.data)
-                sl.bn[sl.d:].copy_(bn.bias.data)
-                sl.d_bn = torch.zeros_like(sl.d_bn)
-        st.steps = self.dropout_step
-        self.dropout_step += 1
-        return st
+            sl.lstm = [q.data for q in self._lstm_tensors(self._parts(relation)[2])]
+        return self._refresh_autograd_step(st)
 
     def autograd_params_and_grads(self, st):
         params, grads = [self.entity_embedding.weight, self.relation_embedding.weight], [st.entity.dW, st.relation.dW]
@@ -243,18 +234,6 @@ class LSTMRelationEmbedder(TokenEncoderEmbedder):
         if bn is not None:
             out += [(bn.weight, (sl.bn, sl.sum_bn), 0), (bn.bias, (sl.bn, sl.sum_bn), sl.d)]
         return out
-
-    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
-                   grad_clip=0.0):
-        """The training driver for this model: shares the module's parameters (updated in place).  The four LSTM tensors of
-        each slot become views of one flat buffer (one optimizer segment).  optimizer / betas / grad_clip: as on FusedTrainStep."""
-        slots = self._lstm_slots(flat=True)
-        st = LSTMTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
-                           label_smoothing=label_smoothing, dropout=self.entity_dropout, relation_dropout=self.relation_dropout,
-                           seed=self.dropout_seed, optimizer=optimizer, betas=betas, grad_clip=grad_clip)
-        if self.entity_batchnorm is not None:
-            st.module_batchnorms = ((slots[0], self.entity_batchnorm), (slots[1], self.relation_batchnorm))
-        return st
 
 
 class LSTMComplexRelationModel(ComplexRelationScorer, LSTMRelationEmbedder):

@@ -16,8 +16,7 @@ import torch
 from . import _native as N
 from . import hotpath as H
 from . import virtual_tables as VT
-from .step_optim import state_views
-from .token_pooled import BN_EPS, BN_MOMENTUM, UnigramPoolingRelationEmbedder, token_id_matrix
+from .token_embedder import TokenBasedRelationEmbedder
 
 MAX_SLOT = 512                                     # the fused tile kernels' largest slot size
 PRECOMPUTE_CHUNK = 16384                           # rows per encode call of precompute_embeddings_from_tokens
@@ -102,9 +101,6 @@ class EncoderTrainStep(VT.VirtualTableStep):
         """the slots' optimizer_tensors(); every=False: without those of a slot the scorer leaves unused"""
         return [t for sl in (self.entity, self.relation) if every or not self._unused(sl) for t in sl.optimizer_tensors()]
 
-    def _unused(self, sl):
-        return False
-
     def flush(self):
         """(no deferred updates here: every parameter is current after every step)"""
 
@@ -158,68 +154,13 @@ class EncodeFn(torch.autograd.Function):
         return (None, None, None, dW, *grad_list, *bn_grads)
 
 
-class TokenEncoderEmbedder(UnigramPoolingRelationEmbedder):
-    """The plumbing of an embedder whose rows come from an EncoderPass.  A subclass brings the constructor (through
-    _refuse_unsupported and _init_token_tables), _parts(relation) -> (embedding, token ids, encoder module, batch-norm),
-    _params(relation), _slot(relation) -> a slot over the module's current parameters without gradient buffers,
-    _train_step_class and what the autograd bridge needs.  The evaluation surface (get_all_* / get_*, prefix scores,
-    loss_only) is the token-pooled embedder's."""
+class TokenEncoderEmbedder(TokenBasedRelationEmbedder):
+    """A token embedder whose rows come from an EncoderPass: _encode, the chunked precompute.  A subclass brings the
+    constructor (through _refuse_unsupported, _init_token_tables and _init_state), _parts(relation), _params(relation),
+    _slot(relation) -> a slot over the module's current parameters without gradient buffers, _precompute_chunk() -> its
+    module's PRECOMPUTE_CHUNK, and what the base class asks of every token embedder for the training bridges."""
 
-    what = None
-
-    @staticmethod
-    def _precompute_chunk():
-        return PRECOMPUTE_CHUNK
-
-    def _refuse_unsupported(self, entity_slot_size, relation_slot_size, encoder_activiation, project_relation, sparse):
-        """the options no token encoder implements; -> the relation slot size"""
-        if relation_slot_size is None or relation_slot_size <= 0:
-            relation_slot_size = entity_slot_size
-        if encoder_activiation is not None:    # (the LSTM reference applies a module class to a tensor, model.py:976-977)
-            raise NotImplementedError(f"encoder_activiation is not implemented for the {self.what} embedder")
-        if project_relation:
-            raise NotImplementedError(f"project_relation is not implemented for the {self.what} embedder")
-        if sparse:
-            raise NotImplementedError(f"sparse gradients are not implemented for the {self.what} embedder")
-        if relation_slot_size != entity_slot_size:
-            raise NotImplementedError("unequal slot sizes: the relation slot size must equal the entity slot size")
-        if entity_slot_size > MAX_SLOT:
-            raise NotImplementedError(f"{self.what} slot sizes above {MAX_SLOT}")
-        return relation_slot_size
-
-    @staticmethod
-    def _max_lengths(train_data):
-        max_len = train_data.max_length
-        return (max_len, max_len) if isinstance(max_len, int) else (max_len[0], max_len[1])
-
-    def _init_token_tables(self, train_data, d, normalize, init_std):
-        """The reference's constructor order (TokenBasedRelationEmbedder.__init__, model.py:568-634): token-id matrices,
-        embeddings, batch-norm modules with uniform_ weights, then the embeddings' normal_ -- the same torch.manual_seed
-        gives bit-identical initial parameters."""
-        e_len, r_len = self._max_lengths(train_data)
-        self.train_data, self.slot_size, self.relation_slot_size, self.normalize = train_data, d, d, normalize
-        self.register_buffer('entity_token_ids', token_id_matrix(train_data.entity_id_to_tokens_map, e_len))
-        self.register_buffer('relation_token_ids', token_id_matrix(train_data.relation_id_to_tokens_map, r_len))
-        self.entity_embedding = torch.nn.Embedding(train_data.entity_tokens_size, d, padding_idx=0)
-        self.relation_embedding = torch.nn.Embedding(train_data.relation_tokens_size, d, padding_idx=0)
-        self.entity_batchnorm = self.relation_batchnorm = None
-        if normalize == 'batchnorm':
-            self.entity_batchnorm = torch.nn.BatchNorm1d(d, momentum=BN_MOMENTUM, eps=BN_EPS)
-            self.relation_batchnorm = torch.nn.BatchNorm1d(d, momentum=BN_MOMENTUM, eps=BN_EPS)
-            torch.nn.init.uniform_(self.entity_batchnorm.weight)
-            torch.nn.init.uniform_(self.relation_batchnorm.weight)
-        torch.nn.init.normal_(self.entity_embedding.weight.data, std=init_std)          # row 0 included
-        torch.nn.init.normal_(self.relation_embedding.weight.data, std=init_std)
-
-    def _init_state(self, dropout, entity_dropout, relation_dropout, seed):
-        """after the encoder modules: dropout fall-backs (model.py:845-846, :953-954) and the embedder's own state"""
-        self.entity_dropout = entity_dropout if entity_dropout else dropout
-        self.relation_dropout = relation_dropout if relation_dropout else dropout
-        self.entity_projection = self.relation_projection = None
-        self.entity_embedding_from_tokens = self.relations_embedding_from_tokens = None
-        self.dropout_seed, self.dropout_step = seed, 0
-        self._pool_engine = self._engine = None
-        self._steps = []
+    max_slot = MAX_SLOT
 
     def _encode(self, ids, relation, stream):
         """the encoder (batch statistics in training mode, running statistics otherwise) -> dropout"""
@@ -250,7 +191,7 @@ class TokenEncoderEmbedder(UnigramPoolingRelationEmbedder):
     def precompute_embeddings_from_tokens(self):
         """model.py:670-712 (the reference encodes 4096 rows per call; in eval mode any chunk size gives the same rows)"""
         if self.entity_embedding_from_tokens is None:
-            torch.nn.Module.train(self, False)         # the reference calls self.eval() here and stays in eval mode
+            super().train(False)                       # the reference calls self.eval() here and stays in eval mode
             dev = self.entity_embedding.weight.device
             chunk = self._precompute_chunk()
 
@@ -264,26 +205,3 @@ class TokenEncoderEmbedder(UnigramPoolingRelationEmbedder):
             with torch.no_grad():
                 self.entity_embedding_from_tokens = table(self.train_data.entities_size, False)
                 self.relations_embedding_from_tokens = table(self.train_data.relations_size, True)
-
-    def optimizer_params_and_state(self, st):
-        """For checkpoint.py, as the token-pooled embedder's: the subclass says in _state_segments(slot, relation) ->
-        [(parameter, (step tensor, its Adagrad accumulator), offset into them)] which part of which flat buffer is whose; a slot
-        the scorer leaves unused (bias_entity) is listed as not moved."""
-        found = {}
-        for sl, relation in ((st.entity, False), (st.relation, True)):
-            moved = not st._unused(sl)
-            for p, (buf, acc), offset in self._state_segments(sl, relation):
-                found[p] = (state_views(st.optimizer_state_of(buf, acc), offset, p), moved)
-        return [(p,) + found[p] for p in self.parameters()], st.adam_word()
-
-    def _cached_autograd_step(self, loss, label_smoothing, make_slots):
-        """the cached train step behind AddLossModule (trainer.py:142, 206-234): rebuilt when the loss, the smoothing or the
-        module's tables changed; its optimizer is NOT used (the caller's torch optimizer steps the module parameters)"""
-        st = getattr(self, "_ag_step", None)
-        if st is None or st.loss != loss or st.label_smoothing != label_smoothing or \
-                st.entity.W.data_ptr() != self.entity_embedding.weight.data_ptr():
-            slots = make_slots()
-            st = self._ag_step = self._train_step_class(slots[0], slots[1], self.scorer_name, loss=loss, label_smoothing=label_smoothing,
-                                                        dropout=self.entity_dropout, relation_dropout=self.relation_dropout,
-                                                        seed=self.dropout_seed)
-        return st

@@ -1,5 +1,5 @@
-"""Token-pooled embedder: UnigramPoolingRelationEmbedder + TokenBasedRelationEmbedder
-(openkge/model.py:561-796) over the HIP kernels of csrc/okge_pool.hip, and the training step that drives the fused
+"""Token-pooled embedder: UnigramPoolingRelationEmbedder (openkge/model.py:715-796; its base
+class is token_embedder.py's) over the HIP kernels of csrc/okge_pool.hip, and the training step that drives the fused
 prefix-scoring path on rows computed from tokens.
 
 Design: the pooled (and batch-normed) rows of one batch are written into the two virtual tables of virtual_tables.py (layout
@@ -12,27 +12,18 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
+from typing import NamedTuple
 
 import torch
 
 from . import _native as N
 from . import hotpath as H
 from . import virtual_tables as VT
-from .model import ComplexRelationScorer, DistmultRelationScorer, Models, RelationEmbedder
-from .step_optim import state_views
+from .model import ComplexRelationScorer, DistmultRelationScorer, Models
+from .token_embedder import BN_EPS, BN_MOMENTUM, TokenBasedRelationEmbedder, token_id_matrix  # noqa: F401  (token_id_matrix: re-exported)
 
 POOLS = {"sum": 0, "mean": 1, "max": 2}
-BN_EPS, BN_MOMENTUM = 1e-5, 0.1                     # torch.nn.BatchNorm1d(momentum=0.1, eps=1e-5), model.py:611-612
-
-
-def token_id_matrix(id_to_tokens_map, max_len, device="cpu"):
-    """TokenBasedRelationEmbedder.__init__ (model.py:579-597): row i = the LAST max_len tokens of item i,
-    right-padded with 0."""
-    out = torch.zeros((len(id_to_tokens_map), max_len), dtype=torch.int32)
-    for i, seq in enumerate(id_to_tokens_map):
-        tail = list(seq)[-max_len:]
-        out[i, :len(tail)] = torch.tensor(tail, dtype=torch.int32)
-    return out.to(device)
 
 
 class TokenSlot:
@@ -40,7 +31,9 @@ class TokenSlot:
 
     bn_calls = 0      # training-mode batch-norm encode calls of a train step since VirtualTableStep.sync_module (host count)
 
-    def __init__(self, W, token_ids, pool="sum", batchnorm=False, bn_weight=None, bn_bias=None):
+    def __init__(self, W, token_ids, pool="sum", batchnorm=False, bn_weight=None, bn_bias=None, running=None, view=False):
+        """running: (mean, var) to share (a module's buffers), None: fresh ones; view: a slot to encode with: no gradient,
+        accumulator or touched-row buffers"""
         self.W, self.token_ids, self.pool = W, token_ids.to(torch.int32).contiguous(), pool
         d, dev = W.shape[1], W.device
         self.d = d
@@ -50,10 +43,13 @@ class TokenSlot:
             self.bn = torch.empty(2 * d, dtype=torch.float32, device=dev)
             self.bn[:d] = torch.rand(d) if bn_weight is None else bn_weight        # init.uniform_(weight), model.py:613
             self.bn[d:] = 0.0 if bn_bias is None else bn_bias
-            self.running_mean = torch.zeros(d, dtype=torch.float32, device=dev)
-            self.running_var = torch.ones(d, dtype=torch.float32, device=dev)
-            self.d_bn = torch.zeros(2 * d, dtype=torch.float32, device=dev)
-            self.sum_bn = torch.zeros(2 * d, dtype=torch.float32, device=dev)
+            self.running_mean, self.running_var = running if running is not None else \
+                (torch.zeros(d, dtype=torch.float32, device=dev), torch.ones(d, dtype=torch.float32, device=dev))
+        if view:
+            return
+        if batchnorm:
+            self.sum_bn = torch.zeros_like(self.bn)
+        self.fresh_grads()
         self.dW = torch.zeros_like(W)
         self.sumW = torch.zeros_like(W)
         # touched-row map of dW for the optimizer sweep: the pooling backward stamps every row it writes, okge_adagrad_multi
@@ -65,6 +61,16 @@ class TokenSlot:
 
     def next_stamp(self):
         self.stamp = self.stamp % 255 + 1
+
+    def fresh_grads(self):
+        """d_bn ([d weight | d bias]): a zeroed buffer of its own"""
+        if self.bn is not None:
+            self.d_bn = torch.zeros_like(self.bn)
+
+    def optimizer_tensors(self):
+        """the token table with the map the pooling backward stamps and the current stamp[, the batch-norm parameters]"""
+        bn = [(self.bn, self.d_bn, self.sum_bn)] if self.bn is not None else []
+        return [(self.W, self.dW, self.sumW, self.touched, self.stamp)] + bn
 
     @property
     def bn_weight(self):
@@ -132,7 +138,6 @@ class PoolEngine:
                                             slot.d_bn[slot.d:].data_ptr() if bn else None, ws.data_ptr(), self._ws_bytes,
                                             self._stream()), "okge_pool_backward")
 
-
     # -- a batch of _encode calls in one go (okge_pool_encode_calls / okge_pool_backward_calls) ----------------------
     def _calls(self, calls, backward):
         """calls: [(slot, ids, first_id, n, raw, out_or_d_out, saved)] with n > 0 -> (ctypes array, keep-alive list)"""
@@ -149,9 +154,8 @@ class PoolEngine:
                 x.d_out, x.dW = other.data_ptr(), slot.dW.data_ptr()
                 if slot.bn is not None:
                     x.d_bn_weight, x.d_bn_bias = slot.d_bn[:slot.d].data_ptr(), slot.d_bn[slot.d:].data_ptr()
-                touched = getattr(slot, "touched", None)
-                if touched is not None:
-                    x.row_touched, x.touched_stamp = touched.data_ptr(), int(slot.stamp)
+                if slot.touched is not None:
+                    x.row_touched, x.touched_stamp = slot.touched.data_ptr(), int(slot.stamp)
             else:
                 x.out = other.data_ptr()
             need += int(self.lib.okge_pool_workspace_bytes(int(n), slot.d))
@@ -203,16 +207,36 @@ class PoolEngine:
         del keep
 
 
+class EncodeCall(NamedTuple):
+    """One of the five encode calls of a step (TokenPooledTrainStep._encode) with its views of the virtual tables: ids (int32,
+    or None: the range from `first`), raw = the pooled rows, out = the finished rows (behind the batch-norm; `raw` itself
+    without one), d_out = their gradients, saved = the call's batch-norm statistics (4 * d) or None."""
+    slot: TokenSlot
+    ids: object
+    first: int
+    n: int
+    raw: torch.Tensor
+    out: torch.Tensor
+    d_out: torch.Tensor
+    saved: object
+
+    def forward(self):                    # as PoolEngine.encode_calls / catch_up_calls take it
+        return self[:6] + self[7:]
+
+    def backward(self):                   # as PoolEngine.backward_calls takes it
+        return self[:5] + self[6:]
+
+
 class TokenPooledTrainStep(VT.VirtualTableStep):
     """forward + loss + backward + Adagrad for UnigramPooling{Complex,Distmult}RelationModel
     (Trainer.compute_one_batch, trainer.py:181-257, over model.py:762-796)."""
 
     def __init__(self, entity: TokenSlot, relation: TokenSlot, scorer, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8,
-                 label_smoothing=0.0, dropout=0.0, seed=0, engine=None, decay_window=None, optimizer="adagrad", betas=(0.9, 0.999),
-                 grad_clip=0.0):
+                 label_smoothing=0.0, dropout=0.0, relation_dropout=None, seed=0, engine=None, decay_window=None, optimizer="adagrad",
+                 betas=(0.9, 0.999), grad_clip=0.0):
         super().__init__(entity, relation, scorer, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
-                         label_smoothing=label_smoothing, dropout=dropout, seed=seed, engine=engine, optimizer=optimizer, betas=betas,
-                         grad_clip=grad_clip)
+                         label_smoothing=label_smoothing, dropout=dropout, relation_dropout=relation_dropout, seed=seed, engine=engine,
+                         optimizer=optimizer, betas=betas, grad_clip=grad_clip)
         # optimizer="adam": every row's moments decay every step, so there is no decay-only update to defer -- the window is 1,
         # whatever the table size or OKGE_LAZY_DECAY; the sweep still skips the gradient rows the maps do not stamp
         if self.optimizer == "adam":
@@ -235,13 +259,11 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
             env = os.environ.get("OKGE_LAZY_DECAY")
             big = (entity.W.numel() + relation.W.numel()) * 4 >= (96 << 20)
             decay_window = int(env) if env else (8 if big else 1)
-        lazy_ok = all(getattr(sl, "row_steps", None) is not None and getattr(sl, "touched", None) is not None for sl in (entity, relation))
+        lazy_ok = all(sl.row_steps is not None and sl.touched is not None for sl in (entity, relation))
         self.decay_window = max(1, int(decay_window)) if lazy_ok else 1
         self._counters = torch.zeros(2, dtype=torch.int32, device=entity.W.device)      # [optimizer steps taken, scratch]
         self._pending = None              # (lr, weight_decay, eps) of the deferred steps; None: every row is current
         self.pool = PoolEngine(self.device)
-        # (rounds 1-2 ran the five encode / backward calls of a step one by one, the relation slot's on a side stream:
-        #  35 small launches; they now go to the library as ONE batch each way: three launches forward, three backward)
         self.saved = torch.zeros((5, 4 * entity.d), device=self.device)      # batch-norm statistics of the five encode calls
 
     def state_tensors(self):
@@ -256,10 +278,9 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
         return out + self._optimizer_state()
 
     def _param_groups(self, every=False):
-        """token tables (with the maps the pooling backward stamps) + batch-norm parameters"""
-        e, r = self.entity, self.relation
-        return [(sl.W, sl.dW, sl.sumW, getattr(sl, "touched", None), getattr(sl, "stamp", 0)) for sl in (e, r)] + \
-            [(sl.bn, sl.d_bn, sl.sum_bn) for sl in (e, r) if sl.bn is not None]
+        """both token tables (with the maps the pooling backward stamps), then both slots' batch-norm parameters"""
+        e, r = self.entity.optimizer_tensors(), self.relation.optimizer_tensors()
+        return [e[0], r[0]] + e[1:] + r[1:]
 
     # -- deferred weight-decay-only updates (decay_window > 1) ---------------------------------------------------------
     def _hparams(self):
@@ -331,14 +352,14 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
         EV, EX, dEV, RV, RX, dRV = bufs
         ent, rel, pe = self.entity, self.relation, self.pool
         # the reference's encode order: candidates, (po rel, po obj), (sp subj, sp rel)   -- trainer.py:75-91
-        # calls: (slot, ids, first id, n, raw rows, batch-normed rows, row gradients, saved statistics)
         calls = []
         for (relation, ids, first, rows), sv in zip(VT.encode_calls(batch), self.saved.unbind(0)):
             sl, X, V, dV = (rel, RX, RV, dRV) if relation else (ent, EX, EV, dEV)
-            calls.append((sl, H._i32(ids, dev), first, rows.stop - rows.start, X[rows], V[rows], dV[rows], sv if sl.bn is not None else None))
+            raw, bn = X[rows], sl.bn is not None
+            calls.append(EncodeCall(sl, H._i32(ids, dev), first, rows.stop - rows.start, raw, V[rows] if bn else raw, dV[rows], sv if bn else None))
         # forward of all five calls: raw pooled rows -> EX / RX, batch-normed rows -> EV / RV (per-call statistics, running
         # statistics updated in this order)
-        enc_calls = [(c_[0], c_[1], c_[2], c_[3], c_[4], c_[5] if c_[0].bn is not None else c_[4], c_[7]) for c_ in calls]
+        enc_calls = [c.forward() for c in calls]
         if self.decay_window > 1:
             # the token rows this batch names take the decay-only steps they owe before the forward reads them (always
             # launched: a captured graph must hold it; with nothing pending it reads the batch's step counters and ends)
@@ -346,14 +367,14 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
             lr, wd, eps = self._hparams()
             pe.catch_up_calls(enc_calls, self.engine.lazy_tensors(self._lazy_tables()), self._counters, lr, wd, eps)
         pe.encode_calls(enc_calls, True)
-        for c_ in calls:
-            if c_[3] > 0 and c_[0].bn is not None:
-                c_[0].bn_calls += 1
+        for c in calls:
+            if c.n > 0 and c.slot.bn is not None:
+                c.slot.bn_calls += 1
         return calls
 
     def _backward(self, batch, bufs, calls):
         """dEV / dRV -> batch-norm and pooling backward of the five calls -> the slots' dW, d_bn ([d weight | d bias])"""
-        self.pool.backward_calls([(c_[0], c_[1], c_[2], c_[3], c_[4], c_[6], c_[7]) for c_ in calls])
+        self.pool.backward_calls([c.backward() for c in calls])
 
     def mark_sparse_rows(self, index, rows):
         """sharded.ReplicaStep wrote other replicas' gradient rows into a sparse gradient (grad_tensors()[index]): stamp them"""
@@ -362,20 +383,19 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
             sl.touched.index_fill_(0, rows.reshape(-1).long(), sl.stamp)
 
     def optimizer_step(self):
-        eng, e, r = self.engine, self.entity, self.relation
+        groups = self._param_groups()
         if self.decay_window > 1:
             # stamped rows: what they owe + this step with their gradient; one row in decay_window of the others: what they
             # owe + this step; batch-norm parameters: dense; the device step counter moves on (okge_adagrad_lazy)
             self._settle_hparams()
             lr, wd, eps = self._hparams()
-            tensors = self._lazy_tables() + [(sl.bn, sl.d_bn, sl.sum_bn) for sl in (e, r) if sl.bn is not None]
-            self._clip(self._param_groups())          # (only stamped rows carry a gradient: the deferred rows are not its business)
-            eng.adagrad_lazy(tensors, self._counters, self.decay_window, False, lr, wd, eps)
+            self._clip(groups)                        # (only stamped rows carry a gradient: the deferred rows are not its business)
+            self.engine.adagrad_lazy(self._lazy_tables() + groups[2:], self._counters, self.decay_window, False, lr, wd, eps)
             self._pending = (lr, wd, eps)
             self._after_update()
             return
         # one launch: token tables (gradient rows the backward did not stamp are neither read nor cleared) + batch-norm parameters
-        self._update(self._param_groups())
+        self._update(groups)
         self._after_update()
 
     def _after_update(self):
@@ -387,76 +407,38 @@ class TokenPooledTrainStep(VT.VirtualTableStep):
 # ------------------------------------------------------------------------------------------------------------------
 # API-compatible model classes (inference protocol; training goes through TokenPooledTrainStep)
 # ------------------------------------------------------------------------------------------------------------------
-def _flush_before_state_dict(module, prefix, keep_vars):
-    module.flush_steps()
-
-
-class UnigramPoolingRelationEmbedder(RelationEmbedder):
-    """openkge/model.py:561-796.  Implemented: pool sum|mean|max, normalize None|'batchnorm', dropout; not implemented
+class UnigramPoolingRelationEmbedder(TokenBasedRelationEmbedder):
+    """openkge/model.py:715-796.  Implemented: pool sum|mean|max, normalize None|'batchnorm', dropout; not implemented
     (raise): normalize='norm', activation, project_relation, sparse gradients.  Training: TokenPooledTrainStep (fused, own
     Adagrad) or trainer.AddLossModule (autograd bridge: any torch optimizer over the module's parameters)."""
+
+    what, _train_step_class = "token-pooled", TokenPooledTrainStep
 
     def __init__(self, entity_slot_size, relation_slot_size, train_data, pool='sum', normalize=None, dropout=0.0,
                  entity_dropout=None, relation_dropout=None, sparse=False, init_std=0.01, activation=None,
                  project_relation=False, seed=0):
         super().__init__()
-        if normalize not in (None, 'batchnorm') or activation is not None or project_relation or sparse:
-            raise NotImplementedError("token-pooled path implements pool sum/mean/max with optional batchnorm only")
-        if relation_slot_size is None or relation_slot_size <= 0:
-            relation_slot_size = entity_slot_size
-        if relation_slot_size != entity_slot_size:
-            raise NotImplementedError("relation slot size must equal the entity slot size without a relation projection")
-        self.train_data, self.slot_size, self.pool, self.normalize = train_data, entity_slot_size, pool, normalize
-        self.entity_dropout = entity_dropout if entity_dropout else dropout            # model.py:757-758
-        self.relation_dropout = relation_dropout if relation_dropout else dropout
-        self.register_buffer('entity_token_ids', token_id_matrix(train_data.entity_id_to_tokens_map, train_data.max_length[0]))
-        self.register_buffer('relation_token_ids', token_id_matrix(train_data.relation_id_to_tokens_map, train_data.max_length[1]))
-        self.entity_embedding = torch.nn.Embedding(train_data.entity_tokens_size, entity_slot_size, padding_idx=0)
-        self.relation_embedding = torch.nn.Embedding(train_data.relation_tokens_size, entity_slot_size, padding_idx=0)
-        torch.nn.init.normal_(self.entity_embedding.weight.data, std=init_std)         # model.py:660-661 (row 0 included)
-        torch.nn.init.normal_(self.relation_embedding.weight.data, std=init_std)
-        self.entity_batchnorm = self.relation_batchnorm = None
-        if normalize == 'batchnorm':
-            self.entity_batchnorm = torch.nn.BatchNorm1d(entity_slot_size, momentum=BN_MOMENTUM, eps=BN_EPS)
-            self.relation_batchnorm = torch.nn.BatchNorm1d(entity_slot_size, momentum=BN_MOMENTUM, eps=BN_EPS)
-            torch.nn.init.uniform_(self.entity_batchnorm.weight)
-            torch.nn.init.uniform_(self.relation_batchnorm.weight)
-        self.entity_projection = self.relation_projection = None                      # the attribute model.py:789 reads
-        self.entity_embedding_from_tokens = self.relations_embedding_from_tokens = None
-        self.dropout_seed, self.dropout_step = seed, 0
-        self._pool_engine = self._engine = None
-        # training drivers that update this module's parameters in place (train_step()): token rows no batch named may owe
-        # decay-only Adagrad steps (TokenPooledTrainStep.decay_window) -- every reader below settles them first
-        self._steps = []
-        self.register_state_dict_pre_hook(_flush_before_state_dict)
-
-    def __getstate__(self):                              # (weak references do not pickle; a copy starts without drivers)
-        state = self.__dict__.copy()
-        state["_steps"] = []
-        return state
-
-    def flush_steps(self):
-        for ref in self._steps:
-            st = ref()
-            if st is not None:
-                st.flush()
+        self._refuse_unsupported(entity_slot_size, relation_slot_size, activation, project_relation, sparse)
+        if normalize not in (None, 'batchnorm'):
+            raise NotImplementedError(f"normalize={normalize!r}: the token-pooled embedder implements None and 'batchnorm'")
+        self.pool = pool
+        self._init_token_tables(train_data, entity_slot_size, normalize, init_std)
+        self._init_state(dropout, entity_dropout, relation_dropout, seed)
+        self._pool_engine = None
 
     # -- plumbing ----------------------------------------------------------------------------------------------
-    def engine(self):
+    def _pool(self):
         dev = self.entity_embedding.weight.device
-        if self._engine is None or self._engine.device != dev:
-            self._engine, self._pool_engine = H.HotPath(dev), PoolEngine(dev)
-        return self._engine
+        if self._pool_engine is None or self._pool_engine.device != dev:
+            self._pool_engine = PoolEngine(dev)
+        return self._pool_engine
 
-    def _slot(self, relation):
-        emb, tok, bn = (self.relation_embedding, self.relation_token_ids, self.relation_batchnorm) if relation else \
-            (self.entity_embedding, self.entity_token_ids, self.entity_batchnorm)
-        s = TokenSlot.__new__(TokenSlot)
-        s.W, s.token_ids, s.pool, s.d, s.bn = emb.weight.data, tok, self.pool, self.slot_size, None
-        if bn is not None:
-            s.bn = torch.cat([bn.weight.data, bn.bias.data])
-            s.running_mean, s.running_var = bn.running_mean, bn.running_var
-        return s
+    def _slot(self, relation, view=True):
+        """a slot over the module's parameters (the table and the running statistics are the module's own tensors, the
+        batch-norm parameters a copy); view: one to encode with"""
+        emb, tok, _, bn = self._parts(relation)
+        bn_args = () if bn is None else (True, bn.weight.data, bn.bias.data, (bn.running_mean, bn.running_var))
+        return TokenSlot(emb.weight.data, tok, self.pool, *bn_args, view=view)
 
     def _encode(self, ids, relation, stream):
         """pool -> batch-norm (batch statistics in training mode, running statistics otherwise) -> dropout -> (n,1,d)"""
@@ -464,8 +446,7 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
         self.flush_steps()
         ids = ids.reshape(-1).to(torch.int32).contiguous()
         n, d = ids.numel(), self.slot_size
-        emb, tok, bn = (self.relation_embedding, self.relation_token_ids, self.relation_batchnorm) if relation else \
-            (self.entity_embedding, self.entity_token_ids, self.entity_batchnorm)
+        emb, tok, _, bn = self._parts(relation)
         p = (self.relation_dropout if relation else self.entity_dropout) if self.training else 0.0
         if torch.is_grad_enabled() and (emb.weight.requires_grad or (bn is not None and bn.weight.requires_grad)):
             # called with gradients enabled outside AddLossModule (a caller's own loss): the reference's op sequence in
@@ -489,26 +470,13 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
         raw = torch.empty((n, d), device=ids.device)
         out = torch.empty_like(raw) if slot.bn is not None else raw
         saved = torch.empty(4 * d, device=ids.device) if slot.bn is not None else None
-        self._pool_engine.encode(slot, ids, 0, n, self.training, raw, out, saved)
+        self._pool().encode(slot, ids, 0, n, self.training, raw, out, saved)
         if p > 0:
             out = eng.encode_rows(out, None, 0, n, H.DropoutSpec(p, self.dropout_seed, stream, self.dropout_step))
         return out.unsqueeze(1)
 
-    def encode_subj(self, subj):
-        return self._encode(subj, False, H.STREAM_SP_ENT)
-
-    def encode_obj(self, obj):
-        return self._encode(obj, False, H.STREAM_PO_ENT)
-
-    def encode_rel(self, rel):
-        return self._encode(rel, True, H.STREAM_SP_REL)
-
-    # -- TokenBasedRelationEmbedder: tables precomputed from tokens (model.py:624-712) -----------------------------
-    def train(self, mode=True):
-        self.entity_embedding_from_tokens = self.relations_embedding_from_tokens = None
-        return super().train(mode)
-
     def precompute_embeddings_from_tokens(self):
+        """model.py:670-712, each table in one encode call"""
         if self.entity_embedding_from_tokens is None:
             super().train(False)                       # the reference calls self.eval() here and stays in eval mode
             dev = self.entity_embedding.weight.device
@@ -517,81 +485,15 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
                 self.entity_embedding_from_tokens = self._encode(ar(self.train_data.entities_size), False, H.STREAM_CAND).squeeze(1)
                 self.relations_embedding_from_tokens = self._encode(ar(self.train_data.relations_size), True, H.STREAM_SP_REL).squeeze(1)
 
-    def get_all_subj(self):
-        self.precompute_embeddings_from_tokens()
-        return self.entity_embedding_from_tokens[self.train_data.min_entities_size:]
-
-    get_all_obj = get_all_subj
-
-    def get_all_rel(self):
-        self.precompute_embeddings_from_tokens()
-        return self.relations_embedding_from_tokens[self.train_data.min_entities_size:]        # sic, model.py:630
-
-    def get_subj(self, subj):
-        self.precompute_embeddings_from_tokens()
-        return self.entity_embedding_from_tokens[subj].unsqueeze(0)
-
-    get_obj = get_subj
-
-    def get_rel(self, rel):
-        self.precompute_embeddings_from_tokens()
-        return self.relations_embedding_from_tokens[rel]
-
-    def get_slot_size(self):
-        return self.slot_size
-
-    # -- prefix scoring: RelationScorer.sp_prefix_score / po_prefix_score (model.py:52-74) ------------------------------
-    def _prefix_score(self, batch: H.PrefixBatch, many=None):
-        if many is None:
-            many = self.get_all_obj()
-        if batch.sp_subj is not None:
-            return self._score(self.encode_subj(batch.sp_subj), self.encode_rel(batch.sp_rel), many, prefix=True, sp=True, po=False)
-        return self._score(many, self.encode_rel(batch.po_rel), self.encode_obj(batch.po_obj), prefix=True, sp=False, po=True)
-
-    # -- top-k prediction over the tables precomputed from tokens (RelationScorer.sp_prefix_topk / po_prefix_topk) -------
-    def _any_dropout(self):
-        return max(self.entity_dropout or 0.0, self.relation_dropout or 0.0) > 0
-
-    def _prefix_topk(self, batch: H.PrefixBatch, k, filt_ptr, filt_col):
-        self.precompute_embeddings_from_tokens()
-        E, R = self.entity_embedding_from_tokens, self.relations_embedding_from_tokens
-        if batch.cand_ids is None:
-            batch.cand_first = self.train_data.min_entities_size
-            batch.n_cand = E.shape[0] - batch.cand_first
-        scores, cols, ids = self.engine().topk_prefixes(E.contiguous(), R.contiguous(), self.scorer_name, batch, k, filt_ptr, filt_col)
-        return scores, ids, cols
-
-    # -- AddLossModule / autograd bridge (the reference Trainer's path: trainer.py:142, 206-234) ---------------------
-    def _module_slots(self):
-        slots = []
-        for emb, tok, bn in ((self.entity_embedding, self.entity_token_ids, self.entity_batchnorm),
-                             (self.relation_embedding, self.relation_token_ids, self.relation_batchnorm)):
-            s = TokenSlot(emb.weight.data, tok, self.pool, bn is not None, None if bn is None else bn.weight.data,
-                          None if bn is None else bn.bias.data)
-            if bn is not None:
-                s.running_mean, s.running_var = bn.running_mean, bn.running_var
-            slots.append(s)
-        return slots
+    # -- the training bridges (TokenBasedRelationEmbedder) ---------------------------------------------------------------
+    def _train_slots(self):
+        return [self._slot(False, view=False), self._slot(True, view=False)]
 
     def autograd_step(self, loss, label_smoothing):
         """the cached TokenPooledTrainStep behind AddLossModule: shares the module's parameters; its optimizer is NOT used
-        (the caller's torch optimizer steps the module parameters)"""
+        (the caller's torch optimizer steps the module parameters: it moves every row every step, so decay_window = 1)"""
         self.flush_steps()
-        st = getattr(self, "_ag_step", None)
-        if st is None or st.loss != loss or st.label_smoothing != label_smoothing or st.entity.W.data_ptr() != self.entity_embedding.weight.data_ptr():
-            e, r = self._module_slots()
-            # (decay_window = 1: this step's own optimizer never runs -- the caller's torch optimizer moves every row every step)
-            st = self._ag_step = TokenPooledTrainStep(e, r, self.scorer_name, loss=loss, label_smoothing=label_smoothing,
-                                                      dropout=self.entity_dropout, seed=self.dropout_seed, decay_window=1)
-        for sl, bn in ((st.entity, self.entity_batchnorm), (st.relation, self.relation_batchnorm)):
-            sl.dW = torch.zeros_like(sl.W)                        # fresh gradient buffers: the last ones went to autograd
-            if bn is not None:                                     # the module's parameters may have been stepped outside
-                sl.bn[:sl.d].copy_(bn.weight.data)
-                sl.bn[sl.d:].copy_(bn.bias.data)
-                sl.d_bn = torch.zeros_like(sl.d_bn)
-        st.steps = self.dropout_step
-        self.dropout_step += 1
-        return st
+        return self._refresh_autograd_step(self._cached_autograd_step(loss, label_smoothing, self._train_slots, decay_window=1))
 
     def autograd_params_and_grads(self, st):
         params, grads = [self.entity_embedding.weight, self.relation_embedding.weight], [st.entity.dW, st.relation.dW]
@@ -601,52 +503,21 @@ class UnigramPoolingRelationEmbedder(RelationEmbedder):
                 grads += [sl.d_bn[:sl.d], sl.d_bn[sl.d:]]
         return params, grads
 
-    def optimizer_params_and_state(self, st):
-        """For checkpoint.py, `st` = the driver train_step() returned: ([(parameter, views of the step's optimizer state that
-        belong to it -- (sum,) under Adagrad, (exp_avg, exp_avg_sq) under Adam, each of the parameter's shape --, whether the step
-        moves it), ...] in self.parameters() order, the Adam device state word or None)."""
-        found = {}
-        for sl, emb, bn in ((st.entity, self.entity_embedding, self.entity_batchnorm),
-                            (st.relation, self.relation_embedding, self.relation_batchnorm)):
-            found[emb.weight] = state_views(st.optimizer_state_of(sl.W, sl.sumW), 0, emb.weight)
-            if bn is not None:
-                states = st.optimizer_state_of(sl.bn, sl.sum_bn)                 # [weight | bias]
-                found[bn.weight], found[bn.bias] = state_views(states, 0, bn.weight), state_views(states, sl.d, bn.bias)
-        return [(p, found[p], True) for p in self.parameters()], st.adam_word()
+    def _state_segments(self, sl, relation):
+        """optimizer_params_and_state: the token table, then the batch-norm's [weight | bias]"""
+        emb, tok, _, bn = self._parts(relation)
+        out = [(emb.weight, (sl.W, sl.sumW), 0)]
+        if bn is not None:
+            out += [(bn.weight, (sl.bn, sl.sum_bn), 0), (bn.bias, (sl.bn, sl.sum_bn), sl.d)]
+        return out
 
-    def loss_only(self, batch: H.PrefixBatch, loss, label_smoothing, scores=None):
-        """eval-mode loss (+ scores) of AddLossModule: rows encoded with the running statistics, no dropout"""
-        eng, dev = self.engine(), self.entity_embedding.weight.device
-        n_po, n_sp, n_c = batch.n_po, batch.n_sp, batch.n_candidates
-        if batch.cand_ids is None:
-            cand = self.get_all_obj()[batch.cand_first - self.train_data.min_entities_size:][:n_c] if not self.training else \
-                self._encode(torch.arange(batch.cand_first, batch.cand_first + n_c, dtype=torch.int32, device=dev), False, H.STREAM_CAND).squeeze(1)
-        else:
-            cand = self._encode(batch.cand_ids, False, H.STREAM_CAND).squeeze(1)
-        parts_e, parts_r = [cand], []
-        if n_po:
-            parts_r.append(self.encode_rel(batch.po_rel).squeeze(1))
-            parts_e.append(self.encode_obj(batch.po_obj).squeeze(1))
-        if n_sp:
-            parts_e.append(self.encode_subj(batch.sp_subj).squeeze(1))
-            parts_r.append(self.encode_rel(batch.sp_rel).squeeze(1))
-        EV, RV = torch.cat(parts_e).contiguous(), torch.cat(parts_r).contiguous()
-        vb = VT.VirtualTables(dev).batch(n_c, n_po, n_sp, batch.pos_row, batch.pos_col)
-        return eng.forward_backward(EV, RV, self.scorer_name, vb, None, None, loss=loss, label_smoothing=label_smoothing,
-                                    normalizer=1.0, scores=scores, loss_only=True)
-
-    def train_step(self, loss="bce", lr=0.1, weight_decay=1e-10, eps=1e-8, label_smoothing=0.0, optimizer="adagrad", betas=(0.9, 0.999),
-                   grad_clip=0.0):
-        """The training driver for this model: shares the module's parameters (updated in place).  optimizer / betas /
-        grad_clip: as on FusedTrainStep."""
-        self.flush_steps()                 # an earlier driver (another epoch's learning rate, ...) may still owe decay-only steps
-        slots = self._module_slots()
-        st = TokenPooledTrainStep(slots[0], slots[1], self.scorer_name, loss=loss, lr=lr, weight_decay=weight_decay, eps=eps,
-                                  label_smoothing=label_smoothing, dropout=self.entity_dropout, seed=self.dropout_seed,
-                                  optimizer=optimizer, betas=betas, grad_clip=grad_clip)
-        if self.entity_batchnorm is not None:
-            st.module_batchnorms = ((slots[0], self.entity_batchnorm), (slots[1], self.relation_batchnorm))
-        import weakref
+    def train_step(self, *args, **kwargs):
+        """TokenBasedRelationEmbedder.train_step.  Token rows no batch named may owe decay-only Adagrad steps
+        (TokenPooledTrainStep.decay_window): an earlier driver (another epoch's learning rate, ...) settles them before this one
+        is built, and the module keeps a weak reference to every driver, so that everything that reads the parameters
+        (flush_steps(): _encode, state_dict) settles them first."""
+        self.flush_steps()
+        st = super().train_step(*args, **kwargs)
         self._steps = [r for r in self._steps if r() is not None] + [weakref.ref(st)]
         return st
 

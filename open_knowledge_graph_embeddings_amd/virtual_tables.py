@@ -117,6 +117,10 @@ class VirtualTableStep(StepOptimizer):
         self._backward(batch, bufs, saved)
         return self.loss_out
 
+    def _unused(self, sl):
+        """whether the scorer leaves this slot out of the score (its parameters then have no gradient and do not move)"""
+        return False
+
     def _sync_module_batchnorms(self):
         """after an optimizer step: keep an attached nn.Module's batch-norm parameters current"""
         for sl, bn in self.module_batchnorms:

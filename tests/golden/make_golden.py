@@ -27,6 +27,8 @@ Vectors:
                   AddLossModule forward + backward -> loss, outputs, token-table / batch-norm gradients, running
                   stats; eval-mode precompute_embeddings_from_tokens.  The reference class lacks the attribute
                   `entity_projection` it reads (model.py:789); the harness sets it to None on the instance.
+  g9_unigram_init_*  the seeded constructor of the token-pooled models (ComplEx / DistMult, normalize None / 'batchnorm'):
+                  parameter names in order, initial parameters, state_dict keys, token-id matrices
   g10_fb15k237    the FIRST 512-prefix evaluation batch of FB15k-237 valid.txt as the reference's dataset + collate
                   produce it, scored / trained / ranked by the reference at the full BASELINE size (|E|=14543, d=200):
                   ids, label / filter coordinates and answer groups, a score slice, per-row score sums, loss,
@@ -618,6 +620,42 @@ def g9():
         save(f"g9_unigram_{name}", **kw)
 
 
+def g9_init():
+    """g9_unigram_init_*: what the reference's constructor leaves after torch.manual_seed -- parameter names in order, every
+    initial parameter, state_dict keys, token-id matrices.  The reference registers no Unigram DistMult model: the harness
+    composes one from the reference's own DistmultRelationScorer and UnigramPoolingRelationEmbedder (the scorer has no
+    parameters and no constructor; the embedder's constructor is what runs)."""
+    import openkge.model as RM
+    distmult = type("UnigramPoolingDistmultRelationModel", (RM.DistmultRelationScorer, RM.UnigramPoolingRelationEmbedder), {})
+    n_ent, n_rel, d, vt_e, vt_r, max_len = 20, 5, 8, 14, 9, (4, 3)
+    flat = lambda m: (np.array([t for row in m for t in row], np.int32), np.cumsum([0] + [len(r) for r in m]).astype(np.int64))  # noqa: E731
+    for ci, (name, cls, normalize) in enumerate([("complex_none", Models.UnigramPoolingComplexRelationModel, None),
+                                                  ("complex_bn", Models.UnigramPoolingComplexRelationModel, "batchnorm"),
+                                                  ("distmult_none", distmult, None), ("distmult_bn", distmult, "batchnorm")]):
+        rng = np.random.default_rng(950 + ci)
+        def token_map(n, vocab):
+            out = [[1], [1]]                                 # reserved ids 0, 1 (dataset.py:200-201)
+            for _ in range(2, n):
+                k = int(rng.integers(0, 5))                  # some longer than max_length: the tail is kept
+                out.append([2] + rng.integers(4, vocab, size=k).tolist() + [3])
+            return tuple(out)
+        md = meta(n_ent, n_rel)
+        md.entity_id_to_tokens_map, md.relation_id_to_tokens_map = token_map(n_ent, vt_e), token_map(n_rel, vt_r)
+        md.entity_tokens_size, md.relation_tokens_size, md.max_length = vt_e, vt_r, max_len
+        torch.manual_seed(950 + ci)
+        m = cls(entity_slot_size=d, relation_slot_size=d, train_data=md, pool="sum", normalize=normalize, dropout=0.0, sparse=False,
+                init_std=0.3)
+        kw = dict(model=cls.__name__, seed=np.int64(950 + ci), d=np.int64(d), normalize=str(normalize), max_len=np.asarray(max_len, np.int64),
+                  n_ent=np.int64(n_ent), n_rel=np.int64(n_rel), vt_e=np.int64(vt_e), vt_r=np.int64(vt_r),
+                  param_names=np.array([k for k, _ in m.named_parameters()]), state_keys=np.array(list(m.state_dict().keys())),
+                  ent_tokens=npy(m.entity_token_ids).astype(np.int32), rel_tokens=npy(m.relation_token_ids).astype(np.int32))
+        kw["ent_map"], kw["ent_map_off"] = flat(md.entity_id_to_tokens_map)
+        kw["rel_map"], kw["rel_map_off"] = flat(md.relation_id_to_tokens_map)
+        for k, p in m.named_parameters():
+            kw["init/" + k] = npy(p).copy()
+        save(f"g9_unigram_init_{name}", **kw)
+
+
 # ----------------------------------------------------------------------------------------------
 # G10: full-size FB15k-237 batch through the reference
 # ----------------------------------------------------------------------------------------------
@@ -1205,7 +1243,7 @@ def g16():
 
 if __name__ == "__main__":
     only = sys.argv[1:]                      # e.g. `make_golden.py g1_triples` regenerates one family
-    for fn in (g1, g1_triples, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16):
+    for fn in (g1, g1_triples, g2, g3, g4, g5, g6, g7, g8, g9, g9_init, g10, g11, g12, g13, g14, g15, g16):
         if fn is g12 and any(a.startswith("g12:") for a in only):    # `make_golden.py g12:all_noshare`: one case of the family
             fn(tuple(a[4:] for a in only if a.startswith("g12:")))
         elif not only or fn.__name__ in only:

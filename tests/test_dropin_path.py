@@ -136,7 +136,7 @@ def test_addloss_gradient_scale_follows_the_upstream_gradient(okge_lib, factor):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", golden_names("g9_unigram_"))
+@pytest.mark.parametrize("name", [n for n in golden_names("g9_unigram_") if "_init_" not in n])
 def test_addloss_on_token_pooled_models(okge_lib, name):
     """AddLossModule + autograd on UnigramPoolingComplexRelationModel: the reference Trainer's own path, vs the
     reference's loss / outputs / parameter gradients (G9)"""

@@ -354,7 +354,7 @@ def unigram_bn(z, which):
                 running_mean=np.zeros(d, np.float32), running_var=np.ones(d, np.float32))
 
 
-@pytest.mark.parametrize("name", golden_names("g9_unigram_"))
+@pytest.mark.parametrize("name", [n for n in golden_names("g9_unigram_") if "_init_" not in n])
 def test_g9_unigram_oracle_matches_reference(name):
     z = golden(name)
     po = (z["po_rel"], z["po_obj"]) if "po_rel" in z.files else None
