@@ -179,6 +179,24 @@ int okge_score_prefixes(const okge_tables *t, const okge_prefix_batch *batch, co
  *               own scratch plus the gathered rows, (N + 2 B) x d floats.  Feed the rows to okge_adagrad_rows with the
  *               occurrence ids [cand ids | po_obj | sp_subj] and [po_rel | sp_rel]. */
 #define OKGE_TRAIN_ROW_GRADS 32
+/*               OKGE_TRAIN_FREEZE_ENTITIES -- the entity table is not trained (the reference's resume_freeze,
+ *               trainer.py:532-536: requires_grad = False on entity_embedding.weight).  dE may be NULL: it is neither read,
+ *               cleared nor written, candidate rows and prefix entity rows alike.  The candidate-gradient product dC = G^T . Q is
+ *               not computed: the tile kernels run an instantiation without it (no product, no write-back, no dc_reduce launch),
+ *               the wide path skips its G^T . Q GEMM and the scatter of its rows.  Loss, G and dQ are those of the unfrozen call
+ *               bit for bit, and so is dR wherever the unfrozen call's dR is order-free (OKGE_TRAIN_DISTINCT_PREFIX_ROWS).
+ *               OKGE_TRAIN_FREEZE_RELATIONS -- the relation table is not trained: dR may be NULL and is not touched; the prefix
+ *               backward writes the prefix entities' rows of dE only.  The tile launch is the ordinary one; dE is the unfrozen
+ *               call's wherever that is order-free (a candidate range or OKGE_TRAIN_UNIQUE_CANDIDATES, with
+ *               OKGE_TRAIN_DISTINCT_PREFIX_ROWS).
+ *               Both flags apply to the dense call (tile kernels up to slot size 512, the wide path up to 4096) on the ComplEx /
+ *               DistMult scorers.  Both together: OKGE_ERR_INVALID (nothing to train).  Either with OKGE_TRAIN_ROW_GRADS or a
+ *               data-bias scorer: OKGE_ERR_UNSUPPORTED.  With OKGE_TRAIN_LOSS_ONLY they change nothing.  With
+ *               OKGE_TRAIN_CLEAR_GRADS only the trained table's buffer is cleared.  The workspace is that of the unfrozen call.
+ *               okge_train_tiles and okge_n3_forward_backward do not know these flags.  A zero gradient is no substitute: the
+ *               optimizer's weight decay and eps still move the table ("The untouched slot"). */
+#define OKGE_TRAIN_FREEZE_ENTITIES 64
+#define OKGE_TRAIN_FREEZE_RELATIONS 128
 int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *batch,
                                 const okge_candidates *cand, const okge_positives *pos,
                                 int32_t loss_kind, float label_smoothing, double normalizer, int32_t flags,

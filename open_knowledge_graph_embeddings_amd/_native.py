@@ -27,6 +27,8 @@ OKGE_TRAIN_UNIQUE_CANDIDATES = 4
 OKGE_TRAIN_DISTINCT_PREFIX_ROWS = 8
 OKGE_TRAIN_CLEAR_GRADS = 16
 OKGE_TRAIN_ROW_GRADS = 32
+OKGE_TRAIN_FREEZE_ENTITIES = 64
+OKGE_TRAIN_FREEZE_RELATIONS = 128
 OKGE_ROWS_STORE, OKGE_ROWS_ACCUMULATE = 0, 1       # okge_rows_to_dense's mode
 SCORERS = {"complex": OKGE_COMPLEX, "distmult": OKGE_DISTMULT, "bias_relation": OKGE_BIAS_RELATION,
            "bias_entity": OKGE_BIAS_ENTITY}

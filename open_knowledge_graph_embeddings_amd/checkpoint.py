@@ -46,8 +46,24 @@ def _is_adam(step):
     return getattr(step, "optimizer", "adagrad") == "adam"
 
 
+def _frozen(step):
+    """None, or the table a FusedTrainStep(freeze=...) does not train: "entities" / "relations" """
+    return getattr(step, "freeze", None)
+
+
+def freeze_names(freeze_param, loaded):
+    """the reference's `freeze_param` (Trainer.load_state_dict, trainer.py:532-536): a list of parameter names, or ["True"] for
+    every loaded name -> the names of `loaded` to freeze.  None / not a list / empty: none"""
+    if type(freeze_param) is not list or not freeze_param:
+        return []
+    if type(freeze_param[0]) is str and freeze_param[0] == "True":
+        return list(loaded)
+    return [name for name in loaded if name in freeze_param]
+
+
 def _full_tables(step):
-    """(E, R, sumE, sumR) as full tables, whatever the step class; an Adam step: (E, R, mE, vE, mR, vR)."""
+    """(E, R, sumE, sumR) as full tables, whatever the step class; an Adam step: (E, R, mE, vE, mR, vR).  A frozen table's
+    missing state comes as None."""
     if _is_adam(step):
         return step.E, step.R, step.mE, step.vE, step.mR, step.vR
     if hasattr(step, "flush"):                                    # deferred weight decay: rows may owe decay-only steps
@@ -64,13 +80,17 @@ def to_reference_checkpoint(step, epoch=0, training_steps=None):
     optimizer "Adam" -- which torch.optim.Adam.load_state_dict takes as it is."""
     if _is_adam(step):
         return _adam_checkpoint(step, epoch, training_steps)
-    E, R, sumE, sumR = (t.detach().cpu().clone() for t in _full_tables(step))
+    E, R, sumE, sumR = (None if t is None else t.detach().cpu().clone() for t in _full_tables(step))
     n_steps = float(step.steps)
+    # a frozen table (FusedTrainStep(freeze=...)): the `sum` the step holds for it, untouched -- zeros where it never had one,
+    # torch.optim.Adagrad's initial state -- and the step count of a parameter that never had a gradient
+    steps_e, steps_r = (0.0 if _frozen(step) == "entities" else n_steps), (0.0 if _frozen(step) == "relations" else n_steps)
+    sumE, sumR = (torch.zeros_like(E) if sumE is None else sumE), (torch.zeros_like(R) if sumR is None else sumR)
     group = {"lr": step.lr, "betas": (0.9, 0.999), "eps": step.eps, "weight_decay": step.weight_decay, "amsgrad": False,
              "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
              "decoupled_weight_decay": False, "lr_decay": 0, "initial_accumulator_value": 0, "params": [0, 1]}
-    optimizer_state = {"state": {0: {"step": torch.tensor(n_steps), "sum": sumE},
-                                 1: {"step": torch.tensor(n_steps), "sum": sumR}},
+    optimizer_state = {"state": {0: {"step": torch.tensor(steps_e), "sum": sumE},
+                                 1: {"step": torch.tensor(steps_r), "sum": sumR}},
                        "param_groups": [group]}
     regime = [{"optimizer": "Adagrad", "epoch": 0, "lr": step.lr, "weight_decay": step.weight_decay}]
     return {"epoch": int(epoch), "training_steps": int(step.steps if training_steps is None else training_steps),
@@ -80,7 +100,7 @@ def to_reference_checkpoint(step, epoch=0, training_steps=None):
 
 
 def _adam_checkpoint(step, epoch, training_steps):
-    E, R, mE, vE, mR, vR = (t.detach().cpu().clone() for t in _full_tables(step))
+    E, R, mE, vE, mR, vR = (None if t is None else t.detach().cpu().clone() for t in _full_tables(step))
     t = float(step.adam_t)
     group = {"lr": step.lr, "betas": tuple(step.betas), "eps": step.eps, "weight_decay": step.weight_decay, "amsgrad": False,
              "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
@@ -88,6 +108,8 @@ def _adam_checkpoint(step, epoch, training_steps):
     optimizer_state = {"state": {0: {"step": torch.tensor(t), "exp_avg": mE, "exp_avg_sq": vE},
                                  1: {"step": torch.tensor(t), "exp_avg": mR, "exp_avg_sq": vR}},
                        "param_groups": [group]}
+    if _frozen(step) is not None:     # torch.optim.Adam creates a parameter's state at its first step: a frozen one has no entry
+        del optimizer_state["state"][0 if _frozen(step) == "entities" else 1]
     regime = [{"optimizer": "Adam", "epoch": 0, "lr": step.lr, "weight_decay": step.weight_decay}]
     return {"epoch": int(epoch), "training_steps": int(step.steps if training_steps is None else training_steps),
             "state_dict": {ENTITY_KEY: E, RELATION_KEY: R},
@@ -98,7 +120,8 @@ def _adam_checkpoint(step, epoch, training_steps):
 def _checkpoint_optimizer(ckpt):
     """'adam' / 'adagrad': what the state entries of the first parameter say (the regime's name where there is no state yet)"""
     reg = ckpt["optimizer_state_dict"][0]
-    st0 = reg["optimizer_state"]["state"].get(0, {})
+    states = reg["optimizer_state"]["state"]
+    st0 = states.get(0) or states.get(1, {})            # (an Adam run with the entity table frozen holds no entry 0)
     if "exp_avg" in st0:
         return "adam"
     if "sum" in st0:
@@ -115,14 +138,23 @@ def save_checkpoint(path, step, epoch=0, training_steps=None):
     return ckpt
 
 
-def load_reference_checkpoint(step, ckpt_or_path, reset_optimizer=False):
+def load_reference_checkpoint(step, ckpt_or_path, reset_optimizer=False, freeze_param=None):
     """Load tables (and, unless `reset_optimizer`, the Adagrad accumulators and step count -- the reference's
-    `Trainer.load(reset_optimizer=...)` switch, trainer.py:561-605) into a fused / sharded train step."""
+    `Trainer.load(reset_optimizer=...)` switch, trainer.py:561-605) into a fused / sharded train step.
+    freeze_param (the reference's resume_freeze, trainer.py:532-536): a list of parameter names, or ["True"] for every loaded
+    one.  `entity_embedding.weight` / `relation_embedding.weight` set the step's `freeze` (FusedTrainStep.set_freeze) before the
+    state is loaded; naming both raises ValueError (nothing to train), a step class without `set_freeze` NotImplementedError."""
     ckpt = ckpt_or_path
     if not isinstance(ckpt, dict):
         ckpt = torch.load(ckpt_or_path, map_location="cpu", weights_only=True)
     sd = ckpt["state_dict"]
     E, R = sd[ENTITY_KEY], sd[RELATION_KEY]
+    names = freeze_names(freeze_param, (ENTITY_KEY, RELATION_KEY))
+    if len(names) == 2:
+        raise ValueError(f"freeze_param {freeze_param!r} names both tables of a bare train step: nothing is left to train")
+    if names and not hasattr(step, "set_freeze"):
+        raise NotImplementedError(f"{type(step).__name__} cannot freeze a table: freeze_param is built for the single-device "
+                                  f"FusedTrainStep")
     lo, hi = (step.ent_lo, step.ent_hi) if hasattr(step, "ent_lo") else (0, E.shape[0])
     if E[lo:hi].shape != step.E.shape or R.shape != step.R.shape:
         raise ValueError(f"checkpoint tables {tuple(E.shape)}, {tuple(R.shape)} do not fit this model")
@@ -131,6 +163,8 @@ def load_reference_checkpoint(step, ckpt_or_path, reset_optimizer=False):
         if want != have:
             raise ValueError(f"the checkpoint holds {have} optimizer state and this step trains with {want}: its accumulators do "
                              f"not carry over -- load with reset_optimizer=True to take the tables alone")
+    if names:                                                     # (every refusal is behind us)
+        step.set_freeze("entities" if names[0] == ENTITY_KEY else "relations")
     if hasattr(step, "flush"):                                    # deferred weight decay: no row may owe steps to the loaded tables
         step.flush()
     step.E.copy_(E[lo:hi])
@@ -138,41 +172,56 @@ def load_reference_checkpoint(step, ckpt_or_path, reset_optimizer=False):
     if _is_adam(step):
         _load_adam_state(step, None if reset_optimizer else ckpt["optimizer_state_dict"][0]["optimizer_state"], ckpt)
     elif reset_optimizer:
-        step.sumE.zero_()
-        step.sumR.zero_()
+        for s in (step.sumE, step.sumR):
+            if s is not None:
+                s.zero_()
         step.steps = 0
     else:
         st = ckpt["optimizer_state_dict"][0]["optimizer_state"]
         group, state = st["param_groups"][0], st["state"]
-        step.sumE.copy_(state[0]["sum"][lo:hi])
-        step.sumR.copy_(state[1]["sum"])
-        step.steps = int(float(state[0]["step"]))
+        if _frozen(step) is not None:
+            # the frozen table's `sum` is carried along untouched; the step count is the trained table's
+            for name, idx, table in (("sumE", 0, step.E), ("sumR", 1, step.R)):
+                if getattr(step, name) is None:
+                    setattr(step, name, torch.empty_like(table))
+                getattr(step, name).copy_(state[idx]["sum"])
+            step.steps = int(float(state[1 if _frozen(step) == "entities" else 0]["step"]))
+        else:
+            step.sumE.copy_(state[0]["sum"][lo:hi])
+            step.sumR.copy_(state[1]["sum"])
+            # (the larger count: a file written by a frozen run holds `step` 0 for the table that never had a gradient, and the
+            #  dropout masks are keyed by the step count)
+            step.steps = int(max(float(state[0]["step"]), float(state[1]["step"])))
         step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
         if float(group.get("lr_decay", 0)) != 0 or float(group.get("initial_accumulator_value", 0)) != 0:
             raise NotImplementedError("Adagrad lr_decay / initial_accumulator_value are not used by the reference configs")
-    if step.dE is not None:                                       # (the row-sparse step keeps no dense gradients)
-        step.dE.zero_()
-        step.dR.zero_()
+    for g in (step.dE, step.dR):                                  # (the row-sparse step keeps no dense gradients, a frozen table none)
+        if g is not None:
+            g.zero_()
     return ckpt
 
 
 def _load_adam_state(step, st, ckpt):
     """moments, t and hyper-parameters of an Adam step from torch.optim.Adam's state (None: reset -- zero moments, t = 0)"""
-    if st is None or 0 not in st["state"]:                       # (a torch optimizer that has not stepped yet holds no state)
+    trained = [i for i, name in ((0, "entities"), (1, "relations")) if _frozen(step) != name]      # (a frozen table has no state)
+    if st is None or trained[0] not in st["state"]:              # (a torch optimizer that has not stepped yet holds no state)
         for x in (step.mE, step.vE, step.mR, step.vR):
-            x.zero_()
+            if x is not None:
+                x.zero_()
         step.set_adam_t(0)
         step.steps = 0
         return
     group, state = st["param_groups"][0], st["state"]
     if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
         raise NotImplementedError("amsgrad, maximize and decoupled weight decay (AdamW) are not implemented")
-    step.mE.copy_(state[0]["exp_avg"])
-    step.vE.copy_(state[0]["exp_avg_sq"])
-    step.mR.copy_(state[1]["exp_avg"])
-    step.vR.copy_(state[1]["exp_avg_sq"])
-    step.set_adam_t(int(float(state[0]["step"])))
-    step.steps = int(ckpt.get("training_steps", int(float(state[0]["step"]))))
+    if 0 in trained:
+        step.mE.copy_(state[0]["exp_avg"])
+        step.vE.copy_(state[0]["exp_avg_sq"])
+    if 1 in trained:
+        step.mR.copy_(state[1]["exp_avg"])
+        step.vR.copy_(state[1]["exp_avg_sq"])
+    step.set_adam_t(int(float(state[trained[0]]["step"])))
+    step.steps = int(ckpt.get("training_steps", int(float(state[trained[0]]["step"]))))
     step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
     step.betas = (float(group["betas"][0]), float(group["betas"][1]))
 
@@ -273,15 +322,30 @@ def _check_model_checkpoint(model, step, entries, ckpt, reset_optimizer):
         raise NotImplementedError("amsgrad, maximize and decoupled weight decay (AdamW) are not implemented")
 
 
-def load_model_checkpoint(model, step, ckpt_or_path, reset_optimizer=False):
+def load_model_checkpoint(model, step, ckpt_or_path, reset_optimizer=False, freeze_param=None):
     """Load what model_checkpoint or the reference's `Trainer.save` wrote into `model` and its driver `step`, so that the next
     step() continues the run.  reset_optimizer (the reference's `Trainer.load(reset_optimizer=...)` switch): the state_dict
     alone is taken; accumulators / moments, the Adam step count and the step counter start from zero, the step keeps its own
-    hyper-parameters.  Without the "okge" key (a file the reference wrote) the step counter is the file's training_steps."""
-    entries, word = _model_and_step(model, step)
+    hyper-parameters.  Without the "okge" key (a file the reference wrote) the step counter is the file's training_steps.
+    freeze_param (the reference's resume_freeze, trainer.py:532-536; a list of parameter names, or ["True"] for every loaded
+    one): with step=None -- a module trained through AddLossModule and a torch / Okge optimizer, which keeps its own state --
+    the state_dict is loaded into the module and the named parameters get requires_grad = False, which AddLossModule reads on
+    every call.  The fused drivers of the token-encoded, Tucker3 and lookup-variant models train every tensor they hold: a
+    driver together with a non-empty freeze_param raises NotImplementedError before anything is written."""
     ckpt = ckpt_or_path
     if not isinstance(ckpt, dict):
         ckpt = torch.load(ckpt_or_path, map_location="cpu", weights_only=True)
+    if step is None:
+        own = dict(model.named_parameters())
+        model.load_state_dict(ckpt["state_dict"])
+        for name in freeze_names(freeze_param, [k for k in ckpt["state_dict"] if k in own]):
+            own[name].requires_grad = False
+        return ckpt
+    if freeze_names(freeze_param, list(ckpt["state_dict"])):
+        raise NotImplementedError(f"load_model_checkpoint(freeze_param=...): {type(step).__name__} trains every tensor it holds; "
+                                  f"frozen parameters are built for the lookup models (FusedTrainStep(freeze=...), or step=None "
+                                  f"and AddLossModule)")
+    entries, word = _model_and_step(model, step)
     _check_model_checkpoint(model, step, entries, ckpt, reset_optimizer)
     step.flush()                                                 # no row may owe decay-only steps to the loaded tables
     model.load_state_dict(ckpt["state_dict"])

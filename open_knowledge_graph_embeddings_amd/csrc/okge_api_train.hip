@@ -217,12 +217,17 @@ int check_topk(int32_t k, const okge_prefix_batch *b, const okge_candidates *c, 
 }
 
 // ---- what the training step shares between the tile kernels (train_core) and the wide path (wide_core) ----------------------
+// OKGE_TRAIN_FREEZE_ENTITIES / _RELATIONS: the table that is not trained.  The entry point hands the cores a null dE / dR with
+// the flag; with FREEZE_ENTITIES the candidate-gradient product and everything that only serves it is left out
+constexpr int32_t FREEZE_FLAGS = OKGE_TRAIN_FREEZE_ENTITIES | OKGE_TRAIN_FREEZE_RELATIONS;
+bool entities_frozen(int32_t flags) { return (flags & OKGE_TRAIN_FREEZE_ENTITIES) != 0 && !(flags & OKGE_TRAIN_LOSS_ONLY); }
+
 int check_train(const okge_candidates *cand, const okge_positives *pos, int32_t loss_kind, int32_t flags, const double *loss_out,
                 const float *dE, double normalizer, const float *scores, int64_t ld_scores)
 {
     if (!pos || pos->nnz < 0 || (pos->nnz > 0 && (!pos->col || !pos->row))) return fail(OKGE_ERR_INVALID, "bad positives");
     if (loss_kind != OKGE_LOSS_BCE && loss_kind != OKGE_LOSS_KL) return fail(OKGE_ERR_INVALID, "unknown loss");
-    if (!loss_out || (!(flags & OKGE_TRAIN_LOSS_ONLY) && !dE)) return fail(OKGE_ERR_INVALID, "null output");
+    if (!loss_out || (!(flags & (OKGE_TRAIN_LOSS_ONLY | OKGE_TRAIN_FREEZE_ENTITIES)) && !dE)) return fail(OKGE_ERR_INVALID, "null output");
     if (cand->table) return fail(OKGE_ERR_INVALID, "training needs candidates from the entity table");
     if (!(normalizer > 0)) return fail(OKGE_ERR_INVALID, "normalizer must be positive");
     if (scores && ld_scores < cand->n) return fail(OKGE_ERR_INVALID, "bad scores buffer");
@@ -241,12 +246,16 @@ int train_clears(ClearSpec &clr, const ClearSpec **clear, int32_t &flags, bool k
     clr = {};
     const bool clear_grads = (flags & OKGE_TRAIN_CLEAR_GRADS) != 0 && !(flags & OKGE_TRAIN_LOSS_ONLY);
     if (clear_grads) {
-        if (cand->ids || sh || !dR) return fail(OKGE_ERR_INVALID, "OKGE_TRAIN_CLEAR_GRADS needs a contiguous candidate range on an unsharded table");
+        if (cand->ids || sh || (!dR && !(flags & OKGE_TRAIN_FREEZE_RELATIONS)))
+            return fail(OKGE_ERR_INVALID, "OKGE_TRAIN_CLEAR_GRADS needs a contiguous candidate range on an unsharded table");
         flags |= OKGE_TRAIN_GRADS_ZERO;
         const int64_t d64 = t->d, hi = (int64_t)cand->first_id + cand->n;
-        clr.p[0] = dR;                      clr.n[0] = (int64_t)t->n_rel * d64;
-        clr.p[1] = dE;                      clr.n[1] = (int64_t)cand->first_id * d64;
-        clr.p[2] = dE + hi * d64;           clr.n[2] = ((int64_t)t->n_ent - hi) * d64;
+        // (a frozen table's buffer is null here: nothing of it is cleared)
+        if (dR) { clr.p[0] = dR;            clr.n[0] = (int64_t)t->n_rel * d64; }
+        if (dE) {
+            clr.p[1] = dE;                  clr.n[1] = (int64_t)cand->first_id * d64;
+            clr.p[2] = dE + hi * d64;       clr.n[2] = ((int64_t)t->n_ent - hi) * d64;
+        }
     }
     if (kl) { clr.p[3] = ysum; clr.n[3] = Bpad; }
     *clear = (clear_grads || kl) ? &clr : nullptr;
@@ -386,6 +395,7 @@ int wide_core(const okge_tables *t, const okge_prefix_batch *batch, const okge_c
         a.row_ysum = ysum;
     }
     const int mode = kl ? MODE_TRAIN_KL : MODE_TRAIN_BCE;
+    const bool frozen_e = entities_frozen(flags);
     const bool dropping = cand->drop.p > 0.f;
     const bool slice = !cand->ids && !dropping;              // the range's masked rows ARE a slice of the table
     float *Cm = reinterpret_cast<float *>(ws + l.off_Cm), *dC = reinterpret_cast<float *>(ws + l.off_dC);
@@ -405,14 +415,17 @@ int wide_core(const okge_tables *t, const okge_prefix_batch *batch, const okge_c
             c_op = Cm; ld_c = g.ldq;
         }
         // dC = G^T . Q.  A plain slice on zero gradients: the product's rows ARE the rows of dE
+        // (a frozen entity table: neither the product nor the scatter of its rows)
         const bool direct = slice && a.grads_zero;
-        if (int rc = OKGE_TIMED("wide_dc_gemm", "gemm_f32_kernel<dC>", st,
-                                launch_gemm_f32(true, a.G, pl.ldg, Q, g.ldq, direct ? dE + (size_t)(cand->first_id + n_lo) * t->d : dC,
-                                                direct ? (int64_t)t->d : (int64_t)g.ldq, n_r, t->d, g.B, 1, g.B, 0, st))) return rc;
-        if (!direct)
-            if (int rc = OKGE_TIMED("wide_dc_scatter", "wide_dc_scatter", st,
-                                    launch_wide_dc_scatter(dC, g.ldq, ar.cand_ids, ar.cand_first, n_lo, n_r, t->d, a.drop_c, a.cand_exclusive,
-                                                           a.grads_zero, dE, a.n_table_rows, st))) return rc;
+        if (!frozen_e) {
+            if (int rc = OKGE_TIMED("wide_dc_gemm", "gemm_f32_kernel<dC>", st,
+                                    launch_gemm_f32(true, a.G, pl.ldg, Q, g.ldq, direct ? dE + (size_t)(cand->first_id + n_lo) * t->d : dC,
+                                                    direct ? (int64_t)t->d : (int64_t)g.ldq, n_r, t->d, g.B, 1, g.B, 0, st))) return rc;
+            if (!direct)
+                if (int rc = OKGE_TIMED("wide_dc_scatter", "wide_dc_scatter", st,
+                                        launch_wide_dc_scatter(dC, g.ldq, ar.cand_ids, ar.cand_first, n_lo, n_r, t->d, a.drop_c,
+                                                               a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, st))) return rc;
+        }
         if (int rc = OKGE_TIMED("wide_dq_gemm", "gemm_f32_kernel<dQ>", st,
                                 launch_gemm_f32(false, a.G, pl.ldg, c_op, ld_c, slab, g.ldq, g.B, t->d, n_r, pl.dq_splits, pl.dq_k_per,
                                                 (int64_t)g.Bpad * g.ldq, st))) return rc;
@@ -508,7 +521,10 @@ int train_core(const okge_tables *t, const okge_shard *sh, const okge_prefix_bat
     q.slab = reinterpret_cast<float *>(ws + l.off_slab);
     q.d = g.d; q.KB = g.KB; q.LDK = g.LDK; q.Bpad = g.Bpad; q.ldq = g.ldq; q.ldg = pl.ldg;
     q.nsplit = pl.nsplit;
-    const int mode = kl ? MODE_TRAIN_KL : MODE_TRAIN_BCE;
+    // a frozen entity table: the instantiation without the candidate-gradient product, in the same launch geometry (the loss
+    // partials and G are those of the unfrozen call), and none of the launches that add its partial rows up
+    const bool frozen_e = entities_frozen(flags);
+    const int mode = frozen_e ? (kl ? MODE_TRAIN_KL_NODC : MODE_TRAIN_BCE_NODC) : (kl ? MODE_TRAIN_KL : MODE_TRAIN_BCE);
     for (int r = 0; r < pl.n_ranges; ++r) {
         const RangeCut c = cut_range(pl, r, g.N, NT);
         const int tiles_r = c.tiles;
@@ -534,18 +550,21 @@ int train_core(const okge_tables *t, const okge_shard *sh, const okge_prefix_bat
             }))
             return rc;
         if (loss_only) continue;
-        if (tail_r > 0)
-            if (int rc = OKGE_TIMED("dc_reduce", "dc_reduce", st,
-                                    launch_dc_reduce(a.dC_slab, pl.dc_slabs, pl.dc_slab_rows, g.D16, at.N, g.d, at.cand_ids, at.cand_first,
-                                                     a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err, st))) return rc;
-        if (pl.sk_wgs > 0) {
-            if (int rc = OKGE_TIMED("dc_reduce", "dc_reduce_streamk", st,
-                                    launch_dc_reduce_streamk(a.dC_slab, tiles_r, pl.sk_chunks, pl.sk_wgs, g.D16, ar.N, g.d, cand->ids, cand->first_id,
-                                                             a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err, st))) return rc;
-        } else if (pl.b_split > 1) {                 // (few candidate tiles: always a single range)
-            if (int rc = OKGE_TIMED("dc_reduce", "dc_reduce", st,
-                                    launch_dc_reduce(a.dC_slab, pl.dc_slabs, pl.dc_slab_rows, g.D16, g.N, g.d, cand->ids, cand->first_id,
-                                                     a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err, st))) return rc;
+        if (!frozen_e) {                             // the launches that add partial candidate gradients up
+            if (tail_r > 0)
+                if (int rc = OKGE_TIMED("dc_reduce", "dc_reduce", st,
+                                        launch_dc_reduce(a.dC_slab, pl.dc_slabs, pl.dc_slab_rows, g.D16, at.N, g.d, at.cand_ids, at.cand_first,
+                                                         a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err, st))) return rc;
+            if (pl.sk_wgs > 0) {
+                if (int rc = OKGE_TIMED("dc_reduce", "dc_reduce_streamk", st,
+                                        launch_dc_reduce_streamk(a.dC_slab, tiles_r, pl.sk_chunks, pl.sk_wgs, g.D16, ar.N, g.d, cand->ids,
+                                                                 cand->first_id, a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err,
+                                                                 st))) return rc;
+            } else if (pl.b_split > 1) {             // (few candidate tiles: always a single range)
+                if (int rc = OKGE_TIMED("dc_reduce", "dc_reduce", st,
+                                        launch_dc_reduce(a.dC_slab, pl.dc_slabs, pl.dc_slab_rows, g.D16, g.N, g.d, cand->ids, cand->first_id,
+                                                         a.cand_exclusive, a.grads_zero, dE, a.n_table_rows, a.id_err, st))) return rc;
+            }
         }
         q.N = ar.N;
         q.accumulate = r > 0 ? 1 : 0;           // later ranges add to the slabs of the first
@@ -695,7 +714,18 @@ int okge_train_forward_backward(const okge_tables *t, const okge_prefix_batch *b
                                 void *stream)
 {
     if (int rc = check_common(t, batch, cand, true)) return rc;
-    if (!(flags & OKGE_TRAIN_LOSS_ONLY) && !dR) return fail(OKGE_ERR_INVALID, "null output");
+    if (const int32_t frozen = flags & FREEZE_FLAGS) {       // (statuses first: nothing is launched, no output touched)
+        if (frozen == FREEZE_FLAGS)
+            return fail(OKGE_ERR_INVALID, "OKGE_TRAIN_FREEZE_ENTITIES and OKGE_TRAIN_FREEZE_RELATIONS together leave nothing to train");
+        if (flags & OKGE_TRAIN_ROW_GRADS)
+            return fail(OKGE_ERR_UNSUPPORTED, "OKGE_TRAIN_FREEZE_ENTITIES / OKGE_TRAIN_FREEZE_RELATIONS belong to the dense call of "
+                                              "okge_train_forward_backward: not with OKGE_TRAIN_ROW_GRADS");
+        if (int rc = refuse_bias(t->scorer, "okge_train_forward_backward(OKGE_TRAIN_FREEZE_*)", "the unused slot is already untouched")) return rc;
+        if (flags & OKGE_TRAIN_LOSS_ONLY) flags &= ~FREEZE_FLAGS;                 // (no gradient either way)
+        if (flags & OKGE_TRAIN_FREEZE_ENTITIES) dE = nullptr;                    // the frozen table's buffer is never looked at
+        if (flags & OKGE_TRAIN_FREEZE_RELATIONS) dR = nullptr;
+    }
+    if (!(flags & (OKGE_TRAIN_LOSS_ONLY | OKGE_TRAIN_FREEZE_RELATIONS)) && !dR) return fail(OKGE_ERR_INVALID, "null output");
     if (is_wide(t->d)) {
         if (flags & OKGE_TRAIN_ROW_GRADS)
             return fail(OKGE_ERR_UNSUPPORTED, "OKGE_TRAIN_ROW_GRADS stops at slot size 512: slot sizes 513 to 4096 train with dense gradients");
@@ -809,7 +839,7 @@ int okge_train_tiles(const okge_tables *t, const okge_shard *sh, const float *Q,
     if (!Q || !dQ || B <= 0 || cand->n <= 0) return fail(OKGE_ERR_INVALID, "bad query block / candidates");
     if (int rc = check_local_range(t, cand)) return rc;
     return train_core(t, sh, nullptr, Q, ldq, B, cand, pos, loss_kind, label_smoothing, normalizer, n_cand_global,
-                      flags, loss_out, dE, nullptr, dQ, nullptr, 0, row_lse, workspace, workspace_bytes, stream);
+                      flags & ~FREEZE_FLAGS, loss_out, dE, nullptr, dQ, nullptr, 0, row_lse, workspace, workspace_bytes, stream);
 }
 
 int okge_score_queries(const okge_tables *t, const okge_shard *sh, const float *Q, int64_t ldq, int32_t B,

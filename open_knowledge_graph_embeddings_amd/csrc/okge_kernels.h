@@ -48,7 +48,18 @@ constexpr int POS_CACHE = 512;     // positives of one candidate tile cached in 
 
 enum { MODE_TRAIN_BCE = 0, MODE_SCORE = 1, MODE_STATS = 2, MODE_TRAIN_KL = 3, MODE_COUNT = 4, MODE_TOPK = 5,
        // MODE_COUNT that also leaves, in `stats`, one float2 per (tile, row): the row's validation-loss partial over the tile
-       MODE_COUNT_BCE = 6, MODE_COUNT_KL = 7 };
+       MODE_COUNT_BCE = 6, MODE_COUNT_KL = 7,
+       // the training modes WITHOUT the candidate-gradient product dC = G^T . Q (OKGE_TRAIN_FREEZE_ENTITIES): score, loss and G
+       // as MODE_TRAIN_*, no dC accumulators, no write-back.  Modes of their own, so the MODE_TRAIN_* instantiations are
+       // the kernels they were, names included
+       MODE_TRAIN_BCE_NODC = 8, MODE_TRAIN_KL_NODC = 9 };
+__host__ __device__ constexpr bool mode_trains(int mode)
+{
+    return mode == MODE_TRAIN_BCE || mode == MODE_TRAIN_KL || mode == MODE_TRAIN_BCE_NODC || mode == MODE_TRAIN_KL_NODC;
+}
+__host__ __device__ constexpr bool mode_no_dc(int mode) { return mode == MODE_TRAIN_BCE_NODC || mode == MODE_TRAIN_KL_NODC; }
+// the loss a training mode computes, as the mode that loss_element takes
+__host__ __device__ constexpr int mode_loss(int mode) { return mode == MODE_TRAIN_BCE_NODC ? MODE_TRAIN_BCE : mode == MODE_TRAIN_KL_NODC ? MODE_TRAIN_KL : mode; }
 __host__ __device__ constexpr bool mode_counts(int mode) { return mode == MODE_COUNT || mode == MODE_COUNT_BCE || mode == MODE_COUNT_KL; }
 __host__ __device__ constexpr bool mode_count_loss(int mode) { return mode == MODE_COUNT_BCE || mode == MODE_COUNT_KL; }
 enum { LOSS_BCE = 0, LOSS_KL = 1 };

@@ -278,6 +278,10 @@ __global__ __launch_bounds__(256) void dc_reduce_streamk_kernel(const float *__r
     }
 }
 
+// which tables' gradient rows a prefix backward writes: both, or the one that is trained (a frozen table's buffer may be null)
+constexpr int PREFIX_ENT = 1, PREFIX_REL = 2, PREFIX_BOTH = 3;
+
+template <int PARTS = PREFIX_BOTH>
 __global__ __launch_bounds__(128) void prefix_backward_kernel(const float *__restrict__ E, const float *__restrict__ R,
                                                               int d, int scorer, const PrefixDev p,
                                                               const float *__restrict__ slab, int nsplit, int Bpad,
@@ -287,6 +291,8 @@ __global__ __launch_bounds__(128) void prefix_backward_kernel(const float *__res
     // ent_rows (sharded path): the already masked prefix entity rows of ALL prefixes, so every rank forms the full
     // relation gradient; the entity gradient is scattered by the owner only.
     // distinct (OKGE_TRAIN_DISTINCT_PREFIX_ROWS): every prefix id occurs once -- its gradient row is stored, not accumulated
+    // PARTS (OKGE_TRAIN_FREEZE_ENTITIES / _RELATIONS leave one out): the gradient rows that are formed and written
+    constexpr bool want_e = (PARTS & PREFIX_ENT) != 0, want_r = (PARTS & PREFIX_REL) != 0;
     auto put = [&](float *dst, float v) {
         if (distinct) *dst = v;
         else atomicAdd(dst, v);
@@ -298,7 +304,7 @@ __global__ __launch_bounds__(128) void prefix_backward_kernel(const float *__res
     const DropDev &dr = rs.sp ? p.drop_sp_rel : p.drop_po_rel;
     const float *e = ent_rows ? ent_rows + (size_t)b * ldq : E + rs.ent * d, *r = R + rs.rel * d;
     const bool e_masked = ent_rows != nullptr;
-    float *ge = dE + (rs.owned ? rs.ent : 0) * d, *gr = dR + rs.rel * d;
+    float *ge = want_e ? dE + (rs.owned ? rs.ent : 0) * d : nullptr, *gr = want_r ? dR + rs.rel * d : nullptr;
     const size_t split_stride = (size_t)Bpad * ldq;
     const float *sl = slab + (size_t)b * ldq;
     if (scorer == SC_DISTMULT) {
@@ -307,8 +313,8 @@ __global__ __launch_bounds__(128) void prefix_backward_kernel(const float *__res
             for (int sidx = 0; sidx < nsplit; ++sidx) dq += sl[sidx * split_stride + k];
             const float me = drop_mult1(de, rs.pos, k, d), mr = drop_mult1(dr, rs.pos, k, d);
             const float ev = e_masked ? e[k] : e[k] * me, rv = r[k] * mr;
-            if (rs.owned) put(ge + k, dq * rv * me);
-            put(gr + k, dq * ev * mr);
+            if (rs.owned && want_e) put(ge + k, dq * rv * me);
+            if (want_r) put(gr + k, dq * ev * mr);
         }
         return;
     }
@@ -331,12 +337,14 @@ __global__ __launch_bounds__(128) void prefix_backward_kernel(const float *__res
             de1 = q1 * r1 - q2 * r2;  de2 = q1 * r2 + q2 * r1;
             dr1 = q1 * e1 + q2 * e2;  dr2 = q1 * e2 - q2 * e1;
         }
-        if (rs.owned) {
+        if (rs.owned && want_e) {
             put(ge + k, de1 * me1);
             put(ge + h + k, de2 * me2);
         }
-        put(gr + k, dr1 * mr1);
-        put(gr + h + k, dr2 * mr2);
+        if (want_r) {
+            put(gr + k, dr1 * mr1);
+            put(gr + h + k, dr2 * mr2);
+        }
     }
 }
 
@@ -354,7 +362,7 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const double *__restri
 // NB: slab loads kept in flight per lane (8 for the single-device step's 32 split-K slabs; 1 for the sharded step, whose dQ
 // arrives already reduced: 89 instead of 149 registers = 5 instead of 3 waves per SIMD, which is what bounds a launch of
 // 4096 one-row workgroups -- 2.7 rounds of a ~7 us dependent-load chain at 3 waves)
-template <int NB>
+template <int NB, int PARTS = PREFIX_BOTH>
 __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *__restrict__ E, const float *__restrict__ R,
                                                                   int d, int scorer, const PrefixDev p,
                                                                   const float *__restrict__ slab, int nsplit, int Bpad,
@@ -381,8 +389,10 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
     const DropDev &dr = rs.sp ? p.drop_sp_rel : p.drop_po_rel;
     const float *e = ent_rows ? ent_rows + (size_t)b * ldq : E + rs.ent * d, *r = R + rs.rel * d;
     const bool e_masked = ent_rows != nullptr;
-    float *ge = de_rows ? de_rows + (size_t)b * ldq : dE + (rs.owned ? rs.ent : 0) * d;
-    float *gr = dr_rows ? dr_rows + (size_t)b * ldq : dR + rs.rel * d;
+    // PARTS (OKGE_TRAIN_FREEZE_ENTITIES / _RELATIONS leave one out): the gradient rows that are formed and written
+    constexpr bool want_e = (PARTS & PREFIX_ENT) != 0, want_r = (PARTS & PREFIX_REL) != 0;
+    float *ge = de_rows ? de_rows + (size_t)b * ldq : want_e ? dE + (rs.owned ? rs.ent : 0) * d : nullptr;
+    float *gr = dr_rows ? dr_rows + (size_t)b * ldq : want_r ? dR + rs.rel * d : nullptr;
     const size_t split_stride = (size_t)Bpad * ldq;
     const float *sl = slab + (size_t)b * ldq;
     const int s_lo = (nsplit * sq) >> 2, s_hi = (nsplit * (sq + 1)) >> 2;
@@ -438,8 +448,8 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
             const float4 me = mult4(de, nib_e), mr = mult4(dr, nib_r);
             const float4 ev = e_masked ? ev0 : f4mul(ev0, me);
             const float4 rv = f4mul(rv0, mr);
-            if (rs.owned) put(store_e, ge + k, f4mul(f4mul(dq, rv), me), act);
-            put(store_r, gr + k, f4mul(f4mul(dq, ev), mr), act);
+            if (rs.owned && want_e) put(store_e, ge + k, f4mul(f4mul(dq, rv), me), act);
+            if (want_r) put(store_r, gr + k, f4mul(f4mul(dq, ev), mr), act);
         }
         return;
     }
@@ -469,8 +479,8 @@ __global__ __launch_bounds__(128) void prefix_backward_vec_kernel(const float *_
             de1 = f4fma(q1, r1, f4neg(f4mul(q2, r2)));    de2 = f4fma(q1, r2, f4mul(q2, r1));
             dr1 = f4fma(q1, e1, f4mul(q2, e2));           dr2 = f4fma(q1, e2, f4neg(f4mul(q2, e1)));
         }
-        if (rs.owned) put2(store_e, ge + k, h, f4mul(de1, me1), f4mul(de2, me2), act);
-        put2(store_r, gr + k, h, f4mul(dr1, mr1), f4mul(dr2, mr2), act);
+        if (rs.owned && want_e) put2(store_e, ge + k, h, f4mul(de1, me1), f4mul(de2, me2), act);
+        if (want_r) put2(store_r, gr + k, h, f4mul(dr1, mr1), f4mul(dr2, mr2), act);
     }
 }
 
@@ -692,6 +702,9 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
 {
     const int B = p.n_po + p.n_sp;
     if (B <= 0) return hipSuccess;
+    // a null table gradient (OKGE_TRAIN_FREEZE_ENTITIES / _RELATIONS; the entry points that train both refuse one): not formed
+    const int parts = (dE ? PREFIX_ENT : 0) | (dR ? PREFIX_REL : 0);
+    if (parts == 0 || (parts != PREFIX_BOTH && (grad_rows || sc_is_bias(scorer)))) return hipErrorInvalidValue;
     const bool vec = scorer == SC_COMPLEX ? (d % 8 == 0) : (d % 4 == 0);       // (ComplEx: float4 over each half)
     if (vec) {
         // grad_rows: [2][Bpad][ldq] scratch -- relation rows, then entity rows
@@ -703,6 +716,15 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
         if (sc_is_bias(scorer)) {
             if (hipError_t e = launch_bias_prefix_rows(d, scorer, p, slab, nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials,
                                                        n_partials, loss_out, dr_rows, de_rows, distinct, st); e != hipSuccess) return e;
+        } else if (parts != PREFIX_BOTH) {
+            // one table frozen: the instantiation that forms the other table's rows alone (the segmented form is not reached:
+            // a caller with row segments trains both tables)
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(B + 1, chunks), dim3(128), 0, st, E, R, d, scorer, p, slab, nsplit, Bpad, ldq, ent_rows, dE,
+                                   dR, loss_partials, n_partials, loss_out, dr_rows, de_rows, distinct);
+            };
+            if (parts == PREFIX_REL) nsplit >= 8 ? launch(prefix_backward_vec_kernel<8, PREFIX_REL>) : launch(prefix_backward_vec_kernel<1, PREFIX_REL>);
+            else nsplit >= 8 ? launch(prefix_backward_vec_kernel<8, PREFIX_ENT>) : launch(prefix_backward_vec_kernel<1, PREFIX_ENT>);
         } else if (nsplit >= 8)
             hipLaunchKernelGGL(prefix_backward_vec_kernel<8>, dim3(B + 1, chunks), dim3(128), 0, st, E, R, d, scorer, p, slab,
                                nsplit, Bpad, ldq, ent_rows, dE, dR, loss_partials, n_partials, loss_out, dr_rows, de_rows, distinct);
@@ -718,8 +740,14 @@ hipError_t launch_prefix_backward(const float *E, const float *R, int d, int sco
         if (sc_is_bias(scorer)) {
             if (hipError_t e = launch_bias_prefix_rows(d, scorer, p, slab, nsplit, Bpad, ldq, ent_rows, dE, dR, nullptr, 0, nullptr,
                                                        nullptr, nullptr, distinct, st); e != hipSuccess) return e;
-        } else
-            hipLaunchKernelGGL(prefix_backward_kernel, dim3(B), dim3(128), 0, st, E, R, d, scorer, p, slab, nsplit, Bpad, ldq,
+        } else if (parts == PREFIX_REL)
+            hipLaunchKernelGGL(prefix_backward_kernel<PREFIX_REL>, dim3(B), dim3(128), 0, st, E, R, d, scorer, p, slab, nsplit, Bpad, ldq,
+                               ent_rows, dE, dR, distinct);
+        else if (parts == PREFIX_ENT)
+            hipLaunchKernelGGL(prefix_backward_kernel<PREFIX_ENT>, dim3(B), dim3(128), 0, st, E, R, d, scorer, p, slab, nsplit, Bpad, ldq,
+                               ent_rows, dE, dR, distinct);
+        else
+            hipLaunchKernelGGL(prefix_backward_kernel<PREFIX_BOTH>, dim3(B), dim3(128), 0, st, E, R, d, scorer, p, slab, nsplit, Bpad, ldq,
                                ent_rows, dE, dR, distinct);
         if (loss_partials)
             hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, loss_partials, n_partials, loss_out);

@@ -23,6 +23,8 @@
 // The two row halves' dC partial sums are added through LDS in the write-back, which also applies the cached dropout
 // flags.  G is stored UNMASKED: padding rows (b >= B) have zero query rows and candidates n >= N zero candidate rows, so
 // whatever dLoss/dX says there meets a zero in both gradient products and the dQ rows of padding are never read.  G leaves for the dQ kernel from registers as 64x64 transposed blocks Gt[(T * nJ + J)][n_local][b_local].
+// MODE_TRAIN_BCE_NODC / MODE_TRAIN_KL_NODC (OKGE_TRAIN_FREEZE_ENTITIES: the entity table is not trained): the same kernel without
+// the dC product, its accumulators and the write-back -- score, loss, G and the masked candidate rows are the code above.
 #include <cstdio>
 
 #include "okge_device.h"
@@ -97,7 +99,11 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     constexpr int QG = 8;                                       // staging: column groups per row (512 threads / 64 rows)
     constexpr int NOIT = (NO + QG - 1) / QG;
     constexpr int NQ = 4 * KB, NQIT = (NQ + QG - 1) / QG;       // float4 per row
-    static_assert(MODE == MODE_TRAIN_BCE || MODE == MODE_TRAIN_KL, "training kernel");
+    static_assert(mode_trains(MODE), "training kernel");
+    // DC: the candidate-gradient product and its write-back (absent from the MODE_TRAIN_*_NODC instances: a frozen entity table);
+    // LM: the loss of the mode
+    constexpr bool DC = !mode_no_dc(MODE);
+    constexpr int LM = mode_loss(MODE);
     const int d = a.d;
     // GSPLIT: two plane chunks of TGS::CHUNK_CELLS cells; the tile (Cs) and the write-back's second stage are the head of the
     // second, the write-back's first stage (Qs) the head of the first.  To fit 160 KiB beside them this instance keeps its keep
@@ -208,7 +214,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
                 }
                 *reinterpret_cast<v4f *>(Cs + r8 * LDK + k) = v0[it];
                 *reinterpret_cast<v4f *>(Cs + r8 * LDK + k + 4) = v1[it];
-                keepb[r8 * KEEP_LDS + o] = (uint8_t)bits[it];
+                if (DC) keepb[r8 * KEEP_LDS + o] = (uint8_t)bits[it];     // (read by the write-back alone)
             }
         }
     }
@@ -223,9 +229,9 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             DqSplit<KB>::write_planes(Cs, LDK, a.Cplanes + (size_t)blockIdx.x * plane_cells_per_tile(16 * KB), tid);
     }
 
-    v4f dc[KB];                                      // dC[n = 16blk + 4s + i][k = grad col(kbi, c)], rows of half h
+    v4f dc[DC ? KB : 1];                             // dC[n = 16blk + 4s + i][k = grad col(kbi, c)], rows of half h
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
+    for (int kb = 0; kb < (DC ? KB : 1); ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
     float lsum = 0.f;
     const bool col_edge = n0 + NT64 > a.N;           // the last tile: candidates past N are masked out of the loss
     // !REGC: masked candidate rows (fp32) for the dQ kernel: written from LDS one octet column group per chunk (chunks 1 .. NOIT), so that
@@ -344,7 +350,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         const float *qb = Qc + (32 * h + 4 * s) * LDK;
         v4f pb[KQ > 0 ? KQ : 1];
         float pr[KR > 0 ? KR : 1];
-        if (!GSPLIT) {
+        if (DC && !GSPLIT) {
 #pragma unroll
             for (int kq = 0; kq < KQ; ++kq) pb[kq] = *reinterpret_cast<const v4f *>(qb + 64 * kq + 4 * c);
 #pragma unroll
@@ -379,7 +385,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
                     const float xv = x[i];
                     const bool pos = (yw[rg][i] >> ybit) & 1u;
                     const int brow = b0 + 32 * h + 16 * rg + 4 * s + i;
-                    if (MODE == MODE_TRAIN_BCE && LOGPROD) {
+                    if (LM == MODE_TRAIN_BCE && LOGPROD) {
                         const float y = pos ? a.y_pos : a.y_neg;
                         BceTerms t = bce_terms(xv);
                         float l = fmaxf(xv, 0.f) - xv * y;
@@ -389,12 +395,12 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
                         g4[rg][i] = fmaf(t.sig, a.inv_norm, pos ? gy_pos : gy_neg);
                         continue;
                     }
-                    const LossTerm t = loss_element<MODE>(a, xv, pos, brow, edge, nvalid, b_end);
+                    const LossTerm t = loss_element<LM>(a, xv, pos, brow, edge, nvalid, b_end);
                     lsum += t.l;
                     g4[rg][i] = t.g;
                 }
             }
-            if (MODE == MODE_TRAIN_BCE && LOGPROD) lsum += lin + __builtin_amdgcn_logf(prod) * TILE_LN2;
+            if (LM == MODE_TRAIN_BCE && LOGPROD) lsum += lin + __builtin_amdgcn_logf(prod) * TILE_LN2;
         }
         if (REGC && !GSPLIT && b0 + BC64 < b_end) {
             // park the next chunk in the other buffer (its last readers finished before this chunk's barrier) and request the
@@ -413,7 +419,9 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
             // ---- dC += G^T . Q over this wave's 32 batch rows: A operands straight from g4 ------------------------
             // GSPLIT: one K = 32 step of the bf16 MFMA per plane product and column block, the lane's 8 G values split here
             // sub-step u = 4 rg + t, slot s  <->  batch row 32h + 16rg + 4s + t ; A = G[row][n = 16blk + c] = g4[rg][t]
-            if constexpr (GSPLIT) {
+            if constexpr (!DC) {
+                // (a frozen entity table: G has left for the dQ kernel, nothing else is owed)
+            } else if constexpr (GSPLIT) {
                 v4f none[1];
                 TGS::template product<true>(dc, none, TGS::a_planes(g4, s), Pc, h, lane);
             } else
@@ -457,7 +465,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
         for (; cm_done < NOIT; ++cm_done) write_cm(cm_done);
         __syncthreads();
     }
-    if (!a.loss_only) {
+    if constexpr (DC) if (!a.loss_only) {
         if (h == 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -492,6 +500,7 @@ __global__ __launch_bounds__(T64_THREADS, 2) void fused_tile64_kernel(const Fuse
     TL_STAMP_AT(44);       // loss partial out
     // batch split over blockIdx.y: every workgroup stores ITS partial rows into a slab (plain 16-byte stores);
     // dc_reduce_kernel sums the slabs into dE
+    if constexpr (DC)
     store_tile_gradient<KB, KEEP_LDS>(a, Cs, keepb, gridDim.y > 1 ? a.dC_slab + ((size_t)blockIdx.y * gridDim.x * NT64 + n0) * (16 * KB) : nullptr,
                             n0, tid);
 #ifdef OKGE_STAMPS
@@ -526,13 +535,15 @@ static hipError_t launch64_t(const FusedArgs &a, dim3 grid, hipStream_t st)
 template <int KB>
 static hipError_t launch64_m(int mode, const FusedArgs &a, dim3 grid, hipStream_t st)
 {
+    if (mode == MODE_TRAIN_KL_NODC) return launch64_t<KB, MODE_TRAIN_KL_NODC>(a, grid, st);
+    if (mode == MODE_TRAIN_BCE_NODC) return launch64_t<KB, MODE_TRAIN_BCE_NODC>(a, grid, st);
     return mode == MODE_TRAIN_KL ? launch64_t<KB, MODE_TRAIN_KL>(a, grid, st) : launch64_t<KB, MODE_TRAIN_BCE>(a, grid, st);
 }
 
 // grid_x = number of 64-candidate tiles
 hipError_t launch_fused64(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st)
 {
-    if (mode != MODE_TRAIN_BCE && mode != MODE_TRAIN_KL) return hipErrorInvalidValue;
+    if (!mode_trains(mode)) return hipErrorInvalidValue;
     const dim3 grid(grid_x, grid_y);
     switch (a.KB) {
         case 4:  return launch64_m<4>(mode, a, grid, st);

@@ -35,6 +35,8 @@
 // segment) or 2 p + 1 (its last) and dc_reduce_streamk_kernel adds a tile's partials up -- every workgroup pays at most two
 // fixed costs and none waits for another (no flags, no spinning: the reduction is a separate launch).
 // With a.sk_tiles == 0 the grid is (tiles, batch splits) as for the other tile kernels.
+// MODE_TRAIN_BCE_NODC / MODE_TRAIN_KL_NODC (OKGE_TRAIN_FREEZE_ENTITIES: the entity table is not trained): the training sweep
+// without the dC product and the write-back; a stream-K segment then leaves nothing in the slabs and no reduction is launched.
 #include <cstdio>
 #include <cstdlib>
 
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
     constexpr int D16 = 16 * KB, KH = 16 * KBW;                 // padded slot size, columns of one half
     constexpr int NQ = 4 * KB, QG = 16, NQIT = NQ / QG;         // float4 per row; staging: 16 column groups per row
     static_assert(KB % 8 == 0, "the column split needs whole quads of 16-column blocks per wave");
-    static_assert(MODE == MODE_TRAIN_BCE || MODE == MODE_TRAIN_KL || MODE == MODE_SCORE || MODE == MODE_STATS || mode_counts(MODE),
+    static_assert(mode_trains(MODE) || MODE == MODE_SCORE || MODE == MODE_STATS || mode_counts(MODE),
                   "training kernel, or the score / statistics / counting sweep");
     // MODE_SCORE / MODE_STATS: the same sweep stops after the score blocks and writes X, or per (16-candidate block, row) the
     // (max, sum-exp) pairs of the KL loss' log-softmax (kl_row_lse_kernel merges them).
@@ -71,7 +73,9 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
     // Same products in the same k order as MODE_SCORE: the counts equal those of the materialised scores bit for bit.
     // MODE_COUNT_BCE / MODE_COUNT_KL: MODE_COUNT that also leaves, per (tile, row), the row's validation-loss partial over the
     // tile's candidates in a.stats (the label bit words are free in the counting modes: they carry the partials between waves).
-    constexpr bool TRAIN = MODE == MODE_TRAIN_BCE || MODE == MODE_TRAIN_KL;
+    constexpr bool TRAIN = mode_trains(MODE);
+    // DC: the candidate-gradient product and its write-back (absent from the MODE_TRAIN_*_NODC instances: a frozen entity table)
+    constexpr bool DC = !mode_no_dc(MODE);
     constexpr bool COUNT = mode_counts(MODE), COUNT_LOSS = mode_count_loss(MODE);
     const int d = a.d;
     float *Qb = reinterpret_cast<float *>(smem);                              // [2][32][LDK]  (end: [64][LDK] gradient stage)
@@ -208,7 +212,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
                 const int r = 2 * j + (s & 1);                                   // the rounds this lane computes
                 const int o = (KH * ks + 16 * r + 4 * s) >> 3;
                 mine[j] = (valid && 8 * o < d) ? drop_keep8<true>(a.drop_c, (uint32_t)(n + a.cand_col0), o, d, dstep) : 0u;
-                if (TRAIN) keepb[nl * KEEP_LD + o] = (uint8_t)mine[j];
+                if (TRAIN && DC) keepb[nl * KEEP_LD + o] = (uint8_t)mine[j];   // (read by the write-back alone)
             }
 #pragma unroll
             for (int j = 0; j < KBW / 2; ++j) {
@@ -233,9 +237,9 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
     if (b_begin + BCK < b_end) fetch_chunk(b_begin + BCK);
     __syncthreads();
 
-    v4f dc[KBW];                         // dC[n = 16 blk + 4 s + i][k = 256 ks + 64 kq + 4 c + e] in dc[4 kq + e][i]
+    v4f dc[DC ? KBW : 1];                // dC[n = 16 blk + 4 s + i][k = 256 ks + 64 kq + 4 c + e] in dc[4 kq + e][i]
 #pragma unroll
-    for (int kb = 0; kb < KBW; ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
+    for (int kb = 0; kb < (DC ? KBW : 1); ++kb) dc[kb] = (v4f){0.f, 0.f, 0.f, 0.f};
     const bool col_edge = n0 + NTK > a.N;
 
     auto set_chunk_labels = [&](int bb, uint32_t *yb) { set_label_bits<BCK>(a, posc, pos_lo, pos_hi, pos_cached, n0, bb, yb, tid); };
@@ -414,8 +418,10 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
         // B operands (query rows) of the dC product's first step: requested now, consumed after the epilogue
         const float *qb = Qc + (4 * s) * LDK + KH * ks + 4 * c;
         v4f pb[KQW];
+        if constexpr (DC) {
 #pragma unroll
-        for (int kq = 0; kq < KQW; ++kq) pb[kq] = *reinterpret_cast<const v4f *>(qb + 64 * kq);
+            for (int kq = 0; kq < KQW; ++kq) pb[kq] = *reinterpret_cast<const v4f *>(qb + 64 * kq);
+        }
 
         // ---- loss epilogue: G = dLoss/dX / normalizer, kept in registers -------------------------------------------------
         v4f g4[2];
@@ -426,7 +432,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
             const int ybit = 16 * (blk & 1) + c;
             const bool edge = col_edge || b0 + BCK > b_end;       // uniform: only the last tile / a partial last chunk
             const bool nvalid = n0 + 16 * blk + c < a.N;
-            constexpr int LOSS = MODE == MODE_TRAIN_BCE ? MODE_TRAIN_BCE : MODE_TRAIN_KL;   // (the sweep modes left the chunk above)
+            constexpr int LOSS = mode_loss(MODE) == MODE_TRAIN_BCE ? MODE_TRAIN_BCE : MODE_TRAIN_KL;   // (the sweep modes left the chunk above)
 #pragma unroll
             for (int rg = 0; rg < 2; ++rg) {
                 const v4f x = rg == 0 ? x0 : x1;
@@ -456,6 +462,7 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
             }
             // ---- dC += G^T . Q over the chunk's 32 rows, this wave's 256 columns: A operands straight from g4 -------
             // sub-step u = 4 rg + t, slot s  <->  batch row 16 rg + 4 s + t ; A = G[row][n = 16 blk + c] = g4[rg][t]
+            if constexpr (DC) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const float av = g4[u >> 2][u & 3];
@@ -470,9 +477,10 @@ __global__ __launch_bounds__(TK_THREADS, 2) void fused_tile64k_kernel(const Fuse
                     if (u + 1 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
                 }
             }
+            }
         }
     }
-    if (!TRAIN) continue;
+    if (!TRAIN || !DC) continue;         // (no gradient to write back: the next segment opens with a barrier of its own)
     __syncthreads();
 
     // ---- write-back: every wave stages ITS (16 candidates x 256 columns) of dC into LDS (the two chunk buffers are one
@@ -516,13 +524,15 @@ static hipError_t launch64k_t(const FusedArgs &a, dim3 grid, hipStream_t st)
 hipError_t launch_fused64k(int mode, const FusedArgs &a, int grid_x, int grid_y, hipStream_t st)
 {
     const dim3 grid(grid_x, grid_y);
-    if ((mode != MODE_TRAIN_BCE && mode != MODE_TRAIN_KL && mode != MODE_SCORE && mode != MODE_STATS && !mode_counts(mode)) || a.KB != 32)
+    if ((!mode_trains(mode) && mode != MODE_SCORE && mode != MODE_STATS && !mode_counts(mode)) || a.KB != 32)
         return hipErrorInvalidValue;
     if (mode == MODE_SCORE) return launch64k_t<32, MODE_SCORE>(a, grid, st);
     if (mode == MODE_COUNT) return launch64k_t<32, MODE_COUNT>(a, grid, st);
     if (mode == MODE_COUNT_BCE) return launch64k_t<32, MODE_COUNT_BCE>(a, grid, st);
     if (mode == MODE_COUNT_KL) return launch64k_t<32, MODE_COUNT_KL>(a, grid, st);
     if (mode == MODE_STATS) return launch64k_t<32, MODE_STATS>(a, grid, st);
+    if (mode == MODE_TRAIN_BCE_NODC) return launch64k_t<32, MODE_TRAIN_BCE_NODC>(a, grid, st);
+    if (mode == MODE_TRAIN_KL_NODC) return launch64k_t<32, MODE_TRAIN_KL_NODC>(a, grid, st);
     return mode == MODE_TRAIN_KL ? launch64k_t<32, MODE_TRAIN_KL>(a, grid, st) : launch64k_t<32, MODE_TRAIN_BCE>(a, grid, st);
 }
 

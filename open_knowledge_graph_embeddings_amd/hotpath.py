@@ -205,10 +205,22 @@ def _need_i32(dev, tensors, message):
             raise N.OkgeError(message)
 
 
+FREEZE_FLAGS = {None: 0, "entities": N.OKGE_TRAIN_FREEZE_ENTITIES, "relations": N.OKGE_TRAIN_FREEZE_RELATIONS}
+
+
+def freeze_flag(freeze):
+    """the OKGE_TRAIN_FREEZE_* bit of `freeze` (None, "entities" or "relations": the table that is not trained)"""
+    try:
+        return FREEZE_FLAGS[freeze]
+    except (KeyError, TypeError):
+        raise ValueError(f"freeze {freeze!r}: None, 'entities' or 'relations'") from None
+
+
 def train_flags(grads_zero=False, loss_only=False, unique_candidates=False, distinct_prefix_rows=False, clear_grads=False,
-                row_grads=False):
-    """the OKGE_TRAIN_* word of okge_train_forward_backward / okge_n3_forward_backward / okge_train_tiles (include/okge.h)"""
-    return (N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0) | (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) | \
+                row_grads=False, freeze=None):
+    """the OKGE_TRAIN_* word of okge_train_forward_backward / okge_n3_forward_backward / okge_train_tiles (include/okge.h);
+    freeze: okge_train_forward_backward alone knows it"""
+    return (0 if freeze is None else freeze_flag(freeze)) | (N.OKGE_TRAIN_GRADS_ZERO if grads_zero else 0) | (N.OKGE_TRAIN_LOSS_ONLY if loss_only else 0) | \
         (N.OKGE_TRAIN_UNIQUE_CANDIDATES if unique_candidates else 0) | (N.OKGE_TRAIN_DISTINCT_PREFIX_ROWS if distinct_prefix_rows else 0) | \
         (N.OKGE_TRAIN_CLEAR_GRADS if clear_grads else 0) | (N.OKGE_TRAIN_ROW_GRADS if row_grads else 0)
 
@@ -385,10 +397,12 @@ class HotPath:
 
     def forward_backward(self, E, R, scorer, batch: PrefixBatch, dE, dR, loss="bce", label_smoothing=0.0,
                          normalizer=None, loss_out=None, scores=None, grads_zero=False, loss_only=False,
-                         distinct_prefix_rows=False, clear_grads=False, row_grads=False):
+                         distinct_prefix_rows=False, clear_grads=False, row_grads=False, freeze=None):
         """Fused forward + loss + backward; accumulates into dE / dR (clear_grads: into whatever-they-held buffers that the
         call itself clears, okge.h OKGE_TRAIN_CLEAR_GRADS); returns the summed loss as a device double[1] tensor (no host sync).
-        row_grads: dE (N + B, d) / dR (B, d) are occurrence-row buffers, every row stored once (okge.h OKGE_TRAIN_ROW_GRADS)."""
+        row_grads: dE (N + B, d) / dR (B, d) are occurrence-row buffers, every row stored once (okge.h OKGE_TRAIN_ROW_GRADS).
+        freeze ("entities" / "relations", okge.h OKGE_TRAIN_FREEZE_*): that table is not trained, its buffer may be None and is
+        not touched; with "entities" the candidate-gradient product is not computed."""
         self._check(batch, E, R)
         call, keep = self._filled(batch)
         d = call.fill_tables(E, R, scorer, self.device).d
@@ -400,7 +414,7 @@ class HotPath:
         if loss_out is None:
             loss_out = torch.empty(1, dtype=torch.float64, device=self.device)
         flags = train_flags(grads_zero=grads_zero, loss_only=loss_only, unique_candidates=batch.cand_unique,
-                            distinct_prefix_rows=distinct_prefix_rows, clear_grads=clear_grads, row_grads=row_grads)
+                            distinct_prefix_rows=distinct_prefix_rows, clear_grads=clear_grads, row_grads=row_grads, freeze=freeze)
         call.train(self, loss, label_smoothing, normalizer, flags, loss_out, dE, dR, scores)
         del keep
         return loss_out
@@ -668,8 +682,9 @@ class HotPath:
         return x
 
     def rescale_gradients_(self, g0, g1, alpha_dev, applied):
-        """g0, g1 *= alpha / applied (alpha: device fp32 scalar) in ONE launch; free when the two are the same number"""
-        N.check(self.lib.okge_rescale_gradients(g0.data_ptr(), g0.numel(), g1.data_ptr(), g1.numel(), alpha_dev.data_ptr(),
+        """g0, g1 *= alpha / applied (alpha: device fp32 scalar) in ONE launch; free when the two are the same number.
+        g1 None: g0 alone"""
+        N.check(self.lib.okge_rescale_gradients(g0.data_ptr(), g0.numel(), _ptr(g1), 0 if g1 is None else g1.numel(), alpha_dev.data_ptr(),
                                                 float(applied), self._stream()), "okge_rescale_gradients")
 
     def adagrad(self, p, g, state_sum, lr, weight_decay=1e-10, eps=1e-8, zero_grad=True):

@@ -116,7 +116,10 @@ def make_row_segments(po_rel, po_obj, sp_subj, sp_rel, device, min_rows=1024, mi
 class ShardedTrainStep:
     def __init__(self, E_local, R, scorer, n_ent, min_entities_size=2, lr=0.3, weight_decay=1e-10, eps=1e-8,
                  loss="bce", label_smoothing=0.0, input_dropout=0.0, relation_input_dropout=0.0, seed=0, engine=None,
-                 group=None):
+                 group=None, freeze=None):
+        if freeze is not None:
+            raise NotImplementedError("ShardedTrainStep: freeze (a table that is not trained) is built for the single-device "
+                                      "FusedTrainStep; train the sharded step with both tables")
         N.refuse_bias_scorer(scorer, type(self).__name__)
         self.group = group
         self.world = dist.get_world_size(group)
@@ -369,6 +372,9 @@ class ReplicaTrainStep(FusedTrainStep):
             raise NotImplementedError("ReplicaTrainStep: deterministic=True is built for the single-device FusedTrainStep (the "
                                       "all-reduce adds the replicas' gradients in an order of its own); train the replicas with "
                                       "deterministic=False")
+        if kw.get("freeze") is not None:
+            raise NotImplementedError("ReplicaTrainStep: freeze (a table that is not trained) is built for the single-device "
+                                      "FusedTrainStep; the all-reduce exchanges both tables' gradients")
         super().__init__(E, R, scorer, **kw)
         self.group = group
         self.world = dist.get_world_size(group)

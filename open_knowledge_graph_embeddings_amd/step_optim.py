@@ -39,6 +39,9 @@ def refuse_for_replicas(inner, who):
     refuse_single_device(inner, who)
     if isinstance(inner, StepOptimizer) and (inner.optimizer != "adagrad" or inner.grad_clip > 0):
         raise NotImplementedError(f"{who}: optimizer='adam' and grad_clip are built for the single-device steps")
+    if getattr(inner, "freeze", None) is not None:
+        raise NotImplementedError(f"{who}: an inner step with a frozen table (freeze={inner.freeze!r}) is built for a single device "
+                                  f"(the exchange moves both tables' gradients); build the inner step with freeze=None")
     if getattr(inner, "deterministic", False):
         raise NotImplementedError(f"{who}: a deterministic inner step is built for a single device (the exchange adds the replicas' "
                                   f"gradients in an order of its own); build the inner step with deterministic=False")

@@ -19,7 +19,7 @@ class FusedTrainStep:
                  input_dropout: float = 0.0, relation_input_dropout: float = 0.0, seed: int = 0, engine=None,
                  grad_clip: float = 0.0, accumulate: int = 1, sparse: bool = False, decay_window=None,
                  l2_reg: float = 0.0, l2_reg_dropout: float = 0.0, l2_reg_per_direction: bool = False,
-                 optimizer: str = "adagrad", betas=(0.9, 0.999), deterministic: bool = False):
+                 optimizer: str = "adagrad", betas=(0.9, 0.999), deterministic: bool = False, freeze=None):
         """Defaults follow config/fb15k237/fb15k237-complex-kge.yaml and the optimizer OptimRegime actually
         builds (utils/optim.py:29,139-160): Adagrad(lr, weight_decay=1e-10, eps=1e-8 leaked from Adam).
 
@@ -61,8 +61,31 @@ class FusedTrainStep:
         state and seed are bit-identical on ANY batch; at weight_decay = 0 the Adagrad step is bit-equal to sparse=True, and at
         weight_decay > 0 to sparse=True with a decay_window after flush().  Costs the (N + 2 B) x d occurrence-row traffic and
         a key sort per step.  Refused: sparse=True (already reproducible), l2_reg > 0 (the N3 kernel's gradient rows go through
-        float atomics), slot sizes above 512 and N + n_po + n_sp > 2^20 (the occurrence-row call's limits)."""
+        float atomics), slot sizes above 512 and N + n_po + n_sp > 2^20 (the occurrence-row call's limits).
+
+        freeze (None: the step above, launch for launch; "entities" or "relations": the reference's resume_freeze,
+        trainer.py:532-536 -- requires_grad = False on that table): the frozen table, its gradient and its optimizer state are
+        never touched -- a step constructed fresh does not even allocate dE / sumE / mE / vE / adam_stateE (or their R
+        counterparts): they are None, unless a checkpoint brought an Adagrad `sum` along, which is kept as it came.  The call
+        passes OKGE_TRAIN_FREEZE_ENTITIES / _RELATIONS (okge.h; with "entities" the tile kernels run without their
+        candidate-gradient product), the optimizer sweeps the trained table alone, and grad_clip clips -- `grad_norm` (device
+        double[1]) reports -- the norm of the trained table's gradient alone, as clip_grad_norm_ over parameters without .grad
+        does.  Works with accumulate, the wide path, Adam, GraphedTrainStep and checkpoints.  A zero gradient is not a freeze:
+        weight decay and eps still move the table ("The untouched slot").  Refused: sparse=True, deterministic=True
+        and l2_reg > 0 (NotImplementedError)."""
         N.refuse_bias_scorer(scorer, type(self).__name__)
+        H.freeze_flag(freeze)                 # (ValueError for anything but None / "entities" / "relations")
+        self.freeze = freeze
+        if freeze is not None:
+            if sparse:
+                raise NotImplementedError(f"FusedTrainStep(freeze={freeze!r}, sparse=True): the row-sparse step trains both tables; "
+                                          f"drop sparse=True (dense gradients), or freeze")
+            if deterministic:
+                raise NotImplementedError(f"FusedTrainStep(freeze={freeze!r}, deterministic=True): the occurrence-row call trains both "
+                                          f"tables; drop deterministic=True, or freeze")
+            if float(l2_reg or 0.0) > 0:
+                raise NotImplementedError(f"FusedTrainStep(freeze={freeze!r}, l2_reg={l2_reg}): the N3 kernel adds to both tables' "
+                                          f"gradients; drop l2_reg (l2_reg=0), or freeze")
         self.optimizer = str(optimizer).lower()
         if self.optimizer not in ("adagrad", "adam"):
             raise ValueError(f"optimizer {optimizer!r}: 'adagrad' or 'adam'")
@@ -113,13 +136,17 @@ class FusedTrainStep:
         self.engine = engine or H.HotPath(E.device)
         self._call = H.PrefixCall()       # persistent argument structs of the per-step call (_fast_forward_backward)
         # dense .grad (model_config.sparse False); the sparse step keeps per-shape occurrence-row buffers instead (_row_buffers)
-        self.dE, self.dR = (None, None) if self.sparse else (torch.zeros_like(E), torch.zeros_like(R))
+        # (a frozen table has no gradient and no optimizer state: None)
+        new_e = (lambda: None) if freeze == "entities" else (lambda: torch.zeros_like(E))
+        new_r = (lambda: None) if freeze == "relations" else (lambda: torch.zeros_like(R))
+        self.dE, self.dR = (None, None) if self.sparse else (new_e(), new_r())
         self._rows = {}
         if self.optimizer == "adam":      # Adam state 'exp_avg' / 'exp_avg_sq' (init 0) and the device step counts
-            self.mE, self.vE, self.mR, self.vR = torch.zeros_like(E), torch.zeros_like(E), torch.zeros_like(R), torch.zeros_like(R)
-            self.adam_stateE, self.adam_stateR = H.HotPath.adam_state(E.device), H.HotPath.adam_state(R.device)
+            self.mE, self.vE, self.mR, self.vR = new_e(), new_e(), new_r(), new_r()
+            self.adam_stateE = None if freeze == "entities" else H.HotPath.adam_state(E.device)
+            self.adam_stateR = None if freeze == "relations" else H.HotPath.adam_state(R.device)
         else:
-            self.sumE, self.sumR = torch.zeros_like(E), torch.zeros_like(R)   # Adagrad state 'sum' (init 0)
+            self.sumE, self.sumR = new_e(), new_r()   # Adagrad state 'sum' (init 0)
         if self.decay_window is not None:
             # deferred weight decay: optimizer steps every row has seen, [steps taken, scratch] on the device (a captured graph
             # replays them), and the (lr, weight_decay, eps) of the steps rows still owe -- None: every row is current
@@ -142,10 +169,50 @@ class FusedTrainStep:
         self.grad_clip, self.accumulate = float(grad_clip or 0.0), max(1, int(accumulate))
         self._accumulated = 0
         # deterministic: the global 2-norm of the last clipped gradient (okge_clip_grad_norm: fixed grid, fixed reduction tree)
-        self.grad_norm = torch.zeros(1, dtype=torch.float64, device=E.device) if self.deterministic and self.grad_clip > 0 else None
+        # (and of a frozen step's: the norm of the trained table's gradient alone)
+        self.grad_norm = torch.zeros(1, dtype=torch.float64, device=E.device) \
+            if (self.deterministic or freeze is not None) and self.grad_clip > 0 else None
+
+    def set_freeze(self, freeze):
+        """Freeze a table of a step that exists (checkpoint.load_reference_checkpoint(freeze_param=...), the reference's
+        resume_freeze), or train both again (None).  The frozen table's gradient buffer and Adam state are dropped; an Adagrad
+        `sum` is kept untouched, as torch keeps it for a parameter without .grad.  The refusals of the constructor hold."""
+        H.freeze_flag(freeze)
+        if freeze is not None and (self.sparse or self.deterministic or self.l2_reg > 0):
+            raise NotImplementedError(f"FusedTrainStep.set_freeze({freeze!r}): not with sparse=True, deterministic=True or l2_reg > 0 "
+                                      f"(they train both tables); drop them, or freeze")
+        if self._accumulated:
+            raise RuntimeError("set_freeze inside an accumulation window: the gradients of earlier micro-batches would be lost")
+        self.freeze = freeze
+        adam = self.optimizer == "adam"
+        for tag, table, frozen in (("E", self.E, freeze == "entities"), ("R", self.R, freeze == "relations")):
+            names = ["d" + tag] + (["m" + tag, "v" + tag] if adam else ["sum" + tag])
+            for name in names:
+                if frozen and not name.startswith("sum"):
+                    setattr(self, name, None)
+                elif not frozen and getattr(self, name) is None:
+                    setattr(self, name, torch.zeros_like(table))
+            if adam:
+                state = "adam_state" + tag
+                if frozen:
+                    setattr(self, state, None)
+                elif getattr(self, state) is None:
+                    other = self.adam_stateR if tag == "E" else self.adam_stateE
+                    setattr(self, state, H.HotPath.adam_state(table.device) if other is None else other.clone())
+        self._grads_zero, self._dE_stale = True, False
+        for g in (self.dE, self.dR):
+            if g is not None:
+                g.zero_()
+        if (self.deterministic or freeze is not None) and self.grad_clip > 0 and self.grad_norm is None:
+            self.grad_norm = torch.zeros(1, dtype=torch.float64, device=self.E.device)
 
     def state_tensors(self):
         """every tensor a step mutates (GraphedTrainStep snapshots them around its warm-up)"""
+        if self.freeze is not None:        # the trained table, its gradient and its state: the frozen table is not among them
+            e = self.freeze == "relations"
+            if self.optimizer == "adam":
+                return [self.E, self.dE, self.mE, self.vE, self.adam_stateE] if e else [self.R, self.dR, self.mR, self.vR, self.adam_stateR]
+            return [self.E, self.dE, self.sumE] if e else [self.R, self.dR, self.sumR]
         if self.optimizer == "adam":       # (the two device states with them: restoring a snapshot restores t)
             grads = [] if self.sparse else [self.dE, self.dR]
             return [self.E, self.R] + grads + [self.mE, self.vE, self.mR, self.vR, self.adam_stateE, self.adam_stateR]
@@ -159,11 +226,13 @@ class FusedTrainStep:
     @property
     def adam_t(self):
         """optimizer steps the Adam state has taken (read back from the device: synchronises)"""
-        return int(self.adam_stateE[0].item())
+        return int((self.adam_stateR if self.adam_stateE is None else self.adam_stateE)[0].item())
 
     def set_adam_t(self, t):
         """both tables' device step counts (a loaded checkpoint, a reset)"""
         for st in (self.adam_stateE, self.adam_stateR):
+            if st is None:                # (a frozen table has none)
+                continue
             st.zero_()
             st[0] = int(t)
 
@@ -224,7 +293,7 @@ class FusedTrainStep:
                       batch.pos_row, batch.pos_col)
         call.fill_dropout(self.input_dropout, self.relation_input_dropout, self.seed, self.steps, self.step_dev)
         flags = H.train_flags(row_grads=True) if self._row_grads else \
-            H.train_flags(grads_zero=self._grads_zero, unique_candidates=batch.cand_unique)
+            H.train_flags(grads_zero=self._grads_zero, unique_candidates=batch.cand_unique, freeze=self.freeze)
         return call.train(self.engine, self.loss, self.label_smoothing, normalizer, flags, self.loss_out, dE, dR)
 
     def _plain(self, batch: H.PrefixBatch):
@@ -264,7 +333,7 @@ class FusedTrainStep:
                                           self._counters, lr, wd, eps)
             dE, dR = rb["gE"], rb["gR"]
         else:
-            if self._dE_stale and not (self._grads_zero and self._covers_all_rows(batch)):
+            if self.dE is not None and self._dE_stale and not (self._grads_zero and self._covers_all_rows(batch)):
                 self.dE.zero_()           # a sampled candidate list leaves rows untouched: they must read as zero
                 self._dE_stale = False
             self._last_full = self._covers_all_rows(batch)
@@ -275,6 +344,8 @@ class FusedTrainStep:
         else:
             self._set_dropout(batch)
             how = dict(row_grads=True) if self.sparse else dict(grads_zero=self._grads_zero)
+            if self.freeze is not None:
+                how["freeze"] = self.freeze
             loss = self.engine.forward_backward(self.E, self.R, self.scorer, batch, dE, dR, loss=self.loss,
                                                 label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out, **how)
         if self.l2_reg > 0:
@@ -312,6 +383,8 @@ class FusedTrainStep:
         every row it uses; it is cleared on demand if a sampled candidate list comes next.
         Sparse step: torch's sparse Adagrad on the occurrence rows of the last forward_backward -- nothing to clear; with a
         decay_window the same rows take the dense step's expression, then the due slice of the deferred decay-only steps."""
+        if self.freeze is not None:       # the trained table alone; the frozen one takes no decay and has no state to move
+            return self._frozen_optimizer_step(lazy_zero)
         if self.optimizer == "adam":
             if self.sparse:               # torch.optim.SparseAdam on the occurrence rows; nothing to clear
                 rb = self._cur_rows
@@ -341,6 +414,20 @@ class FusedTrainStep:
                              self.eps, zero_grad=2 if lazy_zero else 1)
         self._dE_stale = bool(lazy_zero)
 
+    def _frozen_optimizer_step(self, lazy_zero):
+        """optimizer_step of a step with one table frozen: okge_adagrad_step / okge_adam_step on the trained table (the update
+        rule and the fused zero_grad of the two-table sweep).  Only the entity gradient can be left for the next 1-vs-all step
+        to overwrite (lazy_zero)."""
+        e = self.freeze == "relations"
+        keep = bool(lazy_zero) and e
+        if self.optimizer == "adam":
+            t = (self.E, self.dE, self.mE, self.vE, self.adam_stateE) if e else (self.R, self.dR, self.mR, self.vR, self.adam_stateR)
+            self.engine.adam([t], self.lr, self.betas, self.eps, self.weight_decay, zero_grad=0 if keep else 1)
+        else:
+            p, g, s = (self.E, self.dE, self.sumE) if e else (self.R, self.dR, self.sumR)
+            self.engine.adagrad(p, g, s, self.lr, self.weight_decay, self.eps, zero_grad=not keep)
+        self._dE_stale = keep
+
     def step(self, batch: H.PrefixBatch, normalizer=None):
         """forward + loss + backward; every `accumulate`-th call also clips (grad_clip > 0) and takes the Adagrad step"""
         self.steps += 1
@@ -350,7 +437,9 @@ class FusedTrainStep:
         if self._accumulated < self.accumulate:
             return loss                      # trainer.py:233-234, 246-248: no optimizer step yet, gradients keep adding up
         self._accumulated = 0
-        if self.grad_clip > 0:
+        if self.grad_clip > 0 and self.freeze is not None:
+            self.engine.clip_grad_norm_(self.dR if self.dE is None else self.dE, None, self.grad_clip, self.grad_norm)
+        elif self.grad_clip > 0:
             self.engine.clip_grad_norm_(self.dE, self.dR, self.grad_clip, self.grad_norm)
         self.optimizer_step(lazy_zero=self._last_full and self.accumulate == 1)
         self._grads_zero = True

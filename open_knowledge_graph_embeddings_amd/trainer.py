@@ -33,7 +33,8 @@ class _FusedLossFn(torch.autograd.Function):
     def forward(ctx, e_weight, r_weight, loss, g_e, g_r, engine, applied, row_ids):
         """row_ids: None (g_e / g_r are dense table gradients) or the occurrence ids (ids_e, ids_r) of gradient ROWS
         (AddLossModule(sparse_grads=True)): backward then hands autograd uncoalesced sparse tensors, as the backward of
-        nn.Embedding(sparse=True) does (model.py:390-391)"""
+        nn.Embedding(sparse=True) does (model.py:390-391).  g_e or g_r None: that table is frozen (requires_grad False), the
+        call computed no gradient for it and backward returns None for that input"""
         ctx.g_e, ctx.g_r, ctx.engine, ctx.applied = g_e, g_r, engine, applied
         ctx.row_ids, ctx.shapes = row_ids, (e_weight.shape, r_weight.shape)
         return loss.to(torch.float32).reshape(())               # (the cast already yields a fresh tensor)
@@ -42,6 +43,9 @@ class _FusedLossFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         alpha = grad_out.reshape(1).to(torch.float32).contiguous()
         g_e, g_r, ctx.g_e, ctx.g_r = ctx.g_e, ctx.g_r, None, None   # no reference left behind: AccumulateGrad then TAKES the
+        if g_e is None or g_r is None:                              # a frozen table: the trained one's gradient alone
+            ctx.engine.rescale_gradients_(g_r if g_e is None else g_e, None, alpha, ctx.applied)
+            return g_e, g_r, None, None, None, None, None, None
         ctx.engine.rescale_gradients_(g_e, g_r, alpha, ctx.applied) # buffers as .grad instead of copying them (an 11.6 MB
         if ctx.row_ids is not None:                                 # copy per step at FB15k-237)
             (ids_e, ids_r), ctx.row_ids = ctx.row_ids, None         # (the rescale above acted on the value rows)
@@ -194,6 +198,22 @@ class AddLossModule(nn.Module):
             return "bce"
         raise NotImplementedError(f"{self.loss} not supported. Please choose either BCEWithLogitsLoss or KLDivLoss")
 
+    def _frozen_table(self, m, n3=None):
+        """The reference's resume_freeze (trainer.py:532-536) as the fused call sees it: requires_grad of the two tables, read on
+        every call.  -> None (both trained), "entities" / "relations" (that one is frozen: OKGE_TRAIN_FREEZE_*, no gradient
+        buffer, backward returns None for it) or "both" (nothing to train: the loss-only route).
+        With sparse_grads=True or the fused l2_reg hook (n3) one frozen table also answers None: the occurrence-row call and the
+        N3 kernel are not built for a missing buffer, so the whole step runs as it always did and autograd drops the gradient of
+        the input that does not require one -- the frozen parameter's .grad stays None either way"""
+        ge, gr = m.entity_embedding.weight.requires_grad, m.relation_embedding.weight.requires_grad
+        if ge and gr:
+            return None
+        if not ge and not gr:
+            return "both"
+        if self.sparse_grads or n3 is not None:
+            return None
+        return "relations" if ge else "entities"
+
     def forward(self, inputs, labels, use_batch_shared_entities, batch_shared_entities, epoch=-1,
                 input_style_triple_or_prefix="triple"):
         allowed = ["triple", "right_and_left_prefix"]
@@ -261,6 +281,9 @@ class AddLossModule(nn.Module):
             m.dropout_step += 1
         batch.set_dropout([m.dropout_spec(stream, stream in (H.STREAM_PO_REL, H.STREAM_SP_REL)) for stream in H.STREAMS])
         n3 = self._n3_term(m, batch.n_po, batch.n_sp, batch_shared_entities)
+        frozen = self._frozen_table(m, n3) if want_grad else None
+        if frozen == "both":
+            want_grad, frozen = False, None
         if want_grad:
             E, R = m.E, m.R
             # a contiguous candidate range: the call stores the candidate rows and clears the rest itself (all of dR, the
@@ -273,6 +296,8 @@ class AddLossModule(nn.Module):
                 row_ids = H.occurrence_ids(dev, batch.cand_ids, batch.cand_first, n, batch.po_obj, batch.sp_subj, batch.po_rel, batch.sp_rel)
             else:
                 g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
+            if frozen is not None:                                  # the frozen table gets no buffer at all
+                g_e, g_r = (None, g_r) if frozen == "entities" else (g_e, None)
             # the factor the Trainer will apply (trainer.py:221: loss / normalizer_loss, normalizer_loss = B x N,
             # dataset.py:935) goes into the fused step; _FusedLossFn.backward checks it against what autograd delivers
             # (torch divides a fp32 tensor by a Python number as a multiplication by fp32(1) / fp32(number), forward and
@@ -281,7 +306,7 @@ class AddLossModule(nn.Module):
             applied = np.float32(1.0) / np.float32(float(B) * float(n))
             loss = eng.forward_backward(E, R, m.scorer_name, batch, g_e, g_r, loss=kind, label_smoothing=smoothing,
                                         normalizer=1.0 / float(applied), scores=all_outputs, grads_zero=True, clear_grads=clear,
-                                        row_grads=self.sparse_grads)
+                                        row_grads=self.sparse_grads, freeze=frozen)
             if n3 is not None:
                 reg = eng.n3_forward_backward(E, R, m.scorer_name, batch, g_e, g_r, n3[0], cand_passes=n3[1],
                                               normalizer=1.0 / float(applied), row_grads=self.sparse_grads)
@@ -328,6 +353,11 @@ class AddLossModule(nn.Module):
         E, R = m.E, m.R
         if E.dtype != torch.float32 or not E.is_contiguous() or not R.is_contiguous() or R.dtype != torch.float32:
             return None
+        frozen = None
+        if not (m.entity_embedding.weight.requires_grad and m.relation_embedding.weight.requires_grad):
+            frozen = self._frozen_table(m, self._n3_term(m, 1, 1, batch_shared_entities))
+            if frozen == "both":
+                return None                                         # (nothing to train: the general path's loss-only route)
         if getattr(self, "_fd", None) is None:
             self._fd = H.PrefixCall()
         fd = self._fd
@@ -351,7 +381,9 @@ class AddLossModule(nn.Module):
                                       po[0] if n_po else None, sp[1] if n_sp else None)
         else:
             g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
-        flags = H.train_flags(grads_zero=not self.sparse_grads, clear_grads=clear, row_grads=self.sparse_grads)
+        if frozen is not None:                                                # the frozen table gets no buffer at all
+            g_e, g_r = (None, g_r) if frozen == "entities" else (g_e, None)
+        flags = H.train_flags(grads_zero=not self.sparse_grads, clear_grads=clear, row_grads=self.sparse_grads, freeze=frozen)
         applied = np.float32(1.0) / np.float32(float(B) * float(n))           # (see forward below)
         smoothing = self.bce_label_smoothing if kind == "bce" else 0.0
         loss = fd.train(eng, kind, smoothing, 1.0 / float(applied), flags, torch.empty(1, dtype=torch.float64, device=dev), g_e, g_r,
