@@ -28,7 +28,9 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-ENTITY_KEY, RELATION_KEY = "entity_embedding.weight", "relation_embedding.weight"
+from .train_step import ENTITY_KEY, RELATION_KEY
+
+CHECKPOINT_FORMAT = 1
 
 
 def _gather_rows(local, n_rows, group):
@@ -46,9 +48,12 @@ def _is_adam(step):
     return getattr(step, "optimizer", "adagrad") == "adam"
 
 
-def _frozen(step):
-    """None, or the table a FusedTrainStep(freeze=...) does not train: "entities" / "relations" """
-    return getattr(step, "freeze", None)
+def _state_names(step):
+    return ("exp_avg", "exp_avg_sq") if _is_adam(step) else ("sum",)
+
+
+def _cpu(t):
+    return t.detach().cpu().clone()
 
 
 def freeze_names(freeze_param, loaded):
@@ -61,65 +66,66 @@ def freeze_names(freeze_param, loaded):
     return [name for name in loaded if name in freeze_param]
 
 
-def _full_tables(step):
-    """(E, R, sumE, sumR) as full tables, whatever the step class; an Adam step: (E, R, mE, vE, mR, vR).  A frozen table's
-    missing state comes as None."""
-    if _is_adam(step):
-        return step.E, step.R, step.mE, step.vE, step.mR, step.vR
-    if hasattr(step, "flush"):                                    # deferred weight decay: rows may owe decay-only steps
-        step.flush()
-    if hasattr(step, "ent_lo"):                                   # ShardedTrainStep: gather the row shards
-        return (_gather_rows(step.E, step.n_ent, step.group), step.R, _gather_rows(step.sumE, step.n_ent, step.group),
-                step.sumR)
-    return step.E, step.R, step.sumE, step.sumR
+def _lookup_entries(step, full=False, keep_sums=False):
+    """{state_dict key: (parameter, its optimizer state tensors, moved)} of a two-table lookup step -- what
+    optimizer_params_and_state gives for the steps of the other models -- in the order of the reference's optimizer: the entity
+    table, the relation table.  moved: the step trains the table (FusedTrainStep(freeze=...) does not train one); a state tensor
+    the step does not hold comes as None.  The one place that knows a lookup step by its attribute names: FusedTrainStep, the
+    row-sharded step and a bare object with the tables and accumulators all serve.
+    full: the row shards of a ShardedTrainStep gathered into whole tables (collective).  keep_sums: an Adagrad step gets a `sum`
+    where it holds none (a frozen table carries the file's along untouched)."""
+    names = (("mE", "vE"), ("mR", "vR")) if _is_adam(step) else (("sumE",), ("sumR",))
+    entries = {}
+    for key, table, letter, state in ((ENTITY_KEY, "entities", "E", names[0]), (RELATION_KEY, "relations", "R", names[1])):
+        p = getattr(step, letter)
+        if keep_sums and not _is_adam(step) and getattr(step, state[0], None) is None:
+            setattr(step, state[0], torch.empty_like(p))
+        views = tuple(getattr(step, name, None) for name in state)
+        if full and letter == "E" and hasattr(step, "ent_lo"):
+            p, *views = (_gather_rows(t, step.n_ent, step.group) for t in (p, *views))
+        entries[key] = (p, tuple(views), getattr(step, "freeze", None) != table)
+    return entries
+
+
+def _reference_checkpoint(step, state_dict, entries, t, epoch, training_steps):
+    """The dict `Trainer.save` writes around `state_dict`: what torch.optim.Adagrad / torch.optim.Adam over the parameters of
+    `entries` ([(parameter, state tensors, moved)]) would return from state_dict(), every tensor a copy on the CPU, and the regime.
+    t: the optimizer steps taken.  Adagrad holds state for every parameter from its construction: one that is not moved has
+    `step` 0 and the `sum` the step holds for it -- zeros where it holds none; Adam creates a parameter's state at its first step:
+    one that is not moved has no entry."""
+    adam = _is_adam(step)
+    state = {}
+    for i, (p, views, moved) in enumerate(entries):
+        if adam and not moved:
+            continue
+        state[i] = {"step": torch.tensor(t if moved else 0.0)}
+        state[i].update({name: torch.zeros_like(_cpu(p)) if v is None else _cpu(v) for name, v in zip(_state_names(step), views)})
+    group = {"lr": step.lr, "betas": tuple(step.betas) if adam else (0.9, 0.999), "eps": step.eps, "weight_decay": step.weight_decay,
+             "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+             "decoupled_weight_decay": False}
+    if not adam:
+        group.update({"lr_decay": 0, "initial_accumulator_value": 0})
+    group["params"] = list(range(len(entries)))
+    regime = [{"optimizer": "Adam" if adam else "Adagrad", "epoch": 0, "lr": step.lr, "weight_decay": step.weight_decay}]
+    return {"epoch": int(epoch), "training_steps": int(step.steps if training_steps is None else training_steps),
+            "state_dict": state_dict,
+            "optimizer_state_dict": [{"optimizer_state": {"state": state, "param_groups": [group]}, "regime": regime}],
+            "validation_results": None}
 
 
 def to_reference_checkpoint(step, epoch=0, training_steps=None):
     """The dict `Trainer.save` would write for this training state (tensors on the CPU).  An Adam step (FusedTrainStep(optimizer=
     "adam")) writes torch.optim.Adam's layout -- state {step, exp_avg, exp_avg_sq}, `step` = the optimizer steps taken, regime
     optimizer "Adam" -- which torch.optim.Adam.load_state_dict takes as it is."""
-    if _is_adam(step):
-        return _adam_checkpoint(step, epoch, training_steps)
-    E, R, sumE, sumR = (None if t is None else t.detach().cpu().clone() for t in _full_tables(step))
-    n_steps = float(step.steps)
-    # a frozen table (FusedTrainStep(freeze=...)): the `sum` the step holds for it, untouched -- zeros where it never had one,
-    # torch.optim.Adagrad's initial state -- and the step count of a parameter that never had a gradient
-    steps_e, steps_r = (0.0 if _frozen(step) == "entities" else n_steps), (0.0 if _frozen(step) == "relations" else n_steps)
-    sumE, sumR = (torch.zeros_like(E) if sumE is None else sumE), (torch.zeros_like(R) if sumR is None else sumR)
-    group = {"lr": step.lr, "betas": (0.9, 0.999), "eps": step.eps, "weight_decay": step.weight_decay, "amsgrad": False,
-             "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "decoupled_weight_decay": False, "lr_decay": 0, "initial_accumulator_value": 0, "params": [0, 1]}
-    optimizer_state = {"state": {0: {"step": torch.tensor(steps_e), "sum": sumE},
-                                 1: {"step": torch.tensor(steps_r), "sum": sumR}},
-                       "param_groups": [group]}
-    regime = [{"optimizer": "Adagrad", "epoch": 0, "lr": step.lr, "weight_decay": step.weight_decay}]
-    return {"epoch": int(epoch), "training_steps": int(step.steps if training_steps is None else training_steps),
-            "state_dict": {ENTITY_KEY: E, RELATION_KEY: R},
-            "optimizer_state_dict": [{"optimizer_state": optimizer_state, "regime": regime}],
-            "validation_results": None}
+    if hasattr(step, "flush"):                                    # deferred weight decay: rows may owe decay-only steps
+        step.flush()
+    entries = _lookup_entries(step, full=True)
+    return _reference_checkpoint(step, {key: _cpu(e[0]) for key, e in entries.items()}, list(entries.values()),
+                                 float(step.adam_t if _is_adam(step) else step.steps), epoch, training_steps)
 
 
-def _adam_checkpoint(step, epoch, training_steps):
-    E, R, mE, vE, mR, vR = (None if t is None else t.detach().cpu().clone() for t in _full_tables(step))
-    t = float(step.adam_t)
-    group = {"lr": step.lr, "betas": tuple(step.betas), "eps": step.eps, "weight_decay": step.weight_decay, "amsgrad": False,
-             "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "decoupled_weight_decay": False, "params": [0, 1]}
-    optimizer_state = {"state": {0: {"step": torch.tensor(t), "exp_avg": mE, "exp_avg_sq": vE},
-                                 1: {"step": torch.tensor(t), "exp_avg": mR, "exp_avg_sq": vR}},
-                       "param_groups": [group]}
-    if _frozen(step) is not None:     # torch.optim.Adam creates a parameter's state at its first step: a frozen one has no entry
-        del optimizer_state["state"][0 if _frozen(step) == "entities" else 1]
-    regime = [{"optimizer": "Adam", "epoch": 0, "lr": step.lr, "weight_decay": step.weight_decay}]
-    return {"epoch": int(epoch), "training_steps": int(step.steps if training_steps is None else training_steps),
-            "state_dict": {ENTITY_KEY: E, RELATION_KEY: R},
-            "optimizer_state_dict": [{"optimizer_state": optimizer_state, "regime": regime}],
-            "validation_results": None}
-
-
-def _checkpoint_optimizer(ckpt):
+def _checkpoint_optimizer(reg):
     """'adam' / 'adagrad': what the state entries of the first parameter say (the regime's name where there is no state yet)"""
-    reg = ckpt["optimizer_state_dict"][0]
     states = reg["optimizer_state"]["state"]
     st0 = states.get(0) or states.get(1, {})            # (an Adam run with the entity table frozen holds no entry 0)
     if "exp_avg" in st0:
@@ -128,6 +134,52 @@ def _checkpoint_optimizer(ckpt):
         return "adagrad"
     names = [str(r.get("optimizer", "")).lower() for r in reg.get("regime", []) if isinstance(r, dict)]
     return "adam" if names and names[-1].endswith("adam") else "adagrad"
+
+
+def _check_optimizer_state(step, entries, reg):
+    """every refusal of the optimizer state `reg` (an entry of a checkpoint's optimizer_state_dict) for the parameters of `entries`,
+    before anything is written"""
+    want, have = ("adam" if _is_adam(step) else "adagrad"), _checkpoint_optimizer(reg)
+    if want != have:
+        raise ValueError(f"the checkpoint holds {have} optimizer state and this step trains with {want}: its accumulators do "
+                         f"not carry over -- load with reset_optimizer=True to take the tables alone")
+    group, state = reg["optimizer_state"]["param_groups"][0], reg["optimizer_state"]["state"]
+    if len(group["params"]) != len(entries):
+        raise ValueError(f"the checkpoint's optimizer holds {len(group['params'])} parameters, this model has {len(entries)}")
+    for i, (p, views, moved) in enumerate(entries):
+        for name in _state_names(step) if i in state else ():
+            if name not in state[i] or tuple(state[i][name].shape) != tuple(p.shape):
+                got = tuple(state[i][name].shape) if name in state[i] else None
+                raise ValueError(f"optimizer state {name!r} of parameter {i} has shape {got}, the parameter's is {tuple(p.shape)}")
+    if float(group.get("lr_decay", 0)) != 0 or float(group.get("initial_accumulator_value", 0)) != 0:
+        raise NotImplementedError("Adagrad lr_decay / initial_accumulator_value are not used by the reference configs")
+    if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
+        raise NotImplementedError("amsgrad, maximize and decoupled weight decay (AdamW) are not implemented")
+
+
+def _apply_optimizer_state(step, entries, reg):
+    """The state tensors of `entries`, the Adam step count and the step's hyper-parameters from `reg` (checked).  reg None, the
+    reset: the state is zeroed, the counts are 0 and the step keeps its own hyper-parameters.  A parameter the file holds no state
+    for (torch's Adam has not stepped it yet) gets zeros; a state tensor the step does not hold (None: a frozen table's) is passed
+    over.  -> the `step` counts of the moved parameters the file holds state for; None after a reset"""
+    state = {} if reg is None else reg["optimizer_state"]["state"]
+    for i, (p, views, moved) in enumerate(entries):
+        for name, v in zip(_state_names(step), views):
+            if v is not None and i in state:
+                v.copy_(state[i][name])
+            elif v is not None:
+                v.zero_()
+    taken = [int(float(state[i]["step"])) for i, e in enumerate(entries) if e[2] and i in state]
+    if _is_adam(step):
+        step.set_adam_t(taken[0] if taken else 0)
+    if reg is None:
+        step.steps = 0
+        return None
+    group = reg["optimizer_state"]["param_groups"][0]
+    step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
+    if _is_adam(step):
+        step.betas = (float(group["betas"][0]), float(group["betas"][1]))
+    return taken
 
 
 def save_checkpoint(path, step, epoch=0, training_steps=None):
@@ -140,7 +192,8 @@ def save_checkpoint(path, step, epoch=0, training_steps=None):
 
 def load_reference_checkpoint(step, ckpt_or_path, reset_optimizer=False, freeze_param=None):
     """Load tables (and, unless `reset_optimizer`, the Adagrad accumulators and step count -- the reference's
-    `Trainer.load(reset_optimizer=...)` switch, trainer.py:561-605) into a fused / sharded train step.
+    `Trainer.load(reset_optimizer=...)` switch, trainer.py:561-605) into a fused / sharded train step.  Every refusal is raised
+    before anything of the step is written.
     freeze_param (the reference's resume_freeze, trainer.py:532-536): a list of parameter names, or ["True"] for every loaded
     one.  `entity_embedding.weight` / `relation_embedding.weight` set the step's `freeze` (FusedTrainStep.set_freeze) before the
     state is loaded; naming both raises ValueError (nothing to train), a step class without `set_freeze` NotImplementedError."""
@@ -158,82 +211,36 @@ def load_reference_checkpoint(step, ckpt_or_path, reset_optimizer=False, freeze_
     lo, hi = (step.ent_lo, step.ent_hi) if hasattr(step, "ent_lo") else (0, E.shape[0])
     if E[lo:hi].shape != step.E.shape or R.shape != step.R.shape:
         raise ValueError(f"checkpoint tables {tuple(E.shape)}, {tuple(R.shape)} do not fit this model")
-    if not reset_optimizer:
-        want, have = ("adam" if _is_adam(step) else "adagrad"), _checkpoint_optimizer(ckpt)
-        if want != have:
-            raise ValueError(f"the checkpoint holds {have} optimizer state and this step trains with {want}: its accumulators do "
-                             f"not carry over -- load with reset_optimizer=True to take the tables alone")
+    reg = None if reset_optimizer else ckpt["optimizer_state_dict"][0]
+    if reg is not None and hasattr(step, "ent_lo") and 0 in reg["optimizer_state"]["state"]:       # this rank's rows of the entity state
+        st = reg["optimizer_state"]
+        own = {k: v if k == "step" else v[lo:hi] for k, v in st["state"][0].items()}
+        reg = dict(reg, optimizer_state=dict(st, state={**st["state"], 0: own}))
+    if reg is not None:
+        _check_optimizer_state(step, list(_lookup_entries(step).values()), reg)
     if names:                                                     # (every refusal is behind us)
         step.set_freeze("entities" if names[0] == ENTITY_KEY else "relations")
+    entries = list(_lookup_entries(step, keep_sums=reg is not None).values())
+    if _is_adam(step) and reg is not None and [e[2] for e in entries].index(True) not in reg["optimizer_state"]["state"]:
+        reg = None                                                # (a torch optimizer that has not stepped yet holds no state)
     if hasattr(step, "flush"):                                    # deferred weight decay: no row may owe steps to the loaded tables
         step.flush()
     step.E.copy_(E[lo:hi])
     step.R.copy_(R)
-    if _is_adam(step):
-        _load_adam_state(step, None if reset_optimizer else ckpt["optimizer_state_dict"][0]["optimizer_state"], ckpt)
-    elif reset_optimizer:
-        for s in (step.sumE, step.sumR):
-            if s is not None:
-                s.zero_()
-        step.steps = 0
-    else:
-        st = ckpt["optimizer_state_dict"][0]["optimizer_state"]
-        group, state = st["param_groups"][0], st["state"]
-        if _frozen(step) is not None:
-            # the frozen table's `sum` is carried along untouched; the step count is the trained table's
-            for name, idx, table in (("sumE", 0, step.E), ("sumR", 1, step.R)):
-                if getattr(step, name) is None:
-                    setattr(step, name, torch.empty_like(table))
-                getattr(step, name).copy_(state[idx]["sum"])
-            step.steps = int(float(state[1 if _frozen(step) == "entities" else 0]["step"]))
-        else:
-            step.sumE.copy_(state[0]["sum"][lo:hi])
-            step.sumR.copy_(state[1]["sum"])
-            # (the larger count: a file written by a frozen run holds `step` 0 for the table that never had a gradient, and the
-            #  dropout masks are keyed by the step count)
-            step.steps = int(max(float(state[0]["step"]), float(state[1]["step"])))
-        step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
-        if float(group.get("lr_decay", 0)) != 0 or float(group.get("initial_accumulator_value", 0)) != 0:
-            raise NotImplementedError("Adagrad lr_decay / initial_accumulator_value are not used by the reference configs")
-    for g in (step.dE, step.dR):                                  # (the row-sparse step keeps no dense gradients, a frozen table none)
+    taken = _apply_optimizer_state(step, entries, reg)
+    if taken is not None:
+        # Adagrad, the larger count: a file written by a frozen run holds `step` 0 for the table that never had a gradient (and
+        # a frozen step takes the trained table's); the dropout masks are keyed by the step count
+        step.steps = int(ckpt.get("training_steps", taken[0])) if _is_adam(step) else max(taken)
+    for g in (getattr(step, "dE", None), getattr(step, "dR", None)):      # (the row-sparse step keeps no dense gradients, a frozen table none)
         if g is not None:
             g.zero_()
     return ckpt
 
 
-def _load_adam_state(step, st, ckpt):
-    """moments, t and hyper-parameters of an Adam step from torch.optim.Adam's state (None: reset -- zero moments, t = 0)"""
-    trained = [i for i, name in ((0, "entities"), (1, "relations")) if _frozen(step) != name]      # (a frozen table has no state)
-    if st is None or trained[0] not in st["state"]:              # (a torch optimizer that has not stepped yet holds no state)
-        for x in (step.mE, step.vE, step.mR, step.vR):
-            if x is not None:
-                x.zero_()
-        step.set_adam_t(0)
-        step.steps = 0
-        return
-    group, state = st["param_groups"][0], st["state"]
-    if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
-        raise NotImplementedError("amsgrad, maximize and decoupled weight decay (AdamW) are not implemented")
-    if 0 in trained:
-        step.mE.copy_(state[0]["exp_avg"])
-        step.vE.copy_(state[0]["exp_avg_sq"])
-    if 1 in trained:
-        step.mR.copy_(state[1]["exp_avg"])
-        step.vR.copy_(state[1]["exp_avg_sq"])
-    step.set_adam_t(int(float(state[trained[0]]["step"])))
-    step.steps = int(ckpt.get("training_steps", int(float(state[trained[0]]["step"]))))
-    step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
-    step.betas = (float(group["betas"][0]), float(group["betas"][1]))
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # The token-encoded and Tucker3 models: a module and the driver its train_step() returned
 # ------------------------------------------------------------------------------------------------------------------
-CHECKPOINT_FORMAT = 1
-_OPTIMIZER_MISMATCH = ("the checkpoint holds {have} optimizer state and this step trains with {want}: its accumulators do "
-                       "not carry over -- load with reset_optimizer=True to take the tables alone")
-
-
 def _model_and_step(model, step):
     from .step_optim import StepOptimizer
     if not isinstance(step, StepOptimizer) or not hasattr(model, "optimizer_params_and_state"):
@@ -241,10 +248,6 @@ def _model_and_step(model, step):
                         f"train_step() returned, not {type(step).__name__}: the two-table lookup steps go through "
                         f"to_reference_checkpoint / load_reference_checkpoint")
     return model.optimizer_params_and_state(step)
-
-
-def _state_names(step):
-    return ("exp_avg", "exp_avg_sq") if _is_adam(step) else ("sum",)
 
 
 def model_checkpoint(model, step, epoch=0, training_steps=None):
@@ -256,29 +259,12 @@ def model_checkpoint(model, step, epoch=0, training_steps=None):
     same dropout masks and that torch's optimizer state has no place for."""
     entries, word = _model_and_step(model, step)
     step.sync_module()
-    cpu = lambda t: t.detach().cpu().clone()                   # noqa: E731
-    state_dict = {k: cpu(v) if v.is_floating_point() else cpu(v).to(torch.int64) for k, v in model.state_dict().items()}
-    adam = _is_adam(step)
-    t = float(int(word[0].item())) if adam else float(step.steps)
-    state = {}
-    for i, (p, views, moved) in enumerate(entries):
-        if adam and not moved:                                  # torch.optim.Adam creates a parameter's state at its first step
-            continue
-        state[i] = {"step": torch.tensor(t if moved else 0.0)}
-        state[i].update({name: cpu(v) for name, v in zip(_state_names(step), views)})
-    group = {"lr": step.lr, "betas": tuple(step.betas) if adam else (0.9, 0.999), "eps": step.eps, "weight_decay": step.weight_decay,
-             "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "decoupled_weight_decay": False}
-    if not adam:
-        group.update({"lr_decay": 0, "initial_accumulator_value": 0})
-    group["params"] = list(range(len(entries)))
-    regime = [{"optimizer": "Adam" if adam else "Adagrad", "epoch": 0, "lr": step.lr, "weight_decay": step.weight_decay}]
-    return {"epoch": int(epoch), "training_steps": int(step.steps if training_steps is None else training_steps),
-            "state_dict": state_dict,
-            "optimizer_state_dict": [{"optimizer_state": {"state": state, "param_groups": [group]}, "regime": regime}],
-            "validation_results": None,
-            "okge": {"format": CHECKPOINT_FORMAT, "steps": int(step.steps), "dropout_step": int(model.dropout_step),
-                     "dropout_seed": int(model.dropout_seed), "grad_clip": float(step.grad_clip)}}
+    state_dict = {k: _cpu(v) if v.is_floating_point() else _cpu(v).to(torch.int64) for k, v in model.state_dict().items()}
+    t = float(int(word[0].item())) if _is_adam(step) else float(step.steps)
+    ckpt = _reference_checkpoint(step, state_dict, entries, t, epoch, training_steps)
+    ckpt["okge"] = {"format": CHECKPOINT_FORMAT, "steps": int(step.steps), "dropout_step": int(model.dropout_step),
+                    "dropout_seed": int(model.dropout_seed), "grad_clip": float(step.grad_clip)}
+    return ckpt
 
 
 def save_model_checkpoint(path, model, step, epoch=0, training_steps=None):
@@ -302,24 +288,8 @@ def _check_model_checkpoint(model, step, entries, ckpt, reset_optimizer):
     extra = ckpt.get("okge")
     if extra is not None and int(extra.get("format", 0)) != CHECKPOINT_FORMAT:
         raise ValueError(f"checkpoint 'okge' format {extra.get('format')!r}: this package reads format {CHECKPOINT_FORMAT}")
-    if reset_optimizer:
-        return
-    want, have = ("adam" if _is_adam(step) else "adagrad"), _checkpoint_optimizer(ckpt)
-    if want != have:
-        raise ValueError(_OPTIMIZER_MISMATCH.format(have=have, want=want))
-    st = ckpt["optimizer_state_dict"][0]["optimizer_state"]
-    group, state = st["param_groups"][0], st["state"]
-    if len(group["params"]) != len(entries):
-        raise ValueError(f"the checkpoint's optimizer holds {len(group['params'])} parameters, this model has {len(entries)}")
-    for i, (p, views, moved) in enumerate(entries):
-        for name in _state_names(step) if i in state else ():
-            if name not in state[i] or tuple(state[i][name].shape) != tuple(p.shape):
-                got = tuple(state[i][name].shape) if name in state[i] else None
-                raise ValueError(f"optimizer state {name!r} of parameter {i} has shape {got}, the parameter's is {tuple(p.shape)}")
-    if float(group.get("lr_decay", 0)) != 0 or float(group.get("initial_accumulator_value", 0)) != 0:
-        raise NotImplementedError("Adagrad lr_decay / initial_accumulator_value are not used by the reference configs")
-    if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
-        raise NotImplementedError("amsgrad, maximize and decoupled weight decay (AdamW) are not implemented")
+    if not reset_optimizer:
+        _check_optimizer_state(step, entries, ckpt["optimizer_state_dict"][0])
 
 
 def load_model_checkpoint(model, step, ckpt_or_path, reset_optimizer=False, freeze_param=None):
@@ -353,24 +323,9 @@ def load_model_checkpoint(model, step, ckpt_or_path, reset_optimizer=False, free
         model.entity_embedding_from_tokens = model.relations_embedding_from_tokens = None
     step.adopt_module()
     step.reset_gradients()
-    st = None if reset_optimizer else ckpt["optimizer_state_dict"][0]["optimizer_state"]
-    state = {} if st is None else st["state"]
-    for i, (p, views, moved) in enumerate(entries):
-        for name, v in zip(_state_names(step), views):
-            if i in state:
-                v.copy_(state[i][name])
-            else:                                                # (reset, or a parameter torch's Adam has not stepped yet)
-                v.zero_()
-    taken = [int(float(state[i]["step"])) for i, e in enumerate(entries) if e[2] and i in state]
-    if _is_adam(step):
-        step.set_adam_t(taken[0] if taken else 0)
-    if st is None:
-        step.steps = 0
+    taken = _apply_optimizer_state(step, entries, None if reset_optimizer else ckpt["optimizer_state_dict"][0])
+    if taken is None:
         return ckpt
-    group = st["param_groups"][0]
-    step.lr, step.weight_decay, step.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
-    if _is_adam(step):
-        step.betas = (float(group["betas"][0]), float(group["betas"][1]))
     extra = ckpt.get("okge")
     if extra is None:
         step.steps = int(ckpt.get("training_steps", taken[0] if taken else 0))

@@ -12,6 +12,24 @@ from . import _native as N
 from . import hotpath as H
 from .step_optim import refuse_single_device
 
+ENTITY_KEY, RELATION_KEY = "entity_embedding.weight", "relation_embedding.weight"
+
+
+class TableState:
+    """What FusedTrainStep holds for ONE of its two tables.  Plain storage: the step's methods run over both records, or over
+    the trained ones.  `name`: what `freeze` calls the table; `index`: its parameter index in the reference's optimizer; `key`:
+    its state_dict key.  A field the step's configuration does not use -- and everything but `param` and an Adagrad `sum` of
+    a frozen table -- is None."""
+    __slots__ = ("name", "index", "key", "param", "grad", "sum", "exp_avg", "exp_avg_sq", "adam_state", "row_steps")
+
+    def __init__(self, name, index, key, param):
+        self.name, self.index, self.key, self.param = name, index, key, param
+        self.grad = None                                     # dense .grad
+        self.sum = None                                      # Adagrad state 'sum'
+        self.exp_avg = self.exp_avg_sq = None                # Adam state
+        self.adam_state = None                               # HotPath.adam_state: the device step count
+        self.row_steps = None                                # decay_window: optimizer steps every row has seen
+
 
 class FusedTrainStep:
     def __init__(self, E: torch.Tensor, R: torch.Tensor, scorer: str, loss: str = "bce", lr: float = 0.3,
@@ -127,7 +145,8 @@ class FusedTrainStep:
             if float(grad_clip or 0.0) > 0 or int(accumulate) > 1:
                 raise NotImplementedError("FusedTrainStep(sparse=True): grad_clip and accumulate need dense gradients "
                                           "(torch.nn.utils.clip_grad_norm_ refuses sparse gradients)")
-        self.E, self.R = E, R
+        self.ent, self.rel = TableState("entities", 0, ENTITY_KEY, E), TableState("relations", 1, RELATION_KEY, R)
+        self.tables = (self.ent, self.rel)
         self.scorer, self.loss = scorer, loss
         self.lr, self.weight_decay, self.eps = lr, weight_decay, eps
         self.label_smoothing = label_smoothing
@@ -135,23 +154,13 @@ class FusedTrainStep:
         self.seed = seed
         self.engine = engine or H.HotPath(E.device)
         self._call = H.PrefixCall()       # persistent argument structs of the per-step call (_fast_forward_backward)
-        # dense .grad (model_config.sparse False); the sparse step keeps per-shape occurrence-row buffers instead (_row_buffers)
-        # (a frozen table has no gradient and no optimizer state: None)
-        new_e = (lambda: None) if freeze == "entities" else (lambda: torch.zeros_like(E))
-        new_r = (lambda: None) if freeze == "relations" else (lambda: torch.zeros_like(R))
-        self.dE, self.dR = (None, None) if self.sparse else (new_e(), new_r())
         self._rows = {}
-        if self.optimizer == "adam":      # Adam state 'exp_avg' / 'exp_avg_sq' (init 0) and the device step counts
-            self.mE, self.vE, self.mR, self.vR = new_e(), new_e(), new_r(), new_r()
-            self.adam_stateE = None if freeze == "entities" else H.HotPath.adam_state(E.device)
-            self.adam_stateR = None if freeze == "relations" else H.HotPath.adam_state(R.device)
-        else:
-            self.sumE, self.sumR = new_e(), new_r()   # Adagrad state 'sum' (init 0)
+        self._allocate()
         if self.decay_window is not None:
             # deferred weight decay: optimizer steps every row has seen, [steps taken, scratch] on the device (a captured graph
             # replays them), and the (lr, weight_decay, eps) of the steps rows still owe -- None: every row is current
-            self.rowsE = torch.zeros(E.shape[0], dtype=torch.int32, device=E.device)
-            self.rowsR = torch.zeros(R.shape[0], dtype=torch.int32, device=R.device)
+            for t in self.tables:
+                t.row_steps = torch.zeros(t.param.shape[0], dtype=torch.int32, device=t.param.device)
             self._counters = torch.zeros(2, dtype=torch.int32, device=E.device)
         self._pending = None
         self.steps = 0
@@ -173,6 +182,25 @@ class FusedTrainStep:
         self.grad_norm = torch.zeros(1, dtype=torch.float64, device=E.device) \
             if (self.deterministic or freeze is not None) and self.grad_clip > 0 else None
 
+    def _allocate(self):
+        """zeros for the gradient and the optimizer state a trained table lacks (dense .grad unless model_config.sparse: the sparse
+        step keeps per-shape occurrence-row buffers instead, _row_buffers); a frozen table keeps nothing but an Adagrad `sum`"""
+        for t in self.tables:
+            if t.name == self.freeze:
+                t.grad = t.exp_avg = t.exp_avg_sq = t.adam_state = None
+                continue
+            zeros = lambda x, t=t: torch.zeros_like(t.param) if x is None else x      # noqa: E731
+            if not self.sparse:
+                t.grad = zeros(t.grad)
+            if self.optimizer == "adam":  # Adam state 'exp_avg' / 'exp_avg_sq' (init 0) and the device step count
+                t.exp_avg, t.exp_avg_sq = zeros(t.exp_avg), zeros(t.exp_avg_sq)
+                if t.adam_state is None:  # (a table that trains again takes the count of the one that never stopped)
+                    other = self.tables[1 - t.index].adam_state
+                    t.adam_state = H.HotPath.adam_state(t.param.device) if other is None else other.clone()
+            else:
+                t.sum = zeros(t.sum)      # Adagrad state 'sum' (init 0)
+        self.trained = tuple(t for t in self.tables if t.name != self.freeze)
+
     def set_freeze(self, freeze):
         """Freeze a table of a step that exists (checkpoint.load_reference_checkpoint(freeze_param=...), the reference's
         resume_freeze), or train both again (None).  The frozen table's gradient buffer and Adam state are dropped; an Adagrad
@@ -184,55 +212,33 @@ class FusedTrainStep:
         if self._accumulated:
             raise RuntimeError("set_freeze inside an accumulation window: the gradients of earlier micro-batches would be lost")
         self.freeze = freeze
-        adam = self.optimizer == "adam"
-        for tag, table, frozen in (("E", self.E, freeze == "entities"), ("R", self.R, freeze == "relations")):
-            names = ["d" + tag] + (["m" + tag, "v" + tag] if adam else ["sum" + tag])
-            for name in names:
-                if frozen and not name.startswith("sum"):
-                    setattr(self, name, None)
-                elif not frozen and getattr(self, name) is None:
-                    setattr(self, name, torch.zeros_like(table))
-            if adam:
-                state = "adam_state" + tag
-                if frozen:
-                    setattr(self, state, None)
-                elif getattr(self, state) is None:
-                    other = self.adam_stateR if tag == "E" else self.adam_stateE
-                    setattr(self, state, H.HotPath.adam_state(table.device) if other is None else other.clone())
+        self._allocate()
         self._grads_zero, self._dE_stale = True, False
-        for g in (self.dE, self.dR):
-            if g is not None:
-                g.zero_()
+        for t in self.trained:
+            t.grad.zero_()
         if (self.deterministic or freeze is not None) and self.grad_clip > 0 and self.grad_norm is None:
-            self.grad_norm = torch.zeros(1, dtype=torch.float64, device=self.E.device)
+            self.grad_norm = torch.zeros(1, dtype=torch.float64, device=self.ent.param.device)
 
     def state_tensors(self):
-        """every tensor a step mutates (GraphedTrainStep snapshots them around its warm-up)"""
-        if self.freeze is not None:        # the trained table, its gradient and its state: the frozen table is not among them
-            e = self.freeze == "relations"
-            if self.optimizer == "adam":
-                return [self.E, self.dE, self.mE, self.vE, self.adam_stateE] if e else [self.R, self.dR, self.mR, self.vR, self.adam_stateR]
-            return [self.E, self.dE, self.sumE] if e else [self.R, self.dR, self.sumR]
-        if self.optimizer == "adam":       # (the two device states with them: restoring a snapshot restores t)
-            grads = [] if self.sparse else [self.dE, self.dR]
-            return [self.E, self.R] + grads + [self.mE, self.vE, self.mR, self.vR, self.adam_stateE, self.adam_stateR]
-        if self.decay_window is not None:  # (a caller that restores a snapshot restores the step counters with it)
-            self.flush()
-            return [self.E, self.R, self.sumE, self.sumR, self.rowsE, self.rowsR, self._counters]
-        if self.sparse:                   # (the row buffers are written whole before they are read, every step)
-            return [self.E, self.R, self.sumE, self.sumR]
-        return [self.E, self.R, self.dE, self.dR, self.sumE, self.sumR]
+        """every tensor a step mutates (GraphedTrainStep snapshots them around its warm-up, by position): the trained tables,
+        their dense gradients, their optimizer state -- a frozen table and what it holds are not among them"""
+        tr = self.trained
+        out = [t.param for t in tr] + [t.grad for t in tr if t.grad is not None]    # (the row buffers are written whole every step)
+        if self.optimizer == "adam":       # (the device states with them: restoring a snapshot restores t)
+            return out + [m for t in tr for m in (t.exp_avg, t.exp_avg_sq)] + [t.adam_state for t in tr]
+        if self.decay_window is None:
+            return out + [t.sum for t in tr]
+        self.flush()                       # (a caller that restores a snapshot restores the step counters with it)
+        return out + [t.sum for t in tr] + [t.row_steps for t in tr] + [self._counters]
 
     @property
     def adam_t(self):
         """optimizer steps the Adam state has taken (read back from the device: synchronises)"""
-        return int((self.adam_stateR if self.adam_stateE is None else self.adam_stateE)[0].item())
+        return int(self.trained[0].adam_state[0].item())
 
     def set_adam_t(self, t):
-        """both tables' device step counts (a loaded checkpoint, a reset)"""
-        for st in (self.adam_stateE, self.adam_stateR):
-            if st is None:                # (a frozen table has none)
-                continue
+        """the trained tables' device step counts (a loaded checkpoint, a reset)"""
+        for st in (tab.adam_state for tab in self.trained):     # (a frozen table has none)
             st.zero_()
             st[0] = int(t)
 
@@ -246,8 +252,8 @@ class FusedTrainStep:
             return
         lr, wd, eps = self._pending
         # (no row is stamped in a flush, so the gradient operand is never read: the accumulator stands in)
-        self.engine.adagrad_lazy([(self.E, self.sumE, self.sumE, self.rowsE), (self.R, self.sumR, self.sumR, self.rowsR)],
-                                 self._counters, self.decay_window, True, lr, wd, eps)
+        self.engine.adagrad_lazy([(t.param, t.sum, t.sum, t.row_steps) for t in self.tables], self._counters, self.decay_window, True,
+                                 lr, wd, eps)
         self._pending = None
 
     def mark_pending(self):
@@ -268,16 +274,20 @@ class FusedTrainStep:
         key = (n, n_po, n_sp)
         rb = self._rows.get(key)
         if rb is None:
-            dev, d, B = self.E.device, self.E.shape[1], n_po + n_sp
+            dev, d, B = self.ent.param.device, self.ent.param.shape[1], n_po + n_sp
             rb = self._rows[key] = dict(gE=torch.empty((n + B, d), dtype=torch.float32, device=dev),
                                         gR=torch.empty((B, d), dtype=torch.float32, device=dev),
                                         idE=torch.empty(n + B, dtype=torch.int32, device=dev),
                                         idR=torch.empty(B, dtype=torch.int32, device=dev))
         return rb
 
+    def _occurrences(self, rb):
+        """(record, occurrence ids, gradient rows) of both tables in the row buffers rb"""
+        return (self.ent, rb["idE"], rb["gE"]), (self.rel, rb["idR"], rb["gR"])
+
     def _covers_all_rows(self, batch: H.PrefixBatch):
         """1-vs-all: the candidate range is every row from cand_first on, so the step overwrites all of dE it uses"""
-        return batch.cand_ids is None and batch.cand_first + batch.n_cand == self.E.shape[0]
+        return batch.cand_ids is None and batch.cand_first + batch.n_cand == self.ent.param.shape[0]
 
     def _set_dropout(self, batch: H.PrefixBatch):
         batch.set_dropout(H.dropout_specs(self.input_dropout, self.relation_input_dropout, self.seed, self.steps, self.step_dev))
@@ -286,9 +296,9 @@ class FusedTrainStep:
         """same call as HotPath.forward_backward for int32 device tensors (what the batch producer emits), issued from the
         step's persistent argument structs (H.PrefixCall)"""
         if H.VALIDATE:
-            H.validate_ids(batch, self.E.shape[0], self.R.shape[0])
+            H.validate_ids(batch, self.ent.param.shape[0], self.rel.param.shape[0])
         call = self._call
-        call.fill_tables(self.E, self.R, self.scorer, self.engine.device)
+        call.fill_tables(self.ent.param, self.rel.param, self.scorer, self.engine.device)
         call.fill_ids(batch.po_rel, batch.po_obj, batch.sp_subj, batch.sp_rel, batch.cand_ids, batch.cand_first, batch.n_cand,
                       batch.pos_row, batch.pos_col)
         call.fill_dropout(self.input_dropout, self.relation_input_dropout, self.seed, self.steps, self.step_dev)
@@ -299,7 +309,7 @@ class FusedTrainStep:
     def _plain(self, batch: H.PrefixBatch):
         """int32 contiguous tensors ON THE ENGINE'S DEVICE everywhere and no replayed masks: nothing for the generic path
         to convert (a host tensor's data_ptr handed to a kernel would be a GPU fault)"""
-        dev = self.E.device
+        dev = self.ent.param.device
         for x in (batch.po_rel, batch.po_obj, batch.sp_subj, batch.sp_rel, batch.pos_row, batch.pos_col, batch.cand_ids):
             if x is not None and (x.dtype != torch.int32 or not x.is_contiguous() or x.dim() != 1 or x.device != dev):
                 return False
@@ -314,30 +324,31 @@ class FusedTrainStep:
             flags = H.train_flags(unique_candidates=batch.cand_unique, row_grads=self.sparse)
             self._call.n3(self.engine, coef, passes, normalizer, flags, self.reg_out, dE, dR)
         else:
-            self.engine.n3_forward_backward(self.E, self.R, self.scorer, batch, dE, dR, coef, cand_passes=passes, normalizer=normalizer,
+            self.engine.n3_forward_backward(self.ent.param, self.rel.param, self.scorer, batch, dE, dR, coef, cand_passes=passes, normalizer=normalizer,
                                             reg_out=self.reg_out, row_grads=self.sparse)
 
     def forward_backward(self, batch: H.PrefixBatch, normalizer=None):
         """trainer.py:206-234.  Returns the summed loss (device double[1], valid after stream sync)."""
         if self.deterministic:                # (a method of its own: the default step is host-bound, its path stays as short as it was)
             return self._deterministic_forward_backward(batch, normalizer)
+        ent, rel = self.ent, self.rel
         if self.sparse:
             rb = self._cur_rows = self._row_buffers(batch)
-            H.occurrence_ids(self.E.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
+            H.occurrence_ids(ent.param.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
                              batch.po_rel, batch.sp_rel, out=(rb["idE"], rb["idR"]))
             self._last_full = False
             if self.decay_window is not None:      # the rows this batch names take what they owe BEFORE the gather reads them
                 self._settle_hparams()
                 lr, wd, eps = self._hparams()
-                self.engine.rows_catch_up([(self.E, self.sumE, rb["idE"], self.rowsE), (self.R, self.sumR, rb["idR"], self.rowsR)],
-                                          self._counters, lr, wd, eps)
+                self.engine.rows_catch_up([(t.param, t.sum, ids, t.row_steps) for t, ids, _ in self._occurrences(rb)], self._counters,
+                                          lr, wd, eps)
             dE, dR = rb["gE"], rb["gR"]
         else:
-            if self.dE is not None and self._dE_stale and not (self._grads_zero and self._covers_all_rows(batch)):
-                self.dE.zero_()           # a sampled candidate list leaves rows untouched: they must read as zero
+            dE, dR = ent.grad, rel.grad
+            if dE is not None and self._dE_stale and not (self._grads_zero and self._covers_all_rows(batch)):
+                dE.zero_()                # a sampled candidate list leaves rows untouched: they must read as zero
                 self._dE_stale = False
             self._last_full = self._covers_all_rows(batch)
-            dE, dR = self.dE, self.dR
         fast = isinstance(self.engine, H.HotPath) and self._plain(batch)
         if fast:
             loss = self._fast_forward_backward(batch, normalizer, dE, dR)
@@ -346,7 +357,7 @@ class FusedTrainStep:
             how = dict(row_grads=True) if self.sparse else dict(grads_zero=self._grads_zero)
             if self.freeze is not None:
                 how["freeze"] = self.freeze
-            loss = self.engine.forward_backward(self.E, self.R, self.scorer, batch, dE, dR, loss=self.loss,
+            loss = self.engine.forward_backward(ent.param, rel.param, self.scorer, batch, dE, dR, loss=self.loss,
                                                 label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out, **how)
         if self.l2_reg > 0:
             self._regularise(batch, normalizer, fast, dE, dR)
@@ -358,23 +369,23 @@ class FusedTrainStep:
             raise N.OkgeError(f"okge_rows_to_dense takes up to 2^20 occurrence rows per tensor: this batch has "
                               f"{batch.n_candidates} + {batch.B}; train it with deterministic=False")
         rb = self._cur_rows = self._row_buffers(batch)
-        H.occurrence_ids(self.E.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
+        H.occurrence_ids(self.ent.param.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
                          batch.po_rel, batch.sp_rel, out=(rb["idE"], rb["idR"]))
         # a store names -- and so overwrites -- every row of dE only when the candidate range is the whole table from row 0
         names_all = self._covers_all_rows(batch) and batch.cand_first == 0
         if self._dE_stale and not (self._grads_zero and names_all):
-            self.dE.zero_()               # rows this batch does not name must read as zero
+            self.ent.grad.zero_()         # rows this batch does not name must read as zero
             self._dE_stale = False
         self._last_full = names_all
         if isinstance(self.engine, H.HotPath) and self._plain(batch):
             loss = self._fast_forward_backward(batch, normalizer, rb["gE"], rb["gR"])
         else:
             self._set_dropout(batch)
-            loss = self.engine.forward_backward(self.E, self.R, self.scorer, batch, rb["gE"], rb["gR"], loss=self.loss,
+            loss = self.engine.forward_backward(self.ent.param, self.rel.param, self.scorer, batch, rb["gE"], rb["gR"], loss=self.loss,
                                                 label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out,
                                                 row_grads=True)
         # cleared tables (a fresh window): the named rows are stored; later micro-batches continue each row's chain
-        self.engine.rows_to_dense([(self.dE, rb["idE"], rb["gE"]), (self.dR, rb["idR"], rb["gR"])], accumulate=not self._grads_zero)
+        self.engine.rows_to_dense([(t.grad, ids, g) for t, ids, g in self._occurrences(rb)], accumulate=not self._grads_zero)
         return loss
 
     def optimizer_step(self, lazy_zero=False):
@@ -382,50 +393,37 @@ class FusedTrainStep:
         after a 1-vs-all batch): the entity gradient is not cleared here because the next 1-vs-all step overwrites
         every row it uses; it is cleared on demand if a sampled candidate list comes next.
         Sparse step: torch's sparse Adagrad on the occurrence rows of the last forward_backward -- nothing to clear; with a
-        decay_window the same rows take the dense step's expression, then the due slice of the deferred decay-only steps."""
-        if self.freeze is not None:       # the trained table alone; the frozen one takes no decay and has no state to move
-            return self._frozen_optimizer_step(lazy_zero)
-        if self.optimizer == "adam":
-            if self.sparse:               # torch.optim.SparseAdam on the occurrence rows; nothing to clear
-                rb = self._cur_rows
-                self.engine.adam_rows([(self.E, self.mE, self.vE, self.adam_stateE, rb["idE"], rb["gE"]),
-                                       (self.R, self.mR, self.vR, self.adam_stateR, rb["idR"], rb["gR"])], self.lr, self.betas, self.eps)
-                return
-            self.engine.adam([(self.E, self.dE, self.mE, self.vE, self.adam_stateE), (self.R, self.dR, self.mR, self.vR, self.adam_stateR)],
-                             self.lr, self.betas, self.eps, self.weight_decay, zero_grad=2 if lazy_zero else 1)
-            self._dE_stale = bool(lazy_zero)
+        decay_window the same rows take the dense step's expression, then the due slice of the deferred decay-only steps.
+        A frozen table: the same update rule and fused zero_grad on the trained table alone (okge_adagrad_step / okge_adam_step
+        with one tensor); the frozen one takes no decay and has no state to move."""
+        trained = self.trained
+        keep = bool(lazy_zero) and trained[0] is self.ent      # only the entity gradient can be left for the next step to overwrite
+        if self.sparse:                   # (trains both tables)
+            rows = self._occurrences(self._cur_rows)
+            if self.optimizer == "adam":  # torch.optim.SparseAdam on the occurrence rows
+                self.engine.adam_rows([(t.param, t.exp_avg, t.exp_avg_sq, t.adam_state, ids, g) for t, ids, g in rows],
+                                      self.lr, self.betas, self.eps)
+            elif self.decay_window is not None:
+                self._settle_hparams()
+                lr, wd, eps = self._hparams()
+                self.engine.adagrad_rows_decay([(t.param, t.sum, ids, g, t.row_steps) for t, ids, g in rows], self._counters,
+                                               self.decay_window, lr, wd, eps)
+                if self.decay_window > 1:
+                    self._pending = (lr, wd, eps)
+            else:
+                (e, ide, ge), (r, idr, gr) = rows
+                self.engine.adagrad_rows(e.param, e.sum, ide, ge, self.lr, self.eps, second=(r.param, r.sum, idr, gr))
             return
-        if self.decay_window is not None:
-            rb = self._cur_rows
-            self._settle_hparams()
-            lr, wd, eps = self._hparams()
-            self.engine.adagrad_rows_decay([(self.E, self.sumE, rb["idE"], rb["gE"], self.rowsE),
-                                            (self.R, self.sumR, rb["idR"], rb["gR"], self.rowsR)],
-                                           self._counters, self.decay_window, lr, wd, eps)
-            if self.decay_window > 1:
-                self._pending = (lr, wd, eps)
-            return
-        if self.sparse:
-            rb = self._cur_rows
-            self.engine.adagrad_rows(self.E, self.sumE, rb["idE"], rb["gE"], self.lr, self.eps,
-                                     second=(self.R, self.sumR, rb["idR"], rb["gR"]))
-            return
-        self.engine.adagrad2(self.E, self.dE, self.sumE, self.R, self.dR, self.sumR, self.lr, self.weight_decay,
-                             self.eps, zero_grad=2 if lazy_zero else 1)
-        self._dE_stale = bool(lazy_zero)
-
-    def _frozen_optimizer_step(self, lazy_zero):
-        """optimizer_step of a step with one table frozen: okge_adagrad_step / okge_adam_step on the trained table (the update
-        rule and the fused zero_grad of the two-table sweep).  Only the entity gradient can be left for the next 1-vs-all step
-        to overwrite (lazy_zero)."""
-        e = self.freeze == "relations"
-        keep = bool(lazy_zero) and e
-        if self.optimizer == "adam":
-            t = (self.E, self.dE, self.mE, self.vE, self.adam_stateE) if e else (self.R, self.dR, self.mR, self.vR, self.adam_stateR)
-            self.engine.adam([t], self.lr, self.betas, self.eps, self.weight_decay, zero_grad=0 if keep else 1)
+        if self.optimizer == "adam":      # zero_grad: 0 none, 1 all, 2 the second tensor alone
+            self.engine.adam([(t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.adam_state) for t in trained], self.lr, self.betas, self.eps,
+                             self.weight_decay, zero_grad=(2 if len(trained) == 2 else 0) if keep else 1)
+        elif len(trained) == 2:
+            e, r = trained
+            self.engine.adagrad2(e.param, e.grad, e.sum, r.param, r.grad, r.sum, self.lr, self.weight_decay, self.eps,
+                                 zero_grad=2 if keep else 1)
         else:
-            p, g, s = (self.E, self.dE, self.sumE) if e else (self.R, self.dR, self.sumR)
-            self.engine.adagrad(p, g, s, self.lr, self.weight_decay, self.eps, zero_grad=not keep)
+            t, = trained
+            self.engine.adagrad(t.param, t.grad, t.sum, self.lr, self.weight_decay, self.eps, zero_grad=not keep)
         self._dE_stale = keep
 
     def step(self, batch: H.PrefixBatch, normalizer=None):
@@ -437,13 +435,24 @@ class FusedTrainStep:
         if self._accumulated < self.accumulate:
             return loss                      # trainer.py:233-234, 246-248: no optimizer step yet, gradients keep adding up
         self._accumulated = 0
-        if self.grad_clip > 0 and self.freeze is not None:
-            self.engine.clip_grad_norm_(self.dR if self.dE is None else self.dE, None, self.grad_clip, self.grad_norm)
-        elif self.grad_clip > 0:
-            self.engine.clip_grad_norm_(self.dE, self.dR, self.grad_clip, self.grad_norm)
+        if self.grad_clip > 0:               # (the global norm over the trained tables' gradients)
+            grads = [t.grad for t in self.trained]
+            self.engine.clip_grad_norm_(grads[0], grads[1] if len(grads) == 2 else None, self.grad_clip, self.grad_norm)
         self.optimizer_step(lazy_zero=self._last_full and self.accumulate == 1)
         self._grads_zero = True
         return loss
+
+
+def _alias(index, field):
+    return property(lambda self: getattr(self.tables[index], field), lambda self, value: setattr(self.tables[index], field, value))
+
+
+# the per-letter names of the records' fields: step.sumE is step.ent.sum, step.dR = x sets step.rel.grad (callers, subclasses and
+# tests know the step by these; its own methods go through the records)
+for _index, _letter in enumerate("ER"):
+    for _name, _field in (("", "param"), ("d", "grad"), ("sum", "sum"), ("m", "exp_avg"), ("v", "exp_avg_sq"),
+                          ("adam_state", "adam_state"), ("rows", "row_steps")):
+        setattr(FusedTrainStep, _name + _letter, _alias(_index, _field))
 
 
 class GraphedTrainStep:

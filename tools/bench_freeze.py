@@ -7,7 +7,8 @@
   default   the step with default keywords -- the line to compare between two commits: it passes no `freeze` keyword, so a
             checkout from before the keyword runs it too.  Run it from both trees in turn (this, parent, this, parent) with
             --label naming the tree; the margin of the comparison is the spread of the parent's own runs
-  freeze    freeze=None, "entities" and "relations" on this build: eager ms/step and the per-kernel times (okge_timing_*)
+  freeze    freeze=None, "entities" and "relations": eager ms/step and the per-kernel times (okge_timing_*); run from a parent
+            that has the keyword too, it is compared like the default line
 
 Every step figure is the median of `--windows` windows of `--steps` steps, each window closed by a device synchronise, with the
 fastest and slowest window beside it.  One JSON object per line; `--report OUT.md LOG [LOG ...]` turns the logs of such runs into
@@ -91,6 +92,24 @@ def measure(shape, dev, args, label, **kw):
     return out
 
 
+def compare(rows):
+    """per (shape, freeze) measured from both trees: the medians of each, the difference of their means, the parent's own spread
+    -- the margin of the comparison -- and the runs of this tree that lie outside the parent's range"""
+    text = []
+    for shape, freeze in sorted({(r["shape"], str(r["freeze"])) for r in rows}):
+        by = {}
+        for r in rows:
+            if (r["shape"], str(r["freeze"])) == (shape, freeze):
+                by.setdefault(r["build"], []).append(r["ms_per_step_median"])
+        if "parent" in by and "this" in by:
+            lo, hi = min(by["parent"]), max(by["parent"])
+            delta = statistics.mean(by["this"]) - statistics.mean(by["parent"])
+            outside = [x for x in by["this"] if not lo <= x <= hi]
+            text.append(f"{shape}, freeze {freeze}: parent {by['parent']}, this {by['this']}; this - parent = {delta:+.4f} ms, the parent's "
+                        f"own spread {hi - lo:.4f} ms; runs of this tree outside [{lo}, {hi}]: {outside or 'none'}.")
+    return text
+
+
 def report(out_path, logs):
     rows = []
     for path in logs:
@@ -104,26 +123,17 @@ def report(out_path, logs):
             "| run | build | shape | ms/step | min | max |", "|---|---|---|---|---|---|"]
     for i, r in enumerate(default):
         text.append(f"| {i} | {r['build']} | {r['shape']} | {r['ms_per_step_median']:.4f} | {r['min']:.4f} | {r['max']:.4f} |")
-    text.append("")
-    for shape in sorted({r["shape"] for r in default}):
-        by = {}
-        for r in default:
-            if r["shape"] == shape:
-                by.setdefault(r["build"], []).append(r["ms_per_step_median"])
-        if "parent" in by and "this" in by:
-            spread = max(by["parent"]) - min(by["parent"])
-            delta = statistics.mean(by["this"]) - statistics.mean(by["parent"])
-            text.append(f"{shape}: parent {by['parent']}, this {by['this']}; this - parent = {delta:+.4f} ms, the parent's own spread "
-                        f"{spread:.4f} ms.")
-    text += ["", "## freeze=None, \"entities\", \"relations\" on this build", "",
-             "| shape | freeze | ms/step | min | max |", "|---|---|---|---|---|"]
+    text += [""] + compare(default)
+    text += ["", "## freeze=None, \"entities\", \"relations\"", "",
+             "| build | shape | freeze | ms/step | min | max |", "|---|---|---|---|---|---|"]
     for r in frozen:
-        text.append(f"| {r['shape']} | {r['freeze']} | {r['ms_per_step_median']:.4f} | {r['min']:.4f} | {r['max']:.4f} |")
+        text.append(f"| {r['build']} | {r['shape']} | {r['freeze']} | {r['ms_per_step_median']:.4f} | {r['min']:.4f} | {r['max']:.4f} |")
+    text += [""] + compare(frozen)
     text += ["", "## Per-kernel times of those runs (okge_timing_*, us per launch)", ""]
     names = sorted({k for r in frozen for k in r["kernels_us"]})
-    text += ["| shape | freeze | " + " | ".join(names) + " |", "|---|---|" + "---|" * len(names)]
+    text += ["| build | shape | freeze | " + " | ".join(names) + " |", "|---|---|---|" + "---|" * len(names)]
     for r in frozen:
-        text.append(f"| {r['shape']} | {r['freeze']} | " + " | ".join(str(r["kernels_us"].get(k, "-")) for k in names) + " |")
+        text.append(f"| {r['build']} | {r['shape']} | {r['freeze']} | " + " | ".join(str(r["kernels_us"].get(k, "-")) for k in names) + " |")
     reading = "## Reading\n\n(not written yet)\n"
     if os.path.exists(out_path):
         old = open(out_path).read()
