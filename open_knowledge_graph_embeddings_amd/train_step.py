@@ -327,15 +327,34 @@ class FusedTrainStep:
             self.engine.n3_forward_backward(self.ent.param, self.rel.param, self.scorer, batch, dE, dR, coef, cand_passes=passes, normalizer=normalizer,
                                             reg_out=self.reg_out, row_grads=self.sparse)
 
+    def _fill_row_buffers(self, batch: H.PrefixBatch):
+        """this batch's row buffers (the step's current ones from here on) with its occurrence ids written"""
+        rb = self._row_buffers(batch)
+        H.occurrence_ids(self.ent.param.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
+                         batch.po_rel, batch.sp_rel, out=(rb["idE"], rb["idR"]))
+        self._cur_rows = rb
+        return rb
+
+    def _issue(self, batch: H.PrefixBatch, normalizer, dE, dR):
+        """the step's call into dE / dR -> (loss, fast); fast: it went out from the step's persistent structs, which still hold
+        the batch and its masks (_regularise), and not through the engine's converting entry point"""
+        fast = isinstance(self.engine, H.HotPath) and self._plain(batch)
+        if fast:
+            return self._fast_forward_backward(batch, normalizer, dE, dR), True
+        self._set_dropout(batch)
+        how = dict(row_grads=True) if self._row_grads else dict(grads_zero=self._grads_zero)
+        if self.freeze is not None:
+            how["freeze"] = self.freeze
+        loss = self.engine.forward_backward(self.ent.param, self.rel.param, self.scorer, batch, dE, dR, loss=self.loss,
+                                            label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out, **how)
+        return loss, False
+
     def forward_backward(self, batch: H.PrefixBatch, normalizer=None):
         """trainer.py:206-234.  Returns the summed loss (device double[1], valid after stream sync)."""
-        if self.deterministic:                # (a method of its own: the default step is host-bound, its path stays as short as it was)
+        if self.deterministic:                # (a method of its own: the default step is host-bound, its path stays short)
             return self._deterministic_forward_backward(batch, normalizer)
-        ent, rel = self.ent, self.rel
         if self.sparse:
-            rb = self._cur_rows = self._row_buffers(batch)
-            H.occurrence_ids(ent.param.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
-                             batch.po_rel, batch.sp_rel, out=(rb["idE"], rb["idR"]))
+            rb = self._fill_row_buffers(batch)
             self._last_full = False
             if self.decay_window is not None:      # the rows this batch names take what they owe BEFORE the gather reads them
                 self._settle_hparams()
@@ -344,21 +363,12 @@ class FusedTrainStep:
                                           lr, wd, eps)
             dE, dR = rb["gE"], rb["gR"]
         else:
-            dE, dR = ent.grad, rel.grad
+            dE, dR = self.ent.grad, self.rel.grad
             if dE is not None and self._dE_stale and not (self._grads_zero and self._covers_all_rows(batch)):
                 dE.zero_()                # a sampled candidate list leaves rows untouched: they must read as zero
                 self._dE_stale = False
             self._last_full = self._covers_all_rows(batch)
-        fast = isinstance(self.engine, H.HotPath) and self._plain(batch)
-        if fast:
-            loss = self._fast_forward_backward(batch, normalizer, dE, dR)
-        else:
-            self._set_dropout(batch)
-            how = dict(row_grads=True) if self.sparse else dict(grads_zero=self._grads_zero)
-            if self.freeze is not None:
-                how["freeze"] = self.freeze
-            loss = self.engine.forward_backward(ent.param, rel.param, self.scorer, batch, dE, dR, loss=self.loss,
-                                                label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out, **how)
+        loss, fast = self._issue(batch, normalizer, dE, dR)
         if self.l2_reg > 0:
             self._regularise(batch, normalizer, fast, dE, dR)
         return loss
@@ -368,22 +378,14 @@ class FusedTrainStep:
         if batch.n_candidates + batch.B > H.ROWS_MAX_N:            # (before anything is launched or allocated)
             raise N.OkgeError(f"okge_rows_to_dense takes up to 2^20 occurrence rows per tensor: this batch has "
                               f"{batch.n_candidates} + {batch.B}; train it with deterministic=False")
-        rb = self._cur_rows = self._row_buffers(batch)
-        H.occurrence_ids(self.ent.param.device, batch.cand_ids, batch.cand_first, batch.n_candidates, batch.po_obj, batch.sp_subj,
-                         batch.po_rel, batch.sp_rel, out=(rb["idE"], rb["idR"]))
+        rb = self._fill_row_buffers(batch)
         # a store names -- and so overwrites -- every row of dE only when the candidate range is the whole table from row 0
         names_all = self._covers_all_rows(batch) and batch.cand_first == 0
         if self._dE_stale and not (self._grads_zero and names_all):
             self.ent.grad.zero_()         # rows this batch does not name must read as zero
             self._dE_stale = False
         self._last_full = names_all
-        if isinstance(self.engine, H.HotPath) and self._plain(batch):
-            loss = self._fast_forward_backward(batch, normalizer, rb["gE"], rb["gR"])
-        else:
-            self._set_dropout(batch)
-            loss = self.engine.forward_backward(self.ent.param, self.rel.param, self.scorer, batch, rb["gE"], rb["gR"], loss=self.loss,
-                                                label_smoothing=self.label_smoothing, normalizer=normalizer, loss_out=self.loss_out,
-                                                row_grads=True)
+        loss, _ = self._issue(batch, normalizer, rb["gE"], rb["gR"])
         # cleared tables (a fresh window): the named rows are stored; later micro-batches continue each row's chain
         self.engine.rows_to_dense([(t.grad, ids, g) for t, ids, g in self._occurrences(rb)], accumulate=not self._grads_zero)
         return loss

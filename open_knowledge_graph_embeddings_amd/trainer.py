@@ -17,10 +17,11 @@ import os
 
 from . import hotpath as H
 from .metrics import MetricResult
+from .model import LookupBaseRelationEmbedder
 from .virtual_tables import VirtualTables
 
 CALLER_THREAD_BACKWARD = os.environ.get("OKGE_BACKWARD_ON_CALLER_THREAD", "1") == "1"
-FAST_CALL = os.environ.get("OKGE_DROPIN_FAST", "1") == "1"      # persistent argument structs for the common training call
+FAST_CALL = os.environ.get("OKGE_DROPIN_FAST", "1") == "1"      # the lookup route refills persistent argument structs (off: a fresh set per call)
 
 
 class _FusedLossFn(torch.autograd.Function):
@@ -72,6 +73,21 @@ class _FusedLossHookFn(torch.autograd.Function):
 
 def _flat(t):
     return None if t is None else t.reshape(-1)
+
+
+def _check_sorted(pos_col):
+    """OKGE_VALIDATE: one host read"""
+    if pos_col.numel() > 1 and bool((pos_col[1:] < pos_col[:-1]).any()):
+        raise ValueError("coordinate labels must be sorted by column (the kernels partition them by candidate tile)")
+
+
+def _ids(dev, *tensors):
+    """the tensors (None stays None) as flat contiguous int32 tensors on dev -- themselves when their memory already is that (the
+    kernels read a pointer and a count): one pass, no new tensor object on the common call"""
+    for t in tensors:
+        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
+            return [H._i32(x, dev) for x in tensors]
+    return tensors
 
 
 class _VirtualTablesLossFn(torch.autograd.Function):
@@ -214,6 +230,36 @@ class AddLossModule(nn.Module):
             return None
         return "relations" if ge else "entities"
 
+    @staticmethod
+    def _candidates(m, use_batch_shared_entities, batch_shared_entities):
+        """-> (cand_ids or None, first_id, n): all entities [min_entities_size, entities_size) without batch_shared_entities and in
+        eval without batch sharing (trainer.py:77-78), else the shared id list -- which IS that range when it has its length and
+        batch sharing is off: arange(vocab)[offset:] (dataset.py:872)"""
+        n_ent, first = m.train_data.entities_size, m.train_data.min_entities_size
+        if batch_shared_entities is None or (not use_batch_shared_entities and not m.training):
+            return None, first, n_ent - first
+        n = batch_shared_entities.numel()
+        if n == n_ent - first and not use_batch_shared_entities:
+            return None, first, n
+        return batch_shared_entities, first, n
+
+    @staticmethod
+    def _wants_grad(m):
+        want_grad = torch.is_grad_enabled() and m.training
+        if want_grad and CALLER_THREAD_BACKWARD and torch.autograd.is_multithreading_enabled():
+            # The caller's `loss.backward()` (trainer.py:226) hands a CUDA graph to the autograd engine's device thread and waits
+            # for it: ~35 us of thread hand-off per step on a graph of ONE node whose backward only returns the gradients this
+            # forward already computed (0.199 -> 0.162 ms per drop-in step, S-FB).  Run it on the calling thread instead
+            # (thread-local autograd state; it stays set for this thread).  OKGE_BACKWARD_ON_CALLER_THREAD=0 leaves autograd alone.
+            torch.autograd.set_multithreading_enabled(False)
+        return want_grad
+
+    def _outputs(self, m, B, n, dev):
+        """the (B, n) block of predictions, rows padded to a multiple of four floats; None where training does without it"""
+        if self.training_outputs or not m.training:
+            return torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :n]
+        return None
+
     def forward(self, inputs, labels, use_batch_shared_entities, batch_shared_entities, epoch=-1,
                 input_style_triple_or_prefix="triple"):
         allowed = ["triple", "right_and_left_prefix"]
@@ -223,183 +269,117 @@ class AddLossModule(nn.Module):
             return None                                            # trainer.py:64 has no else branch
         kind = self._loss_kind()
         m = self.model
-        eng = m.engine()
         dev = m.entity_embedding.weight.device
         # (models that bring their own fused step -- autograd_step / loss_only: the token encoders, Tucker3 -- share one route)
         token_model = hasattr(m, "entity_token_ids") or getattr(m, "fused_step_model", False)
-        n_ent, first = m.train_data.entities_size, m.train_data.min_entities_size
+        if not token_model and not self._in_torch(m):
+            return self._lookup_result(m, dev, kind, inputs, labels, use_batch_shared_entities, batch_shared_entities, epoch)
         po, sp = inputs
-        if FAST_CALL and not token_model and m.training and torch.is_grad_enabled() and isinstance(labels, tuple) \
-                and not self._in_torch(m) and not H.VALIDATE:
-            fast = self._fast_training_call(m, eng, dev, po, sp, labels, use_batch_shared_entities, batch_shared_entities, kind, epoch)
-            if fast is not None:
-                return fast
         batch = H.PrefixBatch()
         if po is not None:
             batch.po_rel, batch.po_obj = _flat(po[0]), _flat(po[1])
         if sp is not None:
             batch.sp_subj, batch.sp_rel = _flat(sp[0]), _flat(sp[1])
-        # candidates: all entities in eval without batch sharing (trainer.py:77-78), else the shared id list
-        if batch_shared_entities is None or (not use_batch_shared_entities and not m.training):
-            batch.cand_first = first
-            batch.n_cand = n_ent - batch.cand_first
-        else:
-            ids = batch_shared_entities.reshape(-1)
-            if ids.numel() == n_ent - first and not use_batch_shared_entities:
-                batch.cand_first, batch.n_cand = first, int(ids.numel())      # arange(vocab)[offset:] (dataset.py:872)
-            else:
-                batch.cand_ids, batch.n_cand = ids, int(ids.numel())
+        batch.cand_ids, batch.cand_first, batch.n_cand = self._candidates(m, use_batch_shared_entities, batch_shared_entities)
+        batch.cand_ids = _flat(batch.cand_ids)
         if isinstance(labels, tuple):                               # (pos_row, pos_col) coordinates, sorted by column
+            if H.VALIDATE:
+                _check_sorted(labels[1])
             batch.pos_row, batch.pos_col = labels
-            if H.VALIDATE and batch.pos_col.numel() > 1 and bool((batch.pos_col[1:] < batch.pos_col[:-1]).any()):
-                raise ValueError("coordinate labels must be sorted by column (the kernels partition them by candidate tile)")
         else:                                                       # dense (B, N) {0,1} (dataset.py:885-932)
             batch.pos_row, batch.pos_col = H.positives_from_dense(labels.to(dev))
-        B, n = batch.B, batch.n_cand
-        want_grad = torch.is_grad_enabled() and m.training
-        if want_grad and CALLER_THREAD_BACKWARD and torch.autograd.is_multithreading_enabled():
-            # The caller's `loss.backward()` (trainer.py:226) hands a CUDA graph to the autograd engine's device thread and waits
-            # for it: ~35 us of thread hand-off per step on a graph of ONE node whose backward only returns the gradients this
-            # forward already computed (0.199 -> 0.162 ms per drop-in step, S-FB).  Run it on the calling thread instead
-            # (thread-local autograd state; it stays set for this thread).  OKGE_BACKWARD_ON_CALLER_THREAD=0 leaves autograd alone.
-            torch.autograd.set_multithreading_enabled(False)
-        all_outputs = None
-        if self.training_outputs or not m.training:
-            all_outputs = torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :n]
+        want_grad = self._wants_grad(m)
+        all_outputs = self._outputs(m, batch.B, batch.n_cand, dev)
         smoothing = self.bce_label_smoothing if kind == "bce" else 0.0
         if self.fused_variants and (not m.training or (want_grad and batch_shared_entities is not None)):
-            return self._fused_variant_result(m, batch, kind, smoothing, want_grad, all_outputs)
+            # (the hook's gradient is part of the gradients the step leaves; its value is the step's, model.py:447-453)
+            return self._own_step_result(m, batch, kind, smoothing, want_grad, all_outputs, None, step_hook=True)
         if self._in_torch(m):
             return self._variant_result(m, batch, kind, smoothing, want_grad, all_outputs, epoch,
                                         all_entities=not use_batch_shared_entities and not m.training,
                                         per_direction=batch_shared_entities is None)
-        # (read AFTER the variant dispatch: the variants fill the hook while they encode, trainer.py:97-98)
         hook_loss = m.after_batch_loss_hook(epoch) if hasattr(m, "after_batch_loss_hook") else None
-        if token_model:
-            return self._token_result(m, batch, kind, smoothing, want_grad, all_outputs, hook_loss)
+        return self._own_step_result(m, batch, kind, smoothing, want_grad, all_outputs, hook_loss)
+
+    def _lookup_result(self, m, dev, kind, inputs, labels, use_batch_shared_entities, batch_shared_entities, epoch):
+        """The plain lookup models: the call the reference Trainer makes thousands of times per epoch, and its loss-only form
+        (eval mode, no_grad, both tables frozen).  The inputs become flat int32 device tensors -- the Trainer's already are, and
+        are taken as they are -- and fill the four argument structs of a hotpath.PrefixCall, from which the step and, behind it
+        on the same structs, the l2_reg hook are issued.  FAST_CALL: the structs are the module's own (`_fd`), refilled in place
+        -- a fresh set per call is ~10 us of Python on a step whose kernels take 130 us (the path is host-bound, INTEGRATION.md
+        section 1); under OKGE_VALIDATE they are fresh, and the ids are range-checked on the host first."""
+        po, sp = inputs
+        po_rel, po_obj = (None, None) if po is None else po
+        sp_subj, sp_rel = (None, None) if sp is None else sp
+        if isinstance(labels, tuple):                               # (pos_row, pos_col) coordinates, sorted by column
+            if H.VALIDATE:
+                _check_sorted(labels[1])
+            pos_row, pos_col = labels
+        else:                                                       # dense (B, N) {0,1} (dataset.py:885-932)
+            pos_row, pos_col = H.positives_from_dense(labels.to(dev))
+        cand, first, n = self._candidates(m, use_batch_shared_entities, batch_shared_entities)
+        po_rel, po_obj, sp_subj, sp_rel, pos_row, pos_col, cand = _ids(dev, po_rel, po_obj, sp_subj, sp_rel, pos_row, pos_col, cand)
+        want_grad = self._wants_grad(m)
+        hook_loss = m.after_batch_loss_hook(epoch) if hasattr(m, "after_batch_loss_hook") else None
         if m.training:
             m.dropout_step += 1
-        batch.set_dropout([m.dropout_spec(stream, stream in (H.STREAM_PO_REL, H.STREAM_SP_REL)) for stream in H.STREAMS])
-        n3 = self._n3_term(m, batch.n_po, batch.n_sp, batch_shared_entities)
+        E, R, eng = m.E, m.R, m.engine()
+        if H.VALIDATE:
+            H.validate_ids(H.PrefixBatch(po_rel, po_obj, sp_subj, sp_rel, pos_row, pos_col, cand, first, n), E.shape[0], R.shape[0])
+            call = H.PrefixCall()
+        elif FAST_CALL:
+            call = getattr(self, "_fd", None)
+            if call is None:
+                call = self._fd = H.PrefixCall()
+        else:
+            call = H.PrefixCall()
+        call.fill_tables(E, R, m.scorer_name, eng.device)
+        call.fill_ids(po_rel, po_obj, sp_subj, sp_rel, cand, first, n, pos_row, pos_col)
+        if getattr(m.dropout_spec, "__func__", None) is LookupBaseRelationEmbedder.dropout_spec:
+            # (the five DropoutSpec objects m.dropout_spec would build, written in place: same numbers)
+            call.fill_dropout(m.keep_prob_dropout(m.input_dropout, m.dropout), m.keep_prob_dropout(m.relation_input_dropout, m.relation_dropout),
+                              m.dropout_seed, m.dropout_step)
+        else:                                                       # a model that answers dropout_spec itself (replayed `keep` masks)
+            call.fill_dropout_specs([m.dropout_spec(stream, stream in (H.STREAM_PO_REL, H.STREAM_SP_REL)) for stream in H.STREAMS])
+        B = call.B
+        all_outputs = self._outputs(m, B, n, dev)
+        smoothing = self.bce_label_smoothing if kind == "bce" else 0.0
+        n3 = self._n3_term(m, call.n_po, call.n_sp, batch_shared_entities)
         frozen = self._frozen_table(m, n3) if want_grad else None
-        if frozen == "both":
-            want_grad, frozen = False, None
-        if want_grad:
-            E, R = m.E, m.R
-            # a contiguous candidate range: the call stores the candidate rows and clears the rest itself (all of dR, the
-            # reserved rows in front of the candidates) inside its first launch -- fresh buffers, no fill launches.
-            # An id list: candidate rows accumulate, so the buffers start from zero.
-            clear = batch.cand_ids is None and not self.sparse_grads
-            row_ids = None
-            if self.sparse_grads:
-                g_e, g_r = E.new_empty((n + B, E.shape[1])), R.new_empty((B, R.shape[1]))
-                row_ids = H.occurrence_ids(dev, batch.cand_ids, batch.cand_first, n, batch.po_obj, batch.sp_subj, batch.po_rel, batch.sp_rel)
-            else:
-                g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
-            if frozen is not None:                                  # the frozen table gets no buffer at all
-                g_e, g_r = (None, g_r) if frozen == "entities" else (g_e, None)
-            # the factor the Trainer will apply (trainer.py:221: loss / normalizer_loss, normalizer_loss = B x N,
-            # dataset.py:935) goes into the fused step; _FusedLossFn.backward checks it against what autograd delivers
-            # (torch divides a fp32 tensor by a Python number as a multiplication by fp32(1) / fp32(number), forward and
-            #  backward: `applied` is built the same way, and the normalizer handed to the library is the one whose fp32
-            #  reciprocal is exactly that)
-            applied = np.float32(1.0) / np.float32(float(B) * float(n))
-            loss = eng.forward_backward(E, R, m.scorer_name, batch, g_e, g_r, loss=kind, label_smoothing=smoothing,
-                                        normalizer=1.0 / float(applied), scores=all_outputs, grads_zero=True, clear_grads=clear,
-                                        row_grads=self.sparse_grads, freeze=frozen)
+        # (fresh per call: autograd holds on to them)
+        loss_out = torch.empty(1, dtype=torch.float64, device=dev)
+        reg_out = torch.empty(1, dtype=torch.float64, device=dev) if n3 is not None else None
+        if not want_grad or frozen == "both":                       # nothing to train: the loss, and the hook's value
+            flags = H.train_flags(loss_only=True)
+            result = call.train(eng, kind, smoothing, 1.0, flags, loss_out, None, None, all_outputs).to(torch.float32).reshape(())
             if n3 is not None:
-                reg = eng.n3_forward_backward(E, R, m.scorer_name, batch, g_e, g_r, n3[0], cand_passes=n3[1],
-                                              normalizer=1.0 / float(applied), row_grads=self.sparse_grads)
-                result, hook_loss = _FusedLossHookFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, reg, g_e,
-                                                           g_r, eng, float(applied), row_ids)
-            else:
-                result = _FusedLossFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, g_e, g_r, eng,
-                                            float(applied), row_ids)
-        else:
-            loss = eng.forward_backward(m.E, m.R, m.scorer_name, batch, None, None, loss=kind, label_smoothing=smoothing,
-                                        normalizer=1.0, scores=all_outputs, loss_only=True)
-            result = loss.to(torch.float32).reshape(())
-            if n3 is not None:
-                hook_loss = eng.n3_forward_backward(m.E, m.R, m.scorer_name, batch, None, None, n3[0], cand_passes=n3[1],
-                                                    normalizer=1.0, loss_only=True).to(torch.float32).reshape(())
-        return result, hook_loss, all_outputs
-
-    def _fast_training_call(self, m, eng, dev, po, sp, labels, use_batch_shared_entities, batch_shared_entities, kind, epoch):
-        """The call the reference Trainer makes thousands of times per epoch -- lookup model in training mode, coordinate labels,
-        int32 id tensors on the device -- with PERSISTENT argument structs (`_fd`, a hotpath.PrefixCall refilled in place): the
-        general path builds a PrefixBatch, ten DropoutSpec objects and four ctypes structs per call, ~35 us of Python on a step
-        whose kernels take 130 us (the path is host-bound).  Same library call, same flags, same
-        buffers: test_dropin_path.py compares the two bit for bit.  Returns None when an input is not in that form (the general
-        path then converts it)."""
-        prow, pcol = labels
-        ids = []
-        for pair in (po, sp):
-            if pair is not None:
-                ids += [pair[0], pair[1]]
-        for x in (prow, pcol, *ids):
-            if x.dtype != torch.int32 or not x.is_contiguous() or x.device != dev:
-                return None
-        n_ent, first = m.train_data.entities_size, m.train_data.min_entities_size
-        cand = None
-        if batch_shared_entities is None:
-            n = n_ent - first
-        else:
-            cand = batch_shared_entities
-            if cand.dtype != torch.int32 or not cand.is_contiguous() or cand.device != dev:
-                return None
-            n = cand.numel()
-            if n == n_ent - first and not use_batch_shared_entities:
-                cand = None                                         # arange(vocab)[offset:] (dataset.py:872)
-        E, R = m.E, m.R
-        if E.dtype != torch.float32 or not E.is_contiguous() or not R.is_contiguous() or R.dtype != torch.float32:
-            return None
-        frozen = None
-        if not (m.entity_embedding.weight.requires_grad and m.relation_embedding.weight.requires_grad):
-            frozen = self._frozen_table(m, self._n3_term(m, 1, 1, batch_shared_entities))
-            if frozen == "both":
-                return None                                         # (nothing to train: the general path's loss-only route)
-        if getattr(self, "_fd", None) is None:
-            self._fd = H.PrefixCall()
-        fd = self._fd
-        fd.fill_tables(E, R, m.scorer_name, eng.device)
-        hook_loss = m.after_batch_loss_hook(epoch) if hasattr(m, "after_batch_loss_hook") else None
-        m.dropout_step += 1
-        fd.fill_dropout(m.keep_prob_dropout(m.input_dropout, m.dropout), m.keep_prob_dropout(m.relation_input_dropout, m.relation_dropout),
-                        m.dropout_seed, m.dropout_step)
-        po_rel, po_obj = po if po is not None else (None, None)
-        sp_subj, sp_rel = sp if sp is not None else (None, None)
-        fd.fill_ids(po_rel, po_obj, sp_subj, sp_rel, cand, first, n, prow, pcol)
-        n_po, n_sp, B = fd.n_po, fd.n_sp, fd.B
-        all_outputs = None
-        if self.training_outputs:
-            all_outputs = torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :n]
+                hook_loss = call.n3(eng, n3[0], n3[1], 1.0, flags, reg_out, None, None).to(torch.float32).reshape(())
+            return result, hook_loss, all_outputs
+        # a contiguous candidate range: the call stores the candidate rows and clears the rest itself (all of dR, the
+        # reserved rows in front of the candidates) inside its first launch -- fresh buffers, no fill launches.
+        # An id list: candidate rows accumulate, so the buffers start from zero.
         clear = cand is None and not self.sparse_grads
         row_ids = None
-        if self.sparse_grads:
+        if self.sparse_grads:                                       # occurrence rows, every one stored by the call
             g_e, g_r = E.new_empty((n + B, E.shape[1])), R.new_empty((B, R.shape[1]))
-            row_ids = H.occurrence_ids(dev, cand, first, n, po[1] if n_po else None, sp[0] if n_sp else None,
-                                      po[0] if n_po else None, sp[1] if n_sp else None)
+            row_ids = H.occurrence_ids(dev, cand, first, n, po_obj, sp_subj, po_rel, sp_rel)
         else:
             g_e, g_r = (torch.empty_like(E), torch.empty_like(R)) if clear else (torch.zeros_like(E), torch.zeros_like(R))
-        if frozen is not None:                                                # the frozen table gets no buffer at all
+        if frozen is not None:                                      # the frozen table gets no buffer at all
             g_e, g_r = (None, g_r) if frozen == "entities" else (g_e, None)
         flags = H.train_flags(grads_zero=not self.sparse_grads, clear_grads=clear, row_grads=self.sparse_grads, freeze=frozen)
-        applied = np.float32(1.0) / np.float32(float(B) * float(n))           # (see forward below)
-        smoothing = self.bce_label_smoothing if kind == "bce" else 0.0
-        loss = fd.train(eng, kind, smoothing, 1.0 / float(applied), flags, torch.empty(1, dtype=torch.float64, device=dev), g_e, g_r,
-                        all_outputs)
-        n3 = self._n3_term(m, n_po, n_sp, batch_shared_entities)
-        if n3 is not None:                                                     # the l2_reg hook, behind the step on the same structs
-            reg = fd.n3(eng, n3[0], n3[1], 1.0 / float(applied), H.train_flags(row_grads=self.sparse_grads),
-                        torch.empty(1, dtype=torch.float64, device=dev), g_e, g_r)
-        if CALLER_THREAD_BACKWARD and torch.autograd.is_multithreading_enabled():
-            torch.autograd.set_multithreading_enabled(False)                   # (see forward below)
-        if n3 is not None:
-            result, hook_loss = _FusedLossHookFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, reg, g_e, g_r,
-                                                       eng, float(applied), row_ids)
-            return result, hook_loss, all_outputs
-        result = _FusedLossFn.apply(m.entity_embedding.weight, m.relation_embedding.weight, loss, g_e, g_r, eng, float(applied),
-                                    row_ids)
+        # the factor the Trainer will apply (trainer.py:221: loss / normalizer_loss, normalizer_loss = B x N,
+        # dataset.py:935) goes into the fused step; _FusedLossFn.backward checks it against what autograd delivers
+        # (torch divides a fp32 tensor by a Python number as a multiplication by fp32(1) / fp32(number), forward and
+        #  backward: `applied` is built the same way, and the normalizer handed to the library is the one whose fp32
+        #  reciprocal is exactly that)
+        applied = np.float32(1.0) / np.float32(float(B) * float(n))
+        loss = call.train(eng, kind, smoothing, 1.0 / float(applied), flags, loss_out, g_e, g_r, all_outputs)
+        weights = m.entity_embedding.weight, m.relation_embedding.weight
+        if n3 is None:
+            return _FusedLossFn.apply(*weights, loss, g_e, g_r, eng, float(applied), row_ids), hook_loss, all_outputs
+        reg = call.n3(eng, n3[0], n3[1], 1.0 / float(applied), H.train_flags(row_grads=self.sparse_grads), reg_out, g_e, g_r)
+        result, hook_loss = _FusedLossHookFn.apply(*weights, loss, reg, g_e, g_r, eng, float(applied), row_ids)
         return result, hook_loss, all_outputs
 
     def _variant_result(self, m, batch, kind, smoothing, want_grad, all_outputs, epoch, all_entities, per_direction):
@@ -473,31 +453,21 @@ class AddLossModule(nn.Module):
             result = part if result is None else result + part
         return result, hook_loss, all_outputs
 
-    def _fused_variant_result(self, m, batch, kind, smoothing, want_grad, all_outputs):
-        """AddLossModule(fused_variants=True): the lookup embedder's variants on the HIP encode, through the protocol of the token
-        models (autograd_step / autograd_params_and_grads / loss_only).  The step's normalizer is 1 and the hook's gradient is
+    def _own_step_result(self, m, batch, kind, smoothing, want_grad, all_outputs, hook_loss, step_hook=False):
+        """Models that bring their own step (autograd_step / autograd_params_and_grads / loss_only).  The UnigramPooling* models
+        (model.py:716-796) and Tucker3: the encoded rows of the batch form two small virtual tables, the fused step runs on them,
+        and the encoder's backward deposits dense parameter gradients.  AddLossModule(fused_variants=True), step_hook: the lookup
+        embedder's variants on the HIP encode through the same protocol; the step's normalizer is 1 and the hook's gradient is
         part of the gradients it leaves, so `(loss.sum() + hook) / normalizer` (trainer.py:217-221) scales both by the upstream
-        scalar of the loss; the hook's value is returned beside it (model.py:447-453: training mode, l2_reg > 0)."""
+        scalar of the loss, and the hook's value is the step's (model.py:447-453: training mode, l2_reg > 0)."""
         if not want_grad:
-            return m.loss_only(batch, kind, smoothing, all_outputs).to(torch.float32).reshape(()), None, all_outputs
+            return m.loss_only(batch, kind, smoothing, all_outputs).to(torch.float32).reshape(()), hook_loss, all_outputs
         st = m.autograd_step(kind, smoothing)
         loss = st.forward_backward(batch, normalizer=1.0, scores=all_outputs)
         params, grads = m.autograd_params_and_grads(st)
         result = _TokenPooledLossFn.apply(loss, m.engine(), grads, *params)
-        hook_loss = st.reg_out.to(torch.float32).reshape(()) if m.l2_reg > 0 else None
-        return result, hook_loss, all_outputs
-
-    def _token_result(self, m, batch, kind, smoothing, want_grad, all_outputs, hook_loss):
-        """UnigramPooling* models (model.py:716-796): the pooled rows of the batch form two small virtual tables, the
-        fused step runs on them, and the pooling / batch-norm backward deposits dense token-table gradients."""
-        if want_grad:
-            st = m.autograd_step(kind, smoothing)
-            loss = st.forward_backward(batch, normalizer=1.0, scores=all_outputs)
-            params, grads = m.autograd_params_and_grads(st)
-            result = _TokenPooledLossFn.apply(loss, m.engine(), grads, *params)
-        else:
-            loss = m.loss_only(batch, kind, smoothing, all_outputs)
-            result = loss.to(torch.float32).reshape(())
+        if step_hook and m.l2_reg > 0:
+            hook_loss = st.reg_out.to(torch.float32).reshape(())
         return result, hook_loss, all_outputs
 
 

@@ -366,7 +366,53 @@ _STEP_SHAPES = [
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["dense_adagrad", "sparse_l2_reg", "adam_l2_reg"])
+def test_persistent_structs_serve_training_and_eval_calls_alike(okge_lib, monkeypatch):
+    """One AddLossModule, FAST_CALL on: training calls and loss-only calls refill ONE set of argument structs.  Train, eval +
+    no_grad over all entities, train on an id list with an empty direction, eval, train -- against the same sequence on fresh
+    structs per call (FAST_CALL off): loss, all_outputs and both gradients are bit-equal at every step (the batches are order-free),
+    so nothing of a training call survives into an eval call or back (a gradient pointer, the masks, a candidate id list)."""
+    from open_knowledge_graph_embeddings_amd import trainer as T
+    n_ent, n_rel, d = 50, 12, 16
+    g = torch.Generator().manual_seed(5)
+    z = dict(E=(torch.randn((n_ent, d), generator=g) * 0.3).numpy(), R=(torch.randn((n_rel, d), generator=g) * 0.3).numpy())
+    ids = lambda x: torch.tensor(x, dtype=torch.int32, device="cuda")      # noqa: E731
+    sequence = [(0, True), (2, False), (1, True), (3, False), (3, True)]    # (batch of _STEP_SHAPES, training mode)
+
+    def run(fast):
+        monkeypatch.setattr(T, "FAST_CALL", fast)
+        m = _lookup_model(z, dropout=0.3)
+        mod = T.AddLossModule(m, torch.nn.BCEWithLogitsLoss(reduction="sum"), 0.1)
+        seen = []
+        for shape, training in sequence:
+            po, sp, cand, pos = _STEP_SHAPES[shape]
+            inputs = [po and (ids(po[0]), ids(po[1])), sp and (ids(sp[0]), ids(sp[1]))]
+            cand = None if cand is None else ids(cand).reshape(-1, 1)
+            n = n_ent - 2 if cand is None else cand.numel()
+            m.train(training)
+            m.zero_grad(set_to_none=True)
+            with torch.set_grad_enabled(training):
+                loss, hook, outs = mod(inputs=inputs, labels=(ids(pos[0]), ids(pos[1])), use_batch_shared_entities=cand is not None,
+                                       batch_shared_entities=cand, epoch=1, input_style_triple_or_prefix="right_and_left_prefix")
+            assert hook is None and outs.shape == (len(po[0] if po else ()) + len(sp[0] if sp else ()), n)
+            if training:
+                (loss.sum() / float(outs.numel())).backward()
+            assert (m.entity_embedding.weight.grad is not None) == training
+            seen.append([loss.detach().clone(), outs.clone()] +
+                        ([m.entity_embedding.weight.grad.clone(), m.relation_embedding.weight.grad.clone()] if training else []))
+        assert (getattr(mod, "_fd", None) is not None) == fast
+        torch.cuda.synchronize()
+        return seen
+
+    persistent, fresh = run(True), run(False)
+    for i, (a, b) in enumerate(zip(persistent, fresh)):
+        assert len(a) == len(b)
+        for k, (x, y) in enumerate(zip(a, b)):
+            assert torch.isfinite(x).all() and torch.equal(x, y), f"step {i}, tensor {k}: persistent and fresh structs differ"
+    assert not torch.equal(persistent[3][0], persistent[4][0])               # (eval and training of one batch: the masks differ)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["dense_adagrad", "sparse_l2_reg", "adam_l2_reg", "deterministic"])
 def test_fused_step_fast_route_is_the_general_route_over_changing_batches(okge_lib, variant):
     """FusedTrainStep's persistent argument structs over four batch shapes in a row (no GraphedTrainStep): int32 device ids take
     the fast route, the same ids as int64 the general one.  After every step loss, l2_reg term, tables and optimizer state are
@@ -378,7 +424,7 @@ def test_fused_step_fast_route_is_the_general_route_over_changing_batches(okge_l
     g = torch.Generator().manual_seed(5)
     E0, R0 = (torch.randn((n_ent, d), generator=g) * 0.3).cuda(), (torch.randn((n_rel, d), generator=g) * 0.3).cuda()
     kw = dict(dense_adagrad={}, sparse_l2_reg=dict(sparse=True, weight_decay=0.0, l2_reg=0.05),
-              adam_l2_reg=dict(optimizer="adam", l2_reg=0.05))[variant]
+              adam_l2_reg=dict(optimizer="adam", l2_reg=0.05), deterministic=dict(deterministic=True))[variant]
 
     def run(fast):
         dt = torch.int32 if fast else torch.int64
